@@ -19,8 +19,12 @@ Every rank runs the same per-GPU batch on its own tuples (weak scaling, no data-
 collective is the final all-gather of per-pair pose errors for the AUC (RCCL over xGMI), the counterpart of the
 reference's one-element all_reduce (train.py:102-106).
 
-Prints ONE JSON line on rank 0 with `roofline` for the dominant kernel family (HIP events on the launch stream
-inside the timed region) and `cpu_baseline` (the torch-CPU oracle on a bounded sample, rank 0, N=1 only).
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) sets up, warms up, times the K steps, writes the last step's outputs
+(--dump-outputs DIR), runs the untimed AUC leg and prints ONE JSON line on rank 0: `value` (pairs/s), `ms_per_step`, the AUC.
+`--full` adds everything else the line used to carry, each measured in runs of its own after the timed steps: the timed steps
+bracketed by HIP events (`roofline` of the dominant kernel family, `families`, `sinkhorn_bound`) and once more without them,
+the other arithmetic modes, two streams, the batch-1 latency and `cpu_baseline` (the torch-CPU oracle on a bounded sample,
+rank 0, N=1 only) with its AUC parity sample.
 """
 import argparse
 import json
@@ -29,6 +33,7 @@ import socket
 import subprocess
 import sys
 import time
+import zlib
 
 import numpy as np
 
@@ -46,6 +51,7 @@ CONFIGS = {
     "c5": dict(tuple_size=5, kpts=2048, batch=8, sinkhorn_iters=100, desc="f16"),
 }
 CONFIG_LABEL = {"c1": "configs[0]", "c2": "configs[1]", "c4": "configs[3]", "c5": "configs[4] (per-GPU share)"}
+DUMP_BUDGET_BYTES = 60 << 20  # --dump-outputs: the arrays of one step, .npy headers aside (64 MB in all at most)
 
 
 def parse_args(argv=None):
@@ -63,20 +69,27 @@ def parse_args(argv=None):
                     "9x1 two-view / MegaDepth, 7x3 multi-view ScanNet")
     ap.add_argument("--precision", choices=["default", "f32", "bf16x3", "f16x2"], default="default",
                     help="arithmetic of the dense contractions for the timed region (default = the library default)")
-    ap.add_argument("--cpu-pairs", type=int, default=4, help="pairs of the workload timed on the CPU oracle (0 = skip)")
-    ap.add_argument("--no-profile", action="store_true", help="do not bracket kernel families with HIP events")
+    ap.add_argument("--full", action="store_true", help="after the headline, every further measurement: HIP-event roofline, the "
+                    "other arithmetic modes, two streams, batch-1 latency, CPU baseline + AUC parity sample (off: the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the outputs of the last timed step as DIR/<name>.npy "
+                    "(float32, or float64 for integer and fp64 outputs; rank 0)")
+    ap.add_argument("--cpu-pairs", type=int, default=4, help="--full: pairs of the workload timed on the CPU oracle (0 = skip)")
+    ap.add_argument("--no-profile", action="store_true", help="--full: do not bracket kernel families with HIP events")
     ap.add_argument("--ba", action="store_true", help="also run the two-view bundle adjustment (10 LM iterations) per pair "
                     "inside the step (the reference's default eval mode w8pt_ba); off by default: SURVEY 8(d) defines the "
                     "metric on matcher -> w8pt -> pose errors")
     ap.add_argument("--front-end", action="store_true", help="extra (reported separately, never part of `value`): image-in "
                     "pipeline = SuperPoint on tuple_size*batch 480x640 images -> matcher -> w8pt per step")
-    ap.add_argument("--no-alt", action="store_true", help="skip the extra measurement in the other arithmetic mode")
-    ap.add_argument("--no-latency", action="store_true", help="skip the batch-1 latency measurement (eval_pairs.py's loop shape)")
+    ap.add_argument("--no-alt", action="store_true", help="--full: skip the extra measurements in the other arithmetic modes and "
+                    "on two streams")
+    ap.add_argument("--no-latency", action="store_true", help="--full: skip the batch-1 latency measurement (eval_pairs.py's loop shape)")
     ap.add_argument("--baseline-1gpu", type=float, default=None, help="the `value` of the --gpus 1 run of the same config on "
                     "this node: rank 0 then adds scaling_check = {efficiency = value / (n_gpus x it)} to its line (the driver "
                     "computes its own from the per-N lines; this is for a manual 1/2/4/8 sweep)")
     ap.add_argument("--backend", default=None, help="process-group backend (default nccl = RCCL; the CPU test uses gloo)")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     preset = CONFIGS[args.config]
     for key, attr in (("tuple_size", "tuple_size"), ("kpts", "kpts"), ("batch", "batch"), ("sinkhorn_iters", "sinkhorn_iters"),
                       ("desc", "desc")):
@@ -228,7 +241,22 @@ class HipWorkload:
                     Tp[vb] = Tr
                 errs.append(E.pose_errors(Tp, d[f"T_{i}to{j}"]))
         self.last_poses = poses
+        self.last_outputs = (res, poses, errs)
         return res, errs
+
+    def step_outputs(self):
+        """The arrays a caller of the timed path receives from the last step: the matcher's outputs, then per pair the
+        weighted 8-point pose with its by-products and the pose errors."""
+        res, poses, errs = self.last_outputs
+        arrays = {"matcher_" + k: v for k, v in res.items() if self.torch.is_tensor(v)}
+        for q, (i, j) in enumerate(self.pairs):
+            Tp, info = poses[(i, j)]
+            if Tp is not None:
+                arrays[f"w8pt_T_{i}_{j}"] = Tp
+                arrays.update({f"w8pt_{k}_{i}_{j}": v for k, v in info.items() if self.torch.is_tensor(v)})
+            rot, tr = errs[q]
+            arrays[f"pose_err_rot_{i}_{j}"], arrays[f"pose_err_transl_{i}_{j}"] = rot, tr
+        return arrays
 
     def sync(self):
         self.torch.cuda.synchronize()
@@ -275,6 +303,9 @@ class StubWorkload:
     def step(self, model=None, data=None):
         time.sleep(0.002 * (1 + self.rank))
         return None, None
+
+    def step_outputs(self):
+        return {}
 
     def sync(self):
         pass
@@ -387,6 +418,32 @@ def cpu_baseline(args, wl):
     return out, small, nb, best
 
 
+# ----------------------------------------------------------------------------------------- output dump
+def dump_outputs(path, arrays, budget=DUMP_BUDGET_BYTES):
+    """Each array as <path>/<name>.npy: floating-point and boolean outputs as float32 (fp64 stays fp64), integer outputs as
+    float64 (exact).  The budget is shared out smallest array first: an array that fits its share is written whole in its own
+    shape, a larger one as a fixed sample of its share - the flattened elements at sorted indices drawn without replacement from
+    a generator seeded with the crc32 of the name, the same elements in every run of the same arguments."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    items = []
+    for name, t in arrays.items():
+        dt = torch.float64 if (t.dtype == torch.float64 or not (t.is_floating_point() or t.dtype == torch.bool)) else torch.float32
+        items.append((t.numel() * (8 if dt == torch.float64 else 4), name, t.detach(), dt))
+    items.sort(key=lambda e: (e[0], e[1]))
+    left = budget
+    for n, (nbytes, name, t, dt) in enumerate(items):
+        share = left // (len(items) - n)
+        flat = t.reshape(-1)
+        if nbytes > share:
+            k = share // (8 if dt == torch.float64 else 4)
+            idx = np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(flat.numel(), size=k, replace=False))
+            t = flat[torch.from_numpy(idx).to(flat.device)]
+            nbytes = k * (8 if dt == torch.float64 else 4)
+        np.save(os.path.join(path, name + ".npy"), t.to(dt).cpu().numpy())
+        left -= nbytes
+
+
 # ----------------------------------------------------------------------------------------- main
 def run(args):
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -431,26 +488,30 @@ def run(args):
         barrier()
         return reduce_max_seconds(time.perf_counter() - t0, device=wl.coll_dev)  # MAX over ranks
 
+    full = args.full
     for _ in range(args.warmup):
         wl.step()
     wl.sync()
-    if not args.no_profile:
+    profiled = full and not args.no_profile  # (a plain run times the steps without the HIP-event brackets)
+    if profiled:
         wl.profile(True)
     elapsed = timed_steps(args.steps)
     prof = None
-    if not args.no_profile:
+    if profiled:
         prof = wl.profile(False)
     mode = wl.precision()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, wl.step_outputs())
 
     # the same K steps once more without the HIP-event brackets (what the instrumentation costs)
     bare = None
-    if not args.no_profile and not stub:
+    if profiled and not stub:
         bare = timed_steps(args.steps)
 
     # ---- further measurements: the same workload in the other arithmetic modes (reported separately, each with its own
     # kernel family times and roofline)
     alts = []
-    if not args.no_alt and not stub:
+    if full and not args.no_alt and not stub:
         for other in ("f32", "bf16x3", "f16x2"):
             if other == mode:
                 continue
@@ -470,7 +531,7 @@ def run(args):
     # one half's launch boundaries filled by the other half's kernels).  Reported beside the headline, never as it: the
     # per-kernel durations of concurrently running launches are not comparable with the single-stream kernel trace.
     two_streams = None
-    if not args.no_alt and not stub and world == 1 and B >= 2:
+    if full and not args.no_alt and not stub and world == 1 and B >= 2:
         wl.model.config["streams"] = 2
         try:
             for _ in range(3):
@@ -517,7 +578,7 @@ def run(args):
 
     # ---- batch-1 latency: the reference's eval_pairs.py loop is one pair at a time (eval_pairs.py:207-256)
     latency = None
-    if not args.no_latency and not stub and world == 1:
+    if full and not args.no_latency and not stub and world == 1:
         torch = wl.torch
         one = {k: (v[:1].contiguous() if torch.is_tensor(v) else v) for k, v in wl.data.items()}
         for _ in range(3):
@@ -774,7 +835,7 @@ def run(args):
         out["value_f32"], out["ms_per_step_f32"] = out["value"], out["ms_per_step"]
 
     # ---- CPU baseline: the oracle (torch CPU, same unfused op sequence as the reference) on a bounded sample
-    if world == 1 and args.cpu_pairs > 0 and not stub:
+    if full and world == 1 and args.cpu_pairs > 0 and not stub:
         import torch
         from e2e_multi_view_matching_amd.metrics import pair_errors_deg
         from oracle import w8pt as OW

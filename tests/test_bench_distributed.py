@@ -8,6 +8,7 @@ import subprocess
 import sys
 
 import numpy as np
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BENCH = os.path.join(ROOT, "bench.py")
@@ -120,3 +121,29 @@ def test_rank_cpu_slices_partition_the_host_cores():
     assert all(s for s in sl)
     assert len({c for s in sl for c in s}) == sum(len(s) for s in sl)            # disjoint
     assert all(s == d["base"][i * len(s):(i + 1) * len(s)] for i, s in enumerate(sl))  # contiguous, in rank order
+
+
+def test_dump_outputs_is_seeded_and_within_its_budget(tmp_path):
+    """bench.dump_outputs (--dump-outputs): small arrays whole and exact in their own shape, an array above its share of the
+    budget as a sample of the same elements in every run, the files within the budget."""
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    g = torch.Generator().manual_seed(0)
+    arrays = {"scores": torch.randn(4, 257, 257, generator=g), "matches": torch.randint(-1, 256, (4, 256), generator=g),
+              "mask": torch.rand(4, 256, generator=g) > 0.5, "T": torch.randn(4, 4, 4, dtype=torch.float64, generator=g)}
+    budget = 64 << 10
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), arrays, budget=budget)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["T.npy", "mask.npy", "matches.npy", "scores.npy"] and names == sorted(os.listdir(tmp_path / "b"))
+    assert sum(os.path.getsize(tmp_path / "a" / n) for n in names) <= budget + 128 * len(names)  # (+ the .npy headers)
+    for n in names:
+        assert np.array_equal(np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n))
+    m, k, t = (np.load(tmp_path / "a" / n) for n in ("matches.npy", "mask.npy", "T.npy"))
+    assert m.dtype == np.float64 and np.array_equal(m, arrays["matches"].numpy())
+    assert k.dtype == np.float32 and np.array_equal(k, arrays["mask"].numpy().astype(np.float32))
+    assert t.dtype == np.float64 and np.array_equal(t, arrays["T"].numpy())
+    s = np.load(tmp_path / "a" / "scores.npy")
+    assert s.dtype == np.float32 and s.ndim == 1 and 0 < s.size < arrays["scores"].numel()
+    assert np.isin(s, arrays["scores"].numpy().ravel()).all()

@@ -1,13 +1,11 @@
 """The no-edit drop-in (dropin/): with `dropin/` anywhere on sys.path the reference's import statements resolve to the
 MI355X package, while reference modules that are NOT replaced stay importable.  Runs in subprocesses (clean sys.modules)
-against a synthetic checkout with the reference's layout (namespace packages, no __init__.py) and, when it is present in
-this container, against /root/reference itself."""
+against synthetic checkouts with the reference's layout (namespace packages, no __init__.py): a minimal one, and one with
+every Python module and directory the reference checkout has."""
 import os
 import subprocess
 import sys
 import textwrap
-
-import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DROPIN = os.path.join(ROOT, "dropin")
@@ -71,9 +69,34 @@ def test_dropin_shadows_a_checkout_with_the_reference_layout(tmp_path):
     _run(str(ref), extra)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/pose_optimization"), reason="reference checkout not in this container")
-def test_dropin_shadows_the_real_reference_tree():
-    _run("/root/reference")
+# The reference checkout's Python modules (no __init__.py anywhere) and its directories without Python files; the git submodule
+# `models/` is not initialised.  Every module the drop-in replaces raises on import.
+REFERENCE_MODULES = ["convert_megadepth_to_scannet_format.py", "eval_multi_view.py", "eval_pairs.py", "helpers.py", "train.py",
+                     "datasets/matching_dataset.py", "datasets/sampling.py", "datasets/scannet.py",
+                     "pose_optimization/multi_view/bundle_adjust_io.py", "pose_optimization/two_view/bundle_adjust_gauss_newton_2_view.py",
+                     "pose_optimization/two_view/compute_pose_error.py", "pose_optimization/two_view/estimate_relative_pose.py"]
+REFERENCE_DIRS = ["assets", "docs", "models", "pose_optimization/multi_view/bundle_adjustment/ba_init/src",
+                  "pose_optimization/multi_view/bundle_adjustment/io/src", "pose_optimization/multi_view/bundle_adjustment/problem/src"]
+REPLACED = {"pose_optimization/multi_view/bundle_adjust_io.py", "pose_optimization/two_view/compute_pose_error.py",
+            "pose_optimization/two_view/estimate_relative_pose.py"}
+
+
+def test_dropin_shadows_the_real_reference_tree(tmp_path):
+    """The full layout of the reference checkout: the scripts sit beside the packages, `datasets/` is a namespace package of
+    the checkout, the C++ bundle adjuster is a directory tree without Python files."""
+    ref = tmp_path / "reference"
+    for d in REFERENCE_DIRS:
+        (ref / d).mkdir(parents=True)
+    for m in REFERENCE_MODULES:
+        (ref / m).parent.mkdir(parents=True, exist_ok=True)
+        body = "raise ImportError('the reference module was imported instead of the drop-in')\n" if m in REPLACED else \
+            "MARKER = %r\n" % m
+        (ref / m).write_text(body)
+    extra = textwrap.dedent("""
+        from pose_optimization.two_view.bundle_adjust_gauss_newton_2_view import MARKER   # not replaced: the checkout's own
+        assert MARKER == 'pose_optimization/two_view/bundle_adjust_gauss_newton_2_view.py'
+    """)
+    _run(str(ref), extra)
 
 
 def test_executable_launchers_have_the_reference_command_line():

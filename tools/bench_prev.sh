@@ -3,8 +3,8 @@
 cd "$GRAFT_REPO_ROOT" || exit 1
 OUT=$GRAFT_REPO_ROOT/gpurun_out/r6; mkdir -p $OUT; tag=${1:-prev}
 for rep in 1 2; do
-timeout 300 python bench.py --steps 10 --warmup 3 --cpu-pairs 0 --no-alt --no-latency > $OUT/bench_${tag}_new$rep.json 2> $OUT/bench_${tag}_new$rep.err
-E2EMV_LIBRARY=$GRAFT_REPO_ROOT/tools/libe2emv_prev.bin timeout 300 python bench.py --steps 10 --warmup 3 --cpu-pairs 0 --no-alt --no-latency > $OUT/bench_${tag}_old$rep.json 2> $OUT/bench_${tag}_old$rep.err
+timeout 300 python bench.py --full --steps 10 --warmup 3 --cpu-pairs 0 --no-alt --no-latency > $OUT/bench_${tag}_new$rep.json 2> $OUT/bench_${tag}_new$rep.err
+E2EMV_LIBRARY=$PWD/tools/libe2emv_prev.bin timeout 300 python bench.py --full --steps 10 --warmup 3 --cpu-pairs 0 --no-alt --no-latency > $OUT/bench_${tag}_old$rep.json 2> $OUT/bench_${tag}_old$rep.err
 done
 python - $OUT/bench_${tag}_new1.json $OUT/bench_${tag}_old1.json $OUT/bench_${tag}_new2.json $OUT/bench_${tag}_old2.json <<'PY'
 import json, sys

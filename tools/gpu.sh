@@ -2,7 +2,7 @@
 # One parameterised GPU-box script (run through gpurun): tools/gpu.sh <stage> [...]; output under gpurun_out/r6/.
 #   planes   per-kernel parity of the plane kernels + matcher parity + micro-benchmarks + bench A/B (plane vs round-2 kernels)
 #   tests    the whole -m gpu suite
-#   bench    bench.py lines (c2 default, c4, c5)
+#   bench    bench.py --full lines (c2 default, c4, c5)
 #   one      one short bench line with its roofline / sinkhorn_bound objects printed
 #   kt       rocprofv3 kernel trace of one config / mode
 #   prof     rocprofv3 kernel trace + the three PMC passes of config c2
@@ -24,7 +24,7 @@ for f in sys.argv[1:]:
         except Exception: pass
 PY
 }
-B="--steps 10 --warmup 3 --cpu-pairs 0 --no-alt --no-latency"
+B="--full --steps 10 --warmup 3 --cpu-pairs 0 --no-alt --no-latency"
 case $stage in
 chain)
   # round 5: the chained GEMMs - bit-identity with the per-GEMM launches, the parity suites that run through the shared core,
@@ -49,16 +49,16 @@ planes)
   timeout 900 python -m pytest tests/test_gpu_planes.py -x -q 2>&1 | tail -15 | tee $OUT/planes_tests.log
   timeout 900 python -m pytest tests/test_gpu_matcher.py tests/test_gpu_golden_direct.py -x -q 2>&1 | tail -15 | tee $OUT/planes_matcher.log
   timeout 600 python tools/microbench.py --what p2 2>&1 | tee $OUT/microbench_p2.log
-  timeout 300 python bench.py --steps 10 --warmup 3 --cpu-pairs 0 --no-alt --no-latency > $OUT/bench_p2.json 2> $OUT/bench_p2.err
-  E2EMV_F16X2_KERNELS=r2 timeout 300 python bench.py --steps 10 --warmup 3 --cpu-pairs 0 --no-alt --no-latency > $OUT/bench_r2k.json 2> $OUT/bench_r2k.err
+  timeout 300 python bench.py --full --steps 10 --warmup 3 --cpu-pairs 0 --no-alt --no-latency > $OUT/bench_p2.json 2> $OUT/bench_p2.err
+  E2EMV_F16X2_KERNELS=r2 timeout 300 python bench.py --full --steps 10 --warmup 3 --cpu-pairs 0 --no-alt --no-latency > $OUT/bench_r2k.json 2> $OUT/bench_r2k.err
   show $OUT/bench_p2.json $OUT/bench_r2k.json
   ;;
 aw)
   # attention_p2w: parity of the attention kernels on planes, micro-benchmark against attention_p2, one bench line per kernel
   timeout 900 python -m pytest tests/test_gpu_planes.py -x -q -k attention 2>&1 | tail -15 | tee $OUT/aw_tests.log
   timeout 600 python tools/microbench.py --what ap2 2>&1 | tee $OUT/microbench_ap2.log
-  timeout 300 python bench.py --steps 10 --warmup 3 --cpu-pairs 0 --no-alt --no-latency > $OUT/bench_aw.json 2> $OUT/bench_aw.err
-  E2EMV_F16X2_KERNELS=r3 timeout 300 python bench.py --steps 10 --warmup 3 --cpu-pairs 0 --no-alt --no-latency > $OUT/bench_ap8.json 2> $OUT/bench_ap8.err
+  timeout 300 python bench.py --full --steps 10 --warmup 3 --cpu-pairs 0 --no-alt --no-latency > $OUT/bench_aw.json 2> $OUT/bench_aw.err
+  E2EMV_F16X2_KERNELS=r3 timeout 300 python bench.py --full --steps 10 --warmup 3 --cpu-pairs 0 --no-alt --no-latency > $OUT/bench_ap8.json 2> $OUT/bench_ap8.err
   show $OUT/bench_aw.json $OUT/bench_ap8.json
   ;;
 awabl)
@@ -99,8 +99,8 @@ cstamps)
   timeout 1200 python tools/p2c_stamps.py "${@:2}" 2>&1 | tee $OUT/p2c_stamps.log
   ;;
 ab)
-  timeout 300 python bench.py --steps 10 --warmup 3 --cpu-pairs 0 --no-alt --no-latency > $OUT/bench_p2.json 2> $OUT/bench_p2.err
-  E2EMV_F16X2_KERNELS=r2 timeout 300 python bench.py --steps 10 --warmup 3 --cpu-pairs 0 --no-alt --no-latency > $OUT/bench_r2k.json 2> $OUT/bench_r2k.err
+  timeout 300 python bench.py --full --steps 10 --warmup 3 --cpu-pairs 0 --no-alt --no-latency > $OUT/bench_p2.json 2> $OUT/bench_p2.err
+  E2EMV_F16X2_KERNELS=r2 timeout 300 python bench.py --full --steps 10 --warmup 3 --cpu-pairs 0 --no-alt --no-latency > $OUT/bench_r2k.json 2> $OUT/bench_r2k.err
   show $OUT/bench_p2.json $OUT/bench_r2k.json
   ;;
 sk128)
@@ -130,9 +130,9 @@ tests)
   timeout 1500 python -m pytest tests -m gpu -x -q 2>&1 | tail -15 | tee $OUT/tests.log
   ;;
 bench)
-  timeout 400 python bench.py > $OUT/bench_c2.json 2> $OUT/bench_c2.err
-  timeout 300 python bench.py --config c4 --cpu-pairs 0 > $OUT/bench_c4.json 2> $OUT/bench_c4.err
-  timeout 300 python bench.py --config c5 --cpu-pairs 0 > $OUT/bench_c5.json 2> $OUT/bench_c5.err
+  timeout 400 python bench.py --full > $OUT/bench_c2.json 2> $OUT/bench_c2.err
+  timeout 300 python bench.py --full --config c4 --cpu-pairs 0 > $OUT/bench_c4.json 2> $OUT/bench_c4.err
+  timeout 300 python bench.py --full --config c5 --cpu-pairs 0 > $OUT/bench_c5.json 2> $OUT/bench_c5.err
   show $OUT/bench_c2.json $OUT/bench_c4.json $OUT/bench_c5.json
   ;;
 final)
@@ -159,7 +159,7 @@ final)
   grep "gemm_p2_chain\|attention_p2w" $OUT/r6_kernel_stats_c2_f16x2.md $OUT/r6_kernel_stats_c2_f16x2_steps6.md
   ;;
 one)
-  timeout 300 python bench.py --steps 10 --warmup 3 --cpu-pairs 0 --no-alt --no-latency > $OUT/bench_one.json 2> $OUT/bench_one.err
+  timeout 300 python bench.py --full --steps 10 --warmup 3 --cpu-pairs 0 --no-alt --no-latency > $OUT/bench_one.json 2> $OUT/bench_one.err
   show $OUT/bench_one.json
   python -c "
 import json; d=json.loads(open('$OUT/bench_one.json').read().strip().splitlines()[-1]); print(json.dumps(d['roofline'], indent=1)); print(json.dumps(d.get('sinkhorn_bound'), indent=1))"
