@@ -13,8 +13,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libe2emv.so")
 SOURCES = ["ctx.hip", "gemm.hip", "attention.hip", "gemm3.hip", "gemm_x3.hip", "gemm_h2.hip", "gemm_p2.hip", "gemm_p2c.hip", "attention_p2.hip", "attention_p2w.hip", "p2_tools.hip", "attention3.hip", "split3_api.hip", "sinkhorn.hip", "pose.hip", "ba2view.hip", "gtmatch.hip",
            "mvinit.hip", "mvba.hip", "superpoint.hip", "forward.hip", "train.hip", "comm.hip"]
-# (superseded kernels are compiled under #ifdef E2EMV_STAMPS inside their files: gemm3.hip's all-planes GEMM, generations 2 / 3 of the
-# f16x2 selection - A/B arms of the measurement build, not in the product)
+# (one build: every kernel in these files is part of the product library; measurements and probes live in standalone files under tools/)
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-fvisibility-inlines-hidden", "-ffp-contract=fast", "-Wno-unused-result"]
 
 
@@ -28,18 +27,13 @@ def _stamp():
     return h.hexdigest()
 
 
-def build_library(force=False, verbose=False, defines=(), out=None):
-    """`defines` / `out`: a measurement build beside the product library (tools/p2_stamps.py builds tools/libe2emv_stamps.bin with
-    -DE2EMV_STAMPS: in-kernel timestamps and ablation variants that the product library does not contain)."""
+def build_library(force=False, verbose=False):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    if defines or out:
-        # (measurement builds live under tools/*.bin - git-ignored, never next to the product library)
-        return _build(hipcc, os.path.join(HERE, "build_" + os.path.basename(out).split(".")[0]), out, ["-D" + d for d in defines], verbose)
     stamp_file = os.path.join(HERE, "csrc", ".build_stamp")
     stamp = _stamp()
     if not force and os.path.exists(LIB) and os.path.exists(stamp_file) and open(stamp_file).read() == stamp:
         return LIB
-    _build(hipcc, os.path.join(HERE, "build"), LIB, [], verbose)
+    _build(hipcc, os.path.join(HERE, "build"), LIB, verbose)
     with open(stamp_file, "w") as fh:
         fh.write(stamp)
     return LIB
@@ -78,16 +72,16 @@ def check_register_window(asm_file, kernel, window):
     return n
 
 
-def _build(hipcc, objdir, lib, extra, verbose):
+def _build(hipcc, objdir, lib, verbose):
     os.makedirs(objdir, exist_ok=True)
     # gemm_p2c.hip hands tiles from one wave to another of the SAME workgroup through the CU's vector L1 (stores retired + barrier):
     # threadgroup-split mode would put those waves on different CUs / L1s
-    if any("tgsplit" in f for f in FLAGS + list(extra)):
+    if any("tgsplit" in f for f in FLAGS):
         raise RuntimeError("libe2emv is built for CU mode: -mtgsplit breaks the in-workgroup hand-off of gemm_p2c.hip")
     procs = []
     for src in SOURCES:
         obj = os.path.join(objdir, src.replace(".hip", ".o"))
-        cmd = [hipcc] + FLAGS + extra + ["-c", os.path.join(CSRC, src), "-o", obj]
+        cmd = [hipcc] + FLAGS + ["-c", os.path.join(CSRC, src), "-o", obj]
         cwd = None
         if src == "sinkhorn.hip":
             # sinkhorn_resident128 / sinkhorn_resident2k keep most of their data in registers they address by number, outside the

@@ -46,7 +46,7 @@ struct AttnParams {
     float* part_ml;  // [n_img][H][n_rows][ksplit][2]
 };
 
-template <int DBG, bool SPLIT = false>
+template <bool SPLIT = false>
 __global__ __launch_bounds__(256, 3) void attention_kernel(AttnParams p) {
     __shared__ __attribute__((aligned(16))) float Ks[ATT_KV * KLD];
     __shared__ __attribute__((aligned(16))) float Vs[ATT_KV * HD];
@@ -122,7 +122,6 @@ __global__ __launch_bounds__(256, 3) void attention_kernel(AttnParams p) {
     const int tile_hi = SPLIT ? (int)((int64_t)n_tiles * (sp + 1) / p.ksplit) : n_tiles;
     if (tile_lo < tile_hi) gload(tile_lo);
     for (int tile = tile_lo; tile < tile_hi; ++tile) {
-        if (!(DBG & 4) || tile == tile_lo) {
         __syncthreads();  // everyone is done reading the previous tile
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -131,7 +130,6 @@ __global__ __launch_bounds__(256, 3) void attention_kernel(AttnParams p) {
         }
         __syncthreads();
         if (tile + 1 < tile_hi) gload(tile + 1);
-        }
 
         int tt_cur, kt;
         locate(tile, tt_cur, kt);
@@ -165,15 +163,13 @@ __global__ __launch_bounds__(256, 3) void attention_kernel(AttnParams p) {
             float ps = 0.f;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                if (!(DBG & 1)) S[r] = __builtin_amdgcn_exp2f(S[r] - m_new);
+                S[r] = __builtin_amdgcn_exp2f(S[r] - m_new);
                 ps += S[r];
             }
             l_run = l_run * alpha + ps;
             m_run = m_new;
-            if (!(DBG & 2)) {
 #pragma unroll
-                for (int r = 0; r < 16; ++r) { O0[r] *= alpha; O1[r] *= alpha; }
-            }
+            for (int r = 0; r < 16; ++r) { O0[r] *= alpha; O1[r] *= alpha; }
             // O^T[d][q] += V^T[d][key] P^T[key][q]
             const float* vp = &Vs[(sub * 32 + 4 * lh) * HD + l31];
 #pragma unroll
@@ -255,12 +251,8 @@ int launch_attention(e2emv_ctx* ctx, int B, int T, int n_rows, const int* nv, in
     p.groups = B * T * H;
     p.gper = (p.groups + 7) / 8;
     dim3 grid(8 * p.gper * p.nq);
-    static int dbg = -1;  // E2EMV_ATTN_DEBUG: ablation variants for profiling only (results are wrong when != 0)
-    if (dbg < 0) dbg = dbg_knob("E2EMV_ATTN_DEBUG", 0);
     // Small problems (batch 1-2 of the reference's eval loop): one workgroup per (image, head, 128 queries) leaves most CUs
     // idle while each workgroup walks all key tiles serially.  Split the key tiles over up to 8 workgroups + a merge pass.
-    static int split_env = -1;  // E2EMV_ATTN_SPLIT: 0 off, n > 1 forces n
-    if (split_env < 0) split_env = dbg_knob("E2EMV_ATTN_SPLIT", -1);
     p.ksplit = 1; p.part_o = nullptr; p.part_ml = nullptr;
     {
         int min_tiles = 1 << 30;  // key tiles a query walks (smallest over the images)
@@ -271,9 +263,9 @@ int launch_attention(e2emv_ctx* ctx, int B, int T, int n_rows, const int* nv, in
             min_tiles = std::min(min_tiles, n);
         }
         const int blocks = p.groups * p.nq;
-        int ks = split_env > 1 ? split_env : (split_env == 0 ? 1 : (blocks * 2 <= ctx->num_cus ? ctx->num_cus / blocks : 1));
+        int ks = blocks * 2 <= ctx->num_cus ? ctx->num_cus / blocks : 1;
         ks = std::max(1, std::min(std::min(ks, 8), min_tiles));
-        if (ks > 1 && dbg == 0) {
+        if (ks > 1) {
             const size_t rows = (size_t)p.groups * n_rows * ks;
             const size_t need = rows * (HD + 2) * sizeof(float);
             if (ctx->attn_part_bytes < need) {
@@ -286,21 +278,14 @@ int launch_attention(e2emv_ctx* ctx, int B, int T, int n_rows, const int* nv, in
             p.ksplit = ks;
             p.part_o = ctx->d_attn_part;
             p.part_ml = ctx->d_attn_part + rows * HD;
-            hipLaunchKernelGGL((attention_kernel<0, true>), dim3(8 * p.gper * p.nq * ks), dim3(256), 0, s, p);
+            hipLaunchKernelGGL((attention_kernel<true>), dim3(8 * p.gper * p.nq * ks), dim3(256), 0, s, p);
             const int64_t threads = (int64_t)p.groups * n_rows * 16;
             hipLaunchKernelGGL(attention_merge_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, p);
             E2EMV_CHECK_LAUNCH(ctx, "attention_kernel (key-split)");
             return E2EMV_OK;
         }
     }
-    switch (dbg) {
-        case 1: hipLaunchKernelGGL(attention_kernel<1>, grid, dim3(256), 0, s, p); break;
-        case 2: hipLaunchKernelGGL(attention_kernel<2>, grid, dim3(256), 0, s, p); break;
-        case 3: hipLaunchKernelGGL(attention_kernel<3>, grid, dim3(256), 0, s, p); break;
-        case 4: hipLaunchKernelGGL(attention_kernel<4>, grid, dim3(256), 0, s, p); break;
-        case 7: hipLaunchKernelGGL(attention_kernel<7>, grid, dim3(256), 0, s, p); break;
-        default: hipLaunchKernelGGL(attention_kernel<0>, grid, dim3(256), 0, s, p); break;
-    }
+    hipLaunchKernelGGL(attention_kernel<>, grid, dim3(256), 0, s, p);
     E2EMV_CHECK_LAUNCH(ctx, "attention_kernel");
     return E2EMV_OK;
 }

@@ -20,7 +20,6 @@ struct AttnP2Params {
     float* part;          // ... their (O, m, l) records and
     int* part_e;          // ... the V exponent each wave's O sits at
     unsigned* stats;      // attention_p2w: [0] += (wave, stream, tile) softmaxes redone on the slow path (beyond a stream's first tile)
-    long long* dbg;       // measurement build: timestamps of two workgroups (attention_p2w)
 };
 
 // attention_p2w.hip: p.nq / p.gper are filled in by the launcher (256 queries per workgroup)

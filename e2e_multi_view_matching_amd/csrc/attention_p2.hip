@@ -313,13 +313,10 @@ int launch_attention_p2(e2emv_ctx* ctx, int B, int T, int n_rows, const int* nv,
     p.cross = cross;
     p.groups = B * T * H;
     p.gper = (p.groups + 7) / 8;
-    static int nw_knob = -1;
-    if (nw_knob < 0) nw_knob = dbg_knob("E2EMV_AP2_NW", 0);
-    if (nw_knob == 4 || nw_knob == 8 || nw_knob == 1) ctx->attn_p2_nw = nw_knob;
     // above 256 keys: one wave per SIMD with the overlap of matrix and vector work written into the wave's instruction
     // stream (attention_p2w.hip, attn_p2_nw == 1 forces it); below, and for A/B runs (4 / 8), the two-waves-per-SIMD kernel here
-    if (ctx->attn_p2_nw == 1 || (ctx->attn_p2_nw == 0 && ctx->attn_wide && n_valid > 256)) return launch_attention_p2w(ctx, p, n_valid, s);
-    const int nw = ctx->attn_p2_nw == 4 || ctx->attn_p2_nw == 8 ? ctx->attn_p2_nw : (n_valid > 256 ? 8 : 4);  // measured: 222 / 224 us at 1024 keys, 202 / 209 at 2048
+    if (ctx->attn_p2_nw == 1 || (ctx->attn_p2_nw == 0 && n_valid > 256)) return launch_attention_p2w(ctx, p, n_valid, s);
+    const int nw = ctx->attn_p2_nw == 8 ? 8 : 4;  // (8 waves against 4 above 256 keys measured: 222 / 224 us at 1024 keys, 202 / 209 at 2048)
     const size_t lds = 2 * AP_BUFB;
     const void* fn = nw == 8 ? reinterpret_cast<const void*>(attention_p2_kernel<8>) : reinterpret_cast<const void*>(attention_p2_kernel<4>);
     p.nq = (n_valid + 32 * nw - 1) / (32 * nw);

@@ -23,7 +23,6 @@
 // it); fragment reads run two groups of 6 MFMAs ahead, across segment and tile boundaries.
 #include <algorithm>
 #include <type_traits>
-#include <vector>
 
 #include "attention_p2.h"
 
@@ -130,12 +129,10 @@ __device__ __forceinline__ void aw_load_q(const char* qp, p2_f16x8 (&q)[2][4]) {
         : "v"(qp) : "memory");
 }
 
-// ABL (measurement only, wrong results): 1 no softmax arithmetic in the slots, 2 no MFMAs, 4 no fragment reads, 8 no LDS-direct
-// loads, 16 no barrier
 // MULTI: more than one source image per query image (cross layers of tuples with T > 2); without it the tile walk is a counter
 // PART: the instantiation that walks the key-split PARTS of a launch's leftover items (its own launch behind the whole items': the
 // whole-item kernel stays the code it was - carrying the part logic as run-time flags cost it 6 % at configs[1])
-template <bool HAS_E, int ABL = 0, bool MULTI = true, bool PART = false>
+template <bool HAS_E, bool MULTI = true, bool PART = false>
 __global__ __launch_bounds__(256, 1) void attention_p2w_kernel(AttnP2Params p) {
     extern __shared__ __attribute__((aligned(16))) char smem_aw[];
 
@@ -162,15 +159,6 @@ __global__ __launch_bounds__(256, 1) void attention_p2w_kernel(AttnP2Params p) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l31 = lane & 31, lh = lane >> 5;
     const unsigned row_b = 8u * (unsigned)p.D;
-    int n_stamp = 0;
-    auto stamp = [&]() __attribute__((always_inline)) {
-        if constexpr ((ABL & 32) != 0) {
-            const long long tnow = __builtin_amdgcn_s_memtime();
-            if (p.dbg && lane == 0 && n_stamp < 40 && (blockIdx.x == 0 || blockIdx.x == 517)) p.dbg[((blockIdx.x ? 1 : 0) * 4 + wave) * 40 + n_stamp] = tnow;
-            ++n_stamp;
-        }
-    };
-    stamp();  // 0: start
 
     // ---- Q fragments of the two streams (B operand): lane (query l31, lh) holds d = 16 s + 8 lh .. + 7 of both planes
     int q_row[2];
@@ -183,7 +171,6 @@ __global__ __launch_bounds__(256, 1) void attention_p2w_kernel(AttnP2Params p) {
         const char* qp = reinterpret_cast<const char*>(p.qk) + ((int64_t)img * p.n_rows + (q_ok[a] ? q_row[a] : p.n_rows - 1)) * row_b + head * 256;
         aw_load_q(qp + lh * 16, Qf[a]);  // chunk ((s >> 1) * 8 + pl * 4 + 2 * (s & 1) + lh) of the row's 16
     }
-    stamp();  // 1: Q loads issued
     const int q_blk = __builtin_amdgcn_readfirstlane(((int64_t)img * p.n_rows + min(qt * AW_QT + wave * 64, p.n_rows - 1)) >> 6);
     const int e_q = HAS_E ? p.EQK[q_blk * 8 + head] : 0;
 
@@ -365,16 +352,10 @@ __global__ __launch_bounds__(256, 1) void attention_p2w_kernel(AttnP2Params p) {
     // one queue, in issue order: exponents, Q fragments, K(0) | V(0), K(1) | V(1), K(2).  The first scores need the first three:
     // the 16 youngest pieces stay in flight (every workgroup of the chip starts at the same time: the prologue's loads are a
     // 37 MB burst, its tail lands under the first scores and the first softmax)
-    if constexpr ((ABL & 256) != 0) {  // measurement (wrong results): what the prologue's wait for Q / K(0) costs a launch
-        asm volatile("s_waitcnt vmcnt(63)" : "+a"(Qf[0][0][0]), "+a"(Qf[0][0][1]), "+a"(Qf[0][0][2]), "+a"(Qf[0][0][3]), "+a"(Qf[0][1][0]), "+a"(Qf[0][1][1]), "+a"(Qf[0][1][2]), "+a"(Qf[0][1][3]),
-                     "+a"(Qf[1][0][0]), "+a"(Qf[1][0][1]), "+a"(Qf[1][0][2]), "+a"(Qf[1][0][3]), "+a"(Qf[1][1][0]), "+a"(Qf[1][1][1]), "+a"(Qf[1][1][2]), "+a"(Qf[1][1][3]) :: "memory");
-    } else {
-        aw_wait_q(Qf);
-    }
+    aw_wait_q(Qf);
     __syncthreads();
     p2_u32x2 e_pair = {0u, 0u};  // {e_k, e_v} of the tile whose exponents are needed next (all lanes equal)
     if constexpr (HAS_E) e_pair = read_e(0);
-    stamp();  // 2: Q and the first tiles landed
 #pragma unroll
     for (int s = 0; s < 4; ++s)
 #pragma unroll
@@ -400,8 +381,7 @@ __global__ __launch_bounds__(256, 1) void attention_p2w_kernel(AttnP2Params p) {
             }
         // K(0) sits where X(0) puts K(3): everybody is through with it before anybody's pieces go out; and
         // V(0) | K(1) have landed, everybody's (8 pieces - V(1) | K(2) - may still be in flight: the barrier of tile 0 waits for them)
-        if constexpr ((ABL & 256) != 0) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)\n\ts_barrier" ::: "memory");
         sm_slow(std::integral_constant<int, 0>{}, sinv, cS.nv - cS.kt * 64);
         // stream 1's first tile takes the fast path in X(0): its running maximum starts at the tile's row maxima (a ragged
         // first tile is left to the slow path, which masks)
@@ -422,7 +402,6 @@ __global__ __launch_bounds__(256, 1) void attention_p2w_kernel(AttnP2Params p) {
 #pragma unroll
         for (int pl = 0; pl < 2; ++pl) R[s][pl] -= 2 * AW_REGB;  // region 0
     int reg_cur = 0, seg_tile = 0;
-    stamp();  // 3: prologue scores + slow softmax done
 
     // fragment registers: group g of a segment (6 MFMAs: one 16-key step of V^T, or one 16-dim step of K) uses F[g & 3]; the
     // reads run TWO groups (12 MFMAs) ahead of their use - one group ahead the matrix pipe waited for LDS (measured)
@@ -474,7 +453,7 @@ __global__ __launch_bounds__(256, 1) void attention_p2w_kernel(AttnP2Params p) {
         }
         // a ragged tile (the last one of a source with nv % 64 != 0): scores of the keys beyond nv to -inf in front of the
         // fast path (p = 0; the S of this stream are a segment old: no MFMA in flight writes them)
-        if (HAS_SM && !(ABL & 1) && __builtin_expect(valid < 64, 0)) {
+        if (HAS_SM && __builtin_expect(valid < 64, 0)) {
             asm volatile("s_nop 7" : "+v"(S[B][0]), "+v"(S[B][1]));
 #pragma unroll
             for (int kb = 0; kb < 2; ++kb)
@@ -501,9 +480,9 @@ __global__ __launch_bounds__(256, 1) void attention_p2w_kernel(AttnP2Params p) {
             } else if constexpr (m == 49) {  // ... second half
                 Pf[B][1][3][3] = aw_mixhi(lo_k[15], hi_k[15], pa[15][1]);
             } else if constexpr (ph == 0) {
-                xa[k][0] = aw_fma((ABL & 64) ? e0 : S[B][kb][r], sinv_v, e0);  // (ABL 64: the softmax does not read MFMA results)
+                xa[k][0] = aw_fma(S[B][kb][r], sinv_v, e0);
                 if constexpr (k > 0) lo_k[k - 1] = aw_mixlo(hi_k[k - 1], pa[k - 1][0]);
-                xa[k][1] = aw_fma((ABL & 64) ? e0 : S[B][kb][r + 1], sinv_v, e0);
+                xa[k][1] = aw_fma(S[B][kb][r + 1], sinv_v, e0);
             } else if constexpr (ph == 1) {
                 pa[k][0] = aw_exp2(xa[k][0]);
                 if constexpr (k > 0) {
@@ -529,14 +508,11 @@ __global__ __launch_bounds__(256, 1) void attention_p2w_kernel(AttnP2Params p) {
         }
         const int reg_ld = reg_cur == 0 ? 2 : reg_cur - 1;  // (reg_cur + 2) % 3
 
-        long long tslot[9], tm[3] = {0, 0, 0};
         aw_for<0, NSLOT>([&](auto II) __attribute__((always_inline)) {
             constexpr int i = decltype(II)::value;
             constexpr int gq = i / 6, w = i % 6;
-            if constexpr ((ABL & 128) != 0 && !LAST && w == 0) asm volatile("s_memtime %0" : "=s"(tslot[gq]));
             // (1) the slot's MFMA
-            if constexpr (ABL & 2) {
-            } else if constexpr (i < 24) {
+            if constexpr (i < 24) {
                 constexpr int u = i / 6, q = (i % 6) / 2, db = i % 2;
                 aw_mfma_o(O[A][db], F[u & 3][2 * db + PA[q]], Pf[A][PB[q]][u]);
             } else {
@@ -548,7 +524,7 @@ __global__ __launch_bounds__(256, 1) void attention_p2w_kernel(AttnP2Params p) {
             // nine), sums up in slot 46 and evaluates the range check in slot 47 - INSIDE the stream: behind the last MFMA of a
             // segment comes one branch on a scalar flag and the first MFMA of the next, not the tail of a softmax (measured:
             // ~300 cycles of idle matrix pipe per segment boundary).
-            if constexpr (HAS_SM && !(ABL & 1)) {
+            if constexpr (HAS_SM) {
                 if constexpr (LAST) {
                     aw_for<0, MPS>([&](auto JJ) __attribute__((always_inline)) { micro(std::integral_constant<int, MPS * i + decltype(JJ)::value>{}); });
                 } else if constexpr (i < 9) {
@@ -563,7 +539,7 @@ __global__ __launch_bounds__(256, 1) void attention_p2w_kernel(AttnP2Params p) {
                     ps = psA;
                     aw_acc(ps, psB);
                 } else if constexpr (i == 47) {
-                    slow = ((ABL & 28) == 28 || (ABL & 512)) ? false : __builtin_amdgcn_ballot_w64(!(ps < AW_LIMIT)) != 0;
+                    slow = __builtin_amdgcn_ballot_w64(!(ps < AW_LIMIT)) != 0;
                     l_run[B] += slow ? 0.f : ps;
                 }
             }
@@ -571,13 +547,7 @@ __global__ __launch_bounds__(256, 1) void attention_p2w_kernel(AttnP2Params p) {
             // reads region j % 3 any more (the fragments of this segment's last groups were read in slots 25..34)
             if constexpr (A == 1 && !LAST && i == 36) {
                 // counted: the 8 pieces issued in X(j) - the tile after next - stay in flight
-                if constexpr ((ABL & 128) != 0) {  // measurement: what the wait is for
-                    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tm[0]));
-                    asm volatile("s_waitcnt vmcnt(8)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tm[1]));
-                    asm volatile("s_barrier\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tm[2]));
-                }
-                if constexpr (ABL & 16) asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)" ::: "memory");
-                else asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+                asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)\n\ts_barrier" ::: "memory");
                 const unsigned d = reg_cur == 2 ? (unsigned)(-2 * AW_REGB) : (unsigned)AW_REGB;
 #pragma unroll
                 for (int s = 0; s < 4; ++s)
@@ -587,7 +557,7 @@ __global__ __launch_bounds__(256, 1) void attention_p2w_kernel(AttnP2Params p) {
             }
             // (4) fragment reads of the group after next (slots 1..4 of a group); past this segment's last group they are
             // groups 0 / 1 of the NEXT segment - behind the barrier where that is the next tile
-            if constexpr (w >= 1 && w <= 4 && !(ABL & 4)) {
+            if constexpr (w >= 1 && w <= 4) {
                 constexpr int gn = gq + 2;
                 if constexpr (gn < NG) {
                     if constexpr (gn < 4) read_frag(gn & 3, w - 1, gn, 0);       // V(j), 16-key step gn
@@ -598,22 +568,14 @@ __global__ __launch_bounds__(256, 1) void attention_p2w_kernel(AttnP2Params p) {
             }
             // (5) LDS-direct loads of the next tile (segment X): one piece every fourth slot (a piece costs the wave 60 - 180
             // cycles of issue: bunched they starve the matrix pipe), the last one 55 slots ahead of the barrier
-            if constexpr (A == 0 && !LAST && i < 32 && i % 4 == 1 && !(ABL & 8)) {
+            if constexpr (A == 0 && !LAST && i < 32 && i % 4 == 1) {
                 if constexpr (i < 16) v_piece(reg_ld, i / 4, so_v);
                 else k_piece(reg_ld, i / 4 - 4, so_k);
             }
             __builtin_amdgcn_sched_barrier(0);
         });
-        if constexpr ((ABL & 128) != 0 && !LAST) {
-            asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tslot[8]));
-            if (p.dbg && lane == 0 && seg_tile == 2 && (blockIdx.x == 0 || blockIdx.x == 517))
-            {
-                for (int q = 0; q < 9; ++q) p.dbg[320 + (((blockIdx.x ? 1 : 0) * 4 + wave) * 2 + A) * 9 + q] = tslot[q];
-                if (A == 1) for (int q = 0; q < 3; ++q) p.dbg[320 + 144 + ((blockIdx.x ? 1 : 0) * 4 + wave) * 3 + q] = tm[q];
-            }
-        }
 
-        if constexpr (HAS_SM && LAST && !(ABL & 1)) {
+        if constexpr (HAS_SM && LAST) {
             // (the peeled last tile: its softmax ran two micro-steps per slot over 24 slots; split of the last pair and the range
             // check behind the stream)
             lo_k[15] = aw_mixlo(hi_k[15], pa[15][0]);
@@ -626,7 +588,7 @@ __global__ __launch_bounds__(256, 1) void attention_p2w_kernel(AttnP2Params p) {
                 ++n_slow;
             }
         }
-        if constexpr (HAS_SM && !LAST && !(ABL & 1)) {
+        if constexpr (HAS_SM && !LAST) {
             if (__builtin_expect(slow, 0)) {  // (out of line: the fast path falls through)
                 sm_slow(std::integral_constant<int, B>{}, sinv, valid);
                 ++n_slow;
@@ -639,12 +601,9 @@ __global__ __launch_bounds__(256, 1) void attention_p2w_kernel(AttnP2Params p) {
         seg_tile = j;
         seg(std::integral_constant<int, 0>{}, std::false_type{});
         seg(std::integral_constant<int, 1>{}, std::false_type{});
-        stamp();  // 4 .. 4 + n_tiles - 2: after tile j
     }
-    stamp();  // 10: loop done
     seg(std::integral_constant<int, 0>{}, std::true_type{});  // the last tile, peeled: no K(j+1) left
     seg(std::integral_constant<int, 1>{}, std::true_type{});
-    stamp();  // 11: last tile done
 
     // ---- epilogue: scaled planes of the two streams' output rows
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (the pieces the last iterations issued past the last tile: nothing lands in LDS behind this workgroup)
@@ -694,11 +653,6 @@ __global__ __launch_bounds__(256, 1) void attention_p2w_kernel(AttnP2Params p) {
             }
     }
     if (p.stats && n_slow && lane == 0) atomicAdd(p.stats, n_slow);
-    stamp();  // 12: stores issued
-    if constexpr ((ABL & 32) != 0) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        stamp();  // 13: stores done
-    }
 }
 
 // The parts of the key-split items -> output rows.  Part k of a query holds O_k = sum_j 2^(s_j - m_k + c) v_j over ITS keys (at the
@@ -765,43 +719,14 @@ int launch_attention_p2w(e2emv_ctx* ctx, AttnP2Params& p, int n_valid, hipStream
     p.stats = ctx->d_flags + 5;
     const size_t lds = 3 * AW_REGB + 2048;  // + the tile exponents (<= 7 sources x 32 tiles x 8 bytes)
     const bool multi = p.cross && p.T > 2;
-    const void* fn = p.EQK ? (multi ? reinterpret_cast<const void*>(attention_p2w_kernel<true, 0, true>) : reinterpret_cast<const void*>(attention_p2w_kernel<true, 0, false>))
-                           : (multi ? reinterpret_cast<const void*>(attention_p2w_kernel<false, 0, true>) : reinterpret_cast<const void*>(attention_p2w_kernel<false, 0, false>));
-#ifdef E2EMV_STAMPS
-    switch (ctx->attn_abl) {  // measurement build: ablations of the main loop (e2emv_attention_p2 flags bits 4..7 + bit 3)
-        case 1: fn = reinterpret_cast<const void*>(attention_p2w_kernel<true, 1, false>); break;
-        case 2: fn = reinterpret_cast<const void*>(attention_p2w_kernel<true, 2, false>); break;
-        case 3: fn = reinterpret_cast<const void*>(attention_p2w_kernel<true, 3, false>); break;
-        case 4: fn = reinterpret_cast<const void*>(attention_p2w_kernel<true, 4, false>); break;
-        case 5: fn = reinterpret_cast<const void*>(attention_p2w_kernel<true, 5, false>); break;
-        case 8: fn = reinterpret_cast<const void*>(attention_p2w_kernel<true, 8, false>); break;
-        case 13: fn = reinterpret_cast<const void*>(attention_p2w_kernel<true, 13, false>); break;
-        case 16: fn = reinterpret_cast<const void*>(attention_p2w_kernel<true, 16, false>); break;
-        case 29: fn = reinterpret_cast<const void*>(attention_p2w_kernel<true, 29, false>); break;
-        case 12: fn = reinterpret_cast<const void*>(attention_p2w_kernel<true, 28, false>); break;   // MFMAs + softmax only
-        case 11: fn = reinterpret_cast<const void*>(attention_p2w_kernel<true, 92, false>); break;   // ... the softmax fed from a constant
-        case 10: fn = reinterpret_cast<const void*>(attention_p2w_kernel<true, 30, false>); break;   // softmax only
-        case 14: fn = reinterpret_cast<const void*>(attention_p2w_kernel<true, 32, false>); break;  // timestamps
-        case 9: fn = reinterpret_cast<const void*>(attention_p2w_kernel<true, 160, false>); break;
-        case 7: fn = reinterpret_cast<const void*>(attention_p2w_kernel<true, 256 + 512, false>); break;  // no wait for Q / K(0) in the prologue, never the slow path
-        case 6: fn = reinterpret_cast<const void*>(attention_p2w_kernel<true, 512, false>); break;        // never the slow path (the arm to compare it with)  // ... and inside the segments of tile 2
-        default: break;
-    }
-    static long long* d_stamps = nullptr;
-    const size_t nb = sizeof(long long) * (2 * 4 * 40 + 2 * 4 * 2 * 9 + 2 * 4 * 3);
-    p.dbg = nullptr;
-    if (ctx->attn_abl == 14 || ctx->attn_abl == 9) {
-        if (!d_stamps) E2EMV_HIP(ctx, hipMalloc((void**)&d_stamps, nb));
-        E2EMV_HIP(ctx, hipMemsetAsync(d_stamps, 0, nb, s));
-        p.dbg = d_stamps;
-    }
-#endif
+    const void* fn = p.EQK ? (multi ? reinterpret_cast<const void*>(attention_p2w_kernel<true, true>) : reinterpret_cast<const void*>(attention_p2w_kernel<true, false>))
+                           : (multi ? reinterpret_cast<const void*>(attention_p2w_kernel<false, true>) : reinterpret_cast<const void*>(attention_p2w_kernel<false, false>));
     if (int rc = ensure_dynamic_lds(ctx, fn, lds)) return rc;
     void* args[] = {&p};
     // ---- the last round of workgroups.  n_items = R CUs + r: with 0 < r <= CUs / 2 the r leftover items would hold the chip for a whole
     // round at < half its width (T = 5, 1024 keypoints: 640 items, 3 rounds for 2.5 of work) - they are split along the keys into
     // n_split = floor(CUs / r) parts each (<= 8, <= the fewest key tiles of an item) + one small combine launch.  Fewer items than CUs
-    // (R = 0: a pair or two per call) split the same way.  e2emv_attention_p2 flags bit 12 (tests): never.
+    // (R = 0: a pair or two per call) split the same way.
     const int n_items = 8 * p.gper * p.nq, cus = std::max(8, ctx->num_cus / 8 * 8);
     const int r = n_items % cus;
     int min_tiles = 1 << 30;
@@ -836,43 +761,14 @@ int launch_attention_p2w(e2emv_ctx* ctx, AttnP2Params& p, int n_valid, hipStream
         E2EMV_CHECK_LAUNCH(ctx, "attention_p2w_kernel");
     }
     if (p.n_split > 1) {
-        const void* fp = p.EQK ? (multi ? reinterpret_cast<const void*>(attention_p2w_kernel<true, 0, true, true>) : reinterpret_cast<const void*>(attention_p2w_kernel<true, 0, false, true>))
-                               : (multi ? reinterpret_cast<const void*>(attention_p2w_kernel<false, 0, true, true>) : reinterpret_cast<const void*>(attention_p2w_kernel<false, 0, false, true>));
+        const void* fp = p.EQK ? (multi ? reinterpret_cast<const void*>(attention_p2w_kernel<true, true, true>) : reinterpret_cast<const void*>(attention_p2w_kernel<true, false, true>))
+                               : (multi ? reinterpret_cast<const void*>(attention_p2w_kernel<false, true, true>) : reinterpret_cast<const void*>(attention_p2w_kernel<false, false, true>));
         if (int rc = ensure_dynamic_lds(ctx, fp, lds)) return rc;
         E2EMV_HIP(ctx, hipLaunchKernel(fp, dim3((n_items - p.n_full) * p.n_split), dim3(256), args, lds, s));
         E2EMV_CHECK_LAUNCH(ctx, "attention_p2w_kernel (parts)");
         hipLaunchKernelGGL(attention_p2w_combine, dim3(n_items - p.n_full), dim3(1024), 0, s, p);
         E2EMV_CHECK_LAUNCH(ctx, "attention_p2w_combine");
     }
-#ifdef E2EMV_STAMPS
-    if (p.dbg) {
-        E2EMV_HIP(ctx, hipStreamSynchronize(s));
-        std::vector<long long> h(2 * 4 * 40 + 2 * 4 * 2 * 9 + 2 * 4 * 3);
-        E2EMV_HIP(ctx, hipMemcpy(h.data(), p.dbg, h.size() * sizeof(long long), hipMemcpyDeviceToHost));
-        static int printed = 0;
-        if (printed++ < 2)
-            for (int wg = 0; wg < 2; ++wg)
-                for (int w = 0; w < 4; ++w) {
-                    const long long* o = &h[((size_t)wg * 4 + w) * 40];
-                    fprintf(stderr, "attention_p2w wg %d wave %d: cycles since start at the stamps (0 start, 1 Q loads issued, 2 Q and first tiles landed, 3 prologue done, then after every tile of the loop, loop done, last tile done, stores issued, stores done)\n  ", wg ? 517 : 0, w);
-                    for (int i = 0; i < 40 && (i == 0 || o[i]); ++i) fprintf(stderr, " %lld", o[i] - o[0]);
-                    fprintf(stderr, "\n   per tile:");
-                    for (int i = 4; i < 40 && o[i + 4]; ++i) fprintf(stderr, " %lld", o[i] - o[i - 1]);
-                    fprintf(stderr, "\n");
-                    if (ctx->attn_abl == 9)
-                        for (int a = 0; a < 2; ++a) {
-                            const long long* t = &h[320 + (((size_t)wg * 4 + w) * 2 + a) * 9];
-                            fprintf(stderr, "   tile 2 segment %c, first slot at %lld, behind the last slot at %lld; cycles per group of 6 slots:", a ? 'Y' : 'X', t[0] - o[0], t[8] - o[0]);
-                            for (int q = 0; q < 8; ++q) fprintf(stderr, " %lld", t[q + 1] - t[q]);
-                            fprintf(stderr, "\n");
-                            if (a == 1) {
-                                const long long* m = &h[320 + 144 + ((size_t)wg * 4 + w) * 3];
-                                fprintf(stderr, "   its barrier: reached at %lld, pieces landed +%lld, barrier passed +%lld\n", m[0] - o[0], m[1] - m[0], m[2] - m[1]);
-                            }
-                        }
-                }
-    }
-#endif
     return E2EMV_OK;
 }
 

@@ -49,8 +49,6 @@ struct LayerWeights {
     // all device pointers into the weight arena; GEMM weights are [out][in] row-major
     float* w_qkv = nullptr;   // [3D][D]   rows head-major: q | k | v
     float* b_qkv = nullptr;   // [3D]
-    float* w_merge = nullptr; // [D][D]    input columns head-major
-    float* b_merge = nullptr;
     float* w_mlp0 = nullptr;  // [2D][2D]  BN folded
     float* b_mlp0 = nullptr;
     float* w_mlp1 = nullptr;  // [D][2D]
@@ -92,7 +90,6 @@ struct e2emv_ctx {
     std::map<std::string, e2emv::HostTensor> raw;
     // committed model
     bool committed = false;
-    bool fuse_merge = true;  // fold attn.merge into MLP0 at commit time (E2EMV_NO_FUSE_MERGE=1 disables)
     e2emv_model_desc model{};
     float* d_warena = nullptr;
     size_t warena_floats = 0;
@@ -100,13 +97,9 @@ struct e2emv_ctx {
     size_t w3arena_elems = 0;
     int precision = 0;  // E2EMV_PRECISION_F32 | _BF16X3 | _F16X2 (dense GNN contractions)
     int64_t split_min_rows = -1;  // split-operand kernels from this many keypoint rows per call (-1: half a 128-row tile per CU)
-    bool h2_legacy = false;  // f16x2 mode on the round-2 kernels (fp32 activations split inside gemm_h2 / attention_h2f): the A/B arm of the plane path
     int gemm_chain = 1;      // f16x2 kernel generation 5 (default): MLP0 -> MLP1 -> next q|k|v chained in one launch (gemm_p2c.hip); 0 = generation 4 (a launch per GEMM), 2 = chained whenever the shapes allow (e2emv_set_f16x2_kernels(105))
-    bool attn_wide = true;   // f16x2 kernel generations 4, 5: attention_p2w above 256 keys; false = generation 3 (attention_p2 everywhere)
-    bool attn_key_split = true;  // attention_p2w: a half-empty last round of workgroups is split along the keys (attention_p2w.hip; e2emv_attention_p2 flags bit 12 clears it for one call)
-    int attn_abl = 0;        // measurement build: ablation of attention_p2w's main loop
+    bool attn_key_split = true;  // attention_p2w: a half-empty last round of workgroups is split along the keys (attention_p2w.hip)
     int attn_p2_nw = 0;      // attention on planes: 0 = by key count, 4 | 8 = attention_p2 with that many waves, 1 = attention_p2w (micro-benchmarks)
-    bool b3_planes = false;  // bf16x3 mode: q|k|v handed to the attention as planes from the GEMM epilogue (E2EMV_B3_PLANES=1)
     // keypoint encoder: layer 0 (3->c0) used by the ingest kernel, the rest through the GEMM
     float* kenc_w0 = nullptr;  // [c0][3] folded
     float* kenc_b0 = nullptr;  // [c0]
@@ -215,16 +208,6 @@ struct CallGuard {
 // top-level entry point carves it with 256-byte aligned offsets.
 int ws_reserve(e2emv_ctx* ctx, size_t bytes);
 
-// Ablation / profiling knobs (forced tile shapes, kernels with a phase removed - results may be wrong) exist only in the
-// measurement build (-DE2EMV_STAMPS: `python tools/p2_stamps.py --build` makes libe2emv_stamps.so).  The release library
-// compiles them to their defaults and never reads these environment variables.
-#ifdef E2EMV_STAMPS
-inline int dbg_knob(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
-inline const char* dbg_env(const char* name) { return getenv(name); }
-#else
-constexpr int dbg_knob(const char*, int dflt) { return dflt; }
-constexpr const char* dbg_env(const char*) { return nullptr; }
-#endif
 void train_free(e2emv_ctx* ctx);  // train.hip
 // ctx->d_flags (device words: [0] Sinkhorn give-up flag, [1] its sticky count, [2] plane blocks that needed a tile exponent,
 // [3] Sinkhorn problems rescued after a range event, [6] after a timeout, [4] give-ups of the resident kernel's waits,
@@ -254,12 +237,6 @@ struct GemmArgs {
     int64_t ldr = 0, sR = 0;
     float* C = nullptr;
     int64_t ldc = 0, sC = 0;
-    uint16_t* C3 = nullptr;  // optional bf16x3-plane output (S3 [M][3][ldc3]); C may then be null
-    int64_t ldc3 = 0;
-    uint16_t* Vt = nullptr;  // optional: columns >= vt_n0 go out transposed as bf16x3 planes (attention3's V^T)
-    int vt_n0 = 0, n_rows = 0;
-    int q_cols = 0;          // columns < q_cols are scaled by q_scale
-    float q_scale = 1.f;
     float scale = 1.f;
     bool relu = false;
     // implicit-GEMM 3x3 convolution (pad 1, stride 1) over NHWC activations: A = input [imgs*H*W][conv_c], K = 9*conv_c
@@ -271,30 +248,8 @@ int launch_gemm_nt(e2emv_ctx* ctx, const GemmArgs& a, hipStream_t s);
 int launch_attention(e2emv_ctx* ctx, int B, int T, int n_rows, const int* n_valid_img, int D, int H, const float* qkv,
                      int cross, float* out, hipStream_t s);
 
-// ---- bf16x3 split-operand path (gemm3.hip / attention3.hip): fp32-class accuracy on the bf16 pipe ----
+// ---- bf16x3 split-operand path (gemm3.hip / gemm_x3.hip / attention3.hip): fp32-class accuracy on the bf16 pipe ----
 // "S3" = matrix stored as three bf16 planes per row: row r = [plane0 | plane1 | plane2], each ld wide.
-struct Gemm3Args {
-    int M = 0, N = 0, K = 0, K1 = 0;
-    const uint16_t* A = nullptr;
-    int64_t lda = 0;
-    const uint16_t* A2 = nullptr;
-    int64_t lda2 = 0;
-    const uint16_t* W = nullptr;
-    int64_t ldw = 0;
-    const float* bias = nullptr;
-    const float* R = nullptr;
-    int64_t ldr = 0;
-    float* C32 = nullptr;
-    int64_t ldc32 = 0;
-    uint16_t* C3 = nullptr;
-    int64_t ldc3 = 0;
-    uint16_t* Vt = nullptr;
-    int vt_n0 = 0, n_rows = 0;
-    int q_cols = 0;
-    float q_scale = 1.f;
-    bool relu = false;
-};
-int launch_gemm3(e2emv_ctx* ctx, const Gemm3Args& a, hipStream_t s);
 // gemm_x3.hip: fp32 activations (a.A / a.A2, a.bias, a.R, a.C, a.relu as for launch_gemm_nt) x pre-split weights W3 (S3 [N][3][ldw3])
 // host: fp32 weights -> the f16x2 planes appended to `out` (offset returned), *out_scale = 2^-s (ctx.hip)
 size_t add_split_h2(std::vector<uint16_t>& out, const std::vector<float>& w, int rows, int cols, float* out_scale);

@@ -167,15 +167,7 @@ int e2emv_create(e2emv_ctx** out, int device) {
     if (!ctx) return E2EMV_ENOMEM;
     ctx->device = device;
     ctx->num_cus = p.multiProcessorCount;
-    if (dbg_knob("E2EMV_NO_FUSE_MERGE", 0) == 1) ctx->fuse_merge = false;
-    if (dbg_knob("E2EMV_B3_PLANES", 0) == 1) ctx->b3_planes = true;
-    if (const char* e = getenv("E2EMV_F16X2_KERNELS")) {  // r4: a launch per GEMM (the chain's A/B arm and the T = 5 path)
-#ifdef E2EMV_STAMPS
-        // the superseded generations are arms of the measurement build only (round 6: the product selects 5, 105 or 4)
-        ctx->h2_legacy = strcmp(e, "r2") == 0;
-        ctx->attn_wide = strcmp(e, "r3") != 0 && !ctx->h2_legacy;
-        if (strcmp(e, "r2") == 0 || strcmp(e, "r3") == 0) ctx->gemm_chain = 0;
-#endif
+    if (const char* e = getenv("E2EMV_F16X2_KERNELS")) {  // r4: a launch per GEMM (the chain's A/B arm and the T = 5 path); other values: ignored
         if (strcmp(e, "r4") == 0) ctx->gemm_chain = 0;
     }
 
@@ -187,11 +179,11 @@ int e2emv_create(e2emv_ctx** out, int device) {
     // default arithmetic of the dense GNN contractions: the split-operand fp16 x 2 path (22-bit operands, fp32 accumulate;
     // every parity test runs in all three modes at the same bar); E2EMV_PRECISION=bf16x3 selects the 24-bit bf16 x 3
     // split, =f32 the exact fp32-MFMA kernels
-    ctx->precision = ctx->fuse_merge ? E2EMV_PRECISION_F16X2 : E2EMV_PRECISION_F32;
+    ctx->precision = E2EMV_PRECISION_F16X2;
     if (const char* e = getenv("E2EMV_PRECISION")) {
         ctx->precision = E2EMV_PRECISION_F32;
-        if (ctx->fuse_merge && strcmp(e, "bf16x3") == 0) ctx->precision = E2EMV_PRECISION_BF16X3;
-        if (ctx->fuse_merge && strcmp(e, "f16x2") == 0) ctx->precision = E2EMV_PRECISION_F16X2;
+        if (strcmp(e, "bf16x3") == 0) ctx->precision = E2EMV_PRECISION_BF16X3;
+        if (strcmp(e, "f16x2") == 0) ctx->precision = E2EMV_PRECISION_F16X2;
     }
     *out = ctx;
     return E2EMV_OK;
@@ -427,7 +419,7 @@ extern "C" int e2emv_commit_weights(e2emv_ctx* ctx, const e2emv_model_desc* m) {
     }
     // ---- GNN layers ----
     struct LOff {
-        size_t wqkv, bqkv, wm, bm, w0, b0, w1, b1;
+        size_t wqkv, bqkv, w0, b0, w1, b1;
         size_t w3qkv, w3m0, w3m1, whqkv, whm0, whm1, wpqkv, wpm0, wpm1;
         float hsqkv, hsm0, hsm1, baqkv, bam0, bam1;
     };
@@ -456,16 +448,14 @@ extern "C" int e2emv_commit_weights(e2emv_ctx* ctx, const e2emv_model_desc* m) {
         for (int o = 0; o < D; ++o)
             for (int h = 0; h < H; ++h)
                 for (int dd = 0; dd < d; ++dd) wm[(size_t)o * D + h * d + dd] = w[(size_t)o * D + dd * H + h];
-        loff[l].wm = pk.add(wm);
-        loff[l].bm = pk.add(b);
+        const std::vector<float> bmerge = b;
         if ((rc = get_conv(ctx, base + ".mlp.0", 2 * D, 2 * D, w, b))) return rc;
         if ((rc = fold_bn(ctx, base + ".mlp.1", 2 * D, 2 * D, w, b))) return rc;
-        if (ctx->fuse_merge) {
+        {
             // MLP0([x | merge(o)]) = W0x x + (W0m Wmerge) o + (b0 + W0m bmerge): the merge conv is
             // linear and feeds nothing else, so it is folded into MLP0's second K segment (fp64 on
             // the host).  Saves one GEMM (2 N D^2 flops) and one activation round trip per layer.
             std::vector<double> acc((size_t)2 * D * D, 0.0);
-            const float* bmerge = &pk.host[loff[l].bm];
             for (int o = 0; o < 2 * D; ++o) {
                 const float* w0m = &w[(size_t)o * 2 * D + D];
                 double* ao = &acc[(size_t)o * D];
@@ -579,8 +569,6 @@ extern "C" int e2emv_commit_weights(e2emv_ctx* ctx, const e2emv_model_desc* m) {
         LayerWeights& L = ctx->layers[l];
         L.w_qkv = base + loff[l].wqkv;
         L.b_qkv = base + loff[l].bqkv;
-        L.w_merge = base + loff[l].wm;
-        L.b_merge = base + loff[l].bm;
         L.w_mlp0 = base + loff[l].w0;
         L.b_mlp0 = base + loff[l].b0;
         L.w_mlp1 = base + loff[l].w1;
@@ -621,8 +609,6 @@ int e2emv_set_precision(e2emv_ctx* ctx, int precision) {
     E2EMV_LOCK(ctx);
     if (precision != E2EMV_PRECISION_F32 && precision != E2EMV_PRECISION_BF16X3 && precision != E2EMV_PRECISION_F16X2)
         return set_err(ctx, E2EMV_EINVAL, "unknown precision %d", precision);
-    if (precision != E2EMV_PRECISION_F32 && !ctx->fuse_merge)
-        return set_err(ctx, E2EMV_ESTATE, "bf16x3 needs the merge conv folded into MLP0 (unset E2EMV_NO_FUSE_MERGE)");
     ctx->precision = precision;
     return E2EMV_OK;
 }
@@ -659,15 +645,9 @@ int e2emv_set_f16x2_kernels(e2emv_ctx* ctx, int generation) {
     E2EMV_LOCK(ctx);
     const bool always = generation == 105;  // generation 5 with the GEMM chain on every shape that allows it (tests, A/B runs)
     if (always) generation = 5;
-    if (generation < 2 || generation > 5) return set_err(ctx, E2EMV_EINVAL, "f16x2 kernel generation %d (2 .. 5)", generation);
-#ifndef E2EMV_STAMPS
-    if (generation < 4)
-        return set_err(ctx, E2EMV_EINVAL, "f16x2 kernel generations 2 and 3 are A/B arms of the measurement build (tools/p2_stamps.py --build); this "
-                                          "library selects 5 (default), 105 or 4");
-#endif
-    ctx->h2_legacy = generation == 2;
-    ctx->attn_wide = generation >= 4;
-    ctx->gemm_chain = generation >= 5 ? (always ? 2 : 1) : 0;
+    if (generation != 4 && generation != 5)
+        return set_err(ctx, E2EMV_EINVAL, "f16x2 kernel generation %d: this library selects 5 (default), 105 or 4 (generations 2 and 3 are retired)", generation);
+    ctx->gemm_chain = generation == 5 ? (always ? 2 : 1) : 0;
     return E2EMV_OK;
 }
 

@@ -167,35 +167,28 @@ static int forward_joint(e2emv_ctx* ctx, const e2emv_forward_desc* fd, const flo
     // CU (a pair or two - the eval_pairs.py loop) run the fp32-MFMA kernels, whose 64 x 64 tile shape and key-split
     // attention are the latency-tuned forms.  Both arithmetic modes meet the same parity bar.
     const int64_t split_min = ctx->split_min_rows >= 0 ? ctx->split_min_rows : (int64_t)128 * (ctx->num_cus / 2);
-    const bool b3 = ctx->precision != E2EMV_PRECISION_F32 && ctx->fuse_merge && Mtot >= split_min;
+    const bool b3 = ctx->precision != E2EMV_PRECISION_F32 && Mtot >= split_min;
     const bool h2 = b3 && ctx->precision == E2EMV_PRECISION_F16X2;  // fp16 x 2 planes instead of bf16 x 3 (gemm_x3.hip)
     // f16x2 on PLANE activations (p2.h): every producer epilogue emits the two fp16 planes, consumers load them straight
-    // into LDS (gemm_p2.hip, attention_p2.hip); h2_legacy keeps the round-2 kernels (fp32 activations, split in the consumer)
+    // into LDS (gemm_p2.hip, attention_p2.hip)
     // (their operands are addressed with 32-bit byte offsets: the widest plane matrices, q | k and the hidden layer, are
-    // Mtot x 2D x 4 bytes - beyond 2 GB, 2^20 rows at D = 256, the call runs on the round-2 kernels)
-    const bool p2 = h2 && !ctx->h2_legacy && D == 256 && H == 4 && !ctx->layers.empty() && Mtot * 8 * D < ((int64_t)1 << 31);
-    // bf16x3 attention path: x as S3 planes (6D bytes/row) and V^T planes (6D bytes/row); the q|k planes
-    // (S3, 2D wide = 12D bytes/row) live in the fp32 q|k|v buffer, which has exactly that size
-    const size_t sz_x3 = b3 ? al((size_t)Mtot * 3 * D * 2) : 0;
+    // Mtot x 2D x 4 bytes - beyond 2 GB, 2^20 rows at D = 256, the call runs on the round-2 kernels: fp32 activations, split
+    // in the consumer)
+    const bool p2 = h2 && D == 256 && H == 4 && !ctx->layers.empty() && Mtot * 8 * D < ((int64_t)1 << 31);
     // tile exponents of the plane tensors (p2.h): one int per 64 rows x 64 columns of x (4), attention output (4), q|k (8),
     // V^T (4), hidden (8)
     const size_t sz_e = p2 ? al((size_t)(Mtot / 64) * 32 * sizeof(int)) : 0;  // + max |x| per block (4 floats)
-    const size_t need = sz_x * 3 + sz_qkv + sz_hid + sz_S + sz_sk + sz_match + sz_x3 + sz_e + 4096;
+    const size_t need = sz_x * 3 + sz_qkv + sz_hid + sz_S + sz_sk + sz_match + sz_e + 4096;
     int rc = ws_reserve(ctx, need);
     if (rc) return rc;
     char* w = ctx->d_ws;
     float* x = (float*)w; w += sz_x;
     float* att = (float*)w; w += sz_x;     // attention output, later mdesc
-    float* msg = (float*)w; w += sz_x;     // merge output, later conf gather / hidden
+    float* msg = (float*)w; w += sz_x;     // x as planes (f16x2 on planes), later conf gather / hidden
     float* qkv = (float*)w; w += sz_qkv;
     float* hid = (float*)w; w += sz_hid;
     float* S = (float*)w; w += sz_S;
     char* skws = w; w += sz_sk;
-    uint16_t* qk3 = nullptr; uint16_t* vt3 = nullptr;
-    if (b3) {
-        vt3 = (uint16_t*)w; w += sz_x3;
-        qk3 = (uint16_t*)qkv;
-    }
     int* e_x = (int*)w; w += sz_e;
     int* e_att = e_x + (Mtot / 64) * 4;
     int* e_qk = e_att + (Mtot / 64) * 4;
@@ -348,29 +341,15 @@ static int forward_joint(e2emv_ctx* ctx, const e2emv_forward_desc* fd, const flo
         }
         if (b3) {
             // q|k|v on the split-operand GEMM with a plain fp32 output; the attention kernel splits Q / K / V^T into
-            // bf16 planes on the way in (E2EMV_B3_PLANES=1 selects the first-generation hand-over: fp32-pipe GEMM whose
-            // epilogue emits the planes, 3.2x the bytes)
-            if (h2 || !ctx->b3_planes) {
-                g = GemmArgs();
-                g.M = (int)Mtot; g.N = 3 * D; g.K = D; g.K1 = D; g.A = x; g.lda = D; g.bias = L.b_qkv; g.C = qkv; g.ldc = 3 * D;
-                prof_begin(ctx, PS_GEMM, s); rc = h2 ? launch_gemm_x3(ctx, g, L.wh_qkv, D, s, L.hs_qkv) : launch_gemm_x3(ctx, g, L.w3_qkv, D, s); prof_end(ctx, s);
-                if (rc) return rc;
-                prof_begin(ctx, PS_ATTN, s);
-                rc = launch_attention3f(ctx, B, T, n_rows, Nt, D, H, qkv, L.type, att, s, h2);
-                prof_end(ctx, s);
-                if (rc) return rc;
-            } else {
+            // planes on the way in
             g = GemmArgs();
-            g.M = (int)Mtot; g.N = 3 * D; g.K = D; g.K1 = D; g.A = x; g.lda = D; g.W = L.w_qkv; g.ldw = D; g.bias = L.b_qkv;
-            g.C3 = qk3; g.ldc3 = 2 * D; g.Vt = vt3; g.vt_n0 = 2 * D; g.n_rows = n_rows;
-            g.q_cols = D; g.q_scale = 0.125f * 1.4426950408889634f;
-            prof_begin(ctx, PS_GEMM, s); rc = launch_gemm_nt(ctx, g, s); prof_end(ctx, s);
+            g.M = (int)Mtot; g.N = 3 * D; g.K = D; g.K1 = D; g.A = x; g.lda = D; g.bias = L.b_qkv; g.C = qkv; g.ldc = 3 * D;
+            prof_begin(ctx, PS_GEMM, s); rc = h2 ? launch_gemm_x3(ctx, g, L.wh_qkv, D, s, L.hs_qkv) : launch_gemm_x3(ctx, g, L.w3_qkv, D, s); prof_end(ctx, s);
             if (rc) return rc;
             prof_begin(ctx, PS_ATTN, s);
-            rc = launch_attention3(ctx, B, T, n_rows, Nt, D, H, qk3, vt3, L.type, nullptr, att, s);
+            rc = launch_attention3f(ctx, B, T, n_rows, Nt, D, H, qkv, L.type, att, s, h2);
             prof_end(ctx, s);
             if (rc) return rc;
-            }
         } else {
         // q|k|v = x Wqkv^T + b
         g = GemmArgs();
@@ -383,19 +362,10 @@ static int forward_joint(e2emv_ctx* ctx, const e2emv_forward_desc* fd, const flo
         prof_end(ctx, s);
         if (rc) return rc;
         }
-        const float* second = att;  // MLP0's second K segment: attention output (merge folded into W0)
-        if (!ctx->fuse_merge) {
-            // message = merge(attention)
-            g = GemmArgs();
-            g.M = (int)Mtot; g.N = D; g.K = D; g.K1 = D; g.A = att; g.lda = D; g.W = L.w_merge; g.ldw = D; g.bias = L.b_merge;
-            g.C = msg; g.ldc = D;
-            prof_begin(ctx, PS_GEMM, s); rc = launch_gemm_nt(ctx, g, s); prof_end(ctx, s);
-            if (rc) return rc;
-            second = msg;
-        }
-        // hidden = relu(BN(W0 [x | message] + b0))   (concat never materialised: two K segments)
+        // hidden = relu(BN(W0 [x | message] + b0))   (concat never materialised: two K segments; the second is the attention
+        // output, the merge conv folded into W0)
         g = GemmArgs();
-        g.M = (int)Mtot; g.N = 2 * D; g.K = 2 * D; g.K1 = D; g.A = x; g.lda = D; g.A2 = second; g.lda2 = D;
+        g.M = (int)Mtot; g.N = 2 * D; g.K = 2 * D; g.K1 = D; g.A = x; g.lda = D; g.A2 = att; g.lda2 = D;
         g.W = L.w_mlp0; g.ldw = 2 * D; g.bias = L.b_mlp0; g.relu = true; g.C = hid; g.ldc = 2 * D;
         // bf16x3 mode: the two MLP GEMMs (2/3 of the layer's GEMM flops) run on the bf16 pipe with split operands
         prof_begin(ctx, PS_GEMM, s);

@@ -35,9 +35,8 @@ namespace e2emv {
 
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
 
-constexpr int BM = 128, BN = 128;  // BK (K tile, 32 or 64) is a template parameter; LDS rows are BK + 4 floats
+constexpr int BM = 128, BN = 128, BK = 32;  // LDS rows are BK + 4 floats
 
 struct GemmParams {
     const float* A;
@@ -46,12 +45,6 @@ struct GemmParams {
     const float* bias;
     const float* R;
     float* C;
-    uint16_t* C3;   // optional output as bf16x3 planes, S3 [M][3][ldc3] (batch 1 only); C may then be null
-    int64_t ldc3;
-    uint16_t* Vt;   // optional: columns n >= vt_n0 are written TRANSPOSED as bf16x3 planes [img][3][N - vt_n0][n_rows]
-    int vt_n0, n_rows;
-    int q_cols;     // columns n < q_cols are multiplied by q_scale (attention query pre-scale)
-    float q_scale;
     int64_t lda, lda2, ldw, ldr, ldc;
     int64_t sA, sA2, sW, sR, sC;
     int M, N, K, K1;
@@ -73,23 +66,20 @@ struct GemmParams {
 // tiles of consecutive output tiles form ONE software-pipelined stream: the first K tile of
 // the next output tile is prefetched under the last MFMAs of the current one and the
 // epilogue's stores drain under the next tile's MFMAs - no lockstep load/store bursts.
-// EXT = true adds the bf16x3-plane outputs (C3, V^T with swapped operand roles, q pre-scale) used by the
-// q|k|v GEMM of the split-operand attention path; it gets a 256-VGPR budget (2 workgroups/CU) so that the
-// plain kernel (EXT = false, every other GEMM) keeps its spill-free 168-VGPR / 3-workgroups-per-CU build.
 // TN = 2: 128 x 128 output tile, waves 2 x 2 (the default).  TN = 1: 256 x 64 tile, waves 4 x 1 - for outputs only 64
 // channels wide (SuperPoint's conv1b / conv2a / conv2b), where half of a 128-wide tile would multiply padding.
-template <bool EXT, int BK, int DBG = 0, bool CONV = false, int TN = 2>
+template <bool CONV = false, int TN = 2>
 // TN = 0: 64 x 64 tile, waves 2 x 2 of ONE 32 x 32 MFMA tile each - the latency shape for small problems (batch 1-4 of the
 // reference's eval loop): a tile's K loop is 4x shorter and a 2048-row GEMM fills 256 workgroups instead of 64.
-__global__ __launch_bounds__(256, (EXT || BK == 64 || TN == 1) ? 2 : 3) void gemm_nt_kernel(GemmParams p) {
+__global__ __launch_bounds__(256, TN == 1 ? 2 : 3) void gemm_nt_kernel(GemmParams p) {
     constexpr int BM = TN == 2 ? 128 : (TN == 1 ? 256 : 64), BN = TN == 2 ? 128 : 64;  // shadow the namespace-scope defaults
     constexpr int WT = TN == 0 ? 1 : 2;   // 32 x 32 MFMA tiles per wave and dimension
     constexpr int WS = 32 * WT;           // rows / columns of the output tile one wave owns
-    constexpr int LDK = BK + 4;           // 36: 36*i mod 64, 68: 4*i mod 64 - both give 16 distinct 16-byte slots
+    constexpr int LDK = BK + 4;           // 36: 36*i mod 64 gives 16 distinct 16-byte slots
     constexpr int CPR = BK / 4;           // 16-byte chunks per tile row
-    constexpr int NCH = BM * CPR / 256;   // chunks per thread of the activation tile (4 or 8)
+    constexpr int NCH = BM * CPR / 256;   // chunks per thread of the activation tile
     constexpr int NCHB = BN * CPR / 256;  // chunks per thread of the weight tile
-    constexpr int RSTEP = 256 / CPR;      // rows covered by one pass of the 256 threads (32 or 16)
+    constexpr int RSTEP = 256 / CPR;      // rows covered by one pass of the 256 threads
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* As = smem;                       // [BM][BK + 4]  activations
     float* Bs = smem + BM * (BK + 4);       // [BN][BK + 4]  weights
@@ -189,84 +179,27 @@ __global__ __launch_bounds__(256, (EXT || BK == 64 || TN == 1) ? 2 : 3) void gem
 #pragma unroll
                 for (int r = 0; r < 16; ++r) acc[j][i][r] = 0.f;
     };
-    // SWAP = false: weights are the MFMA A operand (rows -> registers), activations B (rows -> lanes);
-    // SWAP = true : roles exchanged (lane = output channel, registers = runs of 4 rows) for V^T tiles
-    auto compute = [&](auto swap_tag) {
-        constexpr bool SWAP = decltype(swap_tag)::value;
+    auto compute = [&]() {
         const float* as = &As[(wr * WS + l31) * LDK + lh * 4];
         const float* bs = &Bs[(wc * WS + l31) * LDK + lh * 4];
-        if (DBG & 1) __builtin_amdgcn_s_setprio(1);
 #pragma unroll
         for (int c = 0; c < BK / 8; ++c) {
             const f32x4 x0 = *reinterpret_cast<const f32x4*>(as + c * 8);
             const f32x4 w0 = *reinterpret_cast<const f32x4*>(bs + c * 8);
             if constexpr (WT == 1) {
 #pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    acc[0][0] = SWAP ? __builtin_amdgcn_mfma_f32_32x32x2f32(x0[e], w0[e], acc[0][0], 0, 0, 0)
-                                     : __builtin_amdgcn_mfma_f32_32x32x2f32(w0[e], x0[e], acc[0][0], 0, 0, 0);
+                for (int e = 0; e < 4; ++e) acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(w0[e], x0[e], acc[0][0], 0, 0, 0);
             } else {
             const f32x4 x1 = *reinterpret_cast<const f32x4*>(as + 32 * LDK + c * 8);
             const f32x4 w1 = *reinterpret_cast<const f32x4*>(bs + 32 * LDK + c * 8);
-            if (DBG & 2) {  // profiling: operand pipeline only (global -> LDS -> registers), no matrix-core work
-#pragma unroll
-                for (int e = 0; e < 4; ++e) acc[0][0][e] += x0[e] + x1[e] + w0[e] + w1[e];
-                continue;
-            }
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                if (SWAP) {
-                    acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(x0[e], w0[e], acc[0][0], 0, 0, 0);
-                    acc[0][WT - 1] = __builtin_amdgcn_mfma_f32_32x32x2f32(x1[e], w0[e], acc[0][WT - 1], 0, 0, 0);
-                    acc[WT - 1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(x0[e], w1[e], acc[WT - 1][0], 0, 0, 0);
-                    acc[WT - 1][WT - 1] = __builtin_amdgcn_mfma_f32_32x32x2f32(x1[e], w1[e], acc[WT - 1][WT - 1], 0, 0, 0);
-                } else {
-                    acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(w0[e], x0[e], acc[0][0], 0, 0, 0);
-                    acc[0][WT - 1] = __builtin_amdgcn_mfma_f32_32x32x2f32(w0[e], x1[e], acc[0][WT - 1], 0, 0, 0);
-                    acc[WT - 1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(w1[e], x0[e], acc[WT - 1][0], 0, 0, 0);
-                    acc[WT - 1][WT - 1] = __builtin_amdgcn_mfma_f32_32x32x2f32(w1[e], x1[e], acc[WT - 1][WT - 1], 0, 0, 0);
-                }
+                acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(w0[e], x0[e], acc[0][0], 0, 0, 0);
+                acc[0][WT - 1] = __builtin_amdgcn_mfma_f32_32x32x2f32(w0[e], x1[e], acc[0][WT - 1], 0, 0, 0);
+                acc[WT - 1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(w1[e], x0[e], acc[WT - 1][0], 0, 0, 0);
+                acc[WT - 1][WT - 1] = __builtin_amdgcn_mfma_f32_32x32x2f32(w1[e], x1[e], acc[WT - 1][WT - 1], 0, 0, 0);
             }
             }
-        }
-        if (DBG & 1) __builtin_amdgcn_s_setprio(0);
-    };
-    auto split4 = [&](const f32x4& v, bf16x4& h0, bf16x4& h1, bf16x4& h2) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const __bf16 a = (__bf16)v[e];
-            const float r1 = v[e] - (float)a;
-            const __bf16 b2 = (__bf16)r1;
-            h0[e] = a; h1[e] = b2; h2[e] = (__bf16)(r1 - (float)b2);
-        }
-    };
-    // V^T tiles (SWAP accumulators): lane = channel n, registers = 4 consecutive rows m -> 8-byte stores along the keys
-    auto epilogue_vt = [&](int t) {
-        const int r = t % tiles_mn;
-        const int tm = r / p.tiles_n, tn = r - tm * p.tiles_n;
-        const int nv = p.N - p.vt_n0;
-#pragma unroll
-        for (int j = 0; j < WT; ++j) {
-            const int n = tn * BN + wc * WS + j * 32 + l31;
-            if (n >= p.N) continue;
-            const float bv = p.bias ? p.bias[n] : 0.f;
-#pragma unroll
-            for (int i = 0; i < WT; ++i)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const int m = tm * BM + wr * WS + i * 32 + 8 * g + 4 * lh;
-                    if (m >= p.M) continue;
-                    const int img = m / p.n_rows, ml = m - img * p.n_rows;
-                    f32x4 v;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = acc[j][i][4 * g + e] * p.scale + bv;
-                    bf16x4 h0, h1, h2;
-                    split4(v, h0, h1, h2);
-                    uint16_t* dst = p.Vt + ((int64_t)(img * 3) * nv + (n - p.vt_n0)) * p.n_rows + ml;
-                    *reinterpret_cast<bf16x4*>(dst) = h0;
-                    *reinterpret_cast<bf16x4*>(dst + (int64_t)nv * p.n_rows) = h1;
-                    *reinterpret_cast<bf16x4*>(dst + 2 * (int64_t)nv * p.n_rows) = h2;
-                }
         }
     };
     auto epilogue = [&](int t) {
@@ -294,7 +227,6 @@ __global__ __launch_bounds__(256, (EXT || BK == 64 || TN == 1) ? 2 : 3) void gem
                             for (int e = 0; e < 4; ++e) v[e] = relu_nan(v[e]);
                         }
                         if (R) v += *reinterpret_cast<const f32x4*>(R + (int64_t)m * p.ldr + n);
-                        if (EXT && n < p.q_cols) v *= p.q_scale;
                         if (CONV && p.conv_pool) {  // lanes 4q..4q+3 hold the 2x2 block of pooled pixel m/4
 #pragma unroll
                             for (int e = 0; e < 4; ++e) {
@@ -304,15 +236,7 @@ __global__ __launch_bounds__(256, (EXT || BK == 64 || TN == 1) ? 2 : 3) void gem
                             if ((lane & 3) == 0) *reinterpret_cast<f32x4*>(C + (int64_t)(m >> 2) * p.ldc + n) = v;
                             continue;
                         }
-                        if (!EXT || p.C) *reinterpret_cast<f32x4*>(C + (int64_t)m * p.ldc + n) = v;
-                        if (EXT && p.C3) {  // bf16x3 planes for the split-operand attention (attention3.hip)
-                            bf16x4 h0, h1, h2;
-                            split4(v, h0, h1, h2);
-                            uint16_t* d3 = p.C3 + (int64_t)m * 3 * p.ldc3 + n;
-                            *reinterpret_cast<bf16x4*>(d3) = h0;
-                            *reinterpret_cast<bf16x4*>(d3 + p.ldc3) = h1;
-                            *reinterpret_cast<bf16x4*>(d3 + 2 * p.ldc3) = h2;
-                        }
+                        *reinterpret_cast<f32x4*>(C + (int64_t)m * p.ldc + n) = v;
                     } else {
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
@@ -336,7 +260,6 @@ __global__ __launch_bounds__(256, (EXT || BK == 64 || TN == 1) ? 2 : 3) void gem
     setup(tile);
     gload(0);
     for (;;) {
-        const bool vt = EXT && ((tile % tiles_mn) % p.tiles_n) * BN >= p.vt_n0;  // workgroup-uniform
         for (int kt = 0; kt + 1 < nk; ++kt) {
             __syncthreads();  // previous K tile fully consumed
             lstore(0);
@@ -346,7 +269,7 @@ __global__ __launch_bounds__(256, (EXT || BK == 64 || TN == 1) ? 2 : 3) void gem
             // the LDS fragments).  Pinning them above with sched_barrier(0) was measured 8-13 % SLOWER
             // (K=2048: 563 -> 645 us): with 3 waves/SIMD the latency is covered by the other waves and
             // the early loads only lengthen the live ranges.  Left to the compiler on purpose.
-            if (EXT && vt) compute(std::true_type{}); else compute(std::false_type{});
+            compute();
         }
         // last K tile of this output tile: prefetch the next output tile's first K tile under it
         const int next = tile + slots;
@@ -358,8 +281,8 @@ __global__ __launch_bounds__(256, (EXT || BK == 64 || TN == 1) ? 2 : 3) void gem
             setup(next);
             gload(0);
         }
-        if (EXT && vt) compute(std::true_type{}); else compute(std::false_type{});
-        if (EXT && vt) epilogue_vt(tile); else epilogue(tile);
+        compute();
+        epilogue(tile);
         if (!more) break;
         zero_acc();
         tile = next;
@@ -373,74 +296,47 @@ int launch_gemm_nt(e2emv_ctx* ctx, const GemmArgs& a, hipStream_t s) {
         return set_err(ctx, E2EMV_ESHAPE, "gemm: K=%d K1=%d must be multiples of 32", a.K, K1);
     GemmParams p;
     p.A = a.A; p.A2 = a.A2; p.W = a.W; p.bias = a.bias; p.R = a.R; p.C = a.C;
-    p.C3 = a.C3; p.ldc3 = a.ldc3;
-    p.Vt = a.Vt; p.vt_n0 = a.Vt ? a.vt_n0 : (1 << 30); p.n_rows = a.n_rows > 0 ? a.n_rows : a.M;
-    p.q_cols = a.q_cols; p.q_scale = a.q_scale;
-    if (!a.C && !a.C3) return set_err(ctx, E2EMV_EINVAL, "gemm: no output");
-    if (a.Vt && (a.vt_n0 % BN || p.n_rows % 128 || a.M % p.n_rows || a.batch != 1))
-        return set_err(ctx, E2EMV_ESHAPE, "gemm: V^T output needs vt_n0 %% 128 == 0, whole images and batch 1");
+    if (!a.C) return set_err(ctx, E2EMV_EINVAL, "gemm: no output");
     p.lda = a.lda; p.lda2 = a.lda2; p.ldw = a.ldw; p.ldr = a.ldr; p.ldc = a.ldc;
     p.sA = a.sA; p.sA2 = a.sA2; p.sW = a.sW; p.sR = a.sR; p.sC = a.sC;
     p.M = a.M; p.N = a.N; p.K = a.K; p.K1 = K1;
     p.conv_h = a.conv_h; p.conv_w = a.conv_w; p.conv_c = a.conv_c; p.conv_pool = a.conv_pool ? 1 : 0;
     const bool conv = a.conv_c > 0;
     if (conv && (a.conv_h > 32767 || a.conv_w > 32767 || a.conv_c % 32 || a.K != 9 * a.conv_c || a.A2 || a.batch != 1 || a.conv_h <= 0 || a.conv_w <= 0 ||
-                 a.M % (a.conv_h * a.conv_w) || a.lda != a.conv_c || a.C3 || a.Vt || a.q_cols > 0))
+                 a.M % (a.conv_h * a.conv_w) || a.lda != a.conv_c))
         return set_err(ctx, E2EMV_ESHAPE, "gemm: conv mode needs NHWC input with C %% 32 == 0, K = 9 C, whole images, batch 1");
     if (a.conv_pool && (!conv || a.conv_h % 2 || a.conv_w % 2 || a.N % 4 || a.R))
         return set_err(ctx, E2EMV_ESHAPE, "gemm: fused 2x2 max-pool needs conv mode, even image sides and N %% 4 == 0");
     // 64-channel-wide outputs: the 256 x 64 tile variant (conv mode only - the matcher never has N <= 64 at scale)
     const bool narrow = a.conv_c > 0 && a.N <= 64;
     // latency shape: when 128 x 128 tiles would leave most CUs idle (batch 1-4 of the reference's eval loop), 64 x 64 tiles
-    // make 4x more, 4x shorter work items (E2EMV_GEMM_SMALL=0 disables)
-    static int small_env = -1;
-    if (small_env < 0) small_env = dbg_knob("E2EMV_GEMM_SMALL", 1);
-    const bool plain = a.conv_c == 0 && !a.C3 && !a.Vt && a.q_cols == 0;
+    // make 4x more, 4x shorter work items
     const int64_t tiles128 = (int64_t)a.batch * ((a.M + 127) / 128) * ((a.N + 127) / 128);
-    const bool small = small_env && plain && tiles128 * 2 <= ctx->num_cus;
+    const bool small = a.conv_c == 0 && tiles128 * 2 <= ctx->num_cus;
     const int bm = narrow ? 256 : (small ? 64 : BM), bn = (narrow || small) ? 64 : BN;
     p.tiles_m = (a.M + bm - 1) / bm;
     p.tiles_n = (a.N + bn - 1) / bn;
     p.total = p.tiles_m * p.tiles_n * a.batch;
     p.scale = a.scale;
     p.relu = a.relu ? 1 : 0;
-    p.vec_store = (a.N % 4 == 0) && (!a.C || ((a.ldc % 4 == 0) && ((uintptr_t)a.C % 16 == 0) && (a.sC % 4 == 0))) &&
+    p.vec_store = (a.N % 4 == 0) && (a.ldc % 4 == 0) && ((uintptr_t)a.C % 16 == 0) && (a.sC % 4 == 0) &&
                   (!a.bias || (uintptr_t)a.bias % 16 == 0) &&
                   (!a.R || ((a.ldr % 4 == 0) && ((uintptr_t)a.R % 16 == 0) && (a.sR % 4 == 0)));
-    if ((p.C3 || a.Vt) && (!p.vec_store || a.batch != 1 || (p.C3 && a.ldc3 % 4)))
-        return set_err(ctx, E2EMV_ESHAPE, "gemm: the bf16x3 side output needs the vector epilogue and batch 1");
     const int per_xcd = (p.total + 7) / 8;
-    static int dbg = -1, wg = -1, bk_env = -1;  // profiling knobs: E2EMV_GEMM_DEBUG (bit0: s_setprio), _WG_PER_CU, _BK
-    if (dbg < 0) dbg = dbg_knob("E2EMV_GEMM_DEBUG", 0);
-    if (wg < 0) wg = dbg_knob("E2EMV_GEMM_WG_PER_CU", 0);
-    if (bk_env < 0) bk_env = dbg_knob("E2EMV_GEMM_BK", 0);
-    const bool ext = p.C3 || a.Vt || a.q_cols > 0;
     // K tile: 32.  A 64-deep tile (half the barrier / staging episodes per MFMA, 2 workgroups per CU) was measured
     // 1-5 % SLOWER at every shape; so were 1 or 2 workgroups per CU and s_setprio around the MFMA block: the main
-    // loop sits at ~125 TFLOP/s (MFMA pipe ~82 % busy at ~2.3 GHz) whatever the schedule.  E2EMV_GEMM_BK=64 keeps
-    // the variant reachable for profiling.
-    int bk = 32;
-    if (bk_env == 64 && a.K % 64 == 0 && K1 % 64 == 0 && !ext && !conv) bk = 64;
-    const int per_cu = wg > 0 ? wg : ((ext || bk == 64 || narrow) ? 2 : 3);
+    // loop sits at ~125 TFLOP/s (MFMA pipe ~82 % busy at ~2.3 GHz) whatever the schedule.
+    const int per_cu = narrow ? 2 : 3;
     const int sl = std::min(per_xcd, std::max(1, ctx->num_cus * per_cu / 8));
-    const size_t lds = sizeof(float) * (bm + bn) * (bk + 4);
+    const size_t lds = sizeof(float) * (bm + bn) * (BK + 4);
     if (small) {
-        hipLaunchKernelGGL((gemm_nt_kernel<false, 32, 0, false, 0>), dim3(8 * sl), dim3(256), lds, s, p);
+        hipLaunchKernelGGL((gemm_nt_kernel<false, 0>), dim3(8 * sl), dim3(256), lds, s, p);
     } else if (conv && narrow) {
-        hipLaunchKernelGGL((gemm_nt_kernel<false, 32, 0, true, 1>), dim3(8 * sl), dim3(256), lds, s, p);
+        hipLaunchKernelGGL((gemm_nt_kernel<true, 1>), dim3(8 * sl), dim3(256), lds, s, p);
     } else if (conv) {
-        hipLaunchKernelGGL((gemm_nt_kernel<false, 32, 0, true>), dim3(8 * sl), dim3(256), lds, s, p);
-    } else if (bk == 64) {
-        if (int rc = ensure_dynamic_lds(ctx, (const void*)gemm_nt_kernel<false, 64, 0>, lds)) return rc;
-        hipLaunchKernelGGL((gemm_nt_kernel<false, 64, 0>), dim3(8 * sl), dim3(256), lds, s, p);
-    } else if (ext) {
-        hipLaunchKernelGGL((gemm_nt_kernel<true, 32, 0>), dim3(8 * sl), dim3(256), lds, s, p);
-    } else if (dbg & 2) {
-        hipLaunchKernelGGL((gemm_nt_kernel<false, 32, 2>), dim3(8 * sl), dim3(256), lds, s, p);
-    } else if (dbg & 1) {
-        hipLaunchKernelGGL((gemm_nt_kernel<false, 32, 1>), dim3(8 * sl), dim3(256), lds, s, p);
+        hipLaunchKernelGGL((gemm_nt_kernel<true>), dim3(8 * sl), dim3(256), lds, s, p);
     } else {
-        hipLaunchKernelGGL((gemm_nt_kernel<false, 32, 0>), dim3(8 * sl), dim3(256), lds, s, p);
+        hipLaunchKernelGGL((gemm_nt_kernel<false>), dim3(8 * sl), dim3(256), lds, s, p);
     }
     E2EMV_CHECK_LAUNCH(ctx, "gemm_nt_kernel");
     return E2EMV_OK;

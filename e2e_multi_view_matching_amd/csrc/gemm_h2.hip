@@ -23,10 +23,8 @@
 //   * one workgroup per CU (2 waves per SIMD), persistent over an XCD-contiguous range of tiles ordered N-fastest, so
 //     the column tiles that share an A row block run back to back on one XCD's L2.
 #include <algorithm>
-#include <cstdio>
 #include <cstdlib>
 #include <type_traits>
-#include <vector>
 
 #include "common.h"
 
@@ -56,10 +54,9 @@ struct GemmH2Params {
     int tiles_n, total;
     int relu;
     float out_scale;  // 2^-s
-    long long* dbg;   // E2EMV_X3_DEBUG=8: phase timestamps of two workgroups
 };
 
-template <int DBG, int NJ>
+template <int NJ>
 __global__ __launch_bounds__(512, 1) void gemm_h2_kernel(GemmH2Params p) {
     extern __shared__ __attribute__((aligned(16))) uint16_t smem_h2[];
     constexpr int H2_BN = 64 * NJ, H2_WPLANE = H2_BN * H2_LD, H2_BUF = 2 * H2_APLANE + 2 * H2_WPLANE;
@@ -120,7 +117,6 @@ __global__ __launch_bounds__(512, 1) void gemm_h2_kernel(GemmH2Params p) {
     // move the load position one K step on; past the last step of the last tile it stays put (the loads then re-fetch
     // that step, harmlessly, and nothing stores them)
     auto advance = [&]() {
-        if ((DBG & 2)) return;  // (profiling: keep re-loading the first K tile - L2 hits only)
         if (ld_kt + 1 < nk) { ++ld_kt; return; }
         if (ld_tile + slots < t_end) {
             asm volatile("" ::: "memory");  // keeps this a (uniform) branch: if-converted, setup's ~30 VALU ran in every K step
@@ -192,10 +188,6 @@ __global__ __launch_bounds__(512, 1) void gemm_h2_kernel(GemmH2Params p) {
 #pragma unroll
                 for (int pl = 0; pl < 2; ++pl) w[pl] = *reinterpret_cast<const h2_f16x8*>(bs + pl * H2_WPLANE + j * 32 * H2_LD + ks * 16);
                 w[2] = w[0] * (_Float16)(1.f / 2048.f);  // 2^-11 w_hi: exact (w_hi is >= 2^-3 wherever it matters)
-                if (DBG & 1) {  // profiling: operand pipeline only
-                    acc[j][0][ks] += (float)x[0][0][0] + (float)x[0][1][0] + (float)x[1][0][0] + (float)x[1][1][0] + (float)w[0][0] + (float)w[1][0];
-                    continue;
-                }
                 constexpr int PW[3] = {1, 2, 0}, PX[3] = {0, 1, 0};  // x_hi w_lo, x_lo' (2^-11 w_hi), x_hi w_hi
 #pragma unroll
                 for (int q = 0; q < 3; ++q)
@@ -260,7 +252,7 @@ __global__ __launch_bounds__(512, 1) void gemm_h2_kernel(GemmH2Params p) {
     };
 
     // pipeline: step g = (tile, kt) in execution order; LDS buffer g & 1 holds step g while registers hold step g + 1.
-    // One barrier per step.  Two alternatives were measured and dropped (s_memtime stamps, E2EMV_X3_DEBUG=8):
+    // One barrier per step.  Two alternatives were measured and dropped (s_memtime stamps):
     //   * the two waves of a SIMD in opposite phase (one splits/stores/loads while the other issues MFMAs, barrier per half
     //     step): 166 us against 142 us at (65536 x 512 x 512) - the MFMA phase of a wave stretches from 1000 to 1500 cycles
     //     and the split phase from 650 to 900-1800 when they run side by side, i.e. the SIMD does not overlap them;
@@ -268,7 +260,6 @@ __global__ __launch_bounds__(512, 1) void gemm_h2_kernel(GemmH2Params p) {
     //     for this block.
     // A step costs ~3600 cycles against 2 x 768 of matrix-pipe time per SIMD: issuing the 6 global loads alone stalls
     // 200-1000 cycles (the L2 -> CU path is saturated at ~8 TB/s, 14 B/clk/CU), the split + LDS stores take 450-850.
-    if (DBG & 1) zero_acc();
     setup(tile);
     gload();      // step 0
     advance();
@@ -276,39 +267,23 @@ __global__ __launch_bounds__(512, 1) void gemm_h2_kernel(GemmH2Params p) {
     gload();      // step 1
     advance();
     __syncthreads();
-    int buf = 0, dbg_n = 0;
+    int buf = 0;
     // one K step; FIRST = first step of an output tile (accumulators start from the MFMA's zero C operand).  The first step
     // is peeled out of the K loop so that each copy of the body keeps the register footprint of a single one.
     auto step = [&](auto FIRST) {
-        long long t0 = 0, t1 = 0, t2 = 0, t3 = 0;
-        if (DBG & 8) t0 = clock64();
         if constexpr (DB) {
             lstore(buf ^ 1);  // step g + 1 into the other buffer (its readers passed the barrier of step g - 1)
-            if (DBG & 8) t1 = clock64();
             gload();          // step g + 2
-            if (DBG & 8) t2 = clock64();
             compute(buf, FIRST);
-            if (DBG & 8) t3 = clock64();
             advance();
             __syncthreads();
         } else {
             compute(0, FIRST);
-            if (DBG & 8) t1 = clock64();
             __syncthreads();  // every wave is done reading step g
             lstore(0);        // step g + 1 (after the last step: stale registers nobody reads)
-            if (DBG & 8) t2 = clock64();
             gload();          // step g + 2
-            if (DBG & 8) t3 = clock64();
             advance();
             __syncthreads();
-        }
-        if (DBG & 8) {
-            const long long t4 = clock64();
-            if (p.dbg && lane == 0 && dbg_n < 48 && (blockIdx.x == 0 || blockIdx.x == 101)) {
-                long long* o = p.dbg + ((blockIdx.x ? 1 : 0) * 8 + wave) * 48 * 5 + dbg_n * 5;
-                o[0] = t0; o[1] = t1; o[2] = t2; o[3] = t3; o[4] = t4;
-                ++dbg_n;
-            }
         }
         if constexpr (DB) buf ^= 1;
     };
@@ -319,7 +294,6 @@ __global__ __launch_bounds__(512, 1) void gemm_h2_kernel(GemmH2Params p) {
         tile += slots;
         if (tile >= t_end) break;
         if constexpr (DB) __syncthreads();  // the slabs live in the buffer the next step's lstore fills
-        if (DBG & 1) zero_acc();
     }
 }
 
@@ -337,64 +311,23 @@ int launch_gemm_h2(e2emv_ctx* ctx, const GemmArgs& a, const uint16_t* WH, int64_
     p.lda = (unsigned)a.lda; p.lda2 = (unsigned)(a.A2 ? a.lda2 : a.lda); p.ldw = (unsigned)ldw; p.ldr = a.ldr; p.ldc = a.ldc;
     p.M = a.M; p.N = a.N; p.K = a.K; p.K1 = K1;
     // tile shape: 256 x 256 when N fills it (per MAC 4/256 + 4/256 B cross L2 instead of 4/128 + 4/256), else 256 x 128
-    static int nj_env = -1;  // E2EMV_H2_NJ=2|4 forces a shape
-    static int dbg = -1;     // profiling knob E2EMV_X3_DEBUG: 1 no MFMA, 2 L2-resident operands only, 8 phase timestamps
-    if (nj_env < 0) nj_env = dbg_knob("E2EMV_H2_NJ", 0);
-    if (dbg < 0) dbg = dbg_knob("E2EMV_X3_DEBUG", 0);
-    const int nj = nj_env == 2 || nj_env == 4 ? nj_env : (a.N % 256 == 0 ? 4 : 2);
+    const int nj = a.N % 256 == 0 ? 4 : 2;
     const int bn = 64 * nj;
     const int tiles_m = (a.M + H2_BM - 1) / H2_BM;
     p.tiles_n = (a.N + bn - 1) / bn;
     p.total = tiles_m * p.tiles_n;
     p.relu = a.relu ? 1 : 0;
     p.out_scale = out_scale;
-    p.dbg = nullptr;
     const int per_xcd = (p.total + 7) / 8;
     const int sl = std::min(per_xcd, std::max(1, ctx->num_cus / 8));
     // NJ = 2: two tile buffers (the idle one carries the epilogue slabs); NJ = 4: one tile buffer + 8 slabs of 32 x 68 floats
     const size_t lds = nj == 2 ? sizeof(uint16_t) * 2 * (2 * H2_APLANE + 2 * bn * H2_LD)
                                : sizeof(uint16_t) * (2 * H2_APLANE + 2 * bn * H2_LD) + sizeof(float) * 8 * 32 * 68;
-    const void* fn = nullptr;
-    switch (dbg * 10 + nj) {
-        case 12: fn = reinterpret_cast<const void*>(gemm_h2_kernel<1, 2>); break;
-        case 14: fn = reinterpret_cast<const void*>(gemm_h2_kernel<1, 4>); break;
-        case 22: fn = reinterpret_cast<const void*>(gemm_h2_kernel<2, 2>); break;
-        case 24: fn = reinterpret_cast<const void*>(gemm_h2_kernel<2, 4>); break;
-        case 82: fn = reinterpret_cast<const void*>(gemm_h2_kernel<8, 2>); break;
-        case 84: fn = reinterpret_cast<const void*>(gemm_h2_kernel<8, 4>); break;
-        default: fn = nj == 2 ? reinterpret_cast<const void*>(gemm_h2_kernel<0, 2>) : reinterpret_cast<const void*>(gemm_h2_kernel<0, 4>);
-    }
+    const void* fn = nj == 2 ? reinterpret_cast<const void*>(gemm_h2_kernel<2>) : reinterpret_cast<const void*>(gemm_h2_kernel<4>);
     if (int rc = ensure_dynamic_lds(ctx, fn, lds)) return rc;
-    long long* d_dbg = nullptr;
-    const size_t nb = sizeof(long long) * 2 * 8 * 48 * 5;
-    if (dbg == 8) {  // phase timestamps of workgroups 0 and 101, printed after the launch (host-synchronising; profiling only)
-        static long long* d_buf = nullptr;
-        if (!d_buf) E2EMV_HIP(ctx, hipMalloc((void**)&d_buf, nb));
-        d_dbg = d_buf;
-        E2EMV_HIP(ctx, hipMemsetAsync(d_dbg, 0, nb, s));
-        p.dbg = d_dbg;
-    }
     void* args[] = {&p};
     E2EMV_HIP(ctx, hipLaunchKernel(fn, dim3(8 * sl), dim3(512), args, lds, s));
     E2EMV_CHECK_LAUNCH(ctx, "gemm_h2_kernel");
-    if (dbg == 8) {
-        E2EMV_HIP(ctx, hipStreamSynchronize(s));
-        std::vector<long long> h(2 * 8 * 48 * 5);
-        E2EMV_HIP(ctx, hipMemcpy(h.data(), d_dbg, nb, hipMemcpyDeviceToHost));
-        static int printed = 0;
-        if (printed++ < 2)
-            for (int wg = 0; wg < 2; ++wg)
-                for (int w = 0; w < 8; w += 3) {
-                    const long long* o = &h[((size_t)wg * 8 + w) * 48 * 5];
-                    fprintf(stderr, "gemm_h2 M=%d N=%d K=%d tile 256x%d wg %d wave %d: cycles between the stamps of a step | total\n", p.M, p.N, p.K, bn, wg ? 101 : 0, w);
-                    for (int i = 0; i < 40; ++i) {
-                        const long long* t = o + i * 5;
-                        if (!t[0]) break;
-                        fprintf(stderr, "  %2d: %5lld %5lld %5lld %5lld | %5lld   (to next step %lld)\n", i, t[1] - t[0], t[2] - t[1], t[3] - t[2], t[4] - t[3],
-                                t[4] - t[0], i + 1 < 48 && t[5] ? t[5] - t[4] : 0);
-                    }
-                }
-    }
     return E2EMV_OK;
 }
 

@@ -21,10 +21,7 @@
 
 namespace e2emv {
 
-// DBG (instantiated only in -DE2EMV_STAMPS builds, tools/p2_stamps.py): 1 no MFMA, 2 no operand loads after the first two K
-// steps, 4 no epilogue, 8 s_memtime stamps per K step, 16 loads of step g + 1 issued one per MFMA group, 32 every wave issues
-// its loads before it computes (no opposite orders on a SIMD), 256 vmcnt(0) at every step (no store overlap)
-template <int OUT, bool HAS_R = false, int DBG = 0>
+template <int OUT, bool HAS_R = false>
 __global__ __launch_bounds__(512, 1) void gemm_p2_kernel(GemmP2Params p) {
     extern __shared__ __attribute__((aligned(16))) char smem_p2[];
 
@@ -62,16 +59,6 @@ __global__ __launch_bounds__(512, 1) void gemm_p2_kernel(GemmP2Params p) {
             w_vo[i] = gn * p.ldw_b + c * 16u;
         }
     };
-    // piece i of a K step: 0..3 activation rows, 4..7 weight rows
-    auto issue_piece = [&](int buf, int kt, int i, unsigned dep) {
-        char* dst = smem_p2 + buf * P2_BUFB + 32 * wave * P2_ROWB;
-        if (i < 4) {
-            if (kt < nk1) p2_glds16(rsA, dst + i * 1024, a_vo[i] + dep, (unsigned)kt * 128u);
-            else p2_glds16(rsA2, dst + i * 1024, a2_vo[i] + dep, (unsigned)(kt - nk1) * 128u);
-        } else {
-            p2_glds16(rsW, dst + P2_TILEB + (i - 4) * 1024, w_vo[i - 4] + dep, (unsigned)kt * 128u);
-        }
-    };
     auto issue = [&](int buf, int kt, unsigned dep) {
         char* dst = smem_p2 + buf * P2_BUFB + 32 * wave * P2_ROWB;
         if (kt < nk1) {
@@ -91,55 +78,8 @@ __global__ __launch_bounds__(512, 1) void gemm_p2_kernel(GemmP2Params p) {
     // ---- fragments: lane (row l31, k half lh); chunk index c = 4 plane + 2 ks + lh, stored at position c ^ ((l31 >> 1) & 7)
     const int swz = (l31 >> 1) & 7;
     p2_f32x16 acc[4][2];
-    // (`late`, DBG & 16 in measurement builds only: the loads of the next step go out one per MFMA group, each behind a
-    // scheduling-only dependency on that group's accumulator - an empty asm, no instruction)
-    auto compute = [&](int buf, auto FIRST, bool late, int ld_buf, int ld_k) {
-        constexpr bool first_step = decltype(FIRST)::value;
-        const char* xs = smem_p2 + buf * P2_BUFB + (wr * 64 + l31) * P2_ROWB;
-        const char* ws = smem_p2 + buf * P2_BUFB + P2_TILEB + (wc * 128 + l31) * P2_ROWB;
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            p2_f16x8 x[2][2];
-#pragma unroll
-            for (int t = 0; t < 2; ++t)
-#pragma unroll
-                for (int pl = 0; pl < 2; ++pl)
-                    x[t][pl] = *reinterpret_cast<const p2_f16x8*>(xs + t * 32 * P2_ROWB + (((4 * pl + 2 * ks + lh) ^ swz) << 4));
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                p2_f16x8 w[3];
-#pragma unroll
-                for (int pl = 0; pl < 2; ++pl)
-                    w[pl] = *reinterpret_cast<const p2_f16x8*>(ws + j * 32 * P2_ROWB + (((4 * pl + 2 * ks + lh) ^ swz) << 4));
-                w[2] = w[0] * (_Float16)(1.f / 2048.f);  // 2^-11 w_hi (exact wherever it matters: gemm_h2.hip)
-                constexpr int PW[3] = {1, 2, 0}, PX[3] = {0, 1, 0};  // x_hi w_lo, x_lo' (2^-11 w_hi), x_hi w_hi: smallest first
-                if (DBG & 1) {  // operand pipeline only
-                    asm volatile("" :: "v"(x[0][0]), "v"(x[0][1]), "v"(x[1][0]), "v"(x[1][1]), "v"(w[0]), "v"(w[1]), "v"(w[2]));
-                    if ((DBG & 16) && late) issue_piece(ld_buf, ld_k, 4 * ks + j, 0u);
-                    continue;
-                }
-#pragma unroll
-                for (int q = 0; q < 3; ++q)
-#pragma unroll
-                    for (int i = 0; i < 2; ++i) {
-                        if (first_step && ks == 0 && q == 0) {
-                            const p2_f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-                            acc[j][i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(w[PW[q]], x[i][PX[q]], zero, 0, 0, 0);
-                        } else {
-                            acc[j][i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(w[PW[q]], x[i][PX[q]], acc[j][i], 0, 0, 0);
-                        }
-                    }
-                if ((DBG & 16) && late) {
-                    unsigned dep = 0;
-                    asm("" : "+v"(dep) : "v"(acc[j][0]));
-                    issue_piece(ld_buf, ld_k, 4 * ks + j, dep);
-                }
-            }
-        }
-    };
 
-    // ---- the K step of the product kernel: gp_kstep (gemm_p2_core.h), software-pipelined inside the wave; `compute` above is kept
-    // for the measurement build's ablations
+    // ---- the K step: gp_kstep (gemm_p2_core.h), software-pipelined inside the wave
 
     // ---- epilogue: gp_epilogue (gemm_p2_core.h)
 
@@ -169,8 +109,8 @@ __global__ __launch_bounds__(512, 1) void gemm_p2_kernel(GemmP2Params p) {
     setup(tile);
     issue(0, 0, 0u);
     advance();
-    const bool issue_first = (DBG & 32) ? true : wave >= 4;
-    const bool overlap = nk >= 3 && !(DBG & (256 | 64 | 4 | 2));
+    const bool issue_first = wave >= 4;
+    const bool overlap = nk >= 3;
     // tile exponents of the A operand (p2.h): the accumulators live at the exponent of the CURRENT K block; when it changes
     // they are rescaled (exact: a power of two) - a wave-uniform branch that an ordinary network never takes
     // The exponents of a tile's K blocks are fetched ONCE, by one vector load (lane i: block i of this wave's 64 rows; the
@@ -203,23 +143,12 @@ __global__ __launch_bounds__(512, 1) void gemm_p2_kernel(GemmP2Params p) {
     ev = fetch_e(tile);
     int since = 8;       // K steps since the last epilogue
     bool ahead = false;  // the loads of the step after next were issued before that epilogue
-    int buf = 0, dbg_n = 0, dbg_steps = 0;
-    if (DBG & 1) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[j][i][r] = 0.f;
-    }
+    int buf = 0;
     auto step = [&](auto FIRST) {
-        long long t0 = 0, t1 = 0, t2 = 0;
-        if (DBG & 8) t0 = clock64();
         if (since == 0 && ahead) asm volatile("s_waitcnt vmcnt(40)" ::: "memory");
         else if (since <= 1 && overlap) asm volatile("s_waitcnt vmcnt(32)" ::: "memory");  // (since == 0 without `ahead`: 8 loads, then the stores)
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        if (DBG & 8) t1 = clock64();
         if (has_e) {
             const int e_step = p.EA ? __builtin_amdgcn_readlane(ev, cur_kt >> 1) : 0;
             if (!decltype(FIRST)::value && e_step != e_run) {
@@ -243,55 +172,37 @@ __global__ __launch_bounds__(512, 1) void gemm_p2_kernel(GemmP2Params p) {
             }
         }
         ++cur_kt;
-        const bool ldv = ld_valid && !(since == 0 && ahead) && !((DBG & 2) && dbg_steps >= 1);
-        ++dbg_steps;
-        if (!(DBG & 16) && issue_first && ldv) issue(buf ^ 1, ld_kt, 0u);
-        if (DBG & 8) t2 = clock64();
-        if constexpr ((DBG & ~8) == 0) gp_kstep<decltype(FIRST)::value>(smem_p2, buf, wr, wc, l31, lh, acc);  // (8 = stamps around the real stream)
-        else compute(buf, FIRST, (DBG & 16) && ldv, buf ^ 1, ld_kt);  // ONE call site: two would double the accumulator live ranges
-        if (!(DBG & 16) && !issue_first && ldv) {
+        const bool ldv = ld_valid && !(since == 0 && ahead);
+        if (issue_first && ldv) issue(buf ^ 1, ld_kt, 0u);
+        gp_kstep<decltype(FIRST)::value>(smem_p2, buf, wr, wc, l31, lh, acc);
+        if (!issue_first && ldv) {
             unsigned dep = 0;
-            if (!(DBG & 1)) asm("" : "+v"(dep) : "v"(acc[3][1]));  // scheduling-only: keeps the loads behind the MFMAs
+            asm("" : "+v"(dep) : "v"(acc[3][1]));  // scheduling-only: keeps the loads behind the MFMAs
             issue(buf ^ 1, ld_kt, dep);
         }
         if (ldv) advance();
         if (since == 0) ahead = false;
         ++since;
-        if (DBG & 8) {
-            const long long t3 = clock64();
-            if (p.dbg && lane == 0 && dbg_n < 48 && (blockIdx.x == 0 || blockIdx.x == 101)) {
-                long long* o = p.dbg + ((blockIdx.x ? 1 : 0) * 8 + wave) * 50 * 4 + dbg_n * 4;
-                o[0] = t0; o[1] = t1; o[2] = t2; o[3] = t3;
-                ++dbg_n;
-            }
-        }
         buf ^= 1;
     };
     for (;;) {
         step(std::true_type{});
         for (int kt = 1; kt < nk; ++kt) step(std::false_type{});
-        long long e0 = 0;
-        if (DBG & 8) e0 = clock64();
-        if (overlap && ld_valid && !(DBG & 2)) {
+        if (overlap && ld_valid) {
             // the buffer of the step just computed is free once every wave is through it: the loads of the step after next
             asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
             unsigned dep = 0;
-            if (!(DBG & 1)) asm("" : "+v"(dep) : "v"(acc[3][1]));
+            asm("" : "+v"(dep) : "v"(acc[3][1]));
             issue(buf ^ 1, ld_kt, dep);
             advance();
             ahead = true;
         }
         cur_kt = 0;
         if (has_e && nk < 4 && tile + slots < t_end) ev_next = fetch_e(tile + slots);
-        if (!(DBG & 4)) { gp_acc_fence(acc); gp_epilogue<OUT, HAS_R, DBG>(p, smem_p2, acc, wave, tile / p.tiles_n, tile % p.tiles_n, e_run, ev); }
-        else asm volatile("" :: "v"(acc[0][0]), "v"(acc[1][0]), "v"(acc[2][0]), "v"(acc[3][0]), "v"(acc[0][1]), "v"(acc[1][1]), "v"(acc[2][1]), "v"(acc[3][1]));
+        gp_acc_fence(acc);
+        gp_epilogue<OUT, HAS_R>(p, smem_p2, acc, wave, tile / p.tiles_n, tile % p.tiles_n, e_run, ev);
         ev = ev_next;
         since = overlap ? 0 : 8;
-        if ((DBG & 8) && p.dbg && lane == 0 && dbg_n < 48 && (blockIdx.x == 0 || blockIdx.x == 101)) {
-            long long* o = p.dbg + ((blockIdx.x ? 1 : 0) * 8 + wave) * 50 * 4 + dbg_n * 4;
-            o[0] = -1; o[1] = e0; o[2] = clock64(); o[3] = 0;
-            ++dbg_n;
-        }
         tile += slots;
         if (tile >= t_end) break;
     }
@@ -353,7 +264,6 @@ int fill_gemm_p2_params(e2emv_ctx* ctx, const GemmP2Args& a, GemmP2Params& p) {
     }
     if (!ctx->d_dummy) E2EMV_HIP(ctx, hipMalloc((void**)&ctx->d_dummy, 4096));
     p.dummy = ctx->d_dummy;
-    p.dbg = nullptr;
     return E2EMV_OK;
 }
 
@@ -369,62 +279,10 @@ int launch_gemm_p2(e2emv_ctx* ctx, const GemmP2Args& a, hipStream_t s) {
     const int per_xcd = (p.total + 7) / 8;
     const int sl = std::min(per_xcd, std::max(1, ctx->num_cus / 8));
     const size_t lds = P2_LDSB;
-#ifdef E2EMV_STAMPS
-    // measurement build only (tools/p2_stamps.py): E2EMV_P2_DBG selects an ablation / the stamped variant of the planes kernel
-    static int dbg = -1;
-    if (dbg < 0) { const char* e = getenv("E2EMV_P2_DBG"); dbg = e ? atoi(e) : 0; }
-    static long long* d_buf = nullptr;
-    const size_t nb = sizeof(long long) * 2 * 8 * 50 * 4;
-    if (dbg && a.out == P2_OUT_PLANES && !a.Rp) {
-        switch (dbg) {
-            case 1: fn = reinterpret_cast<const void*>(gemm_p2_kernel<P2_OUT_PLANES, false, 1>); break;
-            case 2: fn = reinterpret_cast<const void*>(gemm_p2_kernel<P2_OUT_PLANES, false, 2>); break;
-            case 3: fn = reinterpret_cast<const void*>(gemm_p2_kernel<P2_OUT_PLANES, false, 3>); break;
-            case 4: fn = reinterpret_cast<const void*>(gemm_p2_kernel<P2_OUT_PLANES, false, 4>); break;
-            case 6: fn = reinterpret_cast<const void*>(gemm_p2_kernel<P2_OUT_PLANES, false, 6>); break;
-            case 8: fn = reinterpret_cast<const void*>(gemm_p2_kernel<P2_OUT_PLANES, false, 8>); break;
-            case 16: fn = reinterpret_cast<const void*>(gemm_p2_kernel<P2_OUT_PLANES, false, 16>); break;
-            case 17: fn = reinterpret_cast<const void*>(gemm_p2_kernel<P2_OUT_PLANES, false, 17>); break;
-            case 24: fn = reinterpret_cast<const void*>(gemm_p2_kernel<P2_OUT_PLANES, false, 24>); break;
-            case 32: fn = reinterpret_cast<const void*>(gemm_p2_kernel<P2_OUT_PLANES, false, 32>); break;
-            case 64: fn = reinterpret_cast<const void*>(gemm_p2_kernel<P2_OUT_PLANES, false, 64>); break;
-            case 128: fn = reinterpret_cast<const void*>(gemm_p2_kernel<P2_OUT_PLANES, false, 128>); break;
-            case 256: fn = reinterpret_cast<const void*>(gemm_p2_kernel<P2_OUT_PLANES, false, 256>); break;
-            case 36: fn = reinterpret_cast<const void*>(gemm_p2_kernel<P2_OUT_PLANES, false, 36>); break;
-            case 40: fn = reinterpret_cast<const void*>(gemm_p2_kernel<P2_OUT_PLANES, false, 40>); break;
-            default: break;
-        }
-        if (dbg & 8) {
-            if (!d_buf) E2EMV_HIP(ctx, hipMalloc((void**)&d_buf, nb));
-            E2EMV_HIP(ctx, hipMemsetAsync(d_buf, 0, nb, s));
-            p.dbg = d_buf;
-        }
-    }
-#endif
     if (int rc = ensure_dynamic_lds(ctx, fn, lds)) return rc;
     void* args[] = {&p};
     E2EMV_HIP(ctx, hipLaunchKernel(fn, dim3(8 * sl), dim3(512), args, lds, s));
     E2EMV_CHECK_LAUNCH(ctx, "gemm_p2_kernel");
-#ifdef E2EMV_STAMPS
-    if (p.dbg) {
-        E2EMV_HIP(ctx, hipStreamSynchronize(s));
-        std::vector<long long> h(2 * 8 * 50 * 4);
-        E2EMV_HIP(ctx, hipMemcpy(h.data(), d_buf, nb, hipMemcpyDeviceToHost));
-        static int printed = 0;
-        if (printed++ < 2)
-            for (int wg = 0; wg < 2; ++wg)
-                for (int w = 0; w < 8; w += 5) {
-                    const long long* o = &h[((size_t)wg * 8 + w) * 50 * 4];
-                    fprintf(stderr, "gemm_p2 M=%d N=%d K=%d wg %d wave %d: per K step wait+barrier | issue | compute | total   (epilogue rows: -1)\n", p.M, p.N, p.K, wg ? 101 : 0, w);
-                    for (int i = 0; i < 44; ++i) {
-                        const long long* t = o + i * 4;
-                        if (!t[0]) break;
-                        if (t[0] == -1) { fprintf(stderr, "  %2d: epilogue %lld\n", i, t[2] - t[1]); continue; }
-                        fprintf(stderr, "  %2d: %5lld %5lld %5lld | %5lld\n", i, t[1] - t[0], t[2] - t[1], t[3] - t[2], t[3] - t[0]);
-                    }
-                }
-    }
-#endif
     return E2EMV_OK;
 }
 

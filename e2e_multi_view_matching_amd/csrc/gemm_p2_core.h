@@ -45,7 +45,6 @@ struct GemmP2Params {
     float bias_amax;
     unsigned* stats;  // [0]: number of output blocks that needed a non-zero exponent
     char* dummy;     // 4 KB: target of the stores of rows / columns beyond the matrix (a wave always issues all its stores)
-    long long* dbg;  // E2EMV_STAMPS builds only: phase timestamps of two workgroups
 };
 
 // The lane index, recomputed where it is needed (two VALU instructions; volatile: not hoisted, not merged with other copies).
@@ -134,9 +133,8 @@ __device__ __forceinline__ void gp_split8(const p2_f32x4& a0, const p2_f32x4& a1
     lo = p2_u32x4{l0, l1, l2, l3};
 }
 
-// ---- the same K step, software-pipelined inside the wave (the default; `compute` above is kept for the measurement
-// build's ablations).  hipcc's schedule of `compute` reads a group's weight fragments right in front of its MFMAs and
-// waits for them at once (lgkmcnt(0) behind the ds_reads): every group of 6 MFMAs opened with an exposed LDS round trip
+// ---- the K step, software-pipelined inside the wave.  hipcc's schedule of the plain loop (fragment reads, then the group's
+// MFMAs, per group) reads a group's weight fragments right in front of its MFMAs and waits for them at once (lgkmcnt(0) behind the ds_reads): every group of 6 MFMAs opened with an exposed LDS round trip
 // that only the SIMD's other wave could fill.  Here the 8 groups of a step (2 k-halves x 4 weight row blocks) run as one
 // stream: the fragments of group g + 1 (and the activation fragments of the next k-half) are read under the MFMAs of
 // group g, the four v_pk_mul_f16 that make 2^-11 w_hi sit behind the group's first MFMA; MFMAs and multiplies are asm
@@ -144,20 +142,13 @@ __device__ __forceinline__ void gp_split8(const p2_f32x4& a0, const p2_f32x4& a1
 // placement: multiplies -> the MFMA that reads them: one MFMA and two ds_reads apart.
 // (acc[j][i]: weight row block j of the wave's 128 output columns x activation row block i of its 64 rows; wr / wc = the wave's
 // row / column position in the 4 x 2 wave grid, l31 / lh = lane & 31 / lane >> 5)
-// KDBG (measurement builds only): 1 = the fragment reads and multiplies without the MFMAs
-template <bool first_step, int KDBG = 0>
+template <bool first_step>
 __device__ __forceinline__ void gp_kstep(const char* smem, int buf, int wr, int wc, int l31, int lh, p2_f32x16 (&acc)[4][2]) {
     const int swz = (l31 >> 1) & 7;
     const char* xs = smem + buf * P2_BUFB + (wr * 64 + l31) * P2_ROWB;
     const char* ws = smem + buf * P2_BUFB + P2_TILEB + (wc * 128 + l31) * P2_ROWB;
     auto rd_x = [&](int ks, int t, int pl) { return *reinterpret_cast<const p2_f16x8*>(xs + t * 32 * P2_ROWB + (((4 * pl + 2 * ks + lh) ^ swz) << 4)); };
     auto rd_w = [&](int ks, int j, int pl) { return *reinterpret_cast<const p2_f16x8*>(ws + j * 32 * P2_ROWB + (((4 * pl + 2 * ks + lh) ^ swz) << 4)); };
-    auto gp_mfma = [](p2_f32x16& c, p2_f16x8 a, p2_f16x8 b) {
-        if constexpr (KDBG & 1) asm volatile("" :: "v"(a), "v"(b)); else e2emv::gp_mfma(c, a, b);
-    };
-    auto gp_mfma0 = [](p2_f32x16& c, p2_f16x8 a, p2_f16x8 b) {
-        if constexpr (KDBG & 1) asm volatile("" :: "v"(a), "v"(b)); else e2emv::gp_mfma0(c, a, b);
-    };
     p2_f16x8 xb[2][2][2];  // [k-half parity][row block][plane]
     p2_f16x8 wb[2][2];     // [group parity][plane]
     unsigned k2048 = 0x10001000u;  // two fp16 2^-11
@@ -230,7 +221,7 @@ __device__ __forceinline__ void gp_acc_fence(p2_f32x16 (&acc)[4][2]) {
 // the wave cannot go on until it returns: eight store + load round trips per tile (MLP1's epilogue: 24.5 us against 10 for the others);
 // here a load is waited for four blocks after it was issued, with a counted vmcnt that leaves everything younger in flight.
 // (M a multiple of 256 and whole column tiles: the chained kernel's own conditions.)
-template <int OUT, bool HAS_R, int DBG, bool RLDS = false>
+template <int OUT, bool HAS_R, bool RLDS = false>
 __device__ __forceinline__ void gp_epilogue(const GemmP2Params& p, char* smem, const p2_f32x16 (&acc)[4][2], int wave, int tm, int tn, int e_run, int ev) {
     static_assert(!RLDS || (HAS_R && OUT == P2_OUT_PLANES), "the LDS residual ring belongs to the plane epilogue with a residual");
     // (the lane index is recomputed per tile: everything the epilogue derives from it - slab positions, store offsets, masks -
@@ -359,8 +350,6 @@ __device__ __forceinline__ void gp_epilogue(const GemmP2Params& p, char* smem, c
                     const int dim = (wc * 2 + (j >> 1)) * 64 + (j & 1) * 32 + 16 * pass;  // (+ dl0: in vt_lane)
                     uint16_t* dst = vt_lane + off_i + dim * row2;
                     if (m0 >= p.M || tn * P2_BN + wc * 128 + j * 32 + dl >= p.N) dst = reinterpret_cast<uint16_t*>(dummy);
-                    if (DBG & 64) { asm volatile("" :: "v"(hi), "v"(lo), "v"(dst)); continue; }          // measurement: no stores
-                    if (DBG & 128) dst = p.Vt + ((dst - p.Vt) & ((1 << 19) - 1) & ~63ll);                 // measurement: 1 MB target
                     *reinterpret_cast<p2_u32x4*>(dst) = hi;
                     *reinterpret_cast<p2_u32x4*>(dst + 32) = lo;
                 }
@@ -441,7 +430,6 @@ __device__ __forceinline__ void gp_epilogue(const GemmP2Params& p, char* smem, c
             rv[b & 1][pass][1] = *reinterpret_cast<const p2_f32x4*>(sl + r * 128 + (((c0 + 1) ^ o_z) << 4));
             if constexpr (RREG) {
                 int m = min(row0 + i * 32 + 16 * pass, p.M - 1);
-                if (DBG & 8192) m &= 255;  // measurement: the residual from an L2-resident slab
                 const uint16_t* rp = rcol + (int64_t)m * (2 * p.ldr);
                 rr[b & 1][pass][0] = *reinterpret_cast<const p2_u32x4*>(rp);
                 rr[b & 1][pass][1] = *reinterpret_cast<const p2_u32x4*>(rp + 32);
@@ -519,8 +507,6 @@ __device__ __forceinline__ void gp_epilogue(const GemmP2Params& p, char* smem, c
                 }
                 uint16_t* cp = cp_t + (2 * i + pass) * rstep + j * 64;
                 if (!ok) cp = reinterpret_cast<uint16_t*>(dummy);
-                if (DBG & 64) { asm volatile("" :: "v"(hi), "v"(lo), "v"(cp)); continue; }          // measurement: no stores
-                if (DBG & 128) cp = p.Cp + ((cp - p.Cp) & ((1 << 19) - 1) & ~63ll);                   // measurement: 1 MB target
                 *reinterpret_cast<p2_u32x4*>(cp) = hi;
                 *reinterpret_cast<p2_u32x4*>(cp + 32) = lo;
             }

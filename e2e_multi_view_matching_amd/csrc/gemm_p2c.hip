@@ -26,7 +26,6 @@
 //     the one exposed store drain per row block and launch (gemm_p2 exposes one per launch and tile round).
 #include <algorithm>
 #include <cstdlib>
-#include <vector>
 
 #include "gemm_p2_core.h"
 
@@ -44,10 +43,6 @@ struct GemmP2ChainParams {
     int t_info[P2C_MAX_TILES];      // per tile of a row block: stage | column tile << 8 | hard << 16 | soft << 17 (one scalar load)
 };
 
-// DBG (instantiated only in -DE2EMV_STAMPS builds, tools/p2c_stamps.py; results wrong but for 8, 16, 1024): 4 no epilogue, 8 s_memtime
-// stamps per tile (K loop | epilogue | hand-off) of two workgroups, 16 stamps per K step, 512 no wait at the hard hand-off, 1024
-// activation loads non-temporal, 2048 odd column tiles walk K backwards
-template <int DBG>
 __global__ __launch_bounds__(512, 1) void gemm_p2_chain_kernel(GemmP2ChainParams cp_by_value) {
     extern __shared__ __attribute__((aligned(16))) char smem_p2c[];
     // The stage of a tile is a run-time index into the parameter block.  Indexing the by-value argument makes hipcc copy the
@@ -81,7 +76,6 @@ __global__ __launch_bounds__(512, 1) void gemm_p2_chain_kernel(GemmP2ChainParams
     unsigned lda_l = 0, ldw_l = 0;    // row strides in bytes
     __amdgpu_buffer_rsrc_t rsA, rsA2, rsW;
     int nk_l = 0, nk1_l = 0;
-    bool rev_l = false;  // (measurement variant 2048: odd column tiles walk K backwards - their first steps re-read what the tile before read last)
     auto setup = [&](int f) {
         const int rbi = f / tpr, r = f - rbi * tpr, ti = cp.t_info[r], s = ti & 255;
         const int tm = (int)blockIdx.x + rbi * (int)gridDim.x, tn = (ti >> 8) & 255;
@@ -91,10 +85,9 @@ __global__ __launch_bounds__(512, 1) void gemm_p2_chain_kernel(GemmP2ChainParams
         rsW = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(q.W), 0, (int)q.w_bytes, 0x00020000);
         nk_l = q.K / P2_BK;
         nk1_l = q.K1 / P2_BK;
-        rev_l = (DBG & 2048) && (tn & 1);
         lda_l = q.lda_b;
         ldw_l = q.ldw_b;
-        a_base = (((DBG & 4096) ? 0u : (unsigned)tm * P2_BM) + 32u * wave) * lda_l;  // (4096: every workgroup reads row block 0)
+        a_base = ((unsigned)tm * P2_BM + 32u * wave) * lda_l;
         w_base = ((unsigned)tn * P2_BN + 32u * wave) * ldw_l;
     };
     // (ld_r | c16 << 8) of a lane: its row among the 8 of a load and its swizzled 16-byte chunk - two VGPRs' worth of lane
@@ -104,28 +97,24 @@ __global__ __launch_bounds__(512, 1) void gemm_p2_chain_kernel(GemmP2ChainParams
         return ld_r | ((ld_p ^ (ld_r >> 1)) * 16u) << 8;
     };
     auto issue = [&](int buf, int kt, unsigned rc) {
-        if ((DBG & 2048) && rev_l) kt = nk_l - 1 - kt;
         char* dst = smem_p2c + buf * P2_BUFB + 32 * wave * P2_ROWB;
         const unsigned ld_r = rc & 255u, c16 = rc >> 8;
         // (24-bit multiplies: full rate - a 32-bit v_mad_u64_u32 per operand stood in front of every step's loads)
         const unsigned a0 = __umul24(ld_r, lda_l) + c16, a1 = a0 ^ 64u, w0 = __umul24(ld_r, ldw_l) + c16, w1 = w0 ^ 64u;
         const unsigned a_step = 8u * lda_l, w_step = 8u * ldw_l;
-        // (E2EMV_STAMPS builds: DBG & 1024 = the activation stream with the non-temporal hint)
-#define P2C_LDA(rs, d, v, so) do { if constexpr ((DBG & 1024) != 0) p2_glds16_nt(rs, d, v, so); else p2_glds16(rs, d, v, so); } while (0)
         if (kt < nk1_l) {
             const unsigned so = a_base + (unsigned)kt * 128u;
-            P2C_LDA(rsA, dst, a0, so);
-            P2C_LDA(rsA, dst + 1024, a1, so + a_step);
-            P2C_LDA(rsA, dst + 2048, a0, so + 2 * a_step);
-            P2C_LDA(rsA, dst + 3072, a1, so + 3 * a_step);
+            p2_glds16(rsA, dst, a0, so);
+            p2_glds16(rsA, dst + 1024, a1, so + a_step);
+            p2_glds16(rsA, dst + 2048, a0, so + 2 * a_step);
+            p2_glds16(rsA, dst + 3072, a1, so + 3 * a_step);
         } else {
             const unsigned so = a_base + (unsigned)(kt - nk1_l) * 128u;
-            P2C_LDA(rsA2, dst, a0, so);
-            P2C_LDA(rsA2, dst + 1024, a1, so + a_step);
-            P2C_LDA(rsA2, dst + 2048, a0, so + 2 * a_step);
-            P2C_LDA(rsA2, dst + 3072, a1, so + 3 * a_step);
+            p2_glds16(rsA2, dst, a0, so);
+            p2_glds16(rsA2, dst + 1024, a1, so + a_step);
+            p2_glds16(rsA2, dst + 2048, a0, so + 2 * a_step);
+            p2_glds16(rsA2, dst + 3072, a1, so + 3 * a_step);
         }
-#undef P2C_LDA
         const unsigned sw = w_base + (unsigned)kt * 128u;
         p2_glds16(rsW, dst + P2_TILEB, w0, sw);
         p2_glds16(rsW, dst + P2_TILEB + 1024, w1, sw + w_step);
@@ -199,16 +188,11 @@ __global__ __launch_bounds__(512, 1) void gemm_p2_chain_kernel(GemmP2ChainParams
     // per-tile state of the compute position (wave-uniform)
     bool has_e = false, soft = false, prefetch_next = false;
     int f = 0;
-    int n_st = 0;  // (DBG & 16: per K step stamps of workgroup 0 / 101, waves 0 and 5)
     auto step = [&](auto FIRST) {
-        long long t0 = 0, t1 = 0, t2 = 0;
-        if (DBG & 16) t0 = __builtin_amdgcn_s_memtime();
         if (since == 0 && ahead) asm volatile("s_waitcnt vmcnt(40)" ::: "memory");
         else if (since <= 1) asm volatile("s_waitcnt vmcnt(32)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (DBG & 32) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // (measurement: the K loop without its per-step barrier - races, time only)
-        else asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        if (DBG & 16) t1 = __builtin_amdgcn_s_memtime();
+        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
         if (has_e && (cur_kt & 1) == 0) {  // a new K block
             // (everything that runs once per tile is marked unlikely: the K step's own path from the barrier to its first MFMA is
             // matrix-pipe idle time, and a cold block hipcc leaves inside it costs a taken branch + an instruction fetch)
@@ -247,11 +231,9 @@ __global__ __launch_bounds__(512, 1) void gemm_p2_chain_kernel(GemmP2ChainParams
         }
         ++cur_kt;
         const bool ldv = ld_valid && !ld_blocked && !(since == 0 && ahead);
-        const bool ldi = ldv && !(DBG & 2);  // (2: no operand loads in the K loop)
-        if (issue_first && ldi) issue(buf ^ 1, lkt, rc_t);
-        if (DBG & 16) t2 = __builtin_amdgcn_s_memtime();
-        gp_kstep<decltype(FIRST)::value, DBG & 1>(smem_p2c, buf, wr, wc, l31, lh, acc);
-        if (!issue_first && ldi) {
+        if (issue_first && ldv) issue(buf ^ 1, lkt, rc_t);
+        gp_kstep<decltype(FIRST)::value>(smem_p2c, buf, wr, wc, l31, lh, acc);
+        if (!issue_first && ldv) {
             unsigned rc = rc_t;
             asm("" : "+v"(rc) : "v"(acc[3][1]));  // scheduling-only: keeps the loads behind the MFMAs
             issue(buf ^ 1, lkt, rc);
@@ -260,14 +242,6 @@ __global__ __launch_bounds__(512, 1) void gemm_p2_chain_kernel(GemmP2ChainParams
         if (since == 0) ahead = false;
         ++since;
         buf ^= 1;
-        if (DBG & 16) {
-            const GemmP2Params& q0 = cp.st[0];
-            if (q0.dbg && gp_lane_now() == 0 && (blockIdx.x == 0 || blockIdx.x == 101) && (wave == 0 || wave == 5) && n_st < 80) {
-                long long* o = q0.dbg + (((blockIdx.x ? 1 : 0) * 2 + (wave ? 1 : 0)) * 80 + n_st) * 4;
-                o[0] = t0; o[1] = t1; o[2] = t2; o[3] = __builtin_amdgcn_s_memtime();
-            }
-            ++n_st;
-        }
     };
     for (f = 0; f < total; ++f) {
         const int rbi = f / tpr, r = f - rbi * tpr, ti = cp.t_info[r], s = ti & 255;
@@ -283,11 +257,8 @@ __global__ __launch_bounds__(512, 1) void gemm_p2_chain_kernel(GemmP2ChainParams
         has_e = q.EA != nullptr || ((cp.kind[s] & 4) && q.ER != nullptr);
         soft = f > 0 && (ti & (1 << 17)) != 0;
         prefetch_next = f + 1 < total && !is_hard(f + 1);
-        long long ts0 = 0, ts1 = 0, ts2 = 0;
-        if (DBG & 8) ts0 = __builtin_amdgcn_s_memtime();
         step(std::true_type{});
         for (int kt = 1; kt < nk; ++kt) step(std::false_type{});
-        if (DBG & 8) ts1 = __builtin_amdgcn_s_memtime();
         if (ld_valid && !ld_blocked) {
             // the buffer of the step just computed is free once every wave is through it: the loads of the step after next
             asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
@@ -305,28 +276,21 @@ __global__ __launch_bounds__(512, 1) void gemm_p2_chain_kernel(GemmP2ChainParams
             asm("v_writelane_b32 %0, %1, 32\n\tv_writelane_b32 %0, %2, 33\n\tv_writelane_b32 %0, %3, 34\n\tv_writelane_b32 %0, %4, 35"
                 : "+v"(ev) : "s"(er_c[0]), "s"(er_c[1]), "s"(ar_c[0]), "s"(ar_c[1]));
         }
-        if (!(DBG & 4)) {
-            constexpr int EDBG = DBG & (64 | 128 | 8192);  // no stores | stores into 1 MB | residual from a slab
-            switch (cp.kind[s]) {
-                case P2_OUT_PLANES: gp_epilogue<P2_OUT_PLANES, false, EDBG>(q, smem_p2c, acc, wave, tm, tn, e_run, ev); break;
-                case P2_OUT_PLANES | 4:
-                    // MLP1: the tile behind it is hard-dependent - nothing has run ahead into the tile buffers; once every wave is through
-                    // the last K step they carry this epilogue's residual ring (gemm_p2_core.h, RLDS).  (E2EMV_P2C_DBG 32768, measurement
-                    // build: the residual through registers as before)
-                    if (ld_blocked && !(DBG & 32768)) {
-                        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-                        gp_epilogue<P2_OUT_PLANES, true, EDBG, true>(q, smem_p2c, acc, wave, tm, tn, e_run, ev);
-                    } else {
-                        gp_epilogue<P2_OUT_PLANES, true, EDBG>(q, smem_p2c, acc, wave, tm, tn, e_run, ev);
-                    }
-                    break;
-                case P2_OUT_QKV: gp_epilogue<P2_OUT_QKV, false, EDBG>(q, smem_p2c, acc, wave, tm, tn, e_run, ev); break;
-                default: gp_epilogue<P2_OUT_F32, false, EDBG>(q, smem_p2c, acc, wave, tm, tn, e_run, ev); break;
-            }
-        } else {
-            asm volatile("" :: "v"(acc[0][0]), "v"(acc[1][0]), "v"(acc[2][0]), "v"(acc[3][0]), "v"(acc[0][1]), "v"(acc[1][1]), "v"(acc[2][1]), "v"(acc[3][1]));
+        switch (cp.kind[s]) {
+            case P2_OUT_PLANES: gp_epilogue<P2_OUT_PLANES, false>(q, smem_p2c, acc, wave, tm, tn, e_run, ev); break;
+            case P2_OUT_PLANES | 4:
+                // MLP1: the tile behind it is hard-dependent - nothing has run ahead into the tile buffers; once every wave is through
+                // the last K step they carry this epilogue's residual ring (gemm_p2_core.h, RLDS)
+                if (ld_blocked) {
+                    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+                    gp_epilogue<P2_OUT_PLANES, true, true>(q, smem_p2c, acc, wave, tm, tn, e_run, ev);
+                } else {
+                    gp_epilogue<P2_OUT_PLANES, true>(q, smem_p2c, acc, wave, tm, tn, e_run, ev);
+                }
+                break;
+            case P2_OUT_QKV: gp_epilogue<P2_OUT_QKV, false>(q, smem_p2c, acc, wave, tm, tn, e_run, ev); break;
+            default: gp_epilogue<P2_OUT_F32, false>(q, smem_p2c, acc, wave, tm, tn, e_run, ev); break;
         }
-        if (DBG & 8) ts2 = __builtin_amdgcn_s_memtime();
         ew = ew_next;
         since = 0;
         if (ld_blocked) {
@@ -334,8 +298,7 @@ __global__ __launch_bounds__(512, 1) void gemm_p2_chain_kernel(GemmP2ChainParams
             // (buffer_inv sc0: the consumer's loads must not be served from vector-L1 lines older than the producer waves' stores.  In
             // this build - CU mode, no tgsplit: build.py refuses the flag - all waves of the workgroup share one write-through L1 and
             // the invalidate is redundant; it is issued anyway, once per row block, so that the hand-off does not rest on that)
-            if (DBG & 512) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier\n\tbuffer_inv sc0" ::: "memory");
+            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier\n\tbuffer_inv sc0" ::: "memory");
             ld_blocked = false;
             ++lf;
             lkt = 0;
@@ -346,10 +309,6 @@ __global__ __launch_bounds__(512, 1) void gemm_p2_chain_kernel(GemmP2ChainParams
             advance();
             since = 8;
             ahead = false;
-        }
-        if ((DBG & 8) && q.dbg && gp_lane_now() == 0 && (blockIdx.x == 0 || blockIdx.x == 101) && f < 12) {
-            long long* o = q.dbg + (((blockIdx.x ? 1 : 0) * 8 + wave) * 12 + f) * 4;
-            o[0] = ts0; o[1] = ts1; o[2] = ts2; o[3] = __builtin_amdgcn_s_memtime();
         }
     }
 }
@@ -395,84 +354,11 @@ int launch_gemm_p2_chain(e2emv_ctx* ctx, const GemmP2Args* a, const int* dep_kt,
     cp.first[n] = tiles;
     cp.row_blocks = (a[0].M + P2_BM - 1) / P2_BM;
     const int grid = std::min(cp.row_blocks, std::max(1, ctx->num_cus));
-    const void* fn = reinterpret_cast<const void*>(gemm_p2_chain_kernel<0>);
-#ifdef E2EMV_STAMPS
-    // measurement build only (tools/p2c_stamps.py): E2EMV_P2C_DBG selects an ablation / the stamped variant
-    static int dbg = -1;
-    if (dbg < 0) { const char* e = getenv("E2EMV_P2C_DBG"); dbg = e ? atoi(e) : 0; }
-    static long long* d_buf = nullptr;
-    const size_t nb = sizeof(long long) * 4 * 80 * 4;  // (>= 2 * 8 * 12 * 4)
-    switch (dbg) {
-        case 4: fn = reinterpret_cast<const void*>(gemm_p2_chain_kernel<4>); break;
-        case 8: fn = reinterpret_cast<const void*>(gemm_p2_chain_kernel<8>); break;
-        case 512: fn = reinterpret_cast<const void*>(gemm_p2_chain_kernel<512>); break;
-        case 516: fn = reinterpret_cast<const void*>(gemm_p2_chain_kernel<516>); break;
-        case 1024: fn = reinterpret_cast<const void*>(gemm_p2_chain_kernel<1024>); break;
-        case 1028: fn = reinterpret_cast<const void*>(gemm_p2_chain_kernel<1028>); break;
-        case 2048: fn = reinterpret_cast<const void*>(gemm_p2_chain_kernel<2048>); break;
-        case 16: fn = reinterpret_cast<const void*>(gemm_p2_chain_kernel<16>); break;
-        // round 6: 1 no MFMAs, 2 no operand loads in the K loop, 4096 every workgroup's activation rows = row block 0 (L2-resident),
-        // 64 epilogues without stores, 128 epilogue stores into 1 MB, 8192 the residual from an L2-resident slab
-        case 1: fn = reinterpret_cast<const void*>(gemm_p2_chain_kernel<1>); break;
-        case 2: fn = reinterpret_cast<const void*>(gemm_p2_chain_kernel<2>); break;
-        case 4096: fn = reinterpret_cast<const void*>(gemm_p2_chain_kernel<4096>); break;
-        case 4100: fn = reinterpret_cast<const void*>(gemm_p2_chain_kernel<4100>); break;
-        case 64: fn = reinterpret_cast<const void*>(gemm_p2_chain_kernel<64>); break;
-        case 128: fn = reinterpret_cast<const void*>(gemm_p2_chain_kernel<128>); break;
-        case 8192: fn = reinterpret_cast<const void*>(gemm_p2_chain_kernel<8192>); break;
-        case 72: fn = reinterpret_cast<const void*>(gemm_p2_chain_kernel<72>); break;      // per-tile stamps of the variants without stores / with L2-resident activations
-        case 4104: fn = reinterpret_cast<const void*>(gemm_p2_chain_kernel<4104>); break;
-        case 4160: fn = reinterpret_cast<const void*>(gemm_p2_chain_kernel<4160>); break;  // no stores AND L2-resident activations
-        case 32: fn = reinterpret_cast<const void*>(gemm_p2_chain_kernel<32>); break;      // no per-step barrier
-        case 36: fn = reinterpret_cast<const void*>(gemm_p2_chain_kernel<36>); break;
-        case 32768: fn = reinterpret_cast<const void*>(gemm_p2_chain_kernel<32768>); break;  // MLP1's residual through registers (the round-5 form)
-        case 32776: fn = reinterpret_cast<const void*>(gemm_p2_chain_kernel<32776>); break;  // ... with per-tile stamps
-        case 12416: fn = reinterpret_cast<const void*>(gemm_p2_chain_kernel<12416>); break;  // 4096 + 8192 + 128: no HBM traffic but the weights
-        default: break;
-    }
-    if ((dbg & 8) || dbg == 16) {
-        if (!d_buf) E2EMV_HIP(ctx, hipMalloc((void**)&d_buf, nb));
-        E2EMV_HIP(ctx, hipMemsetAsync(d_buf, 0, nb, s));
-        for (int i = 0; i < n; ++i) cp.st[i].dbg = d_buf;
-    }
-#endif
+    const void* fn = reinterpret_cast<const void*>(gemm_p2_chain_kernel);
     if (int rc = ensure_dynamic_lds(ctx, fn, P2_LDSB)) return rc;
     void* args[] = {&cp};
     E2EMV_HIP(ctx, hipLaunchKernel(fn, dim3(grid), dim3(512), args, P2_LDSB, s));
     E2EMV_CHECK_LAUNCH(ctx, "gemm_p2_chain_kernel");
-#ifdef E2EMV_STAMPS
-    if (dbg == 16) {
-        static int printed16 = 0;
-        if (printed16++ < 2) {
-            E2EMV_HIP(ctx, hipStreamSynchronize(s));
-            std::vector<long long> h(4 * 80 * 4);
-            E2EMV_HIP(ctx, hipMemcpy(h.data(), d_buf, nb, hipMemcpyDeviceToHost));
-            for (int q = 0; q < 4; ++q) {
-                fprintf(stderr, "gemm_p2_chain wg %d wave %d: per K step  wait+barrier | exponents+issue | compute(+issue) | total   (ticks)\n", (q >> 1) ? 101 : 0, (q & 1) ? 5 : 0);
-                const long long* o = &h[(size_t)q * 80 * 4];
-                for (int i = 0; i < 80 && o[4 * i]; ++i)
-                    fprintf(stderr, "  %2d: %5lld %5lld %5lld | %5lld   (gap to next %lld)\n", i, o[4 * i + 1] - o[4 * i], o[4 * i + 2] - o[4 * i + 1], o[4 * i + 3] - o[4 * i + 2],
-                            o[4 * i + 3] - o[4 * i], i + 1 < 80 && o[4 * i + 4] ? o[4 * i + 4] - o[4 * i + 3] : 0);
-            }
-        }
-    }
-    if (dbg & 8) {
-        static int printed = 0;
-        if (printed++ < 1) {
-            E2EMV_HIP(ctx, hipStreamSynchronize(s));
-            std::vector<long long> h(2 * 8 * 12 * 4);
-            E2EMV_HIP(ctx, hipMemcpy(h.data(), d_buf, nb, hipMemcpyDeviceToHost));
-            for (int wg = 0; wg < 2; ++wg)
-                for (int w = 0; w < 8; w += 5) {
-                    fprintf(stderr, "gemm_p2_chain wg %d wave %d: per tile  K loop | ahead-issue + epilogue | hand-off   (s_memtime ticks, ~0.54 ns each)\n", wg ? 101 : 0, w);
-                    const long long* o = &h[((size_t)wg * 8 + w) * 12 * 4];
-                    for (int f = 0; f < tiles && f < 12; ++f)
-                        fprintf(stderr, "  tile %d: %6lld | %6lld | %6lld   (start +%lld)\n", f, o[4 * f + 1] - o[4 * f], o[4 * f + 2] - o[4 * f + 1],
-                                o[4 * f + 3] - o[4 * f + 2], o[4 * f] - o[0]);
-                }
-        }
-    }
-#endif
     return E2EMV_OK;
 }
 

@@ -1,6 +1,6 @@
 // fp32-in / fp32-out "NT" GEMM on the gfx950 bf16 matrix pipe with 3-way split operands (fp32-class accuracy):
 //   C[m][n] = act(sum_k A[m][k] W[n][k] + bias[n]) (+ R[m][n])
-// Second generation of the split-operand GEMM (gemm3.hip keeps the all-planes-in-HBM variant as a tested building block).
+// Second generation of the split-operand GEMM (the first generation, with every operand as planes in HBM, is retired).
 // What changed, after measuring that the operand pipeline of the fp32 kernel (gemm.hip) moves 10.8 TB/s from L2 into LDS
 // when the matrix cores are taken out - i.e. the first-generation kernel was not L2-bound, it was badly shaped:
 //  * same skeleton as gemm.hip: 128x128x32 tile, 4 waves (2x2) x (2x2) 32x32 MFMA tiles, transposed accumulators
@@ -42,7 +42,6 @@ struct GemmX3Params {
     int relu;
 };
 
-template <int DBG>
 __global__ __launch_bounds__(256, 2) void gemm_x3_kernel(GemmX3Params p) {
     extern __shared__ __attribute__((aligned(16))) uint16_t smem3[];
     uint16_t* As = smem3;                 // [3][128][40] activations (planes)
@@ -88,7 +87,6 @@ __global__ __launch_bounds__(256, 2) void gemm_x3_kernel(GemmX3Params p) {
     x3_f32x4 ra[4];
     x3_u32x4 rw[6];
     auto gload = [&](int kt) {
-        if ((DBG & 2) && kt > 0) return;  // profiling: no operand traffic after the first K tile
         const int k = kt * X3_BK;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -141,13 +139,6 @@ __global__ __launch_bounds__(256, 2) void gemm_x3_kernel(GemmX3Params p) {
                     x[t][pl] = *reinterpret_cast<const x3_bf16x8*>(as + pl * X3_PLANE + t * 32 * X3_LD + ks * 16);
                     w[t][pl] = *reinterpret_cast<const x3_bf16x8*>(bs + pl * X3_PLANE + t * 32 * X3_LD + ks * 16);
                 }
-            if (DBG & 1) {  // profiling: operand pipeline only
-#pragma unroll
-                for (int t = 0; t < 2; ++t)
-#pragma unroll
-                    for (int pl = 0; pl < 3; ++pl) acc[0][0][t] += (float)x[t][pl][0] + (float)w[t][pl][0];
-                continue;
-            }
             // smallest terms first; weights are the MFMA A operand (rows -> registers), activations B (rows -> lanes).
             // Consecutive MFMAs go to DIFFERENT accumulators: no back-to-back dependency on one accumulator tile.
             constexpr int PW[6] = {2, 0, 1, 1, 0, 0}, PX[6] = {0, 2, 1, 0, 1, 0};
@@ -191,11 +182,9 @@ __global__ __launch_bounds__(256, 2) void gemm_x3_kernel(GemmX3Params p) {
     gload(0);
     for (;;) {
         for (int kt = 0; kt + 1 < nk; ++kt) {
-            if (!(DBG & 4) || kt == 0) {  // (DBG & 4: profiling - LDS filled once, no barriers / LDS stores in the loop)
-                __syncthreads();
-                lstore();
-                __syncthreads();
-            }
+            __syncthreads();
+            lstore();
+            __syncthreads();
             gload(kt + 1);
             compute();
         }
@@ -235,12 +224,7 @@ int launch_gemm_x3(e2emv_ctx* ctx, const GemmArgs& a, const uint16_t* W3, int64_
     const int per_xcd = (p.total + 7) / 8;
     const int sl = std::min(per_xcd, std::max(1, ctx->num_cus * 2 / 8));
     const size_t lds = sizeof(uint16_t) * 6 * X3_PLANE;
-    static int dbg = -1;  // profiling knob E2EMV_X3_DEBUG: bit0 no MFMA, bit1 no operand loads after the first K tile
-    if (dbg < 0) dbg = dbg_knob("E2EMV_X3_DEBUG", 0);
-    if (dbg == 1) hipLaunchKernelGGL(gemm_x3_kernel<1>, dim3(8 * sl), dim3(256), lds, s, p);
-    else if (dbg == 2) hipLaunchKernelGGL(gemm_x3_kernel<2>, dim3(8 * sl), dim3(256), lds, s, p);
-    else if (dbg == 6) hipLaunchKernelGGL(gemm_x3_kernel<6>, dim3(8 * sl), dim3(256), lds, s, p);
-    else hipLaunchKernelGGL(gemm_x3_kernel<0>, dim3(8 * sl), dim3(256), lds, s, p);
+    hipLaunchKernelGGL(gemm_x3_kernel, dim3(8 * sl), dim3(256), lds, s, p);
     E2EMV_CHECK_LAUNCH(ctx, "gemm_x3_kernel");
     return E2EMV_OK;
 }

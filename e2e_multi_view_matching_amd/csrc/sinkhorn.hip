@@ -602,15 +602,10 @@ __device__ __forceinline__ float wave_sum4_dpp(float x0, float x1, float x2, flo
     return wave_sum4_rows(wave_sum4_quads(x0, x1, x2, x3, lane));
 }
 
-// rows per workgroup: 8 waves x 4 rows up to 1024 columns, 8 x 2 rows up to 2048 (64 matrix values per lane either way)
-// rows per workgroup: 8 waves x RW rows.  RW = 4 (64 matrix values per lane at 1024 columns, two workgroups per CU) or RW = 8 at
-// 1024 columns (128 values per lane, one workgroup per CU: the same number of resident problems, HALF as many workgroups in a
-// problem's exchange and half the granule traffic)
-static int g_skr_rw8 = -1;
-static inline int skr_rw(int64_t ldS) {
-    if (g_skr_rw8 < 0) g_skr_rw8 = dbg_knob("E2EMV_SKR_RW", 8) == 8 ? 1 : 0;
-    return (g_skr_rw8 && ldS > 512 && ldS <= 1024) ? 8 : 4;
-}
+// rows per workgroup: 8 waves x RW rows.  RW = 8 at 513 .. 1024 columns (128 values per lane, one workgroup per CU: against
+// RW = 4 - 64 values per lane, two workgroups per CU - the same number of resident problems, HALF as many workgroups in a
+// problem's exchange and half the granule traffic), RW = 4 elsewhere
+static inline int skr_rw(int64_t ldS) { return (ldS > 512 && ldS <= 1024) ? 8 : 4; }
 static inline int skr_rows(int64_t ldS) { return 8 * skr_rw(ldS); }
 constexpr unsigned SKR_SPIN_LIMIT = 1u << 21;
 constexpr unsigned SKR_GAVE_UP_NAN = 0x7fc0dead;  // potentials of a problem whose inter-workgroup wait gave up
@@ -627,8 +622,7 @@ struct SkResParams {
     u64* bufB;          // [n_res][G * cs]                          b granules
     u64* bufU;          // [n_res][2][G]                            sum of r_i a_i over a workgroup's rows, by epoch parity
     unsigned* timeout;  // [1]
-    unsigned long long* dbg;  // optional [16 iterations][G][8] 100 MHz timestamps of resident problem 0 (E2EMV_SKR_DEBUG)
-    int flags;          // experiment switch (E2EMV_SKR_FLAGS): 1 = no s_sleep in the polls
+    int flags;          // 1 = no s_sleep in the polls (the launcher passes 0)
     float* u;           // [B][M+1]  out: row potentials (u[M] = dustbin row)
     float* v;           // [B][ldV]  out: column potentials (v[N] = dustbin column)
     int64_t ldV;
@@ -816,8 +810,6 @@ __global__ __launch_bounds__(512, (KT <= 4 && RW == 4) ? 4 : 2) void sinkhorn_re
             int tq = tid;
             asm volatile("" : "+v"(tq));
             u64* const bufU = bufU2 + (epoch & 1u) * (unsigned)G;
-            unsigned long long* const dbg = (p.dbg && grp == 0 && round == 0 && it < 16 && tid == 0) ? p.dbg + ((int64_t)it * G + w) * 8 : nullptr;
-            if (dbg) dbg[0] = __builtin_amdgcn_s_memrealtime();
             // ---- row half-iteration: a_i = mu / (sum_j K_ij b_j + r_i b_N) for the wave's 4 rows; a_M from sum_j b_j
             {
                 f32x2 acc[RW], accb = {0.f, 0.f};
@@ -866,7 +858,6 @@ __global__ __launch_bounds__(512, (KT <= 4 && RW == 4) ? 4 : 2) void sinkhorn_re
                 for (int r = 1; r < RW; ++r) ra = fmaf(rK[r], a[r], ra);
                 if (lane == 0) red[wave] = ra;  // dustbin column
             }
-            if (dbg) dbg[1] = __builtin_amdgcn_s_memrealtime();
             __syncthreads();
             // ---- fold the 8 waves, publish the workgroup's partial column sums (stage A) and its dustbin-column sum
             if constexpr (pair) {
@@ -913,7 +904,6 @@ __global__ __launch_bounds__(512, (KT <= 4 && RW == 4) ? 4 : 2) void sinkhorn_re
                     granule_store(bufU + w, epoch, U);
                 }
             }
-            if (dbg) dbg[2] = __builtin_amdgcn_s_memrealtime();
             // ---- stage A consume: my slice of columns over all producers -> b_j = nu / (sum + a_M), published as stage B
             if constexpr (pair) {
                 const int q = tq & 15, cg = tq >> 4;
@@ -968,7 +958,6 @@ __global__ __launch_bounds__(512, (KT <= 4 && RW == 4) ? 4 : 2) void sinkhorn_re
                     if (act && q == 0) granule_store(bufB + c, epoch, mu / (T + aM));  // nu_j = mu
                 }
             }
-            if (dbg) dbg[3] = __builtin_amdgcn_s_memrealtime();
             // ---- b_N = nu_N / (sum_i r_i a_i + a_M) from the G workgroup sums (wave 0)
             if (wave == 0) {
                 float U = 0.f;
@@ -982,7 +971,6 @@ __global__ __launch_bounds__(512, (KT <= 4 && RW == 4) ? 4 : 2) void sinkhorn_re
                 U = wave_sum_dpp(U);
                 if (lane == 0) vbuf[W] = nuN / (U + aM);
             }
-            if (dbg) dbg[4] = __builtin_amdgcn_s_memrealtime();
             // ---- stage B consume: all of b into LDS
             if constexpr (pair) {
                 for (int c0 = 0; c0 < W; c0 += 1024) {  // wave-uniform trip count
@@ -1002,9 +990,7 @@ __global__ __launch_bounds__(512, (KT <= 4 && RW == 4) ? 4 : 2) void sinkhorn_re
                 if (ca < W) vbuf[ca] = ca < N ? __uint_as_float(val[0]) : 0.f;
                 if (cb < W) vbuf[cb] = cb < N ? __uint_as_float(val[1]) : 0.f;
             }
-            if (dbg) dbg[5] = __builtin_amdgcn_s_memrealtime();
             if (__syncthreads_or(dead ? 1 : 0)) dead = true;
-            if (dbg) dbg[6] = __builtin_amdgcn_s_memrealtime();
             bN = vbuf[W];
         }
 
@@ -1062,15 +1048,6 @@ __device__ __forceinline__ void sk_static_for(F&& f) { sk_static_for_impl(std::m
 constexpr int SK128_RV = 12, SK128_RA = 12, SK128_RL = 8, SK128_RR = SK128_RV + SK128_RA, SK128_R0 = 64;
 constexpr int sk128_base(int r) { return SK128_R0 + 16 * (r < SK128_RV ? r : r - SK128_RV); }
 #include "sinkhorn128_rows.h"
-// per-phase timestamps (tools/skr_timing.py): only in the measurement build - in these two kernels a 64-bit pointer kept over the
-// iteration costs registers the compiler's window does not have (it went to scratch and was reloaded at every stamp)
-#ifdef E2EMV_STAMPS
-#define SK_STAMP_PTR() unsigned long long* const dbg = (p.dbg && grp == 0 && round == 0 && it < 16 && tid == 0) ? p.dbg + ((int64_t)it * G + w) * 8 : nullptr
-#define SK_STAMP(i) do { if (dbg) dbg[i] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#else
-#define SK_STAMP_PTR() do {} while (0)
-#define SK_STAMP(i) do {} while (0)
-#endif
 template <bool FULL>
 __global__ __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(56))) void sinkhorn_resident128(SkResParams p) {
     constexpr int KT = 4, W = 1024, RW = SK128_RR + SK128_RL, ROWS = 4 * RW;
@@ -1158,8 +1135,6 @@ __global__ __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(56))) void s
             asm volatile("" : "+v"(tq));
             u64* const bufU = bufU2 + (epoch & 1u) * (unsigned)G;
             const bool last = it + 1 == p.iters;
-            SK_STAMP_PTR();
-            SK_STAMP(0);
             // ---- the wave's 32 rows in three phases, so that no latency-bound chain stands between two streams of multiply-adds:
             //   (1) row sums of all rows (asm), four rows folded into one register by two butterflies;
             //   (2) the 8 reductions over quads and rows and the 8 divisions - independent chains, interleaved by the compiler;
@@ -1276,7 +1251,6 @@ __global__ __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(56))) void s
 #pragma unroll
                 for (int k = 0; k < KT; ++k) *reinterpret_cast<f32x4*>(lf + 256 * k) = f32x4{cl[k][0], cl[k][1], ch[k][0], ch[k][1]};
                 if (lane == 0) red[wave] = ra;
-                SK_STAMP(1);
                 __syncthreads();
             }
             // ---- publish the workgroup's partial column sums (stage A, 16-byte pairs: 4 adjacent columns per thread) and its dustbin sum
@@ -1295,7 +1269,6 @@ __global__ __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(56))) void s
                     granule_store(bufU + w, epoch, U);
                 }
             }
-            SK_STAMP(2);
             // ---- stage A consume: my slice of columns over all producers -> b_j = mu / (sum + a_M), published as stage B
             {
                 const int q = tq & 3, cg = tq >> 2;  // 4 lanes per column pair, each two producers: q, q + 4 (, + 8, + 12)
@@ -1324,7 +1297,6 @@ __global__ __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(56))) void s
                     if (act && q == 0) granule_store2(rsB, (unsigned)c * 8u, epoch, mu / (T0 + aM), mu / (T1 + aM));
                 }
             }
-            SK_STAMP(3);
             // ---- b_N = nu_N / (sum_i r_i a_i + a_M) from the G workgroup sums (wave 0)
             if (wave == 0) {
                 float U = 0.f;
@@ -1338,7 +1310,6 @@ __global__ __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(56))) void s
                 U = wave_sum_dpp(U);
                 if (lane == 0) vbuf[W] = nuN / (U + aM);
             }
-            SK_STAMP(4);
             // ---- stage B consume: all of b into LDS (2 pairs per thread)
             {
                 unsigned off[2];
@@ -1357,9 +1328,7 @@ __global__ __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(56))) void s
                     *reinterpret_cast<f32x2*>(vbuf + ca) = f32x2{ca < N ? __uint_as_float(val[i][0]) : 0.f, ca + 1 < N ? __uint_as_float(val[i][1]) : 0.f};
                 }
             }
-            SK_STAMP(5);
             if (__syncthreads_or(dead ? 1 : 0)) dead = true;
-            SK_STAMP(6);
             bN = vbuf[W];
         }
 
@@ -1483,8 +1452,6 @@ __global__ __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(56))) void s
             asm volatile("" : "+v"(tq));
             u64* const bufU = bufU2 + (epoch & 1u) * (unsigned)G;
             const bool last = it + 1 == p.iters;
-            SK_STAMP_PTR();
-            SK_STAMP(0);
             // ---- row sums, per column half: one register per row
             float accp[RW];
 #pragma unroll
@@ -1595,7 +1562,6 @@ __global__ __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(56))) void s
                         for (int k = 0; k < 4; ++k) *reinterpret_cast<f32x4*>(lf + 256 * (4 * h + k)) = f32x4{cl[h][k][0], cl[h][k][1], ch[h][k][0], ch[h][k][1]};
                 }
                 if (lane == 0) red[wave] = ra;
-                SK_STAMP(1);
                 __syncthreads();
                 if (wave < 2) {
 #pragma unroll
@@ -1625,7 +1591,6 @@ __global__ __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(56))) void s
                     granule_store(bufU + w, epoch, U);
                 }
             }
-            SK_STAMP(2);
             // ---- stage A consume: my slice of columns over all producers -> b_j = mu / (sum + a_M), published as stage B
             {
                 // 8 lanes per column pair, each two producers per wait (four per wait - all 32 producers in one round trip - was
@@ -1656,7 +1621,6 @@ __global__ __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(56))) void s
                     if (act && q == 0) granule_store2(rsB, (unsigned)c * 8u, epoch, mu / (T0 + aM), mu / (T1 + aM));
                 }
             }
-            SK_STAMP(3);
             // ---- b_N = nu_N / (sum_i r_i a_i + a_M) from the G workgroup sums (wave 0)
             if (wave == 0) {
                 float U = 0.f;
@@ -1670,7 +1634,6 @@ __global__ __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(56))) void s
                 U = wave_sum_dpp(U);
                 if (lane == 0) vbuf[W] = nuN / (U + aM);
             }
-            SK_STAMP(4);
             // ---- stage B consume: all of b into LDS (4 pairs per thread, one wait)
             {
                 unsigned off[4];
@@ -1689,9 +1652,7 @@ __global__ __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(56))) void s
                     *reinterpret_cast<f32x2*>(vbuf + ca) = f32x2{ca < N ? __uint_as_float(val[i][0]) : 0.f, ca + 1 < N ? __uint_as_float(val[i][1]) : 0.f};
                 }
             }
-            SK_STAMP(5);
             if (__syncthreads_or(dead ? 1 : 0)) dead = true;
-            SK_STAMP(6);
             bN = vbuf[W];
         }
 
@@ -1901,17 +1862,14 @@ static int plan_sinkhorn(e2emv_ctx* ctx, int B, int M, int N, int64_t ldS, int i
     // granule pairs (16-byte exchange stores / loads): a thread must own an even number of columns and a consumer's column
     // slice must be even
     const int G0 = (M + skr_rows(ldS) - 1) / skr_rows(ldS);
-    const bool pairs = KT_of(ldS) >= 4 && ((N + G0 - 1) / G0) % 2 == 0 && dbg_knob("E2EMV_SKR_PAIR", 1) != 0;
+    const bool pairs = KT_of(ldS) >= 4 && ((N + G0 - 1) / G0) % 2 == 0;
     const void* kfn = nullptr;
     switch (KT_of(ldS)) {
         case 1: kfn = full ? (const void*)sinkhorn_resident<1, true> : (const void*)sinkhorn_resident<1, false>; break;
         case 2: kfn = full ? (const void*)sinkhorn_resident<2, true> : (const void*)sinkhorn_resident<2, false>; break;
-        case 4:
-            if (skr_rw(ldS) == 8) {
-                if (pairs) kfn = full ? (const void*)sinkhorn_resident<4, true, true, 8> : (const void*)sinkhorn_resident<4, false, true, 8>;
-                else kfn = full ? (const void*)sinkhorn_resident<4, true, false, 8> : (const void*)sinkhorn_resident<4, false, false, 8>;
-            } else if (pairs) kfn = full ? (const void*)sinkhorn_resident<4, true, true> : (const void*)sinkhorn_resident<4, false, true>;
-            else kfn = full ? (const void*)sinkhorn_resident<4, true> : (const void*)sinkhorn_resident<4, false>;
+        case 4:  // (skr_rw: 8 rows per wave)
+            if (pairs) kfn = full ? (const void*)sinkhorn_resident<4, true, true, 8> : (const void*)sinkhorn_resident<4, false, true, 8>;
+            else kfn = full ? (const void*)sinkhorn_resident<4, true, false, 8> : (const void*)sinkhorn_resident<4, false, false, 8>;
             break;
         default:
             if (pairs) kfn = full ? (const void*)sinkhorn_resident<8, true, true> : (const void*)sinkhorn_resident<8, false, true>;
@@ -2034,7 +1992,6 @@ int launch_sinkhorn(e2emv_ctx* ctx, int B, int M, int N, const float* S, int64_t
         if (int rc_f = ensure_flags(ctx)) return rc_f;
         const SkSegment* seg = plan.seg;
         const int n_seg = plan.n_seg;
-        const char* dbg_path = dbg_env("E2EMV_SKR_DEBUG");
         for (int si = 0; si < n_seg; ++si) {
             const SkKernel& k = seg[si].k;
             const int b0 = seg[si].b0, nb = seg[si].n;
@@ -2048,11 +2005,6 @@ int launch_sinkhorn(e2emv_ctx* ctx, int B, int M, int N, const float* S, int64_t
             rpar.bufB = (u64*)gw; gw += rp.bytesB;
             rpar.bufU = (u64*)gw; gw += rp.bytesU;
             rpar.timeout = ctx->d_flags;
-            unsigned long long* d_dbg = nullptr;
-            const size_t dbg_bytes = (size_t)16 * rp.G * 8 * sizeof(unsigned long long);
-            if (dbg_path && si == 0 && hipMalloc((void**)&d_dbg, dbg_bytes) == hipSuccess) (void)hipMemsetAsync(d_dbg, 0, dbg_bytes, s);
-            rpar.dbg = d_dbg;
-            rpar.flags = dbg_knob("E2EMV_SKR_FLAGS", rpar.flags);
             rpar.u = p.u + (int64_t)b0 * (M + 1); rpar.v = p.v + (int64_t)b0 * p.ldV; rpar.ldV = p.ldV;
             // every polled word starts from 0 in every launch (epochs count from 1)
             // (ONE launch for the granule buffers and the give-up flag: two hipMemsetAsync were two fill kernels of ~14 us each per segment)
@@ -2061,22 +2013,6 @@ int launch_sinkhorn(e2emv_ctx* ctx, int B, int M, int N, const float* S, int64_t
             E2EMV_CHECK_LAUNCH(ctx, "skr_zero_kernel");
             hipLaunchKernelGGL_ptr(k.fn, dim3((unsigned)(rp.n_res * rp.G)), dim3(k.threads), k.lds, s, rpar);
             E2EMV_CHECK_LAUNCH(ctx, "sinkhorn_resident");
-            if (d_dbg) {  // development aid: per-phase timestamps of resident problem 0, appended as text
-                std::vector<unsigned long long> h(dbg_bytes / 8);
-                (void)hipStreamSynchronize(s);
-                (void)hipMemcpy(h.data(), d_dbg, dbg_bytes, hipMemcpyDeviceToHost);
-                (void)hipFree(d_dbg);
-                if (FILE* f = fopen(dbg_path, "a")) {
-                    fprintf(f, "# B=%d M=%d N=%d iters=%d G=%d n_res=%d flags=%d\n", nb, M, N, iters, rp.G, rp.n_res, rpar.flags);
-                    for (int it = 0; it < 16 && it < iters; ++it)
-                        for (int g = 0; g < rp.G; ++g) {
-                            fprintf(f, "%d %d", it, g);
-                            for (int kk = 0; kk < 7; ++kk) fprintf(f, " %llu", h[((size_t)it * rp.G + g) * 8 + kk]);
-                            fprintf(f, "\n");
-                        }
-                    fclose(f);
-                }
-            }
         }
         if (seg[0].k.big) ++ctx->stat_sinkhorn_rows128;
         // problems the exponential-domain kernel could not finish are re-solved in the log domain before anything reads u, v

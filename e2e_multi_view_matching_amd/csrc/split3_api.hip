@@ -1,6 +1,6 @@
 // Test/bench entry points of the bf16x3 building blocks on plain fp32 buffers: the split into S3 planes,
 // the V transpose and the merge back to fp32 are done here by small helper kernels so that the kernels of
-// gemm3.hip / attention3.hip can be checked in isolation against an fp64 reference.
+// gemm_x3.hip / attention3.hip can be checked in isolation against an fp64 reference.
 #include <vector>
 
 #include "common.h"
@@ -55,11 +55,9 @@ extern "C" int e2emv_gemm_bf16x3(e2emv_ctx* ctx, int M, int Nout, int K, const f
     if (M <= 0 || Nout <= 0 || K <= 0 || K % 32 || Nout % 4) return set_err(ctx, E2EMV_ESHAPE, "gemm_bf16x3: M=%d N=%d K=%d", M, Nout, K);
     hipStream_t s = (hipStream_t)stream;
     auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
-    const size_t szA = al((size_t)M * 3 * K * 2), szW = al((size_t)Nout * 3 * K * 2);
-    int rc = ws_reserve(ctx, szA + szW);
+    int rc = ws_reserve(ctx, al((size_t)Nout * 3 * K * 2));
     if (rc) return rc;
-    uint16_t* A3 = (uint16_t*)ctx->d_ws;
-    uint16_t* W3 = (uint16_t*)(ctx->d_ws + szA);
+    uint16_t* W3 = (uint16_t*)ctx->d_ws;
     if (flags & 4) {  // f16x2 GEMM (gemm_h2.hip); the weight planes are made on the host as e2emv_commit_weights makes them
         std::vector<float> hw((size_t)Nout * K);
         E2EMV_HIP(ctx, hipStreamSynchronize(s));
@@ -75,27 +73,15 @@ extern "C" int e2emv_gemm_bf16x3(e2emv_ctx* ctx, int M, int Nout, int K, const f
         prof_end(ctx, s);
         return rc;
     }
+    if (flags & 2) return set_err(ctx, E2EMV_EINVAL, "gemm_bf16x3: flags bit1 (the all-planes first-generation kernel) is retired");
     if ((rc = launch_split3(ctx, d_W, Nout, K, K, W3, K, s))) return rc;
-    if (!(flags & 2)) {  // second-generation kernel: activations stay fp32, split on the way into LDS (gemm_x3.hip)
-        GemmArgs g;
-        g.M = M; g.N = Nout; g.K = K; g.K1 = K; g.A = d_A; g.lda = K; g.bias = d_bias; g.C = d_C; g.ldc = Nout; g.relu = (flags & 1) != 0;
-        prof_begin(ctx, PS_GEMM, s);
-        rc = launch_gemm_x3(ctx, g, W3, K, s);
-        prof_end(ctx, s);
-        return rc;
-    }
-#ifndef E2EMV_STAMPS
-    return set_err(ctx, E2EMV_EINVAL, "gemm_bf16x3: the all-planes first-generation kernel (flags bit1, gemm3.hip) is part of the measurement build only");
-#else
-    if ((rc = launch_split3(ctx, d_A, M, K, K, A3, K, s))) return rc;
-    Gemm3Args g;
-    g.M = M; g.N = Nout; g.K = K; g.K1 = K; g.A = A3; g.lda = K; g.W = W3; g.ldw = K; g.bias = d_bias;
-    g.C32 = d_C; g.ldc32 = Nout; g.relu = (flags & 1) != 0;
+    // activations stay fp32, split on the way into LDS (gemm_x3.hip)
+    GemmArgs g;
+    g.M = M; g.N = Nout; g.K = K; g.K1 = K; g.A = d_A; g.lda = K; g.bias = d_bias; g.C = d_C; g.ldc = Nout; g.relu = (flags & 1) != 0;
     prof_begin(ctx, PS_GEMM, s);
-    rc = launch_gemm3(ctx, g, s);
+    rc = launch_gemm_x3(ctx, g, W3, K, s);
     prof_end(ctx, s);
     return rc;
-#endif
 }
 
 extern "C" int e2emv_attention_bf16x3(e2emv_ctx* ctx, int B, int T, int n_rows, int n_valid, int D, int H, const float* d_qkv,

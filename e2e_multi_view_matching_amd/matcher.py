@@ -409,7 +409,7 @@ class MultiViewMatcher(nn.Module):
             want = _lib.PRECISION_NAMES[mode]
         if ctx.precision() != want:
             ctx.call("e2emv_set_precision", want)
-        gen = {"f16x2-r2": 2, "f16x2-r3": 3, "f16x2-r4": 4, "f16x2-chain": 105}.get(mode, ctx.default_f16x2_kernels)
+        gen = {"f16x2-r4": 4, "f16x2-chain": 105}.get(mode, ctx.default_f16x2_kernels)
         if ctx.f16x2_kernels != gen:
             ctx.set_f16x2_kernels(gen)
         kpts, scores, descs = [], [], []

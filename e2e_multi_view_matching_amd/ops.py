@@ -72,10 +72,9 @@ def attention(qkv, B, T, n_valid, H, cross):
     return out
 
 
-def gemm_bf16x3(A, W, bias=None, relu=False, all_planes=False, f16x2=False):
+def gemm_bf16x3(A, W, bias=None, relu=False, f16x2=False):
     """bf16x3 split-operand GEMM building block on fp32 tensors: act(A W^T + bias).  Default: gemm_x3.hip (activations
-    split on the way into LDS); ``all_planes=True``: the first-generation kernel that reads pre-split planes (gemm3.hip); ``f16x2=True``: the
-    fp16 x 2 form of gemm_x3.hip (two activation planes, three products)."""
+    split on the way into LDS); ``f16x2=True``: the fp16 x 2 form of gemm_x3.hip (two activation planes, three products)."""
     ctx = _ctx(A)
     A_, W_ = A.contiguous().float(), W.contiguous().float()
     M, K = A_.shape
@@ -83,7 +82,7 @@ def gemm_bf16x3(A, W, bias=None, relu=False, all_planes=False, f16x2=False):
     C = torch.empty((M, N), dtype=torch.float32, device=A.device)
     b = bias.contiguous().float() if bias is not None else None
     with torch.cuda.device(A.device):
-        ctx.call("e2emv_gemm_bf16x3", M, N, K, _lib.ptr(A_), _lib.ptr(W_), _lib.ptr(b), _lib.ptr(C), (1 if relu else 0) | (2 if all_planes else 0) | (4 if f16x2 else 0),
+        ctx.call("e2emv_gemm_bf16x3", M, N, K, _lib.ptr(A_), _lib.ptr(W_), _lib.ptr(b), _lib.ptr(C), (1 if relu else 0) | (4 if f16x2 else 0),
                  _lib.stream_ptr(A.device))
     return C
 
@@ -134,15 +133,16 @@ def qkv_p2(X, W, bias, n_rows, H=4):
     return out
 
 
-def attention_p2(qkv, B, T, n_valid, H, cross, waves=0, reps=1, abl=0):
+def attention_p2(qkv, B, T, n_valid, H, cross, waves=0, reps=1):
     """attention_p2.hip on an fp32 q|k|v matrix (split into the plane operands by a helper kernel); same contract as
-    `attention`.  waves: 0 = by key count, 4 / 8 = attention_p2 with that workgroup size, 1 = attention_p2w (one wave per SIMD)."""
+    `attention`.  waves: 0 = by key count, 4 / 8 = attention_p2 with that workgroup size, 1 = attention_p2w (one wave per SIMD);
+    reps: launches of the attention per call (micro-benchmarks)."""
     ctx = _ctx(qkv)
     q = qkv.contiguous().float()
     n_img, n_rows, D3 = q.shape
     D = D3 // 3
     out = torch.empty((n_img, n_rows, D), dtype=torch.float32, device=q.device)
-    flags = (1 if cross else 0) | {0: 0, 4: 2, 8: 4, 1: 8}[waves] | (int(reps) << 8 if reps > 1 else 0) | ((int(abl) & 15) << 4)
+    flags = (1 if cross else 0) | {0: 0, 4: 2, 8: 4, 1: 8}[waves] | (int(reps) << 8 if reps > 1 else 0)
     with torch.cuda.device(q.device):
         ctx.call("e2emv_attention_p2", B, T, n_rows, n_valid, D, H, _lib.ptr(q), flags, _lib.ptr(out), _lib.stream_ptr(q.device))
     return out

@@ -326,9 +326,9 @@ int e2emv_get_precision(e2emv_ctx* ctx, int* precision);
  * them at small sizes). */
 int e2emv_set_split_min_rows(e2emv_ctx* ctx, int64_t min_rows);
 /* building blocks of the bf16x3 path on fp32 buffers (split / merge done internally; for tests):
- * C = act(A W^T + bias), A [M,K], W [N,K], C [M,N]; flags bit0 relu, bit1 = first-generation kernel reading pre-split
- * activation planes (gemm3.hip) instead of the default gemm_x3.hip (fp32 activations split on the way into LDS),
- * bit2 = the f16x2 GEMM, gemm_h2.hip (host-synchronising: the weight planes are made on the host). */
+ * C = act(A W^T + bias), A [M,K], W [N,K], C [M,N] on gemm_x3.hip (fp32 activations split on the way into LDS); flags bit0
+ * relu, bit2 = the f16x2 GEMM, gemm_h2.hip (host-synchronising: the weight planes are made on the host).  Bit1 (the retired
+ * first-generation kernel on pre-split activation planes) returns E2EMV_EINVAL. */
 int e2emv_gemm_bf16x3(e2emv_ctx* ctx, int M, int Nout, int K, const float* d_A, const float* d_W, const float* d_bias,
                       float* d_C, int flags, void* stream);
 /* same contract as e2emv_attention; cross: bit0 = cross layer, bit1 = the forward pass's kernel (fp32 q|k|v in, the
@@ -341,11 +341,11 @@ int e2emv_attention_bf16x3(e2emv_ctx* ctx, int B, int T, int n_rows, int n_valid
  * blocks of {hi, lo}); every producer splits its output once in its epilogue, consumers move the planes from global
  * memory straight into LDS.  generation 5 (default) = these kernels (gemm_p2.hip; attention_p2w.hip - one wave per SIMD,
  * matrix and softmax work interleaved inside the wave - above 256 keys, attention_p2.hip below; needs descriptor_dim 256 /
- * 4 heads, other widths use generation 2) with the row-local GEMMs between two attentions (MLP0, MLP1, the next layer's
- * q | k | v) chained per 256-row block in ONE launch where that takes no more tile rounds than three launches (gemm_p2c.hip;
- * bit-identical results; 105 = chained on every shape that allows it), 4 = a launch per GEMM, 3 = the same with the round-3 attention (attention_p2.hip everywhere), 2 = the
- * round-2 kernels that keep fp32 activations and split them inside the consuming GEMM / attention (kept as A/B arms and
- * for other widths).  Also E2EMV_F16X2_KERNELS=r2 | r3 | r4 at e2emv_create. */
+ * 4 heads, other widths run the round-2 kernels that keep fp32 activations and split them inside the consuming GEMM /
+ * attention) with the row-local GEMMs between two attentions (MLP0, MLP1, the next layer's q | k | v) chained per 256-row
+ * block in ONE launch where that takes no more tile rounds than three launches (gemm_p2c.hip; bit-identical results; 105 =
+ * chained on every shape that allows it), 4 = a launch per GEMM.  Other values (the retired generations 2 and 3 among
+ * them) return E2EMV_EINVAL.  Also E2EMV_F16X2_KERNELS=r4 at e2emv_create (other values are ignored). */
 int e2emv_set_f16x2_kernels(e2emv_ctx* ctx, int generation);
 /* attention_p2w (f16x2, above 256 keys): when the (image, head, 256-query) items of a launch leave the last round of workgroups at most
  * half full - tuple_size 5 at 1024 keypoints: 640 items on 256 CUs, three rounds for 2.5 of work; a pair or two per call: fewer items
@@ -365,7 +365,7 @@ int e2emv_gemm_p2(e2emv_ctx* ctx, int M, int Nout, int K, int K1, const float* d
 int e2emv_qkv_p2(e2emv_ctx* ctx, int n_img, int n_rows, int D, int H, const float* d_X, const float* d_W, const float* d_bias,
                  float* d_qkv, void* stream);
 /* same contract as e2emv_attention on the plane kernel; flags: bit0 cross, bit1 / bit2 force attention_p2 with 4 / 8 waves per workgroup, bit3 forces attention_p2w (one wave per SIMD),
- * bits 8.. = timed repetitions. */
+ * bits 4..7 reserved (ignored), bits 8.. = timed repetitions. */
 int e2emv_attention_p2(e2emv_ctx* ctx, int B, int T, int n_rows, int n_valid, int D, int H, const float* d_qkv, int flags,
                        float* d_out, void* stream);
 

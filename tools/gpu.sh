@@ -1,6 +1,6 @@
 #!/bin/bash
 # One parameterised GPU-box script (run through gpurun): tools/gpu.sh <stage> [...]; output under gpurun_out/r6/.
-#   planes   per-kernel parity of the plane kernels + matcher parity + micro-benchmarks + bench A/B (plane vs round-2 kernels)
+#   planes   per-kernel parity of the plane kernels + matcher parity + micro-benchmarks + a bench line
 #   tests    the whole -m gpu suite
 #   bench    bench.py --full lines (c2 default, c4, c5)
 #   one      one short bench line with its roofline / sinkhorn_bound objects printed
@@ -50,58 +50,14 @@ planes)
   timeout 900 python -m pytest tests/test_gpu_matcher.py tests/test_gpu_golden_direct.py -x -q 2>&1 | tail -15 | tee $OUT/planes_matcher.log
   timeout 600 python tools/microbench.py --what p2 2>&1 | tee $OUT/microbench_p2.log
   timeout 300 python bench.py --full --steps 10 --warmup 3 --cpu-pairs 0 --no-alt --no-latency > $OUT/bench_p2.json 2> $OUT/bench_p2.err
-  E2EMV_F16X2_KERNELS=r2 timeout 300 python bench.py --full --steps 10 --warmup 3 --cpu-pairs 0 --no-alt --no-latency > $OUT/bench_r2k.json 2> $OUT/bench_r2k.err
-  show $OUT/bench_p2.json $OUT/bench_r2k.json
+  show $OUT/bench_p2.json
   ;;
 aw)
   # attention_p2w: parity of the attention kernels on planes, micro-benchmark against attention_p2, one bench line per kernel
   timeout 900 python -m pytest tests/test_gpu_planes.py -x -q -k attention 2>&1 | tail -15 | tee $OUT/aw_tests.log
   timeout 600 python tools/microbench.py --what ap2 2>&1 | tee $OUT/microbench_ap2.log
   timeout 300 python bench.py --full --steps 10 --warmup 3 --cpu-pairs 0 --no-alt --no-latency > $OUT/bench_aw.json 2> $OUT/bench_aw.err
-  E2EMV_F16X2_KERNELS=r3 timeout 300 python bench.py --full --steps 10 --warmup 3 --cpu-pairs 0 --no-alt --no-latency > $OUT/bench_ap8.json 2> $OUT/bench_ap8.err
-  show $OUT/bench_aw.json $OUT/bench_ap8.json
-  ;;
-awabl)
-  # attention_p2w ablations (measurement build) + a PMC pass over attention_p2w and attention_p2
-  timeout 600 python tools/aw_ablate.py 2>&1 | grep -v amdgpu.ids | tee $OUT/aw_ablate.log
-  (cd /tmp && timeout 300 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU --output-format csv -d /tmp/aw_pmc -- python $GRAFT_REPO_ROOT/tools/aw_ablate.py --pmc > $OUT/aw_pmc.log 2>&1)
-  f=$(find /tmp/aw_pmc -name '*counter_collection.csv' | head -1)
-  [ -n "$f" ] && python - "$f" <<'PY' | tee $OUT/aw_pmc_summary.txt
-import csv, sys, collections
-rows = list(csv.DictReader(open(sys.argv[1])))
-acc = collections.defaultdict(lambda: collections.defaultdict(float)); n = collections.Counter()
-for r in rows:
-    k = r['Kernel_Name'][:60]
-    if 'attention_p2' not in k: continue
-    acc[k][r['Counter_Name']] += float(r['Counter_Value']); 
-for k, d in acc.items():
-    print(k); [print('   ', c, f'{v:.4g}') for c, v in sorted(d.items())]
-PY
-  (cd /tmp && timeout 300 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_MFMA SQ_INSTS_VMEM SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE --output-format csv -d /tmp/aw_pmc2 -- python $GRAFT_REPO_ROOT/tools/aw_ablate.py --pmc >> $OUT/aw_pmc.log 2>&1)
-  f=$(find /tmp/aw_pmc2 -name '*counter_collection.csv' | head -1)
-  [ -n "$f" ] && python - "$f" <<'PY' | tee -a $OUT/aw_pmc_summary.txt
-import csv, sys, collections
-rows = list(csv.DictReader(open(sys.argv[1])))
-acc = collections.defaultdict(lambda: collections.defaultdict(float))
-for r in rows:
-    k = r['Kernel_Name'][:60]
-    if 'attention_p2' not in k: continue
-    acc[k][r['Counter_Name']] += float(r['Counter_Value'])
-for k, d in acc.items():
-    print(k); [print('   ', c, f'{v:.4g}') for c, v in sorted(d.items())]
-PY
-  tail -5 $OUT/aw_pmc.log
-  ;;
-stamps)
-  timeout 900 python tools/p2_stamps.py 2>&1 | tee $OUT/p2_stamps.log
-  ;;
-cstamps)
-  timeout 1200 python tools/p2c_stamps.py "${@:2}" 2>&1 | tee $OUT/p2c_stamps.log
-  ;;
-ab)
-  timeout 300 python bench.py --full --steps 10 --warmup 3 --cpu-pairs 0 --no-alt --no-latency > $OUT/bench_p2.json 2> $OUT/bench_p2.err
-  E2EMV_F16X2_KERNELS=r2 timeout 300 python bench.py --full --steps 10 --warmup 3 --cpu-pairs 0 --no-alt --no-latency > $OUT/bench_r2k.json 2> $OUT/bench_r2k.err
-  show $OUT/bench_p2.json $OUT/bench_r2k.json
+  show $OUT/bench_aw.json
   ;;
 sk128)
   # sinkhorn_resident128: its tests, then ms per call (100 iterations incl. the final sweep) against the 64-row kernel, alternating
@@ -151,10 +107,9 @@ final)
   (cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats -d /tmp/kt_c2_steps6 -- python $GRAFT_REPO_ROOT/bench.py $args > $OUT/kt_c2_steps6.log 2>&1)
   db=$(find /tmp/kt_c2_steps6 -name '*.db' | head -1)
   [ -n "$db" ] && python profiles/summarize_rocpd.py "$db" > $OUT/r6_kernel_stats_c2_f16x2_steps6.md 2>&1
-  # the Sinkhorn kernels against each other (product library), then their per-phase timestamps (measurement build)
+  # the Sinkhorn kernels against each other
   bash tools/gpu.sh sk128 > /dev/null 2>&1
-  timeout 400 python tools/skr_timing.py --rows128 2>&1 | grep -v amdgpu.ids > $OUT/skr_rows128.log
-  { echo "# ms per call of 100 iterations incl. the final sweep, one box, alternating (tools/gpu.sh sk128; rows64 = E2EMV_SINKHORN=rows64: the 64-row"; echo "# (32-row at 2048 columns) workgroups only, rows128 / 2k = the kernels with the couplings in registers addressed by number for the whole batch,"; echo "# library's plan = their full rounds + the remainder on whichever is cheaper: what a call gets by default)"; grep " x " $OUT/sk128_time.log; echo; echo "# tests/test_gpu_sinkhorn_resident.py on the same box:"; tail -1 $OUT/sk128_tests.log; echo; echo "# per-phase timestamps (tools/skr_timing.py --rows128, measurement build tools/libe2emv_stamps.bin; workgroup 0's thread 0, iterations 2 - 13):"; cat $OUT/skr_rows128.log; } > $OUT/r6_sinkhorn_rows128.log
+  { echo "# ms per call of 100 iterations incl. the final sweep, one box, alternating (tools/gpu.sh sk128; rows64 = E2EMV_SINKHORN=rows64: the 64-row"; echo "# (32-row at 2048 columns) workgroups only, rows128 / 2k = the kernels with the couplings in registers addressed by number for the whole batch,"; echo "# library's plan = their full rounds + the remainder on whichever is cheaper: what a call gets by default)"; grep " x " $OUT/sk128_time.log; echo; echo "# tests/test_gpu_sinkhorn_resident.py on the same box:"; tail -1 $OUT/sk128_tests.log; } > $OUT/r6_sinkhorn_rows128.log
   echo "at::native launches: steps 2 / steps 6"; grep "at::native" $OUT/r6_kernel_stats_c2_f16x2.md $OUT/r6_kernel_stats_c2_f16x2_steps6.md
   grep "gemm_p2_chain\|attention_p2w" $OUT/r6_kernel_stats_c2_f16x2.md $OUT/r6_kernel_stats_c2_f16x2_steps6.md
   ;;
