@@ -2,7 +2,8 @@
 
 Python surface (mirrors the reference's callables):
   MultiViewMatcher / SuperGlue, estimate_relative_pose_w8pt, run_weighted_8_point, get_kpts,
-  normalize, compute_rotation_error, compute_translation_error_as_angle, pose_auc.
+  normalize, compute_rotation_error, compute_translation_error_as_angle, pose_auc,
+  estimate_pose / estimate_poses_ransac (the RANSAC baseline).
 Everything computes in libe2emv.so (hand-written HIP for gfx950) through ctypes.
 """
 from .matcher import MultiViewMatcher, SuperGlue, last_descriptors  # noqa: F401
@@ -13,6 +14,7 @@ from .pose import (compute_rotation_error, compute_translation_error_as_angle, e
                    get_kpts, mask_confidence, normalize, pose_errors, run_bundle_adjust_2_view,
                    run_weighted_8_point, run_weighted_8_point_tuple)
 
+from .ransac import estimate_pose, estimate_poses_ransac  # noqa: F401,E402
 from .superpoint import SuperPoint  # noqa: F401,E402
 from .targets import (compute_gt_matches_of_image_pair, compute_match_loss, gt_matches_for_tuple,  # noqa: F401,E402
                       relative_pose)
@@ -20,4 +22,5 @@ from .targets import (compute_gt_matches_of_image_pair, compute_match_loss, gt_m
 __all__ = ["SuperPoint", "compute_gt_matches_of_image_pair", "compute_match_loss", "gt_matches_for_tuple", "relative_pose",
            "run_weighted_8_point_tuple", "MultiViewMatcher", "SuperGlue", "estimate_relative_pose_w8pt", "run_weighted_8_point", "get_kpts",
            "run_bundle_adjust_2_view", "normalize", "compute_rotation_error", "compute_translation_error_as_angle", "pose_errors", "pose_auc",
-           "compute_pose_error", "log_optimal_transport", "extract_matches", "gemm_nt", "attention"]
+           "compute_pose_error", "log_optimal_transport", "extract_matches", "gemm_nt", "attention", "estimate_pose",
+           "estimate_poses_ransac"]

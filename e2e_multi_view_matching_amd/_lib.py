@@ -94,6 +94,10 @@ SIGNATURES = {
                                        c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "e2emv_mv_bundle_adjust_files": (c_int, [c_void_p, c_char_p, c_char_p, c_void_p]),
     "e2emv_mv_triangulate": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "e2emv_essential_ransac": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_double, c_int,
+                                       ctypes.c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_void_p]),
+    "e2emv_essential_5pt": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "e2emv_superpoint_commit": (c_int, [c_void_p]),
     "e2emv_superpoint_forward": (c_int, [c_void_p, ctypes.POINTER(SuperPointDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                          c_void_p, c_void_p]),

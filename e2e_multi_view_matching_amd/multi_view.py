@@ -4,7 +4,8 @@ position averaging -> weighted bundle adjustment, keeping the reference's CSV wi
 ``ba_in/out.csv``).
 
 Same function names, arguments, dictionary keys and file layouts as the reference.  What differs is where the work runs:
-* relative poses: the HIP w8pt + two-view BA kernels (``pose.py``) instead of kornia/pytorch3d ops;
+* relative poses: the HIP w8pt + two-view BA kernels (``pose.py``) instead of kornia/pytorch3d ops, and the RANSAC
+  baseline (``ransac.py``: 5-point RANSAC + recoverPose on the device) instead of OpenCV;
 * ``ba_initializer`` / ``bundle_adjuster``: not separate executables built on Theia/Ceres but entry points of
   libe2emv.so called in-process (``run_ba_initializer`` = host C++ averaging, ``run_bundle_adjuster`` = one HIP workgroup
   doing the whole LM/Schur optimisation); ``python -m e2e_multi_view_matching_amd.multi_view ba_initializer <dir>`` and
@@ -24,6 +25,7 @@ from scipy.sparse.csgraph import minimum_spanning_tree
 
 from . import _lib
 from .pose import mask_confidence, run_bundle_adjust_2_view
+from .ransac import estimate_poses_ransac, normalize_keypoints
 
 
 def _dev():
@@ -83,6 +85,52 @@ def estimate_relative_pose_w8pt_ba(intr0, intr1, mkpts0, mkpts1, conf):
     """``estimate_relative_pose_w8pt_ba`` (bundle_adjust_io.py:12-23): numpy in, ``(success, R, t, inliers)`` out - the
     one-pair form of ``relative_poses_w8pt_ba``."""
     return relative_poses_w8pt_ba([(intr0, intr1, mkpts0, mkpts1, conf)])[0]
+
+
+def relative_poses_ransac(problems, ba=False, n_iterations=10):
+    """Relative pose of MANY image pairs by the RANSAC baseline in one device pass: ``estimate_pose(..., thresh=1.0)``
+    (5-point RANSAC + recoverPose, ``ransac.py``) for all pairs, then with ``ba`` the two-view bundle adjustment of every
+    solved pair on its RANSAC inliers only, weighted by their confidences and started from the RANSAC pose (one batched
+    launch; zero-weight padding rows do not enter it).  ``problems`` = list of ``(intr0, intr1, mkpts0 [n,2], mkpts1 [n,2],
+    conf [n,c])``; returns one ``(success, R, t, inliers)`` per problem with the meaning of the reference's
+    ``estimate_relative_pose_ransac`` / ``estimate_relative_pose_ransac_ba`` (bundle_adjust_io.py:25-58)."""
+    poses = estimate_poses_ransac([(m0, m1, K0, K1) for K0, K1, m0, m1, _ in problems], thresh=1.0)
+    out = [(False, None, None, None) if r is None else (True, r[0], r[1], r[2]) for r in poses]
+    solved = [q for q, r in enumerate(poses) if r is not None]
+    if not ba or not solved:
+        return out
+    dev = _dev()
+    n_in = [int(poses[q][2].sum()) for q in solved]
+    Pn, Nmax = len(solved), max(n_in)
+    k0, k1 = np.zeros((Pn, Nmax, 2), np.float32), np.zeros((Pn, Nmax, 2), np.float32)
+    cf = np.zeros((Pn, Nmax), np.float32)
+    T0 = np.tile(np.eye(4, dtype=np.float32), (Pn, 1, 1))
+    for r, q in enumerate(solved):
+        K0, K1, m0, m1, conf = problems[q]
+        R, t, inl = poses[q]
+        k0[r, :n_in[r]] = normalize_keypoints(m0[inl], K0)
+        k1[r, :n_in[r]] = normalize_keypoints(m1[inl], K1)
+        cf[r, :n_in[r]] = np.asarray(conf).reshape(len(m0), -1)[inl, 0]
+        T0[r, :3, :3], T0[r, :3, 3] = R, t
+    up = lambda a: torch.from_numpy(a).to(dev)  # noqa: E731
+    T = up(T0)
+    refined, ok = run_bundle_adjust_2_view(up(k0), up(k1), up(cf), T, n_iterations=n_iterations)
+    T[ok] = refined
+    T_h = T.cpu().numpy()
+    for r, q in enumerate(solved):
+        out[q] = (True, T_h[r, :3, :3], T_h[r, :3, 3], poses[q][2])
+    return out
+
+
+def estimate_relative_pose_ransac(intr0, intr1, mkpts0, mkpts1):
+    """``estimate_relative_pose_ransac`` (bundle_adjust_io.py:44-54): ``(success, R, t, inliers)``."""
+    return relative_poses_ransac([(intr0, intr1, mkpts0, mkpts1, np.ones((len(mkpts0), 1), np.float32))])[0]
+
+
+def estimate_relative_pose_ransac_ba(intr0, intr1, mkpts0, mkpts1, conf):
+    """``estimate_relative_pose_ransac_ba`` (bundle_adjust_io.py:25-42): RANSAC, then the two-view bundle adjustment on the
+    inliers weighted by ``conf[inliers]``; ``(success, R, t, inliers)``."""
+    return relative_poses_ransac([(intr0, intr1, mkpts0, mkpts1, conf)], ba=True)[0]
 
 
 def _pairs(n_images):
@@ -150,23 +198,30 @@ def _chain_along_tree(n_images, edges, rel_pose):
 
 
 def initialize_bundle_adjust(n_images, data, result, file_path, conf_thresh=0., rel_pose_method="w8pt_ba"):
-    """``initialize_bundle_adjust`` (bundle_adjust_io.py:62-191): matches of batch element 0 -> pairwise poses (w8pt + two-view
-    BA on the device) -> maximum spanning tree of the inlier-count graph -> chained absolute poses -> ``ba_init_in.csv``.
+    """``initialize_bundle_adjust`` (bundle_adjust_io.py:62-191): matches of batch element 0 -> pairwise poses on the device
+    (``rel_pose_method`` "w8pt_ba": w8pt + two-view BA; "ransac" / "ransac_ba": the RANSAC baseline, without / with two-view
+    BA on its inliers) -> maximum spanning tree of the inlier-count graph -> chained absolute poses -> ``ba_init_in.csv``.
     Returns the reference's ``pair_wise_data`` dictionary (same keys)."""
-    if rel_pose_method != "w8pt_ba":
-        # the "ransac" / "ransac_ba" variants call OpenCV's findEssentialMat (absent submodule + absent cv2): out of scope
-        raise NotImplementedError("relative pose method {} needs OpenCV RANSAC, which is outside this back-end".format(rel_pose_method))
+    if rel_pose_method not in ("w8pt_ba", "ransac", "ransac_ba"):
+        raise NotImplementedError("relative pose method {} is not defined".format(rel_pose_method))
+    ransac = rel_pose_method != "w8pt_ba"
     min_inliers = 20
     pw = _collect_matches(n_images, data, result, conf_thresh)
     graph = np.zeros((n_images, n_images), dtype=int)
     rel = {}
     have = [(i, j) for i, j in _pairs(n_images) if _key("mkpts", str(i), i, j) in pw]
     # all pairs of the tuple in one device pass (they differ in their number of matches)
-    solved = relative_poses_w8pt_ba([(pw["intr" + str(i)], pw["intr" + str(j)], pw[_key("mkpts", str(i), i, j)],
-                                      pw[_key("mkpts", str(j), i, j)], pw[_key("conf", str(i), i, j)]) for i, j in have])
+    problems = [(pw["intr" + str(i)], pw["intr" + str(j)], pw[_key("mkpts", str(i), i, j)], pw[_key("mkpts", str(j), i, j)],
+                 pw[_key("conf", str(i), i, j)]) for i, j in have]
+    solved = relative_poses_ransac(problems, ba=rel_pose_method == "ransac_ba") if ransac else relative_poses_w8pt_ba(problems)
     for (i, j), (ok, R, t, inl) in zip(have, solved):
-        # every match is kept for the bundle adjustment; the inlier count only weights the match graph (:111-113, :133)
+        # w8pt_ba: every match is kept for the bundle adjustment, the inlier count only weights the match graph (:111-113,
+        # :133); ransac / ransac_ba: matches and confidences are filtered to the RANSAC inliers (:104-131)
         pw[_key("inlier_count", i, j)] = inl.sum() if ok else 0
+        if ok and ransac:
+            for v in (i, j):
+                pw[_key("mkpts", str(v), i, j)] = pw[_key("mkpts", str(v), i, j)][inl]
+                pw[_key("conf", str(v), i, j)] = pw[_key("conf", str(v), i, j)][inl]
         if ok:
             T = np.eye(4)
             T[:3, :3], T[:3, 3] = R, t

@@ -260,6 +260,32 @@ int e2emv_mv_bundle_adjust_files(e2emv_ctx* ctx, const char* in_csv, const char*
 int e2emv_mv_triangulate(e2emv_ctx* ctx, int n, const double* P0, const double* P1, const double* x0, const double* x1,
                          double* xyz, void* stream);
 
+/* ---- RANSAC essential matrix (SuperGlue's estimate_pose: OpenCV findEssentialMat(RANSAC) + recoverPose) ------------
+ * A ragged batch of P problems in one call, no host synchronisation inside: problem p uses its first d_n_per[p]
+ * (0 <= n <= Mmax <= 4096) rows of d_kpts0n / d_kpts1n [P,Mmax,2] fp64, keypoints already NORMALISED by their
+ * intrinsics, and the normalised threshold d_thresh[p] (fp64).  RANSAC with the 5-point solver: up to max_iters
+ * iterations (upstream: 1000), confidence conf; a match is an inlier of E iff its squared Sampson distance is
+ * <= thresh^2; a model replaces the best only with strictly more inliers than max(best, 4), and every new best lowers the
+ * iteration count to RANSACUpdateNumIters(conf, outlier share, 5, count).  n == 5: no sampling, every solution of the
+ * minimal problem is a candidate and the mask is all ones.  Then recoverPose (distance threshold 1e9) of each candidate,
+ * restricted to the mask; the candidate with the most points in front of both cameras is kept, only if that count > 0.
+ * Sample stream: iteration i draws d = 0, 1, 2, ... -> index floor(h * n / 2^32),
+ *   h = mix(mix(mix(seed ^ 0x9E3779B9) ^ i) ^ d),  mix(x): x ^= x>>16; x *= 0x7feb352d; x ^= x>>15; x *= 0x846ca68b; x ^= x>>16
+ * (uint32 arithmetic), an index equal to an earlier pick of the iteration is drawn again; 64 draws without 5 distinct
+ * picks leave the iteration without a model.  The batch position is not an input: a problem's result does not depend on
+ * the other problems.
+ * Outputs per problem: d_E, d_R [P,3,3], d_t [P,3] fp64 (zeros unless status 0); d_inliers [P,Mmax] u8 the RANSAC inlier
+ * mask (padding rows 0); d_n_inliers its count; d_n_cheiral recoverPose's count of the kept candidate; d_iters the
+ * RANSAC iterations run (1 for n == 5); d_status 0 ok, 1 fewer than 5 matches, 2 RANSAC found no model, 3 no candidate
+ * with a point in front of both cameras, 4 n outside [0, Mmax]. */
+int e2emv_essential_ransac(e2emv_ctx* ctx, int P, int Mmax, const int32_t* d_n_per, const double* d_kpts0n, const double* d_kpts1n,
+                           const double* d_thresh, double conf, int max_iters, uint32_t seed, double* d_E, double* d_R, double* d_t,
+                           uint8_t* d_inliers, int32_t* d_n_inliers, int32_t* d_n_cheiral, int32_t* d_iters, int32_t* d_status,
+                           void* stream);
+/* The 5-point minimal solver alone: n problems of 5 normalised correspondences d_x0, d_x1 [n,5,2] fp64 -> every real
+ * essential matrix, d_E [n,10,3,3] (unit Frobenius norm, rows beyond d_nsol[i] zero), d_nsol [n] int32 (0..10). */
+int e2emv_essential_5pt(e2emv_ctx* ctx, int n, const double* d_x0, const double* d_x1, double* d_E, int32_t* d_nsol, void* stream);
+
 /* ---- SuperPoint front-end --------------------------------------
  * Replaces models.models.superpoint.SuperPoint (absent submodule; call sites helpers.py:73-96, configs train.py:335-341,
  * eval_pairs.py:197-202, eval_multi_view.py:135-140) = upstream magicleap SuperPoint.  Weights go in through
