@@ -18,6 +18,7 @@ MAX_TUPLE, MAX_LAYERS, MAX_KENC, PROF_SLOTS = 8, 64, 8, 16
 FLAG_FULL_OUTPUT, FLAG_MULTI_FRAME = 1, 2
 DESC_F32, DESC_F16 = 0, 1
 OK, EINVAL, ENOMEM, EHIP, ESHAPE, ESTATE = 0, -1, -2, -3, -4, -5
+BN_FROZEN, BN_BATCH = 0, 1  # e2emv_train_set_batchnorm
 PRECISION_F32, PRECISION_BF16X3, PRECISION_F16X2 = 0, 1, 2
 PRECISION_NAMES = {"f32": PRECISION_F32, "bf16x3": PRECISION_BF16X3, "f16x2": PRECISION_F16X2,
                    "f16x2-r4": PRECISION_F16X2, "f16x2-chain": PRECISION_F16X2}  # "-r4" / "-chain": the same arithmetic, other kernels
@@ -124,6 +125,8 @@ SIGNATURES = {
     "e2emv_conf_forward_train": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "e2emv_matcher_backward": (c_int, [c_void_p, _PP, _PP, c_void_p]),
     "e2emv_get_grad": (c_int, [c_void_p, c_char_p, c_void_p, c_int64, c_void_p]),
+    "e2emv_train_set_batchnorm": (c_int, [c_void_p, c_int, ctypes.c_float]),
+    "e2emv_train_running_update": (c_int, [c_void_p, c_int, ctypes.POINTER(ctypes.c_char_p), _PP, _PP, c_void_p]),
     "e2emv_w8pt_backward": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "e2emv_pose_errors_backward": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "e2emv_get_stats": (c_int, [c_void_p, ctypes.POINTER(ctypes.c_uint64), c_int, c_int]),

@@ -148,6 +148,8 @@ struct e2emv_ctx {
     // drained first, because the arena contents of the earlier call may still be in use there.
     std::recursive_mutex mu;
     void* train = nullptr;  // e2emv::TrainState (train.hip)
+    int train_bn_mode = E2EMV_BN_FROZEN;  // BatchNorm of the training path (e2emv_train_set_batchnorm); the arena records the mode it was built with
+    float train_bn_momentum = 0.1f;
     // matched descriptors (final_proj output) of the last forward_joint call, in the workspace: [md_imgs][md_rows][md_dim] fp32
     const float* last_mdesc = nullptr;
     int md_imgs = 0, md_rows = 0, md_n = 0, md_dim = 0;

@@ -7,10 +7,11 @@
 // matrix, the dustbin score, the unrolled log-domain Sinkhorn (the reverse sweep walks the stored u_t, v_t of every
 // iteration - the same gradient torch.autograd computes through upstream's log_optimal_transport, not an implicit
 // differentiation) and the conf_mlp head (e2emv_conf_forward_train; the pose loss reaches it through pose.hip's
-// e2emv_w8pt_backward).  BatchNorm layers normalise with their RUNNING statistics (frozen-statistics fine-tuning; the
-// reference builds its DDP wrapper with broadcast_buffers=False "until BatchNorm stats are updated", train.py:351-356);
-// their affine parameters get gradients through the folded convolution.  Still forward-only: batch-statistics BatchNorm,
-// ragged keypoint counts, the confidences of a model without conf_mlp (the match score).
+// e2emv_w8pt_backward).  BatchNorm layers normalise with their RUNNING statistics (E2EMV_BN_FROZEN, frozen-statistics
+// fine-tuning: the reference builds its DDP wrapper with broadcast_buffers=False "until BatchNorm stats are updated",
+// train.py:351-356; their affine parameters get gradients through the folded convolution) or with the statistics of the
+// batch (E2EMV_BN_BATCH, torch's training-mode BatchNorm1d: the BN layers stay unfolded, bn_* kernels of train_kernels.h).
+// Still forward-only: ragged keypoint counts, the confidences of a model without conf_mlp (the match score).
 //
 // The backward is a sequence of general fp32 MFMA GEMMs (dgrad: dY W, wgrad: dY^T X with the row contraction split over
 // workgroups) and row-wise kernels; the attention backward re-computes the probabilities from the saved q|k|v.
@@ -69,6 +70,20 @@ struct TrainState {
     float* t_uv = nullptr;                // [P*B][iters + 1][2][N + 1]: u_t, v_t (t = 0: zeros)
     std::vector<float*> t_cfeat, t_chid;  // conf head, per pair: [B][N][2D] input, [B][N][D] hidden (post ReLU)
     std::vector<const int64_t*> t_cmatch; // matches the conf head of a pair was run with (caller's buffer, must stay alive until backward)
+    // batch-statistics BatchNorm (bn_mode E2EMV_BN_BATCH): the BatchNorm layers are NOT folded into their convolutions; the tape
+    // keeps each one's conv output y and the statistics of every call
+    int bn_mode = E2EMV_BN_FROZEN;
+    struct Bn {
+        std::string name;     // module prefix (kenc.encoder.{1,4,..}, gnn.layers.{l}.mlp.1, conf_mlp.1)
+        int C;
+        size_t gamma, beta;   // offsets in the raw arena (and in the raw gradient arena)
+    };
+    std::vector<Bn> bns;                  // encoder BNs 1 .. nk-1 (bns[j - 1]), then the L GNN MLPs, then conf_mlp.1
+    std::vector<float*> t_ky, t_kst;      // encoder BN j (j = 1 .. nk-1): y [Mtot][kdims[j]], statistics [T][3][kdims[j]]
+    std::vector<float*> t_hy, t_hst;      // GNN layer l: y [Mtot][2D], statistics [T][3][2D]
+    std::vector<float*> t_cy;             // conf head of pair q: y [B*N][D]
+    float* t_cst = nullptr;               // [P][3][D]
+    double* t_part = nullptr;             // forward partial sums (bn_chunks_max x calls x 2 x C doubles)
 };
 
 static TrainState* ts_of(e2emv_ctx* ctx) { return static_cast<TrainState*>(ctx->train); }
@@ -121,6 +136,43 @@ static int colsum(e2emv_ctx* ctx, const float* X, int64_t rows, int N, int64_t l
 }
 static unsigned ew_grid(int64_t n) { return (unsigned)std::min<int64_t>((n + 255) / 256, 4096); }
 
+// ---- batch-statistics BatchNorm launches (train_kernels.h, BnCall) ----
+constexpr int BN_MAX_CHUNKS = 64;  // (64 rows per chunk: 16 per thread, 4 steps of 4 loads in flight)
+static int bn_chunks(int64_t rows) { return (int)std::max<int64_t>(1, std::min<int64_t>(BN_MAX_CHUNKS, (rows + 63) / 64)); }
+// BN `j` of the tape over the T images ([b][t][n_rows][C] arena): one call per image
+static BnCall bn_images(const TrainState* t, int j, float* y, float* out, float* stats, double* part) {
+    BnCall a;
+    const TrainState::Bn& bn = t->bns[j];
+    a.y = y; a.out = out; a.stats = stats; a.part = part;
+    a.gamma = t->d_raw + bn.gamma; a.beta = t->d_raw + bn.beta;
+    a.dgamma = t->d_graw + bn.gamma; a.dbeta = t->d_graw + bn.beta;
+    a.C = bn.C; a.N = t->N; a.nseg = t->B; a.seg_rows = t->n_rows;
+    a.seg_stride = (int64_t)t->T * t->n_rows; a.z_stride = t->n_rows;
+    a.chunks = bn_chunks((int64_t)t->B * t->N);
+    return a;
+}
+// conf_mlp.1 on one pair's dense [B*N][D] features: one call
+static BnCall bn_conf(const TrainState* t, float* y, float* out, float* stats, double* part) {
+    BnCall a = bn_images(t, (int)t->bns.size() - 1, y, out, stats, part);
+    a.N = a.seg_rows = t->B * t->N; a.nseg = 1; a.seg_stride = 0; a.z_stride = 0;
+    return a;
+}
+static int bn_forward(e2emv_ctx* ctx, const BnCall& a, int calls, hipStream_t s) {
+    const dim3 grid((a.C + 63) / 64, a.chunks, calls);
+    hipLaunchKernelGGL(bn_stats_kernel, grid, dim3(256), 0, s, a, 0);
+    hipLaunchKernelGGL(bn_stats_kernel, grid, dim3(256), 0, s, a, 1);
+    hipLaunchKernelGGL(bn_apply_kernel, grid, dim3(256), 0, s, a);
+    E2EMV_CHECK_LAUNCH(ctx, "batchnorm forward kernels");
+    return E2EMV_OK;
+}
+static int bn_backward(e2emv_ctx* ctx, const BnCall& a, int calls, hipStream_t s) {
+    const dim3 grid((a.C + 63) / 64, a.chunks, calls);
+    hipLaunchKernelGGL(bn_bwd_stats_kernel, grid, dim3(256), 0, s, a);
+    hipLaunchKernelGGL(bn_bwd_apply_kernel, grid, dim3(256), 0, s, a);
+    E2EMV_CHECK_LAUNCH(ctx, "batchnorm backward kernels");
+    return E2EMV_OK;
+}
+
 }  // namespace e2emv
 
 using namespace e2emv;
@@ -165,6 +217,10 @@ int conv_bn(e2emv_ctx* ctx, TrainState* t, Pack& raw, const std::string& prefix,
     t->raw[bn + ".bias"] = {raw.add(be->data), (size_t)out};
     t->raw[bn + ".running_mean"] = {raw.add(mean->data), (size_t)out};
     t->raw[bn + ".running_var"] = {raw.add(var->data), (size_t)out};
+    if (t->bn_mode == E2EMV_BN_BATCH) {  // batch statistics: the convolution stays raw, the BatchNorm runs on the tape
+        t->bns.push_back({bn, out, t->raw[bn + ".weight"].off, t->raw[bn + ".bias"].off});
+        return E2EMV_OK;
+    }
     for (int o = 0; o < out; ++o) {
         const double sc = (double)g->data[o] / std::sqrt((double)var->data[o] + 1e-5);
         for (int i = 0; i < in; ++i) w[(size_t)o * in + i] = (float)((double)w[(size_t)o * in + i] * sc);
@@ -243,6 +299,8 @@ static int train_build(e2emv_ctx* ctx, const e2emv_model_desc* m, TrainState* t,
     t->bin_score = bs->data[0];
     t->alpha = pk.add(std::vector<float>{bs->data[0]});
     t->raw["bin_score"] = {raw.add(bs->data), 1};
+    if (t->bn_mode == E2EMV_BN_BATCH && t->bns.size() != (size_t)(nk - 1 + m->n_layers + (t->conf_mlp ? 1 : 0)))
+        return set_err(ctx, E2EMV_ESTATE, "train_commit: batch-statistics BatchNorm needs every BatchNorm's running_mean / running_var");
     t->w_floats = pk.host.size();
     t->raw_floats = raw.host.size();
     return E2EMV_OK;
@@ -256,6 +314,7 @@ extern "C" int e2emv_train_commit(e2emv_ctx* ctx, const e2emv_model_desc* m) {
     if (m->n_kenc < 1 || m->n_kenc > E2EMV_MAX_KENC || m->n_layers < 0 || m->n_layers > E2EMV_MAX_LAYERS) return set_err(ctx, E2EMV_ESHAPE, "train_commit: bad layer counts");
     (void)hipSetDevice(ctx->device);
     TrainState* t = new TrainState();
+    t->bn_mode = ctx->train_bn_mode;
     Pack pk, raw;
     {   // (every optimiser step comes through here: no re-allocation while the ~50 MB packs grow)
         const TrainState* prev = ts_of(ctx);
@@ -313,6 +372,8 @@ extern "C" int e2emv_train_update(e2emv_ctx* ctx, const e2emv_model_desc* m, int
     TrainState* t = ts_of(ctx);
     if (!t || !t->d_w || !t->d_raw || !t->d_maps || memcmp(&t->model, m, sizeof(*m)) != 0)
         return set_err(ctx, E2EMV_ESTATE, "train_update: no training arena of this model on the context (e2emv_train_commit first)");
+    if (t->bn_mode != ctx->train_bn_mode)
+        return set_err(ctx, E2EMV_ESTATE, "train_update: the BatchNorm mode changed since e2emv_train_commit (commit again)");
     (void)hipSetDevice(ctx->device);
     hipStream_t s = (hipStream_t)stream;
     // pass 1 validates every entry, pass 2 enqueues: a rejected call leaves the raw arena, the folded weights and the tape as
@@ -342,7 +403,7 @@ extern "C" int e2emv_train_update(e2emv_ctx* ctx, const e2emv_model_desc* m, int
     auto fold = [&](const std::string& conv, const std::string& bn, float* Wf, float* bf, int64_t ldwf, int rows, int cols, const int* rmap, int rbase, const int* cmap) {
         FoldArgs a{};
         a.W = ref(conv + ".weight"); a.b = ref(conv + ".bias");
-        if (!bn.empty() && ref(bn + ".running_mean")) { a.gamma = ref(bn + ".weight"); a.beta = ref(bn + ".bias"); a.mean = ref(bn + ".running_mean"); a.var = ref(bn + ".running_var"); }
+        if (!bn.empty() && ref(bn + ".running_mean") && t->bn_mode == E2EMV_BN_FROZEN) { a.gamma = ref(bn + ".weight"); a.beta = ref(bn + ".bias"); a.mean = ref(bn + ".running_mean"); a.var = ref(bn + ".running_var"); }
         a.Wf = Wf + (int64_t)rbase * ldwf; a.bf = bf + rbase; a.ldwf = ldwf; a.col0 = 0; a.rows = rows; a.cols = cols; a.rmap = rmap; a.cmap = cmap;
         hipLaunchKernelGGL(fold_kernel, dim3(rows), dim3(256), 0, s, a);
     };
@@ -384,6 +445,10 @@ extern "C" int e2emv_matcher_forward_train(e2emv_ctx* ctx, const e2emv_forward_d
     for (int i = 0; i < T; ++i)
         if (fd->n_kpts_img[i] > 0 && fd->n_kpts_img[i] != N) return set_err(ctx, E2EMV_ESHAPE, "matcher_forward_train: all images of a call carry the same number of keypoints");
     if (fd->sinkhorn_iters < 0) return set_err(ctx, E2EMV_EINVAL, "negative sinkhorn_iters");
+    if (t->bn_mode != ctx->train_bn_mode)
+        return set_err(ctx, E2EMV_ESTATE, "matcher_forward_train: the BatchNorm mode changed since e2emv_train_commit (commit again)");
+    const bool bnb = t->bn_mode == E2EMV_BN_BATCH;
+    if (bnb && (int64_t)B * N < 2) return set_err(ctx, E2EMV_ESHAPE, "matcher_forward_train: batch statistics need more than one value per channel");
     (void)hipSetDevice(ctx->device);
     hipStream_t s = (hipStream_t)stream;
     const int n_rows = (N + 127) / 128 * 128, n_img = B * T, P = T * (T - 1) / 2, iters = fd->sinkhorn_iters, ldS = (N + 3) / 4 * 4;
@@ -395,6 +460,12 @@ extern "C" int e2emv_matcher_forward_train(e2emv_ctx* ctx, const e2emv_forward_d
     need += (size_t)(L + 1) * al256((size_t)Mtot * D * 4) + (size_t)L * (al256((size_t)Mtot * 3 * D * 4) + 2 * al256((size_t)Mtot * D * 4) + al256((size_t)Mtot * 2 * D * 4));
     need += al256((size_t)Mtot * D * 4) + al256((size_t)P * B * N * ldS * 4) + al256((size_t)P * B * (iters + 1) * 2 * (N + 1) * 4);
     if (t->conf_mlp) need += (size_t)P * (al256((size_t)B * N * 2 * D * 4) + al256((size_t)B * N * D * 4));
+    if (bnb) {  // y and the statistics of every BatchNorm, the partial sums
+        for (int j = 1; j < nk; ++j) need += al256((size_t)Mtot * t->kdims[j] * 4) + al256((size_t)T * 3 * t->kdims[j] * 4);
+        need += (size_t)L * (al256((size_t)Mtot * 2 * D * 4) + al256((size_t)T * 3 * 2 * D * 4));
+        if (t->conf_mlp) need += (size_t)P * al256((size_t)B * N * D * 4) + al256((size_t)P * 3 * D * 4);
+        need += al256((size_t)T * BN_MAX_CHUNKS * 2 * 2 * D * 8);
+    }
     if (need > t->tape_bytes) {
         E2EMV_HIP(ctx, hipDeviceSynchronize());
         if (t->d_tape) E2EMV_HIP(ctx, hipFree(t->d_tape));
@@ -430,6 +501,17 @@ extern "C" int e2emv_matcher_forward_train(e2emv_ctx* ctx, const e2emv_forward_d
             t->t_cfeat[q] = take((size_t)B * N * 2 * D * 4);
             t->t_chid[q] = take((size_t)B * N * D * 4);
         }
+    t->t_ky.assign(nk, nullptr); t->t_kst.assign(nk, nullptr); t->t_hy.assign(L, nullptr); t->t_hst.assign(L, nullptr); t->t_cy.assign(P, nullptr);
+    t->t_cst = nullptr; t->t_part = nullptr;
+    if (bnb) {
+        for (int j = 1; j < nk; ++j) { t->t_ky[j] = take((size_t)Mtot * t->kdims[j] * 4); t->t_kst[j] = take((size_t)T * 3 * t->kdims[j] * 4); }
+        for (int l = 0; l < L; ++l) { t->t_hy[l] = take((size_t)Mtot * 2 * D * 4); t->t_hst[l] = take((size_t)T * 3 * 2 * D * 4); }
+        if (t->conf_mlp) {
+            for (int q = 0; q < P; ++q) t->t_cy[q] = take((size_t)B * N * D * 4);
+            t->t_cst = take((size_t)P * 3 * D * 4);
+        }
+        t->t_part = (double*)take((size_t)T * BN_MAX_CHUNKS * 2 * 2 * D * 8);
+    }
     t->B = B; t->T = T; t->N = N; t->n_rows = n_rows; t->iters = iters; t->P = P; t->ldS = ldS; t->Mtot = Mtot;
     t->have_tape = false;
 
@@ -448,16 +530,24 @@ extern "C" int e2emv_matcher_forward_train(e2emv_ctx* ctx, const e2emv_forward_d
     hipLaunchKernelGGL(ingest_kenc0, dim3((n_rows + 255) / 256, n_img), dim3(256), 0, s, ip);
     E2EMV_CHECK_LAUNCH(ctx, "ingest kernels");
     int rc;
+    if (bnb) {  // layer 0 again, without the BatchNorm ingest_kenc0 fuses: y, then the batch-statistics BN + ReLU over t_kh[1]
+        const int c0 = t->kdims[1];
+        hipLaunchKernelGGL(kenc0_conv_kernel, dim3(ew_grid(Mtot * c0)), dim3(256), 0, s, (const float*)t->t_inp, (const float*)t->d_w + t->kw[0],
+                           (const float*)t->d_w + t->kb[0], c0, Mtot, t->t_ky[1]);
+        E2EMV_CHECK_LAUNCH(ctx, "kenc0_conv_kernel");
+        if ((rc = bn_forward(ctx, bn_images(t, 0, t->t_ky[1], t->t_kh[1], t->t_kst[1], t->t_part), T, s))) return rc;
+    }
     // encoder layers 1 .. nk-1; the last adds the descriptors (x_0 = desc + kenc)
     for (int i = 1; i < nk; ++i) {
         const int cin = t->kdims[i], cout = t->kdims[i + 1];
         const bool last = i == nk - 1;
         GemmArgs g;
         g.M = (int)Mtot; g.N = cout; g.K = cin; g.K1 = cin; g.A = t->t_kh[i]; g.lda = cin;
-        g.W = t->d_w + t->kw[i]; g.ldw = cin; g.bias = t->d_w + t->kb[i]; g.relu = !last;
+        g.W = t->d_w + t->kw[i]; g.ldw = cin; g.bias = t->d_w + t->kb[i]; g.relu = !last && !bnb;
         if (last) { g.R = t->t_x[0]; g.ldr = D; g.C = t->t_x[0]; g.ldc = D; }
-        else { g.C = t->t_kh[i + 1]; g.ldc = cout; }
+        else { g.C = bnb ? t->t_ky[i + 1] : t->t_kh[i + 1]; g.ldc = cout; }
         if ((rc = launch_gemm_nt(ctx, g, s))) return rc;
+        if (bnb && !last && (rc = bn_forward(ctx, bn_images(t, i, t->t_ky[i + 1], t->t_kh[i + 1], t->t_kst[i + 1], t->t_part), T, s))) return rc;
     }
     // ---- attentional GNN (merge NOT folded: its parameters get their own gradients) ----
     for (int l = 0; l < L; ++l) {
@@ -473,8 +563,9 @@ extern "C" int e2emv_matcher_forward_train(e2emv_ctx* ctx, const e2emv_forward_d
         if ((rc = launch_gemm_nt(ctx, g, s))) return rc;
         g = GemmArgs();
         g.M = (int)Mtot; g.N = 2 * D; g.K = 2 * D; g.K1 = D; g.A = t->t_x[l]; g.lda = D; g.A2 = t->t_msg[l]; g.lda2 = D;
-        g.W = t->d_w + Lw.w0; g.ldw = 2 * D; g.bias = t->d_w + Lw.b0; g.relu = true; g.C = t->t_h[l]; g.ldc = 2 * D;
+        g.W = t->d_w + Lw.w0; g.ldw = 2 * D; g.bias = t->d_w + Lw.b0; g.relu = !bnb; g.C = bnb ? t->t_hy[l] : t->t_h[l]; g.ldc = 2 * D;
         if ((rc = launch_gemm_nt(ctx, g, s))) return rc;
+        if (bnb && (rc = bn_forward(ctx, bn_images(t, nk - 1 + l, t->t_hy[l], t->t_h[l], t->t_hst[l], t->t_part), T, s))) return rc;
         g = GemmArgs();
         g.M = (int)Mtot; g.N = D; g.K = 2 * D; g.K1 = 2 * D; g.A = t->t_h[l]; g.lda = 2 * D; g.W = t->d_w + Lw.w1; g.ldw = 2 * D; g.bias = t->d_w + Lw.b1;
         g.R = t->t_x[l]; g.ldr = D; g.C = t->t_x[l + 1]; g.ldc = D;
@@ -546,8 +637,11 @@ extern "C" int e2emv_conf_forward_train(e2emv_ctx* ctx, int pair, const int64_t*
     E2EMV_CHECK_LAUNCH(ctx, "conf_feat_kernel");
     GemmArgs g;
     g.M = B * N; g.N = D; g.K = 2 * D; g.K1 = 2 * D; g.A = feat; g.lda = 2 * D; g.W = t->d_w + t->wc0; g.ldw = 2 * D; g.bias = t->d_w + t->bc0;
-    g.relu = true; g.C = hid; g.ldc = D;
+    const bool bnb = t->bn_mode == E2EMV_BN_BATCH;
+    g.relu = !bnb; g.C = bnb ? t->t_cy[pair] : hid; g.ldc = D;
     if (int rc = launch_gemm_nt(ctx, g, s)) return rc;
+    if (bnb)
+        if (int rc = bn_forward(ctx, bn_conf(t, t->t_cy[pair], hid, t->t_cst + (int64_t)pair * 3 * D, t->t_part), 1, s)) return rc;
     hipLaunchKernelGGL(conf_fwd_kernel, dim3((unsigned)(((int64_t)B * N + 3) / 4)), dim3(256), 0, s, (int64_t)B * N, D, (const float*)hid,
                        (const float*)t->d_w + t->wc1, (const float*)t->d_w + t->bc1, d_matches0, d_conf);
     E2EMV_CHECK_LAUNCH(ctx, "conf_fwd_kernel");
@@ -623,7 +717,9 @@ extern "C" int e2emv_matcher_backward(e2emv_ctx* ctx, const float* const* d_dlog
     const size_t sz_x = al256((size_t)Mtot * D * 4), sz_2 = al256((size_t)Mtot * 2 * D * 4), sz_3 = al256((size_t)Mtot * 3 * D * 4);
     const size_t sz_C = al256((size_t)B * (N + 1) * (N + 1) * 4), sz_v = al256((size_t)B * (N + 1) * 4);
     const size_t sz_P = al256((size_t)B * H * N * n_src_max * N * 4);
-    const size_t need = 3 * sz_x + 2 * sz_2 + sz_3 + sz_C + 3 * sz_v + 2 * sz_P + 4096;
+    const bool bnb = t->bn_mode == E2EMV_BN_BATCH;
+    const size_t sz_bn = bnb ? al256((size_t)T * BN_MAX_CHUNKS * 2 * 2 * D * 8) : 0;
+    const size_t need = 3 * sz_x + 2 * sz_2 + sz_3 + sz_C + 3 * sz_v + 2 * sz_P + sz_bn + 4096;
     int rc = ws_reserve(ctx, need);
     if (rc) return rc;
     char* w = ctx->d_ws;
@@ -640,6 +736,7 @@ extern "C" int e2emv_matcher_backward(e2emv_ctx* ctx, const float* const* d_dlog
     float* dv2 = take(sz_v);
     float* Pb = take(sz_P);
     float* dPb = take(sz_P);
+    double* bpart = bnb ? (double*)take(sz_bn) : nullptr;
     float* gw = t->d_gw;
     const float* W = t->d_w;
     E2EMV_HIP(ctx, hipMemsetAsync(gw, 0, t->w_floats * sizeof(float), s));
@@ -689,6 +786,10 @@ extern "C" int e2emv_matcher_backward(e2emv_ctx* ctx, const float* const* d_dlog
             if ((rc = launch_gg(ctx, g, s))) return rc;
         }
     // ---- confidence heads (pose loss): d conf -> conf_mlp gradients and two more contributions to d mdesc ----
+    if (bnb && t->conf_mlp) {  // conf_mlp.1's dgamma / dbeta are summed over the pairs below (zero when no pair has a d conf)
+        E2EMV_HIP(ctx, hipMemsetAsync(t->d_graw + t->bns.back().gamma, 0, (size_t)D * sizeof(float), s));
+        E2EMV_HIP(ctx, hipMemsetAsync(t->d_graw + t->bns.back().beta, 0, (size_t)D * sizeof(float), s));
+    }
     if (d_dconf && t->conf_mlp) {
         int q = 0;
         for (int j = 0; j < T; ++j)
@@ -704,11 +805,17 @@ extern "C" int e2emv_matcher_backward(e2emv_ctx* ctx, const float* const* d_dlog
                 E2EMV_CHECK_LAUNCH(ctx, "conf_bwd_kernel");
                 if ((rc = wgrad(ctx, dz, 1, 1, t->t_chid[q], D, D, rows, gw + t->wc1, D, s))) return rc;
                 if ((rc = colsum(ctx, dz, rows, 1, 1, gw + t->bc1, s))) return rc;
+                if (bnb) {  // dhc: d hidden (ReLU mask applied) -> d y of conf_mlp.0
+                    BnCall a = bn_conf(t, t->t_cy[q], dhc, t->t_cst + (int64_t)q * 3 * D, bpart);
+                    a.h = t->t_chid[q];
+                    a.accumulate = 1;
+                    if ((rc = bn_backward(ctx, a, 1, s))) return rc;
+                }
                 if ((rc = wgrad(ctx, dhc, D, D, t->t_cfeat[q], 2 * D, 2 * D, rows, gw + t->wc0, 2 * D, s))) return rc;
                 if ((rc = colsum(ctx, dhc, rows, D, D, gw + t->bc0, s))) return rc;
                 if ((rc = dgrad(ctx, dhc, D, D, W + t->wc0, 2 * D, 2 * D, rows, dfeat, 2 * D, false, s))) return rc;
                 hipLaunchKernelGGL(conf_scatter_kernel, dim3((N + 3) / 4, B), dim3(256), 0, s, N, D, (const float*)dfeat, t->t_cmatch[q],
-                                   dmd + (int64_t)i * n_rows * D, dmd + (int64_t)j * n_rows * D, tuple_stride);
+                                   dmd + (int64_t)i * n_rows * D, dmd + (int64_t)j * n_rows * D, tuple_stride, bnb ? 1 : 0);
                 E2EMV_CHECK_LAUNCH(ctx, "conf_scatter_kernel");
             }
         E2EMV_HIP(ctx, hipMemsetAsync(du, 0, (size_t)B * (N + 1) * sizeof(float), s));
@@ -725,7 +832,13 @@ extern "C" int e2emv_matcher_backward(e2emv_ctx* ctx, const float* const* d_dlog
         if ((rc = wgrad(ctx, dx, D, D, t->t_h[l], 2 * D, 2 * D, Mtot, gw + Lw.w1, 2 * D, s))) return rc;
         if ((rc = colsum(ctx, dx, Mtot, D, D, gw + Lw.b1, s))) return rc;
         // h = relu(W0 [x_l | msg] + b0)
-        hipLaunchKernelGGL(relu_bwd_kernel, dim3(ew_grid(Mtot * 2 * D)), dim3(256), 0, s, dh, (const float*)t->t_h[l], Mtot * 2 * D);
+        if (bnb) {  // h = relu(BN(y)), y = W0 [x_l | msg] + b0 (batch statistics): dh -> dy
+            BnCall a = bn_images(t, nk - 1 + l, t->t_hy[l], dh, t->t_hst[l], bpart);
+            a.h = t->t_h[l];
+            if ((rc = bn_backward(ctx, a, T, s))) return rc;
+        } else {
+            hipLaunchKernelGGL(relu_bwd_kernel, dim3(ew_grid(Mtot * 2 * D)), dim3(256), 0, s, dh, (const float*)t->t_h[l], Mtot * 2 * D);
+        }
         if ((rc = dgrad(ctx, dh, 2 * D, 2 * D, W + Lw.w0, 2 * D, 2 * D, Mtot, dcat, 2 * D, false, s))) return rc;
         if ((rc = wgrad(ctx, dh, 2 * D, 2 * D, t->t_x[l], D, D, Mtot, gw + Lw.w0, 2 * D, s))) return rc;
         if ((rc = wgrad(ctx, dh, 2 * D, 2 * D, t->t_msg[l], D, D, Mtot, gw + Lw.w0 + D, 2 * D, s))) return rc;
@@ -750,7 +863,13 @@ extern "C" int e2emv_matcher_backward(e2emv_ctx* ctx, const float* const* d_dlog
         int bi = 0;
         for (int i = nk - 1; i >= 1; --i) {
             const int cin = t->kdims[i], cout = t->kdims[i + 1];
-            if (i < nk - 1) hipLaunchKernelGGL(relu_bwd_kernel, dim3(ew_grid(Mtot * cout)), dim3(256), 0, s, cur, (const float*)t->t_kh[i + 1], Mtot * cout);
+            if (i < nk - 1 && bnb) {
+                BnCall a = bn_images(t, i, t->t_ky[i + 1], cur, t->t_kst[i + 1], bpart);
+                a.h = t->t_kh[i + 1];
+                if ((rc = bn_backward(ctx, a, T, s))) return rc;
+            } else if (i < nk - 1) {
+                hipLaunchKernelGGL(relu_bwd_kernel, dim3(ew_grid(Mtot * cout)), dim3(256), 0, s, cur, (const float*)t->t_kh[i + 1], Mtot * cout);
+            }
             if ((rc = wgrad(ctx, cur, cout, cout, t->t_kh[i], cin, cin, Mtot, gw + t->kw[i], cin, s))) return rc;
             if ((rc = colsum(ctx, cur, Mtot, cout, cout, gw + t->kb[i], s))) return rc;
             if ((rc = dgrad(ctx, cur, cout, cout, W + t->kw[i], cin, cin, Mtot, bufs[bi], cin, false, s))) return rc;
@@ -759,7 +878,13 @@ extern "C" int e2emv_matcher_backward(e2emv_ctx* ctx, const float* const* d_dlog
         }
         // layer 0: 3 -> c0 (+ BN folded, ReLU); its input is re-derived from the keypoints: not kept, the gradient w.r.t. it is not needed
         const int c0 = t->kdims[1];
-        hipLaunchKernelGGL(relu_bwd_kernel, dim3(ew_grid(Mtot * c0)), dim3(256), 0, s, cur, (const float*)t->t_kh[1], Mtot * c0);
+        if (bnb) {
+            BnCall a = bn_images(t, 0, t->t_ky[1], cur, t->t_kst[1], bpart);
+            a.h = t->t_kh[1];
+            if ((rc = bn_backward(ctx, a, T, s))) return rc;
+        } else {
+            hipLaunchKernelGGL(relu_bwd_kernel, dim3(ew_grid(Mtot * c0)), dim3(256), 0, s, cur, (const float*)t->t_kh[1], Mtot * c0);
+        }
         if ((rc = wgrad(ctx, cur, c0, c0, t->t_inp, 4, 3, Mtot, gw + t->kw[0], 3, s))) return rc;
         if ((rc = colsum(ctx, cur, Mtot, c0, c0, gw + t->kb[0], s))) return rc;
         E2EMV_CHECK_LAUNCH(ctx, "encoder backward kernels");
@@ -772,7 +897,7 @@ extern "C" int e2emv_matcher_backward(e2emv_ctx* ctx, const float* const* d_dlog
         UnfoldArgs a{};
         a.dWf = dWf + (int64_t)rbase * ldwf; a.dbf = dbf + rbase; a.ldwf = ldwf; a.col0 = col0;
         a.W = ref(conv + ".weight"); a.b = ref(conv + ".bias");
-        if (!bn.empty() && ref(bn + ".running_mean")) {
+        if (!bn.empty() && ref(bn + ".running_mean") && t->bn_mode == E2EMV_BN_FROZEN) {  // (batch statistics: dgamma / dbeta come from bn_backward)
             a.gamma = ref(bn + ".weight"); a.beta = ref(bn + ".bias"); a.mean = ref(bn + ".running_mean"); a.var = ref(bn + ".running_var");
             a.dgamma = gref(bn + ".weight"); a.dbeta = gref(bn + ".bias");
         }
@@ -812,5 +937,56 @@ extern "C" int e2emv_get_grad(e2emv_ctx* ctx, const char* key, float* d_dst, int
     if (it == t->raw.end()) return set_err(ctx, E2EMV_EINVAL, "get_grad: no gradient for '%s'", key);
     if ((int64_t)it->second.numel != numel) return set_err(ctx, E2EMV_ESHAPE, "get_grad: '%s' has %zu elements, not %lld", key, it->second.numel, (long long)numel);
     E2EMV_HIP(ctx, hipMemcpyAsync(d_dst, t->d_graw + it->second.off, numel * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return E2EMV_OK;
+}
+
+extern "C" int e2emv_train_set_batchnorm(e2emv_ctx* ctx, int mode, float momentum) {
+    if (!ctx) return E2EMV_EINVAL;
+    if (mode != E2EMV_BN_FROZEN && mode != E2EMV_BN_BATCH) return set_err(ctx, E2EMV_EINVAL, "train_set_batchnorm: mode %d", mode);
+    if (!(momentum >= 0.f && momentum <= 1.f)) return set_err(ctx, E2EMV_EINVAL, "train_set_batchnorm: momentum %g outside [0, 1]", (double)momentum);
+    E2EMV_LOCK(ctx);
+    ctx->train_bn_mode = mode;
+    ctx->train_bn_momentum = momentum;
+    return E2EMV_OK;
+}
+
+// torch's running-buffer update for the BatchNorm calls of the last forward_train (T per encoder / GNN BatchNorm, image order)
+// and of its conf forwards (one per pair that ran, pair order) - onto the caller's device buffers, stream-ordered
+extern "C" int e2emv_train_running_update(e2emv_ctx* ctx, int n, const char* const* keys, float* const* d_running_mean, float* const* d_running_var,
+                                          void* stream) {
+    if (!ctx || n < 0 || (n && (!keys || !d_running_mean || !d_running_var))) return E2EMV_EINVAL;
+    E2EMV_ENTER(ctx, stream);
+    TrainState* t = ts_of(ctx);
+    if (!t || !t->have_tape) return set_err(ctx, E2EMV_ESTATE, "train_running_update: no tape - e2emv_matcher_forward_train first");
+    if (t->bn_mode != E2EMV_BN_BATCH) return set_err(ctx, E2EMV_ESTATE, "train_running_update: the tape was made with frozen BatchNorm statistics");
+    std::vector<int> which(n);
+    for (int i = 0; i < n; ++i) {  // (all entries checked before the first launch)
+        if (!keys[i] || !d_running_mean[i] || !d_running_var[i]) return set_err(ctx, E2EMV_EINVAL, "train_running_update: null entry %d", i);
+        std::string k(keys[i]);
+        if (k.rfind("module.", 0) == 0) k = k.substr(7);
+        which[i] = -1;
+        for (size_t j = 0; j < t->bns.size(); ++j)
+            if (t->bns[j].name == k) which[i] = (int)j;
+        if (which[i] < 0) return set_err(ctx, E2EMV_EINVAL, "train_running_update: no BatchNorm '%s' in the committed model", keys[i]);
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const int nk = (int)t->kdims.size() - 1, L = (int)t->layers.size();
+    const int64_t cnt = (int64_t)t->B * t->N;
+    const double unbias = (double)cnt / (double)(cnt - 1);
+    const float m = ctx->train_bn_momentum;
+    for (int i = 0; i < n; ++i) {
+        const int j = which[i], C = t->bns[j].C;
+        const dim3 grid((C + 255) / 256);
+        if (j < nk - 1 + L) {
+            const float* st = j < nk - 1 ? t->t_kst[j + 1] : t->t_hst[j - (nk - 1)];
+            hipLaunchKernelGGL(bn_running_kernel, grid, dim3(256), 0, s, C, t->T, st, m, unbias, d_running_mean[i], d_running_var[i]);
+        } else {
+            for (int q = 0; q < t->P; ++q)
+                if (t->t_cmatch[q])
+                    hipLaunchKernelGGL(bn_running_kernel, grid, dim3(256), 0, s, C, 1, (const float*)t->t_cst + (int64_t)q * 3 * C, m, unbias,
+                                       d_running_mean[i], d_running_var[i]);
+        }
+    }
+    E2EMV_CHECK_LAUNCH(ctx, "bn_running_kernel");
     return E2EMV_OK;
 }

@@ -364,18 +364,220 @@ __global__ __launch_bounds__(256) void conf_bwd_kernel(int64_t rows, int D, cons
     for (int c = lane; c < D; c += 64) dh[r * D + c] = h[c] > 0.f ? d * w1[c] : 0.f;
 }
 // dmdesc_i[b][n][:] += dfeat[b][n][:D];  dmdesc_j[b][match][:] += dfeat[b][n][D:]  (matched rows only; mutual matches are unique,
-// atomics keep it safe for any index list)
+// atomics keep it safe for any index list).  all_rows: unmatched rows too, at their feature's mdesc_j row max(match, 0) - with
+// batch-statistics BatchNorm in the conf head every row's features reach the loss through the batch mean and variance.
 __global__ __launch_bounds__(256) void conf_scatter_kernel(int N, int D, const float* dfeat, const int64_t* matches, float* dmd_i, float* dmd_j,
-                                                           int64_t tuple_stride) {
+                                                           int64_t tuple_stride, int all_rows) {
     const int b = blockIdx.y;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (row >= N) return;
-    const int64_t j = matches[(int64_t)b * N + row];
-    if (j < 0) return;
+    int64_t j = matches[(int64_t)b * N + row];
+    if (j < 0 && !all_rows) return;
+    if (j < 0) j = 0;
     const float* src = dfeat + ((int64_t)b * N + row) * 2 * D;
     float* di = dmd_i + b * tuple_stride + (int64_t)row * D;
     float* dj = dmd_j + b * tuple_stride + j * D;
     for (int c = lane; c < D; c += 64) { atomicAdd(di + c, src[c]); atomicAdd(dj + c, src[D + c]); }
+}
+
+// ---- batch-statistics BatchNorm (torch's BatchNorm1d in training mode, eps 1e-5) -----------------------------------------
+// One BN call z normalises `nseg` segments of `seg_rows` rows of a [rows][C] matrix, the first N rows of each segment valid:
+// valid row r in [0, nseg N) lives at row z z_stride + (r / N) seg_stride + r % N (an image of a [b][t][n_rows] arena: N = n_kpts,
+// nseg = B, seg_rows = n_rows, seg_stride = T n_rows, z_stride = n_rows; a pair's conf features: nseg = 1, N = seg_rows = B n_kpts).
+// Sums are fp64 per-workgroup partials over a chunk of rows, combined per channel in a fixed order by every reader: no atomics,
+// bitwise reproducible.  Grid of every kernel: ((C + 63) / 64, chunks, calls), 256 threads = 64 channels x 4 row phases.
+struct BnCall {
+    const float* y = nullptr;  // conv output (pre-BN)
+    float* out = nullptr;      // forward: relu(gamma (y - mean) invstd + beta);  backward: d out (post-ReLU) in, d y out, in place
+    const float* h = nullptr;  // backward: the forward's post-ReLU output (its mask)
+    const float* gamma = nullptr;
+    const float* beta = nullptr;
+    float* stats = nullptr;    // [calls][3][C]: mean, biased variance, invstd (written by the forward, read by the backward)
+    double* part = nullptr;    // [calls][chunks][2][C] scratch
+    float* dgamma = nullptr;   // backward: sum over the calls of sum dz x^ / sum dz, written (accumulate = 0) or added
+    float* dbeta = nullptr;
+    int C = 0, N = 0, nseg = 0, seg_rows = 0, chunks = 1, accumulate = 0;
+    int64_t seg_stride = 0, z_stride = 0;
+};
+
+__device__ __forceinline__ int64_t bn_row(const BnCall& a, int z, int64_t r) { return z * a.z_stride + (r / a.N) * a.seg_stride + r % a.N; }
+// fixed-order sum of the `which` partial of channel c, call z (four independent chains, combined in order)
+__device__ __forceinline__ double bn_combine(const BnCall& a, int z, int c, int which) {
+    const double* p = a.part + (int64_t)z * a.chunks * 2 * a.C + (int64_t)which * a.C + c;
+    const int64_t st = 2 * (int64_t)a.C;
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+    int k = 0;
+    for (; k + 4 <= a.chunks; k += 4) { s0 += p[k * st]; s1 += p[(k + 1) * st]; s2 += p[(k + 2) * st]; s3 += p[(k + 3) * st]; }
+    for (; k < a.chunks; ++k) s0 += p[k * st];
+    return (s0 + s1) + (s2 + s3);
+}
+// partial sums over the rows of this workgroup's chunk, 4 phases merged in order -> part[z][chunk][which][c]
+__device__ __forceinline__ void bn_store_partial(const BnCall& a, double v, int which) {
+    __shared__ double red[4][64];
+    const int cl = threadIdx.x & 63, ph = threadIdx.x >> 6, c = blockIdx.x * 64 + cl;
+    red[ph][cl] = v;
+    __syncthreads();
+    if (ph == 0 && c < a.C)
+        a.part[((int64_t)blockIdx.z * a.chunks + blockIdx.y) * 2 * a.C + (int64_t)which * a.C + c] = ((red[0][cl] + red[1][cl]) + red[2][cl]) + red[3][cl];
+}
+// The row loops below take four rows per step (rows r, r + 4, r + 8, r + 12 of the thread's phase): four loads in flight per
+// thread - one dependent load per step left these kernels latency-bound.
+
+// pass 0: part[..][0] = sum y;  pass 1: part[..][1] = sum (y - mean)^2, the mean from pass 0's partials (two-pass variance)
+__global__ __launch_bounds__(256) void bn_stats_kernel(BnCall a, int pass) {
+    const int cl = threadIdx.x & 63, ph = threadIdx.x >> 6, c = blockIdx.x * 64 + cl, z = blockIdx.z;
+    const int64_t R = (int64_t)a.nseg * a.N, per = (R + a.chunks - 1) / a.chunks;
+    const int64_t r0 = blockIdx.y * per, r1 = min(R, r0 + per);
+    double s[4] = {0.0, 0.0, 0.0, 0.0};
+    if (c < a.C) {
+        const double mean = pass ? bn_combine(a, z, c, 0) / (double)R : 0.0;
+        int64_t r = r0 + ph;
+        for (; r + 12 < r1; r += 16) {
+            float v[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) v[u] = a.y[bn_row(a, z, r + 4 * u) * a.C + c];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const double d = (double)v[u] - mean;
+                s[u] += pass ? d * d : d;
+            }
+        }
+        for (; r < r1; r += 4) {
+            const double d = (double)a.y[bn_row(a, z, r) * a.C + c] - mean;
+            s[0] += pass ? d * d : d;
+        }
+    }
+    bn_store_partial(a, (s[0] + s[1]) + (s[2] + s[3]), pass);
+}
+// out = relu(gamma (y - mean) invstd + beta) on the valid rows (padding rows are left as they are: zeros of the tape);
+// the first workgroup row of a call writes its statistics
+__global__ __launch_bounds__(256) void bn_apply_kernel(BnCall a) {
+    const int cl = threadIdx.x & 63, ph = threadIdx.x >> 6, c = blockIdx.x * 64 + cl, z = blockIdx.z;
+    if (c >= a.C) return;
+    const int64_t R = (int64_t)a.nseg * a.N, per = (R + a.chunks - 1) / a.chunks;
+    const int64_t r0 = blockIdx.y * per, r1 = min(R, r0 + per);
+    const double md = bn_combine(a, z, c, 0) / (double)R, vd = bn_combine(a, z, c, 1) / (double)R;
+    const float mean = (float)md, invstd = (float)(1.0 / sqrt(vd + 1e-5));
+    if (blockIdx.y == 0 && ph == 0) {
+        float* st = a.stats + (int64_t)z * 3 * a.C;
+        st[c] = mean; st[a.C + c] = (float)vd; st[2 * a.C + c] = invstd;
+    }
+    const float g = a.gamma[c] * invstd, be = a.beta[c];
+    int64_t r = r0 + ph;
+    for (; r + 12 < r1; r += 16) {
+        int64_t o[4];
+        float v[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) { o[u] = bn_row(a, z, r + 4 * u) * a.C + c; v[u] = a.y[o[u]]; }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) a.out[o[u]] = relu_nan(g * (v[u] - mean) + be);
+    }
+    for (; r < r1; r += 4) {
+        const int64_t o = bn_row(a, z, r) * a.C + c;
+        a.out[o] = relu_nan(g * (a.y[o] - mean) + be);
+    }
+}
+// backward, pass 1: part[..][0] = sum dz, part[..][1] = sum dz x^ with dz = (h > 0) d out, x^ = (y - mean) invstd
+__global__ __launch_bounds__(256) void bn_bwd_stats_kernel(BnCall a) {
+    const int cl = threadIdx.x & 63, ph = threadIdx.x >> 6, c = blockIdx.x * 64 + cl, z = blockIdx.z;
+    const int64_t R = (int64_t)a.nseg * a.N, per = (R + a.chunks - 1) / a.chunks;
+    const int64_t r0 = blockIdx.y * per, r1 = min(R, r0 + per);
+    double s0[4] = {0.0, 0.0, 0.0, 0.0}, s1[4] = {0.0, 0.0, 0.0, 0.0};
+    if (c < a.C) {
+        const float* st = a.stats + (int64_t)z * 3 * a.C;
+        const float mean = st[c], invstd = st[2 * a.C + c];
+        int64_t r = r0 + ph;
+        for (; r + 12 < r1; r += 16) {
+            float h[4], d[4], y[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int64_t o = bn_row(a, z, r + 4 * u) * a.C + c;
+                h[u] = a.h[o]; d[u] = a.out[o]; y[u] = a.y[o];
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const float dz = h[u] > 0.f ? d[u] : 0.f;
+                s0[u] += dz;
+                s1[u] += (double)dz * (double)((y[u] - mean) * invstd);
+            }
+        }
+        for (; r < r1; r += 4) {
+            const int64_t o = bn_row(a, z, r) * a.C + c;
+            const float dz = a.h[o] > 0.f ? a.out[o] : 0.f;
+            s0[0] += dz;
+            s1[0] += (double)dz * (double)((a.y[o] - mean) * invstd);
+        }
+    }
+    bn_store_partial(a, (s0[0] + s0[1]) + (s0[2] + s0[3]), 0);
+    __syncthreads();
+    bn_store_partial(a, (s1[0] + s1[1]) + (s1[2] + s1[3]), 1);
+}
+// backward, pass 2 (every row of the call, padding rows := 0): dy = gamma invstd (dz - mean(dz) - x^ mean(dz x^)), in place;
+// workgroup (x, 0, 0) also leaves d gamma = sum dz x^, d beta = sum dz over all calls
+__global__ __launch_bounds__(256) void bn_bwd_apply_kernel(BnCall a) {
+    const int cl = threadIdx.x & 63, ph = threadIdx.x >> 6, c = blockIdx.x * 64 + cl, z = blockIdx.z;
+    if (c >= a.C) return;
+    const double R = (double)a.nseg * a.N;
+    const float* st = a.stats + (int64_t)z * 3 * a.C;
+    const float mean = st[c], invstd = st[2 * a.C + c];
+    const float mdz = (float)(bn_combine(a, z, c, 0) / R), mdzx = (float)(bn_combine(a, z, c, 1) / R);
+    const float g = a.gamma[c] * invstd;
+    const int64_t rows = (int64_t)a.nseg * a.seg_rows, per = (rows + a.chunks - 1) / a.chunks;
+    const int64_t q0 = blockIdx.y * per, q1 = min(rows, q0 + per);
+    auto at = [&](int64_t q, bool& valid) {
+        const int64_t sg = q / a.seg_rows, n = q - sg * a.seg_rows;
+        valid = n < a.N;
+        return (z * a.z_stride + sg * a.seg_stride + n) * a.C + c;
+    };
+    auto dy = [&](float h, float d, float y) { return g * ((h > 0.f ? d : 0.f) - mdz - (y - mean) * invstd * mdzx); };
+    int64_t q = q0 + ph;
+    for (; q + 12 < q1; q += 16) {
+        int64_t o[4];
+        bool ok[4];
+        float h[4], d[4], y[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            o[u] = at(q + 4 * u, ok[u]);
+            h[u] = ok[u] ? a.h[o[u]] : 0.f; d[u] = ok[u] ? a.out[o[u]] : 0.f; y[u] = ok[u] ? a.y[o[u]] : 0.f;
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) a.out[o[u]] = ok[u] ? dy(h[u], d[u], y[u]) : 0.f;
+    }
+    for (; q < q1; q += 4) {
+        bool ok;
+        const int64_t o = at(q, ok);
+        a.out[o] = ok ? dy(a.h[o], a.out[o], a.y[o]) : 0.f;
+    }
+    if (blockIdx.y == 0 && z == 0 && ph == 0) {
+        double sg = 0.0, sb = 0.0;
+        for (int k = 0; k < (int)gridDim.z; ++k) { sb += bn_combine(a, k, c, 0); sg += bn_combine(a, k, c, 1); }
+        a.dgamma[c] = (a.accumulate ? a.dgamma[c] : 0.f) + (float)sg;
+        a.dbeta[c] = (a.accumulate ? a.dbeta[c] : 0.f) + (float)sb;
+    }
+}
+// encoder layer 0 without its BatchNorm: y[row][c] = w0[c] . (x, y, score) + b0[c] from the tape's normalised keypoints [rows][4]
+__global__ __launch_bounds__(256) void kenc0_conv_kernel(const float* inp, const float* w0, const float* b0, int c0, int64_t rows, float* y) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < rows * c0; i += (int64_t)gridDim.x * 256) {
+        const int64_t r = i / c0;
+        const int c = (int)(i - r * c0);
+        const float* x = inp + r * 4;
+        const float* w = w0 + c * 3;
+        y[i] = w[0] * x[0] + w[1] * x[1] + w[2] * x[2] + b0[c];
+    }
+}
+// running buffers after `calls` consecutive calls (statistics [calls][3][C]), torch's update in call order:
+// mean <- (1 - m) mean + m mean_call,  var <- (1 - m) var + m var_call n / (n - 1)
+__global__ __launch_bounds__(256) void bn_running_kernel(int C, int calls, const float* stats, float m, double unbias, float* rmean, float* rvar) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= C) return;
+    float rm = rmean[c], rv = rvar[c];
+    for (int k = 0; k < calls; ++k) {
+        const float* st = stats + (int64_t)k * 3 * C;
+        rm = (1.f - m) * rm + m * st[c];
+        rv = (1.f - m) * rv + m * (float)((double)st[C + c] * unbias);
+    }
+    rmean[c] = rm;
+    rvar[c] = rv;
 }
 
 // ---- folded gradients -> the gradients of the upstream parameters --------------------------------------------------------

@@ -23,12 +23,16 @@ there) and runs the hand-written HIP path; without the library or an MI355X it r
 Training, first slice: in ``.train()`` mode with gradients enabled the ``scores_{i}_{j}`` carry an autograd
 graph (``_MatchScores``: the library's fp32 forward with a tape and its hand-written backward, csrc/train.hip), so the
 reference's stage-1 step ``match_loss(...).backward(); optimizer.step()`` (``train.py:406-425``) works unchanged.
-BatchNorm layers normalise with their running statistics there (they are not updated).  With ``full_output`` (the reference
+BatchNorm layers normalise either with their running statistics (frozen, not updated: the default) or, with
+``config["frozen_batchnorm"] = False`` or ``E2EMV_TRAIN_BATCHNORM=batch``, with the statistics of the batch as torch's
+training-mode ``BatchNorm1d`` does, updating ``running_mean`` / ``running_var`` / ``num_batches_tracked`` on every forward
+(the reference's ``matcher.train()``, ``train.py:348``).  With ``full_output`` (the reference
 sets it for the pose loss, ``helpers.py:245``) the matches come from the same fp32 forward and, for a model with ``conf_mlp``,
 ``conf_scores_{i}_{j}`` carry the graph too: the pose loss of stage 2 reaches ``conf_mlp`` and the GNN through
 ``pose.run_weighted_8_point`` (its backward: ``e2emv_w8pt_backward``).
 """
 import ctypes
+import os
 
 import torch
 from torch import nn
@@ -50,10 +54,12 @@ DEFAULT_CONFIG = {
     # planes, 6 bf16-MFMA products) or "f16x2" (two fp16 planes, 3 fp16-MFMA products), all with fp32 accumulation and the
     # same parity bar.  None = the library default (environment variable E2EMV_PRECISION, else "f16x2").
     "mfma_precision": None,
-    # Training (.train() + gradients): BatchNorm layers normalise with their RUNNING statistics and do not update them
-    # (csrc/train.hip) - gradients for their affine parameters are returned.  Upstream's matcher.train() (train.py:131,348)
-    # would use batch statistics on a stock torch BatchNorm; the fork's own behaviour is not in the checkout.  The first
-    # differentiable forward of a model warns about this unless the key is set to True (= "I know").
+    # Training (.train() + gradients), BatchNorm layers.  True: normalise with the RUNNING statistics and do not update them
+    # (csrc/train.hip folds them into the convolutions) - gradients for their affine parameters are returned.  False: batch
+    # statistics, exactly torch's BatchNorm1d in training mode (the reference's matcher.train(), train.py:348): every call
+    # normalises with the statistics of its own keypoints and updates running_mean / running_var / num_batches_tracked.
+    # None: the environment variable E2EMV_TRAIN_BATCHNORM decides ("batch" | "frozen", unset = "frozen"); frozen that way
+    # warns on the first differentiable forward of a model.
     "frozen_batchnorm": None,
     # True: forward() synchronises and raises if the device reported non-finite scores (off by default: the reference's
     # forward is asynchronous too, and the NaN / inf is in the outputs either way)
@@ -72,7 +78,7 @@ class _MatchScores(torch.autograd.Function):
 
     @staticmethod
     def forward(fctx, cfg, *params):
-        ctx, fd, kpts, scores, descs, shapes, names, full, thr, holder = cfg
+        ctx, fd, kpts, scores, descs, shapes, names, full, thr, holder, bns = cfg
         dev = params[0].device
         P = len(shapes)
         logZ = [torch.empty(s, dtype=torch.float32, device=dev) for s in shapes]
@@ -103,6 +109,8 @@ class _MatchScores(torch.autograd.Function):
                     extra["conf"].append(mask_confidence(s0, m0 >= 0))
             holder.append(extra)
             fctx.keep = extra  # (the library reads the matches again in the backward)
+        if bns is not None:  # batch-statistics BatchNorm: the running buffers take this forward's statistics, as torch's forward does
+            _running_update(ctx, dev, bns if conf else [(k, m) for k, m in bns if not k.startswith("conf_mlp.")], fd.tuple_size, len(conf))
         fctx.lib_ctx, fctx.generation, fctx.names, fctx.dev, fctx.P = ctx, ctx.train_generation, names, dev, P
         fctx.n_conf = len(conf)
         fctx.param_shapes = [p.shape for p in params]
@@ -139,6 +147,21 @@ class _MatchScores(torch.autograd.Function):
             if ctx.train_generation != fctx.generation:
                 raise RuntimeError("MultiViewMatcher: another training forward ran on this device during backward()")
         return tuple(out)
+
+
+def _running_update(ctx, dev, bns, T, n_conf):
+    """e2emv_train_running_update on the modules' own buffers (device, stream-ordered), then what torch's BatchNorm forward
+    does besides: the buffers' version counters (the weight fingerprint sees the change: the next inference forward re-commits)
+    and num_batches_tracked (+1 per call: T per encoder / GNN BatchNorm, one per conf head that ran for conf_mlp.1)."""
+    n = len(bns)
+    keys = (ctypes.c_char_p * n)(*[k.encode() for k, _ in bns])
+    pm, keep_m = _lib.ptr_array([m.running_mean for _, m in bns])
+    pv, keep_v = _lib.ptr_array([m.running_var for _, m in bns])
+    with torch.cuda.device(dev):
+        ctx.call("e2emv_train_running_update", n, keys, pm, pv, _lib.stream_ptr(dev))
+    for k, m in bns:
+        torch.autograd.graph.increment_version([m.running_mean, m.running_var])
+        m.num_batches_tracked.add_(n_conf if k.startswith("conf_mlp.") else T)
 
 
 def _mlp(channels, do_bn=True):
@@ -271,7 +294,8 @@ class MultiViewMatcher(nn.Module):
 
     def _send_weights(self, ctx, owner):
         """e2emv_set_weight for every tensor (the library's host-side store), once per (module, parameter values)."""
-        if getattr(ctx, "sent_owner", None) == owner:
+        sent = getattr(ctx, "sent_owner", None)
+        if sent is not None and sent[:2] == owner[:2]:  # (a training owner carries the BatchNorm mode as a third entry)
             return
         ctx.sent_owner = None
         items = [(k, v.detach()) for k, v in self.state_dict().items() if v.dtype.is_floating_point]  # (not num_batches_tracked)
@@ -296,11 +320,12 @@ class MultiViewMatcher(nn.Module):
         ctx.call("e2emv_commit_weights", ctypes.byref(md))
         ctx.weights_owner = owner
 
-    def _push_train_weights(self, ctx):
+    def _push_train_weights(self, ctx, bn_mode=_lib.BN_FROZEN):
         """Training commit only: after an optimiser step the parameters changed, and what the differentiable path needs is the
         training arena (e2emv_train_commit: BN / head-order folds, arenas and tape kept) - NOT the inference commit with its
-        fp64 merge fold and the bf16x3 / f16x2 planes, which is made when (if) an inference forward next needs it."""
-        owner = (self._token, self._fingerprint())
+        fp64 merge fold and the bf16x3 / f16x2 planes, which is made when (if) an inference forward next needs it.  The
+        BatchNorm mode is part of the owner: the arena of one mode is not the other's (e2emv_train_update refuses, ESTATE)."""
+        owner = (self._token, self._fingerprint(), bn_mode)
         if ctx.train_owner == owner:
             return
         md = self._model_desc()
@@ -325,6 +350,36 @@ class MultiViewMatcher(nn.Module):
         self._send_weights(ctx, owner)
         ctx.call("e2emv_train_commit", ctypes.byref(md))
         ctx.train_owner = owner
+
+    def _batchnorm_mode(self):
+        """BatchNorm of the differentiable path: BN_BATCH | BN_FROZEN (config key, else E2EMV_TRAIN_BATCHNORM, else frozen)."""
+        v = self.config.get("frozen_batchnorm")
+        if v is not None:
+            return _lib.BN_FROZEN if v else _lib.BN_BATCH
+        env = os.environ.get("E2EMV_TRAIN_BATCHNORM", "")
+        if env not in ("", "batch", "frozen"):
+            raise ValueError(f"E2EMV_TRAIN_BATCHNORM={env!r}: expected 'batch' or 'frozen'")
+        return _lib.BN_BATCH if env == "batch" else _lib.BN_FROZEN
+
+    def _batch_norms(self):
+        """[(name, module)] of every BatchNorm, checked for what batch-statistics training supports (raises before any launch)."""
+        bns = [(k, m) for k, m in self.named_modules() if isinstance(m, nn.modules.batchnorm._BatchNorm)]
+        momenta = set()
+        for k, m in bns:
+            if not m.track_running_stats or m.running_mean is None or m.running_var is None or m.num_batches_tracked is None:
+                raise ValueError(f"batch-statistics BatchNorm: {k} needs track_running_stats=True")
+            if m.momentum is None or not isinstance(m.momentum, (float, int)):
+                raise ValueError(f"batch-statistics BatchNorm: {k}.momentum = {m.momentum!r} - only a float momentum is supported "
+                                 "(not None, the cumulative average)")
+            if m.eps != 1e-5:
+                raise ValueError(f"batch-statistics BatchNorm: {k}.eps = {m.eps!r} - only eps = 1e-5 is supported")
+            for b in (m.running_mean, m.running_var):
+                if b.dtype != torch.float32 or not b.is_contiguous() or b.device != self.bin_score.device:
+                    raise ValueError(f"batch-statistics BatchNorm: {k}'s running buffers must be contiguous fp32 on {self.bin_score.device}")
+            momenta.add(float(m.momentum))
+        if len(momenta) > 1:
+            raise ValueError(f"batch-statistics BatchNorm: every BatchNorm needs the same momentum (found {sorted(momenta)})")
+        return bns, (momenta.pop() if momenta else 0.1)
 
     def _differentiable(self):
         if self.config.get("autograd", None) is False or not self.training or not torch.is_grad_enabled():
@@ -461,16 +516,21 @@ class MultiViewMatcher(nn.Module):
                                           "(the reference's training batches do, datasets pad to max_keypoints)")
             if T > 2 and not cfg["multi_frame_matching"]:
                 raise NotImplementedError("training path: tuples of more than two images need multi_frame_matching")
-            if not cfg.get("frozen_batchnorm") and not getattr(self, "_warned_bn", False):
+            bn_mode = self._batchnorm_mode()
+            bns, momentum = self._batch_norms() if bn_mode == _lib.BN_BATCH else (None, 0.1)
+            if bn_mode == _lib.BN_FROZEN and cfg.get("frozen_batchnorm") is None and not getattr(self, "_warned_bn", False):
                 self._warned_bn = True
                 import warnings
                 warnings.warn("MultiViewMatcher in .train() mode: BatchNorm layers use their running statistics (frozen) and do not "
-                              "update them - batch-statistics BatchNorm is not implemented on the differentiable path.  Set "
-                              "config['frozen_batchnorm'] = True to acknowledge (e.g. fine-tuning from a checkpoint).", stacklevel=3)
-            self._push_train_weights(ctx)
+                              "update them.  For torch's training-mode BatchNorm (batch statistics, running buffers updated) set "
+                              "config['frozen_batchnorm'] = False or the environment variable E2EMV_TRAIN_BATCHNORM=batch; set "
+                              "config['frozen_batchnorm'] = True to keep frozen statistics without this warning (e.g. fine-tuning "
+                              "from a checkpoint).", stacklevel=3)
+            ctx.call("e2emv_train_set_batchnorm", bn_mode, ctypes.c_float(momentum))
+            self._push_train_weights(ctx, bn_mode)
             named = [(k, p) for k, p in self.named_parameters()]
             holder = []
-            cfgt = (ctx, fd, kpts, scores, descs, [(B, N + 1, N + 1)] * P, [k for k, _ in named], full, float(cfg["match_threshold"]), holder)
+            cfgt = (ctx, fd, kpts, scores, descs, [(B, N + 1, N + 1)] * P, [k for k, _ in named], full, float(cfg["match_threshold"]), holder, bns)
             outs = _MatchScores.apply(cfgt, *[p for _, p in named])
             out = {f"scores_{i}_{j}": outs[p] for p, (i, j) in enumerate(pairs)}
             if full:  # matches / confidences from the scores of this very forward (the fp32 training arithmetic)

@@ -441,10 +441,11 @@ int e2emv_sinkhorn_plan(e2emv_ctx* ctx, int B, int M, int N, int iters, int* pla
  *   pred = run_matcher(...); train_loss.backward()        (/root/reference/helpers.py:243-260, train.py:406-425)
  * with the reference's own arithmetic (fp32).  Differentiated: keypoint encoder, every GNN layer (projections, attention,
  * merge, MLP), final_proj, the score matrix, bin_score and the unrolled log-domain Sinkhorn (SuperGlue's
- * log_optimal_transport, models/superglue.py:156-186 upstream).  BatchNorm layers use their running statistics (frozen) and
- * still hand back gradients for their affine parameters.  The pose loss (helpers.py:253-258) reaches the network through the
- * confidences: e2emv_w8pt_backward (below) -> e2emv_conf_forward_train / d_dconf here.  Forward-only: batch-statistics
- * BatchNorm, images with differing keypoint counts, the confidences of a model WITHOUT conf_mlp (the match score).
+ * log_optimal_transport, models/superglue.py:156-186 upstream).  BatchNorm layers use their running statistics (frozen) or
+ * the statistics of the batch (e2emv_train_set_batchnorm, below) and hand back gradients for their affine parameters either way.
+ * The pose loss (helpers.py:253-258) reaches the network through the confidences: e2emv_w8pt_backward (below) ->
+ * e2emv_conf_forward_train / d_dconf here.  Forward-only: images with differing keypoint counts, the confidences of a model
+ * WITHOUT conf_mlp (the match score).
  *
  * e2emv_train_commit        folds the weights handed over with e2emv_set_weight into the training arena (call again after
  *                           every optimiser step, after re-sending the changed tensors).
@@ -475,6 +476,30 @@ int e2emv_matcher_forward_train(e2emv_ctx* ctx, const e2emv_forward_desc* fd, co
 int e2emv_conf_forward_train(e2emv_ctx* ctx, int pair, const int64_t* d_matches0, float* d_conf, void* stream);
 int e2emv_matcher_backward(e2emv_ctx* ctx, const float* const* d_dlogZ, const float* const* d_dconf, void* stream);
 int e2emv_get_grad(e2emv_ctx* ctx, const char* key, float* d_dst, int64_t numel, void* stream);
+/* BatchNorm of the training path.  E2EMV_BN_FROZEN (the default): every BatchNorm normalises with its running statistics,
+ * folded into the convolution in front of it, and the buffers are not written.  E2EMV_BN_BATCH: torch's BatchNorm1d in
+ * training mode (the reference's matcher.train(), train.py:348) - each call normalises with the statistics of its own rows
+ * (biased variance, eps 1e-5) and the backward is the batch-statistics gradient.  One call per image for kenc.encoder.{1,4,..}
+ * and gnn.layers.{l}.mlp.1 (t = 0 .. T-1 in order), one per pair for conf_mlp.1 (its B x n_kpts features, unmatched rows
+ * included); padding rows never enter a sum; statistics are fp64 partials combined in a fixed order (bitwise reproducible).
+ *
+ * e2emv_train_set_batchnorm   selects the mode and the momentum of the running update (one value for every BatchNorm).  A mode
+ *                             other than the arena's makes e2emv_train_update and e2emv_matcher_forward_train return
+ *                             E2EMV_ESTATE: hand the tensors over again and e2emv_train_commit.
+ * e2emv_train_running_update  (E2EMV_BN_BATCH) applies the statistics of the last forward_train and of its conf forwards (each
+ *                             pair whose conf head ran, in pair order) to the caller's buffers, call by call:
+ *                               mean <- (1 - m) mean + m mean_call,  var <- (1 - m) var + m var_call n / (n - 1),  n = batch x n_kpts
+ *                             keys[i] = BatchNorm module name (e.g. "gnn.layers.3.mlp.1", an optional "module." prefix is
+ *                             ignored), d_running_mean[i] / d_running_var[i] = its fp32 device buffers.  Stream-ordered, no
+ *                             synchronisation; num_batches_tracked is the caller's (+ T, or + the conf calls).  E2EMV_ESTATE
+ *                             without a tape or in frozen mode.
+ * Not covered: momentum None (cumulative average), SyncBatchNorm across ranks, .train() without gradients (the inference
+ * path, running statistics).                                                                                              */
+#define E2EMV_BN_FROZEN 0
+#define E2EMV_BN_BATCH 1
+int e2emv_train_set_batchnorm(e2emv_ctx* ctx, int mode, float momentum);
+int e2emv_train_running_update(e2emv_ctx* ctx, int n, const char* const* keys, float* const* d_running_mean, float* const* d_running_var,
+                               void* stream);
 
 /* Backward of e2emv_w8pt with respect to the confidences (training, the pose loss of helpers.py:253-258: rot / translation
  * error of run_weighted_8_point's pose).  Inputs: the normalised correspondences and the pose the forward returned (info

@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """A training step at full depth (18 layers, 1024 keypoints, 100 Sinkhorn iterations): weights re-commit + forward with a tape +
 match loss + pose loss + backward + SGD step, with the inference forward of the same batch beside it (the row of
-tools/bench_next_rows.py, alone)."""
+tools/bench_next_rows.py, alone).  Each shape runs with frozen BatchNorm statistics and with batch statistics
+(config["frozen_batchnorm"] = False: torch's training-mode BatchNorm, running buffers updated)."""
 import os
 import sys
 import time
@@ -26,8 +27,9 @@ def timeit(fn, iters=10, warm=2):
 
 dev = torch.device("cuda:0")
 print("| stage | ms |\n|---|---|")
-for (Bt, Nt) in ((4, 1024), (8, 1024)):
-    cfg = {"GNN_layers": ["self", "cross"] * 9, "sinkhorn_iterations": 100, "conf_mlp": True, "full_output": True, "frozen_batchnorm": True}
+for (Bt, Nt, frozen) in ((4, 1024, True), (4, 1024, False), (8, 1024, True), (8, 1024, False)):
+    mode = "frozen BN" if frozen else "batch-statistics BN"
+    cfg = {"GNN_layers": ["self", "cross"] * 9, "sinkhorn_iterations": 100, "conf_mlp": True, "full_output": True, "frozen_batchnorm": frozen}
     torch.manual_seed(0)
     model = synthetic.identity_like_state(E.MultiViewMatcher(cfg)).to(dev).train()
     opt = torch.optim.SGD(model.parameters(), lr=1e-6)
@@ -54,6 +56,6 @@ for (Bt, Nt) in ((4, 1024), (8, 1024)):
         model.train()
     t_fwd = timeit(lambda: fwd(), iters=3, warm=1)
     t_step = timeit(step, iters=3, warm=1)
-    print(f"| training step, {Bt} pairs x {Nt}, 18 layers, 100 iterations | {t_step:.3f} |")
+    print(f"| training step, {Bt} pairs x {Nt}, 18 layers, 100 iterations, {mode} | {t_step:.3f} |")
     print(f"|   of which forward with the tape + losses | {t_fwd:.3f} |")
     print(f"|   for comparison: inference forward of the same batch | {f_inf:.3f} |", flush=True)
