@@ -131,353 +131,338 @@ __global__ __launch_bounds__(256) void conf_final_kernel(int N, int n_rows, int 
 
 static int round_up(int x, int m) { return (x + m - 1) / m * m; }
 
+// arithmetic of the GNN's dense contractions in one forward call
+enum class FwdMode {
+    F32,           // fp32-MFMA kernels
+    BF16X3,        // fp32 activations, split into three bf16 planes in the consumer (gemm_x3.hip, attention3.hip)
+    F16X2,         // fp32 activations, split into two fp16 planes in the consumer (gemm_h2.hip, attention_h2f)
+    F16X2_PLANES,  // activations stored as two fp16 planes (p2.h; gemm_p2.hip, gemm_p2c.hip, attention_p2.hip)
+};
+
+// what a forward call derives before its first launch: shapes, arithmetic and the carved workspace (plan_forward)
+struct FwdPlan {
+    int B, T, D, H;
+    int Nt[E2EMV_MAX_TUPLE];  // per-image keypoint counts (eval_pairs.py feeds images with different numbers of keypoints)
+    int N, n_rows, P, ldS;    // the largest count, rows per image in the activation buffers, pairs per tuple, score stride
+    bool uniform, full;       // every image has N keypoints; E2EMV_FLAG_FULL_OUTPUT
+    int64_t Mtot;             // rows of an activation buffer
+    FwdMode mode;
+    bool chain;               // F16X2_PLANES: MLP0, MLP1 and the next q | k | v (or final_proj) in one launch (gemm_p2c.hip)
+    float *x, *att, *msg, *qkv, *hid, *S;
+    char* skws;
+    int *e_x, *e_att, *e_qk, *e_vt, *e_hid;
+    float* a_x;
+    int64_t* tmp_m0[kMaxGroups];
+    float* tmp_ms0[kMaxGroups];
+    bool f16x2() const { return mode == FwdMode::F16X2 || mode == FwdMode::F16X2_PLANES; }
+};
+
 }  // namespace e2emv
 
 using namespace e2emv;
 
-static int forward_joint(e2emv_ctx* ctx, const e2emv_forward_desc* fd, const float* const* d_kpts,
-                         const float* const* d_kscores, const void* const* d_desc, float* const* d_logZ,
-                         int64_t* const* d_m0, int64_t* const* d_m1, float* const* d_ms0, float* const* d_ms1,
-                         float* const* d_conf, hipStream_t s) {
-    const int B = fd->batch, T = fd->tuple_size;
-    const int D = ctx->model.desc_dim, H = ctx->model.num_heads;
-    // per-image keypoint counts (eval_pairs.py feeds images with different numbers of keypoints)
-    int Nt[E2EMV_MAX_TUPLE] = {0};
-    int N = 0;
-    bool uniform = true;
-    for (int t = 0; t < T; ++t) {
-        Nt[t] = fd->n_kpts_img[t] > 0 ? fd->n_kpts_img[t] : fd->n_kpts;
-        N = std::max(N, Nt[t]);
-        uniform = uniform && Nt[t] == Nt[0];
-    }
-    const int n_rows = round_up(N, 128);
-    const int n_img = B * T;
-    const int64_t Mtot = (int64_t)n_img * n_rows;
-    const int P = T * (T - 1) / 2;
-    const int ldS = round_up(N, 4);  // allocation stride; a pair (i, j) uses ld = round_up(N_j, 4)
-    const bool full = (fd->flags & E2EMV_FLAG_FULL_OUTPUT) != 0;
+static int plan_forward(e2emv_ctx* ctx, const e2emv_forward_desc* fd, FwdPlan& p) {
+    p = FwdPlan{};
+    const int B = p.B = fd->batch, T = p.T = fd->tuple_size;
+    const int D = p.D = ctx->model.desc_dim, H = p.H = ctx->model.num_heads;
+    for (int t = 0; t < T; ++t) p.Nt[t] = fd->n_kpts_img[t] > 0 ? fd->n_kpts_img[t] : fd->n_kpts;
+    const int N = p.N = *std::max_element(p.Nt, p.Nt + T);
+    p.uniform = std::count(p.Nt, p.Nt + T, N) == T;
+    p.n_rows = round_up(N, 128);
+    const int64_t Mtot = p.Mtot = (int64_t)(B * T) * p.n_rows;
+    const int P = p.P = T * (T - 1) / 2;
+    const int ldS = p.ldS = round_up(N, 4);  // allocation stride; a pair (i, j) uses ld = round_up(N_j, 4)
+    p.full = (fd->flags & E2EMV_FLAG_FULL_OUTPUT) != 0;
 
-    // ---- workspace ----
-    auto al = [](size_t bytes) { return (bytes + 255) & ~size_t(255); };
-    const size_t sz_x = al((size_t)Mtot * D * 4), sz_qkv = al((size_t)Mtot * 3 * D * 4), sz_hid = al((size_t)Mtot * 2 * D * 4);
-    const size_t sz_S = al((size_t)P * B * N * ldS * 4);
-    const size_t sz_sk = sinkhorn_ws_bytes(P * B, N, N);
-    const size_t sz_match = full ? (size_t)P * (al((size_t)B * N * 8) + al((size_t)B * N * 4)) : 0;
     // bf16x3 (split operands on the bf16 pipe) pays once the 128-row GEMM tiles fill the chip; calls below half a tile per
     // CU (a pair or two - the eval_pairs.py loop) run the fp32-MFMA kernels, whose 64 x 64 tile shape and key-split
     // attention are the latency-tuned forms.  Both arithmetic modes meet the same parity bar.
     const int64_t split_min = ctx->split_min_rows >= 0 ? ctx->split_min_rows : (int64_t)128 * (ctx->num_cus / 2);
-    const bool b3 = ctx->precision != E2EMV_PRECISION_F32 && Mtot >= split_min;
-    const bool h2 = b3 && ctx->precision == E2EMV_PRECISION_F16X2;  // fp16 x 2 planes instead of bf16 x 3 (gemm_x3.hip)
-    // f16x2 on PLANE activations (p2.h): every producer epilogue emits the two fp16 planes, consumers load them straight
-    // into LDS (gemm_p2.hip, attention_p2.hip)
-    // (their operands are addressed with 32-bit byte offsets: the widest plane matrices, q | k and the hidden layer, are
-    // Mtot x 2D x 4 bytes - beyond 2 GB, 2^20 rows at D = 256, the call runs on the round-2 kernels: fp32 activations, split
-    // in the consumer)
-    const bool p2 = h2 && D == 256 && H == 4 && !ctx->layers.empty() && Mtot * 8 * D < ((int64_t)1 << 31);
-    // tile exponents of the plane tensors (p2.h): one int per 64 rows x 64 columns of x (4), attention output (4), q|k (8),
-    // V^T (4), hidden (8)
-    const size_t sz_e = p2 ? al((size_t)(Mtot / 64) * 32 * sizeof(int)) : 0;  // + max |x| per block (4 floats)
-    const size_t need = sz_x * 3 + sz_qkv + sz_hid + sz_S + sz_sk + sz_match + sz_e + 4096;
-    int rc = ws_reserve(ctx, need);
-    if (rc) return rc;
-    char* w = ctx->d_ws;
-    float* x = (float*)w; w += sz_x;
-    float* att = (float*)w; w += sz_x;     // attention output, later mdesc
-    float* msg = (float*)w; w += sz_x;     // x as planes (f16x2 on planes), later conf gather / hidden
-    float* qkv = (float*)w; w += sz_qkv;
-    float* hid = (float*)w; w += sz_hid;
-    float* S = (float*)w; w += sz_S;
-    char* skws = w; w += sz_sk;
-    int* e_x = (int*)w; w += sz_e;
-    int* e_att = e_x + (Mtot / 64) * 4;
-    int* e_qk = e_att + (Mtot / 64) * 4;
-    int* e_vt = e_qk + (Mtot / 64) * 8;
-    int* e_hid = e_vt + (Mtot / 64) * 4;
-    float* a_x = (float*)(e_hid + (Mtot / 64) * 8);  // max |x| of the blocks: the residual's share of the bound that picks x's next exponent
-    std::vector<int64_t*> tmp_m0(P, nullptr);
-    std::vector<float*> tmp_ms0(P, nullptr);
-    if (full)
-        for (int q = 0; q < P; ++q) {
-            tmp_m0[q] = (int64_t*)w; w += al((size_t)B * N * 8);
-            tmp_ms0[q] = (float*)w; w += al((size_t)B * N * 4);
-        }
+    // f16x2 on PLANE activations: every producer epilogue emits the two fp16 planes, consumers load them straight into LDS.
+    // Their operands are addressed with 32-bit byte offsets: the widest plane matrices, q | k and the hidden layer, are
+    // Mtot x 2D x 4 bytes - beyond 2 GB, 2^20 rows at D = 256, the call runs on fp32 activations, split in the consumer.
+    const bool planes = D == 256 && H == 4 && !ctx->layers.empty() && Mtot * 8 * D < ((int64_t)1 << 31);
+    if (ctx->precision == E2EMV_PRECISION_F32 || Mtot < split_min) p.mode = FwdMode::F32;
+    else if (ctx->precision != E2EMV_PRECISION_F16X2) p.mode = FwdMode::BF16X3;
+    else p.mode = planes ? FwdMode::F16X2_PLANES : FwdMode::F16X2;
 
-    // ---- ingest ----
-    const std::vector<int>& kd = ctx->kenc_dims;  // [3, c0, ..., D]
-    const int c0 = kd[1];
-    {
-        int64_t tot = 0;
-        for (size_t i = 1; i + 1 < kd.size(); ++i) tot += kd[i];
-        if (tot > 2 * D) return set_err(ctx, E2EMV_ESHAPE, "keypoint_encoder too wide for the workspace plan");
-    }
-    IngestParams ip{};
-    for (int t = 0; t < T; ++t) {
-        ip.kpts[t] = d_kpts[t]; ip.ksc[t] = d_kscores[t]; ip.desc[t] = d_desc[t];
-        ip.img_w[t] = fd->img_w[t]; ip.img_h[t] = fd->img_h[t];
-    }
-    for (int t = 0; t < T; ++t) ip.Nimg[t] = Nt[t];
-    ip.B = B; ip.T = T; ip.n_rows = n_rows; ip.D = D; ip.c0 = c0; ip.f16 = fd->desc_dtype == E2EMV_DESC_F16;
-    ip.w0 = ctx->kenc_w0; ip.b0 = ctx->kenc_b0; ip.x0 = x; ip.h0 = hid;
-    prof_begin(ctx, PS_INGEST, s);
-    hipLaunchKernelGGL(ingest_transpose, dim3(n_rows / 64, D / 64, n_img), dim3(256), 0, s, ip);
-    hipLaunchKernelGGL(ingest_kenc0, dim3((n_rows + 255) / 256, n_img), dim3(256), 0, s, ip);
-    prof_end(ctx, s);
-    E2EMV_CHECK_LAUNCH(ctx, "ingest kernels");
-
-    // ---- keypoint encoder layers 1..n through the GEMM; the last adds the descriptors ----
-    {
-        float* cur = hid;  // [Mtot][c0]
-        float* nxt = hid + Mtot * c0;
-        const int nl = (int)ctx->kenc_w.size();
-        for (int i = 0; i < nl; ++i) {
-            const int cin = kd[i + 1], cout = kd[i + 2];
-            const bool last = i == nl - 1;
-            GemmArgs g;
-            g.M = (int)Mtot; g.N = cout; g.K = cin; g.K1 = cin;
-            g.A = cur; g.lda = cin;
-            g.W = ctx->kenc_w[i]; g.ldw = cin; g.bias = ctx->kenc_b[i];
-            g.relu = !last;
-            if (last) { g.R = x; g.ldr = D; g.C = x; g.ldc = D; }
-            else { g.C = nxt; g.ldc = cout; }
-            prof_begin(ctx, PS_GEMM, s);
-            // f16x2 mode: the wide layers (fan-in >= 128) on the fp16 x 2 kernel as well - same parity bar, 3x less matrix-core time
-            rc = (h2 && ctx->kenc_wh[i]) ? launch_gemm_x3(ctx, g, ctx->kenc_wh[i], cin, s, ctx->kenc_hs[i]) : launch_gemm_nt(ctx, g, s);
-            prof_end(ctx, s);
-            if (rc) return rc;
-            cur = nxt;
-            nxt = nxt + Mtot * cout;
-        }
-    }
-
-    // ---- attentional GNN ----
-    uint16_t* xp = (uint16_t*)msg;            // x as scaled planes (msg is free until the conf head)
-    uint16_t* attp = (uint16_t*)att;          // attention output as scaled planes
-    uint16_t* qkp = (uint16_t*)qkv;           // q | k plain planes [Mtot][2D]
-    uint16_t* vtp = qkp + Mtot * 4 * D;       // V^T plain planes [n_img][H][64][n_rows]
-    uint16_t* hidp = (uint16_t*)hid;          // hidden as scaled planes [Mtot][2D]
-    if (p2) {
-        prof_begin(ctx, PS_INGEST, s);
-        // (the attention skips query tiles beyond the keypoints of an image: their exponent entries must not be stale)
-        E2EMV_HIP(ctx, hipMemsetAsync(e_x, 0, (size_t)(Mtot / 64) * 28 * sizeof(int), s));
-        rc = launch_to_planes(ctx, x, Mtot, D, D, xp, s, e_x, a_x);
-        prof_end(ctx, s);
-        if (rc) return rc;
-    }
     // f16x2 kernel generation 5: the row-local GEMMs between two attentions - MLP0, MLP1 of layer l and q | k | v of layer l + 1
     // (final_proj behind the last layer) - chained per 256-row block in ONE launch (gemm_p2c.hip).  A workgroup then walks 6 tiles
     // where the three launches walk ceil(2 rb / CUs) + ceil(rb / CUs) + ceil(3 rb / CUs) (rb = row blocks): chained when that is
     // not more (configs[1]: 256 row blocks on 256 CUs, 6 = 6, and 36 launches fewer per forward; T = 5 shapes with 160 / 320 row
     // blocks keep the three launches).  e2emv_set_f16x2_kernels: 4 = never, 105 = whenever the shapes allow.
-    bool chain = false;
-    if (p2 && ctx->gemm_chain && Mtot % 256 == 0) {
-        const int64_t rb = Mtot / 256, cu = std::max(1, ctx->num_cus);
-        auto rounds = [&](int64_t tiles) { return (tiles + cu - 1) / cu; };
-        chain = ctx->gemm_chain == 2 || 6 * rounds(rb) <= rounds(2 * rb) + rounds(rb) + rounds(3 * rb);
-    }
-    bool final_done = false;
-    auto qkv_args = [&](const LayerWeights& L) {
-        GemmP2Args q;
-        q.M = (int)Mtot; q.N = 3 * D; q.K = D; q.K1 = D; q.A = xp; q.lda = D; q.W = L.wp_qkv; q.out_scale = L.hs_qkv; q.bias = L.b_qkv;
-        q.out = P2_OUT_QKV; q.Cp = qkp; q.Vt = vtp; q.n_rows = n_rows; q.heads = H;
-        q.EA = e_x; q.EC = e_qk; q.EVt = e_vt; q.bias_amax = L.ba_qkv;
-        return q;
-    };
-    for (size_t l = 0; l < ctx->layers.size(); ++l) {
-        const LayerWeights& L = ctx->layers[l];
-        GemmArgs g;
-        if (p2) {
-            const bool last = l + 1 == ctx->layers.size();
-            if (!chain || l == 0) {  // (chained: the chain of layer l - 1 made this layer's q | k | v)
-                const GemmP2Args q = qkv_args(L);
-                prof_begin(ctx, PS_GEMM_QKV, s); rc = launch_gemm_p2(ctx, q, s); prof_end(ctx, s);
-                if (rc) return rc;
-            }
-            prof_begin(ctx, PS_ATTN, s);
-            rc = launch_attention_p2(ctx, B, T, n_rows, Nt, D, H, qkp, vtp, L.type, attp, s, e_qk, e_vt, e_att);
-            prof_end(ctx, s);
-            if (rc) return rc;
-            // hidden = relu(W0 [x | attention] + b0)   (merge folded into W0, BN folded)
-            GemmP2Args m0;
-            m0.M = (int)Mtot; m0.N = 2 * D; m0.K = 2 * D; m0.K1 = D; m0.A = xp; m0.lda = D; m0.A2 = attp; m0.lda2 = D;
-            m0.W = L.wp_mlp0; m0.out_scale = L.hs_mlp0; m0.bias = L.b_mlp0; m0.relu = true;
-            m0.out = P2_OUT_PLANES; m0.Cp = hidp; m0.ldc = 2 * D;
-            m0.EA = e_x; m0.EA2 = e_att; m0.EC = e_hid; m0.bias_amax = L.ba_mlp0;
-            // x += W1 hidden + b1; the last layer hands x to final_proj as fp32
-            GemmP2Args m1;
-            m1.M = (int)Mtot; m1.N = D; m1.K = 2 * D; m1.K1 = 2 * D; m1.A = hidp; m1.lda = 2 * D;
-            m1.W = L.wp_mlp1; m1.out_scale = L.hs_mlp1; m1.bias = L.b_mlp1; m1.Rp = xp; m1.ldr = D;
-            m1.EA = e_hid; m1.ER = e_x; m1.AR = a_x; m1.bias_amax = L.ba_mlp1;
-            if (last && !ctx->wp_final) { m1.out = P2_OUT_F32; m1.C32 = x; m1.ldc = D; }  // (final_proj then runs on the fp32-input kernel)
-            else { m1.out = P2_OUT_PLANES; m1.Cp = xp; m1.ldc = D; m1.EC = e_x; m1.AC = a_x; }
-            if (chain && (!last || ctx->wp_final)) {
-                GemmP2Args st[3] = {m0, m1, GemmP2Args()};
-                if (!last) {
-                    st[2] = qkv_args(ctx->layers[l + 1]);
-                } else {
-                    GemmP2Args& q = st[2];
-                    q.M = (int)Mtot; q.N = D; q.K = D; q.K1 = D; q.A = xp; q.lda = D; q.W = ctx->wp_final; q.out_scale = ctx->hs_final; q.bias = ctx->b_final;
-                    q.out = P2_OUT_F32; q.C32 = att; q.ldc = D; q.EA = e_x; q.bias_amax = ctx->ba_final;  // (att = mdesc below)
-                }
-                // MLP1's K steps 8 .. 15 read the hidden columns MLP0's SECOND tile stores right in front of it; q | k | v and
-                // final_proj read x_new from their first K step on
-                const int dep[3] = {P2_CHAIN_INDEP, (2 * D - 256) / 32, 0};
-                prof_begin(ctx, PS_GEMM_CHAIN, s); rc = launch_gemm_p2_chain(ctx, st, dep, 3, s); prof_end(ctx, s);
-                if (rc == E2EMV_OK) {
-                    if (last) final_done = true;
-                    continue;
-                }
-                // the chain launcher validates before it launches: a shape it does not take (ESHAPE / EINVAL) leaves nothing enqueued -
-                // this layer and the rest run a launch per GEMM (the next layer then makes its own q | k | v: `!chain` above)
-                if (rc != E2EMV_ESHAPE && rc != E2EMV_EINVAL) return rc;
-                chain = false;
-                ctx->err.clear();
-            }
-            prof_begin(ctx, PS_GEMM_MLP0, s); rc = launch_gemm_p2(ctx, m0, s); prof_end(ctx, s);
-            if (rc) return rc;
-            prof_begin(ctx, PS_GEMM_MLP1, s); rc = launch_gemm_p2(ctx, m1, s); prof_end(ctx, s);
-            if (rc) return rc;
-            continue;
+    const int64_t rb = Mtot / 256, cu = std::max(1, ctx->num_cus);
+    auto rounds = [&](int64_t tiles) { return (tiles + cu - 1) / cu; };
+    p.chain = p.mode == FwdMode::F16X2_PLANES && ctx->gemm_chain && Mtot % 256 == 0 &&
+              (ctx->gemm_chain == 2 || 6 * rounds(rb) <= rounds(2 * rb) + rounds(rb) + rounds(3 * rb));
+
+    auto al = [](size_t bytes) { return (bytes + 255) & ~size_t(255); };
+    const size_t sz_x = al((size_t)Mtot * D * 4), sz_qkv = al((size_t)Mtot * 3 * D * 4), sz_hid = al((size_t)Mtot * 2 * D * 4);
+    const size_t sz_S = al((size_t)P * B * N * ldS * 4);
+    const size_t sz_sk = sinkhorn_ws_bytes(P * B, N, N);
+    const size_t sz_match = p.full ? (size_t)P * (al((size_t)B * N * 8) + al((size_t)B * N * 4)) : 0;
+    // tile exponents of the plane tensors (p2.h): one int per 64 rows x 64 columns of x (4), attention output (4), q|k (8),
+    // V^T (4), hidden (8)
+    const size_t sz_e = p.mode == FwdMode::F16X2_PLANES ? al((size_t)(Mtot / 64) * 32 * sizeof(int)) : 0;  // + max |x| per block (4 floats)
+    const size_t need = sz_x * 3 + sz_qkv + sz_hid + sz_S + sz_sk + sz_match + sz_e + 4096;
+    if (int rc = ws_reserve(ctx, need)) return rc;
+    char* w = ctx->d_ws;
+    p.x = (float*)w; w += sz_x;
+    p.att = (float*)w; w += sz_x;    // attention output, later mdesc
+    p.msg = (float*)w; w += sz_x;    // x as planes (F16X2_PLANES), later conf gather / hidden
+    p.qkv = (float*)w; w += sz_qkv;
+    p.hid = (float*)w; w += sz_hid;
+    p.S = (float*)w; w += sz_S;
+    p.skws = w; w += sz_sk;
+    p.e_x = (int*)w; w += sz_e;
+    p.e_att = p.e_x + (Mtot / 64) * 4;
+    p.e_qk = p.e_att + (Mtot / 64) * 4;
+    p.e_vt = p.e_qk + (Mtot / 64) * 8;
+    p.e_hid = p.e_vt + (Mtot / 64) * 4;
+    p.a_x = (float*)(p.e_hid + (Mtot / 64) * 8);  // max |x| of the blocks: the residual's share of the bound that picks x's next exponent
+    if (p.full)  // (matches0 / mscores0 of the pairs whose conf head needs them when the caller does not)
+        for (int q = 0; q < P; ++q) {
+            p.tmp_m0[q] = (int64_t*)w; w += al((size_t)B * N * 8);
+            p.tmp_ms0[q] = (float*)w; w += al((size_t)B * N * 4);
         }
-        if (b3) {
-            // q|k|v on the split-operand GEMM with a plain fp32 output; the attention kernel splits Q / K / V^T into
-            // planes on the way in
-            g = GemmArgs();
-            g.M = (int)Mtot; g.N = 3 * D; g.K = D; g.K1 = D; g.A = x; g.lda = D; g.bias = L.b_qkv; g.C = qkv; g.ldc = 3 * D;
-            prof_begin(ctx, PS_GEMM, s); rc = h2 ? launch_gemm_x3(ctx, g, L.wh_qkv, D, s, L.hs_qkv) : launch_gemm_x3(ctx, g, L.w3_qkv, D, s); prof_end(ctx, s);
-            if (rc) return rc;
-            prof_begin(ctx, PS_ATTN, s);
-            rc = launch_attention3f(ctx, B, T, n_rows, Nt, D, H, qkv, L.type, att, s, h2);
-            prof_end(ctx, s);
-            if (rc) return rc;
-        } else {
-        // q|k|v = x Wqkv^T + b
-        g = GemmArgs();
-        g.M = (int)Mtot; g.N = 3 * D; g.K = D; g.K1 = D; g.A = x; g.lda = D; g.W = L.w_qkv; g.ldw = D; g.bias = L.b_qkv;
-        g.C = qkv; g.ldc = 3 * D;
-        prof_begin(ctx, PS_GEMM, s); rc = launch_gemm_nt(ctx, g, s); prof_end(ctx, s);
-        if (rc) return rc;
+    return E2EMV_OK;
+}
+
+// A GEMM on fp32 activations in the plan's arithmetic (profile slot "gemm").  g.W are the fp32 weights, wh (2^s W as fp16 x 2
+// planes, hs = 2^-s) and w3 (bf16x3 planes) the same weights, [N][K]; where the mode's form is null the fp32 kernel runs.
+static int gemm_fp32_act(e2emv_ctx* ctx, const FwdPlan& p, const GemmArgs& g, const uint16_t* wh, float hs, const uint16_t* w3, hipStream_t s) {
+    prof_begin(ctx, PS_GEMM, s);
+    int rc;
+    if (p.f16x2() && wh) rc = launch_gemm_x3(ctx, g, wh, g.K, s, hs);
+    else if (p.mode == FwdMode::BF16X3 && w3) rc = launch_gemm_x3(ctx, g, w3, g.K, s);
+    else rc = launch_gemm_nt(ctx, g, s);
+    prof_end(ctx, s);
+    return rc;
+}
+
+// ingest, then keypoint encoder layers 1..n through the GEMM; the last adds the descriptors: x = the GNN's input
+static int encode(e2emv_ctx* ctx, const FwdPlan& p, const e2emv_forward_desc* fd, const float* const* d_kpts,
+                  const float* const* d_kscores, const void* const* d_desc, hipStream_t s) {
+    const std::vector<int>& kd = ctx->kenc_dims;  // [3, c0, ..., D]
+    const int c0 = kd[1];
+    int64_t tot = 0;
+    for (size_t i = 1; i + 1 < kd.size(); ++i) tot += kd[i];
+    if (tot > 2 * p.D) return set_err(ctx, E2EMV_ESHAPE, "keypoint_encoder too wide for the workspace plan");
+    IngestParams ip{};
+    for (int t = 0; t < p.T; ++t) {
+        ip.kpts[t] = d_kpts[t]; ip.ksc[t] = d_kscores[t]; ip.desc[t] = d_desc[t];
+        ip.img_w[t] = fd->img_w[t]; ip.img_h[t] = fd->img_h[t]; ip.Nimg[t] = p.Nt[t];
+    }
+    ip.B = p.B; ip.T = p.T; ip.n_rows = p.n_rows; ip.D = p.D; ip.c0 = c0; ip.f16 = fd->desc_dtype == E2EMV_DESC_F16;
+    ip.w0 = ctx->kenc_w0; ip.b0 = ctx->kenc_b0; ip.x0 = p.x; ip.h0 = p.hid;
+    prof_begin(ctx, PS_INGEST, s);
+    hipLaunchKernelGGL(ingest_transpose, dim3(p.n_rows / 64, p.D / 64, p.B * p.T), dim3(256), 0, s, ip);
+    hipLaunchKernelGGL(ingest_kenc0, dim3((p.n_rows + 255) / 256, p.B * p.T), dim3(256), 0, s, ip);
+    prof_end(ctx, s);
+    E2EMV_CHECK_LAUNCH(ctx, "ingest kernels");
+
+    float* cur = p.hid;  // [Mtot][c0]
+    float* nxt = p.hid + p.Mtot * c0;
+    const int nl = (int)ctx->kenc_w.size();
+    for (int i = 0; i < nl; ++i) {
+        const int cin = kd[i + 1], cout = kd[i + 2];
+        const bool last = i == nl - 1;
+        GemmArgs g;
+        g.M = (int)p.Mtot; g.N = cout; g.K = cin; g.K1 = cin;
+        g.A = cur; g.lda = cin;
+        g.W = ctx->kenc_w[i]; g.ldw = cin; g.bias = ctx->kenc_b[i];
+        g.relu = !last;
+        if (last) { g.R = p.x; g.ldr = p.D; g.C = p.x; g.ldc = p.D; }
+        else { g.C = nxt; g.ldc = cout; }
+        // no bf16x3 planes; f16x2 mode: the wide layers (fan-in >= 128) on the fp16 x 2 kernel as well - same parity bar, 3x less
+        // matrix-core time
+        if (int rc = gemm_fp32_act(ctx, p, g, ctx->kenc_wh[i], ctx->kenc_hs[i], nullptr, s)) return rc;
+        cur = nxt;
+        nxt = nxt + p.Mtot * cout;
+    }
+    return E2EMV_OK;
+}
+
+// F32, BF16X3 and F16X2: the GNN layers and final_proj (mdesc = att) on fp32 activations
+static int gnn_fp32_activations(e2emv_ctx* ctx, const FwdPlan& p, hipStream_t s) {
+    const int D = p.D, M = (int)p.Mtot;
+    for (const LayerWeights& L : ctx->layers) {
+        // q|k|v = x Wqkv^T + b; the split modes' attention kernels split Q / K / V^T into planes on the way in
+        GemmArgs g;
+        g.M = M; g.N = 3 * D; g.K = D; g.K1 = D; g.A = p.x; g.lda = D; g.W = L.w_qkv; g.ldw = D; g.bias = L.b_qkv;
+        g.C = p.qkv; g.ldc = 3 * D;
+        int rc;
+        if ((rc = gemm_fp32_act(ctx, p, g, L.wh_qkv, L.hs_qkv, L.w3_qkv, s))) return rc;
         prof_begin(ctx, PS_ATTN, s);
-        rc = launch_attention(ctx, B, T, n_rows, Nt, D, H, qkv, L.type, att, s);
+        if (p.mode == FwdMode::F32) rc = launch_attention(ctx, p.B, p.T, p.n_rows, p.Nt, D, p.H, p.qkv, L.type, p.att, s);
+        else rc = launch_attention3f(ctx, p.B, p.T, p.n_rows, p.Nt, D, p.H, p.qkv, L.type, p.att, s, p.mode == FwdMode::F16X2);
         prof_end(ctx, s);
         if (rc) return rc;
-        }
         // hidden = relu(BN(W0 [x | message] + b0))   (concat never materialised: two K segments; the second is the attention
         // output, the merge conv folded into W0)
         g = GemmArgs();
-        g.M = (int)Mtot; g.N = 2 * D; g.K = 2 * D; g.K1 = D; g.A = x; g.lda = D; g.A2 = att; g.lda2 = D;
-        g.W = L.w_mlp0; g.ldw = 2 * D; g.bias = L.b_mlp0; g.relu = true; g.C = hid; g.ldc = 2 * D;
-        // bf16x3 mode: the two MLP GEMMs (2/3 of the layer's GEMM flops) run on the bf16 pipe with split operands
-        prof_begin(ctx, PS_GEMM, s);
-        rc = h2 ? launch_gemm_x3(ctx, g, L.wh_mlp0, 2 * D, s, L.hs_mlp0) : b3 ? launch_gemm_x3(ctx, g, L.w3_mlp0, 2 * D, s) : launch_gemm_nt(ctx, g, s);
-        prof_end(ctx, s);
-        if (rc) return rc;
+        g.M = M; g.N = 2 * D; g.K = 2 * D; g.K1 = D; g.A = p.x; g.lda = D; g.A2 = p.att; g.lda2 = D;
+        g.W = L.w_mlp0; g.ldw = 2 * D; g.bias = L.b_mlp0; g.relu = true; g.C = p.hid; g.ldc = 2 * D;
+        if ((rc = gemm_fp32_act(ctx, p, g, L.wh_mlp0, L.hs_mlp0, L.w3_mlp0, s))) return rc;
         // x += W1 hidden + b1
         g = GemmArgs();
-        g.M = (int)Mtot; g.N = D; g.K = 2 * D; g.K1 = 2 * D; g.A = hid; g.lda = 2 * D; g.W = L.w_mlp1; g.ldw = 2 * D;
-        g.bias = L.b_mlp1; g.R = x; g.ldr = D; g.C = x; g.ldc = D;
-        prof_begin(ctx, PS_GEMM, s);
-        rc = h2 ? launch_gemm_x3(ctx, g, L.wh_mlp1, 2 * D, s, L.hs_mlp1) : b3 ? launch_gemm_x3(ctx, g, L.w3_mlp1, 2 * D, s) : launch_gemm_nt(ctx, g, s);
+        g.M = M; g.N = D; g.K = 2 * D; g.K1 = 2 * D; g.A = p.hid; g.lda = 2 * D; g.W = L.w_mlp1; g.ldw = 2 * D;
+        g.bias = L.b_mlp1; g.R = p.x; g.ldr = D; g.C = p.x; g.ldc = D;
+        if ((rc = gemm_fp32_act(ctx, p, g, L.wh_mlp1, L.hs_mlp1, L.w3_mlp1, s))) return rc;
+    }
+    GemmArgs g;  // (no bf16x3 planes of final_proj)
+    g.M = M; g.N = D; g.K = D; g.K1 = D; g.A = p.x; g.lda = D; g.W = ctx->w_final; g.ldw = D; g.bias = ctx->b_final;
+    g.C = p.att; g.ldc = D;
+    return gemm_fp32_act(ctx, p, g, ctx->wh_final, ctx->hs_final, nullptr, s);
+}
+
+// F16X2_PLANES: x to planes, the GNN layers - a launch per GEMM or chained - and final_proj on planes (D = 256: wp_final exists)
+static int gnn_planes(e2emv_ctx* ctx, const FwdPlan& p, hipStream_t s) {
+    const int D = p.D, H = p.H, M = (int)p.Mtot;
+    uint16_t* xp = (uint16_t*)p.msg;       // x as scaled planes (msg is free until the conf head)
+    uint16_t* attp = (uint16_t*)p.att;     // attention output as scaled planes
+    uint16_t* qkp = (uint16_t*)p.qkv;      // q | k plain planes [Mtot][2D]
+    uint16_t* vtp = qkp + p.Mtot * 4 * D;  // V^T plain planes [n_img][H][64][n_rows]
+    uint16_t* hidp = (uint16_t*)p.hid;     // hidden as scaled planes [Mtot][2D]
+    prof_begin(ctx, PS_INGEST, s);
+    // (the attention skips query tiles beyond the keypoints of an image: their exponent entries must not be stale)
+    E2EMV_HIP(ctx, hipMemsetAsync(p.e_x, 0, (size_t)(p.Mtot / 64) * 28 * sizeof(int), s));
+    int rc = launch_to_planes(ctx, p.x, p.Mtot, D, D, xp, s, p.e_x, p.a_x);
+    prof_end(ctx, s);
+    if (rc) return rc;
+    auto qkv_args = [&](const LayerWeights& L) {
+        GemmP2Args q;
+        q.M = M; q.N = 3 * D; q.K = D; q.K1 = D; q.A = xp; q.lda = D; q.W = L.wp_qkv; q.out_scale = L.hs_qkv; q.bias = L.b_qkv;
+        q.out = P2_OUT_QKV; q.Cp = qkp; q.Vt = vtp; q.n_rows = p.n_rows; q.heads = H;
+        q.EA = p.e_x; q.EC = p.e_qk; q.EVt = p.e_vt; q.bias_amax = L.ba_qkv;
+        return q;
+    };
+    // final_proj: x arrives as planes with their tile exponents, any magnitude fp32 holds is fine
+    GemmP2Args fin;
+    fin.M = M; fin.N = D; fin.K = D; fin.K1 = D; fin.A = xp; fin.lda = D; fin.W = ctx->wp_final; fin.out_scale = ctx->hs_final;
+    fin.bias = ctx->b_final; fin.out = P2_OUT_F32; fin.C32 = p.att; fin.ldc = D; fin.EA = p.e_x; fin.bias_amax = ctx->ba_final;
+    for (size_t l = 0; l < ctx->layers.size(); ++l) {
+        const LayerWeights& L = ctx->layers[l];
+        if (!p.chain || l == 0) {  // (chained: the chain of layer l - 1 made this layer's q | k | v)
+            prof_begin(ctx, PS_GEMM_QKV, s); rc = launch_gemm_p2(ctx, qkv_args(L), s); prof_end(ctx, s);
+            if (rc) return rc;
+        }
+        prof_begin(ctx, PS_ATTN, s);
+        rc = launch_attention_p2(ctx, p.B, p.T, p.n_rows, p.Nt, D, H, qkp, vtp, L.type, attp, s, p.e_qk, p.e_vt, p.e_att);
         prof_end(ctx, s);
         if (rc) return rc;
-    }
-
-    // ---- final projection ----
-    float* mdesc = att;
-    if (final_done) {
-        // (the last layer's chain wrote mdesc)
-    } else if (p2 && ctx->wp_final) {  // x arrives as planes with their tile exponents: any magnitude fp32 holds is fine
-        GemmP2Args q;
-        q.M = (int)Mtot; q.N = D; q.K = D; q.K1 = D; q.A = xp; q.lda = D; q.W = ctx->wp_final; q.out_scale = ctx->hs_final; q.bias = ctx->b_final;
-        q.out = P2_OUT_F32; q.C32 = mdesc; q.ldc = D; q.EA = e_x; q.bias_amax = ctx->ba_final;
-        prof_begin(ctx, PS_GEMM, s); rc = launch_gemm_p2(ctx, q, s); prof_end(ctx, s);
+        // hidden = relu(W0 [x | attention] + b0)   (merge folded into W0, BN folded)
+        GemmP2Args m0;
+        m0.M = M; m0.N = 2 * D; m0.K = 2 * D; m0.K1 = D; m0.A = xp; m0.lda = D; m0.A2 = attp; m0.lda2 = D;
+        m0.W = L.wp_mlp0; m0.out_scale = L.hs_mlp0; m0.bias = L.b_mlp0; m0.relu = true; m0.out = P2_OUT_PLANES; m0.Cp = hidp; m0.ldc = 2 * D;
+        m0.EA = p.e_x; m0.EA2 = p.e_att; m0.EC = p.e_hid; m0.bias_amax = L.ba_mlp0;
+        // x += W1 hidden + b1
+        GemmP2Args m1;
+        m1.M = M; m1.N = D; m1.K = 2 * D; m1.K1 = 2 * D; m1.A = hidp; m1.lda = 2 * D; m1.Rp = xp; m1.ldr = D;
+        m1.W = L.wp_mlp1; m1.out_scale = L.hs_mlp1; m1.bias = L.b_mlp1; m1.out = P2_OUT_PLANES; m1.Cp = xp; m1.ldc = D;
+        m1.EA = p.e_hid; m1.ER = p.e_x; m1.AR = p.a_x; m1.EC = p.e_x; m1.AC = p.a_x; m1.bias_amax = L.ba_mlp1;
+        if (p.chain) {
+            const GemmP2Args st[3] = {m0, m1, l + 1 == ctx->layers.size() ? fin : qkv_args(ctx->layers[l + 1])};
+            // MLP1's K steps 8 .. 15 read the hidden columns MLP0's SECOND tile stores right in front of it; q | k | v and
+            // final_proj read x_new from their first K step on
+            const int dep[3] = {P2_CHAIN_INDEP, (2 * D - 256) / 32, 0};
+            prof_begin(ctx, PS_GEMM_CHAIN, s); rc = launch_gemm_p2_chain(ctx, st, dep, 3, s); prof_end(ctx, s);
+            if (rc) return rc;
+            continue;
+        }
+        prof_begin(ctx, PS_GEMM_MLP0, s); rc = launch_gemm_p2(ctx, m0, s); prof_end(ctx, s);
         if (rc) return rc;
-    } else {
-        GemmArgs g;
-        g.M = (int)Mtot; g.N = D; g.K = D; g.K1 = D; g.A = x; g.lda = D; g.W = ctx->w_final; g.ldw = D; g.bias = ctx->b_final;
-        g.C = mdesc; g.ldc = D;
-        prof_begin(ctx, PS_GEMM, s); rc = h2 ? launch_gemm_x3(ctx, g, ctx->wh_final, D, s, ctx->hs_final) : launch_gemm_nt(ctx, g, s); prof_end(ctx, s);
+        prof_begin(ctx, PS_GEMM_MLP1, s); rc = launch_gemm_p2(ctx, m1, s); prof_end(ctx, s);
         if (rc) return rc;
     }
+    if (p.chain) return E2EMV_OK;  // (the last layer's chain ran final_proj)
+    prof_begin(ctx, PS_GEMM, s); rc = launch_gemm_p2(ctx, fin, s); prof_end(ctx, s);
+    return rc;
+}
 
-    ctx->last_mdesc = mdesc; ctx->md_imgs = B * T; ctx->md_rows = n_rows; ctx->md_n = N; ctx->md_dim = D;  // (e2emv_get_descriptors)
-
-    // ---- all pairs: scores -> Sinkhorn -> matches; then the conf head per pair.  With equal keypoint counts all
-    // P*B problems go through ONE Sinkhorn batch; a ragged tuple runs one batch per pair (M = N_i, N = N_j).
-    const int64_t tuple_stride = (int64_t)T * n_rows * D;
-    const int64_t pair_stride = (int64_t)B * N * ldS;
-    SinkhornOut so;
-    so.n_groups = P;
+// All pairs: score GEMM (1/sqrt(D) fused) -> Sinkhorn -> matches, into so (one output group per pair).  With equal keypoint
+// counts all P*B problems go through ONE Sinkhorn batch; a ragged tuple runs one batch per pair (M = N_i, N = N_j).
+static int match_pairs(e2emv_ctx* ctx, const FwdPlan& p, const e2emv_forward_desc* fd, float* const* d_logZ, int64_t* const* d_m0,
+                       int64_t* const* d_m1, float* const* d_ms0, float* const* d_ms1, float* const* d_conf, SinkhornOut& so,
+                       hipStream_t s) {
+    const int B = p.B, D = p.D, n_rows = p.n_rows;
+    const int64_t tuple_stride = (int64_t)p.T * n_rows * D;
+    const int64_t pair_stride = (int64_t)B * p.N * p.ldS;
+    so.n_groups = p.P;
     so.group_batch = B;
-    std::vector<bool> want_conf(P, false);
-    std::vector<int64_t*> pm0(P, nullptr);
-    std::vector<float*> pms0(P, nullptr);
+    int rc;
     int pidx = 0;
-    for (int j = 0; j < T; ++j)
+    for (int j = 0; j < p.T; ++j)
         for (int i = 0; i < j; ++i, ++pidx) {
-            const int Ni = Nt[i], Nj = Nt[j], ldj = round_up(Nj, 4);
+            const int Ni = p.Nt[i], Nj = p.Nt[j], ldj = round_up(Nj, 4);
             GemmArgs g;
             g.batch = B; g.M = Ni; g.N = Nj; g.K = D; g.K1 = D;
-            g.A = mdesc + (int64_t)i * n_rows * D; g.lda = D; g.sA = tuple_stride;
-            g.W = mdesc + (int64_t)j * n_rows * D; g.ldw = D; g.sW = tuple_stride;
-            g.C = S + pidx * pair_stride; g.ldc = ldj; g.sC = (int64_t)Ni * ldj;
+            g.A = p.att + (int64_t)i * n_rows * D; g.lda = D; g.sA = tuple_stride;
+            g.W = p.att + (int64_t)j * n_rows * D; g.ldw = D; g.sW = tuple_stride;
+            g.C = p.S + pidx * pair_stride; g.ldc = ldj; g.sC = (int64_t)Ni * ldj;
             g.scale = 1.0f / sqrtf((float)D);
             prof_begin(ctx, PS_SCORE, s); rc = launch_gemm_nt(ctx, g, s); prof_end(ctx, s);
             if (rc) return rc;
-            want_conf[pidx] = full && d_conf && d_conf[pidx];
-            SinkhornOut one;  // outputs of this pair
+            const bool want_conf = p.full && d_conf && d_conf[pidx];
+            SinkhornOut one;  // outputs of this pair: one group of B problems
             one.logZ[0] = d_logZ ? d_logZ[pidx] : nullptr;
-            if (full) {
-                one.m0[0] = (d_m0 && d_m0[pidx]) ? d_m0[pidx] : (want_conf[pidx] ? tmp_m0[pidx] : nullptr);
+            if (p.full) {
+                one.m0[0] = (d_m0 && d_m0[pidx]) ? d_m0[pidx] : (want_conf ? p.tmp_m0[pidx] : nullptr);
                 one.m1[0] = d_m1 ? d_m1[pidx] : nullptr;
-                one.ms0[0] = (d_ms0 && d_ms0[pidx]) ? d_ms0[pidx] : (want_conf[pidx] ? tmp_ms0[pidx] : nullptr);
+                one.ms0[0] = (d_ms0 && d_ms0[pidx]) ? d_ms0[pidx] : (want_conf ? p.tmp_ms0[pidx] : nullptr);
                 one.ms1[0] = d_ms1 ? d_ms1[pidx] : nullptr;
             }
-            pm0[pidx] = one.m0[0];
-            pms0[pidx] = one.ms0[0];
             so.logZ[pidx] = one.logZ[0]; so.m0[pidx] = one.m0[0]; so.m1[pidx] = one.m1[0];
             so.ms0[pidx] = one.ms0[0]; so.ms1[pidx] = one.ms1[0];
-            if (!uniform) {
-                one.n_groups = 1;
-                one.group_batch = B;
+            if (!p.uniform) {
                 prof_begin(ctx, PS_SINKHORN, s);
-                rc = launch_sinkhorn(ctx, B, Ni, Nj, S + pidx * pair_stride, ldj, ctx->bin_score, fd->sinkhorn_iters,
-                                     fd->match_threshold, one, skws, s);
+                rc = launch_sinkhorn(ctx, B, Ni, Nj, p.S + pidx * pair_stride, ldj, ctx->bin_score, fd->sinkhorn_iters,
+                                     fd->match_threshold, one, p.skws, s);
                 prof_end(ctx, s);
                 if (rc) return rc;
             }
         }
-    if (uniform) {
+    if (p.uniform) {
         prof_begin(ctx, PS_SINKHORN, s);
-        rc = launch_sinkhorn(ctx, P * B, N, N, S, ldS, ctx->bin_score, fd->sinkhorn_iters, fd->match_threshold, so, skws, s);
+        rc = launch_sinkhorn(ctx, p.P * B, p.N, p.N, p.S, p.ldS, ctx->bin_score, fd->sinkhorn_iters, fd->match_threshold, so, p.skws, s);
         prof_end(ctx, s);
         if (rc) return rc;
     }
-    pidx = 0;
-    for (int j = 0; j < T; ++j)
+    return E2EMV_OK;
+}
+
+// the conf head of every pair whose confidences the caller wants (full output), from the matches0 / mscores0 in so
+static int conf_heads(e2emv_ctx* ctx, const FwdPlan& p, const SinkhornOut& so, float* const* d_conf, hipStream_t s) {
+    const int B = p.B, D = p.D, n_rows = p.n_rows;
+    const int64_t tuple_stride = (int64_t)p.T * n_rows * D;
+    const bool use_mlp = ctx->model.conf_mlp != 0;
+    float* gathered = p.msg;  // [B][n_rows][D] ([B][n_rows][2D] in the f16x2 modes)
+    float* chid = p.hid;      // [B][n_rows][D]
+    int rc;
+    int pidx = 0;
+    for (int j = 0; j < p.T; ++j)
         for (int i = 0; i < j; ++i, ++pidx) {
-            if (!want_conf[pidx]) continue;
-            const int Ni = Nt[i];
-            const bool use_mlp = ctx->model.conf_mlp != 0;
-            float* gathered = msg;          // [B][n_rows][D] ([B][n_rows][2D] in the f16x2 modes)
-            float* chid = hid;              // [B][n_rows][D]
-            if (use_mlp && p2 && ctx->wp_conf0) {
+            if (!p.full || !d_conf || !d_conf[pidx]) continue;
+            const int Ni = p.Nt[i];
+            const float* mdesc_i = p.att + (int64_t)i * n_rows * D;
+            const float* mdesc_j = p.att + (int64_t)j * n_rows * D;
+            if (use_mlp && p.mode == FwdMode::F16X2_PLANES && ctx->wp_conf0) {
                 // plane kernels: [mdesc_i | mdesc_j(match)] -> planes with tile exponents -> conf_mlp.0 (+ BN, ReLU) on gemm_p2
                 // (one pass: the gather is resolved in the source address of the plane conversion - p2_tools.hip)
+                uint16_t* feat = (uint16_t*)p.qkv;  // [B * n_rows][2D]
                 prof_begin(ctx, PS_CONF, s);
-                rc = launch_conf_gather_planes(ctx, mdesc + (int64_t)i * n_rows * D, mdesc + (int64_t)j * n_rows * D, tuple_stride, pm0[pidx], Ni, n_rows, B, D, qkp,
-                                               e_hid, s);
+                rc = launch_conf_gather_planes(ctx, mdesc_i, mdesc_j, tuple_stride, so.m0[pidx], Ni, n_rows, B, D, feat, p.e_hid, s);
                 prof_end(ctx, s);
                 if (rc) return rc;
                 GemmP2Args q;
-                q.M = B * n_rows; q.N = D; q.K = 2 * D; q.K1 = 2 * D; q.A = qkp; q.lda = 2 * D; q.W = ctx->wp_conf0; q.out_scale = ctx->hs_conf0;
-                q.bias = ctx->b_conf0; q.relu = true; q.out = P2_OUT_F32; q.C32 = chid; q.ldc = D; q.EA = e_hid; q.bias_amax = ctx->ba_conf0;
+                q.M = B * n_rows; q.N = D; q.K = 2 * D; q.K1 = 2 * D; q.A = feat; q.lda = 2 * D; q.W = ctx->wp_conf0; q.out_scale = ctx->hs_conf0;
+                q.bias = ctx->b_conf0; q.relu = true; q.out = P2_OUT_F32; q.C32 = chid; q.ldc = D; q.EA = p.e_hid; q.bias_amax = ctx->ba_conf0;
                 prof_begin(ctx, PS_GEMM, s); rc = launch_gemm_p2(ctx, q, s); prof_end(ctx, s);
                 if (rc) return rc;
-            } else if (use_mlp && h2 && ctx->wh_conf0) {
+            } else if (use_mlp && p.f16x2() && ctx->wh_conf0) {
                 prof_begin(ctx, PS_CONF, s);
-                hipLaunchKernelGGL(conf_gather2_kernel, dim3((n_rows + 3) / 4, B), dim3(256), 0, s, Ni, n_rows, D, mdesc + (int64_t)i * n_rows * D,
-                                   mdesc + (int64_t)j * n_rows * D, tuple_stride, pm0[pidx], gathered);
+                hipLaunchKernelGGL(conf_gather2_kernel, dim3((n_rows + 3) / 4, B), dim3(256), 0, s, Ni, n_rows, D, mdesc_i, mdesc_j,
+                                   tuple_stride, so.m0[pidx], gathered);
                 prof_end(ctx, s);
                 GemmArgs c;
                 c.M = B * n_rows; c.N = D; c.K = 2 * D; c.K1 = 2 * D; c.A = gathered; c.lda = 2 * D;
@@ -486,12 +471,12 @@ static int forward_joint(e2emv_ctx* ctx, const e2emv_forward_desc* fd, const flo
                 if (rc) return rc;
             } else if (use_mlp) {
                 prof_begin(ctx, PS_CONF, s);
-                hipLaunchKernelGGL(conf_gather_kernel, dim3((n_rows + 3) / 4, B), dim3(256), 0, s, Ni, n_rows, D,
-                                   mdesc + (int64_t)j * n_rows * D, tuple_stride, pm0[pidx], gathered);
+                hipLaunchKernelGGL(conf_gather_kernel, dim3((n_rows + 3) / 4, B), dim3(256), 0, s, Ni, n_rows, D, mdesc_j, tuple_stride,
+                                   so.m0[pidx], gathered);
                 prof_end(ctx, s);
                 GemmArgs c;
                 c.batch = B; c.M = n_rows; c.N = D; c.K = 2 * D; c.K1 = D;
-                c.A = mdesc + (int64_t)i * n_rows * D; c.lda = D; c.sA = tuple_stride;
+                c.A = mdesc_i; c.lda = D; c.sA = tuple_stride;
                 c.A2 = gathered; c.lda2 = D; c.sA2 = (int64_t)n_rows * D;
                 c.W = ctx->w_conf0; c.ldw = 2 * D; c.bias = ctx->b_conf0; c.relu = true;
                 c.C = chid; c.ldc = D; c.sC = (int64_t)n_rows * D;
@@ -500,11 +485,25 @@ static int forward_joint(e2emv_ctx* ctx, const e2emv_forward_desc* fd, const flo
             }
             prof_begin(ctx, PS_CONF, s);
             hipLaunchKernelGGL(conf_final_kernel, dim3((Ni + 3) / 4, B), dim3(256), 0, s, Ni, n_rows, D, chid, ctx->w_conf1,
-                               ctx->b_conf1, pm0[pidx], pms0[pidx], use_mlp ? 1 : 0, d_conf[pidx]);
+                               ctx->b_conf1, so.m0[pidx], so.ms0[pidx], use_mlp ? 1 : 0, d_conf[pidx]);
             prof_end(ctx, s);
             E2EMV_CHECK_LAUNCH(ctx, "conf kernels");
         }
     return E2EMV_OK;
+}
+
+static int forward_joint(e2emv_ctx* ctx, const e2emv_forward_desc* fd, const float* const* d_kpts,
+                         const float* const* d_kscores, const void* const* d_desc, float* const* d_logZ,
+                         int64_t* const* d_m0, int64_t* const* d_m1, float* const* d_ms0, float* const* d_ms1,
+                         float* const* d_conf, hipStream_t s) {
+    FwdPlan p;
+    if (int rc = plan_forward(ctx, fd, p)) return rc;
+    if (int rc = encode(ctx, p, fd, d_kpts, d_kscores, d_desc, s)) return rc;
+    if (int rc = p.mode == FwdMode::F16X2_PLANES ? gnn_planes(ctx, p, s) : gnn_fp32_activations(ctx, p, s)) return rc;
+    ctx->last_mdesc = p.att; ctx->md_imgs = p.B * p.T; ctx->md_rows = p.n_rows; ctx->md_n = p.N; ctx->md_dim = p.D;  // (e2emv_get_descriptors)
+    SinkhornOut so;
+    if (int rc = match_pairs(ctx, p, fd, d_logZ, d_m0, d_m1, d_ms0, d_ms1, d_conf, so, s)) return rc;
+    return conf_heads(ctx, p, so, d_conf, s);
 }
 
 extern "C" int e2emv_matcher_forward(e2emv_ctx* ctx, const e2emv_forward_desc* fd, const float* const* d_kpts,

@@ -58,8 +58,8 @@ def _compare(out, ref, pairs):
 
 
 # "-chain": generation 5 with the GEMM chain forced on; "-r4": a launch per GEMM (the T = 5 path).  The superseded generations
-# ("-r2", "-r3") left the product in round 6 (measurement build only); the round-2 kernels still serve widths other than 256 and
-# are reached that way by tests/test_gpu_golden_direct.py (D = 64)
+# ("-r2", "-r3") left the product in round 6 (measurement build only); the round-2 kernels (f16x2 on fp32 activations) still
+# serve every width other than 256 with 4 heads: test_pair_width_128_two_heads
 PRECISIONS = ["f32", "bf16x3", "f16x2", "f16x2-chain", "f16x2-r4"]
 
 
@@ -69,6 +69,16 @@ def test_pair_random_weights(gpu, conf_mlp, precision):
     cfg = {"GNN_layers": ["self", "cross"] * 2, "sinkhorn_iterations": 20, "conf_mlp": conf_mlp, "match_threshold": 0.0,
            "mfma_precision": precision}
     out, ref, _ = _run(cfg, dict(batch=2, tuple_size=2, n_kpts=256), gpu, seed=1)
+    _compare(out, ref, [(0, 1)])
+
+
+@pytest.mark.parametrize("precision", ["f16x2", "bf16x3"])
+def test_pair_width_128_two_heads(gpu, precision):
+    """D = 128 with 2 heads: the split modes on fp32 activations (f16x2: gemm_h2 + attention_h2f, the plane kernels take only
+    D = 256 with 4 heads; bf16x3: gemm_x3 + attention3f), the encoder's layers below fan-in 128 on the fp32 kernel."""
+    cfg = {"descriptor_dim": 128, "num_heads": 2, "keypoint_encoder": [32, 64, 128], "GNN_layers": ["self", "cross"] * 2,
+           "sinkhorn_iterations": 20, "conf_mlp": True, "match_threshold": 0.0, "mfma_precision": precision}
+    out, ref, _ = _run(cfg, dict(batch=2, tuple_size=2, n_kpts=256, desc_dim=128), gpu, seed=6)
     _compare(out, ref, [(0, 1)])
 
 
