@@ -11,9 +11,13 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libe2emv.so")
-SOURCES = ["ctx.hip", "gemm.hip", "attention.hip", "gemm3.hip", "gemm_x3.hip", "gemm_h2.hip", "gemm_p2.hip", "gemm_p2c.hip", "attention_p2.hip", "attention_p2w.hip", "p2_tools.hip", "attention3.hip", "split3_api.hip", "sinkhorn.hip", "pose.hip", "ba2view.hip", "gtmatch.hip",
+SOURCES = ["ctx.hip", "gemm.hip", "attention.hip", "gemm3.hip", "gemm_x3.hip", "gemm_h2.hip", "gemm_p2.hip", "gemm_p2c.hip", "attention_p2.hip", "attention_p2w.hip", "p2_tools.hip", "attention3.hip", "split3_api.hip", "sinkhorn.hip", "sinkhorn_stream.hip", "sinkhorn_resident.hip", "sinkhorn_regs.hip", "pose.hip", "ba2view.hip", "gtmatch.hip",
            "mvinit.hip", "mvba.hip", "ransac.hip", "superpoint.hip", "forward.hip", "train.hip", "comm.hip"]
 # (one build: every kernel in these files is part of the product library; measurements and probes live in standalone files under tools/)
+# The kernels of this file keep most of their data in registers they address by number, outside the window their amdgpu_num_vgpr
+# attribute leaves to the compiler.  The device assembly hipcc ASSEMBLES into this very object is kept (-save-temps: one compile,
+# its own intermediate .s - not a second -S compile that could diverge) as build/<stem>.s and checked (check_register_window)
+REGISTER_WINDOW = ("sinkhorn_regs.hip", ("sinkhorn_resident128", "sinkhorn_resident2k"), 56)
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-fvisibility-inlines-hidden", "-ffp-contract=fast", "-Wno-unused-result"]
 
 
@@ -79,19 +83,16 @@ def _build(hipcc, objdir, lib, verbose):
     if any("tgsplit" in f for f in FLAGS):
         raise RuntimeError("libe2emv is built for CU mode: -mtgsplit breaks the in-workgroup hand-off of gemm_p2c.hip")
     procs = []
+    stem = REGISTER_WINDOW[0].replace(".hip", "")
     for src in SOURCES:
         obj = os.path.join(objdir, src.replace(".hip", ".o"))
         cmd = [hipcc] + FLAGS + ["-c", os.path.join(CSRC, src), "-o", obj]
         cwd = None
-        if src == "sinkhorn.hip":
-            # sinkhorn_resident128 / sinkhorn_resident2k keep most of their data in registers they address by number, outside the
-            # window their amdgpu_num_vgpr attribute leaves to the compiler.  The device assembly hipcc ASSEMBLES into this very
-            # object is kept (-save-temps: one compile, its own intermediate .s - not a second -S compile that could diverge) and
-            # checked below (check_register_window)
-            cwd = os.path.join(objdir, "sinkhorn_temps")
+        if src == REGISTER_WINDOW[0]:
+            cwd = os.path.join(objdir, stem + "_temps")
             os.makedirs(cwd, exist_ok=True)
             cmd.insert(1, "-save-temps=obj")
-            cmd[-1] = os.path.join(cwd, "sinkhorn.o")
+            cmd[-1] = os.path.join(cwd, stem + ".o")
         procs.append((src, obj, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, cwd=cwd)))
     objs = []
     for src, obj, p in procs:
@@ -102,12 +103,12 @@ def _build(hipcc, objdir, lib, verbose):
             print(out)
         objs.append(obj)
     import shutil
-    temps = os.path.join(objdir, "sinkhorn_temps")
-    shutil.copyfile(os.path.join(temps, "sinkhorn.o"), os.path.join(objdir, "sinkhorn.o"))  # the object that is linked
-    asm_file = os.path.join(objdir, "sinkhorn.s")
-    shutil.copyfile(os.path.join(temps, "sinkhorn-hip-amdgcn-amd-amdhsa-gfx950.s"), asm_file)  # the assembly it was made from
-    check_register_window(asm_file, "sinkhorn_resident128", 56)
-    check_register_window(asm_file, "sinkhorn_resident2k", 56)
+    temps = os.path.join(objdir, stem + "_temps")
+    shutil.copyfile(os.path.join(temps, stem + ".o"), os.path.join(objdir, stem + ".o"))  # the object that is linked
+    asm_file = os.path.join(objdir, stem + ".s")
+    shutil.copyfile(os.path.join(temps, stem + "-hip-amdgcn-amd-amdhsa-gfx950.s"), asm_file)  # the assembly it was made from
+    for kernel in REGISTER_WINDOW[1]:
+        check_register_window(asm_file, kernel, REGISTER_WINDOW[2])
     # the dynamic symbol table is the C ABI of include/e2emv.h and nothing else (hipcc gives kernel host stubs default
     # visibility whatever -fvisibility says: the version script takes them and every C++ internal out)
     vs = os.path.join(objdir, "e2emv.map")

@@ -42,16 +42,25 @@ def test_no_measurement_binaries_next_to_the_product():
     assert [f for f in os.listdir(pkg) if f.endswith(".so")] == ["libe2emv.so"]
 
 
+def _register_window_asm():
+    """The device assembly the build kept for the file of build.REGISTER_WINDOW (re-made from that one file when stale)."""
+    from e2e_multi_view_matching_amd import build
+    src = os.path.join(build.CSRC, build.REGISTER_WINDOW[0])
+    asm = os.path.join(ROOT, "e2e_multi_view_matching_amd", "build", build.REGISTER_WINDOW[0].replace(".hip", ".s"))
+    if not os.path.exists(asm) or os.path.getmtime(asm) < os.path.getmtime(src):
+        subprocess.run([os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")] + build.FLAGS + ["--cuda-device-only", "-S", src, "-o", asm],
+                       check=True, capture_output=True)
+    return asm
+
+
 def test_sinkhorn128_keeps_the_compiler_inside_its_register_window(lib_built):
     """sinkhorn_resident128 holds 24 of a wave's 32 rows in registers it addresses by number (v64 .. v255, a64 .. a255; v56 .. v63
     are its temporaries); amdgpu_num_vgpr(56) confines hipcc to v0 .. v55 / a0 .. a55.  The device assembly the build wrote is the
     proof: no compiler-generated instruction of either instance touches a register outside that window, and the wave is allocated
     all 512 registers.  (build.py runs the same check on every build.)"""
     from e2e_multi_view_matching_amd import build
-    asm = os.path.join(ROOT, "e2e_multi_view_matching_amd", "build", "sinkhorn.s")
-    if not os.path.exists(asm) or os.path.getmtime(asm) < os.path.getmtime(os.path.join(build.CSRC, "sinkhorn.hip")):
-        subprocess.run([os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")] + build.FLAGS + ["--cuda-device-only", "-S", os.path.join(build.CSRC, "sinkhorn.hip"), "-o", asm],
-                       check=True, capture_output=True)
+    asm = _register_window_asm()
+    assert build.REGISTER_WINDOW[1:] == (("sinkhorn_resident128", "sinkhorn_resident2k"), 56)
     assert build.check_register_window(asm, "sinkhorn_resident128", 56) == 2  # <true> (full tiles) and <false> (ragged)
     txt = open(asm).read()
     body = txt[txt.index("sinkhorn_resident128ILb1E"):]
@@ -60,6 +69,16 @@ def test_sinkhorn128_keeps_the_compiler_inside_its_register_window(lib_built):
     assert len(mine) == 384 + 2 * (12 * 8 + 12 * 16)  # the statements that DO address them: 384 writes; per pass 8 packed operations per vector row, 16 reads per accumulation row
     with pytest.raises(RuntimeError, match="outside its window"):
         build.check_register_window(asm, "sinkhorn_resident128", 40)
+
+
+def test_sinkhorn2k_keeps_the_compiler_inside_its_register_window(lib_built):
+    """The same proof for sinkhorn_resident2k (12 of a wave's 16 rows of 2048 columns in v64 .. v255 / a64 .. a255): both instances
+    stay inside the window of 56 with all 512 registers allocated, and the check does fail for a window the kernel does not keep."""
+    from e2e_multi_view_matching_amd import build
+    asm = _register_window_asm()
+    assert build.check_register_window(asm, "sinkhorn_resident2k", 56) == 2  # <true> (full tiles) and <false> (ragged)
+    with pytest.raises(RuntimeError, match="outside its window"):
+        build.check_register_window(asm, "sinkhorn_resident2k", 40)
 
 
 def test_struct_layouts_match_the_header():
