@@ -93,6 +93,14 @@ SIGNATURES = {
     "e2emv_mv_init_files": (c_int, [c_char_p, c_char_p]),
     "e2emv_mv_bundle_adjust": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "e2emv_mv_bundle_adjust_batch": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                             c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "e2emv_mv_collect": (c_int, [c_void_p, c_int, c_int, c_int, _PP, _PP, c_void_p, _PP, _PP, c_int, c_float, c_void_p, c_void_p, c_void_p,
+                                 c_void_p, c_void_p]),
+    "e2emv_mv_tuple_ba": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, _PP, c_int, c_int, c_void_p, c_int,
+                                  c_void_p, c_void_p, c_void_p]),
+    "e2emv_mv_tuple_problem": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, _PP, c_int, c_int, c_void_p,
+                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "e2emv_mv_bundle_adjust_files": (c_int, [c_void_p, c_char_p, c_char_p, c_void_p]),
     "e2emv_mv_triangulate": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "e2emv_essential_ransac": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_double, c_int,

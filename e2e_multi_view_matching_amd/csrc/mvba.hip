@@ -20,7 +20,9 @@
 // Quirk kept (ba_problem.cpp:129-137): observations of the fixed camera are predicted with the identity pose and that
 // camera's parameters are written back untouched.
 #include <algorithm>
+#include <climits>
 #include <cmath>
+#include <cstdint>
 #include <cstring>
 #include <fstream>
 #include <iomanip>
@@ -139,7 +141,11 @@ __device__ __forceinline__ void mv_transform(const double* cam, bool identity, c
         for (int j = 0; j < 3; ++j) D[3 * i + j] = -(Rl[3 * i] * T[j] + Rl[3 * i + 1] * T[3 + j] + Rl[3 * i + 2] * T[6 + j]);
 }
 
-__global__ __launch_bounds__(kMvThreads) void mvba_kernel(MvbaArgs a) {
+// One workgroup per problem: blockIdx.x selects the problem's record (sizes, intrinsics, fixed camera and the addresses of
+// ITS slices of the shared index / data / scratch arrays and of its summary slot).  Nothing below knows of the other
+// workgroups: several problems may share a CU (24 KB of LDS, 8 waves each), none shares a byte of global memory.
+__global__ __launch_bounds__(kMvThreads) void mvba_kernel(const MvbaArgs* __restrict__ recs) {
+    const MvbaArgs& a = recs[blockIdx.x];
     __shared__ double s_cams[kMvN], s_cand[kMvN], s_scale[kMvN], s_lam[kMvN], s_gc[kMvN], s_dc[kMvN], s_rhs[kMvN];
     __shared__ double s_U[kMvMaxCams * 36];
     __shared__ double s_S[kMvN * kMvN];
@@ -501,17 +507,15 @@ __global__ __launch_bounds__(kMvThreads) void mvba_kernel(MvbaArgs a) {
     }
 }
 
-// one thread per point: homogeneous DLT of two views (cv2.triangulatePoints at bundle_adjust_io.py:226-227)
-__global__ void mv_triangulate_kernel(int n, const double* P0, const double* P1, const double* x0, const double* x1, double* xyz) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
+// homogeneous DLT of two views (cv2.triangulatePoints at bundle_adjust_io.py:226-227): P0, P1 [3,4] row-major
+__device__ __forceinline__ void mv_dlt(const double* P0, const double* P1, double x0x, double x0y, double x1x, double x1y, double* xyz) {
     double A[16];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-        A[k] = x0[2 * i] * P0[8 + k] - P0[k];
-        A[4 + k] = x0[2 * i + 1] * P0[8 + k] - P0[4 + k];
-        A[8 + k] = x1[2 * i] * P1[8 + k] - P1[k];
-        A[12 + k] = x1[2 * i + 1] * P1[8 + k] - P1[4 + k];
+        A[k] = x0x * P0[8 + k] - P0[k];
+        A[4 + k] = x0y * P0[8 + k] - P0[4 + k];
+        A[8 + k] = x1x * P1[8 + k] - P1[k];
+        A[12 + k] = x1y * P1[8 + k] - P1[4 + k];
     }
     // smallest eigenvector of A^T A by cyclic Jacobi (fp64)
     double M[16], V[16];
@@ -555,14 +559,299 @@ __global__ void mv_triangulate_kernel(int n, const double* P0, const double* P1,
     for (int k = 1; k < 4; ++k)
         if (M[5 * k] < M[5 * m]) m = k;
     const double w = V[12 + m];
-    xyz[3 * i] = V[m] / w;
-    xyz[3 * i + 1] = V[4 + m] / w;
-    xyz[3 * i + 2] = V[8 + m] / w;
+    xyz[0] = V[m] / w;
+    xyz[1] = V[4 + m] / w;
+    xyz[2] = V[8 + m] / w;
+}
+
+// one thread per point
+__global__ void mv_triangulate_kernel(int n, const double* P0, const double* P1, const double* x0, const double* x1, double* xyz) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    mv_dlt(P0, P1, x0[2 * i], x0[2 * i + 1], x1[2 * i], x1[2 * i + 1], xyz + 3 * i);
+}
+
+
+// ---- the in-memory path for a whole batch of tuples (multi_view.solve_tuple_poses_batch) ---------------------------------------
+constexpr int kMvMaxPairs = kMvMaxCams * (kMvMaxCams - 1) / 2;
+constexpr int kMvRowThreads = 256;
+
+struct MvCollectArgs {
+    int B, P, N, channels;  // problems = B * P, problem (b, q) at index b * P + q; N = keypoints of the first image = row stride
+    float thresh;
+    int n1[kMvMaxPairs];               // keypoints of the second image
+    const float* k0[kMvMaxPairs];      // [B,N,2]
+    const float* k1[kMvMaxPairs];      // [B,n1,2]
+    const int64_t* match[kMvMaxPairs]; // [B,N] or NULL (no matches for this pair)
+    const float* conf[kMvMaxPairs];    // [B,N,channels]
+    float *o0, *o1, *oc;               // [B*P,N,2] x2, [B*P,N]
+    int* count;                        // [B*P]
+};
+
+// Ordered compaction, one workgroup per problem: keypoint n of the first image is kept when it has a match and every confidence
+// channel is above the threshold; the kept rows keep their order (ballot prefix inside a wave, wave totals through LDS, a
+// running base across the chunks of 256) because every later sum runs over them in that order.  Rows behind the count read 0.
+__global__ __launch_bounds__(kMvRowThreads) void mv_collect_kernel(MvCollectArgs a) {
+    __shared__ int s_wave[kMvRowThreads / 64];
+    const int pp = blockIdx.x, b = pp / a.P, q = pp - b * a.P, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int N = a.N, n1 = a.n1[q];
+    const int64_t* match = a.match[q] ? a.match[q] + size_t(b) * N : nullptr;
+    const float* conf = a.conf[q] + size_t(b) * N * a.channels;
+    const float* k0 = a.k0[q] + size_t(b) * N * 2;
+    const float* k1 = a.k1[q] + size_t(b) * n1 * 2;
+    float* o0 = a.o0 + size_t(pp) * N * 2;
+    float* o1 = a.o1 + size_t(pp) * N * 2;
+    float* oc = a.oc + size_t(pp) * N;
+    int base = 0;
+    if (match) {
+        for (int c0 = 0; c0 < N; c0 += kMvRowThreads) {
+            const int n = c0 + tid;
+            int64_t m = -1;
+            bool keep = false;
+            if (n < N) {
+                m = match[n];
+                keep = m >= 0 && m < n1;
+                for (int c = 0; c < a.channels; ++c) keep = keep && conf[size_t(n) * a.channels + c] > a.thresh;
+            }
+            const unsigned long long mask = __ballot(keep);
+            if (lane == 0) s_wave[wave] = __popcll(mask);
+            __syncthreads();
+            int off = base + __popcll(mask & ((1ull << lane) - 1ull)), total = 0;
+            for (int w = 0; w < kMvRowThreads / 64; ++w) {
+                if (w < wave) off += s_wave[w];
+                total += s_wave[w];
+            }
+            if (keep) {
+                o0[2 * off] = k0[2 * n]; o0[2 * off + 1] = k0[2 * n + 1];
+                o1[2 * off] = k1[2 * m]; o1[2 * off + 1] = k1[2 * m + 1];
+                oc[off] = conf[size_t(n) * a.channels];
+            }
+            base += total;
+            __syncthreads();
+        }
+    }
+    for (int n = base + tid; n < N; n += kMvRowThreads) {
+        o0[2 * n] = 0.f; o0[2 * n + 1] = 0.f; o1[2 * n] = 0.f; o1[2 * n + 1] = 0.f; oc[n] = 0.f;
+    }
+    if (tid == 0) a.count[pp] = base;
+}
+
+// what the host knows of pair block q of tuple b once the match counts are on the host: with one point per match and two
+// observations per point, every index list of the bundle adjustment has a closed form in the prefix sums of the counts
+struct MvPairRec {
+    int i, j, count;
+    int pt_base;       // first point of the block; its observations are 2 * pt_base + [0, count) (image i) and + count + [0, count) (image j)
+    int list_i, list_j;  // where the block's observations start in the observation lists of cameras i and j
+};
+
+struct MvBuildArgs {
+    int P, T, N, kdim, intr_batch;
+    const float* k0; const float* k1; const float* conf;  // collected: [B*P,N,2] x2, [B*P,N]
+    const float* intr[kMvMaxCams];                         // [intr_batch,kdim,kdim] per image
+    const double* proj;                                    // [B,T,3,4] world -> camera
+    const MvPairRec* pairs;                                // [B*P]
+    const MvbaArgs* recs;                                  // [B] the problems being built
+};
+
+// Bundle-adjustment problem of every tuple from the collected matches (write_bundle_adjust_problem without the text): thread =
+// match.  blockIdx.y = pair block, blockIdx.x = chunk of 256 matches.
+__global__ __launch_bounds__(kMvRowThreads) void mv_build_kernel(MvBuildArgs g) {
+    __shared__ double s_red[kMvRowThreads / 64];
+    const int pp = blockIdx.y, b = pp / g.P, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const MvPairRec rec = g.pairs[pp];
+    const MvbaArgs& a = g.recs[b];
+    // confidences of the tuple summed in fp64, always in this order (every workgroup of the tuple repeats it and gets the same
+    // bits): thread-strided inside a pair block, blocks in pair order, then lanes, then waves
+    double sum = 0.0;
+    for (int q = 0; q < g.P; ++q) {
+        const int cnt = g.pairs[b * g.P + q].count;
+        const float* cf = g.conf + size_t(b * g.P + q) * g.N;
+        for (int m = tid; m < cnt; m += kMvRowThreads) sum += double(cf[m]);
+    }
+    sum = mv_wsum(sum);
+    if (lane == 0) s_red[wave] = sum;
+    __syncthreads();
+    sum = s_red[0];
+    for (int w = 1; w < kMvRowThreads / 64; ++w) sum += s_red[w];
+    const double half_total = 0.5 * (2.0 * sum + 1e-3);  // every confidence is seen by two observations (normalize_confidences)
+    if (blockIdx.x == 0 && blockIdx.y == b * g.P && tid == 0) const_cast<int*>(a.pt_start)[a.P] = 2 * a.P;
+    const int m = blockIdx.x * kMvRowThreads + tid;
+    if (m >= rec.count) return;
+    const size_t row = size_t(pp) * g.N + m;
+    const int pt = rec.pt_base + m, oi = 2 * rec.pt_base + m, oj = oi + rec.count;
+    double x[4];
+#pragma unroll
+    for (int v = 0; v < 2; ++v) {
+        const int img = v ? rec.j : rec.i;
+        const float* K = g.intr[img] + (g.intr_batch == 1 ? 0 : size_t(b) * g.kdim * g.kdim);
+        const float* kp = (v ? g.k1 : g.k0) + 2 * row;
+        // pixel -> normalised camera coordinates in fp32 like the host path: one rounded subtraction, one rounded division
+        const float xn = (kp[0] - K[2]) / K[0], yn = (kp[1] - K[g.kdim + 2]) / K[g.kdim + 1];
+        x[2 * v] = double(xn); x[2 * v + 1] = double(yn);
+    }
+    const double w = double(g.conf[row]) / half_total;
+    int* cam_idx = const_cast<int*>(a.cam_idx); int* pt_idx = const_cast<int*>(a.pt_idx);
+    double* obs = const_cast<double*>(a.obs); double* wts = const_cast<double*>(a.wts);
+    cam_idx[oi] = rec.i; cam_idx[oj] = rec.j;
+    pt_idx[oi] = pt; pt_idx[oj] = pt;
+    obs[2 * oi] = x[0]; obs[2 * oi + 1] = x[1]; obs[2 * oj] = x[2]; obs[2 * oj + 1] = x[3];
+    wts[2 * oi] = w; wts[2 * oi + 1] = w; wts[2 * oj] = w; wts[2 * oj + 1] = w;
+    const_cast<int*>(a.pt_start)[pt] = 2 * pt;
+    const_cast<int*>(a.pt_obs)[2 * pt] = oi;
+    const_cast<int*>(a.pt_obs)[2 * pt + 1] = oj;
+    const_cast<int*>(a.cam_obs)[rec.list_i + m] = oi;
+    const_cast<int*>(a.cam_obs)[rec.list_j + m] = oj;
+    mv_dlt(g.proj + size_t(b * g.T + rec.i) * 12, g.proj + size_t(b * g.T + rec.j) * 12, x[0], x[1], x[2], x[3], a.pts + 3 * size_t(pt));
+}
+
+// Device memory of a batch of problems inside the context workspace.  First what the host uploads in one piece (records, start
+// cameras, camera list starts, `extra` bytes of the caller), then the per-observation / per-point arrays; problem k owns the
+// slice behind its camera / point / observation offsets in each of them.
+struct MvLayout {
+    MvbaArgs* recs; double* cams; int* cam_start; char* extra;
+    size_t upload_bytes;
+    double *pts, *gp, *dp, *scale_p, *cand, *Vinv, *obs, *wts, *r, *Jc, *Jp, *Y, *summary;
+    int *cam_idx, *pt_idx, *pt_obs, *cam_obs, *pt_start;
+    size_t bytes;
+};
+
+static MvLayout mv_layout(char* base, size_t n, size_t totC, size_t totP, size_t totO, size_t extra) {
+    MvLayout L{};
+    size_t off = 0;
+    auto take = [&](size_t bytes) { char* q = base + off; off += (bytes + 255) & ~size_t(255); return q; };
+    L.recs = reinterpret_cast<MvbaArgs*>(take(n * sizeof(MvbaArgs)));
+    L.cams = reinterpret_cast<double*>(take(totC * 6 * 8));
+    L.cam_start = reinterpret_cast<int*>(take((totC + n) * 4));
+    L.extra = take(extra);
+    L.upload_bytes = off;
+    auto dbl = [&](size_t k) { return reinterpret_cast<double*>(take(k * 8)); };
+    auto i32 = [&](size_t k) { return reinterpret_cast<int*>(take(k * 4)); };
+    L.pts = dbl(3 * totP); L.gp = dbl(3 * totP); L.dp = dbl(3 * totP); L.scale_p = dbl(3 * totP); L.cand = dbl(3 * totP); L.Vinv = dbl(6 * totP);
+    L.obs = dbl(2 * totO); L.wts = dbl(2 * totO); L.r = dbl(2 * totO); L.Jc = dbl(12 * totO); L.Jp = dbl(6 * totO); L.Y = dbl(18 * totO);
+    L.summary = dbl(4 * n);
+    L.cam_idx = i32(totO); L.pt_idx = i32(totO); L.pt_obs = i32(totO); L.cam_obs = i32(totO); L.pt_start = i32(totP + n);
+    L.bytes = off;
+    return L;
+}
+
+// record of problem k: its sizes and its slices (c0 / p0 / o0 = cameras / points / observations of the problems before it)
+static MvbaArgs mv_record(const MvLayout& L, size_t k, size_t c0, size_t p0, size_t o0, int C, int fixed, int P, int O, int max_iters,
+                          const double* intr) {
+    MvbaArgs a{};
+    a.C = C; a.fixed = fixed; a.P = P; a.O = O; a.max_iters = max_iters;
+    a.fx = intr[0]; a.fy = intr[1]; a.cx = intr[2]; a.cy = intr[3];
+    a.cam_idx = L.cam_idx + o0; a.pt_idx = L.pt_idx + o0; a.pt_obs = L.pt_obs + o0; a.cam_obs = L.cam_obs + o0;
+    a.pt_start = L.pt_start + p0 + k; a.cam_start = L.cam_start + c0 + k;
+    a.obs = L.obs + 2 * o0; a.wts = L.wts + 2 * o0;
+    a.cams = L.cams + 6 * c0; a.pts = L.pts + 3 * p0;
+    a.r = L.r + 2 * o0; a.Jc = L.Jc + 12 * o0; a.Jp = L.Jp + 6 * o0; a.Y = L.Y + 18 * o0;
+    a.Vinv = L.Vinv + 6 * p0; a.gp = L.gp + 3 * p0; a.dp = L.dp + 3 * p0; a.scale_p = L.scale_p + 3 * p0; a.cand = L.cand + 3 * p0;
+    a.summary = L.summary + 4 * k;
+    return a;
+}
+
+static int mv_launch_ba(e2emv_ctx* ctx, const MvLayout& L, int n, hipStream_t s) {
+    prof_begin(ctx, PS_W8PT, s);
+    hipLaunchKernelGGL(mvba_kernel, dim3(n), dim3(kMvThreads), 0, s, L.recs);
+    E2EMV_CHECK_LAUNCH(ctx, "mvba_kernel");
+    prof_end(ctx, s);
+    return E2EMV_OK;
+}
+
+static void mv_extr_to_cam(const double* E /* 4x4 row-major */, double* cam) {
+    const double R[9] = {E[0], E[4], E[8], E[1], E[5], E[9], E[2], E[6], E[10]};  // column-major
+    mv::R_to_aa(R, cam);
+    cam[3] = E[3]; cam[4] = E[7]; cam[5] = E[11];
+}
+static void mv_cam_to_extr(const double* cam, double* E) {
+    double R[9];
+    mv::aa_to_R(cam, R);
+    for (int r = 0; r < 3; ++r) {
+        for (int c = 0; c < 3; ++c) E[4 * r + c] = R[3 * c + r];
+        E[4 * r + 3] = cam[3 + r];
+    }
+    E[12] = 0; E[13] = 0; E[14] = 0; E[15] = 1;
 }
 
 }  // namespace e2emv
 
 using namespace e2emv;
+
+extern "C" int e2emv_mv_bundle_adjust_batch(e2emv_ctx* ctx, int n_problems, const int32_t* n_cams, const int32_t* fixed_cam,
+                                            const double* intr, const int64_t* pt_off, const int64_t* obs_off, const int32_t* cam_idx,
+                                            const int32_t* pt_idx, const double* obs_xy, const double* obs_w, double* cams, double* pts,
+                                            int max_iterations, double* summary, void* stream) {
+    if (!ctx) return E2EMV_EINVAL;
+    E2EMV_ENTER(ctx, stream);
+    if (n_problems < 1 || !n_cams || !fixed_cam || !intr || !pt_off || !obs_off || !cams)
+        return set_err(ctx, E2EMV_EINVAL, "mv_bundle_adjust_batch: bad argument (n_problems >= 1, no NULL size / offset array)");
+    const size_t n = size_t(n_problems);
+    if (pt_off[0] != 0 || obs_off[0] != 0) return set_err(ctx, E2EMV_ESHAPE, "mv_bundle_adjust_batch: offsets must start at 0");
+    size_t totC = 0;
+    for (size_t k = 0; k < n; ++k) {
+        if (n_cams[k] < 1 || n_cams[k] > kMvMaxCams)
+            return set_err(ctx, E2EMV_EINVAL, "mv_bundle_adjust_batch: problem %zu has %d cameras (1 <= n_cams <= %d)", k, n_cams[k], kMvMaxCams);
+        if (pt_off[k + 1] < pt_off[k] || obs_off[k + 1] < obs_off[k] || pt_off[k + 1] - pt_off[k] > INT32_MAX / 8 || obs_off[k + 1] - obs_off[k] > INT32_MAX / 32)
+            return set_err(ctx, E2EMV_ESHAPE, "mv_bundle_adjust_batch: offsets of problem %zu are not monotone (or the problem is too large)", k);
+        totC += size_t(n_cams[k]);
+    }
+    const size_t totP = size_t(pt_off[n]), totO = size_t(obs_off[n]);
+    if ((totP && !pts) || (totO && (!cam_idx || !pt_idx || !obs_xy || !obs_w)))
+        return set_err(ctx, E2EMV_EINVAL, "mv_bundle_adjust_batch: NULL array for %zu points / %zu observations", totP, totO);
+    for (size_t k = 0; k < n; ++k) {
+        const int C = n_cams[k], P = int(pt_off[k + 1] - pt_off[k]);
+        for (int64_t o = obs_off[k]; o < obs_off[k + 1]; ++o)
+            if (cam_idx[o] < 0 || cam_idx[o] >= C || pt_idx[o] < 0 || pt_idx[o] >= P)
+                return set_err(ctx, E2EMV_EINVAL, "mv_bundle_adjust_batch: observation %lld of problem %zu refers to camera %d / point %d",
+                               (long long)(o - obs_off[k]), k, cam_idx[o], pt_idx[o]);
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const int rc = ws_reserve(ctx, mv_layout(nullptr, n, totC, totP, totO, 0).bytes);
+    if (rc) return rc;
+    const MvLayout L = mv_layout(ctx->d_ws, n, totC, totP, totO, 0);
+    // observation lists per point and per camera (stable order -> deterministic sums), indices local to their problem
+    std::vector<MvbaArgs> recs(n);
+    std::vector<int> pstart(totP + n, 0), pobs(totO), cstart(totC + n, 0), cobs(totO);
+    size_t c0 = 0;
+    for (size_t k = 0; k < n; ++k) {
+        const size_t p0 = size_t(pt_off[k]), o0 = size_t(obs_off[k]);
+        const int C = n_cams[k], P = int(pt_off[k + 1] - pt_off[k]), O = int(obs_off[k + 1] - obs_off[k]);
+        int* ps = pstart.data() + p0 + k;
+        int* cs = cstart.data() + c0 + k;
+        const int32_t* ci = cam_idx + o0;
+        const int32_t* pi = pt_idx + o0;
+        for (int o = 0; o < O; ++o) { ++ps[pi[o] + 1]; ++cs[ci[o] + 1]; }
+        for (int p = 0; p < P; ++p) ps[p + 1] += ps[p];
+        for (int c = 0; c < C; ++c) cs[c + 1] += cs[c];
+        std::vector<int> pf(ps, ps + P), cf(cs, cs + C);
+        for (int o = 0; o < O; ++o) { pobs[o0 + pf[pi[o]]++] = o; cobs[o0 + cf[ci[o]]++] = o; }
+        recs[k] = mv_record(L, k, c0, p0, o0, C, fixed_cam[k], P, O, max_iterations, intr + 4 * k);
+        c0 += size_t(C);
+    }
+    E2EMV_HIP(ctx, hipMemcpyAsync(L.recs, recs.data(), sizeof(MvbaArgs) * n, hipMemcpyHostToDevice, s));
+    E2EMV_HIP(ctx, hipMemcpyAsync(L.cams, cams, sizeof(double) * 6 * totC, hipMemcpyHostToDevice, s));
+    E2EMV_HIP(ctx, hipMemcpyAsync(L.cam_start, cstart.data(), sizeof(int) * (totC + n), hipMemcpyHostToDevice, s));
+    E2EMV_HIP(ctx, hipMemcpyAsync(L.pt_start, pstart.data(), sizeof(int) * (totP + n), hipMemcpyHostToDevice, s));
+    if (totP) E2EMV_HIP(ctx, hipMemcpyAsync(L.pts, pts, sizeof(double) * 3 * totP, hipMemcpyHostToDevice, s));
+    if (totO) {
+        E2EMV_HIP(ctx, hipMemcpyAsync(L.obs, obs_xy, sizeof(double) * 2 * totO, hipMemcpyHostToDevice, s));
+        E2EMV_HIP(ctx, hipMemcpyAsync(L.wts, obs_w, sizeof(double) * 2 * totO, hipMemcpyHostToDevice, s));
+        E2EMV_HIP(ctx, hipMemcpyAsync(L.cam_idx, cam_idx, sizeof(int) * totO, hipMemcpyHostToDevice, s));
+        E2EMV_HIP(ctx, hipMemcpyAsync(L.pt_idx, pt_idx, sizeof(int) * totO, hipMemcpyHostToDevice, s));
+        E2EMV_HIP(ctx, hipMemcpyAsync(L.pt_obs, pobs.data(), sizeof(int) * totO, hipMemcpyHostToDevice, s));
+        E2EMV_HIP(ctx, hipMemcpyAsync(L.cam_obs, cobs.data(), sizeof(int) * totO, hipMemcpyHostToDevice, s));
+    }
+    E2EMV_HIP(ctx, hipStreamSynchronize(s));  // the host staging vectors die at return
+    const int lrc = mv_launch_ba(ctx, L, n_problems, s);
+    if (lrc) return lrc;
+    E2EMV_HIP(ctx, hipMemcpyAsync(cams, L.cams, sizeof(double) * 6 * totC, hipMemcpyDeviceToHost, s));
+    if (totP) E2EMV_HIP(ctx, hipMemcpyAsync(pts, L.pts, sizeof(double) * 3 * totP, hipMemcpyDeviceToHost, s));
+    std::vector<double> sm(4 * n);
+    E2EMV_HIP(ctx, hipMemcpyAsync(sm.data(), L.summary, sizeof(double) * 4 * n, hipMemcpyDeviceToHost, s));
+    E2EMV_HIP(ctx, hipStreamSynchronize(s));
+    if (summary) std::memcpy(summary, sm.data(), sizeof(double) * 4 * n);
+    return E2EMV_OK;
+}
 
 extern "C" int e2emv_mv_bundle_adjust(e2emv_ctx* ctx, int n_cams, int fixed_cam, int n_pts, int n_obs, const double* intr,
                                       const int32_t* cam_idx, const int32_t* pt_idx, const double* obs_xy, const double* obs_w,
@@ -575,61 +864,153 @@ extern "C" int e2emv_mv_bundle_adjust(e2emv_ctx* ctx, int n_cams, int fixed_cam,
     for (int o = 0; o < n_obs; ++o)
         if (cam_idx[o] < 0 || cam_idx[o] >= n_cams || pt_idx[o] < 0 || pt_idx[o] >= n_pts)
             return set_err(ctx, E2EMV_EINVAL, "mv_bundle_adjust: observation %d refers to camera %d / point %d", o, cam_idx[o], pt_idx[o]);
-    hipStream_t s = (hipStream_t)stream;
-    const int C = n_cams, P = n_pts, O = n_obs;
-    // observation lists per point and per camera (stable order -> deterministic sums)
-    std::vector<int> pstart(P + 1, 0), pobs(O), cstart(C + 1, 0), cobs(O);
-    for (int o = 0; o < O; ++o) { ++pstart[pt_idx[o] + 1]; ++cstart[cam_idx[o] + 1]; }
-    for (int p = 0; p < P; ++p) pstart[p + 1] += pstart[p];
-    for (int c = 0; c < C; ++c) cstart[c + 1] += cstart[c];
-    {
-        std::vector<int> pf(pstart.begin(), pstart.end() - 1), cf(cstart.begin(), cstart.end() - 1);
-        for (int o = 0; o < O; ++o) { pobs[pf[pt_idx[o]]++] = o; cobs[cf[cam_idx[o]]++] = o; }
+    // the batch of one
+    const int32_t nc = n_cams, fc = fixed_cam;
+    const int64_t po[2] = {0, n_pts}, oo[2] = {0, n_obs};
+    return e2emv_mv_bundle_adjust_batch(ctx, 1, &nc, &fc, intr, po, oo, cam_idx, pt_idx, obs_xy, obs_w, cams, pts, max_iterations, summary, stream);
+}
+
+extern "C" int e2emv_mv_collect(e2emv_ctx* ctx, int B, int T, int N, const float* const* d_kpts0, const float* const* d_kpts1,
+                                const int32_t* n_kpts1, const int64_t* const* d_matches, const float* const* d_conf, int conf_channels,
+                                float conf_thresh, float* d_mkpts0, float* d_mkpts1, float* d_mconf, int32_t* d_count, void* stream) {
+    if (!ctx) return E2EMV_EINVAL;
+    E2EMV_ENTER(ctx, stream);
+    if (B < 1 || N < 1 || conf_channels < 1 || !d_kpts0 || !d_kpts1 || !n_kpts1 || !d_matches || !d_conf || !d_mkpts0 || !d_mkpts1 || !d_mconf || !d_count)
+        return set_err(ctx, E2EMV_EINVAL, "mv_collect: bad argument (B, N, conf_channels >= 1, no NULL array)");
+    if (T < 2 || T > kMvMaxCams) return set_err(ctx, E2EMV_EINVAL, "mv_collect: tuple of %d images (2 <= T <= %d)", T, kMvMaxCams);
+    MvCollectArgs a{};
+    a.B = B; a.P = T * (T - 1) / 2; a.N = N; a.channels = conf_channels; a.thresh = conf_thresh;
+    if (size_t(B) * a.P * N > size_t(INT32_MAX) / 2) return set_err(ctx, E2EMV_ESHAPE, "mv_collect: B * pairs * N = %zu is too large", size_t(B) * a.P * N);
+    for (int q = 0; q < a.P; ++q) {
+        if (d_matches[q] && (!d_kpts0[q] || !d_kpts1[q] || !d_conf[q] || n_kpts1[q] < 1))
+            return set_err(ctx, E2EMV_EINVAL, "mv_collect: pair %d has matches but no keypoints / confidences", q);
+        a.k0[q] = d_kpts0[q]; a.k1[q] = d_kpts1[q]; a.match[q] = d_matches[q]; a.conf[q] = d_conf[q]; a.n1[q] = n_kpts1[q];
     }
-    auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
-    const size_t nd = size_t(6) * C + size_t(3) * P * 5 + size_t(6) * P + size_t(O) * (2 + 2 + 2 + 12 + 6 + 18) + 8;
-    const size_t ni = size_t(O) * 4 + P + 1 + C + 1;
-    const size_t bytes = al(nd * 8) + al(ni * 4) + 4096;
-    int rc = ws_reserve(ctx, bytes);
+    a.o0 = d_mkpts0; a.o1 = d_mkpts1; a.oc = d_mconf; a.count = d_count;
+    hipLaunchKernelGGL(mv_collect_kernel, dim3(B * a.P), dim3(kMvRowThreads), 0, (hipStream_t)stream, a);
+    E2EMV_CHECK_LAUNCH(ctx, "mv_collect_kernel");
+    return E2EMV_OK;
+}
+
+// stage 4 (and the uploads in front of it) shared by e2emv_mv_tuple_ba and e2emv_mv_tuple_problem; leaves the problems of the B
+// tuples in the workspace, described by *L
+static int mv_tuple_build(e2emv_ctx* ctx, const char* who, int B, int T, int N, const int32_t* counts, const float* d_mkpts0,
+                          const float* d_mkpts1, const float* d_mconf, const float* const* d_intr, int kdim, int intr_batch,
+                          const double* extr, int max_iterations, MvLayout* L, size_t* totP_out, hipStream_t s) {
+    if (B < 1 || N < 1 || !counts || !d_mkpts0 || !d_mkpts1 || !d_mconf || !d_intr || !extr)
+        return set_err(ctx, E2EMV_EINVAL, "%s: bad argument (B, N >= 1, no NULL array)", who);
+    if (T < 2 || T > kMvMaxCams) return set_err(ctx, E2EMV_EINVAL, "%s: tuple of %d images (2 <= T <= %d)", who, T, kMvMaxCams);
+    if (kdim != 3 && kdim != 4) return set_err(ctx, E2EMV_ESHAPE, "%s: intrinsics must be 3x3 or 4x4", who);
+    if (intr_batch != 1 && intr_batch != B) return set_err(ctx, E2EMV_ESHAPE, "%s: intr_batch must be 1 or B", who);
+    const int P = T * (T - 1) / 2;
+    for (int t = 0; t < T; ++t)
+        if (!d_intr[t]) return set_err(ctx, E2EMV_EINVAL, "%s: NULL intrinsics of image %d", who, t);
+    size_t totP = 0;
+    for (int k = 0; k < B * P; ++k) {
+        if (counts[k] < 0 || counts[k] > N) return set_err(ctx, E2EMV_EINVAL, "%s: count %d of pair block %d is outside [0, N = %d]", who, counts[k], k, N);
+        totP += size_t(counts[k]);
+    }
+    if (size_t(B) * P * N > size_t(INT32_MAX) / 64) return set_err(ctx, E2EMV_ESHAPE, "%s: B * pairs * N = %zu is too large", who, size_t(B) * P * N);
+    const size_t n = size_t(B), totC = n * T, totO = 2 * totP;
+    const size_t proj_bytes = (totC * 12 * 8 + 255) & ~size_t(255), extra = proj_bytes + n * P * sizeof(MvPairRec);
+    const int rc = ws_reserve(ctx, mv_layout(nullptr, n, totC, totP, totO, extra).bytes);
     if (rc) return rc;
-    double* d = reinterpret_cast<double*>(ctx->d_ws);
-    MvbaArgs a{};
-    a.C = C; a.fixed = fixed_cam; a.P = P; a.O = O; a.max_iters = max_iterations;
-    a.fx = intr[0]; a.fy = intr[1]; a.cx = intr[2]; a.cy = intr[3];
-    double* cur = d;
-    auto take = [&](size_t n) { double* q = cur; cur += n; return q; };
-    a.cams = take(6 * C); a.pts = take(3 * size_t(P)); a.gp = take(3 * size_t(P)); a.dp = take(3 * size_t(P));
-    a.scale_p = take(3 * size_t(P)); a.cand = take(3 * size_t(P)); a.Vinv = take(6 * size_t(P));
-    double* d_obs = take(2 * size_t(O)); double* d_w = take(2 * size_t(O));
-    a.r = take(2 * size_t(O)); a.Jc = take(12 * size_t(O)); a.Jp = take(6 * size_t(O)); a.Y = take(18 * size_t(O));
-    a.summary = take(8);
-    int* di = reinterpret_cast<int*>(ctx->d_ws + al(nd * 8));
-    int* d_ci = di; int* d_pi = di + O; int* d_pobs = di + 2 * size_t(O); int* d_cobs = di + 3 * size_t(O);
-    int* d_ps = di + 4 * size_t(O); int* d_cs = d_ps + P + 1;
-    a.obs = d_obs; a.wts = d_w; a.cam_idx = d_ci; a.pt_idx = d_pi; a.pt_obs = d_pobs; a.cam_obs = d_cobs; a.pt_start = d_ps; a.cam_start = d_cs;
-    E2EMV_HIP(ctx, hipMemcpyAsync(a.cams, cams, sizeof(double) * 6 * C, hipMemcpyHostToDevice, s));
-    if (P) E2EMV_HIP(ctx, hipMemcpyAsync(a.pts, pts, sizeof(double) * 3 * P, hipMemcpyHostToDevice, s));
-    if (O) {
-        E2EMV_HIP(ctx, hipMemcpyAsync(d_obs, obs_xy, sizeof(double) * 2 * O, hipMemcpyHostToDevice, s));
-        E2EMV_HIP(ctx, hipMemcpyAsync(d_w, obs_w, sizeof(double) * 2 * O, hipMemcpyHostToDevice, s));
-        E2EMV_HIP(ctx, hipMemcpyAsync(d_ci, cam_idx, sizeof(int) * O, hipMemcpyHostToDevice, s));
-        E2EMV_HIP(ctx, hipMemcpyAsync(d_pi, pt_idx, sizeof(int) * O, hipMemcpyHostToDevice, s));
-        E2EMV_HIP(ctx, hipMemcpyAsync(d_pobs, pobs.data(), sizeof(int) * O, hipMemcpyHostToDevice, s));
-        E2EMV_HIP(ctx, hipMemcpyAsync(d_cobs, cobs.data(), sizeof(int) * O, hipMemcpyHostToDevice, s));
+    *L = mv_layout(ctx->d_ws, n, totC, totP, totO, extra);
+    // everything the host contributes in one staging block = one copy: records, start cameras, camera list starts, projection
+    // matrices, pair records
+    std::vector<char> stage(L->upload_bytes, 0);
+    auto at = [&](const void* dev) { return stage.data() + (reinterpret_cast<const char*>(dev) - ctx->d_ws); };
+    MvbaArgs* recs = reinterpret_cast<MvbaArgs*>(at(L->recs));
+    double* cams = reinterpret_cast<double*>(at(L->cams));
+    int* cstart = reinterpret_cast<int*>(at(L->cam_start));
+    double* proj = reinterpret_cast<double*>(at(L->extra));
+    MvPairRec* pairs = reinterpret_cast<MvPairRec*>(at(L->extra + proj_bytes));
+    const double unit_intr[4] = {1.0, 1.0, 0.0, 0.0};  // the intrinsics are folded into the observations
+    size_t p0 = 0;
+    for (int b = 0; b < B; ++b) {
+        const int32_t* cnt = counts + size_t(b) * P;
+        int* cs = cstart + size_t(b) * T + b;  // [T + 1]
+        int q = 0, pts_b = 0;
+        for (int j = 0; j < T; ++j)
+            for (int i = 0; i < j; ++i, ++q) { cs[i + 1] += cnt[q]; cs[j + 1] += cnt[q]; pts_b += cnt[q]; }
+        for (int c = 0; c < T; ++c) cs[c + 1] += cs[c];
+        int fill[kMvMaxCams];
+        for (int c = 0; c < T; ++c) fill[c] = cs[c];
+        q = 0;
+        int pt_base = 0;
+        for (int j = 0; j < T; ++j)
+            for (int i = 0; i < j; ++i, ++q) {
+                MvPairRec& r = pairs[size_t(b) * P + q];
+                r.i = i; r.j = j; r.count = cnt[q]; r.pt_base = pt_base; r.list_i = fill[i]; r.list_j = fill[j];
+                fill[i] += cnt[q]; fill[j] += cnt[q]; pt_base += cnt[q];
+            }
+        for (int t = 0; t < T; ++t) {
+            const double* E = extr + (size_t(b) * T + t) * 16;
+            std::memcpy(proj + (size_t(b) * T + t) * 12, E, 12 * sizeof(double));
+            mv_extr_to_cam(E, cams + (size_t(b) * T + t) * 6);
+        }
+        recs[b] = mv_record(*L, size_t(b), size_t(b) * T, p0, 2 * p0, T, 0, pts_b, 2 * pts_b, max_iterations, unit_intr);
+        p0 += size_t(pts_b);
     }
-    E2EMV_HIP(ctx, hipMemcpyAsync(d_ps, pstart.data(), sizeof(int) * (P + 1), hipMemcpyHostToDevice, s));
-    E2EMV_HIP(ctx, hipMemcpyAsync(d_cs, cstart.data(), sizeof(int) * (C + 1), hipMemcpyHostToDevice, s));
-    E2EMV_HIP(ctx, hipStreamSynchronize(s));  // the host staging vectors die at return
-    prof_begin(ctx, PS_W8PT, s);
-    hipLaunchKernelGGL(mvba_kernel, dim3(1), dim3(kMvThreads), 0, s, a);
-    E2EMV_CHECK_LAUNCH(ctx, "mvba_kernel");
-    prof_end(ctx, s);
-    double sm[4];
-    E2EMV_HIP(ctx, hipMemcpyAsync(cams, a.cams, sizeof(double) * 6 * C, hipMemcpyDeviceToHost, s));
-    if (P) E2EMV_HIP(ctx, hipMemcpyAsync(pts, a.pts, sizeof(double) * 3 * P, hipMemcpyDeviceToHost, s));
-    E2EMV_HIP(ctx, hipMemcpyAsync(sm, a.summary, sizeof(double) * 4, hipMemcpyDeviceToHost, s));
+    E2EMV_HIP(ctx, hipMemcpyAsync(ctx->d_ws, stage.data(), stage.size(), hipMemcpyHostToDevice, s));
+    E2EMV_HIP(ctx, hipStreamSynchronize(s));  // the staging block dies at return
+    MvBuildArgs g{};
+    g.P = P; g.T = T; g.N = N; g.kdim = kdim; g.intr_batch = intr_batch;
+    g.k0 = d_mkpts0; g.k1 = d_mkpts1; g.conf = d_mconf;
+    for (int t = 0; t < T; ++t) g.intr[t] = d_intr[t];
+    g.proj = reinterpret_cast<const double*>(L->extra);
+    g.pairs = reinterpret_cast<const MvPairRec*>(L->extra + proj_bytes);
+    g.recs = L->recs;
+    hipLaunchKernelGGL(mv_build_kernel, dim3((N + kMvRowThreads - 1) / kMvRowThreads, B * P), dim3(kMvRowThreads), 0, s, g);
+    E2EMV_CHECK_LAUNCH(ctx, "mv_build_kernel");
+    *totP_out = totP;
+    return E2EMV_OK;
+}
+
+extern "C" int e2emv_mv_tuple_ba(e2emv_ctx* ctx, int B, int T, int N, const int32_t* counts, const float* d_mkpts0, const float* d_mkpts1,
+                                 const float* d_mconf, const float* const* d_intr, int kdim, int intr_batch, const double* extr,
+                                 int max_iterations, double* out_extr, double* summary, void* stream) {
+    if (!ctx) return E2EMV_EINVAL;
+    E2EMV_ENTER(ctx, stream);
+    if (!out_extr) return set_err(ctx, E2EMV_EINVAL, "mv_tuple_ba: NULL output");
+    hipStream_t s = (hipStream_t)stream;
+    MvLayout L;
+    size_t totP = 0;
+    int rc = mv_tuple_build(ctx, "mv_tuple_ba", B, T, N, counts, d_mkpts0, d_mkpts1, d_mconf, d_intr, kdim, intr_batch, extr, max_iterations, &L, &totP, s);
+    if (rc) return rc;
+    rc = mv_launch_ba(ctx, L, B, s);
+    if (rc) return rc;
+    std::vector<double> cams(size_t(B) * T * 6), sm(size_t(B) * 4);
+    E2EMV_HIP(ctx, hipMemcpyAsync(cams.data(), L.cams, sizeof(double) * cams.size(), hipMemcpyDeviceToHost, s));
+    E2EMV_HIP(ctx, hipMemcpyAsync(sm.data(), L.summary, sizeof(double) * sm.size(), hipMemcpyDeviceToHost, s));
     E2EMV_HIP(ctx, hipStreamSynchronize(s));
-    if (summary) std::memcpy(summary, sm, sizeof(sm));
+    for (size_t v = 0; v < size_t(B) * T; ++v) mv_cam_to_extr(&cams[6 * v], out_extr + 16 * v);
+    if (summary) std::memcpy(summary, sm.data(), sizeof(double) * sm.size());
+    return E2EMV_OK;
+}
+
+extern "C" int e2emv_mv_tuple_problem(e2emv_ctx* ctx, int B, int T, int N, const int32_t* counts, const float* d_mkpts0,
+                                      const float* d_mkpts1, const float* d_mconf, const float* const* d_intr, int kdim, int intr_batch,
+                                      const double* extr, int32_t* cam_idx, int32_t* pt_idx, double* obs_xy, double* obs_w, double* cams,
+                                      double* pts, void* stream) {
+    if (!ctx) return E2EMV_EINVAL;
+    E2EMV_ENTER(ctx, stream);
+    if (!cams) return set_err(ctx, E2EMV_EINVAL, "mv_tuple_problem: NULL output");
+    hipStream_t s = (hipStream_t)stream;
+    MvLayout L;
+    size_t totP = 0;
+    const int rc = mv_tuple_build(ctx, "mv_tuple_problem", B, T, N, counts, d_mkpts0, d_mkpts1, d_mconf, d_intr, kdim, intr_batch, extr, 0, &L, &totP, s);
+    if (rc) return rc;
+    if (totP && (!cam_idx || !pt_idx || !obs_xy || !obs_w || !pts)) return set_err(ctx, E2EMV_EINVAL, "mv_tuple_problem: NULL output for %zu points", totP);
+    E2EMV_HIP(ctx, hipMemcpyAsync(cams, L.cams, sizeof(double) * 6 * B * T, hipMemcpyDeviceToHost, s));
+    if (totP) {
+        E2EMV_HIP(ctx, hipMemcpyAsync(cam_idx, L.cam_idx, sizeof(int) * 2 * totP, hipMemcpyDeviceToHost, s));
+        E2EMV_HIP(ctx, hipMemcpyAsync(pt_idx, L.pt_idx, sizeof(int) * 2 * totP, hipMemcpyDeviceToHost, s));
+        E2EMV_HIP(ctx, hipMemcpyAsync(obs_xy, L.obs, sizeof(double) * 4 * totP, hipMemcpyDeviceToHost, s));
+        E2EMV_HIP(ctx, hipMemcpyAsync(obs_w, L.wts, sizeof(double) * 4 * totP, hipMemcpyDeviceToHost, s));
+        E2EMV_HIP(ctx, hipMemcpyAsync(pts, L.pts, sizeof(double) * 3 * totP, hipMemcpyDeviceToHost, s));
+    }
+    E2EMV_HIP(ctx, hipStreamSynchronize(s));
     return E2EMV_OK;
 }
 

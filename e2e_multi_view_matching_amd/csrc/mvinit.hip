@@ -407,7 +407,11 @@ int run_init(int n_views, const double* init_R, int n_pairs, const int* pair_ids
     if (!estimate_positions(n_views, pairs, rot, pos)) status |= 4;
     // t = -R * position (ba_init.cpp:65), then the world frame is re-based onto camera 0 (R_v <- R_v R_0^T, positions
     // rotated by R_0, so t is unchanged): a pure gauge change that leaves every relative pose untouched and hands the
-    // bundle adjuster - which treats camera 0 as the identity (ba_problem.cpp:129-137) - a consistent start.
+    // bundle adjuster - which treats camera 0 as the identity (ba_problem.cpp:129-137) - a consistent start.  Only the views
+    // connected to camera 0 share its frame: another component (an image without matches) keeps its initial rotation, as
+    // `components` promises, instead of inheriting the inverse of a gauge drift it has no part in.
+    const std::vector<int> comp = components(n_views, pairs);
+    const double I3[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
     double R0[9], R0T[9];
     aa_to_R(&rot[0], R0);
     mat3_T(R0, R0T);
@@ -415,7 +419,7 @@ int run_init(int n_views, const double* init_R, int n_pairs, const int* pair_ids
         double R[9];
         aa_to_R(&rot[3 * v], R);
         for (int r = 0; r < 3; ++r) out_t[3 * v + r] = -(R[r] * pos[3 * v] + R[3 + r] * pos[3 * v + 1] + R[6 + r] * pos[3 * v + 2]);
-        mat3_mul(R, R0T, out_R + 9 * v);
+        mat3_mul(R, comp[v] == comp[0] ? R0T : I3, out_R + 9 * v);
     }
     return status;
 }

@@ -301,9 +301,27 @@ __global__ __launch_bounds__(256) void w8pt_fundamental(W8Params p) {
     const float* cf = p.conf + (int64_t)b * ldN;
     float* k0n = p.k0n + (int64_t)b * ldN * 2;
     float* k1n = p.k1n + (int64_t)b * ldN * 2;
-    for (int i = N + tid; i < ldN; i += 256) {  // rows beyond this sample's count: defined, weightless
+    const bool too_few = p.n_per && N < 8;  // a ragged sample without a solvable system: every row is padding
+    for (int i = (too_few ? 0 : N) + tid; i < ldN; i += 256) {  // rows beyond this sample's count: defined, weightless
         k0n[2 * i] = 0.f; k0n[2 * i + 1] = 0.f; k1n[2 * i] = 0.f; k1n[2 * i + 1] = 0.f;
         p.conf_n[(int64_t)b * ldN + i] = 0.f;
+    }
+    if (too_few) {
+        // Nothing below is meant for fewer than 8 rows (0 rows: 0 / 0 Hartley statistics, and the eigenvalue skip of the tail would
+        // run past the ninth): identity pose through the sel < 0 path of w8pt_select, E = 0, status bit 3.
+        if (tid == 0) {
+            for (int i = 0; i < 9; ++i) {
+                p.E[b * 9 + i] = 0.0;
+                if (p.F) p.F[b * 9 + i] = 0.f;
+            }
+            double* cd = p.cands + (int64_t)b * 48;
+            for (int c = 0; c < 4; ++c)
+                for (int i = 0; i < 12; ++i) cd[c * 12 + i] = (i == 0 || i == 4 || i == 8) ? 1.0 : 0.0;
+            p.sel[b] = -2;
+            for (int c = 0; c < 4; ++c) p.counts[b * 4 + c] = 0;
+            if (p.status) p.status[b] = 8;
+        }
+        return;
     }
 
     // pass 1: intrinsics normalisation (fp32 like the reference), sums for Hartley + weights
@@ -646,7 +664,8 @@ __global__ __launch_bounds__(256) void w8pt_triangulate(W8Params p) {
     if (threadIdx.x < 12) sRt[threadIdx.x] = p.cands[(int64_t)b * 48 + c * 12 + threadIdx.x];
     __syncthreads();
     bool ok = false;
-    if (i < (p.n_per ? p.n_per[b] : p.N)) {
+    const int nb = p.n_per ? (p.n_per[b] < 8 ? 0 : p.n_per[b]) : p.N;
+    if (i < nb) {
         const float* a = p.k0n + ((int64_t)b * p.N + i) * 2;
         const float* q = p.k1n + ((int64_t)b * p.N + i) * 2;
         double d0, d1;
@@ -681,7 +700,7 @@ __global__ __launch_bounds__(256) void w8pt_select(W8Params p) {
         if (!fin && p.status) p.status[b] |= 2;
     }
     if (i >= p.N) return;
-    if (p.n_per && i >= p.n_per[b]) {  // padding row of a ragged batch
+    if (p.n_per && (i >= p.n_per[b] || p.n_per[b] < 8)) {  // padding row of a ragged batch
         p.posdepth[(int64_t)b * p.N + i] = 0;
         if (p.determine_inliers) p.inliers[(int64_t)b * p.N + i] = 0;
         return;

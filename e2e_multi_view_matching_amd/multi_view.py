@@ -38,6 +38,28 @@ def _p(a):
     return a.ctypes.data_as(ctypes.c_void_p)
 
 
+def _w8pt_ba_on_device(dev, d_n, d_k0, d_k1, d_cf, d_K0, d_K1, n_iterations=10):
+    """The launch sequence behind every "w8pt_ba" relative pose, on device buffers: ``e2emv_w8pt_ragged`` (``d_n`` [Pn] int32
+    rows in use of ``d_k0`` / ``d_k1`` [Pn,N,2], ``d_cf`` [Pn,N]; intrinsics [Pn,k,k]) -> confidences of negative-depth matches
+    zeroed -> two-view bundle adjustment.  A problem with fewer than 8 rows comes back as the identity with no inlier.
+    Returns ``(T [Pn,4,4] float32, inliers [Pn,N] uint8)`` on the device."""
+    ctx = _lib.context(dev)
+    Pn, N = d_k0.shape[:2]
+    kdim = d_K0.shape[-1]
+    T = torch.empty((Pn, 4, 4), dtype=torch.float32, device=dev)
+    k0n, k1n, cfn = torch.empty_like(d_k0), torch.empty_like(d_k1), torch.empty_like(d_cf)
+    inl = torch.empty((Pn, N), dtype=torch.uint8, device=dev)
+    pos = torch.empty((Pn, N), dtype=torch.uint8, device=dev)
+    status = torch.empty((Pn,), dtype=torch.int32, device=dev)
+    P = _lib.ptr
+    with torch.cuda.device(dev):
+        ctx.call("e2emv_w8pt_ragged", Pn, N, P(d_n), P(d_k0), P(d_k1), P(d_K0), P(d_K1), kdim, Pn, P(d_cf), 0, P(None), 1, P(T),
+                 P(k0n), P(k1n), P(cfn), P(inl), P(pos), P(None), P(status), _lib.stream_ptr(dev))
+    refined, ok = run_bundle_adjust_2_view(k0n, k1n, mask_confidence(cfn, pos), T, n_iterations=n_iterations)
+    T[ok] = refined
+    return T, inl
+
+
 def relative_poses_w8pt_ba(problems, n_iterations=10):
     """Relative pose of MANY image pairs with different numbers of matches in one device pass: ragged weighted 8-point
     (``e2emv_w8pt_ragged``: every pair keeps its own Hartley statistics) -> confidences of negative-depth matches zeroed
@@ -50,7 +72,6 @@ def relative_poses_w8pt_ba(problems, n_iterations=10):
     if not live:
         return out
     dev = _dev()
-    ctx = _lib.context(dev)
     n_per = np.array([problems[q][2].shape[0] for q in live], np.int32)
     Pn, Nmax = len(live), int(n_per.max())
     kdim = problems[live[0]][0].shape[-1]
@@ -63,18 +84,7 @@ def relative_poses_w8pt_ba(problems, n_iterations=10):
         cf[r, :n_per[r]] = np.asarray(conf).reshape(n_per[r], -1)[:, 0]
         K0[r], K1[r] = intr0, intr1
     up = lambda a: torch.from_numpy(a).to(dev)  # noqa: E731
-    d_n, d_k0, d_k1, d_cf, d_K0, d_K1 = up(n_per), up(k0), up(k1), up(cf), up(K0), up(K1)
-    T = torch.empty((Pn, 4, 4), dtype=torch.float32, device=dev)
-    k0n, k1n, cfn = torch.empty_like(d_k0), torch.empty_like(d_k1), torch.empty_like(d_cf)
-    inl = torch.empty((Pn, Nmax), dtype=torch.uint8, device=dev)
-    pos = torch.empty((Pn, Nmax), dtype=torch.uint8, device=dev)
-    status = torch.empty((Pn,), dtype=torch.int32, device=dev)
-    P = _lib.ptr
-    with torch.cuda.device(dev):
-        ctx.call("e2emv_w8pt_ragged", Pn, Nmax, P(d_n), P(d_k0), P(d_k1), P(d_K0), P(d_K1), kdim, Pn, P(d_cf), 0, P(None), 1, P(T),
-                 P(k0n), P(k1n), P(cfn), P(inl), P(pos), P(None), P(status), _lib.stream_ptr(dev))
-    refined, ok = run_bundle_adjust_2_view(k0n, k1n, mask_confidence(cfn, pos), T, n_iterations=n_iterations)
-    T[ok] = refined
+    T, inl = _w8pt_ba_on_device(dev, up(n_per), up(k0), up(k1), up(cf), up(K0), up(K1), n_iterations)
     T_h, inl_h = T.cpu().numpy(), inl.cpu().numpy().astype(bool)
     for r, q in enumerate(live):
         out[q] = (True, T_h[r, :3, :3], T_h[r, :3, 3], inl_h[r, :n_per[r]])
@@ -197,6 +207,56 @@ def _chain_along_tree(n_images, edges, rel_pose):
     return pose
 
 
+def _init_arrays(n_images, rel, inlier_count, graph, min_inliers=20):
+    """Second stage of ``initialize_bundle_adjust`` (bundle_adjust_io.py:133-189) as arrays: ``rel`` {(i, j): 4x4 relative
+    pose}, ``inlier_count`` {(i, j): count}, ``graph`` [n,n] int match-graph weights (0 = no edge) -> maximum spanning tree ->
+    poses chained from image 0 -> the pairs worth keeping (``min_inliers`` or a tree edge).  Returns ``((init_R [n,9], pair_ids
+    [k,2] int32, pair_R [k,9], pair_pos [k,3]), {image: camera-to-world 4x4})``, rotations column-major: the arguments of
+    ``e2emv_mv_init`` and, as text, the rows of ``ba_init_in.csv``."""
+    graph = np.array(graph, dtype=int)
+    # maximum spanning tree = minimum spanning tree of (max - w + 1) on the existing edges (:135-138)
+    has_edge = graph != 0
+    graph[has_edge] = np.amax(graph) - graph[has_edge] + 1
+    tree = minimum_spanning_tree(graph).toarray().astype(int)
+    tree_edges = [(min(r, c), max(r, c)) for r, c in zip(*np.nonzero(tree))]
+    abs_pose = {0: np.eye(4)}
+    abs_pose.update(_chain_along_tree(n_images, tree_edges, rel))
+    world_to_cam = [np.linalg.inv(abs_pose[v]) if v in abs_pose else np.eye(4) for v in range(n_images)]
+    init_R = np.array([_colmajor(world_to_cam[v][:3, :3]) for v in range(n_images)], np.float64).reshape(n_images, 9)
+    ids, pair_R, pair_pos = [], [], []
+    for i, j in _pairs(n_images):
+        if (i, j) in rel and (inlier_count[(i, j)] >= min_inliers or (i, j) in tree_edges):
+            R = rel[(i, j)][:3, :3]
+            ids.append((i, j))
+            pair_R.append(_colmajor(R))
+            pair_pos.append(-R.transpose() @ rel[(i, j)][:3, 3])  # camera j in the frame of camera i
+    return (init_R, np.array(ids, np.int32).reshape(-1, 2), np.array(pair_R, np.float64).reshape(-1, 9),
+            np.array(pair_pos, np.float64).reshape(-1, 3)), abs_pose
+
+
+def _init_csv_lines(init_R, pair_ids, pair_R, pair_pos):
+    """The arrays of ``_init_arrays`` as the rows of ``ba_init_in.csv``."""
+    lines = [_csv([v] + list(R)) for v, R in enumerate(init_R)]  # 10 fields, ba_init.cpp:18-30
+    lines += [_csv([int(i), int(j)] + list(R) + list(pos)) for (i, j), R, pos in zip(pair_ids, pair_R, pair_pos)]  # 14 fields, :31-50
+    return lines
+
+
+def _averaged_extrinsics(init_R, pair_ids, pair_R, pair_pos):
+    """``e2emv_mv_init`` (= ``ba_initializer`` without its files) on the arrays of ``_init_arrays``: world-to-camera [n,4,4]."""
+    n = len(init_R)
+    init_R, pair_R, pair_pos = (np.ascontiguousarray(a, np.float64) for a in (init_R, pair_R, pair_pos))
+    pair_ids = np.ascontiguousarray(pair_ids, np.int32)
+    out_R, out_t, status = np.zeros((n, 9)), np.zeros((n, 3)), ctypes.c_int32(0)
+    rc = _lib.load_library().e2emv_mv_init(n, _p(init_R), len(pair_ids), _p(pair_ids), _p(pair_R), _p(pair_pos), _p(out_R), _p(out_t),
+                                           ctypes.byref(status))
+    if rc != 0:
+        raise _lib.E2EMVError(rc, "e2emv_mv_init failed")
+    E = np.tile(np.eye(4), (n, 1, 1))
+    E[:, :3, :3] = out_R.reshape(n, 3, 3).transpose(0, 2, 1)
+    E[:, :3, 3] = out_t
+    return E
+
+
 def initialize_bundle_adjust(n_images, data, result, file_path, conf_thresh=0., rel_pose_method="w8pt_ba"):
     """``initialize_bundle_adjust`` (bundle_adjust_io.py:62-191): matches of batch element 0 -> pairwise poses on the device
     (``rel_pose_method`` "w8pt_ba": w8pt + two-view BA; "ransac" / "ransac_ba": the RANSAC baseline, without / with two-view
@@ -228,22 +288,11 @@ def initialize_bundle_adjust(n_images, data, result, file_path, conf_thresh=0., 
             pw[_key("rel_pose", i, j)] = rel[(i, j)] = T
             graph[i, j] = len(pw[_key("mkpts", str(i), i, j)])
 
-    # maximum spanning tree = minimum spanning tree of (max - w + 1) on the existing edges (:135-138)
-    has_edge = graph != 0
-    graph[has_edge] = np.amax(graph) - graph[has_edge] + 1
-    tree = minimum_spanning_tree(graph).toarray().astype(int)
-    tree_edges = [(min(r, c), max(r, c)) for r, c in zip(*np.nonzero(tree))]
-    pw["abs_init_pose0"] = np.eye(4)
-    for node, P in _chain_along_tree(n_images, tree_edges, rel).items():
+    inlier_count = {(i, j): pw[_key("inlier_count", i, j)] for i, j in rel}
+    arrays, abs_pose = _init_arrays(n_images, rel, inlier_count, graph, min_inliers)
+    for node, P in abs_pose.items():
         pw["abs_init_pose" + str(node)] = P
-    world_to_cam = [np.linalg.inv(pw["abs_init_pose" + str(v)]) if "abs_init_pose" + str(v) in pw else np.eye(4) for v in range(n_images)]
-
-    lines = [_csv([v] + _colmajor(world_to_cam[v][:3, :3])) for v in range(n_images)]  # 10 fields, ba_init.cpp:18-30
-    for i, j in _pairs(n_images):
-        if (i, j) in rel and (pw[_key("inlier_count", i, j)] >= min_inliers or (i, j) in tree_edges):
-            R = rel[(i, j)][:3, :3]
-            position = -R.transpose() @ rel[(i, j)][:3, 3]  # camera j in the frame of camera i
-            lines.append(_csv([i, j] + _colmajor(R) + list(position)))  # 14 fields, ba_init.cpp:31-50
+    lines = _init_csv_lines(*arrays)
     with open(file_path, "w") as f:
         f.writelines(lines)
     return pw
@@ -334,8 +383,38 @@ def bundle_adjust(n_cams, fixed_cam, intr, cam_idx, pt_idx, obs_xy, obs_w, cams,
     summary = np.zeros(4)
     ctx.call("e2emv_mv_bundle_adjust", int(n_cams), int(fixed_cam), len(pts), len(cam_idx), _p(intr), _p(cam_idx), _p(pt_idx), _p(obs_xy),
              _p(obs_w), _p(cams), _p(pts), int(max_iterations), _p(summary), _lib.stream_ptr(dev))
+    return cams, pts, _ba_summary(summary)
+
+
+def _ba_summary(summary):
     names = ["max_iterations", "gradient_tolerance", "parameter_tolerance", "function_tolerance", "invalid_steps", "radius"]
-    return cams, pts, dict(initial_cost=summary[0], final_cost=summary[1], iterations=int(summary[2]), termination=names[int(summary[3])])
+    return dict(initial_cost=summary[0], final_cost=summary[1], iterations=int(summary[2]), termination=names[int(summary[3])])
+
+
+def bundle_adjust_batch(problems, max_iterations=50):
+    """Many bundle adjustments in ONE kernel launch, one workgroup each (``e2emv_mv_bundle_adjust_batch``).  ``problems``: list
+    of the argument tuples of ``bundle_adjust`` ``(n_cams, fixed_cam, intr, cam_idx, pt_idx, obs_xy, obs_w, cams, pts)``; they
+    may differ in every size, have no point, or cameras without observations.  Returns one ``(cams, pts, summary)`` per problem,
+    bit for bit what ``bundle_adjust`` returns for it alone."""
+    if not problems:
+        return []
+    dev = _dev()
+    ctx = _lib.context(dev)
+    n = len(problems)
+    cat = lambda k, dt, w: np.ascontiguousarray(np.concatenate([np.asarray(pr[k], dt).reshape(-1, w) for pr in problems]))  # noqa: E731
+    n_cams, fixed = np.array([pr[0] for pr in problems], np.int32), np.array([pr[1] for pr in problems], np.int32)
+    intr, cam_idx, pt_idx = cat(2, np.float64, 4), cat(3, np.int32, 1), cat(4, np.int32, 1)
+    obs_xy, obs_w, cams, pts = cat(5, np.float64, 2), cat(6, np.float64, 2), cat(7, np.float64, 6), cat(8, np.float64, 3)
+    size = lambda k, w: [np.asarray(pr[k]).size // w for pr in problems]  # noqa: E731
+    if size(7, 6) != list(n_cams) or size(4, 1) != size(3, 1) or size(5, 2) != size(3, 1) or size(6, 2) != size(3, 1):
+        raise ValueError("bundle_adjust_batch: a problem's arrays disagree in length")
+    pt_off = np.concatenate([[0], np.cumsum(size(8, 3))]).astype(np.int64)
+    obs_off = np.concatenate([[0], np.cumsum(size(3, 1))]).astype(np.int64)
+    summary = np.zeros((n, 4))
+    ctx.call("e2emv_mv_bundle_adjust_batch", n, _p(n_cams), _p(fixed), _p(intr), _p(pt_off), _p(obs_off), _p(cam_idx), _p(pt_idx), _p(obs_xy),
+             _p(obs_w), _p(cams), _p(pts), int(max_iterations), _p(summary), _lib.stream_ptr(dev))
+    cam_off = np.concatenate([[0], np.cumsum(n_cams)])
+    return [(cams[cam_off[k]:cam_off[k + 1]].copy(), pts[pt_off[k]:pt_off[k + 1]].copy(), _ba_summary(summary[k])) for k in range(n)]
 
 
 def solve_tuple_poses(tuple_size, data, result, tmp_dir):
@@ -349,6 +428,136 @@ def solve_tuple_poses(tuple_size, data, result, tmp_dir):
     write_bundle_adjust_problem(tuple_size, pair_wise_data, start, path("ba_in.csv"))
     run_bundle_adjuster(tmp_dir)
     return np.array(read_bundle_adjust_result(path("ba_out.csv")))
+
+
+def _collect_matches_batch(tuple_size, data, result, conf_thresh):
+    """``_collect_matches`` for every batch element at once and on the device (``e2emv_mv_collect``): returns ``(mkpts0, mkpts1
+    [B*P,N,2], conf [B*P,N], count [B*P] int32)`` device tensors, problem (b, pair q) at row ``b * P + q``, the kept matches in
+    ascending keypoint order, rows behind the count zero.  A pair without a ``matches`` entry has count 0."""
+    pairs = _pairs(tuple_size)
+    keys = [_key("matches", str(i), i, j) for i, j in pairs]
+    have = [k for k in keys if k in result]
+    if not have:
+        raise ValueError("no pair of the tuple has matches")
+    dev = result[have[0]].device
+    if dev.type != "cuda":
+        dev = _dev()
+    ctx = _lib.context(dev)
+    B, N = result[have[0]].shape[:2]
+    prep = lambda t, dt: t.to(dev, dt).contiguous()  # noqa: E731
+    k0s, k1s, ms, cs, n1, channels = [], [], [], [], [], None
+    for (i, j), mkey in zip(pairs, keys):
+        if mkey not in result:
+            k0s.append(None); k1s.append(None); ms.append(None); cs.append(None); n1.append(0)
+            continue
+        if "keypoints" + str(i) in data:
+            k0, k1 = data["keypoints" + str(i)], data["keypoints" + str(j)]
+        else:
+            k0, k1 = data[_key("keypoints", str(i), i, j)], data[_key("keypoints", str(j), i, j)]
+        m, c = prep(result[mkey], torch.int64), prep(result[_key("conf_scores_", i, j)], torch.float32)
+        c = c.reshape(B, N, -1)
+        k0, k1 = prep(k0, torch.float32), prep(k1, torch.float32)
+        if m.shape != (B, N) or k0.shape != (B, N, 2) or k1.shape[0] != B or k1.shape[2] != 2 or (channels not in (None, c.shape[2])):
+            raise ValueError("matches / keypoints / conf_scores of pair {} disagree in shape".format((i, j)))
+        channels = c.shape[2]
+        k0s.append(k0); k1s.append(k1); ms.append(m); cs.append(c); n1.append(k1.shape[1])
+    Pn = B * len(pairs)
+    o0 = torch.empty((Pn, N, 2), dtype=torch.float32, device=dev)
+    o1, oc = torch.empty_like(o0), torch.empty((Pn, N), dtype=torch.float32, device=dev)
+    count = torch.empty((Pn,), dtype=torch.int32, device=dev)
+    n1 = np.array(n1, np.int32)
+    ptrs = [_lib.ptr_array(lst) for lst in (k0s, k1s, ms, cs)]  # (pointer, owner) pairs: the owners live until the call returns
+    with torch.cuda.device(dev):
+        ctx.call("e2emv_mv_collect", B, tuple_size, N, ptrs[0][0], ptrs[1][0], _p(n1), ptrs[2][0], ptrs[3][0], channels, float(conf_thresh),
+                 _lib.ptr(o0), _lib.ptr(o1), _lib.ptr(oc), _lib.ptr(count), _lib.stream_ptr(dev))
+    return o0, o1, oc, count
+
+
+def _tuple_intrinsics(tuple_size, data, dev, B):
+    """``data["intr{v}"]`` of every image as contiguous float32 device tensors [nb,k,k] with one common layout."""
+    intr = [data["intr" + str(v)].to(dev, torch.float32) for v in range(tuple_size)]
+    intr = [(K.unsqueeze(0) if K.dim() == 2 else K).contiguous() for K in intr]
+    kdim, nb = intr[0].shape[-1], intr[0].shape[0]
+    if kdim not in (3, 4) or nb not in (1, B) or any(K.shape != (nb, kdim, kdim) for K in intr):
+        raise ValueError("the intrinsics of a tuple must share one [1 | B, k, k] layout, k = 3 or 4")
+    return intr, kdim, nb
+
+
+def _tuple_ba_call(name, tuple_size, collected, counts, intr, kdim, nb, extrinsics, *tail):
+    o0, o1, oc, _ = collected
+    dev = o0.device
+    pa, owner = _lib.ptr_array(intr)
+    with torch.cuda.device(dev):
+        _lib.context(dev).call(name, len(extrinsics), tuple_size, o0.shape[1], _p(counts), _lib.ptr(o0), _lib.ptr(o1), _lib.ptr(oc), pa, kdim, nb,
+                               _p(extrinsics), *tail, _lib.stream_ptr(dev))
+    del owner
+
+
+def solve_tuple_poses_batch(tuple_size, data, result, conf_thresh=0., timings=None):
+    """``solve_tuple_poses`` for EVERY batch element of the matcher result, in memory: returns the refined world-to-camera
+    extrinsics ``float64 [B, tuple_size, 4, 4]``, camera 0 the gauge.  Relative poses are "w8pt_ba" only here (the RANSAC
+    methods stay on the CSV path: ``initialize_bundle_adjust(..., rel_pose_method=...)``).  Stages: matches collected on the
+    device (one launch) -> w8pt + two-view BA of all B * T(T-1)/2 pairs -> one copy to the host, spanning tree and rotation /
+    position averaging per tuple (``e2emv_mv_init``) -> all bundle-adjustment problems built on the device (one launch) and
+    solved one workgroup per tuple (one launch).  No file, and no element's result depends on its batch neighbours.
+    ``timings``: optional dict that receives the wall time of each stage in seconds (synchronises after every stage)."""
+    import time
+    pairs = _pairs(tuple_size)
+    P = len(pairs)
+    clock = [time.perf_counter()]
+
+    def lap(name):
+        if timings is not None:
+            torch.cuda.synchronize()
+            now = time.perf_counter()
+            timings[name] = timings.get(name, 0.0) + now - clock[0]
+            clock[0] = now
+
+    collected = _collect_matches_batch(tuple_size, data, result, conf_thresh)
+    o0, o1, oc, count = collected
+    dev = o0.device
+    B = o0.shape[0] // P
+    lap("collect")
+    intr, kdim, nb = _tuple_intrinsics(tuple_size, data, dev, B)
+    per_pair = lambda side: torch.stack([intr[pr[side]].expand(B, kdim, kdim) for pr in pairs], 1).reshape(B * P, kdim, kdim).contiguous()  # noqa: E731
+    T_d, inl = _w8pt_ba_on_device(dev, count, o0, o1, oc, per_pair(0), per_pair(1))
+    # one device -> host copy for the whole batch: poses, inlier counts, match counts
+    packed = torch.cat([T_d.reshape(B * P, 16).double(), inl.sum(1, dtype=torch.int32).double()[:, None], count.double()[:, None]], 1).cpu().numpy()
+    lap("relative_poses")
+    rel_T, n_inl = packed[:, :16].reshape(B, P, 4, 4), packed[:, 16].astype(np.int64).reshape(B, P)
+    counts = np.ascontiguousarray(packed[:, 17].astype(np.int32))
+    start = np.zeros((B, tuple_size, 4, 4))
+    for b in range(B):
+        graph = np.zeros((tuple_size, tuple_size), dtype=int)
+        rel, inlier_count = {}, {}
+        for q, (i, j) in enumerate(pairs):
+            if counts[b * P + q] >= 8:  # success of estimate_relative_pose_w8pt_ba
+                rel[(i, j)], inlier_count[(i, j)] = rel_T[b, q], int(n_inl[b, q])
+                graph[i, j] = counts[b * P + q]
+        start[b] = _averaged_extrinsics(*_init_arrays(tuple_size, rel, inlier_count, graph)[0])
+    lap("initialisation")
+    out, summary = np.zeros((B, tuple_size, 4, 4)), np.zeros((B, 4))
+    _tuple_ba_call("e2emv_mv_tuple_ba", tuple_size, collected, counts, intr, kdim, nb, start, 50, _p(out), _p(summary))
+    lap("build_and_bundle_adjust")
+    return out
+
+
+def _tuple_problems(tuple_size, collected, counts, intr, kdim, nb, extrinsics):
+    """The bundle-adjustment problems ``solve_tuple_poses_batch`` solves (``e2emv_mv_tuple_problem``), one argument tuple of
+    ``bundle_adjust`` per batch element: what ``write_bundle_adjust_problem`` writes as text, built on the device."""
+    extrinsics = np.ascontiguousarray(extrinsics, np.float64)
+    B, P = len(extrinsics), len(_pairs(tuple_size))
+    counts = np.ascontiguousarray(counts, np.int32)
+    n_pts = counts.reshape(B, P).sum(1)
+    tot = int(n_pts.sum())
+    cam_idx, pt_idx = np.zeros(2 * tot, np.int32), np.zeros(2 * tot, np.int32)
+    obs_xy, obs_w, cams, pts = np.zeros((2 * tot, 2)), np.zeros((2 * tot, 2)), np.zeros((B * tuple_size, 6)), np.zeros((tot, 3))
+    _tuple_ba_call("e2emv_mv_tuple_problem", tuple_size, collected, counts, intr, kdim, nb, extrinsics, _p(cam_idx), _p(pt_idx), _p(obs_xy),
+                   _p(obs_w), _p(cams), _p(pts))
+    off = np.concatenate([[0], np.cumsum(n_pts)])
+    return [(tuple_size, 0, np.array([1., 1., 0., 0.]), cam_idx[2 * off[b]:2 * off[b + 1]], pt_idx[2 * off[b]:2 * off[b + 1]],
+             obs_xy[2 * off[b]:2 * off[b + 1]], obs_w[2 * off[b]:2 * off[b + 1]], cams[b * tuple_size:(b + 1) * tuple_size], pts[off[b]:off[b + 1]])
+            for b in range(B)]
 
 
 def tuple_pose_errors(extrinsics, cam_to_world):
@@ -379,6 +588,23 @@ def eval_bundle_adjust(tuple_size, data, result, tmp_dir, pose_errors, verbose=F
     if verbose:
         for (i, j), et, er in zip(_pairs(tuple_size), err_t, err_R):
             logging.info("%d -> %d: rot %5.1fdeg\tt %5.1fdeg", i, j, er, et)
+    return pose_errors
+
+
+def eval_bundle_adjust_batch(tuple_size, data, result, pose_errors, verbose=False):
+    """``eval_bundle_adjust`` for every batch element through ``solve_tuple_poses_batch``: extends ``pose_errors = [max errors,
+    translation errors, rotation errors]`` by ``B * T(T-1)/2`` entries, batch element outer, pairs in ``_pairs`` order inside
+    (for ``B = 1`` the entries ``eval_bundle_adjust`` appends, in its order)."""
+    extrinsics = solve_tuple_poses_batch(tuple_size, data, result)
+    poses = np.stack([data["pose" + str(v)].cpu().numpy() for v in range(tuple_size)], 1)  # [B,T,4,4]: one copy per image
+    for b, E in enumerate(extrinsics):
+        err_t, err_R = tuple_pose_errors(E, poses[b])
+        pose_errors[0].extend(np.maximum(err_t, err_R))
+        pose_errors[1].extend(err_t)
+        pose_errors[2].extend(err_R)
+        if verbose:
+            for (i, j), et, er in zip(_pairs(tuple_size), err_t, err_R):
+                logging.info("[%d] %d -> %d: rot %5.1fdeg\tt %5.1fdeg", b, i, j, er, et)
     return pose_errors
 
 

@@ -148,7 +148,7 @@ int e2emv_gather_matched(e2emv_ctx* ctx, int B, int N0, int N1, const float* d_k
  * d_inliers [B,N] u8 (written iff determine_inliers); d_posdepth [B,N] u8; d_F [B,3,3]
  * (the estimated essential matrix, may be NULL); d_status [B] int32 (bit0: sum(conf)<=1e-6,
  * bit1: non-finite result, bit2: essential matrix of rank < 2 - no usable correspondence; the pose is then finite but
- * arbitrary, like a library SVD's null-space choice in the reference), may be NULL.  Returns E2EMV_ESHAPE when N < 8 (the Python shim
+ * arbitrary, like a library SVD's null-space choice in the reference; bit3: see e2emv_w8pt_ragged), may be NULL.  Returns E2EMV_ESHAPE when N < 8 (the Python shim
  * maps that to the reference's (None, None), estimate_relative_pose.py:85-86).             */
 int e2emv_w8pt(e2emv_ctx* ctx, int B, int N, const float* d_kpts0, const float* d_kpts1, const float* d_intr0,
                const float* d_intr1, int kdim, int intr_batch, const float* d_conf, int choose_closest,
@@ -156,10 +156,12 @@ int e2emv_w8pt(e2emv_ctx* ctx, int B, int N, const float* d_kpts0, const float* 
                float* d_conf_n, uint8_t* d_inliers, uint8_t* d_posdepth, float* d_F, int32_t* d_status,
                void* stream);
 
-/* e2emv_w8pt on a RAGGED batch: sample b uses its first d_n_per[b] (8 <= n <= N) correspondences; every per-correspondence
+/* e2emv_w8pt on a RAGGED batch: sample b uses its first d_n_per[b] (0 <= n <= N) correspondences; every per-correspondence
  * buffer keeps the row stride N and the rows beyond n read 0 / false in the outputs.  The Hartley statistics of sample b
  * run over its own n rows only (a zero-weight padding row would change them - estimate_relative_pose.py:56-57), which is
- * what lets the pairs of a tuple with different numbers of matches share one launch (bundle_adjust_io.py:98-131). */
+ * what lets the pairs of a tuple with different numbers of matches share one launch (bundle_adjust_io.py:98-131).
+ * A sample with n < 8 is not solved (the counts may live on the device only, so the caller cannot drop it): d_T = identity,
+ * d_F = 0, all its rows read 0 / false, d_status bit3 is set and no other bit. */
 int e2emv_w8pt_ragged(e2emv_ctx* ctx, int B, int N, const int32_t* d_n_per, const float* d_kpts0, const float* d_kpts1,
                       const float* d_intr0, const float* d_intr1, int kdim, int intr_batch, const float* d_conf,
                       int choose_closest, const float* d_T_gt, int determine_inliers, float* d_T, float* d_kpts0n,
@@ -254,11 +256,52 @@ int e2emv_mv_bundle_adjust(e2emv_ctx* ctx, int n_cams, int fixed_cam, int n_pts,
                            const int32_t* cam_idx, const int32_t* pt_idx, const double* obs_xy, const double* obs_w,
                            double* cams, double* pts, int max_iterations, double* summary, void* stream);
 /* `ba_in.csv` -> `ba_out.csv` (bundle_adjuster.cpp:7-23; parser ba_problem.cpp:8-88, writer :98-113), 50 iterations. */
+/* n_problems such problems solved by ONE kernel launch, one workgroup per problem; e2emv_mv_bundle_adjust is the batch of
+ * one, and a problem's result does not depend on its neighbours or its position (bit for bit).  HOST pointers.  Problem k
+ * has n_cams[k] cameras (its rows of cams follow those of problem k - 1), fixed camera fixed_cam[k], intrinsics
+ * intr[4k..4k+3], the points pt_off[k] .. pt_off[k+1] of pts and the observations obs_off[k] .. obs_off[k+1] of cam_idx /
+ * pt_idx / obs_xy / obs_w; cam_idx and pt_idx count from 0 inside their problem.  Offsets start at 0 and do not decrease
+ * (E2EMV_ESHAPE); a problem may have no point, and cameras without observations keep their parameters.  summary
+ * [n_problems,4] as above (may be NULL).  Synchronous.                                                               */
+int e2emv_mv_bundle_adjust_batch(e2emv_ctx* ctx, int n_problems, const int32_t* n_cams, const int32_t* fixed_cam,
+                                 const double* intr, const int64_t* pt_off, const int64_t* obs_off, const int32_t* cam_idx,
+                                 const int32_t* pt_idx, const double* obs_xy, const double* obs_w, double* cams, double* pts,
+                                 int max_iterations, double* summary, void* stream);
+/* `ba_in.csv` -> `ba_out.csv` (bundle_adjuster.cpp:7-23; parser ba_problem.cpp:8-88, writer :98-113), 50 iterations. */
 int e2emv_mv_bundle_adjust_files(e2emv_ctx* ctx, const char* in_csv, const char* out_csv, void* stream);
 /* cv2.triangulatePoints as used by write_bundle_adjust_problem (bundle_adjust_io.py:226-227): homogeneous DLT of
  * two views, one thread per point, fp64.  HOST pointers: P0, P1 [3,4] row-major, x0, x1 [n,2], xyz [n,3].           */
 int e2emv_mv_triangulate(e2emv_ctx* ctx, int n, const double* P0, const double* P1, const double* x0, const double* x1,
                          double* xyz, void* stream);
+
+/* The multi-view back-end for a whole batch of B tuples of T images without files (the first stage of
+ * bundle_adjust_io.py:62-96 for every batch element at once).  Pair q enumerates (i, j), i < j, j outer; problem (b, q) has
+ * index b * P + q, P = T (T - 1) / 2.  HOST arrays of P DEVICE pointers: d_kpts0[q] [B,N,2] keypoints of image i,
+ * d_kpts1[q] [B,n_kpts1[q],2] keypoints of image j, d_matches[q] [B,N] int64 (NULL: the pair has no matches, count 0),
+ * d_conf[q] [B,N,conf_channels].  Keypoint n of image i is kept when 0 <= match < n_kpts1[q] and every confidence channel is
+ * > conf_thresh; the kept rows go, IN ASCENDING n, to d_mkpts0 / d_mkpts1 [B*P,N,2] (the keypoint and its match) and d_mconf
+ * [B*P,N] (first channel) - the padded layout e2emv_w8pt_ragged reads, rows behind the count 0 - and their number to
+ * d_count [B*P].  One launch, no host synchronisation.                                                                  */
+int e2emv_mv_collect(e2emv_ctx* ctx, int B, int T, int N, const float* const* d_kpts0, const float* const* d_kpts1,
+                     const int32_t* n_kpts1, const int64_t* const* d_matches, const float* const* d_conf, int conf_channels,
+                     float conf_thresh, float* d_mkpts0, float* d_mkpts1, float* d_mconf, int32_t* d_count, void* stream);
+/* write_bundle_adjust_problem + bundle_adjuster + read_bundle_adjust_result (bundle_adjust_io.py:193-273) for B tuples
+ * from the buffers of e2emv_mv_collect, in memory: counts [B*P] HOST copy of d_count; d_intr HOST array of T DEVICE
+ * pointers [intr_batch,kdim,kdim] (intr_batch 1 or B, kdim 3 or 4); extr HOST [B,T,4,4] row-major world -> camera start
+ * poses.  One launch builds all problems (fp32 (kp - c) / f observations widened to fp64, one DLT point per match, weights
+ * = confidence / (0.5 (sum + 1e-3)) with the tuple's sum over its 2 n_pts observations in fp64, index lists in closed
+ * form from the counts), one launch solves them (camera 0 fixed, f = 1, c = 0), as e2emv_mv_bundle_adjust_batch would.
+ * out_extr HOST [B,T,4,4], summary HOST [B,4] (may be NULL).  Synchronous.                                             */
+int e2emv_mv_tuple_ba(e2emv_ctx* ctx, int B, int T, int N, const int32_t* counts, const float* d_mkpts0, const float* d_mkpts1,
+                      const float* d_mconf, const float* const* d_intr, int kdim, int intr_batch, const double* extr,
+                      int max_iterations, double* out_extr, double* summary, void* stream);
+/* The problems e2emv_mv_tuple_ba would solve, copied out instead (HOST, concatenated in the layout
+ * e2emv_mv_bundle_adjust_batch takes; tuple b owns n_b = sum of its counts points and 2 n_b observations): cam_idx, pt_idx
+ * [2n], obs_xy, obs_w [2n,2], cams [B*T,6], pts [n,3].                                                                  */
+int e2emv_mv_tuple_problem(e2emv_ctx* ctx, int B, int T, int N, const int32_t* counts, const float* d_mkpts0,
+                           const float* d_mkpts1, const float* d_mconf, const float* const* d_intr, int kdim, int intr_batch,
+                           const double* extr, int32_t* cam_idx, int32_t* pt_idx, double* obs_xy, double* obs_w, double* cams,
+                           double* pts, void* stream);
 
 /* ---- RANSAC essential matrix (SuperGlue's estimate_pose: OpenCV findEssentialMat(RANSAC) + recoverPose) ------------
  * A ragged batch of P problems in one call, no host synchronisation inside: problem p uses its first d_n_per[p]
