@@ -6,9 +6,9 @@
 //   * no fp32 -> plane split (40 VALU per thread) and no ds_write at all: the 64 KB of operand planes go from global
 //     memory straight into LDS, 64 buffer_load_dwordx4 ... lds per step (8 per wave), each a full 128-byte line per row;
 //   * LDS double-buffered (2 x 64 KB), ONE barrier per K step: the loads of step g + 1 are issued right after the barrier
-//     that opens step g and have that whole step (48 MFMAs per wave) to land;
+//     that opens step g and have that whole step (96 MFMAs per wave) to land;
 //   * bank-conflict-free fragment reads without padding (XOR swizzle applied on the source address, p2.h).
-// The epilogue goes through per-wave LDS slabs (32 rows x 36 floats) so that bias / ReLU / residual / the plane split
+// The epilogue goes through per-wave LDS slabs (32 rows x 32 floats, the 16-byte chunks of a row XOR-swizzled by the row) so that bias / ReLU / residual / the plane split
 // work on 8 consecutive columns of one row per lane and every store covers 64-byte row segments; the residual is read
 // back from its planes (22 bits) in the same layout.  Output kinds: fp32, scaled planes (the next GEMM's operand), or
 // the attention operands q | k (plain planes, q pre-scaled) + V^T (transposed plain planes, keys in the order of the
@@ -35,7 +35,6 @@ __global__ __launch_bounds__(512, 1) void gemm_p2_kernel(GemmP2Params p) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wr = wave >> 1, wc = wave & 1;
-    const int l31 = lane & 31, lh = lane >> 5;
     const int nk = p.K / P2_BK, nk1 = p.K1 / P2_BK;
 
     const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(p.A), 0, (int)p.a_bytes, 0x00020000);
@@ -75,9 +74,9 @@ __global__ __launch_bounds__(512, 1) void gemm_p2_kernel(GemmP2Params p) {
         for (int i = 0; i < 4; ++i) p2_glds16(rsW, dst + P2_TILEB + i * 1024, w_vo[i] + dep, sw);
     };
 
-    // ---- fragments: lane (row l31, k half lh); chunk index c = 4 plane + 2 ks + lh, stored at position c ^ ((l31 >> 1) & 7)
-    const int swz = (l31 >> 1) & 7;
-    p2_f32x16 acc[4][2];
+    // ---- fragments (gp_kstep): lane l = (row l & 15 of a 16-row block, k-chunk l >> 4); chunk index c = 4 plane + (l >> 4), stored at
+    // position c ^ ((row >> 1) & 7)
+    p2_acc_t acc;
 
     // ---- the K step: gp_kstep (gemm_p2_core.h), software-pipelined inside the wave
 
@@ -156,11 +155,11 @@ __global__ __launch_bounds__(512, 1) void gemm_p2_kernel(GemmP2Params p) {
                 const int d = e_run - e_step;
                 const float f = d < -126 ? 0.f : p2_exp2i(d);
 #pragma unroll
-                for (int j = 0; j < 4; ++j)
+                for (int j = 0; j < P2_ACC_J; ++j)
 #pragma unroll
-                    for (int i = 0; i < 2; ++i)
+                    for (int i = 0; i < P2_ACC_I; ++i)
 #pragma unroll
-                        for (int r = 0; r < 16; ++r) acc[j][i][r] *= f;
+                        for (int r = 0; r < 4; ++r) acc[j][i][r] *= f;
             }
             e_run = e_step;
             // the NEXT tile's exponents: loaded beside the operand loads of K step 2, picked up at the head of step 3, right
@@ -174,10 +173,10 @@ __global__ __launch_bounds__(512, 1) void gemm_p2_kernel(GemmP2Params p) {
         ++cur_kt;
         const bool ldv = ld_valid && !(since == 0 && ahead);
         if (issue_first && ldv) issue(buf ^ 1, ld_kt, 0u);
-        gp_kstep<decltype(FIRST)::value>(smem_p2, buf, wr, wc, l31, lh, acc);
+        gp_kstep<decltype(FIRST)::value>(smem_p2, buf, wr, wc, lane, acc);
         if (!issue_first && ldv) {
             unsigned dep = 0;
-            asm("" : "+v"(dep) : "v"(acc[3][1]));  // scheduling-only: keeps the loads behind the MFMAs
+            asm("" : "+v"(dep) : "v"(acc[P2_ACC_J - 1][P2_ACC_I - 1]));  // scheduling-only: keeps the loads behind the MFMAs
             issue(buf ^ 1, ld_kt, dep);
         }
         if (ldv) advance();
@@ -192,7 +191,7 @@ __global__ __launch_bounds__(512, 1) void gemm_p2_kernel(GemmP2Params p) {
             // the buffer of the step just computed is free once every wave is through it: the loads of the step after next
             asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
             unsigned dep = 0;
-            asm("" : "+v"(dep) : "v"(acc[3][1]));
+            asm("" : "+v"(dep) : "v"(acc[P2_ACC_J - 1][P2_ACC_I - 1]));
             issue(buf ^ 1, ld_kt, dep);
             advance();
             ahead = true;

@@ -56,8 +56,8 @@ __global__ __launch_bounds__(512, 1) void gemm_p2_chain_kernel(GemmP2ChainParams
     // Nothing derived from the lane index lives longer than it must (gp_lane_now): the K loop's fragment addresses are derived
     // anew per tile (so the epilogue between two K loops has their registers), the loader's offsets per K step, the exponent
     // fetch's per fetch.  The four epilogues of this kernel need every register gemm_p2's single one has.
-    int l31 = 0, lh = 0;
-    unsigned rc_t = 0;  // the loader's lane constants (lane_rc below), per tile like l31 / lh
+    int lane_t = 0;     // the lane index the K step derives its fragment addresses from
+    unsigned rc_t = 0;  // the loader's lane constants (lane_rc below), per tile like lane_t
     const int nst = cp.n_stages, tpr = cp.first[nst];
     // workgroup b walks row blocks b, b + gridDim.x, ...; flat tile index f = (row block of mine) * tpr + tile within the block
     const int n_my = (cp.row_blocks - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x;
@@ -164,7 +164,7 @@ __global__ __launch_bounds__(512, 1) void gemm_p2_chain_kernel(GemmP2ChainParams
     };
     auto e_of = [](unsigned long long ew, int kb) { return (int)(signed char)(ew >> (8 * kb)); };
 
-    p2_f32x16 acc[4][2];
+    p2_acc_t acc;
     int lf = 0, lkt = 0;                        // load position: (flat tile, K step)
     bool ld_valid = true, ld_blocked = false;   // blocked: the next tile is hard-dependent - its loads wait for this tile's epilogue
     auto advance = [&]() {
@@ -206,11 +206,11 @@ __global__ __launch_bounds__(512, 1) void gemm_p2_chain_kernel(GemmP2ChainParams
                 const int d = e_run - e_step;
                 const float fs = d < -126 ? 0.f : p2_exp2i(d);
 #pragma unroll
-                for (int j = 0; j < 4; ++j)
+                for (int j = 0; j < P2_ACC_J; ++j)
 #pragma unroll
-                    for (int i = 0; i < 2; ++i)
+                    for (int i = 0; i < P2_ACC_I; ++i)
 #pragma unroll
-                        for (int r = 0; r < 16; ++r) acc[j][i][r] *= fs;
+                        for (int r = 0; r < 4; ++r) acc[j][i][r] *= fs;
             }
             e_run = e_step;
             if (__builtin_expect(cur_kt == 2, 0)) {  // once per tile, beside the operand loads of K step 2
@@ -232,10 +232,10 @@ __global__ __launch_bounds__(512, 1) void gemm_p2_chain_kernel(GemmP2ChainParams
         ++cur_kt;
         const bool ldv = ld_valid && !ld_blocked && !(since == 0 && ahead);
         if (issue_first && ldv) issue(buf ^ 1, lkt, rc_t);
-        gp_kstep<decltype(FIRST)::value>(smem_p2c, buf, wr, wc, l31, lh, acc);
+        gp_kstep<decltype(FIRST)::value>(smem_p2c, buf, wr, wc, lane_t, acc);
         if (!issue_first && ldv) {
             unsigned rc = rc_t;
-            asm("" : "+v"(rc) : "v"(acc[3][1]));  // scheduling-only: keeps the loads behind the MFMAs
+            asm("" : "+v"(rc) : "v"(acc[P2_ACC_J - 1][P2_ACC_I - 1]));  // scheduling-only: keeps the loads behind the MFMAs
             issue(buf ^ 1, lkt, rc);
         }
         if (ldv) advance();
@@ -249,9 +249,7 @@ __global__ __launch_bounds__(512, 1) void gemm_p2_chain_kernel(GemmP2ChainParams
         const GemmP2Params& q = cp.st[s];
         const int nk = q.K / P2_BK;
         {
-            const int ln = gp_lane_now();
-            l31 = ln & 31;
-            lh = ln >> 5;
+            lane_t = gp_lane_now();
             rc_t = lane_rc();
         }
         has_e = q.EA != nullptr || ((cp.kind[s] & 4) && q.ER != nullptr);
@@ -263,7 +261,7 @@ __global__ __launch_bounds__(512, 1) void gemm_p2_chain_kernel(GemmP2ChainParams
             // the buffer of the step just computed is free once every wave is through it: the loads of the step after next
             asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
             unsigned rc = lane_rc();
-            asm("" : "+v"(rc) : "v"(acc[3][1]));
+            asm("" : "+v"(rc) : "v"(acc[P2_ACC_J - 1][P2_ACC_I - 1]));
             issue(buf ^ 1, lkt, rc);
             advance();
             ahead = true;

@@ -11,7 +11,8 @@
 // The PRODUCER of an activation emits the planes in its epilogue (gemm_p2.hip, attention_p2.hip); consumers move the
 // 128-byte pieces straight from global memory into LDS (buffer_load ... lds, no VGPR staging, no split in the K loop).
 // LDS image of a tile row = the 8 16-byte chunks of the piece, chunk c stored at position c ^ ((row >> 1) & 7): every
-// ds_read_b128 of an MFMA fragment (32 rows, one chunk index) then touches 16 different 16-byte bank slots per lane group.
+// ds_read_b128 of an MFMA fragment (32 rows of one chunk index for a 32x32x16 operand; 16 rows x the 4 chunks of a plane for the
+// 16x16x32 operands of gemm_p2_core.h, derived there) then touches 16 different 16-byte bank slots per lane group.
 // The swizzle is applied on the SOURCE address of the LDS-direct load (the destination of such a load is lane-linear).
 #pragma once
 #include "common.h"
