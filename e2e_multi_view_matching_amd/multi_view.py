@@ -8,7 +8,8 @@ Same function names, arguments, dictionary keys and file layouts as the referenc
   baseline (``ransac.py``: 5-point RANSAC + recoverPose on the device) instead of OpenCV;
 * ``ba_initializer`` / ``bundle_adjuster``: not separate executables built on Theia/Ceres but entry points of
   libe2emv.so called in-process (``run_ba_initializer`` = host C++ averaging, ``run_bundle_adjuster`` = one HIP workgroup
-  doing the whole LM/Schur optimisation); ``python -m e2e_multi_view_matching_amd.multi_view ba_initializer <dir>`` and
+  doing the whole LM/Schur optimisation; the batched path can run the averaging on the device instead, one wave per tuple:
+  ``solve_tuple_poses_batch(..., init="device")``, ``averaged_extrinsics_batch``); ``python -m e2e_multi_view_matching_amd.multi_view ba_initializer <dir>`` and
   ``... bundle_adjuster <dir>`` give the reference's command-line shape;
 * triangulation: ``cv2.triangulatePoints`` (OpenCV is absent) -> ``e2emv_mv_triangulate`` (same homogeneous DLT).
 Host glue (dict plumbing, spanning tree via scipy like the reference, CSV text) stays in Python like the reference's.
@@ -257,6 +258,35 @@ def _averaged_extrinsics(init_R, pair_ids, pair_R, pair_pos):
     return E
 
 
+def averaged_extrinsics_batch(problems):
+    """``_averaged_extrinsics`` for MANY problems in one kernel launch on the device, one wave each (``e2emv_mv_init_batch``).
+    ``problems``: list of ``_init_arrays`` outputs (``((init_R, pair_ids, pair_R, pair_pos), poses)``) or of the four arrays
+    alone; at most 8 views and 28 pairs each, a pair of views at most once.  Returns ``(extrinsics, status)``: one world-to-camera
+    ``[n,4,4]`` per problem and the int32 status words of the solver (bit 1: rotations failed, bit 2: positions failed; not
+    raised, as on the host path).  Same solver and options as ``e2emv_mv_init``; the numbers agree to rounding."""
+    if not problems:
+        return [], np.zeros(0, np.int32)
+    dev = _dev()
+    arrays = [pr[0] if len(pr) == 2 else pr for pr in problems]
+    n_views = np.array([len(a[0]) for a in arrays], np.int32)
+    n_pairs = [len(a[1]) for a in arrays]
+    cat = lambda k, dt, w: np.ascontiguousarray(np.concatenate([np.asarray(a[k], dt).reshape(-1, w) for a in arrays]))  # noqa: E731
+    init_R, pair_ids, pair_R, pair_pos = cat(0, np.float64, 9), cat(1, np.int32, 2), cat(2, np.float64, 9), cat(3, np.float64, 3)
+    if [len(np.asarray(a[2]).reshape(-1, 9)) for a in arrays] != n_pairs or [len(np.asarray(a[3]).reshape(-1, 3)) for a in arrays] != n_pairs:
+        raise ValueError("averaged_extrinsics_batch: a problem's pair arrays disagree in length")
+    pair_off = np.concatenate([[0], np.cumsum(n_pairs)]).astype(np.int64)
+    tot = int(n_views.sum())
+    out_R, out_t, status = np.zeros((tot, 9)), np.zeros((tot, 3)), np.zeros(len(arrays), np.int32)
+    with torch.cuda.device(dev):
+        _lib.context(dev).call("e2emv_mv_init_batch", len(arrays), _p(n_views), _p(init_R), _p(pair_off), _p(pair_ids), _p(pair_R), _p(pair_pos),
+                               _p(out_R), _p(out_t), _p(status), _lib.stream_ptr(dev))
+    E = np.tile(np.eye(4), (tot, 1, 1))
+    E[:, :3, :3] = out_R.reshape(tot, 3, 3).transpose(0, 2, 1)
+    E[:, :3, 3] = out_t
+    off = np.concatenate([[0], np.cumsum(n_views)])
+    return [E[off[k]:off[k + 1]].copy() for k in range(len(arrays))], status
+
+
 def initialize_bundle_adjust(n_images, data, result, file_path, conf_thresh=0., rel_pose_method="w8pt_ba"):
     """``initialize_bundle_adjust`` (bundle_adjust_io.py:62-191): matches of batch element 0 -> pairwise poses on the device
     (``rel_pose_method`` "w8pt_ba": w8pt + two-view BA; "ransac" / "ransac_ba": the RANSAC baseline, without / with two-view
@@ -493,15 +523,45 @@ def _tuple_ba_call(name, tuple_size, collected, counts, intr, kdim, nb, extrinsi
     del owner
 
 
-def solve_tuple_poses_batch(tuple_size, data, result, conf_thresh=0., timings=None):
+def _tuple_init_on_device(tuple_size, T_d, inl, count, min_matches=8, min_inliers=20):
+    """The initialisation stage on the device (``e2emv_mv_tuple_init``), enqueued behind the relative-pose stage on the current
+    stream: ``T_d`` [B*P,4,4] float32, ``inl`` [B*P,N] uint8, ``count`` [B*P] int32 device tensors -> ``(extrinsics [B,T,4,4],
+    counts [B*P] int32)`` on the host, brought back by ONE device-to-host copy (which is the only synchronisation).  The status
+    words stay on the device: a failed averaging is not raised on the host path either."""
+    dev = T_d.device
+    P = len(_pairs(tuple_size))
+    B = T_d.shape[0] // P
+    n_inl = inl.sum(1, dtype=torch.int32).contiguous()
+    extr = torch.empty((B, tuple_size * 16), dtype=torch.float64, device=dev)
+    status = torch.empty((B,), dtype=torch.int32, device=dev)
+    T_d, count = T_d.contiguous(), count.contiguous()
+    with torch.cuda.device(dev):
+        _lib.context(dev).call("e2emv_mv_tuple_init", B, tuple_size, _lib.ptr(T_d), _lib.ptr(n_inl), _lib.ptr(count), int(min_matches),
+                               int(min_inliers), _lib.ptr(extr), _lib.ptr(status), _lib.stream_ptr(dev))
+    packed = torch.cat([extr, count.reshape(B, P).double()], 1).cpu().numpy()
+    start = np.ascontiguousarray(packed[:, :tuple_size * 16]).reshape(B, tuple_size, 4, 4)
+    return start, np.ascontiguousarray(packed[:, tuple_size * 16:].astype(np.int32).reshape(-1))
+
+
+def _check_init(init):
+    if init not in ("host", "device"):
+        raise ValueError("init must be \"host\" or \"device\", not {!r}".format(init))
+
+
+def solve_tuple_poses_batch(tuple_size, data, result, conf_thresh=0., timings=None, init="host"):
     """``solve_tuple_poses`` for EVERY batch element of the matcher result, in memory: returns the refined world-to-camera
     extrinsics ``float64 [B, tuple_size, 4, 4]``, camera 0 the gauge.  Relative poses are "w8pt_ba" only here (the RANSAC
     methods stay on the CSV path: ``initialize_bundle_adjust(..., rel_pose_method=...)``).  Stages: matches collected on the
     device (one launch) -> w8pt + two-view BA of all B * T(T-1)/2 pairs -> one copy to the host, spanning tree and rotation /
     position averaging per tuple (``e2emv_mv_init``) -> all bundle-adjustment problems built on the device (one launch) and
     solved one workgroup per tuple (one launch).  No file, and no element's result depends on its batch neighbours.
-    ``timings``: optional dict that receives the wall time of each stage in seconds (synchronises after every stage)."""
+    ``timings``: optional dict that receives the wall time of each stage in seconds (synchronises after every stage).
+    ``init``: where the initialisation stage runs.  "host" (default): the loop above.  "device": ``e2emv_mv_tuple_init``, one
+    launch for the batch (one wave per tuple: spanning tree, chained start, averaging) enqueued behind the relative poses; match
+    counts and start extrinsics come back in one copy.  Same solver and options; the results agree to rounding (DESIGN.md
+    section 1), equal match counts of two pairs of a tuple are ordered by ascending (i, j) there and by scipy here."""
     import time
+    _check_init(init)
     pairs = _pairs(tuple_size)
     P = len(pairs)
     clock = [time.perf_counter()]
@@ -521,6 +581,14 @@ def solve_tuple_poses_batch(tuple_size, data, result, conf_thresh=0., timings=No
     intr, kdim, nb = _tuple_intrinsics(tuple_size, data, dev, B)
     per_pair = lambda side: torch.stack([intr[pr[side]].expand(B, kdim, kdim) for pr in pairs], 1).reshape(B * P, kdim, kdim).contiguous()  # noqa: E731
     T_d, inl = _w8pt_ba_on_device(dev, count, o0, o1, oc, per_pair(0), per_pair(1))
+    if init == "device":
+        lap("relative_poses")
+        start, counts = _tuple_init_on_device(tuple_size, T_d, inl, count)
+        lap("initialisation")
+        out, summary = np.zeros((B, tuple_size, 4, 4)), np.zeros((B, 4))
+        _tuple_ba_call("e2emv_mv_tuple_ba", tuple_size, collected, counts, intr, kdim, nb, start, 50, _p(out), _p(summary))
+        lap("build_and_bundle_adjust")
+        return out
     # one device -> host copy for the whole batch: poses, inlier counts, match counts
     packed = torch.cat([T_d.reshape(B * P, 16).double(), inl.sum(1, dtype=torch.int32).double()[:, None], count.double()[:, None]], 1).cpu().numpy()
     lap("relative_poses")
@@ -591,11 +659,11 @@ def eval_bundle_adjust(tuple_size, data, result, tmp_dir, pose_errors, verbose=F
     return pose_errors
 
 
-def eval_bundle_adjust_batch(tuple_size, data, result, pose_errors, verbose=False):
+def eval_bundle_adjust_batch(tuple_size, data, result, pose_errors, verbose=False, init="host"):
     """``eval_bundle_adjust`` for every batch element through ``solve_tuple_poses_batch``: extends ``pose_errors = [max errors,
     translation errors, rotation errors]`` by ``B * T(T-1)/2`` entries, batch element outer, pairs in ``_pairs`` order inside
-    (for ``B = 1`` the entries ``eval_bundle_adjust`` appends, in its order)."""
-    extrinsics = solve_tuple_poses_batch(tuple_size, data, result)
+    (for ``B = 1`` the entries ``eval_bundle_adjust`` appends, in its order).  ``init``: as in ``solve_tuple_poses_batch``."""
+    extrinsics = solve_tuple_poses_batch(tuple_size, data, result, init=init)
     poses = np.stack([data["pose" + str(v)].cpu().numpy() for v in range(tuple_size)], 1)  # [B,T,4,4]: one copy per image
     for b, E in enumerate(extrinsics):
         err_t, err_R = tuple_pose_errors(E, poses[b])

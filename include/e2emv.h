@@ -225,10 +225,12 @@ int e2emv_match_loss(e2emv_ctx* ctx, int B, int N, const float* d_logZ, const in
                      float* d_loss, void* stream);
 
 /* ---- multi-view pose back-end --------------------------------
- * HOST-side global initialisation = the reference's `ba_initializer` executable (bundle_adjustment/ba_init/src/
+ * Global initialisation = the reference's `ba_initializer` executable (bundle_adjustment/ba_init/src/
  * ba_init.cpp:10-90): robust rotation averaging (Chatterjee & Govindu 2013; L1 steps then IRLS) followed by
- * least-unsquared-deviation positions (Ozyesil & Singer 2015), both fp64 on the host like the reference (tiny
- * problems: <= 64 views).  All pointers are HOST memory, no context needed.  Rotations are COLUMN-major 3x3
+ * least-unsquared-deviation positions (Ozyesil & Singer 2015).  Two forms of the same solver: the four HOST entry
+ * points below (fp64 on one host thread like the reference, <= 64 views, behind the CSV path) and, further down, the
+ * DEVICE form for a batch of problems (e2emv_mv_init_batch, e2emv_mv_tuple_init: one wave per problem, <= 8 views).
+ * Host form: all pointers are HOST memory, no context needed.  Rotations are COLUMN-major 3x3
  * (the CSV order), world -> camera; pair e = (id0, id1) carries R_021 and the position of camera id1 in the frame of
  * camera id0 (ba_init.cpp:30-50).  View 0 is the gauge.  out_t = -R * position (ba_init.cpp:65).
  * *status: bit 1 = rotation averaging failed, bit 2 = position estimation failed (results then = best so far).      */
@@ -302,6 +304,32 @@ int e2emv_mv_tuple_problem(e2emv_ctx* ctx, int B, int T, int N, const int32_t* c
                            const float* d_mkpts1, const float* d_mconf, const float* const* d_intr, int kdim, int intr_batch,
                            const double* extr, int32_t* cam_idx, int32_t* pt_idx, double* obs_xy, double* obs_w, double* cams,
                            double* pts, void* stream);
+
+/* The global initialisation on the DEVICE (csrc/mvinit_device.hip): the solver of e2emv_mv_init with the same options,
+ * fp64, one wave per problem, the problem and its working set in LDS; a problem's result depends on neither its
+ * neighbours nor its position in the batch (bit for bit), and agrees with the host form to rounding (summation orders
+ * differ).  n_problems problems in the array form of e2emv_mv_init, HOST pointers, concatenated, one launch, synchronous:
+ * problem k has n_views[k] views (1..E2EMV_MAX_TUPLE; its rows of init_R / out_R [.,9] column-major and out_t [.,3]
+ * follow those of problem k - 1) and the pairs pair_off[k] .. pair_off[k+1] (at most 28, each unordered pair of views at
+ * most once) of pair_ids [.,2] / pair_R [.,9] / pair_pos [.,3]; ids count from 0 inside their problem.  status
+ * [n_problems] as *status of e2emv_mv_init (may be NULL).  A problem without pairs returns its initial rotations and zero
+ * translations.  E2EMV_EINVAL: n_views outside 1..8, an id outside its problem or i == j, a repeated pair, a NULL array,
+ * offsets that decrease or do not start at 0.                                                                          */
+int e2emv_mv_init_batch(e2emv_ctx* ctx, int n_problems, const int32_t* n_views, const double* init_R, const int64_t* pair_off,
+                        const int32_t* pair_ids, const double* pair_R, const double* pair_pos, double* out_R, double* out_t,
+                        int32_t* status, void* stream);
+/* The whole initialisation stage of the batched path for B tuples of T images (2..E2EMV_MAX_TUPLE) on DEVICE buffers,
+ * one launch, no host synchronisation: d_rel_T [B*P,16] fp32 row-major 4x4 relative poses (the output of the w8pt +
+ * two-view-BA stage), d_n_inliers, d_count [B*P] int32, pair order as in e2emv_mv_collect.  Per tuple: pairs with count >=
+ * min_matches are edges weighted by their count; camera-to-world poses are chained from image 0 along the maximum spanning
+ * tree (Kruskal in descending weight; EQUAL weights in ascending row-major (i, j) - this library's rule, other spanning
+ * tree codes order ties differently) with pose_j = pose_i inv(T_ij), pose_i = pose_j T_ij, every inverse a real fp64
+ * matrix inverse (the fp32 rotation blocks are orthonormal to 1e-7 only); the initial rotations are those of the inverted
+ * chained poses, the identity for images not reached from image 0; the pairs with n_inliers >= min_inliers or on the tree
+ * enter the solver with R_ij and the position -R_ij^T t_ij.  d_extr [B,T,16] fp64 row-major world -> camera, camera 0 the
+ * gauge; d_status [B] int32 as *status of e2emv_mv_init.                                                                */
+int e2emv_mv_tuple_init(e2emv_ctx* ctx, int B, int T, const float* d_rel_T, const int32_t* d_n_inliers, const int32_t* d_count,
+                        int min_matches, int min_inliers, double* d_extr, int32_t* d_status, void* stream);
 
 /* ---- RANSAC essential matrix (SuperGlue's estimate_pose: OpenCV findEssentialMat(RANSAC) + recoverPose) ------------
  * A ragged batch of P problems in one call, no host synchronisation inside: problem p uses its first d_n_per[p]

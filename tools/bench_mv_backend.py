@@ -4,9 +4,12 @@ result.  Default shape: 8 tuples of 5 images at 1024 keypoints (configs[3] of BA
 in tests/test_gpu_multi_view_flow.py.  One warm-up call of each path, then --reps timed calls of each, alternating; every timed
 window ends with a device synchronise.  Prints one JSON line: median / min / max of both paths in milliseconds, the per-stage
 split of the batched path (medians of a separate set of calls that synchronise after every stage) and the largest difference
-between the two paths' extrinsics.
+between the two paths' extrinsics.  ``--init`` selects where the batched path runs its initialisation stage: ``host`` (the loop
+over ``e2emv_mv_init``), ``device`` (``e2emv_mv_tuple_init``, one launch) or ``both`` (default): both batched forms are then
+timed inside the same repetition loop, alternating, and the line also carries the device form's figures and the largest
+difference between the two forms' extrinsics.
 
-    python tools/bench_mv_backend.py [--batch 8] [--tuple-size 5] [--kpts 1024] [--reps 7]
+    python tools/bench_mv_backend.py [--batch 8] [--tuple-size 5] [--kpts 1024] [--reps 7] [--init host|device|both]
 """
 import argparse
 import json
@@ -29,6 +32,7 @@ def main():
     ap.add_argument("--tuple-size", type=int, default=5)
     ap.add_argument("--kpts", type=int, default=1024)
     ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--init", choices=("host", "device", "both"), default="both")
     args = ap.parse_args()
     B, T = args.batch, args.tuple_size
     gpu = torch.device("cuda", 0)
@@ -46,8 +50,10 @@ def main():
         def csv_path():
             return np.stack([multi_view.solve_tuple_poses(T, d, r, os.path.join(tmp, str(b))) for b, (d, r) in enumerate(slices)])
 
-        def batched(timings=None):
-            return multi_view.solve_tuple_poses_batch(T, dev, result, timings=timings)
+        forms = ("host", "device") if args.init == "both" else (args.init,)
+
+        def batched(init, timings=None):
+            return multi_view.solve_tuple_poses_batch(T, dev, result, timings=timings, init=init)
 
         def timed(fn):
             torch.cuda.synchronize()
@@ -56,21 +62,31 @@ def main():
             torch.cuda.synchronize()
             return (time.perf_counter() - t0) * 1e3, out
 
-        e_csv, e_batch = csv_path(), batched()  # warm-up (workspace growth, lazy module loads)
-        t_csv, t_batch = [], []
+        e_csv = csv_path()  # warm-up (workspace growth, lazy module loads)
+        e_batch = {f: batched(f) for f in forms}
+        t_csv, t_batch = [], {f: [] for f in forms}
         for _ in range(args.reps):
             t_csv.append(timed(csv_path)[0])
-            t_batch.append(timed(batched)[0])
-        stages = {}
+            for f in forms:
+                t_batch[f].append(timed(lambda: batched(f))[0])
+        stages = {f: {} for f in forms}
         for _ in range(args.reps):
-            tm = {}
-            batched(tm)
-            for k, v in tm.items():
-                stages.setdefault(k, []).append(v * 1e3)
+            for f in forms:
+                tm = {}
+                batched(f, tm)
+                for k, v in tm.items():
+                    stages[f].setdefault(k, []).append(v * 1e3)
     stat = lambda ts: {"median": float(np.median(ts)), "min": float(np.min(ts)), "max": float(np.max(ts))}  # noqa: E731
-    print(json.dumps({"batch": B, "tuple_size": T, "n_kpts": args.kpts, "reps": args.reps, "csv_path_ms": stat(t_csv),
-                      "batched_path_ms": stat(t_batch), "batched_stage_ms": {k: float(np.median(v)) for k, v in stages.items()},
-                      "max_abs_extrinsics_difference": float(np.abs(e_csv - e_batch).max())}), flush=True)
+    first = forms[0]  # the form the unsuffixed keys describe: the host form unless --init device
+    line = {"batch": B, "tuple_size": T, "n_kpts": args.kpts, "reps": args.reps, "init": args.init, "csv_path_ms": stat(t_csv),
+            "batched_path_ms": stat(t_batch[first]), "batched_stage_ms": {k: float(np.median(v)) for k, v in stages[first].items()},
+            "max_abs_extrinsics_difference": float(np.abs(e_csv - e_batch[first]).max())}
+    if args.init == "both":
+        line["batched_path_device_init_ms"] = stat(t_batch["device"])
+        line["batched_stage_device_init_ms"] = {k: float(np.median(v)) for k, v in stages["device"].items()}
+        line["initialisation_stage_ms"] = {f: stat(stages[f]["initialisation"]) for f in forms}
+        line["max_abs_extrinsics_difference_device_vs_host"] = float(np.abs(e_batch["device"] - e_batch["host"]).max())
+    print(json.dumps(line), flush=True)
 
 
 if __name__ == "__main__":
