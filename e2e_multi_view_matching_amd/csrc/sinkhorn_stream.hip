@@ -234,7 +234,9 @@ __global__ __launch_bounds__(256) void sinkhorn_sweep(SkParams p) {
                 }
                 if (lane == 0) {
                     p.max0[(int64_t)b * p.M + row] = best;
-                    p.idx0[(int64_t)b * p.M + row] = bj;
+                    // no element compared greater than -inf (a row of -inf or NaN): index 0, as torch.max gives; match_finalize
+                    // indexes its LDS arrays with this value
+                    p.idx0[(int64_t)b * p.M + row] = bj == 0x7fffffff ? 0 : bj;
                 }
             }
         }
@@ -445,7 +447,7 @@ __global__ __launch_bounds__(256) void dense_row_argmax(const float* Z, int M, i
         int oj = __shfl_xor(bj, o);
         if (ob > best || (ob == best && oj < bj)) { best = ob; bj = oj; }
     }
-    if (lane == 0) { max0[(int64_t)b * M + row] = best; idx0[(int64_t)b * M + row] = bj; }
+    if (lane == 0) { max0[(int64_t)b * M + row] = best; idx0[(int64_t)b * M + row] = bj == 0x7fffffff ? 0 : bj; }  // as in the final sweep
 }
 __global__ __launch_bounds__(256) void dense_col_argmax(const float* Z, int M, int N, int* idx1) {
     const int b = blockIdx.y, j = blockIdx.x * 256 + threadIdx.x;

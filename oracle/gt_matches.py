@@ -19,9 +19,10 @@ def transform_kpts(kpts, d, K0, K1, T_021):
     return depth, p[..., :2, 0] / depth
 
 
-def compute_gt_matches_of_image_pair(kpts0, kpts1, K0, K1, T0to1, depth0, depth1, max_matched_reproj_err,
-                                     min_unmatched_reproj_err):
-    """helpers.py:121-203 -> (indices [B,2,N+1] int64, weights [B,2,N+1] f32)."""
+def reprojection_errors(kpts0, kpts1, K0, K1, T0to1, depth0, depth1):
+    """helpers.py:124-138, the quantities every decision of the builder is taken on: the mean bidirectional reprojection
+    error err [B,N0,N1] of the truncated keypoints, their depths d0 / d1 [B,N,1] and the depths dep01 / dep10 [B,N,1] of
+    the reprojected keypoints in the other image.  In the dtype of the inputs (fp32 as the reference, or fp64)."""
     bs, n, _ = kpts0.shape
     bidx = torch.arange(bs).unsqueeze(-1).expand(bs, n)
     k0, k1 = kpts0.long(), kpts1.long()
@@ -32,7 +33,41 @@ def compute_gt_matches_of_image_pair(kpts0, kpts1, K0, K1, T0to1, depth0, depth1
     dep10, k1to0 = transform_kpts(k1, d1, K1u, K0u, torch.linalg.inv(Tu))
     err = torch.sqrt(((k1to0.unsqueeze(2) - k0.unsqueeze(1)) ** 2).sum(3)).transpose(1, 2)
     err = err + torch.sqrt(((k0to1.unsqueeze(2) - k1.unsqueeze(1)) ** 2).sum(3))
-    err = err / 2.0  # [B, N0, N1]
+    return err / 2.0, d0, d1, dep01, dep10
+
+
+def decision_margins(kpts0, kpts1, K0, K1, T0to1, depth0, depth1, max_matched_reproj_err, min_unmatched_reproj_err):
+    """How far every row (keypoint of image 0) and column (keypoint of image 1) of the builder sits from each of its decision
+    boundaries, in the dtype of the inputs (tests call it in fp64).  -> dict of
+      row_min / col_min [B,N] the arg-min partners,
+      row_thr / col_thr [B,N] distance of the selected (minimal) error from the nearer of the two thresholds,
+      row_gap / col_gap [B,N] second-smallest minus smallest error (0 on an exact tie),
+      row_rel [B,N] distance of the nearer of the two relative depths of (i, row_min[i]) from 0.1.
+    Entries that are not finite (a keypoint without depth) stay inf / NaN: such a row has no margin to speak of."""
+    err, d0, d1, dep01, dep10 = reprojection_errors(kpts0, kpts1, K0, K1, T0to1, depth0, depth1)
+    bs, n, _ = err.shape
+    bidx = torch.arange(bs).unsqueeze(-1).expand(bs, n)
+    out = {}
+    for name, dim in (("row", 2), ("col", 1)):
+        two = torch.topk(err, min(2, n), dim=dim, largest=False).values.movedim(dim, -1)
+        out[name + "_min"] = torch.argmin(err, dim=dim)
+        emin = two[..., 0]
+        out[name + "_thr"] = torch.minimum((emin - max_matched_reproj_err).abs(), (emin - min_unmatched_reproj_err).abs())
+        out[name + "_gap"] = two[..., 1] - emin if n > 1 else torch.full_like(emin, float("inf"))
+    i1s = out["row_min"]
+    d0s, md1 = d0.squeeze(-1), d1.squeeze(-1)[bidx, i1s]
+    rel01 = (dep01.squeeze(-1) - md1).abs() / md1
+    rel10 = (dep10.squeeze(-1)[bidx, i1s] - d0s).abs() / d0s
+    out["row_rel"] = torch.minimum((rel01 - 0.1).abs(), (rel10 - 0.1).abs())
+    return out
+
+
+def compute_gt_matches_of_image_pair(kpts0, kpts1, K0, K1, T0to1, depth0, depth1, max_matched_reproj_err,
+                                     min_unmatched_reproj_err):
+    """helpers.py:121-203 -> (indices [B,2,N+1] int64, weights [B,2,N+1] f32)."""
+    bs, n, _ = kpts0.shape
+    bidx = torch.arange(bs).unsqueeze(-1).expand(bs, n)
+    err, d0, d1, dep01, dep10 = reprojection_errors(kpts0, kpts1, K0, K1, T0to1, depth0, depth1)
     row_min, col_min = torch.argmin(err, dim=2), torch.argmin(err, dim=1)
     idx0 = torch.full((bs, n + 1), -1, dtype=torch.int64)
     idx1 = torch.full((bs, n + 1), -1, dtype=torch.int64)
