@@ -5,7 +5,7 @@
 // the tuple (N_src = (T-1) N; T = 2 is upstream SuperGlue's swap).
 //
 // Layout: qkv [n_img][n_rows][3D], channels head-major (c = h*64 + dd; the upstream order
-// c = dd*H + h is undone on the weights at load time, ctx.hip), image g = b*T + t.
+// c = dd*H + h is undone on the weights at load time, weights.hip), image g = b*T + t.
 //
 // Per workgroup: one (image, head, 128-query tile); 4 waves x 32 queries.  Everything is
 // computed TRANSPOSED so that each lane owns ONE query (q = lane & 31) for its whole life:

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/e2emv.h"
+#include "weights.h"
 
 namespace e2emv {
 
@@ -38,36 +39,6 @@ enum ProfSlot {
     PS_GEMM_MLP1,
     PS_GEMM_CHAIN,
     PS_COUNT
-};
-
-struct HostTensor {
-    std::vector<float> data;
-    std::vector<int64_t> shape;
-};
-
-struct LayerWeights {
-    // all device pointers into the weight arena; GEMM weights are [out][in] row-major
-    float* w_qkv = nullptr;   // [3D][D]   rows head-major: q | k | v
-    float* b_qkv = nullptr;   // [3D]
-    float* w_mlp0 = nullptr;  // [2D][2D]  BN folded
-    float* b_mlp0 = nullptr;
-    float* w_mlp1 = nullptr;  // [D][2D]
-    float* b_mlp1 = nullptr;
-    int type = 0;             // 0 self, 1 cross
-    // bf16x3 planes ("S3": [out][3][in]) of the three big GEMMs
-    uint16_t* w3_qkv = nullptr;
-    uint16_t* w3_mlp0 = nullptr;
-    uint16_t* w3_mlp1 = nullptr;
-    // f16x2 planes ([out][{hi, lo}][in] of 2^s W, gemm_h2.hip) of the same GEMMs and their 2^-s
-    uint16_t* wh_qkv = nullptr;
-    uint16_t* wh_mlp0 = nullptr;
-    uint16_t* wh_mlp1 = nullptr;
-    float hs_qkv = 0.f, hs_mlp0 = 0.f, hs_mlp1 = 0.f;
-    // the same 2^s W as P2 planes (p2.h: 32-column blocks of {hi, lo}) for gemm_p2.hip; the scales are hs_* above
-    uint16_t* wp_qkv = nullptr;
-    uint16_t* wp_mlp0 = nullptr;
-    uint16_t* wp_mlp1 = nullptr;
-    float ba_qkv = 0.f, ba_mlp0 = 0.f, ba_mlp1 = 0.f;  // max |bias| of the three GEMMs (bounds for the tile exponents, p2.h)
 };
 
 // Family timing as a CHAIN of events on the launch stream: one event where the family changes (it ends the previous
@@ -101,24 +72,14 @@ struct e2emv_ctx {
     bool attn_key_split = true;  // attention_p2w: a half-empty last round of workgroups is split along the keys (attention_p2w.hip)
     int attn_p2_nw = 0;      // attention on planes: 0 = by key count, 4 | 8 = attention_p2 with that many waves, 1 = attention_p2w (micro-benchmarks)
     // keypoint encoder: layer 0 (3->c0) used by the ingest kernel, the rest through the GEMM
-    float* kenc_w0 = nullptr;  // [c0][3] folded
-    float* kenc_b0 = nullptr;  // [c0]
-    std::vector<float*> kenc_w, kenc_b;  // layers 1..n (folded), [out][in]
-    std::vector<const uint16_t*> kenc_wh;  // the same layers as fp16 x 2 weight planes (null: fan-in < 128, stays on the fp32 kernel)
-    std::vector<float> kenc_hs;
-    const uint16_t* wh_final = nullptr;  // final_proj / conf_mlp.0 as fp16 x 2 weight planes
-    const uint16_t* wh_conf0 = nullptr;
-    const uint16_t* wp_final = nullptr;  // ... and in the plane kernels' weight format (gemm_p2)
-    const uint16_t* wp_conf0 = nullptr;
-    float hs_final = 0.f, hs_conf0 = 0.f, ba_final = 0.f, ba_conf0 = 0.f;
+    const float* kenc_w0 = nullptr;  // [c0][3] folded
+    const float* kenc_b0 = nullptr;  // [c0]
+    std::vector<e2emv::DenseWeights> kenc;  // layers 1..n (folded); fp16 x 2 planes where fan-in >= 128, the others stay on the fp32 kernel
     std::vector<int> kenc_dims;          // [3, c0, c1, ..., D]
     std::vector<e2emv::LayerWeights> layers;
-    float* w_final = nullptr;
-    float* b_final = nullptr;
+    e2emv::DenseWeights final_proj, conf0;  // final_proj, conf_mlp.0 ([D][2D] folded; null without conf_mlp): fp16 x 2 and P2 planes
     float bin_score = 1.f;
-    float* w_conf0 = nullptr;  // [D][2D] folded
-    float* b_conf0 = nullptr;
-    float* w_conf1 = nullptr;  // [D]
+    const float* w_conf1 = nullptr;  // conf_mlp.3 [D]
     float b_conf1 = 0.f;
     // SuperPoint front-end (superpoint.hip): packed conv weights [Cout][ky][kx][Cin] + biases
     bool sp_committed = false;
@@ -253,8 +214,6 @@ int launch_attention(e2emv_ctx* ctx, int B, int T, int n_rows, const int* n_vali
 // ---- bf16x3 split-operand path (gemm3.hip / gemm_x3.hip / attention3.hip): fp32-class accuracy on the bf16 pipe ----
 // "S3" = matrix stored as three bf16 planes per row: row r = [plane0 | plane1 | plane2], each ld wide.
 // gemm_x3.hip: fp32 activations (a.A / a.A2, a.bias, a.R, a.C, a.relu as for launch_gemm_nt) x pre-split weights W3 (S3 [N][3][ldw3])
-// host: fp32 weights -> the f16x2 planes appended to `out` (offset returned), *out_scale = 2^-s (ctx.hip)
-size_t add_split_h2(std::vector<uint16_t>& out, const std::vector<float>& w, int rows, int cols, float* out_scale);
 // h2_out_scale != 0 selects the fp16 x 2 form (gemm_h2.hip): W3 = fp16 planes [N][{hi, lo}][ldw3] of 2^s W, h2_out_scale = 2^-s
 int launch_gemm_h2(e2emv_ctx* ctx, const GemmArgs& a, const uint16_t* WH, int64_t ldw, float out_scale, hipStream_t s);
 int launch_gemm_x3(e2emv_ctx* ctx, const GemmArgs& a, const uint16_t* W3, int64_t ldw3, hipStream_t s, float h2_out_scale = 0.f);

@@ -228,13 +228,26 @@ static int plan_forward(e2emv_ctx* ctx, const e2emv_forward_desc* fd, FwdPlan& p
     return E2EMV_OK;
 }
 
-// A GEMM on fp32 activations in the plan's arithmetic (profile slot "gemm").  g.W are the fp32 weights, wh (2^s W as fp16 x 2
-// planes, hs = 2^-s) and w3 (bf16x3 planes) the same weights, [N][K]; where the mode's form is null the fp32 kernel runs.
-static int gemm_fp32_act(e2emv_ctx* ctx, const FwdPlan& p, const GemmArgs& g, const uint16_t* wh, float hs, const uint16_t* w3, hipStream_t s) {
+// The weight side of a GEMM over M rows with the dense layer w, one K segment: on fp32 activations ...
+static GemmArgs dense_gemm(const DenseWeights& w, int M) {
+    GemmArgs g;
+    g.M = M; g.N = w.out; g.K = w.in; g.K1 = w.in; g.W = w.w; g.ldw = w.in; g.bias = w.b;
+    return g;
+}
+// ... and on planes
+static GemmP2Args dense_gemm_p2(const DenseWeights& w, int M) {
+    GemmP2Args g;
+    g.M = M; g.N = w.out; g.K = w.in; g.K1 = w.in; g.W = w.wp; g.out_scale = w.hs; g.bias = w.b; g.bias_amax = w.ba;
+    return g;
+}
+
+// A GEMM on fp32 activations in the plan's arithmetic (profile slot "gemm"); g = dense_gemm(w) and the activation side.  Where
+// the mode's form of the weights is null the fp32 kernel runs.
+static int gemm_fp32_act(e2emv_ctx* ctx, const FwdPlan& p, const GemmArgs& g, const DenseWeights& w, hipStream_t s) {
     prof_begin(ctx, PS_GEMM, s);
     int rc;
-    if (p.f16x2() && wh) rc = launch_gemm_x3(ctx, g, wh, g.K, s, hs);
-    else if (p.mode == FwdMode::BF16X3 && w3) rc = launch_gemm_x3(ctx, g, w3, g.K, s);
+    if (p.f16x2() && w.wh) rc = launch_gemm_x3(ctx, g, w.wh, g.K, s, w.hs);
+    else if (p.mode == FwdMode::BF16X3 && w.w3) rc = launch_gemm_x3(ctx, g, w.w3, g.K, s);
     else rc = launch_gemm_nt(ctx, g, s);
     prof_end(ctx, s);
     return rc;
@@ -263,22 +276,18 @@ static int encode(e2emv_ctx* ctx, const FwdPlan& p, const e2emv_forward_desc* fd
 
     float* cur = p.hid;  // [Mtot][c0]
     float* nxt = p.hid + p.Mtot * c0;
-    const int nl = (int)ctx->kenc_w.size();
-    for (int i = 0; i < nl; ++i) {
-        const int cin = kd[i + 1], cout = kd[i + 2];
-        const bool last = i == nl - 1;
-        GemmArgs g;
-        g.M = (int)p.Mtot; g.N = cout; g.K = cin; g.K1 = cin;
-        g.A = cur; g.lda = cin;
-        g.W = ctx->kenc_w[i]; g.ldw = cin; g.bias = ctx->kenc_b[i];
+    for (const DenseWeights& w : ctx->kenc) {
+        const bool last = &w == &ctx->kenc.back();
+        GemmArgs g = dense_gemm(w, (int)p.Mtot);
+        g.A = cur; g.lda = w.in;
         g.relu = !last;
         if (last) { g.R = p.x; g.ldr = p.D; g.C = p.x; g.ldc = p.D; }
-        else { g.C = nxt; g.ldc = cout; }
+        else { g.C = nxt; g.ldc = w.out; }
         // no bf16x3 planes; f16x2 mode: the wide layers (fan-in >= 128) on the fp16 x 2 kernel as well - same parity bar, 3x less
         // matrix-core time
-        if (int rc = gemm_fp32_act(ctx, p, g, ctx->kenc_wh[i], ctx->kenc_hs[i], nullptr, s)) return rc;
+        if (int rc = gemm_fp32_act(ctx, p, g, w, s)) return rc;
         cur = nxt;
-        nxt = nxt + p.Mtot * cout;
+        nxt = nxt + p.Mtot * w.out;
     }
     return E2EMV_OK;
 }
@@ -288,11 +297,10 @@ static int gnn_fp32_activations(e2emv_ctx* ctx, const FwdPlan& p, hipStream_t s)
     const int D = p.D, M = (int)p.Mtot;
     for (const LayerWeights& L : ctx->layers) {
         // q|k|v = x Wqkv^T + b; the split modes' attention kernels split Q / K / V^T into planes on the way in
-        GemmArgs g;
-        g.M = M; g.N = 3 * D; g.K = D; g.K1 = D; g.A = p.x; g.lda = D; g.W = L.w_qkv; g.ldw = D; g.bias = L.b_qkv;
-        g.C = p.qkv; g.ldc = 3 * D;
+        GemmArgs g = dense_gemm(L.qkv, M);
+        g.A = p.x; g.lda = D; g.C = p.qkv; g.ldc = 3 * D;
         int rc;
-        if ((rc = gemm_fp32_act(ctx, p, g, L.wh_qkv, L.hs_qkv, L.w3_qkv, s))) return rc;
+        if ((rc = gemm_fp32_act(ctx, p, g, L.qkv, s))) return rc;
         prof_begin(ctx, PS_ATTN, s);
         if (p.mode == FwdMode::F32) rc = launch_attention(ctx, p.B, p.T, p.n_rows, p.Nt, D, p.H, p.qkv, L.type, p.att, s);
         else rc = launch_attention3f(ctx, p.B, p.T, p.n_rows, p.Nt, D, p.H, p.qkv, L.type, p.att, s, p.mode == FwdMode::F16X2);
@@ -300,23 +308,20 @@ static int gnn_fp32_activations(e2emv_ctx* ctx, const FwdPlan& p, hipStream_t s)
         if (rc) return rc;
         // hidden = relu(BN(W0 [x | message] + b0))   (concat never materialised: two K segments; the second is the attention
         // output, the merge conv folded into W0)
-        g = GemmArgs();
-        g.M = M; g.N = 2 * D; g.K = 2 * D; g.K1 = D; g.A = p.x; g.lda = D; g.A2 = p.att; g.lda2 = D;
-        g.W = L.w_mlp0; g.ldw = 2 * D; g.bias = L.b_mlp0; g.relu = true; g.C = p.hid; g.ldc = 2 * D;
-        if ((rc = gemm_fp32_act(ctx, p, g, L.wh_mlp0, L.hs_mlp0, L.w3_mlp0, s))) return rc;
+        g = dense_gemm(L.mlp0, M);
+        g.K1 = D; g.A = p.x; g.lda = D; g.A2 = p.att; g.lda2 = D; g.relu = true; g.C = p.hid; g.ldc = 2 * D;
+        if ((rc = gemm_fp32_act(ctx, p, g, L.mlp0, s))) return rc;
         // x += W1 hidden + b1
-        g = GemmArgs();
-        g.M = M; g.N = D; g.K = 2 * D; g.K1 = 2 * D; g.A = p.hid; g.lda = 2 * D; g.W = L.w_mlp1; g.ldw = 2 * D;
-        g.bias = L.b_mlp1; g.R = p.x; g.ldr = D; g.C = p.x; g.ldc = D;
-        if ((rc = gemm_fp32_act(ctx, p, g, L.wh_mlp1, L.hs_mlp1, L.w3_mlp1, s))) return rc;
+        g = dense_gemm(L.mlp1, M);
+        g.A = p.hid; g.lda = 2 * D; g.R = p.x; g.ldr = D; g.C = p.x; g.ldc = D;
+        if ((rc = gemm_fp32_act(ctx, p, g, L.mlp1, s))) return rc;
     }
-    GemmArgs g;  // (no bf16x3 planes of final_proj)
-    g.M = M; g.N = D; g.K = D; g.K1 = D; g.A = p.x; g.lda = D; g.W = ctx->w_final; g.ldw = D; g.bias = ctx->b_final;
-    g.C = p.att; g.ldc = D;
-    return gemm_fp32_act(ctx, p, g, ctx->wh_final, ctx->hs_final, nullptr, s);
+    GemmArgs g = dense_gemm(ctx->final_proj, M);  // (no bf16x3 planes of final_proj)
+    g.A = p.x; g.lda = D; g.C = p.att; g.ldc = D;
+    return gemm_fp32_act(ctx, p, g, ctx->final_proj, s);
 }
 
-// F16X2_PLANES: x to planes, the GNN layers - a launch per GEMM or chained - and final_proj on planes (D = 256: wp_final exists)
+// F16X2_PLANES: x to planes, the GNN layers - a launch per GEMM or chained - and final_proj on planes
 static int gnn_planes(e2emv_ctx* ctx, const FwdPlan& p, hipStream_t s) {
     const int D = p.D, H = p.H, M = (int)p.Mtot;
     uint16_t* xp = (uint16_t*)p.msg;       // x as scaled planes (msg is free until the conf head)
@@ -331,16 +336,14 @@ static int gnn_planes(e2emv_ctx* ctx, const FwdPlan& p, hipStream_t s) {
     prof_end(ctx, s);
     if (rc) return rc;
     auto qkv_args = [&](const LayerWeights& L) {
-        GemmP2Args q;
-        q.M = M; q.N = 3 * D; q.K = D; q.K1 = D; q.A = xp; q.lda = D; q.W = L.wp_qkv; q.out_scale = L.hs_qkv; q.bias = L.b_qkv;
-        q.out = P2_OUT_QKV; q.Cp = qkp; q.Vt = vtp; q.n_rows = p.n_rows; q.heads = H;
-        q.EA = p.e_x; q.EC = p.e_qk; q.EVt = p.e_vt; q.bias_amax = L.ba_qkv;
+        GemmP2Args q = dense_gemm_p2(L.qkv, M);
+        q.A = xp; q.lda = D; q.out = P2_OUT_QKV; q.Cp = qkp; q.Vt = vtp; q.n_rows = p.n_rows; q.heads = H;
+        q.EA = p.e_x; q.EC = p.e_qk; q.EVt = p.e_vt;
         return q;
     };
     // final_proj: x arrives as planes with their tile exponents, any magnitude fp32 holds is fine
-    GemmP2Args fin;
-    fin.M = M; fin.N = D; fin.K = D; fin.K1 = D; fin.A = xp; fin.lda = D; fin.W = ctx->wp_final; fin.out_scale = ctx->hs_final;
-    fin.bias = ctx->b_final; fin.out = P2_OUT_F32; fin.C32 = p.att; fin.ldc = D; fin.EA = p.e_x; fin.bias_amax = ctx->ba_final;
+    GemmP2Args fin = dense_gemm_p2(ctx->final_proj, M);
+    fin.A = xp; fin.lda = D; fin.out = P2_OUT_F32; fin.C32 = p.att; fin.ldc = D; fin.EA = p.e_x;
     for (size_t l = 0; l < ctx->layers.size(); ++l) {
         const LayerWeights& L = ctx->layers[l];
         if (!p.chain || l == 0) {  // (chained: the chain of layer l - 1 made this layer's q | k | v)
@@ -352,15 +355,13 @@ static int gnn_planes(e2emv_ctx* ctx, const FwdPlan& p, hipStream_t s) {
         prof_end(ctx, s);
         if (rc) return rc;
         // hidden = relu(W0 [x | attention] + b0)   (merge folded into W0, BN folded)
-        GemmP2Args m0;
-        m0.M = M; m0.N = 2 * D; m0.K = 2 * D; m0.K1 = D; m0.A = xp; m0.lda = D; m0.A2 = attp; m0.lda2 = D;
-        m0.W = L.wp_mlp0; m0.out_scale = L.hs_mlp0; m0.bias = L.b_mlp0; m0.relu = true; m0.out = P2_OUT_PLANES; m0.Cp = hidp; m0.ldc = 2 * D;
-        m0.EA = p.e_x; m0.EA2 = p.e_att; m0.EC = p.e_hid; m0.bias_amax = L.ba_mlp0;
+        GemmP2Args m0 = dense_gemm_p2(L.mlp0, M);
+        m0.K1 = D; m0.A = xp; m0.lda = D; m0.A2 = attp; m0.lda2 = D; m0.relu = true; m0.out = P2_OUT_PLANES; m0.Cp = hidp; m0.ldc = 2 * D;
+        m0.EA = p.e_x; m0.EA2 = p.e_att; m0.EC = p.e_hid;
         // x += W1 hidden + b1
-        GemmP2Args m1;
-        m1.M = M; m1.N = D; m1.K = 2 * D; m1.K1 = 2 * D; m1.A = hidp; m1.lda = 2 * D; m1.Rp = xp; m1.ldr = D;
-        m1.W = L.wp_mlp1; m1.out_scale = L.hs_mlp1; m1.bias = L.b_mlp1; m1.out = P2_OUT_PLANES; m1.Cp = xp; m1.ldc = D;
-        m1.EA = p.e_hid; m1.ER = p.e_x; m1.AR = p.a_x; m1.EC = p.e_x; m1.AC = p.a_x; m1.bias_amax = L.ba_mlp1;
+        GemmP2Args m1 = dense_gemm_p2(L.mlp1, M);
+        m1.A = hidp; m1.lda = 2 * D; m1.Rp = xp; m1.ldr = D; m1.out = P2_OUT_PLANES; m1.Cp = xp; m1.ldc = D;
+        m1.EA = p.e_hid; m1.ER = p.e_x; m1.AR = p.a_x; m1.EC = p.e_x; m1.AC = p.a_x;
         if (p.chain) {
             const GemmP2Args st[3] = {m0, m1, l + 1 == ctx->layers.size() ? fin : qkv_args(ctx->layers[l + 1])};
             // MLP1's K steps 8 .. 15 read the hidden columns MLP0's SECOND tile stores right in front of it; q | k | v and
@@ -436,6 +437,7 @@ static int conf_heads(e2emv_ctx* ctx, const FwdPlan& p, const SinkhornOut& so, f
     const int B = p.B, D = p.D, n_rows = p.n_rows;
     const int64_t tuple_stride = (int64_t)p.T * n_rows * D;
     const bool use_mlp = ctx->model.conf_mlp != 0;
+    const DenseWeights& c0 = ctx->conf0;
     float* gathered = p.msg;  // [B][n_rows][D] ([B][n_rows][2D] in the f16x2 modes)
     float* chid = p.hid;      // [B][n_rows][D]
     int rc;
@@ -446,7 +448,7 @@ static int conf_heads(e2emv_ctx* ctx, const FwdPlan& p, const SinkhornOut& so, f
             const int Ni = p.Nt[i];
             const float* mdesc_i = p.att + (int64_t)i * n_rows * D;
             const float* mdesc_j = p.att + (int64_t)j * n_rows * D;
-            if (use_mlp && p.mode == FwdMode::F16X2_PLANES && ctx->wp_conf0) {
+            if (use_mlp && p.mode == FwdMode::F16X2_PLANES && c0.wp) {
                 // plane kernels: [mdesc_i | mdesc_j(match)] -> planes with tile exponents -> conf_mlp.0 (+ BN, ReLU) on gemm_p2
                 // (one pass: the gather is resolved in the source address of the plane conversion - p2_tools.hip)
                 uint16_t* feat = (uint16_t*)p.qkv;  // [B * n_rows][2D]
@@ -454,32 +456,29 @@ static int conf_heads(e2emv_ctx* ctx, const FwdPlan& p, const SinkhornOut& so, f
                 rc = launch_conf_gather_planes(ctx, mdesc_i, mdesc_j, tuple_stride, so.m0[pidx], Ni, n_rows, B, D, feat, p.e_hid, s);
                 prof_end(ctx, s);
                 if (rc) return rc;
-                GemmP2Args q;
-                q.M = B * n_rows; q.N = D; q.K = 2 * D; q.K1 = 2 * D; q.A = feat; q.lda = 2 * D; q.W = ctx->wp_conf0; q.out_scale = ctx->hs_conf0;
-                q.bias = ctx->b_conf0; q.relu = true; q.out = P2_OUT_F32; q.C32 = chid; q.ldc = D; q.EA = p.e_hid; q.bias_amax = ctx->ba_conf0;
+                GemmP2Args q = dense_gemm_p2(c0, B * n_rows);
+                q.A = feat; q.lda = 2 * D; q.relu = true; q.out = P2_OUT_F32; q.C32 = chid; q.ldc = D; q.EA = p.e_hid;
                 prof_begin(ctx, PS_GEMM, s); rc = launch_gemm_p2(ctx, q, s); prof_end(ctx, s);
                 if (rc) return rc;
-            } else if (use_mlp && p.f16x2() && ctx->wh_conf0) {
+            } else if (use_mlp && p.f16x2() && c0.wh) {
                 prof_begin(ctx, PS_CONF, s);
                 hipLaunchKernelGGL(conf_gather2_kernel, dim3((n_rows + 3) / 4, B), dim3(256), 0, s, Ni, n_rows, D, mdesc_i, mdesc_j,
                                    tuple_stride, so.m0[pidx], gathered);
                 prof_end(ctx, s);
-                GemmArgs c;
-                c.M = B * n_rows; c.N = D; c.K = 2 * D; c.K1 = 2 * D; c.A = gathered; c.lda = 2 * D;
-                c.bias = ctx->b_conf0; c.relu = true; c.C = chid; c.ldc = D;
-                prof_begin(ctx, PS_GEMM, s); rc = launch_gemm_x3(ctx, c, ctx->wh_conf0, 2 * D, s, ctx->hs_conf0); prof_end(ctx, s);
+                GemmArgs c = dense_gemm(c0, B * n_rows);
+                c.A = gathered; c.lda = 2 * D; c.relu = true; c.C = chid; c.ldc = D;
+                prof_begin(ctx, PS_GEMM, s); rc = launch_gemm_x3(ctx, c, c0.wh, 2 * D, s, c0.hs); prof_end(ctx, s);
                 if (rc) return rc;
             } else if (use_mlp) {
                 prof_begin(ctx, PS_CONF, s);
                 hipLaunchKernelGGL(conf_gather_kernel, dim3((n_rows + 3) / 4, B), dim3(256), 0, s, Ni, n_rows, D, mdesc_j, tuple_stride,
                                    so.m0[pidx], gathered);
                 prof_end(ctx, s);
-                GemmArgs c;
-                c.batch = B; c.M = n_rows; c.N = D; c.K = 2 * D; c.K1 = D;
+                GemmArgs c = dense_gemm(c0, n_rows);
+                c.batch = B; c.K1 = D;
                 c.A = mdesc_i; c.lda = D; c.sA = tuple_stride;
                 c.A2 = gathered; c.lda2 = D; c.sA2 = (int64_t)n_rows * D;
-                c.W = ctx->w_conf0; c.ldw = 2 * D; c.bias = ctx->b_conf0; c.relu = true;
-                c.C = chid; c.ldc = D; c.sC = (int64_t)n_rows * D;
+                c.relu = true; c.C = chid; c.ldc = D; c.sC = (int64_t)n_rows * D;
                 prof_begin(ctx, PS_GEMM, s); rc = launch_gemm_nt(ctx, c, s); prof_end(ctx, s);
                 if (rc) return rc;
             }

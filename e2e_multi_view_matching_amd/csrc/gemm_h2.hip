@@ -4,7 +4,7 @@
 //   x = x_hi + 2^-11 x_lo',   x_hi = fp16(x),   x_lo' = fp16(2^11 (x - x_hi))        |x - x_hi - 2^-11 x_lo'| <= 2^-22 |x|
 // the low plane kept scaled by 2^11 so that it has the exponent range of the high plane (no fp16 underflow for
 // 6e-5 <= |x| <= 65504; below that the representation degrades gracefully to an absolute 2^-36).  The weights are static:
-// their planes are made once at commit time (ctx.hip, add_split_h2) from 2^s W (s per matrix: max |2^s w| in [2^13, 2^14))
+// their planes are made once at commit time (weights.hip, add_split_h2) from 2^s W (s per matrix: max |2^s w| in [2^13, 2^14))
 // as w_hi, w_lo (unscaled low plane - always a normal number at that scale).  The three products that matter,
 //   x_hi w_hi + x_hi w_lo + x_lo' (2^-11 w_hi)                          (dropped: lo x lo <= 2^-22 |x w|)
 // all land in ONE fp32 accumulator with their true weight; 2^-11 w_hi is made from the w_hi fragment in registers (4

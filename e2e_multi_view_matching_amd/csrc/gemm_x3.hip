@@ -9,7 +9,7 @@
 //  * ACTIVATIONS stay fp32 in HBM (4 B/element instead of 6 B of planes, and no producer has to emit planes): the split
 //    x = x1 + x2 + x3 happens once per workgroup on the way from the prefetch registers into LDS (16 elements per thread
 //    and K tile - noise next to 48 MFMAs per wave), LDS then holds three bf16 planes per operand;
-//  * WEIGHTS are split once at commit time (S3 planes, ctx.hip);
+//  * WEIGHTS are split once at commit time (S3 planes, weights.hip);
 //  * a product is the 6 largest of the 9 plane products (dropped terms <= 2^-25 |ab|), each exact in fp32, accumulated
 //    in fp32 by v_mfma_f32_32x32x16_bf16: 48 MFMAs x 32 cycles per wave and K tile against 64 x 64 cycles for fp32.
 // LDS rows are 40 bf16 (80 B): 16 rows x 16 B of a ds_read_b128 fall in 16 distinct 16-byte bank groups.

@@ -127,7 +127,7 @@ struct GemmP2Args {
     int64_t lda = 0;
     const uint16_t* A2 = nullptr;  // second K segment (k >= K1)
     int64_t lda2 = 0;
-    const uint16_t* W = nullptr;   // P2 planes of 2^s W [N][K columns] (ctx.hip: add_split_p2)
+    const uint16_t* W = nullptr;   // P2 planes of 2^s W [N][K columns] (weights.hip: add_split_p2)
     float out_scale = 1.f;         // 2^-s
     const float* bias = nullptr;
     const uint16_t* Rp = nullptr;  // residual, P2 scaled planes [M][ldr columns]
@@ -163,8 +163,6 @@ int launch_from_planes(e2emv_ctx* ctx, const uint16_t* src, int64_t rows, int C,
 // [mdesc_i[n] | mdesc_j[matches[n]]] of B samples ([B][n_rows][2 D]) straight to scaled planes + tile exponents (the conf head's GEMM operand)
 int launch_conf_gather_planes(e2emv_ctx* ctx, const float* mdesc_i, const float* mdesc_j, int64_t tuple_stride, const int64_t* matches, int N, int n_rows,
                               int B, int D, uint16_t* dst, int* E, hipStream_t s);
-// host: fp32 weights [rows][cols] -> P2 planes of 2^s W appended to `out` (offset returned), *out_scale = 2^-s
-size_t add_split_p2(std::vector<uint16_t>& out, const std::vector<float>& w, int rows, int cols, float* out_scale);
 // softmax(q k^T / sqrt(64)) v on plane operands: qk = q | k plain planes [n_img * n_rows][2D], vt = V^T plain planes;
 // out = P2 scaled planes [n_img * n_rows][D]
 // EQK [rows/64][8], EVt [rows/64][4]: tile exponents of the operands, EO [rows/64][4] of the output (null = zero / not wanted)

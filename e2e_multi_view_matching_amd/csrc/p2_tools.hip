@@ -1,8 +1,6 @@
-// Plane format helpers (p2.h): fp32 <-> planes conversion kernels, the host-side weight split, and the building-block
+// Plane format helpers (p2.h): fp32 <-> planes conversion kernels and the building-block
 // entry points that let tests and micro-benchmarks drive gemm_p2.hip / attention_p2.hip on plain fp32 buffers.
-#include <cmath>
-#include <cstring>
-#include <vector>
+#include <algorithm>
 
 #include "p2.h"
 
@@ -262,59 +260,11 @@ int launch_from_planes(e2emv_ctx* ctx, const uint16_t* src, int64_t rows, int C,
     return E2EMV_OK;
 }
 
-namespace {
-inline uint16_t f2h(float f) {
-    const _Float16 h = (_Float16)f;  // round to nearest even
-    uint16_t u;
-    memcpy(&u, &h, 2);
-    return u;
-}
-inline float h2f(uint16_t u) {
-    _Float16 h;
-    memcpy(&h, &u, 2);
-    return (float)h;
-}
-}  // namespace
-
-// weights [rows][cols] fp32 -> P2 planes [rows][cols / 32 blocks of {32 hi, 32 lo}] of 2^s W, appended to `out`.  Same
-// numbers as add_split_h2 (ctx.hip): s brings max |w| into [2^13, 2^14), lo is the UNSCALED residual fp16(v - hi).
-size_t add_split_p2(std::vector<uint16_t>& out, const std::vector<float>& w, int rows, int cols, float* out_scale) {
-    float mx = 0.f;
-    for (float v : w) mx = std::max(mx, std::fabs(v));
-    int e = 0;
-    if (mx > 0.f && std::isfinite(mx)) (void)std::frexp(mx, &e);
-    const int sh = 14 - e;
-    const float sc = std::ldexp(1.f, sh);
-    *out_scale = std::ldexp(1.f, -sh);
-    const size_t off = (out.size() + 127) & ~size_t(127);
-    out.resize(off + (size_t)rows * 2 * cols);
-    for (int r = 0; r < rows; ++r)
-        for (int c = 0; c < cols; ++c) {
-            const float v = w[(size_t)r * cols + c] * sc;
-            const uint16_t hi = f2h(v);
-            uint16_t* o = &out[off + (size_t)p2_index(r, c, cols)];
-            o[0] = hi;
-            o[32] = f2h(v - h2f(hi));
-        }
-    return off;
-}
-
 }  // namespace e2emv
 
 using namespace e2emv;
 
 static size_t al256(size_t b) { return (b + 255) & ~size_t(255); }
-
-// weights fp32 [N][K] on the device -> P2 planes at d_dst (host-synchronising: the split is the host code of the commit path)
-static int weights_to_planes(e2emv_ctx* ctx, const float* d_W, int N, int K, uint16_t* d_dst, float* out_scale, hipStream_t s) {
-    std::vector<float> hw((size_t)N * K);
-    E2EMV_HIP(ctx, hipStreamSynchronize(s));
-    E2EMV_HIP(ctx, hipMemcpy(hw.data(), d_W, hw.size() * sizeof(float), hipMemcpyDeviceToHost));
-    std::vector<uint16_t> planes;
-    const size_t off = add_split_p2(planes, hw, N, K, out_scale);
-    E2EMV_HIP(ctx, hipMemcpy(d_dst, planes.data() + off, (size_t)N * 2 * K * 2, hipMemcpyHostToDevice));
-    return E2EMV_OK;
-}
 
 extern "C" int e2emv_gemm_p2(e2emv_ctx* ctx, int M, int Nout, int K, int K1, const float* d_A, const float* d_A2, const float* d_W,
                              const float* d_bias, const float* d_R, float* d_C, int flags, void* stream) {
@@ -343,8 +293,8 @@ extern "C" int e2emv_gemm_p2(e2emv_ctx* ctx, int M, int Nout, int K, int K1, con
     int* ER = use_e && d_R ? EA + (M / 64) * (K / 64) : nullptr;
     int* EC = use_e && planes_out ? EA + (M / 64) * ((K + Nout) / 64) : nullptr;
     float* AR = use_e && d_R ? (float*)(EA + (M / 64) * ((K + 2 * Nout) / 64)) : nullptr;
-    float out_scale = 1.f;
-    if ((rc = weights_to_planes(ctx, d_W, Nout, K, Wp, &out_scale, s))) return rc;
+    DenseWeights dw;  // (the planes and the bias bound as the commit path makes them)
+    if ((rc = dense_from_device(ctx, d_W, d_bias, Nout, K, WF_P2, Wp, dw, s))) return rc;
     if ((rc = launch_to_planes(ctx, d_A, M, K1, K1, Ap, s, EA))) return rc;
     if (K2 && (rc = launch_to_planes(ctx, d_A2, M, K2, K2, A2p, s, EA2))) return rc;
     if (d_R && (rc = launch_to_planes(ctx, d_R, M, Nout, Nout, Rp, s, ER, AR))) return rc;
@@ -352,16 +302,10 @@ extern "C" int e2emv_gemm_p2(e2emv_ctx* ctx, int M, int Nout, int K, int K1, con
     g.M = M; g.N = Nout; g.K = K; g.K1 = K1;
     g.A = Ap; g.lda = K1;
     if (K2) { g.A2 = A2p; g.lda2 = K2; }
-    g.W = Wp; g.out_scale = out_scale; g.bias = d_bias;
+    g.W = dw.wp; g.out_scale = dw.hs; g.bias = dw.b; g.bias_amax = dw.ba;
     if (d_R) { g.Rp = Rp; g.ldr = Nout; }
     g.relu = (flags & 1) != 0;
     g.EA = EA; g.EA2 = EA2; g.ER = ER; g.EC = EC; g.AR = AR;
-    if (d_bias) {  // the bound the commit path computes on the host
-        std::vector<float> hb(Nout);
-        E2EMV_HIP(ctx, hipStreamSynchronize(s));
-        E2EMV_HIP(ctx, hipMemcpy(hb.data(), d_bias, hb.size() * sizeof(float), hipMemcpyDeviceToHost));
-        for (float v : hb) g.bias_amax = std::max(g.bias_amax, std::fabs(v));
-    }
     if (planes_out) { g.out = P2_OUT_PLANES; g.Cp = Cp; g.ldc = Nout; }
     else { g.out = P2_OUT_F32; g.C32 = d_C; g.ldc = Nout; }
     const int reps = (flags >> 8) > 0 ? (flags >> 8) : 1;  // bits 8+: repeat the launch (micro-benchmarks time the family slot)
@@ -395,19 +339,13 @@ extern "C" int e2emv_qkv_p2(e2emv_ctx* ctx, int n_img, int n_rows, int D, int H,
     int* EX = (int*)w;
     int* EQK = EX + (M / 64) * 4;
     int* EVt = EQK + (M / 64) * 8;
-    float out_scale = 1.f;
-    if ((rc = weights_to_planes(ctx, d_W, 3 * D, D, Wp, &out_scale, s))) return rc;
+    DenseWeights dw;
+    if ((rc = dense_from_device(ctx, d_W, d_bias, 3 * D, D, WF_P2, Wp, dw, s))) return rc;
     if ((rc = launch_to_planes(ctx, d_X, M, D, D, Xp, s, EX))) return rc;
     GemmP2Args g;
-    g.M = (int)M; g.N = 3 * D; g.K = D; g.K1 = D; g.A = Xp; g.lda = D; g.W = Wp; g.out_scale = out_scale; g.bias = d_bias;
+    g.M = (int)M; g.N = 3 * D; g.K = D; g.K1 = D; g.A = Xp; g.lda = D; g.W = dw.wp; g.out_scale = dw.hs; g.bias = dw.b; g.bias_amax = dw.ba;
     g.out = P2_OUT_QKV; g.Cp = QK; g.Vt = VT; g.n_rows = n_rows; g.heads = H;
     g.EA = EX; g.EC = EQK; g.EVt = EVt;
-    if (d_bias) {
-        std::vector<float> hb(3 * D);
-        E2EMV_HIP(ctx, hipStreamSynchronize(s));
-        E2EMV_HIP(ctx, hipMemcpy(hb.data(), d_bias, hb.size() * sizeof(float), hipMemcpyDeviceToHost));
-        for (float v : hb) g.bias_amax = std::max(g.bias_amax, std::fabs(v));
-    }
     prof_begin(ctx, PS_GEMM, s);
     rc = launch_gemm_p2(ctx, g, s);
     prof_end(ctx, s);

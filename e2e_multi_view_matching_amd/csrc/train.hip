@@ -179,11 +179,6 @@ using namespace e2emv;
 
 namespace {
 
-const HostTensor* findt(e2emv_ctx* ctx, const std::string& k) {
-    auto it = ctx->raw.find(k);
-    return it == ctx->raw.end() ? nullptr : &it->second;
-}
-
 struct Pack {
     std::vector<float> host;
     size_t add(const std::vector<float>& v) {
@@ -197,8 +192,8 @@ struct Pack {
 // conv `prefix` [out][in] (+ the BatchNorm `bn` behind it when present) -> folded copies; the raw tensors go to `raw`
 int conv_bn(e2emv_ctx* ctx, TrainState* t, Pack& raw, const std::string& prefix, const std::string& bn, int out, int in, std::vector<float>& w,
             std::vector<float>& b) {
-    const HostTensor* tw = findt(ctx, prefix + ".weight");
-    const HostTensor* tb = findt(ctx, prefix + ".bias");
+    const HostTensor* tw = find(ctx, prefix + ".weight");
+    const HostTensor* tb = find(ctx, prefix + ".bias");
     if (!tw || !tb || (int64_t)tw->data.size() != (int64_t)out * in || (int)tb->data.size() != out)
         return set_err(ctx, E2EMV_ESTATE, "train_commit: '%s.{weight,bias}' missing or not [%d,%d]", prefix.c_str(), out, in);
     w = tw->data;
@@ -206,11 +201,11 @@ int conv_bn(e2emv_ctx* ctx, TrainState* t, Pack& raw, const std::string& prefix,
     t->raw[prefix + ".weight"] = {raw.add(w), w.size()};
     t->raw[prefix + ".bias"] = {raw.add(b), b.size()};
     if (bn.empty()) return E2EMV_OK;
-    const HostTensor* mean = findt(ctx, bn + ".running_mean");
+    const HostTensor* mean = find(ctx, bn + ".running_mean");
     if (!mean) return E2EMV_OK;
-    const HostTensor* var = findt(ctx, bn + ".running_var");
-    const HostTensor* g = findt(ctx, bn + ".weight");
-    const HostTensor* be = findt(ctx, bn + ".bias");
+    const HostTensor* var = find(ctx, bn + ".running_var");
+    const HostTensor* g = find(ctx, bn + ".weight");
+    const HostTensor* be = find(ctx, bn + ".bias");
     if (!var || !g || !be || (int)mean->data.size() != out || (int)var->data.size() != out || (int)g->data.size() != out || (int)be->data.size() != out)
         return set_err(ctx, E2EMV_ESHAPE, "train_commit: BatchNorm '%s' incomplete", bn.c_str());
     t->raw[bn + ".weight"] = {raw.add(g->data), (size_t)out};
@@ -294,7 +289,7 @@ static int train_build(e2emv_ctx* ctx, const e2emv_model_desc* m, TrainState* t,
         t->wc1 = pk.add(w);
         t->bc1 = pk.add(b);
     }
-    const HostTensor* bs = findt(ctx, "bin_score");
+    const HostTensor* bs = find(ctx, "bin_score");
     if (!bs || bs->data.size() != 1) return set_err(ctx, E2EMV_ESTATE, "train_commit: missing scalar 'bin_score'");
     t->bin_score = bs->data[0];
     t->alpha = pk.add(std::vector<float>{bs->data[0]});
