@@ -436,6 +436,48 @@ int sp_conv1x1(e2emv_ctx* ctx, int layer, const float* in, float* out, int64_t r
     return rc;
 }
 
+// The detector tail behind the score map: simple_nms (5 max-pool launches) and the keypoint selection.  The caller owns the
+// profiling scope (forward keeps softmax + NMS + selection in one PS_MATCH scope).
+int sp_detect(e2emv_ctx* ctx, const e2emv_superpoint_desc* d, const float* score, float* mask, float* supp, float* ss, float* nms, int* lidx,
+              float* lsc, int B, int H, int W, float* d_kpts, float* d_scores, int32_t* d_count, hipStream_t s) {
+    const int r = d->nms_radius, K = d->max_keypoints;
+    {
+        NmsArgs n{};
+        n.s = score; n.mask = mask; n.supp = supp; n.ss = ss; n.out = nms; n.H = H; n.W = W; n.r = r;
+        const dim3 grid((W + kNmsT - 1) / kNmsT, (H + kNmsT - 1) / kNmsT, B);
+        const int R = kNmsT + 2 * r;
+        const size_t lds = sizeof(float) * (R * R + R * kNmsT);
+        auto run = [&](const float* in, int mode, int last) {
+            n.in = in; n.mode = mode; n.last = last;
+            hipLaunchKernelGGL(sp_nms_kernel, grid, dim3(256), lds, s, n);
+        };
+        run(score, 0, 0);
+        for (int it = 0; it < 2; ++it) {
+            run(mask, 1, 0);
+            run(ss, 2, it == 1);
+        }
+        E2EMV_CHECK_LAUNCH(ctx, "sp_nms_kernel");
+    }
+    {
+        SelArgs a{};
+        a.nms = nms; a.H = H; a.W = W; a.border = d->remove_borders; a.K = K; a.fill_random = d->fill_random ? 1 : 0;
+        a.thr = d->keypoint_threshold; a.seed = d->seed;
+        a.list_idx = lidx; a.list_sc = lsc; a.kpts = d_kpts; a.scores = d_scores; a.count = d_count;
+        hipLaunchKernelGGL(sp_select_kernel, dim3(B), dim3(kSelThreads), 0, s, a);
+        E2EMV_CHECK_LAUNCH(ctx, "sp_select_kernel");
+    }
+    return E2EMV_OK;
+}
+
+// Descriptors at the keypoints: dense [B][Hc][Wc][256] is the UNnormalised descriptor-head output.
+int sp_sample(e2emv_ctx* ctx, const float* dense, const float* d_kpts, const int32_t* d_count, float* d_desc, int B, int Hc, int Wc, int K, hipStream_t s) {
+    prof_begin(ctx, PS_MISC, s);
+    hipLaunchKernelGGL(sp_sample_kernel, dim3(K, B), dim3(64), 0, s, dense, d_kpts, d_count, d_desc, Hc, Wc, K);
+    E2EMV_CHECK_LAUNCH(ctx, "sp_sample_kernel");
+    prof_end(ctx, s);
+    return E2EMV_OK;
+}
+
 }  // namespace
 
 extern "C" int e2emv_superpoint_forward(e2emv_ctx* ctx, const e2emv_superpoint_desc* d, const float* d_images, float* d_kpts, float* d_scores,
@@ -513,38 +555,44 @@ extern "C" int e2emv_superpoint_forward(e2emv_ctx* ctx, const e2emv_superpoint_d
     prof_begin(ctx, PS_MATCH, s);
     hipLaunchKernelGGL(sp_softmax_d2s_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, s, S65, score, Hc, Wc, cells);
     E2EMV_CHECK_LAUNCH(ctx, "sp_softmax_d2s_kernel");
-    {
-        NmsArgs n{};
-        n.s = score; n.mask = mask; n.supp = supp; n.ss = ss; n.out = nms; n.H = H; n.W = W; n.r = r;
-        const dim3 grid((W + kNmsT - 1) / kNmsT, (H + kNmsT - 1) / kNmsT, B);
-        const int R = kNmsT + 2 * r;
-        const size_t lds = sizeof(float) * (R * R + R * kNmsT);
-        auto run = [&](const float* in, int mode, int last) {
-            n.in = in; n.mode = mode; n.last = last;
-            hipLaunchKernelGGL(sp_nms_kernel, grid, dim3(256), lds, s, n);
-        };
-        run(score, 0, 0);
-        for (int it = 0; it < 2; ++it) {
-            run(mask, 1, 0);
-            run(ss, 2, it == 1);
-        }
-        E2EMV_CHECK_LAUNCH(ctx, "sp_nms_kernel");
-    }
-    {
-        SelArgs a{};
-        a.nms = nms; a.H = H; a.W = W; a.border = d->remove_borders; a.K = K; a.fill_random = d->fill_random ? 1 : 0;
-        a.thr = d->keypoint_threshold; a.seed = d->seed;
-        a.list_idx = lidx; a.list_sc = lsc; a.kpts = d_kpts; a.scores = d_scores; a.count = d_count;
-        hipLaunchKernelGGL(sp_select_kernel, dim3(B), dim3(kSelThreads), 0, s, a);
-        E2EMV_CHECK_LAUNCH(ctx, "sp_select_kernel");
-    }
+    if ((rc = sp_detect(ctx, d, score, mask, supp, ss, nms, lidx, lsc, B, H, W, d_kpts, d_scores, d_count, s))) return rc;
     prof_end(ctx, s);
     // ---- descriptor head ----
     if ((rc = sp_conv3x3(ctx, 10, X, P1, B, Hc, Wc, s))) return rc;
     if ((rc = sp_conv1x1(ctx, 11, P1, P2, cells, s))) return rc;
-    prof_begin(ctx, PS_MISC, s);
-    hipLaunchKernelGGL(sp_sample_kernel, dim3(K, B), dim3(64), 0, s, P2, d_kpts, d_count, d_desc, Hc, Wc, K);
-    E2EMV_CHECK_LAUNCH(ctx, "sp_sample_kernel");
+    if ((rc = sp_sample(ctx, P2, d_kpts, d_count, d_desc, B, Hc, Wc, K, s))) return rc;
+    return E2EMV_OK;
+}
+
+// The detector tail alone on a caller-supplied score map (building block for per-kernel parity tests): the same kernels, launch
+// geometry and order as the tail of e2emv_superpoint_forward, on a workspace reservation of its own; no weights needed.
+extern "C" int e2emv_superpoint_detect(e2emv_ctx* ctx, const e2emv_superpoint_desc* d, const float* d_score, const float* d_dense, float* d_kpts,
+                                       float* d_scores, int32_t* d_count, float* d_desc, float* d_nms_map, void* stream) {
+    if (!ctx) return E2EMV_EINVAL;
+    E2EMV_ENTER(ctx, stream);
+    if (!d || !d_score || !d_kpts || !d_scores || !d_count) return set_err(ctx, E2EMV_EINVAL, "superpoint_detect: NULL argument");
+    if ((d_dense != nullptr) != (d_desc != nullptr)) return set_err(ctx, E2EMV_EINVAL, "superpoint_detect: d_desc is required if and only if d_dense is given");
+    const int B = d->batch, K = d->max_keypoints, r = d->nms_radius, H = d->height, W = d->width;
+    if (B < 1 || H < 16 || W < 16 || H % 8 || W % 8) return set_err(ctx, E2EMV_ESHAPE, "superpoint_detect: score map %dx%d must be a multiple of 8 (>= 16)", H, W);
+    if ((d->valid_height != 0 && d->valid_height != H) || (d->valid_width != 0 && d->valid_width != W))
+        return set_err(ctx, E2EMV_ESHAPE, "superpoint_detect: valid size %dx%d must be 0 or the grid %dx%d", d->valid_height, d->valid_width, H, W);
+    if (K < 1 || K > kSelMaxK) return set_err(ctx, E2EMV_ESHAPE, "superpoint_detect: max_keypoints %d outside 1..%d", K, kSelMaxK);
+    if (r < 0 || r > 16 || d->remove_borders < 0) return set_err(ctx, E2EMV_EINVAL, "superpoint_detect: nms_radius %d / remove_borders %d", r, d->remove_borders);
+    if ((int64_t)B * H * W >= (int64_t(1) << 31)) return set_err(ctx, E2EMV_ESHAPE, "superpoint_detect: batch too large for one call (B*H*W < 2^31)");
+    hipStream_t s = (hipStream_t)stream;
+    const size_t sz_map = (sizeof(float) * (size_t)B * H * W + 255) & ~size_t(255);
+    int rc = ws_reserve(ctx, 6 * sz_map);  // mask, supp, ss, the NMS-ed map, the two candidate lists
+    if (rc) return rc;
+    char* p = ctx->d_ws;
+    auto take = [&](size_t b) { char* q = p; p += b; return q; };
+    float* mask = (float*)take(sz_map); float* supp = (float*)take(sz_map); float* ss = (float*)take(sz_map);
+    float* own = (float*)take(sz_map);
+    float* nms = d_nms_map ? d_nms_map : own;
+    int* lidx = (int*)take(sz_map); float* lsc = (float*)take(sz_map);
+    prof_begin(ctx, PS_MATCH, s);
+    rc = sp_detect(ctx, d, d_score, mask, supp, ss, nms, lidx, lsc, B, H, W, d_kpts, d_scores, d_count, s);
     prof_end(ctx, s);
+    if (rc) return rc;
+    if (d_dense) return sp_sample(ctx, d_dense, d_kpts, d_count, d_desc, B, H / 8, W / 8, K, s);
     return E2EMV_OK;
 }

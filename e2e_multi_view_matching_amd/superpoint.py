@@ -97,3 +97,44 @@ class SuperPoint(nn.Module):
             if smap is not None:
                 out.setdefault("score_map", []).append(smap)
         return out
+
+
+def detect(score, dense=None, **config):
+    """The detector tail alone (``e2emv_superpoint_detect``: a building block for per-kernel parity tests): ``score`` [B,H,W] fp32 on
+    the device is the map upstream's ``simple_nms`` receives, ``dense`` (optional) [B,256,H/8,W/8] the UNnormalised output of the
+    descriptor head.  ``config`` takes the keys of ``SuperPoint.default_config`` (+ ``seed``).  Returns per-image lists like
+    ``SuperPoint.forward`` (``descriptors`` only with ``dense``) plus ``score_map`` [B,H,W], the NMS-ed map, and ``raw``: the whole
+    output buffers ``(kpts [B,K,2], scores [B,K], count [B], desc [B,256,K] or None)`` including the slots beyond each count."""
+    cfg = {**SuperPoint.default_config, **config}
+    if not score.is_cuda:
+        raise RuntimeError("SuperPoint needs its score map on an MI355X (no CPU fallback)")
+    mk = cfg["max_keypoints"]
+    if mk == 0 or mk > MAX_KEYPOINTS_CAPACITY:
+        raise ValueError('"max_keypoints" must be positive (<= {}) or -1'.format(MAX_KEYPOINTS_CAPACITY))
+    dev = score.device
+    ctx = _lib.context(dev)
+    B, H, W = score.shape
+    score = score.to(torch.float32).contiguous()
+    K = mk if mk > 0 else MAX_KEYPOINTS_CAPACITY
+    d = _lib.SuperPointDesc(valid_height=0, valid_width=0, batch=B, height=H, width=W, nms_radius=int(cfg["nms_radius"]), max_keypoints=K,
+                            remove_borders=int(cfg["remove_borders"]), fill_random=1 if cfg["fill_with_random_keypoints"] else 0,
+                            keypoint_threshold=float(cfg["keypoint_threshold"]), seed=int(cfg.get("seed", 0)))
+    kpts = torch.empty((B, K, 2), dtype=torch.float32, device=dev)
+    scores = torch.empty((B, K), dtype=torch.float32, device=dev)
+    count = torch.empty((B,), dtype=torch.int32, device=dev)
+    smap = torch.empty((B, H, W), dtype=torch.float32, device=dev)
+    desc = nhwc = None
+    if dense is not None:
+        if tuple(dense.shape) != (B, 256, H // 8, W // 8):
+            raise AssertionError("dense must be [B,256,H/8,W/8], got {}".format(tuple(dense.shape)))
+        nhwc = dense.to(dev, torch.float32).permute(0, 2, 3, 1).contiguous()
+        desc = torch.empty((B, 256, K), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev), ctx.py_lock:
+        ctx.call("e2emv_superpoint_detect", ctypes.byref(d), _lib.ptr(score), _lib.ptr(nhwc), _lib.ptr(kpts), _lib.ptr(scores), _lib.ptr(count),
+                 _lib.ptr(desc), _lib.ptr(smap), _lib.stream_ptr(dev))
+    n = count.tolist()
+    out = {"keypoints": [kpts[b, :n[b]] for b in range(B)], "scores": [scores[b, :n[b]] for b in range(B)], "score_map": smap,
+           "raw": (kpts, scores, count, desc)}
+    if desc is not None:
+        out["descriptors"] = [desc[b, :, :n[b]] for b in range(B)]
+    return out

@@ -399,6 +399,19 @@ int e2emv_gemm_nt(e2emv_ctx* ctx, int batch, int M, int Nout, int K, int K1, con
 int e2emv_attention(e2emv_ctx* ctx, int B, int T, int n_rows, int n_valid, int D, int H, const float* d_qkv,
                     int cross, float* d_out, void* stream);
 
+/* The SuperPoint detector tail alone, on a score map the caller supplies: simple_nms -> threshold -> border removal -> top-k,
+ * and (if d_dense is given) the descriptor sampling - the kernels, launch geometry and order e2emv_superpoint_forward runs
+ * behind its detector and descriptor heads.  desc as for forward (height, width = size of the score map: multiples of 8, at
+ * least 16; valid_height / valid_width 0 or equal to them; max_keypoints 1..4096; nms_radius 0..16); needs no committed
+ * weights.  Outputs as for forward: entries beyond d_count[b] are zero.                                               */
+int e2emv_superpoint_detect(e2emv_ctx* ctx, const e2emv_superpoint_desc* desc,
+                            const float* d_score,  /* [B,H,W] fp32: the map simple_nms receives                        */
+                            const float* d_dense,  /* optional [B,H/8,W/8,256] NHWC: the UNnormalised descriptor-head output */
+                            float* d_kpts, float* d_scores, int32_t* d_count,
+                            float* d_desc,         /* [B,256,K]; required if and only if d_dense is given               */
+                            float* d_nms_map,      /* optional [B,H,W]: the NMS-ed map                                  */
+                            void* stream);
+
 /* ---- arithmetic of the dense GNN contractions -----------------------------------------
  * E2EMV_PRECISION_F32    : v_mfma_f32_32x32x2_f32, exact fp32 products (the audit mode).
  * E2EMV_PRECISION_BF16X3 : fp32 operands split into three bf16 planes, six bf16 MFMA products per

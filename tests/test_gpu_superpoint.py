@@ -54,8 +54,12 @@ def test_matches_oracle(gpu, B, H, W, maxk, r, border):
     assert (smap - ref["score_map"]).abs().max() < 1e-5
     # the NMS decisions themselves (which pixels survive) must agree wherever the fp32 score fields do not tie within rounding
     assert ((smap > 0) != (ref["score_map"] > 0)).float().mean() < 1e-4
+    thr32 = float(torch.tensor(0.005, dtype=torch.float32))  # the threshold as the library receives it
     for b in range(B):
         kp, sc, de = out["keypoints"][b].cpu(), out["scores"][b].cpu(), out["descriptors"][b].cpu()
+        # selection reads the very buffer that is returned as score_map: on it the decisions carry no tolerance - shape, order, values
+        ek, es = OS.select_keypoints(smap[b], thr32, border, maxk if maxk > 0 else 4096)
+        assert torch.equal(kp, torch.flip(ek, [1]).float()) and torch.equal(sc, es)
         rk, rs, rd = ref["keypoints"][b], ref["scores"][b], ref["descriptors"][b]
         assert kp.shape == rk.shape
         same = (kp == rk).all(1)
