@@ -44,14 +44,27 @@ def _normal_equations(extr1, pts, x0, x1, c):
     return J.T @ J, -(J.T @ r), (r ** 2).sum()
 
 
-def run_bundle_adjust_2_view(kpts0_norm, kpts1_norm, confidence, init_T021, n_iterations, lm_increase=1.5, lm_decrease=3.5):
-    """Returns (refined T_021 of the valid samples [n_valid,4,4], valid_batch [B] bool) like the reference."""
+def run_bundle_adjust_2_view(kpts0_norm, kpts1_norm, confidence, init_T021, n_iterations, lm_increase=1.5, lm_decrease=3.5,
+                             homogeneous_sign=None, return_trajectory=False):
+    """Returns (refined T_021 of the valid samples [n_valid,4,4], valid_batch [B] bool) like the reference.
+
+    ``homogeneous_sign`` (+1 / -1): the DLT null vector of the triangulation has no defined sign, and the ``1 / (w + 1e-8)``
+    of the de-homogenisation makes the start points depend on it (relative ~1e-8 / |w|).  With a sign given, every null
+    vector is flipped so that its last component has that sign before it is de-homogenised; ``None`` keeps whatever the
+    SVD returned.  Two runs with +1 and -1 bracket what an implementation with another null-vector routine may return.
+
+    ``return_trajectory``: also returns, as a third value, one dict per valid sample with an entry for each residual
+    evaluation ``it = 0..n_iterations``: ``best`` [n+1,4,4] the best pose AFTER that evaluation, ``rn`` [n+1] its residual,
+    ``best_r`` [n+1] the best residual BEFORE the comparison (NaN at it = 0, which compares with nothing) and ``accepted``
+    [n+1] bool (True at it = 0).  The loop does not look ahead: a run with n iterations is a prefix of a run with n' > n,
+    and ``best[n]`` IS the result of ``n_iterations = n``.  One 10-iteration run yields the expected result of every
+    ``n_iterations <= 10``."""
     conf = confidence.squeeze(-1) if confidence.dim() == 3 else confidence
     B = kpts0_norm.shape[0]
     dt = kpts0_norm.dtype
     valid = conf > 0.0
     valid_batch = valid.sum(-1) > 6
-    out = []
+    out, trajectory = [], []
     for b in range(B):
         if not bool(valid_batch[b]):
             continue
@@ -60,19 +73,30 @@ def run_bundle_adjust_2_view(kpts0_norm, kpts1_norm, confidence, init_T021, n_it
         c = c / (0.5 * (2 * c.sum()).clamp(min=1e-6))  # each match is two observations (:45-48)
         extr1 = init_T021[b].clone().to(dt)
         P0 = torch.eye(4, dtype=dt)[:3]
-        pts = K.triangulate_points(P0[None], extr1[None, :3], x0[None], x1[None])[0]
+        if homogeneous_sign is None:
+            pts = K.triangulate_points(P0[None], extr1[None, :3], x0[None], x1[None])[0]
+        else:
+            h = K.triangulate_points_homogeneous(P0[None], extr1[None, :3], x0[None], x1[None])[0]
+            flip = torch.where(torch.signbit(h[:, 3:]) != (homogeneous_sign < 0), -torch.ones_like(h[:, 3:]), torch.ones_like(h[:, 3:]))
+            pts = K.convert_points_from_homogeneous(h * flip)
         lam = 0.1
         best_r, best = None, extr1.clone()
+        tr = {"best": [], "rn": [], "best_r": [], "accepted": []}
         for it in range(n_iterations + 1):
             A, bvec, rn = _normal_equations(extr1, pts, x0, x1, c)
+            tr["rn"].append(rn)
+            tr["best_r"].append(rn * float("nan") if it == 0 else best_r)
             if it == 0:
                 best_r, best = rn, extr1.clone()
+                tr["accepted"].append(True)
             else:
+                tr["accepted"].append(bool(rn < best_r))
                 if rn < best_r:
                     best_r, best = rn, extr1.clone()
                     lam = lam / lm_decrease
                 else:
                     lam = lam * lm_increase
+            tr["best"].append(best)
             if it == n_iterations:
                 break
             d = torch.diagonal(A)
@@ -89,5 +113,9 @@ def run_bundle_adjust_2_view(kpts0_norm, kpts1_norm, confidence, init_T021, n_it
             extr1 = delta @ extr1
             pts = pts + dx[6:].view(-1, 3)
         out.append(best)
+        trajectory.append({"best": torch.stack(tr["best"]), "rn": torch.stack(tr["rn"]), "best_r": torch.stack(tr["best_r"]),
+                           "accepted": torch.tensor(tr["accepted"])})
     res = torch.stack(out) if out else torch.zeros(0, 4, 4, dtype=dt)
+    if return_trajectory:
+        return res, valid_batch, trajectory
     return res, valid_batch

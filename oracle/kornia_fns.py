@@ -79,8 +79,8 @@ def motion_from_essential(E):
     return torch.stack([R1, R1, R2, R2], dim=-3), torch.stack([t, -t, t, -t], dim=-3)
 
 
-def triangulate_points(P1, P2, x1, x2):
-    """Linear (DLT) triangulation; P [*,3,4], x [*,N,2] -> [*,N,3]."""
+def triangulate_points_homogeneous(P1, P2, x1, x2):
+    """Linear (DLT) triangulation; P [*,3,4], x [*,N,2] -> the unit null vectors [*,N,4] (their sign is the SVD's)."""
     shape = max(x1.shape, x2.shape)
     A = torch.zeros(shape[:-1] + (4, 4), dtype=x1.dtype)
     for i in range(4):
@@ -89,7 +89,12 @@ def triangulate_points(P1, P2, x1, x2):
         A[..., 2, i] = x2[..., 0] * P2[..., 2:3, i] - P2[..., 0:1, i]
         A[..., 3, i] = x2[..., 1] * P2[..., 2:3, i] - P2[..., 1:2, i]
     _, _, V = svd(A)
-    return convert_points_from_homogeneous(V[..., -1])
+    return V[..., -1]
+
+
+def triangulate_points(P1, P2, x1, x2):
+    """Linear (DLT) triangulation; P [*,3,4], x [*,N,2] -> [*,N,3]."""
+    return convert_points_from_homogeneous(triangulate_points_homogeneous(P1, P2, x1, x2))
 
 
 def depth_from_point(R, t, X):
