@@ -109,6 +109,9 @@ SIGNATURES = {
     "e2emv_essential_ransac": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_double, c_int,
                                        ctypes.c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_void_p]),
+    "e2emv_mv_ransac_prepare": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, _PP, c_int, c_int, ctypes.c_double,
+                                        c_void_p, c_void_p, c_void_p, c_void_p]),
+    "e2emv_mv_ransac_filter": (c_int, [c_void_p, c_int, c_int, c_int] + [c_void_p] * 21),
     "e2emv_essential_5pt": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "e2emv_superpoint_commit": (c_int, [c_void_p]),
     "e2emv_superpoint_forward": (c_int, [c_void_p, ctypes.POINTER(SuperPointDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

@@ -5,7 +5,8 @@ position averaging -> weighted bundle adjustment, keeping the reference's CSV wi
 
 Same function names, arguments, dictionary keys and file layouts as the reference.  What differs is where the work runs:
 * relative poses: the HIP w8pt + two-view BA kernels (``pose.py``) instead of kornia/pytorch3d ops, and the RANSAC
-  baseline (``ransac.py``: 5-point RANSAC + recoverPose on the device) instead of OpenCV;
+  baseline (``ransac.py``: 5-point RANSAC + recoverPose on the device) instead of OpenCV; all three methods on the CSV path
+  and on the batched path (``rel_pose_method``);
 * ``ba_initializer`` / ``bundle_adjuster``: not separate executables built on Theia/Ceres but entry points of
   libe2emv.so called in-process (``run_ba_initializer`` = host C++ averaging, ``run_bundle_adjuster`` = one HIP workgroup
   doing the whole LM/Schur optimisation; the batched path can run the averaging on the device instead, one wave per tuple:
@@ -26,7 +27,7 @@ from scipy.sparse.csgraph import minimum_spanning_tree
 
 from . import _lib
 from .pose import mask_confidence, run_bundle_adjust_2_view
-from .ransac import estimate_poses_ransac, normalize_keypoints
+from .ransac import MAX_MATCHES, estimate_poses_ransac, normalize_keypoints
 
 
 def _dev():
@@ -292,8 +293,7 @@ def initialize_bundle_adjust(n_images, data, result, file_path, conf_thresh=0., 
     (``rel_pose_method`` "w8pt_ba": w8pt + two-view BA; "ransac" / "ransac_ba": the RANSAC baseline, without / with two-view
     BA on its inliers) -> maximum spanning tree of the inlier-count graph -> chained absolute poses -> ``ba_init_in.csv``.
     Returns the reference's ``pair_wise_data`` dictionary (same keys)."""
-    if rel_pose_method not in ("w8pt_ba", "ransac", "ransac_ba"):
-        raise NotImplementedError("relative pose method {} is not defined".format(rel_pose_method))
+    _check_rel_pose_method(rel_pose_method)
     ransac = rel_pose_method != "w8pt_ba"
     min_inliers = 20
     pw = _collect_matches(n_images, data, result, conf_thresh)
@@ -447,12 +447,13 @@ def bundle_adjust_batch(problems, max_iterations=50):
     return [(cams[cam_off[k]:cam_off[k + 1]].copy(), pts[pt_off[k]:pt_off[k + 1]].copy(), _ba_summary(summary[k])) for k in range(n)]
 
 
-def solve_tuple_poses(tuple_size, data, result, tmp_dir):
-    """Pairwise poses -> averaging -> weighted bundle adjustment for one tuple through the reference's four CSV files in
-    ``tmp_dir``; returns the refined world-to-camera extrinsics [tuple_size,4,4]."""
+def solve_tuple_poses(tuple_size, data, result, tmp_dir, rel_pose_method="w8pt_ba"):
+    """Pairwise poses (``rel_pose_method`` as in ``initialize_bundle_adjust``) -> averaging -> weighted bundle adjustment for
+    one tuple through the reference's four CSV files in ``tmp_dir``; returns the refined world-to-camera extrinsics
+    [tuple_size,4,4]."""
     os.makedirs(tmp_dir, exist_ok=True)
     path = lambda name: os.path.join(tmp_dir, name)  # noqa: E731
-    pair_wise_data = initialize_bundle_adjust(tuple_size, data, result, path("ba_init_in.csv"))
+    pair_wise_data = initialize_bundle_adjust(tuple_size, data, result, path("ba_init_in.csv"), rel_pose_method=rel_pose_method)
     run_ba_initializer(tmp_dir)
     start = np.array(read_bundle_adjust_result(path("ba_init_out.csv")))
     write_bundle_adjust_problem(tuple_size, pair_wise_data, start, path("ba_in.csv"))
@@ -528,19 +529,69 @@ def _tuple_init_on_device(tuple_size, T_d, inl, count, min_matches=8, min_inlier
     stream: ``T_d`` [B*P,4,4] float32, ``inl`` [B*P,N] uint8, ``count`` [B*P] int32 device tensors -> ``(extrinsics [B,T,4,4],
     counts [B*P] int32)`` on the host, brought back by ONE device-to-host copy (which is the only synchronisation).  The status
     words stay on the device: a failed averaging is not raised on the host path either."""
+    return _tuple_init_launch(tuple_size, T_d, inl.sum(1, dtype=torch.int32).contiguous(), count, count, min_matches, min_inliers)
+
+
+def _tuple_init_launch(tuple_size, T_d, n_inl, weight, ba_count, min_matches, min_inliers):
+    """``e2emv_mv_tuple_init`` on ``T_d`` [B*P,4,4] float32, ``n_inl`` and ``weight`` [B*P] int32 (a pair is an edge of the match
+    graph iff ``weight >= min_matches``); ``ba_count`` [B*P] int32 rides along in the one copy that brings the start extrinsics
+    back.  Returns ``(extrinsics [B,T,4,4], ba_count)`` on the host."""
     dev = T_d.device
     P = len(_pairs(tuple_size))
     B = T_d.shape[0] // P
-    n_inl = inl.sum(1, dtype=torch.int32).contiguous()
     extr = torch.empty((B, tuple_size * 16), dtype=torch.float64, device=dev)
     status = torch.empty((B,), dtype=torch.int32, device=dev)
-    T_d, count = T_d.contiguous(), count.contiguous()
+    T_d, weight = T_d.contiguous(), weight.contiguous()
     with torch.cuda.device(dev):
-        _lib.context(dev).call("e2emv_mv_tuple_init", B, tuple_size, _lib.ptr(T_d), _lib.ptr(n_inl), _lib.ptr(count), int(min_matches),
+        _lib.context(dev).call("e2emv_mv_tuple_init", B, tuple_size, _lib.ptr(T_d), _lib.ptr(n_inl), _lib.ptr(weight), int(min_matches),
                                int(min_inliers), _lib.ptr(extr), _lib.ptr(status), _lib.stream_ptr(dev))
-    packed = torch.cat([extr, count.reshape(B, P).double()], 1).cpu().numpy()
+    packed = torch.cat([extr, ba_count.reshape(B, P).double()], 1).cpu().numpy()
     start = np.ascontiguousarray(packed[:, :tuple_size * 16]).reshape(B, tuple_size, 4, 4)
     return start, np.ascontiguousarray(packed[:, tuple_size * 16:].astype(np.int32).reshape(-1))
+
+
+def _ransac_on_device(tuple_size, collected, intr, kdim, nb, ba=False, seed=0):
+    """The launch sequence behind the "ransac" / "ransac_ba" relative poses of a batch of tuples, on the buffers of
+    ``_collect_matches_batch`` and the intrinsics of ``_tuple_intrinsics``, nothing read back: ``e2emv_mv_ransac_prepare`` (fp64
+    normalised keypoints, thresholds) -> ``e2emv_essential_ransac`` (threshold 1 pixel, conf 0.99999, 1000 iterations, as
+    ``relative_poses_ransac``) -> ``e2emv_mv_ransac_filter`` (matches reduced to the inliers, pose as 4x4) -> with ``ba`` the
+    two-view bundle adjustment of every solved pair on its inliers, 10 iterations started from the RANSAC pose
+    (``e2emv_ba_2view`` directly: it returns the start of a pair it declares invalid, which is ``T[ok] = refined`` without the
+    host's boolean indexing and its synchronisation).  Per pair what ``relative_poses_ransac`` computes, bit for bit.  Returns a
+    dict of device tensors: ``filtered`` (mkpts0, mkpts1 [B*P,N,2], conf [B*P,N]; a pair that was not solved keeps all its
+    matches), ``T`` [B*P,4,4] float32 (the identity unless solved), ``ba_count`` (rows in use of ``filtered``), ``graph_w``
+    (inliers of a solved pair, else 0) and the stages' own outputs ``kpts0n``, ``kpts1n``, ``thresh``, ``inliers``,
+    ``n_inliers``, ``R``, ``t``, ``status``, ``T0``."""
+    o0, o1, oc, count = collected
+    dev = o0.device
+    ctx = _lib.context(dev)
+    Pn, N = o0.shape[:2]
+    B = Pn // len(_pairs(tuple_size))
+    if N > MAX_MATCHES:
+        raise ValueError("the RANSAC relative poses take at most {} keypoints per image (got {})".format(MAX_MATCHES, N))
+    new = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)  # noqa: E731
+    f32, f64, i32 = torch.float32, torch.float64, torch.int32
+    k0n, k1n, th = new((Pn, N, 2), f64), new((Pn, N, 2), f64), new((Pn,), f64)
+    E, R, t = new((Pn, 3, 3), f64), new((Pn, 3, 3), f64), new((Pn, 3), f64)
+    inl = new((Pn, N), torch.uint8)
+    n_inl, n_ch, iters, status, ba_count, graph_w = (new((Pn,), i32) for _ in range(6))
+    f0, f1, fc, T0 = new((Pn, N, 2), f32), new((Pn, N, 2), f32), new((Pn, N), f32), new((Pn, 4, 4), f32)
+    f0n, f1n, fcn = (new((Pn, N, 2), f32), new((Pn, N, 2), f32), new((Pn, N), f32)) if ba else (None, None, None)
+    pa, owner = _lib.ptr_array(intr)
+    P, s = _lib.ptr, _lib.stream_ptr(dev)
+    with torch.cuda.device(dev):
+        ctx.call("e2emv_mv_ransac_prepare", B, tuple_size, N, P(o0), P(o1), P(count), pa, kdim, nb, 1.0, P(k0n), P(k1n), P(th), s)
+        ctx.call("e2emv_essential_ransac", Pn, N, P(count), P(k0n), P(k1n), P(th), 0.99999, 1000, int(seed) & 0xFFFFFFFF, P(E), P(R), P(t),
+                 P(inl), P(n_inl), P(n_ch), P(iters), P(status), s)
+        ctx.call("e2emv_mv_ransac_filter", B, tuple_size, N, P(o0), P(o1), P(oc), P(count), P(k0n), P(k1n), P(inl), P(n_inl), P(R), P(t),
+                 P(status), P(f0), P(f1), P(fc), P(f0n), P(f1n), P(fcn), P(T0), P(ba_count), P(graph_w), s)
+        T = T0
+        if ba:
+            T, valid = new((Pn, 4, 4), f32), new((Pn,), torch.uint8)
+            ctx.call("e2emv_ba_2view", Pn, N, P(f0n), P(f1n), P(fcn), P(T0), 10, P(T), P(valid), s)
+    del owner
+    return dict(filtered=(f0, f1, fc), T=T, ba_count=ba_count, graph_w=graph_w, kpts0n=k0n, kpts1n=k1n, thresh=th, inliers=inl,
+                n_inliers=n_inl, R=R, t=t, status=status, T0=T0)
 
 
 def _check_init(init):
@@ -548,13 +599,23 @@ def _check_init(init):
         raise ValueError("init must be \"host\" or \"device\", not {!r}".format(init))
 
 
-def solve_tuple_poses_batch(tuple_size, data, result, conf_thresh=0., timings=None, init="host"):
+def _check_rel_pose_method(rel_pose_method):
+    if rel_pose_method not in ("w8pt_ba", "ransac", "ransac_ba"):
+        raise NotImplementedError("relative pose method {} is not defined".format(rel_pose_method))
+
+
+def solve_tuple_poses_batch(tuple_size, data, result, conf_thresh=0., timings=None, init="host", rel_pose_method="w8pt_ba", seed=0):
     """``solve_tuple_poses`` for EVERY batch element of the matcher result, in memory: returns the refined world-to-camera
-    extrinsics ``float64 [B, tuple_size, 4, 4]``, camera 0 the gauge.  Relative poses are "w8pt_ba" only here (the RANSAC
-    methods stay on the CSV path: ``initialize_bundle_adjust(..., rel_pose_method=...)``).  Stages: matches collected on the
-    device (one launch) -> w8pt + two-view BA of all B * T(T-1)/2 pairs -> one copy to the host, spanning tree and rotation /
+    extrinsics ``float64 [B, tuple_size, 4, 4]``, camera 0 the gauge.  Stages: matches collected on the device (one launch) ->
+    relative poses of all B * T(T-1)/2 pairs (``rel_pose_method``) -> one copy to the host, spanning tree and rotation /
     position averaging per tuple (``e2emv_mv_init``) -> all bundle-adjustment problems built on the device (one launch) and
     solved one workgroup per tuple (one launch).  No file, and no element's result depends on its batch neighbours.
+    ``rel_pose_method``: the three of ``initialize_bundle_adjust``.  "w8pt_ba" (default): w8pt + two-view BA; every match goes to
+    the bundle adjustment, pairs with at least 8 matches are the edges of the match graph, weighted by their match count.
+    "ransac" / "ransac_ba": ``_ransac_on_device`` (``seed``: the RANSAC's sample stream; at most 4096 keypoints per image, else
+    ``ValueError``), per pair bit for bit what ``relative_poses_ransac`` gives; the matches of a solved pair are reduced to its
+    inliers on the device, the solved pairs are the edges, weighted by their inlier count, and a pair the RANSAC did not solve
+    keeps all its matches for the bundle adjustment, as on the CSV path.  Another name raises ``NotImplementedError``.
     ``timings``: optional dict that receives the wall time of each stage in seconds (synchronises after every stage).
     ``init``: where the initialisation stage runs.  "host" (default): the loop above.  "device": ``e2emv_mv_tuple_init``, one
     launch for the batch (one wave per tuple: spanning tree, chained start, averaging) enqueued behind the relative poses; match
@@ -562,6 +623,8 @@ def solve_tuple_poses_batch(tuple_size, data, result, conf_thresh=0., timings=No
     section 1), equal match counts of two pairs of a tuple are ordered by ascending (i, j) there and by scipy here."""
     import time
     _check_init(init)
+    _check_rel_pose_method(rel_pose_method)
+    ransac = rel_pose_method != "w8pt_ba"
     pairs = _pairs(tuple_size)
     P = len(pairs)
     clock = [time.perf_counter()]
@@ -579,29 +642,42 @@ def solve_tuple_poses_batch(tuple_size, data, result, conf_thresh=0., timings=No
     B = o0.shape[0] // P
     lap("collect")
     intr, kdim, nb = _tuple_intrinsics(tuple_size, data, dev, B)
-    per_pair = lambda side: torch.stack([intr[pr[side]].expand(B, kdim, kdim) for pr in pairs], 1).reshape(B * P, kdim, kdim).contiguous()  # noqa: E731
-    T_d, inl = _w8pt_ba_on_device(dev, count, o0, o1, oc, per_pair(0), per_pair(1))
+    if ransac:
+        # what the later stages see of a pair: its inliers (n_inl, also its weight in the match graph: 0 = not solved, no edge)
+        # and the rows the bundle adjustment takes from the filtered buffers
+        st = _ransac_on_device(tuple_size, collected, intr, kdim, nb, ba=rel_pose_method == "ransac_ba", seed=seed)
+        collected, T_d, n_inl_d, ba_count_d, min_matches = st["filtered"] + (None,), st["T"], st["graph_w"], st["ba_count"], 1
+    else:
+        per_pair = lambda side: torch.stack([intr[pr[side]].expand(B, kdim, kdim) for pr in pairs], 1).reshape(B * P, kdim, kdim).contiguous()  # noqa: E731
+        T_d, inl = _w8pt_ba_on_device(dev, count, o0, o1, oc, per_pair(0), per_pair(1))
+        ba_count_d, min_matches = count, 8  # success of estimate_relative_pose_w8pt_ba; the match count is the weight
     if init == "device":
         lap("relative_poses")
-        start, counts = _tuple_init_on_device(tuple_size, T_d, inl, count)
+        if ransac:
+            start, counts = _tuple_init_launch(tuple_size, T_d, n_inl_d, n_inl_d, ba_count_d, min_matches, 20)
+        else:
+            start, counts = _tuple_init_on_device(tuple_size, T_d, inl, count)
         lap("initialisation")
         out, summary = np.zeros((B, tuple_size, 4, 4)), np.zeros((B, 4))
         _tuple_ba_call("e2emv_mv_tuple_ba", tuple_size, collected, counts, intr, kdim, nb, start, 50, _p(out), _p(summary))
         lap("build_and_bundle_adjust")
         return out
     # one device -> host copy for the whole batch: poses, inlier counts, match counts
-    packed = torch.cat([T_d.reshape(B * P, 16).double(), inl.sum(1, dtype=torch.int32).double()[:, None], count.double()[:, None]], 1).cpu().numpy()
+    if not ransac:
+        n_inl_d = inl.sum(1, dtype=torch.int32)
+    packed = torch.cat([T_d.reshape(B * P, 16).double(), n_inl_d.double()[:, None], ba_count_d.double()[:, None]], 1).cpu().numpy()
     lap("relative_poses")
     rel_T, n_inl = packed[:, :16].reshape(B, P, 4, 4), packed[:, 16].astype(np.int64).reshape(B, P)
     counts = np.ascontiguousarray(packed[:, 17].astype(np.int32))
+    weight = n_inl if ransac else counts.reshape(B, P)
     start = np.zeros((B, tuple_size, 4, 4))
     for b in range(B):
         graph = np.zeros((tuple_size, tuple_size), dtype=int)
         rel, inlier_count = {}, {}
         for q, (i, j) in enumerate(pairs):
-            if counts[b * P + q] >= 8:  # success of estimate_relative_pose_w8pt_ba
+            if weight[b, q] >= min_matches:
                 rel[(i, j)], inlier_count[(i, j)] = rel_T[b, q], int(n_inl[b, q])
-                graph[i, j] = counts[b * P + q]
+                graph[i, j] = weight[b, q]
         start[b] = _averaged_extrinsics(*_init_arrays(tuple_size, rel, inlier_count, graph)[0])
     lap("initialisation")
     out, summary = np.zeros((B, tuple_size, 4, 4)), np.zeros((B, 4))
@@ -645,10 +721,11 @@ def tuple_pose_errors(extrinsics, cam_to_world):
     return np.minimum(err_t, 180.0 - err_t), np.rad2deg(np.abs(np.arccos(cos_r)))
 
 
-def eval_bundle_adjust(tuple_size, data, result, tmp_dir, pose_errors, verbose=False):
+def eval_bundle_adjust(tuple_size, data, result, tmp_dir, pose_errors, verbose=False, rel_pose_method="w8pt_ba"):
     """``eval_bundle_adjust`` (eval_multi_view.py:21-68): the multi-view back-end for one tuple (batch element 0);
-    extends ``pose_errors = [max errors, translation errors, rotation errors]`` by one entry per image pair."""
-    extrinsics = solve_tuple_poses(tuple_size, data, result, tmp_dir)
+    extends ``pose_errors = [max errors, translation errors, rotation errors]`` by one entry per image pair.
+    ``rel_pose_method``: as in ``initialize_bundle_adjust``."""
+    extrinsics = solve_tuple_poses(tuple_size, data, result, tmp_dir, rel_pose_method=rel_pose_method)
     err_t, err_R = tuple_pose_errors(extrinsics, [data["pose" + str(v)][0].cpu().numpy() for v in range(tuple_size)])
     pose_errors[0].extend(np.maximum(err_t, err_R))
     pose_errors[1].extend(err_t)
@@ -659,11 +736,12 @@ def eval_bundle_adjust(tuple_size, data, result, tmp_dir, pose_errors, verbose=F
     return pose_errors
 
 
-def eval_bundle_adjust_batch(tuple_size, data, result, pose_errors, verbose=False, init="host"):
+def eval_bundle_adjust_batch(tuple_size, data, result, pose_errors, verbose=False, init="host", rel_pose_method="w8pt_ba"):
     """``eval_bundle_adjust`` for every batch element through ``solve_tuple_poses_batch``: extends ``pose_errors = [max errors,
     translation errors, rotation errors]`` by ``B * T(T-1)/2`` entries, batch element outer, pairs in ``_pairs`` order inside
-    (for ``B = 1`` the entries ``eval_bundle_adjust`` appends, in its order).  ``init``: as in ``solve_tuple_poses_batch``."""
-    extrinsics = solve_tuple_poses_batch(tuple_size, data, result, init=init)
+    (for ``B = 1`` the entries ``eval_bundle_adjust`` appends, in its order).  ``init``, ``rel_pose_method``: as in
+    ``solve_tuple_poses_batch``."""
+    extrinsics = solve_tuple_poses_batch(tuple_size, data, result, init=init, rel_pose_method=rel_pose_method)
     poses = np.stack([data["pose" + str(v)].cpu().numpy() for v in range(tuple_size)], 1)  # [B,T,4,4]: one copy per image
     for b, E in enumerate(extrinsics):
         err_t, err_R = tuple_pose_errors(E, poses[b])

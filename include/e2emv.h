@@ -353,6 +353,37 @@ int e2emv_essential_ransac(e2emv_ctx* ctx, int P, int Mmax, const int32_t* d_n_p
                            const double* d_thresh, double conf, int max_iters, uint32_t seed, double* d_E, double* d_R, double* d_t,
                            uint8_t* d_inliers, int32_t* d_n_inliers, int32_t* d_n_cheiral, int32_t* d_iters, int32_t* d_status,
                            void* stream);
+/* The RANSAC relative-pose methods on the batched multi-view path (csrc/mvransac.hip): the device glue between
+ * e2emv_mv_collect, e2emv_essential_ransac, e2emv_ba_2view and e2emv_mv_tuple_init / e2emv_mv_tuple_ba.  B tuples of T
+ * images (2..E2EMV_MAX_TUPLE), problem (b, q) at index b * P + q as in e2emv_mv_collect; DEVICE buffers except d_intr, the
+ * HOST array of T DEVICE pointers [intr_batch,kdim,kdim] of e2emv_mv_tuple_ba; one launch each, one workgroup per problem,
+ * no host synchronisation.  N > 4096 (the RANSAC's limit): E2EMV_ESHAPE.
+ * prepare = ransac.normalize_keypoints + the threshold of estimate_poses_ransac, to the bit: the first d_count[p] rows of
+ * d_mkpts0 / d_mkpts1 [B*P,N,2] fp32 pixels -> d_kpts0n / d_kpts1n [B*P,N,2] fp64, (x - K[.,2]) / K[.,.] with keypoint
+ * and intrinsic widened to fp64 first (image i of the pair for kpts0, image j for kpts1; rows behind the count 0), and
+ * d_thresh [B*P] fp64 = thresh / ((((K_i[0,0] + K_j[1,1]) + K_i[0,0]) + K_j[1,1]) / 4) (upstream's mean, thresh in
+ * pixels, upstream: 1.0): what e2emv_essential_ransac reads.                                                            */
+int e2emv_mv_ransac_prepare(e2emv_ctx* ctx, int B, int T, int N, const float* d_mkpts0, const float* d_mkpts1,
+                            const int32_t* d_count, const float* const* d_intr, int kdim, int intr_batch, double thresh,
+                            double* d_kpts0n, double* d_kpts1n, double* d_thresh, void* stream);
+/* filter = what initialize_bundle_adjust does with a RANSAC result (bundle_adjust_io.py:104-133): the collected buffers, the
+ * outputs of prepare and d_inliers [B*P,N] / d_n_inliers / d_R / d_t / d_status of e2emv_essential_ransac (Mmax = N) ->
+ * (a) d_fkpts0 / d_fkpts1 [B*P,N,2], d_fconf [B*P,N] fp32: the rows of a solved problem (status 0) reduced to its inliers IN
+ *     THEIR ORDER; a problem that was not solved keeps all its rows (the reference filters only on success and hands every
+ *     match of the tuple to the bundle adjustment);
+ * (b) d_fkpts0n / d_fkpts1n / d_fconfn, all three or all NULL: the same rows of the NORMALISED keypoints as fp32 (the fp64
+ *     value rounded once) and their confidences, 0 for a problem that was not solved - the input of e2emv_ba_2view, which
+ *     leaves such a problem at its start;
+ * (c) d_T0 [B*P,4,4] fp32 row-major: R | t rounded from fp64, bottom row 0 0 0 1; the identity unless solved;
+ * (d) d_ba_count [B*P]: rows in use of (a) = d_n_inliers if solved, else d_count;
+ * (e) d_graph_w [B*P]: match-graph weight = d_n_inliers if solved, else 0 (no edge).
+ * Rows behind d_ba_count are 0 in (a) and (b).  The outputs must not alias the inputs.                                  */
+int e2emv_mv_ransac_filter(e2emv_ctx* ctx, int B, int T, int N, const float* d_mkpts0, const float* d_mkpts1,
+                           const float* d_mconf, const int32_t* d_count, const double* d_kpts0n, const double* d_kpts1n,
+                           const uint8_t* d_inliers, const int32_t* d_n_inliers, const double* d_R, const double* d_t,
+                           const int32_t* d_status, float* d_fkpts0, float* d_fkpts1, float* d_fconf, float* d_fkpts0n,
+                           float* d_fkpts1n, float* d_fconfn, float* d_T0, int32_t* d_ba_count, int32_t* d_graph_w,
+                           void* stream);
 /* The 5-point minimal solver alone: n problems of 5 normalised correspondences d_x0, d_x1 [n,5,2] fp64 -> every real
  * essential matrix, d_E [n,10,3,3] (unit Frobenius norm, rows beyond d_nsol[i] zero), d_nsol [n] int32 (0..10). */
 int e2emv_essential_5pt(e2emv_ctx* ctx, int n, const double* d_x0, const double* d_x1, double* d_E, int32_t* d_nsol, void* stream);

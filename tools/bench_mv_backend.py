@@ -7,9 +7,11 @@ split of the batched path (medians of a separate set of calls that synchronise a
 between the two paths' extrinsics.  ``--init`` selects where the batched path runs its initialisation stage: ``host`` (the loop
 over ``e2emv_mv_init``), ``device`` (``e2emv_mv_tuple_init``, one launch) or ``both`` (default): both batched forms are then
 timed inside the same repetition loop, alternating, and the line also carries the device form's figures and the largest
-difference between the two forms' extrinsics.
+difference between the two forms' extrinsics.  ``--rel-pose-method`` selects the relative poses of both paths: ``w8pt_ba``
+(default), ``ransac`` or ``ransac_ba``.
 
     python tools/bench_mv_backend.py [--batch 8] [--tuple-size 5] [--kpts 1024] [--reps 7] [--init host|device|both]
+                                     [--rel-pose-method w8pt_ba|ransac|ransac_ba]
 """
 import argparse
 import json
@@ -33,8 +35,9 @@ def main():
     ap.add_argument("--kpts", type=int, default=1024)
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--init", choices=("host", "device", "both"), default="both")
+    ap.add_argument("--rel-pose-method", choices=("w8pt_ba", "ransac", "ransac_ba"), default="w8pt_ba")
     args = ap.parse_args()
-    B, T = args.batch, args.tuple_size
+    B, T, method = args.batch, args.tuple_size, args.rel_pose_method
     gpu = torch.device("cuda", 0)
     cfg = {"GNN_layers": ["self", "cross"] * 2, "sinkhorn_iterations": 50, "multi_frame_matching": True, "tuple_size": T}
     model = identity_like_state(MultiViewMatcher(cfg).eval()).to(gpu)
@@ -48,12 +51,12 @@ def main():
 
     with tempfile.TemporaryDirectory() as tmp:
         def csv_path():
-            return np.stack([multi_view.solve_tuple_poses(T, d, r, os.path.join(tmp, str(b))) for b, (d, r) in enumerate(slices)])
+            return np.stack([multi_view.solve_tuple_poses(T, d, r, os.path.join(tmp, str(b)), rel_pose_method=method) for b, (d, r) in enumerate(slices)])
 
         forms = ("host", "device") if args.init == "both" else (args.init,)
 
         def batched(init, timings=None):
-            return multi_view.solve_tuple_poses_batch(T, dev, result, timings=timings, init=init)
+            return multi_view.solve_tuple_poses_batch(T, dev, result, timings=timings, init=init, rel_pose_method=method)
 
         def timed(fn):
             torch.cuda.synchronize()
@@ -78,7 +81,7 @@ def main():
                     stages[f].setdefault(k, []).append(v * 1e3)
     stat = lambda ts: {"median": float(np.median(ts)), "min": float(np.min(ts)), "max": float(np.max(ts))}  # noqa: E731
     first = forms[0]  # the form the unsuffixed keys describe: the host form unless --init device
-    line = {"batch": B, "tuple_size": T, "n_kpts": args.kpts, "reps": args.reps, "init": args.init, "csv_path_ms": stat(t_csv),
+    line = {"batch": B, "tuple_size": T, "n_kpts": args.kpts, "reps": args.reps, "init": args.init, "rel_pose_method": method, "csv_path_ms": stat(t_csv),
             "batched_path_ms": stat(t_batch[first]), "batched_stage_ms": {k: float(np.median(v)) for k, v in stages[first].items()},
             "max_abs_extrinsics_difference": float(np.abs(e_csv - e_batch[first]).max())}
     if args.init == "both":
