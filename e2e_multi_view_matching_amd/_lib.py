@@ -101,6 +101,11 @@ SIGNATURES = {
                                   c_void_p, c_void_p, c_void_p]),
     "e2emv_mv_tuple_problem": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, _PP, c_int, c_int, c_void_p,
                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "e2emv_mv_tracks": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, _PP, _PP, c_int, c_float, c_void_p, c_void_p, c_void_p]),
+    "e2emv_mv_tuple_ba_tracks": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, _PP, c_void_p, _PP, _PP, c_int, c_float, _PP,
+                                         c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "e2emv_mv_tuple_problem_tracks": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, _PP, c_void_p, _PP, _PP, c_int, c_float,
+                                              _PP, c_int, c_int, c_void_p] + [c_void_p] * 7),
     "e2emv_mv_init_batch": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                     c_void_p]),
     "e2emv_mv_tuple_init": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),

@@ -29,36 +29,9 @@
 
 #include "common.h"
 #include "mv_host.h"
+#include "mvba.h"
 
 namespace e2emv {
-
-constexpr int kMvThreads = 512;  // 8 waves = 2 per SIMD -> 256 VGPRs each (phase E keeps a 6x6 fp64 block per lane)
-constexpr int kMvWaves = kMvThreads / 64;
-constexpr int kMvMaxCams = E2EMV_MAX_TUPLE;
-constexpr int kMvN = 6 * kMvMaxCams;  // reduced system order bound (48)
-
-struct MvbaArgs {
-    int C, fixed, P, O, max_iters;
-    double fx, fy, cx, cy;
-    const int *cam_idx, *pt_idx, *pt_start, *pt_obs, *cam_start, *cam_obs;
-    const double *obs, *wts;
-    double *cams, *pts;
-    double *r, *Jc, *Jp, *Y, *Vinv, *gp, *dp, *scale_p, *cand;
-    double* summary;  // [0] initial cost [1] final cost [2] iterations [3] termination code
-};
-
-enum { kTermMaxIter = 0, kTermGradient = 1, kTermParameter = 2, kTermFunction = 3, kTermInvalid = 4, kTermRadius = 5 };
-
-__device__ __forceinline__ double mv_wsum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-__device__ __forceinline__ double mv_wmax(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
-    return v;
-}
 
 // block-wide reduction of up to 4 values (sum for k < nsum, max for the rest); all threads get the result
 template <int NV, int NSUM>
@@ -507,63 +480,6 @@ __global__ __launch_bounds__(kMvThreads) void mvba_kernel(const MvbaArgs* __rest
     }
 }
 
-// homogeneous DLT of two views (cv2.triangulatePoints at bundle_adjust_io.py:226-227): P0, P1 [3,4] row-major
-__device__ __forceinline__ void mv_dlt(const double* P0, const double* P1, double x0x, double x0y, double x1x, double x1y, double* xyz) {
-    double A[16];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        A[k] = x0x * P0[8 + k] - P0[k];
-        A[4 + k] = x0y * P0[8 + k] - P0[4 + k];
-        A[8 + k] = x1x * P1[8 + k] - P1[k];
-        A[12 + k] = x1y * P1[8 + k] - P1[4 + k];
-    }
-    // smallest eigenvector of A^T A by cyclic Jacobi (fp64)
-    double M[16], V[16];
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            M[4 * r + c] = A[r] * A[c] + A[4 + r] * A[4 + c] + A[8 + r] * A[8 + c] + A[12 + r] * A[12 + c];
-            V[4 * r + c] = r == c ? 1.0 : 0.0;
-        }
-    for (int sweep = 0; sweep < 30; ++sweep) {
-        double off = 0;
-        for (int p = 0; p < 4; ++p)
-            for (int q = p + 1; q < 4; ++q) off += M[4 * p + q] * M[4 * p + q];
-        if (off < 1e-300) break;
-        for (int p = 0; p < 4; ++p)
-            for (int q = p + 1; q < 4; ++q) {
-                const double apq = M[4 * p + q];
-                if (apq == 0.0) continue;
-                const double theta = (M[4 * q + q] - M[4 * p + p]) / (2.0 * apq);
-                const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-                const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-                for (int k = 0; k < 4; ++k) {
-                    const double mkp = M[4 * k + p], mkq = M[4 * k + q];
-                    M[4 * k + p] = c * mkp - s * mkq;
-                    M[4 * k + q] = s * mkp + c * mkq;
-                }
-                for (int k = 0; k < 4; ++k) {
-                    const double mpk = M[4 * p + k], mqk = M[4 * q + k];
-                    M[4 * p + k] = c * mpk - s * mqk;
-                    M[4 * q + k] = s * mpk + c * mqk;
-                }
-                for (int k = 0; k < 4; ++k) {
-                    const double vkp = V[4 * k + p], vkq = V[4 * k + q];
-                    V[4 * k + p] = c * vkp - s * vkq;
-                    V[4 * k + q] = s * vkp + c * vkq;
-                }
-            }
-    }
-    int m = 0;
-    for (int k = 1; k < 4; ++k)
-        if (M[5 * k] < M[5 * m]) m = k;
-    const double w = V[12 + m];
-    xyz[0] = V[m] / w;
-    xyz[1] = V[4 + m] / w;
-    xyz[2] = V[8 + m] / w;
-}
-
 // one thread per point
 __global__ void mv_triangulate_kernel(int n, const double* P0, const double* P1, const double* x0, const double* x1, double* xyz) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -573,9 +489,6 @@ __global__ void mv_triangulate_kernel(int n, const double* P0, const double* P1,
 
 
 // ---- the in-memory path for a whole batch of tuples (multi_view.solve_tuple_poses_batch) ---------------------------------------
-constexpr int kMvMaxPairs = kMvMaxCams * (kMvMaxCams - 1) / 2;
-constexpr int kMvRowThreads = 256;
-
 struct MvCollectArgs {
     int B, P, N, channels;  // problems = B * P, problem (b, q) at index b * P + q; N = keypoints of the first image = row stride
     float thresh;
@@ -704,18 +617,8 @@ __global__ __launch_bounds__(kMvRowThreads) void mv_build_kernel(MvBuildArgs g) 
     mv_dlt(g.proj + size_t(b * g.T + rec.i) * 12, g.proj + size_t(b * g.T + rec.j) * 12, x[0], x[1], x[2], x[3], a.pts + 3 * size_t(pt));
 }
 
-// Device memory of a batch of problems inside the context workspace.  First what the host uploads in one piece (records, start
-// cameras, camera list starts, `extra` bytes of the caller), then the per-observation / per-point arrays; problem k owns the
-// slice behind its camera / point / observation offsets in each of them.
-struct MvLayout {
-    MvbaArgs* recs; double* cams; int* cam_start; char* extra;
-    size_t upload_bytes;
-    double *pts, *gp, *dp, *scale_p, *cand, *Vinv, *obs, *wts, *r, *Jc, *Jp, *Y, *summary;
-    int *cam_idx, *pt_idx, *pt_obs, *cam_obs, *pt_start;
-    size_t bytes;
-};
-
-static MvLayout mv_layout(char* base, size_t n, size_t totC, size_t totP, size_t totO, size_t extra) {
+// (MvLayout: mvba.h)
+MvLayout mv_layout(char* base, size_t n, size_t totC, size_t totP, size_t totO, size_t extra) {
     MvLayout L{};
     size_t off = 0;
     auto take = [&](size_t bytes) { char* q = base + off; off += (bytes + 255) & ~size_t(255); return q; };
@@ -735,8 +638,8 @@ static MvLayout mv_layout(char* base, size_t n, size_t totC, size_t totP, size_t
 }
 
 // record of problem k: its sizes and its slices (c0 / p0 / o0 = cameras / points / observations of the problems before it)
-static MvbaArgs mv_record(const MvLayout& L, size_t k, size_t c0, size_t p0, size_t o0, int C, int fixed, int P, int O, int max_iters,
-                          const double* intr) {
+MvbaArgs mv_record(const MvLayout& L, size_t k, size_t c0, size_t p0, size_t o0, int C, int fixed, int P, int O, int max_iters,
+                   const double* intr) {
     MvbaArgs a{};
     a.C = C; a.fixed = fixed; a.P = P; a.O = O; a.max_iters = max_iters;
     a.fx = intr[0]; a.fy = intr[1]; a.cx = intr[2]; a.cy = intr[3];
@@ -750,7 +653,7 @@ static MvbaArgs mv_record(const MvLayout& L, size_t k, size_t c0, size_t p0, siz
     return a;
 }
 
-static int mv_launch_ba(e2emv_ctx* ctx, const MvLayout& L, int n, hipStream_t s) {
+int mv_launch_ba(e2emv_ctx* ctx, const MvLayout& L, int n, hipStream_t s) {
     prof_begin(ctx, PS_W8PT, s);
     hipLaunchKernelGGL(mvba_kernel, dim3(n), dim3(kMvThreads), 0, s, L.recs);
     E2EMV_CHECK_LAUNCH(ctx, "mvba_kernel");
@@ -758,12 +661,12 @@ static int mv_launch_ba(e2emv_ctx* ctx, const MvLayout& L, int n, hipStream_t s)
     return E2EMV_OK;
 }
 
-static void mv_extr_to_cam(const double* E /* 4x4 row-major */, double* cam) {
+void mv_extr_to_cam(const double* E /* 4x4 row-major */, double* cam) {
     const double R[9] = {E[0], E[4], E[8], E[1], E[5], E[9], E[2], E[6], E[10]};  // column-major
     mv::R_to_aa(R, cam);
     cam[3] = E[3]; cam[4] = E[7]; cam[5] = E[11];
 }
-static void mv_cam_to_extr(const double* cam, double* E) {
+void mv_cam_to_extr(const double* cam, double* E) {
     double R[9];
     mv::aa_to_R(cam, R);
     for (int r = 0; r < 3; ++r) {

@@ -1,0 +1,552 @@
+// Track merging for the batched multi-view back-end: the pairwise matches of a T-tuple become tracks (one 3-D point per scene
+// point, seen by 2 .. T images) and the bundle-adjustment problem is built from the tracks instead of one point per match.
+//
+// Semantics (DESIGN.md section 1 quotes them):
+//   node      keypoint n of image t of tuple b, id t * Nmax + n, Nmax = the label row stride (the largest keypoint count)
+//   edge      pair q = (i, j) in the order of e2emv_mv_collect: every keypoint n of image i that mv_collect_kernel keeps
+//             (0 <= match < n_kpts_j, every confidence channel > conf_thresh) joins (i, n) and (j, match) and carries the
+//             confidence of channel 0; a pair without matches has no edge
+//   label     the smallest node id of the node's connected component (a unique fixed point: any propagation order ends there)
+//   track     a component of >= 2 nodes with AT MOST ONE node per image; a component with two keypoints of one image is a
+//             conflict and contributes nothing
+//   problem   points = tracks in ascending label, observations of a point in ascending image, concatenated in point order;
+//             index lists as e2emv_mv_bundle_adjust_batch builds them; camera 0 fixed, f = 1, c = 0
+//   weight    node confidence = fp64 mean of its kept edges' confidences (ascending other image); weights = confidence /
+//             (0.5 (sum + 1e-3)), sum over the tuple's observations in a fixed order
+//   start     homogeneous DLT over the k views (rows x P[2] - P[0], y P[2] - P[1]), smallest eigenvector of the 4x4 normal
+//             matrix by the cyclic Jacobi of mv_dlt; for k = 2 mv_dlt itself
+// Nothing crosses tuples, no floating-point atomics: a tuple's labels, problem and solution are bit-identical alone, at any batch
+// position and run to run.  The integer LDS atomics used (min, or, add) have order-independent results.
+//
+// LIMIT: T * Nmax <= 16384 nodes per tuple (8 images of 2048 keypoints): mv_tracks_kernel keeps a 32-bit label per node (native
+// LDS atomic min; 16 bits would do for the ids but LDS has no 16-bit atomic), 8 image bits and one conflict bit per root in LDS
+// = 5.125 bytes per node, 82 KiB at the limit, of the 160 KiB one workgroup may declare on gfx950.  Above the limit the entry
+// points return E2EMV_ESHAPE before any launch.
+#include <algorithm>
+#include <cstdint>
+#include <cstring>
+
+#include "common.h"
+#include "mv_host.h"
+#include "mvba.h"
+
+namespace e2emv {
+
+constexpr int kMvTrackThreads = 1024;
+constexpr int kMvTrackMaxNodes = 16384;
+
+struct MvEdgeArgs {
+    int B, T, P, N, Nmax, channels;  // N = rows of every match array (keypoints of a pair's first image), Nmax = label row stride
+    float thresh;
+    int n1[kMvMaxPairs];                // keypoints of the second image
+    unsigned char pi[kMvMaxPairs], pj[kMvMaxPairs];
+    const int64_t* match[kMvMaxPairs];  // [B,N] or NULL (no matches for this pair)
+    const float* conf[kMvMaxPairs];     // [B,N,channels]
+};
+
+// the match of keypoint n of the first image of pair q of tuple b when mv_collect_kernel keeps it (the edge), else -1; *c0 its
+// confidence (channel 0)
+__device__ __forceinline__ int mv_edge(const MvEdgeArgs& a, int b, int q, int n, float* c0) {
+    const int64_t* match = a.match[q];
+    if (!match) return -1;
+    const size_t row = size_t(b) * a.N + n;
+    const int64_t m = match[row];
+    bool keep = m >= 0 && m < a.n1[q];
+    const float* conf = a.conf[q] + row * a.channels;
+    for (int c = 0; c < a.channels; ++c) keep = keep && conf[c] > a.thresh;
+    if (c0) *c0 = conf[0];
+    return keep ? int(m) : -1;
+}
+
+__device__ __forceinline__ int mv_pair_index(int i, int j) { return j * (j - 1) / 2 + i; }  // i < j, j outer
+
+// Connected components of one tuple per workgroup, labels in LDS: min-label propagation over the edges (atomic min on the larger
+// label's node and on the edge's own end) followed by pointer jumping (every label is a node of the same component with an id
+// not above the node's, so chains end at a root), until a sweep changes nothing.  Labels only decrease, so the loop ends; the
+// bound of `nodes` sweeps holds whatever the input.  Then the images of every component are OR-ed into 8 bits of its root, a
+// second hit of a set bit marks the conflict, and every node writes its track's label or -1.
+// stats[b] = {tracks, observations (nodes in tracks), conflict components, edges}.
+__global__ __launch_bounds__(kMvTrackThreads) void mv_tracks_kernel(MvEdgeArgs a, int* __restrict__ out_label, int* __restrict__ out_stats) {
+    extern __shared__ __attribute__((aligned(16))) int s_trk[];
+    __shared__ int s_changed, s_stats[4];
+    const int b = blockIdx.x, tid = threadIdx.x, nodes = a.T * a.Nmax, n_edges = a.P * a.N;
+    int* s_label = s_trk;                                                 // [nodes]
+    unsigned* s_mask = reinterpret_cast<unsigned*>(s_trk + nodes);         // [(nodes + 3) / 4]: 8 image bits per root
+    unsigned* s_bad = s_mask + (nodes + 3) / 4;                            // [(nodes + 31) / 32]: conflict bit per root
+    for (int x = tid; x < nodes; x += kMvTrackThreads) s_label[x] = x;
+    for (int x = tid; x < (nodes + 3) / 4; x += kMvTrackThreads) s_mask[x] = 0u;
+    for (int x = tid; x < (nodes + 31) / 32; x += kMvTrackThreads) s_bad[x] = 0u;
+    if (tid < 4) s_stats[tid] = 0;
+    int edges = 0;
+    for (int sweep = 0; sweep < nodes; ++sweep) {
+        if (tid == 0) s_changed = 0;
+        __syncthreads();
+        bool changed = false;
+        for (int e = tid; e < n_edges; e += kMvTrackThreads) {
+            const int q = e / a.N, n = e - q * a.N;
+            const int m = mv_edge(a, b, q, n, nullptr);
+            if (m < 0) continue;
+            if (sweep == 0) ++edges;
+            const int x = a.pi[q] * a.Nmax + n, y = a.pj[q] * a.Nmax + m;
+            const int lx = s_label[x], ly = s_label[y];
+            if (lx == ly) continue;
+            const int lo = min(lx, ly), hi = max(lx, ly);
+            atomicMin(&s_label[hi], lo);
+            atomicMin(&s_label[lx > ly ? x : y], lo);
+            changed = true;
+        }
+        if (changed) s_changed = 1;
+        __syncthreads();
+        for (int x = tid; x < nodes; x += kMvTrackThreads) {
+            int l = s_label[x];
+            while (true) {
+                const int up = s_label[l];
+                if (up == l) break;
+                l = up;
+            }
+            s_label[x] = l;
+        }
+        const int again = s_changed;
+        __syncthreads();
+        if (!again) break;
+    }
+    for (int x = tid; x < nodes; x += kMvTrackThreads) {
+        const int t = x / a.Nmax, r = s_label[x];
+        const unsigned bit = 1u << (t + 8 * (r & 3));
+        if (atomicOr(&s_mask[r >> 2], bit) & bit) atomicOr(&s_bad[r >> 5], 1u << (r & 31));
+    }
+    __syncthreads();
+    int tracks = 0, obs = 0, bad = 0;
+    for (int x = tid; x < nodes; x += kMvTrackThreads) {
+        const int r = s_label[x];
+        const int views = __popc((s_mask[r >> 2] >> (8 * (r & 3))) & 0xffu);
+        const bool conflict = (s_bad[r >> 5] >> (r & 31)) & 1u, valid = !conflict && views >= 2;
+        out_label[size_t(b) * nodes + x] = valid ? r : -1;
+        if (r == x) { tracks += valid; obs += valid ? views : 0; bad += conflict; }
+    }
+    atomicAdd(&s_stats[0], tracks); atomicAdd(&s_stats[1], obs); atomicAdd(&s_stats[2], bad); atomicAdd(&s_stats[3], edges);
+    __syncthreads();
+    if (tid < 4) out_stats[4 * b + tid] = s_stats[tid];
+}
+
+// dehomogenised smallest eigenvector of the symmetric 4x4 M (row-major, destroyed): the cyclic Jacobi of mv_dlt, statement for
+// statement, for the normal matrix of k >= 3 views (mv_dlt keeps its own copy: its kernels compile to the code they always had)
+__device__ __forceinline__ void mv_null4(double* M, double* xyz) {
+    double V[16];
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) V[4 * r + c] = r == c ? 1.0 : 0.0;
+    for (int sweep = 0; sweep < 30; ++sweep) {
+        double off = 0;
+        for (int p = 0; p < 4; ++p)
+            for (int q = p + 1; q < 4; ++q) off += M[4 * p + q] * M[4 * p + q];
+        if (off < 1e-300) break;
+        for (int p = 0; p < 4; ++p)
+            for (int q = p + 1; q < 4; ++q) {
+                const double apq = M[4 * p + q];
+                if (apq == 0.0) continue;
+                const double theta = (M[4 * q + q] - M[4 * p + p]) / (2.0 * apq);
+                const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+                const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+                for (int k = 0; k < 4; ++k) {
+                    const double mkp = M[4 * k + p], mkq = M[4 * k + q];
+                    M[4 * k + p] = c * mkp - s * mkq;
+                    M[4 * k + q] = s * mkp + c * mkq;
+                }
+                for (int k = 0; k < 4; ++k) {
+                    const double mpk = M[4 * p + k], mqk = M[4 * q + k];
+                    M[4 * p + k] = c * mpk - s * mqk;
+                    M[4 * q + k] = s * mpk + c * mqk;
+                }
+                for (int k = 0; k < 4; ++k) {
+                    const double vkp = V[4 * k + p], vkq = V[4 * k + q];
+                    V[4 * k + p] = c * vkp - s * vkq;
+                    V[4 * k + q] = s * vkp + c * vkq;
+                }
+            }
+    }
+    int m = 0;
+    for (int k = 1; k < 4; ++k)
+        if (M[5 * k] < M[5 * m]) m = k;
+    const double w = V[12 + m];
+    xyz[0] = V[m] / w;
+    xyz[1] = V[4 + m] / w;
+    xyz[2] = V[8 + m] / w;
+}
+
+struct MvEmitArgs {
+    MvEdgeArgs e;
+    int kdim, intr_batch;
+    int n_img[kMvMaxCams];          // keypoints of every image
+    const float* kpts[kMvMaxCams];  // [B,n_img[t],2]
+    const float* intr[kMvMaxCams];  // [intr_batch,kdim,kdim]
+    const int* label;               // [B,T,Nmax] of mv_tracks_kernel
+    const double* proj;             // [B,T,3,4] world -> camera
+    int* member;                    // [points of the batch,T] scratch: the keypoint of image t in the point, or -1
+    const MvbaArgs* recs;           // [B] the problems being built
+};
+
+// The track problem of one tuple per workgroup, from its labels.  Roots (label == own id) in ascending id are the points (ordered
+// compaction: ballot prefix inside a wave, wave totals through LDS, a running base over the chunks of 256, as mv_collect_kernel);
+// every labelled node enters its point's row of `member`.  Then per point: observation offset = exclusive prefix of the view
+// counts, position in camera t's list = number of earlier points seen by t (the same compaction per camera), both ascending
+// in the observation index as the host lists of e2emv_mv_bundle_adjust_batch.  Every write is bounded by the record's sizes: a
+// label array that disagrees with the counts the record was sized from gives a wrong problem, not a write outside it.
+__global__ __launch_bounds__(kMvRowThreads) void mv_tracks_emit_kernel(MvEmitArgs g) {
+    extern __shared__ __attribute__((aligned(16))) unsigned short s_pidx[];  // [nodes]: point of a root, 0xffff otherwise
+    __shared__ int s_wave[(kMvMaxCams + 1) * (kMvRowThreads / 64)], s_cnt[kMvMaxCams], s_cstart[kMvMaxCams + 1];
+    __shared__ double s_red[kMvRowThreads / 64];
+    const MvEdgeArgs& e = g.e;
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int T = e.T, Nmax = e.Nmax, nodes = T * Nmax;
+    const MvbaArgs& a = g.recs[b];
+    const int P = a.P, O = a.O;
+    int* member = g.member + size_t(a.pts - g.recs[0].pts) / 3 * T;
+    const int* label = g.label + size_t(b) * nodes;
+    int* cam_idx = const_cast<int*>(a.cam_idx); int* pt_idx = const_cast<int*>(a.pt_idx);
+    int* pt_start = const_cast<int*>(a.pt_start); int* pt_obs = const_cast<int*>(a.pt_obs);
+    int* cam_start = const_cast<int*>(a.cam_start); int* cam_obs = const_cast<int*>(a.cam_obs);
+    double* obs = const_cast<double*>(a.obs); double* wts = const_cast<double*>(a.wts);
+    const unsigned long long below = (1ull << lane) - 1ull;
+
+    for (int i = tid; i < P * T; i += kMvRowThreads) member[i] = -1;
+    if (tid < kMvMaxCams) s_cnt[tid] = 0;
+    int base = 0;
+    for (int c0 = 0; c0 < nodes; c0 += kMvRowThreads) {
+        const int x = c0 + tid;
+        const bool root = x < nodes && label[x] == x;
+        const unsigned long long mask = __ballot(root);
+        if (lane == 0) s_wave[wave] = __popcll(mask);
+        __syncthreads();
+        int off = base + __popcll(mask & below), total = 0;
+        for (int w = 0; w < kMvRowThreads / 64; ++w) {
+            if (w < wave) off += s_wave[w];
+            total += s_wave[w];
+        }
+        if (x < nodes) s_pidx[x] = (root && off < P) ? (unsigned short)off : (unsigned short)0xffff;
+        base += total;
+        __syncthreads();
+    }
+    int cnt[kMvMaxCams];
+#pragma unroll
+    for (int t = 0; t < kMvMaxCams; ++t) cnt[t] = 0;
+    for (int x = tid; x < nodes; x += kMvRowThreads) {
+        const int L = label[x], t = x / Nmax, n = x - t * Nmax;
+        if (L < 0 || L >= nodes || n >= g.n_img[t]) continue;
+        const int p = s_pidx[L];
+        if (p >= P) continue;
+        member[p * T + t] = n;
+#pragma unroll
+        for (int u = 0; u < kMvMaxCams; ++u) cnt[u] += (u == t);
+    }
+#pragma unroll
+    for (int t = 0; t < kMvMaxCams; ++t)
+        if (cnt[t]) atomicAdd(&s_cnt[t], cnt[t]);
+    __syncthreads();  // the rows of `member` and the camera totals are complete
+    if (tid == 0) {
+        int c = 0;
+        for (int t = 0; t < T; ++t) { s_cstart[t] = c; cam_start[t] = c; c += s_cnt[t]; }
+        s_cstart[T] = c; cam_start[T] = c;
+        pt_start[P] = O;
+    }
+    __syncthreads();
+
+    int o_base = 0, c_base[kMvMaxCams];
+#pragma unroll
+    for (int t = 0; t < kMvMaxCams; ++t) c_base[t] = 0;
+    double conf_sum = 0.0;
+    for (int c0 = 0; c0 < P; c0 += kMvRowThreads) {
+        const int p = c0 + tid;
+        int mem[kMvMaxCams], k = 0;
+#pragma unroll
+        for (int t = 0; t < kMvMaxCams; ++t) {
+            mem[t] = (p < P && t < T) ? member[p * T + t] : -1;
+            k += mem[t] >= 0;
+        }
+        // exclusive prefix of the view counts: inclusive scan inside the wave, then the waves in front
+        int incl = k;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const int up = __shfl_up(incl, d);
+            if (lane >= d) incl += up;
+        }
+        int rank[kMvMaxCams];
+#pragma unroll
+        for (int t = 0; t < kMvMaxCams; ++t) {
+            const unsigned long long mask = __ballot(mem[t] >= 0);
+            rank[t] = __popcll(mask & below);
+            if (lane == 0) s_wave[(t + 1) * (kMvRowThreads / 64) + wave] = __popcll(mask);
+        }
+        if (lane == 63) s_wave[wave] = incl;
+        __syncthreads();
+        int o0 = o_base + incl - k;
+        for (int w = 0; w < kMvRowThreads / 64; ++w) {
+            if (w < wave) o0 += s_wave[w];
+            o_base += s_wave[w];
+        }
+#pragma unroll
+        for (int t = 0; t < kMvMaxCams; ++t) {
+            rank[t] += c_base[t];
+            for (int w = 0; w < kMvRowThreads / 64; ++w) {
+                const int tot = s_wave[(t + 1) * (kMvRowThreads / 64) + w];
+                if (w < wave) rank[t] += tot;
+                c_base[t] += tot;
+            }
+        }
+        if (p < P && o0 + k <= O) {
+            pt_start[p] = o0;
+            double x[2 * kMvMaxCams];
+            int o = o0;
+#pragma unroll
+            for (int t = 0; t < kMvMaxCams; ++t) {
+                x[2 * t] = 0.0; x[2 * t + 1] = 0.0;
+                if (mem[t] < 0) continue;
+                const float* K = g.intr[t] + (g.intr_batch == 1 ? 0 : size_t(b) * g.kdim * g.kdim);
+                const float* kp = g.kpts[t] + (size_t(b) * g.n_img[t] + mem[t]) * 2;
+                // pixel -> normalised camera coordinates in fp32 like mv_build_kernel: one rounded subtraction, one rounded division
+                const float xn = (kp[0] - K[2]) / K[0], yn = (kp[1] - K[g.kdim + 2]) / K[g.kdim + 1];
+                x[2 * t] = double(xn); x[2 * t + 1] = double(yn);
+                // confidence of the node: mean of its kept edges, other image ascending
+                double cs = 0.0;
+                int ce = 0;
+#pragma unroll
+                for (int u = 0; u < kMvMaxCams; ++u) {
+                    if (u == t || mem[u] < 0) continue;
+                    float c = 0.f;
+                    int m = -1;
+                    if (u < t) {
+                        if (mem[u] < e.N) m = mv_edge(e, b, mv_pair_index(u, t), mem[u], &c);
+                        if (m != mem[t]) continue;
+                    } else {
+                        if (mem[t] < e.N) m = mv_edge(e, b, mv_pair_index(t, u), mem[t], &c);
+                        if (m != mem[u]) continue;
+                    }
+                    cs += double(c);
+                    ++ce;
+                }
+                const double cn = ce ? cs / double(ce) : 0.0;
+                conf_sum += cn;
+                cam_idx[o] = t; pt_idx[o] = p; pt_obs[o] = o;
+                obs[2 * o] = x[2 * t]; obs[2 * o + 1] = x[2 * t + 1];
+                wts[2 * o] = cn;
+                const int slot = s_cstart[t] + rank[t];
+                if (slot < O) cam_obs[slot] = o;
+                ++o;
+            }
+            const double* proj = g.proj + size_t(b) * T * 12;
+            double* X = a.pts + 3 * size_t(p);
+            if (k == 2) {
+                int t0 = -1, t1 = -1;
+#pragma unroll
+                for (int t = kMvMaxCams - 1; t >= 0; --t)
+                    if (mem[t] >= 0) { t1 = t1 < 0 ? t : t1; t0 = t; }
+                double x0x = 0, x0y = 0, x1x = 0, x1y = 0;
+#pragma unroll
+                for (int t = 0; t < kMvMaxCams; ++t) {
+                    if (t == t0) { x0x = x[2 * t]; x0y = x[2 * t + 1]; }
+                    if (t == t1) { x1x = x[2 * t]; x1y = x[2 * t + 1]; }
+                }
+                mv_dlt(proj + 12 * t0, proj + 12 * t1, x0x, x0y, x1x, x1y, X);
+            } else {
+                double M[16];
+#pragma unroll
+                for (int i = 0; i < 16; ++i) M[i] = 0.0;
+#pragma unroll
+                for (int t = 0; t < kMvMaxCams; ++t) {
+                    if (mem[t] < 0) continue;
+                    const double* Pm = proj + 12 * t;
+                    double r0[4], r1[4];
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) {
+                        r0[c] = x[2 * t] * Pm[8 + c] - Pm[c];
+                        r1[c] = x[2 * t + 1] * Pm[8 + c] - Pm[4 + c];
+                    }
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+#pragma unroll
+                        for (int c = 0; c < 4; ++c) M[4 * r + c] += r0[r] * r0[c] + r1[r] * r1[c];
+                }
+                mv_null4(M, X);
+            }
+        }
+        __syncthreads();
+    }
+    // sum of the node confidences in a fixed order (points strided over the threads, then lanes, then waves), the weights
+    conf_sum = mv_wsum(conf_sum);
+    if (lane == 0) s_red[wave] = conf_sum;
+    __syncthreads();
+    double total = s_red[0];
+    for (int w = 1; w < kMvRowThreads / 64; ++w) total += s_red[w];
+    const double half_total = 0.5 * (total + 1e-3);
+    for (int o = tid; o < O; o += kMvRowThreads) {
+        const double w = wts[2 * o] / half_total;
+        wts[2 * o] = w; wts[2 * o + 1] = w;
+    }
+}
+
+// argument checks and the edge description shared by the three entry points
+static int mv_edge_args(e2emv_ctx* ctx, const char* who, int B, int T, int N, int Nmax, const int32_t* n1, const int64_t* const* d_matches,
+                        const float* const* d_conf, int channels, float thresh, MvEdgeArgs* a) {
+    if (B < 1 || N < 1 || channels < 1 || !n1 || !d_matches || !d_conf) return set_err(ctx, E2EMV_EINVAL, "%s: bad argument (B, N, conf_channels >= 1, no NULL array)", who);
+    if (T < 2 || T > kMvMaxCams) return set_err(ctx, E2EMV_EINVAL, "%s: tuple of %d images (2 <= T <= %d)", who, T, kMvMaxCams);
+    *a = MvEdgeArgs{};
+    a->B = B; a->T = T; a->P = T * (T - 1) / 2; a->N = N; a->channels = channels; a->thresh = thresh;
+    int q = 0, widest = N;
+    for (int j = 0; j < T; ++j)
+        for (int i = 0; i < j; ++i, ++q) {
+            if (d_matches[q] && (!d_conf[q] || n1[q] < 1)) return set_err(ctx, E2EMV_EINVAL, "%s: pair %d has matches but no confidences / keypoints", who, q);
+            a->match[q] = d_matches[q]; a->conf[q] = d_conf[q]; a->n1[q] = d_matches[q] ? n1[q] : 0;
+            a->pi[q] = (unsigned char)i; a->pj[q] = (unsigned char)j;
+            widest = std::max(widest, int(n1[q]));  // also of a pair without matches: the stride covers every image the caller names
+        }
+    a->Nmax = Nmax > 0 ? Nmax : widest;
+    if (a->Nmax < widest) return set_err(ctx, E2EMV_ESHAPE, "%s: label stride %d below the keypoint count %d", who, a->Nmax, widest);
+    if (size_t(T) * size_t(a->Nmax) > size_t(kMvTrackMaxNodes))
+        return set_err(ctx, E2EMV_ESHAPE, "%s: %d images of up to %d keypoints are %zu nodes (limit %d)", who, T, a->Nmax, size_t(T) * a->Nmax, kMvTrackMaxNodes);
+    if (size_t(B) * T * a->Nmax > size_t(INT32_MAX) / 64) return set_err(ctx, E2EMV_ESHAPE, "%s: B * T * Nmax = %zu is too large", who, size_t(B) * T * a->Nmax);
+    return E2EMV_OK;
+}
+
+// the track problems of the B tuples in the workspace, described by *L (the counterpart of mv_tuple_build)
+static int mv_tracks_build(e2emv_ctx* ctx, const char* who, int B, int T, int N, int Nmax, const int32_t* d_label, const int32_t* stats,
+                           const float* const* d_kpts, const int32_t* n_kpts, const int64_t* const* d_matches, const float* const* d_conf,
+                           int channels, float thresh, const float* const* d_intr, int kdim, int intr_batch, const double* extr,
+                           int max_iterations, MvLayout* L, size_t* totP_out, size_t* totO_out, hipStream_t s) {
+    if (!d_label || !stats || !d_kpts || !n_kpts || !d_intr || !extr || Nmax < 1) return set_err(ctx, E2EMV_EINVAL, "%s: bad argument (Nmax >= 1, no NULL array)", who);
+    if (T < 2 || T > kMvMaxCams) return set_err(ctx, E2EMV_EINVAL, "%s: tuple of %d images (2 <= T <= %d)", who, T, kMvMaxCams);
+    if (kdim != 3 && kdim != 4) return set_err(ctx, E2EMV_ESHAPE, "%s: intrinsics must be 3x3 or 4x4", who);
+    if (intr_batch != 1 && intr_batch != B) return set_err(ctx, E2EMV_ESHAPE, "%s: intr_batch must be 1 or B", who);
+    int32_t n1[kMvMaxPairs];
+    int q = 0;
+    for (int j = 0; j < T; ++j)
+        for (int i = 0; i < j; ++i, ++q) n1[q] = n_kpts[j];
+    MvEmitArgs g{};
+    int rc = mv_edge_args(ctx, who, B, T, N, Nmax, n1, d_matches, d_conf, channels, thresh, &g.e);
+    if (rc) return rc;
+    for (int t = 0; t < T; ++t) {
+        if (!d_intr[t] || !d_kpts[t]) return set_err(ctx, E2EMV_EINVAL, "%s: NULL intrinsics / keypoints of image %d", who, t);
+        if (n_kpts[t] < 1 || n_kpts[t] > Nmax) return set_err(ctx, E2EMV_EINVAL, "%s: image %d has %d keypoints (1 <= n <= Nmax = %d)", who, t, n_kpts[t], Nmax);
+        g.n_img[t] = n_kpts[t]; g.kpts[t] = d_kpts[t]; g.intr[t] = d_intr[t];
+    }
+    q = 0;
+    for (int j = 0; j < T; ++j)
+        for (int i = 0; i < j; ++i, ++q)
+            if (d_matches[q] && n_kpts[i] < N) return set_err(ctx, E2EMV_EINVAL, "%s: pair %d has %d match rows but image %d only %d keypoints", who, q, N, i, n_kpts[i]);
+    size_t totP = 0, totO = 0;
+    for (int b = 0; b < B; ++b) {
+        const int Pb = stats[4 * b], Ob = stats[4 * b + 1];
+        if (Pb < 0 || Ob < 2 * Pb || Ob > T * Pb || Ob > T * Nmax)
+            return set_err(ctx, E2EMV_EINVAL, "%s: tuple %d counts %d tracks / %d observations (2 .. %d views per track, at most %d nodes)", who, b, Pb, Ob, T, T * Nmax);
+        totP += size_t(Pb); totO += size_t(Ob);
+    }
+    const size_t n = size_t(B), totC = n * T;
+    const size_t proj_bytes = (totC * 12 * 8 + 255) & ~size_t(255), extra = proj_bytes + totP * T * sizeof(int);
+    rc = ws_reserve(ctx, mv_layout(nullptr, n, totC, totP, totO, extra).bytes);
+    if (rc) return rc;
+    *L = mv_layout(ctx->d_ws, n, totC, totP, totO, extra);
+    // one staging block = one copy: records, start cameras, (zero) camera list starts, projection matrices
+    std::vector<char> stage(L->upload_bytes - (extra - proj_bytes), 0);
+    auto at = [&](const void* dev) { return stage.data() + (reinterpret_cast<const char*>(dev) - ctx->d_ws); };
+    MvbaArgs* recs = reinterpret_cast<MvbaArgs*>(at(L->recs));
+    double* cams = reinterpret_cast<double*>(at(L->cams));
+    double* proj = reinterpret_cast<double*>(at(L->extra));
+    const double unit_intr[4] = {1.0, 1.0, 0.0, 0.0};  // the intrinsics are folded into the observations
+    size_t p0 = 0, o0 = 0;
+    for (int b = 0; b < B; ++b) {
+        for (int t = 0; t < T; ++t) {
+            const double* E = extr + (size_t(b) * T + t) * 16;
+            std::memcpy(proj + (size_t(b) * T + t) * 12, E, 12 * sizeof(double));
+            mv_extr_to_cam(E, cams + (size_t(b) * T + t) * 6);
+        }
+        recs[b] = mv_record(*L, size_t(b), size_t(b) * T, p0, o0, T, 0, stats[4 * b], stats[4 * b + 1], max_iterations, unit_intr);
+        p0 += size_t(stats[4 * b]); o0 += size_t(stats[4 * b + 1]);
+    }
+    E2EMV_HIP(ctx, hipMemcpyAsync(ctx->d_ws, stage.data(), stage.size(), hipMemcpyHostToDevice, s));
+    E2EMV_HIP(ctx, hipStreamSynchronize(s));  // the staging block dies at return
+    g.kdim = kdim; g.intr_batch = intr_batch;
+    g.label = d_label;
+    g.proj = reinterpret_cast<const double*>(L->extra);
+    g.member = reinterpret_cast<int*>(L->extra + proj_bytes);
+    g.recs = L->recs;
+    const size_t lds = size_t(T) * Nmax * sizeof(unsigned short);
+    rc = ensure_dynamic_lds(ctx, reinterpret_cast<const void*>(mv_tracks_emit_kernel), lds);
+    if (rc) return rc;
+    hipLaunchKernelGGL(mv_tracks_emit_kernel, dim3(B), dim3(kMvRowThreads), lds, s, g);
+    E2EMV_CHECK_LAUNCH(ctx, "mv_tracks_emit_kernel");
+    *totP_out = totP; *totO_out = totO;
+    return E2EMV_OK;
+}
+
+}  // namespace e2emv
+
+using namespace e2emv;
+
+extern "C" int e2emv_mv_tracks(e2emv_ctx* ctx, int B, int T, int N, const int32_t* n_kpts1, const int64_t* const* d_matches,
+                               const float* const* d_conf, int conf_channels, float conf_thresh, int32_t* d_label, int32_t* d_stats,
+                               void* stream) {
+    if (!ctx) return E2EMV_EINVAL;
+    E2EMV_ENTER(ctx, stream);
+    if (!d_label || !d_stats) return set_err(ctx, E2EMV_EINVAL, "mv_tracks: NULL output");
+    MvEdgeArgs a;
+    int rc = mv_edge_args(ctx, "mv_tracks", B, T, N, 0, n_kpts1, d_matches, d_conf, conf_channels, conf_thresh, &a);
+    if (rc) return rc;
+    const size_t nodes = size_t(T) * a.Nmax, lds = (nodes + (nodes + 3) / 4 + (nodes + 31) / 32) * 4;
+    rc = ensure_dynamic_lds(ctx, reinterpret_cast<const void*>(mv_tracks_kernel), lds);
+    if (rc) return rc;
+    hipLaunchKernelGGL(mv_tracks_kernel, dim3(B), dim3(kMvTrackThreads), lds, (hipStream_t)stream, a, d_label, d_stats);
+    E2EMV_CHECK_LAUNCH(ctx, "mv_tracks_kernel");
+    return E2EMV_OK;
+}
+
+extern "C" int e2emv_mv_tuple_ba_tracks(e2emv_ctx* ctx, int B, int T, int N, int Nmax, const int32_t* d_label, const int32_t* stats,
+                                        const float* const* d_kpts, const int32_t* n_kpts, const int64_t* const* d_matches,
+                                        const float* const* d_conf, int conf_channels, float conf_thresh, const float* const* d_intr,
+                                        int kdim, int intr_batch, const double* extr, int max_iterations, double* out_extr,
+                                        double* summary, void* stream) {
+    if (!ctx) return E2EMV_EINVAL;
+    E2EMV_ENTER(ctx, stream);
+    if (!out_extr) return set_err(ctx, E2EMV_EINVAL, "mv_tuple_ba_tracks: NULL output");
+    hipStream_t s = (hipStream_t)stream;
+    MvLayout L;
+    size_t totP = 0, totO = 0;
+    int rc = mv_tracks_build(ctx, "mv_tuple_ba_tracks", B, T, N, Nmax, d_label, stats, d_kpts, n_kpts, d_matches, d_conf, conf_channels,
+                             conf_thresh, d_intr, kdim, intr_batch, extr, max_iterations, &L, &totP, &totO, s);
+    if (rc) return rc;
+    rc = mv_launch_ba(ctx, L, B, s);
+    if (rc) return rc;
+    std::vector<double> cams(size_t(B) * T * 6), sm(size_t(B) * 4);
+    E2EMV_HIP(ctx, hipMemcpyAsync(cams.data(), L.cams, sizeof(double) * cams.size(), hipMemcpyDeviceToHost, s));
+    E2EMV_HIP(ctx, hipMemcpyAsync(sm.data(), L.summary, sizeof(double) * sm.size(), hipMemcpyDeviceToHost, s));
+    E2EMV_HIP(ctx, hipStreamSynchronize(s));
+    for (size_t v = 0; v < size_t(B) * T; ++v) mv_cam_to_extr(&cams[6 * v], out_extr + 16 * v);
+    if (summary) std::memcpy(summary, sm.data(), sizeof(double) * sm.size());
+    return E2EMV_OK;
+}
+
+extern "C" int e2emv_mv_tuple_problem_tracks(e2emv_ctx* ctx, int B, int T, int N, int Nmax, const int32_t* d_label, const int32_t* stats,
+                                             const float* const* d_kpts, const int32_t* n_kpts, const int64_t* const* d_matches,
+                                             const float* const* d_conf, int conf_channels, float conf_thresh,
+                                             const float* const* d_intr, int kdim, int intr_batch, const double* extr, int32_t* cam_idx,
+                                             int32_t* pt_idx, double* obs_xy, double* obs_w, double* cams, double* pts, void* stream) {
+    if (!ctx) return E2EMV_EINVAL;
+    E2EMV_ENTER(ctx, stream);
+    if (!cams) return set_err(ctx, E2EMV_EINVAL, "mv_tuple_problem_tracks: NULL output");
+    hipStream_t s = (hipStream_t)stream;
+    MvLayout L;
+    size_t totP = 0, totO = 0;
+    const int rc = mv_tracks_build(ctx, "mv_tuple_problem_tracks", B, T, N, Nmax, d_label, stats, d_kpts, n_kpts, d_matches, d_conf,
+                                   conf_channels, conf_thresh, d_intr, kdim, intr_batch, extr, 0, &L, &totP, &totO, s);
+    if (rc) return rc;
+    if (totP && (!cam_idx || !pt_idx || !obs_xy || !obs_w || !pts)) return set_err(ctx, E2EMV_EINVAL, "mv_tuple_problem_tracks: NULL output for %zu points", totP);
+    E2EMV_HIP(ctx, hipMemcpyAsync(cams, L.cams, sizeof(double) * 6 * B * T, hipMemcpyDeviceToHost, s));
+    if (totP) {
+        E2EMV_HIP(ctx, hipMemcpyAsync(cam_idx, L.cam_idx, sizeof(int) * totO, hipMemcpyDeviceToHost, s));
+        E2EMV_HIP(ctx, hipMemcpyAsync(pt_idx, L.pt_idx, sizeof(int) * totO, hipMemcpyDeviceToHost, s));
+        E2EMV_HIP(ctx, hipMemcpyAsync(obs_xy, L.obs, sizeof(double) * 2 * totO, hipMemcpyDeviceToHost, s));
+        E2EMV_HIP(ctx, hipMemcpyAsync(obs_w, L.wts, sizeof(double) * 2 * totO, hipMemcpyDeviceToHost, s));
+        E2EMV_HIP(ctx, hipMemcpyAsync(pts, L.pts, sizeof(double) * 3 * totP, hipMemcpyDeviceToHost, s));
+    }
+    E2EMV_HIP(ctx, hipStreamSynchronize(s));
+    return E2EMV_OK;
+}

@@ -594,6 +594,84 @@ def _ransac_on_device(tuple_size, collected, intr, kdim, nb, ba=False, seed=0):
                 n_inliers=n_inl, R=R, t=t, status=status, T0=T0)
 
 
+def _check_tracks(tuple_size, data, rel_pose_method="w8pt_ba"):
+    """What ``tracks=True`` needs, checked on the host before any device call."""
+    if rel_pose_method != "w8pt_ba":
+        raise ValueError("tracks=True needs rel_pose_method=\"w8pt_ba\" (got {!r}): the RANSAC methods filter compacted rows that no "
+                         "longer carry keypoint indices".format(rel_pose_method))
+    missing = [t for t in range(tuple_size) if "keypoints" + str(t) not in data]
+    if missing:
+        raise ValueError("tracks=True needs the per-image keypoints{{t}} in data (missing for images {}): with per-pair keypoints "
+                         "only, a keypoint has no identity across pairs".format(missing))
+
+
+def _track_inputs(tuple_size, data, result):
+    """Device arrays of the track entry points: per-image keypoints [B,n_t,2] float32, per pair (order of ``_pairs``) matches [B,N]
+    int64 and confidences [B,N,channels] float32 (``None`` for a pair without a ``matches`` entry), ``n1`` = keypoints of every
+    pair's second image, ``Nmax`` = ``max(N, n1)`` = the largest keypoint count (every image but the last is the first image of a
+    pair, so it has ``N`` keypoints wherever that pair has matches)."""
+    _check_tracks(tuple_size, data)
+    pairs = _pairs(tuple_size)
+    keys = [_key("matches", str(i), i, j) for i, j in pairs]
+    have = [k for k in keys if k in result]
+    if not have:
+        raise ValueError("no pair of the tuple has matches")
+    dev = result[have[0]].device
+    if dev.type != "cuda":
+        dev = _dev()
+    B, N = result[have[0]].shape[:2]
+    prep = lambda t, dt: t.to(dev, dt).contiguous()  # noqa: E731
+    kpts = [prep(data["keypoints" + str(t)], torch.float32) for t in range(tuple_size)]
+    if any(k.dim() != 3 or k.shape[0] != B or k.shape[2] != 2 for k in kpts):
+        raise ValueError("keypoints{t} must be [B, n, 2]")
+    ms, cs, channels = [], [], None
+    for (i, j), mkey in zip(pairs, keys):
+        if mkey not in result:
+            ms.append(None); cs.append(None)
+            continue
+        m, c = prep(result[mkey], torch.int64), prep(result[_key("conf_scores_", i, j)], torch.float32).reshape(B, N, -1)
+        if m.shape != (B, N) or kpts[i].shape[1] != N or (channels not in (None, c.shape[2])):
+            raise ValueError("matches / keypoints / conf_scores of pair {} disagree in shape".format((i, j)))
+        channels = c.shape[2]
+        ms.append(m); cs.append(c)
+    n_kpts = np.array([k.shape[1] for k in kpts], np.int32)
+    n1 = np.array([n_kpts[j] for _, j in pairs], np.int32)
+    return dict(dev=dev, B=B, N=N, Nmax=int(max(N, n1.max())), kpts=kpts, n_kpts=n_kpts, matches=ms, conf=cs, n1=n1, channels=channels)
+
+
+def match_tracks(tuple_size, data, result, conf_thresh=0., _inputs=None):
+    """The pairwise matches of every tuple merged into tracks on the device (``e2emv_mv_tracks``, one launch, no synchronisation).
+    Node = keypoint ``n`` of image ``t``, id ``t * Nmax + n`` (``Nmax`` = the largest keypoint count of the tuple's images); edge
+    = every match ``_collect_matches_batch`` keeps; a track is a connected component of at least 2 nodes with at most ONE node
+    per image (a component with two keypoints of one image is a conflict and is dropped).  Returns ``(label [B, T, Nmax] int32,
+    stats [B, 4] int32)`` device tensors: the smallest node id of the node's track, or -1 for a node in no track;
+    ``stats[b] = (tracks, observations, conflict components, edges)``.  At most 16384 nodes per tuple (``E2EMVError`` above)."""
+    inp = _inputs or _track_inputs(tuple_size, data, result)
+    dev = inp["dev"]
+    label = torch.empty((inp["B"], tuple_size, inp["Nmax"]), dtype=torch.int32, device=dev)
+    stats = torch.empty((inp["B"], 4), dtype=torch.int32, device=dev)
+    pm, pc = _lib.ptr_array(inp["matches"]), _lib.ptr_array(inp["conf"])  # (pointer, owner) pairs
+    with torch.cuda.device(dev):
+        _lib.context(dev).call("e2emv_mv_tracks", inp["B"], tuple_size, inp["N"], _p(inp["n1"]), pm[0], pc[0], inp["channels"], float(conf_thresh),
+                               _lib.ptr(label), _lib.ptr(stats), _lib.stream_ptr(dev))
+    return label, stats
+
+
+def _tracks_ba_call(name, tuple_size, data, result, conf_thresh, intr, kdim, nb, extrinsics, *tail):
+    """Labels (``match_tracks``), the one small copy of their counts to the host, then the track entry point ``name``.  Returns
+    ``(label, stats)``, the counts as a host array."""
+    inp = _track_inputs(tuple_size, data, result)
+    dev = inp["dev"]
+    label, stats_d = match_tracks(tuple_size, data, result, conf_thresh, _inputs=inp)
+    stats = np.ascontiguousarray(stats_d.cpu().numpy())  # tracks and observations per tuple lay out the workspace
+    extrinsics = np.ascontiguousarray(extrinsics, np.float64)
+    pk, pm, pc, pi = (_lib.ptr_array(lst) for lst in (inp["kpts"], inp["matches"], inp["conf"], intr))
+    with torch.cuda.device(dev):
+        _lib.context(dev).call(name, inp["B"], tuple_size, inp["N"], inp["Nmax"], _lib.ptr(label), _p(stats), pk[0], _p(inp["n_kpts"]), pm[0], pc[0],
+                               inp["channels"], float(conf_thresh), pi[0], kdim, nb, _p(extrinsics), *tail, _lib.stream_ptr(dev))
+    return label, stats
+
+
 def _check_init(init):
     if init not in ("host", "device"):
         raise ValueError("init must be \"host\" or \"device\", not {!r}".format(init))
@@ -604,7 +682,7 @@ def _check_rel_pose_method(rel_pose_method):
         raise NotImplementedError("relative pose method {} is not defined".format(rel_pose_method))
 
 
-def solve_tuple_poses_batch(tuple_size, data, result, conf_thresh=0., timings=None, init="host", rel_pose_method="w8pt_ba", seed=0):
+def solve_tuple_poses_batch(tuple_size, data, result, conf_thresh=0., timings=None, init="host", rel_pose_method="w8pt_ba", seed=0, tracks=False):
     """``solve_tuple_poses`` for EVERY batch element of the matcher result, in memory: returns the refined world-to-camera
     extrinsics ``float64 [B, tuple_size, 4, 4]``, camera 0 the gauge.  Stages: matches collected on the device (one launch) ->
     relative poses of all B * T(T-1)/2 pairs (``rel_pose_method``) -> one copy to the host, spanning tree and rotation /
@@ -620,10 +698,19 @@ def solve_tuple_poses_batch(tuple_size, data, result, conf_thresh=0., timings=No
     ``init``: where the initialisation stage runs.  "host" (default): the loop above.  "device": ``e2emv_mv_tuple_init``, one
     launch for the batch (one wave per tuple: spanning tree, chained start, averaging) enqueued behind the relative poses; match
     counts and start extrinsics come back in one copy.  Same solver and options; the results agree to rounding (DESIGN.md
-    section 1), equal match counts of two pairs of a tuple are ordered by ascending (i, j) there and by scipy here."""
+    section 1), equal match counts of two pairs of a tuple are ordered by ascending (i, j) there and by scipy here.
+    ``tracks``: ``False`` (default): one 3-D point per pairwise match, like the reference.  ``True``: the first three stages stay
+    as they are (the start comes from the pairwise relative poses) and the last stage bundle-adjusts the TRACKS of
+    ``match_tracks`` - one point per scene point, seen by 2 .. T images; components with two keypoints of one image are dropped -
+    built on the device (``e2emv_mv_tuple_ba_tracks``).  A tuple without any track returns its start.  Needs
+    ``rel_pose_method="w8pt_ba"`` (the RANSAC methods filter rows that no longer carry keypoint indices) and per-image
+    ``keypoints{t}`` in ``data`` (with per-pair keypoints only, a keypoint has no identity across pairs): ``ValueError``
+    otherwise, before any device call."""
     import time
     _check_init(init)
     _check_rel_pose_method(rel_pose_method)
+    if tracks:
+        _check_tracks(tuple_size, data, rel_pose_method)
     ransac = rel_pose_method != "w8pt_ba"
     pairs = _pairs(tuple_size)
     P = len(pairs)
@@ -659,7 +746,10 @@ def solve_tuple_poses_batch(tuple_size, data, result, conf_thresh=0., timings=No
             start, counts = _tuple_init_on_device(tuple_size, T_d, inl, count)
         lap("initialisation")
         out, summary = np.zeros((B, tuple_size, 4, 4)), np.zeros((B, 4))
-        _tuple_ba_call("e2emv_mv_tuple_ba", tuple_size, collected, counts, intr, kdim, nb, start, 50, _p(out), _p(summary))
+        if tracks:
+            _tracks_ba_call("e2emv_mv_tuple_ba_tracks", tuple_size, data, result, conf_thresh, intr, kdim, nb, start, 50, _p(out), _p(summary))
+        else:
+            _tuple_ba_call("e2emv_mv_tuple_ba", tuple_size, collected, counts, intr, kdim, nb, start, 50, _p(out), _p(summary))
         lap("build_and_bundle_adjust")
         return out
     # one device -> host copy for the whole batch: poses, inlier counts, match counts
@@ -681,7 +771,10 @@ def solve_tuple_poses_batch(tuple_size, data, result, conf_thresh=0., timings=No
         start[b] = _averaged_extrinsics(*_init_arrays(tuple_size, rel, inlier_count, graph)[0])
     lap("initialisation")
     out, summary = np.zeros((B, tuple_size, 4, 4)), np.zeros((B, 4))
-    _tuple_ba_call("e2emv_mv_tuple_ba", tuple_size, collected, counts, intr, kdim, nb, start, 50, _p(out), _p(summary))
+    if tracks:
+        _tracks_ba_call("e2emv_mv_tuple_ba_tracks", tuple_size, data, result, conf_thresh, intr, kdim, nb, start, 50, _p(out), _p(summary))
+    else:
+        _tuple_ba_call("e2emv_mv_tuple_ba", tuple_size, collected, counts, intr, kdim, nb, start, 50, _p(out), _p(summary))
     lap("build_and_bundle_adjust")
     return out
 
@@ -702,6 +795,24 @@ def _tuple_problems(tuple_size, collected, counts, intr, kdim, nb, extrinsics):
     return [(tuple_size, 0, np.array([1., 1., 0., 0.]), cam_idx[2 * off[b]:2 * off[b + 1]], pt_idx[2 * off[b]:2 * off[b + 1]],
              obs_xy[2 * off[b]:2 * off[b + 1]], obs_w[2 * off[b]:2 * off[b + 1]], cams[b * tuple_size:(b + 1) * tuple_size], pts[off[b]:off[b + 1]])
             for b in range(B)]
+
+
+def _tuple_problems_tracks(tuple_size, data, result, conf_thresh, intr, kdim, nb, extrinsics):
+    """The track problems ``solve_tuple_poses_batch(..., tracks=True)`` solves (``e2emv_mv_tuple_problem_tracks``): ``(problems,
+    label, stats)``, one argument tuple of ``bundle_adjust`` per batch element and what ``match_tracks`` returned (label on the
+    device, stats on the host)."""
+    inp = _track_inputs(tuple_size, data, result)
+    stats = match_tracks(tuple_size, data, result, conf_thresh, _inputs=inp)[1].cpu().numpy()
+    B = inp["B"]
+    n_pts, n_obs = stats[:, 0].astype(np.int64), stats[:, 1].astype(np.int64)
+    tp, to = int(n_pts.sum()), int(n_obs.sum())
+    cam_idx, pt_idx = np.zeros(to, np.int32), np.zeros(to, np.int32)
+    obs_xy, obs_w, cams, pts = np.zeros((to, 2)), np.zeros((to, 2)), np.zeros((B * tuple_size, 6)), np.zeros((tp, 3))
+    label, stats = _tracks_ba_call("e2emv_mv_tuple_problem_tracks", tuple_size, data, result, conf_thresh, intr, kdim, nb, extrinsics, _p(cam_idx),
+                                   _p(pt_idx), _p(obs_xy), _p(obs_w), _p(cams), _p(pts))
+    po, oo = np.concatenate([[0], np.cumsum(n_pts)]), np.concatenate([[0], np.cumsum(n_obs)])
+    return [(tuple_size, 0, np.array([1., 1., 0., 0.]), cam_idx[oo[b]:oo[b + 1]], pt_idx[oo[b]:oo[b + 1]], obs_xy[oo[b]:oo[b + 1]],
+             obs_w[oo[b]:oo[b + 1]], cams[b * tuple_size:(b + 1) * tuple_size], pts[po[b]:po[b + 1]]) for b in range(B)], label, stats
 
 
 def tuple_pose_errors(extrinsics, cam_to_world):
@@ -736,12 +847,12 @@ def eval_bundle_adjust(tuple_size, data, result, tmp_dir, pose_errors, verbose=F
     return pose_errors
 
 
-def eval_bundle_adjust_batch(tuple_size, data, result, pose_errors, verbose=False, init="host", rel_pose_method="w8pt_ba"):
+def eval_bundle_adjust_batch(tuple_size, data, result, pose_errors, verbose=False, init="host", rel_pose_method="w8pt_ba", tracks=False):
     """``eval_bundle_adjust`` for every batch element through ``solve_tuple_poses_batch``: extends ``pose_errors = [max errors,
     translation errors, rotation errors]`` by ``B * T(T-1)/2`` entries, batch element outer, pairs in ``_pairs`` order inside
-    (for ``B = 1`` the entries ``eval_bundle_adjust`` appends, in its order).  ``init``, ``rel_pose_method``: as in
-    ``solve_tuple_poses_batch``."""
-    extrinsics = solve_tuple_poses_batch(tuple_size, data, result, init=init, rel_pose_method=rel_pose_method)
+    (for ``B = 1`` the entries ``eval_bundle_adjust`` appends, in its order).  ``init``, ``rel_pose_method``, ``tracks``: as
+    in ``solve_tuple_poses_batch``."""
+    extrinsics = solve_tuple_poses_batch(tuple_size, data, result, init=init, rel_pose_method=rel_pose_method, tracks=tracks)
     poses = np.stack([data["pose" + str(v)].cpu().numpy() for v in range(tuple_size)], 1)  # [B,T,4,4]: one copy per image
     for b, E in enumerate(extrinsics):
         err_t, err_R = tuple_pose_errors(E, poses[b])

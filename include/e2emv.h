@@ -305,6 +305,42 @@ int e2emv_mv_tuple_problem(e2emv_ctx* ctx, int B, int T, int N, const int32_t* c
                            const double* extr, int32_t* cam_idx, int32_t* pt_idx, double* obs_xy, double* obs_w, double* cams,
                            double* pts, void* stream);
 
+/* Track merging (csrc/mvtracks.hip): the pairwise matches of B tuples become tracks, one 3-D point per scene point instead of
+ * one per match.  B, T, N, n_kpts1, d_matches, d_conf, conf_channels, conf_thresh as in e2emv_mv_collect.  Node = keypoint n of
+ * image t, id t * Nmax + n, Nmax = max(N, n_kpts1[q]) over ALL pairs (the largest keypoint count); edge = every keypoint of the first image of a
+ * pair that e2emv_mv_collect keeps, joined to its match; label = the smallest node id of the connected component; track = a
+ * component of >= 2 nodes with at most ONE node per image (a component holding two keypoints of one image is a conflict and
+ * is dropped).  d_label [B,T,Nmax] int32 DEVICE: the track's label, -1 for a node in no track; d_stats [B,4] int32 DEVICE:
+ * {tracks, observations = nodes in tracks, conflict components, edges}.  One workgroup per tuple, labels in LDS; the result
+ * does not depend on the batch position or the run.  One launch, no host synchronisation.  LIMIT: T * Nmax <= 16384 nodes
+ * (8 images of 2048 keypoints), E2EMV_ESHAPE above it.                                                                   */
+int e2emv_mv_tracks(e2emv_ctx* ctx, int B, int T, int N, const int32_t* n_kpts1, const int64_t* const* d_matches,
+                    const float* const* d_conf, int conf_channels, float conf_thresh, int32_t* d_label, int32_t* d_stats,
+                    void* stream);
+/* The counterpart of e2emv_mv_tuple_ba on the tracks: d_label [B,T,Nmax] DEVICE and stats [B,4] HOST copy of d_stats from
+ * e2emv_mv_tracks on the same matches / confidences / threshold; d_kpts HOST array of T DEVICE pointers [B,n_kpts[t],2]
+ * (the per-image keypoints), n_kpts HOST [T] (<= Nmax; the first image of a pair with matches has >= N); intrinsics and extr
+ * as in e2emv_mv_tuple_ba.  One launch builds every tuple's problem: points = tracks in ascending label, the observations
+ * of a point in ascending image, concatenated in point order, index lists as e2emv_mv_bundle_adjust_batch builds them;
+ * observation = fp32 (kp - c) / f widened to fp64; weight = c / (0.5 (sum + 1e-3)), c the fp64 mean of the node's kept
+ * edges' confidences (channel 0, other image ascending), sum over the tuple's observations in a fixed order; start point =
+ * homogeneous DLT over the track's k views (for k = 2 the routine of e2emv_mv_triangulate).  One launch solves them (camera
+ * 0 fixed, f = 1, c = 0).  A tuple without tracks returns its start.  out_extr HOST [B,T,4,4], summary HOST [B,4] (may
+ * be NULL).  Synchronous.                                                                                               */
+int e2emv_mv_tuple_ba_tracks(e2emv_ctx* ctx, int B, int T, int N, int Nmax, const int32_t* d_label, const int32_t* stats,
+                             const float* const* d_kpts, const int32_t* n_kpts, const int64_t* const* d_matches,
+                             const float* const* d_conf, int conf_channels, float conf_thresh, const float* const* d_intr,
+                             int kdim, int intr_batch, const double* extr, int max_iterations, double* out_extr,
+                             double* summary, void* stream);
+/* The problems e2emv_mv_tuple_ba_tracks would solve, copied out instead (HOST, concatenated in the layout
+ * e2emv_mv_bundle_adjust_batch takes; tuple b owns stats[b][0] points and stats[b][1] observations): cam_idx, pt_idx [O],
+ * obs_xy, obs_w [O,2], cams [B*T,6], pts [P,3].                                                                         */
+int e2emv_mv_tuple_problem_tracks(e2emv_ctx* ctx, int B, int T, int N, int Nmax, const int32_t* d_label, const int32_t* stats,
+                                  const float* const* d_kpts, const int32_t* n_kpts, const int64_t* const* d_matches,
+                                  const float* const* d_conf, int conf_channels, float conf_thresh, const float* const* d_intr,
+                                  int kdim, int intr_batch, const double* extr, int32_t* cam_idx, int32_t* pt_idx,
+                                  double* obs_xy, double* obs_w, double* cams, double* pts, void* stream);
+
 /* The global initialisation on the DEVICE (csrc/mvinit_device.hip): the solver of e2emv_mv_init with the same options,
  * fp64, one wave per problem, the problem and its working set in LDS; a problem's result depends on neither its
  * neighbours nor its position in the batch (bit for bit), and agrees with the host form to rounding (summation orders

@@ -8,10 +8,13 @@ between the two paths' extrinsics.  ``--init`` selects where the batched path ru
 over ``e2emv_mv_init``), ``device`` (``e2emv_mv_tuple_init``, one launch) or ``both`` (default): both batched forms are then
 timed inside the same repetition loop, alternating, and the line also carries the device form's figures and the largest
 difference between the two forms' extrinsics.  ``--rel-pose-method`` selects the relative poses of both paths: ``w8pt_ba``
-(default), ``ransac`` or ``ransac_ba``.
+(default), ``ransac`` or ``ransac_ba``.  ``--tracks``: the batched path bundle-adjusts the merged tracks
+(``solve_tuple_poses_batch(..., tracks=True)``; the CSV path has no tracks and stays as it is, so the difference between the two
+paths' extrinsics is then the effect of the tracks); the line also carries the track counts and the time of the label launch
+and of labels + problem build + copy-out on their own (each synchronised), the share of the last stage the new kernels take.
 
     python tools/bench_mv_backend.py [--batch 8] [--tuple-size 5] [--kpts 1024] [--reps 7] [--init host|device|both]
-                                     [--rel-pose-method w8pt_ba|ransac|ransac_ba]
+                                     [--rel-pose-method w8pt_ba|ransac|ransac_ba] [--tracks]
 """
 import argparse
 import json
@@ -36,6 +39,7 @@ def main():
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--init", choices=("host", "device", "both"), default="both")
     ap.add_argument("--rel-pose-method", choices=("w8pt_ba", "ransac", "ransac_ba"), default="w8pt_ba")
+    ap.add_argument("--tracks", action="store_true")
     args = ap.parse_args()
     B, T, method = args.batch, args.tuple_size, args.rel_pose_method
     gpu = torch.device("cuda", 0)
@@ -56,7 +60,7 @@ def main():
         forms = ("host", "device") if args.init == "both" else (args.init,)
 
         def batched(init, timings=None):
-            return multi_view.solve_tuple_poses_batch(T, dev, result, timings=timings, init=init, rel_pose_method=method)
+            return multi_view.solve_tuple_poses_batch(T, dev, result, timings=timings, init=init, rel_pose_method=method, tracks=args.tracks)
 
         def timed(fn):
             torch.cuda.synchronize()
@@ -79,16 +83,25 @@ def main():
                 batched(f, tm)
                 for k, v in tm.items():
                     stages[f].setdefault(k, []).append(v * 1e3)
+        if args.tracks:
+            intr, kdim, nb = multi_view._tuple_intrinsics(T, dev, gpu, B)
+            t_label = [timed(lambda: multi_view.match_tracks(T, dev, result))[0] for _ in range(args.reps + 1)][1:]
+            t_build = [timed(lambda: multi_view._tuple_problems_tracks(T, dev, result, 0., intr, kdim, nb, e_batch[forms[0]]))[0]
+                       for _ in range(args.reps + 1)][1:]
+            track_stats = multi_view.match_tracks(T, dev, result)[1].cpu().numpy()
     stat = lambda ts: {"median": float(np.median(ts)), "min": float(np.min(ts)), "max": float(np.max(ts))}  # noqa: E731
     first = forms[0]  # the form the unsuffixed keys describe: the host form unless --init device
     line = {"batch": B, "tuple_size": T, "n_kpts": args.kpts, "reps": args.reps, "init": args.init, "rel_pose_method": method, "csv_path_ms": stat(t_csv),
-            "batched_path_ms": stat(t_batch[first]), "batched_stage_ms": {k: float(np.median(v)) for k, v in stages[first].items()},
+            "tracks": args.tracks, "batched_path_ms": stat(t_batch[first]), "batched_stage_ms": {k: float(np.median(v)) for k, v in stages[first].items()},
             "max_abs_extrinsics_difference": float(np.abs(e_csv - e_batch[first]).max())}
     if args.init == "both":
         line["batched_path_device_init_ms"] = stat(t_batch["device"])
         line["batched_stage_device_init_ms"] = {k: float(np.median(v)) for k, v in stages["device"].items()}
         line["initialisation_stage_ms"] = {f: stat(stages[f]["initialisation"]) for f in forms}
         line["max_abs_extrinsics_difference_device_vs_host"] = float(np.abs(e_batch["device"] - e_batch["host"]).max())
+    if args.tracks:
+        line["track_labels_ms"], line["track_labels_build_copy_out_ms"] = stat(t_label), stat(t_build)
+        line["tracks_observations_conflicts_edges"] = track_stats.sum(0).tolist()
     print(json.dumps(line), flush=True)
 
 
