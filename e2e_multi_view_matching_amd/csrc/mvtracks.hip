@@ -9,6 +9,16 @@
 //   label     the smallest node id of the node's connected component (a unique fixed point: any propagation order ends there)
 //   track     a component of >= 2 nodes with AT MOST ONE node per image; a component with two keypoints of one image is a
 //             conflict and contributes nothing
+//   repair    (e2emv_mv_tracks_repair, rounds >= 0; a stage between "edge" and "label") edge id e = q * N + n, every kept edge
+//             starts LIVE.  One round: components over the live edges; in EVERY conflicting component the live edge with the
+//             smallest key (confidence of channel 0 compared as floats with <, -0.0 = +0.0; then the smaller edge id) is cut,
+//             exactly one per component per round.  The stage ends after `rounds` rounds or when no component conflicts; label,
+//             track and conflict are then the definitions above over the live edges (a component that still conflicts
+//             contributes nothing, a node that lost all its live edges is in no track).  rounds = 0 is e2emv_mv_tracks bit for
+//             bit.  The problem does NOT see the cuts: labels and stats are the only interface to mv_tracks_emit_kernel, and a
+//             node's confidence stays the mean of the KEPT (original) edges between it and the other members of its track.  A cut
+//             edge whose ends land in different tracks drops out by that rule; a cut edge that lay on a cycle, so that both its
+//             ends end in the same valid track, still counts - it is consistent with the track it ended in.
 //   problem   points = tracks in ascending label, observations of a point in ascending image, concatenated in point order;
 //             index lists as e2emv_mv_bundle_adjust_batch builds them; camera 0 fixed, f = 1, c = 0
 //   weight    node confidence = fp64 mean of its kept edges' confidences (ascending other image); weights = confidence /
@@ -21,7 +31,10 @@
 // LIMIT: T * Nmax <= 16384 nodes per tuple (8 images of 2048 keypoints): mv_tracks_kernel keeps a 32-bit label per node (native
 // LDS atomic min; 16 bits would do for the ids but LDS has no 16-bit atomic), 8 image bits and one conflict bit per root in LDS
 // = 5.125 bytes per node, 82 KiB at the limit, of the 160 KiB one workgroup may declare on gfx950.  Above the limit the entry
-// points return E2EMV_ESHAPE before any launch.
+// points return E2EMV_ESHAPE before any launch.  mv_tracks_repair_kernel adds a 32-bit arg-min key per root (the 64-bit key
+// (confidence, edge id) would not fit: it is found in two 32-bit passes, first the smallest confidence, then the smallest edge
+// id among the edges that have it) = 9.125 bytes per node, 146 KiB at the limit, and one dead bit per edge id: P * N <= (T - 1) / 2
+// * T * Nmax <= 3.5 * 16384 bits = 7 KiB.  153 KiB + 32 bytes of static LDS at the limit; the same limit holds.
 #include <algorithm>
 #include <cstdint>
 #include <cstring>
@@ -116,6 +129,157 @@ __global__ __launch_bounds__(kMvTrackThreads) void mv_tracks_kernel(MvEdgeArgs a
         if (atomicOr(&s_mask[r >> 2], bit) & bit) atomicOr(&s_bad[r >> 5], 1u << (r & 31));
     }
     __syncthreads();
+    int tracks = 0, obs = 0, bad = 0;
+    for (int x = tid; x < nodes; x += kMvTrackThreads) {
+        const int r = s_label[x];
+        const int views = __popc((s_mask[r >> 2] >> (8 * (r & 3))) & 0xffu);
+        const bool conflict = (s_bad[r >> 5] >> (r & 31)) & 1u, valid = !conflict && views >= 2;
+        out_label[size_t(b) * nodes + x] = valid ? r : -1;
+        if (r == x) { tracks += valid; obs += valid ? views : 0; bad += conflict; }
+    }
+    atomicAdd(&s_stats[0], tracks); atomicAdd(&s_stats[1], obs); atomicAdd(&s_stats[2], bad); atomicAdd(&s_stats[3], edges);
+    __syncthreads();
+    if (tid < 4) out_stats[4 * b + tid] = s_stats[tid];
+}
+
+// float -> unsigned whose unsigned order is the float order (no NaN reaches it: a kept edge has conf > thresh); -0.0 ties +0.0
+__device__ __forceinline__ unsigned mv_conf_key(float c) {
+    unsigned u = __float_as_uint(c);
+    if ((u << 1) == 0u) u = 0u;
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+constexpr unsigned kMvNoKey = 0xffffffffu;  // above every confidence key (it is the key of a NaN) and every edge id
+constexpr int kMvRepairMaxRounds = 64;
+constexpr int kMvRepairMaxEdgeIds = 64 * kMvTrackThreads;  // one candidate bit per edge id a thread visits, in one 64-bit register
+
+// mv_tracks_kernel with the repair stage of the header comment: the labelling of mv_tracks_kernel (the same sweeps over the LIVE
+// edges, the same classification) once per round, then one cut per conflicting component:
+//   1. every live edge of a conflicting root takes an atomic min of its confidence key on s_key[root];
+//   2. every thread notes, one bit per edge id it visits, the live edges whose key equals that minimum (the candidates);
+//   3. s_key is reset and the candidates take an atomic min of their edge id on s_key[root];
+//   4. the candidate whose id is the minimum sets its bit in the dead-edge bitmap.
+// Both minima are unique values, so the cut does not depend on the order of the atomics.  Before the next round the nodes of the
+// conflicting components go back to their own ids (labels only decrease: a stale label would keep a split component glued;
+// the other components have no cut and keep their converged labels), mask and conflict bits are cleared.
+// Bounds: rounds <= `rounds` <= 64 (the host checks), sweeps <= nodes per round, pointer chains end at a root as in
+// mv_tracks_kernel, edge ids per thread <= 64 (P * N <= kMvRepairMaxEdgeIds, the host checks).  rounds = 0 is mv_tracks_kernel.
+// stats[b] = {tracks, observations, conflict components left, live edges}.
+__global__ __launch_bounds__(kMvTrackThreads) void mv_tracks_repair_kernel(MvEdgeArgs a, int rounds, int* __restrict__ out_label,
+                                                                            int* __restrict__ out_stats) {
+    extern __shared__ __attribute__((aligned(16))) int s_trk[];
+    __shared__ int s_changed, s_any_bad, s_stats[4];
+    const int b = blockIdx.x, tid = threadIdx.x, nodes = a.T * a.Nmax, n_edges = a.P * a.N;
+    const int mask_words = (nodes + 3) / 4, bad_words = (nodes + 31) / 32, dead_words = (n_edges + 31) / 32;
+    int* s_label = s_trk;                                              // [nodes]
+    unsigned* s_mask = reinterpret_cast<unsigned*>(s_trk + nodes);      // [mask_words]: 8 image bits per root
+    unsigned* s_bad = s_mask + mask_words;                              // [bad_words]: conflict bit per root
+    unsigned* s_dead = s_bad + bad_words;                               // [dead_words]: cut bit per edge id
+    unsigned* s_key = s_dead + dead_words;                              // [nodes]: arg-min key per root
+    for (int x = tid; x < nodes; x += kMvTrackThreads) s_label[x] = x;
+    for (int x = tid; x < mask_words; x += kMvTrackThreads) s_mask[x] = 0u;
+    for (int x = tid; x < bad_words; x += kMvTrackThreads) s_bad[x] = 0u;
+    for (int x = tid; x < dead_words; x += kMvTrackThreads) s_dead[x] = 0u;
+    if (tid < 4) s_stats[tid] = 0;
+    int edges = 0;
+    for (int round = 0;; ++round) {
+        edges = 0;
+        for (int sweep = 0; sweep < nodes; ++sweep) {
+            if (tid == 0) s_changed = 0;
+            __syncthreads();
+            bool changed = false;
+            for (int e = tid; e < n_edges; e += kMvTrackThreads) {
+                if ((s_dead[e >> 5] >> (e & 31)) & 1u) continue;
+                const int q = e / a.N, n = e - q * a.N;
+                const int m = mv_edge(a, b, q, n, nullptr);
+                if (m < 0) continue;
+                if (sweep == 0) ++edges;
+                const int x = a.pi[q] * a.Nmax + n, y = a.pj[q] * a.Nmax + m;
+                const int lx = s_label[x], ly = s_label[y];
+                if (lx == ly) continue;
+                const int lo = min(lx, ly), hi = max(lx, ly);
+                atomicMin(&s_label[hi], lo);
+                atomicMin(&s_label[lx > ly ? x : y], lo);
+                changed = true;
+            }
+            if (changed) s_changed = 1;
+            __syncthreads();
+            for (int x = tid; x < nodes; x += kMvTrackThreads) {
+                int l = s_label[x];
+                while (true) {
+                    const int up = s_label[l];
+                    if (up == l) break;
+                    l = up;
+                }
+                s_label[x] = l;
+            }
+            const int again = s_changed;
+            __syncthreads();
+            if (!again) break;
+        }
+        for (int x = tid; x < nodes; x += kMvTrackThreads) {
+            const int t = x / a.Nmax, r = s_label[x];
+            const unsigned bit = 1u << (t + 8 * (r & 3));
+            if (atomicOr(&s_mask[r >> 2], bit) & bit) atomicOr(&s_bad[r >> 5], 1u << (r & 31));
+        }
+        if (tid == 0) s_any_bad = 0;
+        __syncthreads();
+        if (round >= rounds) break;  // uniform: the labels of the last round are the result
+        bool any = false;
+        for (int x = tid; x < bad_words; x += kMvTrackThreads) any = any || s_bad[x] != 0u;
+        if (any) s_any_bad = 1;
+        for (int x = tid; x < nodes; x += kMvTrackThreads) s_key[x] = kMvNoKey;
+        __syncthreads();
+        if (!s_any_bad) break;  // uniform: nothing conflicts, nothing to cut
+        // 1. the smallest confidence among the live edges of every conflicting root
+        for (int e = tid; e < n_edges; e += kMvTrackThreads) {
+            if ((s_dead[e >> 5] >> (e & 31)) & 1u) continue;
+            const int q = e / a.N, n = e - q * a.N;
+            float c;
+            if (mv_edge(a, b, q, n, &c) < 0) continue;
+            const int r = s_label[a.pi[q] * a.Nmax + n];
+            if ((s_bad[r >> 5] >> (r & 31)) & 1u) atomicMin(&s_key[r], mv_conf_key(c));
+        }
+        __syncthreads();
+        // 2. the candidates: bit k of `cand` is edge id tid + k * 1024
+        unsigned long long cand = 0ull;
+        int k = 0;
+        for (int e = tid; e < n_edges; e += kMvTrackThreads, ++k) {
+            if ((s_dead[e >> 5] >> (e & 31)) & 1u) continue;
+            const int q = e / a.N, n = e - q * a.N;
+            float c;
+            if (mv_edge(a, b, q, n, &c) < 0) continue;
+            const int r = s_label[a.pi[q] * a.Nmax + n];
+            if (((s_bad[r >> 5] >> (r & 31)) & 1u) && s_key[r] == mv_conf_key(c)) cand |= 1ull << k;
+        }
+        __syncthreads();
+        // 3. the smallest edge id among them
+        for (int x = tid; x < nodes; x += kMvTrackThreads) s_key[x] = kMvNoKey;
+        __syncthreads();
+        k = 0;
+        for (int e = tid; e < n_edges; e += kMvTrackThreads, ++k) {
+            if (!((cand >> k) & 1ull)) continue;
+            const int q = e / a.N, n = e - q * a.N;
+            atomicMin(&s_key[s_label[a.pi[q] * a.Nmax + n]], unsigned(e));
+        }
+        __syncthreads();
+        // 4. the cut
+        k = 0;
+        for (int e = tid; e < n_edges; e += kMvTrackThreads, ++k) {
+            if (!((cand >> k) & 1ull)) continue;
+            const int q = e / a.N, n = e - q * a.N;
+            if (s_key[s_label[a.pi[q] * a.Nmax + n]] == unsigned(e)) atomicOr(&s_dead[e >> 5], 1u << (e & 31));
+        }
+        __syncthreads();
+        // the next round starts the cut components from their own ids
+        for (int x = tid; x < nodes; x += kMvTrackThreads) {
+            const int r = s_label[x];
+            if ((s_bad[r >> 5] >> (r & 31)) & 1u) s_label[x] = x;
+        }
+        __syncthreads();  // s_bad is read above and cleared below
+        for (int x = tid; x < mask_words; x += kMvTrackThreads) s_mask[x] = 0u;
+        for (int x = tid; x < bad_words; x += kMvTrackThreads) s_bad[x] = 0u;
+    }
     int tracks = 0, obs = 0, bad = 0;
     for (int x = tid; x < nodes; x += kMvTrackThreads) {
         const int r = s_label[x];
@@ -496,6 +660,26 @@ extern "C" int e2emv_mv_tracks(e2emv_ctx* ctx, int B, int T, int N, const int32_
     if (rc) return rc;
     hipLaunchKernelGGL(mv_tracks_kernel, dim3(B), dim3(kMvTrackThreads), lds, (hipStream_t)stream, a, d_label, d_stats);
     E2EMV_CHECK_LAUNCH(ctx, "mv_tracks_kernel");
+    return E2EMV_OK;
+}
+
+extern "C" int e2emv_mv_tracks_repair(e2emv_ctx* ctx, int B, int T, int N, const int32_t* n_kpts1, const int64_t* const* d_matches,
+                                      const float* const* d_conf, int conf_channels, float conf_thresh, int rounds, int32_t* d_label,
+                                      int32_t* d_stats, void* stream) {
+    if (!ctx) return E2EMV_EINVAL;
+    E2EMV_ENTER(ctx, stream);
+    if (!d_label || !d_stats) return set_err(ctx, E2EMV_EINVAL, "mv_tracks_repair: NULL output");
+    if (rounds < 0 || rounds > kMvRepairMaxRounds) return set_err(ctx, E2EMV_EINVAL, "mv_tracks_repair: %d rounds (0 <= rounds <= %d)", rounds, kMvRepairMaxRounds);
+    MvEdgeArgs a;
+    int rc = mv_edge_args(ctx, "mv_tracks_repair", B, T, N, 0, n_kpts1, d_matches, d_conf, conf_channels, conf_thresh, &a);
+    if (rc) return rc;
+    const size_t nodes = size_t(T) * a.Nmax, edge_ids = size_t(a.P) * N;  // N <= Nmax: edge_ids <= (T - 1) / 2 * nodes <= 3.5 * 16384
+    if (edge_ids > size_t(kMvRepairMaxEdgeIds)) return set_err(ctx, E2EMV_ESHAPE, "mv_tracks_repair: %zu edge ids (limit %d)", edge_ids, kMvRepairMaxEdgeIds);
+    const size_t lds = (2 * nodes + (nodes + 3) / 4 + (nodes + 31) / 32 + (edge_ids + 31) / 32) * 4;
+    rc = ensure_dynamic_lds(ctx, reinterpret_cast<const void*>(mv_tracks_repair_kernel), lds);
+    if (rc) return rc;
+    hipLaunchKernelGGL(mv_tracks_repair_kernel, dim3(B), dim3(kMvTrackThreads), lds, (hipStream_t)stream, a, rounds, d_label, d_stats);
+    E2EMV_CHECK_LAUNCH(ctx, "mv_tracks_repair_kernel");
     return E2EMV_OK;
 }
 

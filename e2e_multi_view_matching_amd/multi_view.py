@@ -605,6 +605,14 @@ def _check_tracks(tuple_size, data, rel_pose_method="w8pt_ba"):
                          "only, a keypoint has no identity across pairs".format(missing))
 
 
+def _check_repair_rounds(repair_rounds, tracks=True):
+    """``repair_rounds`` is an int in 0 .. 64 and 0 without tracks, checked on the host before any device call."""
+    if isinstance(repair_rounds, bool) or not isinstance(repair_rounds, (int, np.integer)) or not 0 <= repair_rounds <= 64:
+        raise ValueError("repair_rounds must be an int in 0 .. 64, not {!r}".format(repair_rounds))
+    if repair_rounds and not tracks:
+        raise ValueError("repair_rounds={} needs tracks=True: only the track problem has conflicts to repair".format(repair_rounds))
+
+
 def _track_inputs(tuple_size, data, result):
     """Device arrays of the track entry points: per-image keypoints [B,n_t,2] float32, per pair (order of ``_pairs``) matches [B,N]
     int64 and confidences [B,N,channels] float32 (``None`` for a pair without a ``matches`` entry), ``n1`` = keypoints of every
@@ -639,30 +647,42 @@ def _track_inputs(tuple_size, data, result):
     return dict(dev=dev, B=B, N=N, Nmax=int(max(N, n1.max())), kpts=kpts, n_kpts=n_kpts, matches=ms, conf=cs, n1=n1, channels=channels)
 
 
-def match_tracks(tuple_size, data, result, conf_thresh=0., _inputs=None):
+def match_tracks(tuple_size, data, result, conf_thresh=0., _inputs=None, repair_rounds=0):
     """The pairwise matches of every tuple merged into tracks on the device (``e2emv_mv_tracks``, one launch, no synchronisation).
     Node = keypoint ``n`` of image ``t``, id ``t * Nmax + n`` (``Nmax`` = the largest keypoint count of the tuple's images); edge
     = every match ``_collect_matches_batch`` keeps; a track is a connected component of at least 2 nodes with at most ONE node
     per image (a component with two keypoints of one image is a conflict and is dropped).  Returns ``(label [B, T, Nmax] int32,
     stats [B, 4] int32)`` device tensors: the smallest node id of the node's track, or -1 for a node in no track;
-    ``stats[b] = (tracks, observations, conflict components, edges)``.  At most 16384 nodes per tuple (``E2EMVError`` above)."""
+    ``stats[b] = (tracks, observations, conflict components, edges)``.  At most 16384 nodes per tuple (``E2EMVError`` above).
+    ``repair_rounds`` (int, 0 .. 64, else ``ValueError``): 0 (default) is the call above.  ``R > 0`` goes to
+    ``e2emv_mv_tracks_repair`` (one launch as well): up to ``R`` rounds in each of which EVERY conflicting component loses its
+    weakest live edge - smallest confidence of channel 0, then smallest edge id ``q * N + n`` - before the components are taken
+    again; it ends early when nothing conflicts.  Labels are then the definitions above over the live edges, ``stats[b]`` counts
+    the conflicts LEFT and the LIVE edges."""
+    _check_repair_rounds(repair_rounds)
     inp = _inputs or _track_inputs(tuple_size, data, result)
     dev = inp["dev"]
     label = torch.empty((inp["B"], tuple_size, inp["Nmax"]), dtype=torch.int32, device=dev)
     stats = torch.empty((inp["B"], 4), dtype=torch.int32, device=dev)
     pm, pc = _lib.ptr_array(inp["matches"]), _lib.ptr_array(inp["conf"])  # (pointer, owner) pairs
     with torch.cuda.device(dev):
-        _lib.context(dev).call("e2emv_mv_tracks", inp["B"], tuple_size, inp["N"], _p(inp["n1"]), pm[0], pc[0], inp["channels"], float(conf_thresh),
-                               _lib.ptr(label), _lib.ptr(stats), _lib.stream_ptr(dev))
+        head = (inp["B"], tuple_size, inp["N"], _p(inp["n1"]), pm[0], pc[0], inp["channels"], float(conf_thresh))
+        tail = (_lib.ptr(label), _lib.ptr(stats), _lib.stream_ptr(dev))
+        if repair_rounds:
+            _lib.context(dev).call("e2emv_mv_tracks_repair", *head, int(repair_rounds), *tail)
+        else:
+            _lib.context(dev).call("e2emv_mv_tracks", *head, *tail)
     return label, stats
 
 
-def _tracks_ba_call(name, tuple_size, data, result, conf_thresh, intr, kdim, nb, extrinsics, *tail):
+def _tracks_ba_call(name, tuple_size, data, result, conf_thresh, intr, kdim, nb, extrinsics, *tail, repair_rounds=0):
     """Labels (``match_tracks``), the one small copy of their counts to the host, then the track entry point ``name``.  Returns
-    ``(label, stats)``, the counts as a host array."""
+    ``(label, stats)``, the counts as a host array.  ``repair_rounds``: as in ``match_tracks``; the entry point takes the repaired
+    labels like any others (it weighs a node by the KEPT edges between the members of its track, cut or not)."""
+    _check_repair_rounds(repair_rounds)
     inp = _track_inputs(tuple_size, data, result)
     dev = inp["dev"]
-    label, stats_d = match_tracks(tuple_size, data, result, conf_thresh, _inputs=inp)
+    label, stats_d = match_tracks(tuple_size, data, result, conf_thresh, _inputs=inp, repair_rounds=repair_rounds)
     stats = np.ascontiguousarray(stats_d.cpu().numpy())  # tracks and observations per tuple lay out the workspace
     extrinsics = np.ascontiguousarray(extrinsics, np.float64)
     pk, pm, pc, pi = (_lib.ptr_array(lst) for lst in (inp["kpts"], inp["matches"], inp["conf"], intr))
@@ -682,7 +702,8 @@ def _check_rel_pose_method(rel_pose_method):
         raise NotImplementedError("relative pose method {} is not defined".format(rel_pose_method))
 
 
-def solve_tuple_poses_batch(tuple_size, data, result, conf_thresh=0., timings=None, init="host", rel_pose_method="w8pt_ba", seed=0, tracks=False):
+def solve_tuple_poses_batch(tuple_size, data, result, conf_thresh=0., timings=None, init="host", rel_pose_method="w8pt_ba", seed=0, tracks=False,
+                            repair_rounds=0):
     """``solve_tuple_poses`` for EVERY batch element of the matcher result, in memory: returns the refined world-to-camera
     extrinsics ``float64 [B, tuple_size, 4, 4]``, camera 0 the gauge.  Stages: matches collected on the device (one launch) ->
     relative poses of all B * T(T-1)/2 pairs (``rel_pose_method``) -> one copy to the host, spanning tree and rotation /
@@ -705,10 +726,13 @@ def solve_tuple_poses_batch(tuple_size, data, result, conf_thresh=0., timings=No
     built on the device (``e2emv_mv_tuple_ba_tracks``).  A tuple without any track returns its start.  Needs
     ``rel_pose_method="w8pt_ba"`` (the RANSAC methods filter rows that no longer carry keypoint indices) and per-image
     ``keypoints{t}`` in ``data`` (with per-pair keypoints only, a keypoint has no identity across pairs): ``ValueError``
-    otherwise, before any device call."""
+    otherwise, before any device call.
+    ``repair_rounds`` (int, 0 .. 64; must be 0 unless ``tracks=True``; ``ValueError`` otherwise, before any device call): 0
+    (default) drops the conflicting components as described; ``R > 0`` repairs them first as in ``match_tracks``."""
     import time
     _check_init(init)
     _check_rel_pose_method(rel_pose_method)
+    _check_repair_rounds(repair_rounds, tracks)
     if tracks:
         _check_tracks(tuple_size, data, rel_pose_method)
     ransac = rel_pose_method != "w8pt_ba"
@@ -747,7 +771,8 @@ def solve_tuple_poses_batch(tuple_size, data, result, conf_thresh=0., timings=No
         lap("initialisation")
         out, summary = np.zeros((B, tuple_size, 4, 4)), np.zeros((B, 4))
         if tracks:
-            _tracks_ba_call("e2emv_mv_tuple_ba_tracks", tuple_size, data, result, conf_thresh, intr, kdim, nb, start, 50, _p(out), _p(summary))
+            _tracks_ba_call("e2emv_mv_tuple_ba_tracks", tuple_size, data, result, conf_thresh, intr, kdim, nb, start, 50, _p(out), _p(summary),
+                            repair_rounds=repair_rounds)
         else:
             _tuple_ba_call("e2emv_mv_tuple_ba", tuple_size, collected, counts, intr, kdim, nb, start, 50, _p(out), _p(summary))
         lap("build_and_bundle_adjust")
@@ -772,7 +797,8 @@ def solve_tuple_poses_batch(tuple_size, data, result, conf_thresh=0., timings=No
     lap("initialisation")
     out, summary = np.zeros((B, tuple_size, 4, 4)), np.zeros((B, 4))
     if tracks:
-        _tracks_ba_call("e2emv_mv_tuple_ba_tracks", tuple_size, data, result, conf_thresh, intr, kdim, nb, start, 50, _p(out), _p(summary))
+        _tracks_ba_call("e2emv_mv_tuple_ba_tracks", tuple_size, data, result, conf_thresh, intr, kdim, nb, start, 50, _p(out), _p(summary),
+                        repair_rounds=repair_rounds)
     else:
         _tuple_ba_call("e2emv_mv_tuple_ba", tuple_size, collected, counts, intr, kdim, nb, start, 50, _p(out), _p(summary))
     lap("build_and_bundle_adjust")
@@ -797,19 +823,20 @@ def _tuple_problems(tuple_size, collected, counts, intr, kdim, nb, extrinsics):
             for b in range(B)]
 
 
-def _tuple_problems_tracks(tuple_size, data, result, conf_thresh, intr, kdim, nb, extrinsics):
+def _tuple_problems_tracks(tuple_size, data, result, conf_thresh, intr, kdim, nb, extrinsics, repair_rounds=0):
     """The track problems ``solve_tuple_poses_batch(..., tracks=True)`` solves (``e2emv_mv_tuple_problem_tracks``): ``(problems,
     label, stats)``, one argument tuple of ``bundle_adjust`` per batch element and what ``match_tracks`` returned (label on the
-    device, stats on the host)."""
+    device, stats on the host).  ``repair_rounds``: as in ``match_tracks``."""
+    _check_repair_rounds(repair_rounds)
     inp = _track_inputs(tuple_size, data, result)
-    stats = match_tracks(tuple_size, data, result, conf_thresh, _inputs=inp)[1].cpu().numpy()
+    stats = match_tracks(tuple_size, data, result, conf_thresh, _inputs=inp, repair_rounds=repair_rounds)[1].cpu().numpy()
     B = inp["B"]
     n_pts, n_obs = stats[:, 0].astype(np.int64), stats[:, 1].astype(np.int64)
     tp, to = int(n_pts.sum()), int(n_obs.sum())
     cam_idx, pt_idx = np.zeros(to, np.int32), np.zeros(to, np.int32)
     obs_xy, obs_w, cams, pts = np.zeros((to, 2)), np.zeros((to, 2)), np.zeros((B * tuple_size, 6)), np.zeros((tp, 3))
     label, stats = _tracks_ba_call("e2emv_mv_tuple_problem_tracks", tuple_size, data, result, conf_thresh, intr, kdim, nb, extrinsics, _p(cam_idx),
-                                   _p(pt_idx), _p(obs_xy), _p(obs_w), _p(cams), _p(pts))
+                                   _p(pt_idx), _p(obs_xy), _p(obs_w), _p(cams), _p(pts), repair_rounds=repair_rounds)
     po, oo = np.concatenate([[0], np.cumsum(n_pts)]), np.concatenate([[0], np.cumsum(n_obs)])
     return [(tuple_size, 0, np.array([1., 1., 0., 0.]), cam_idx[oo[b]:oo[b + 1]], pt_idx[oo[b]:oo[b + 1]], obs_xy[oo[b]:oo[b + 1]],
              obs_w[oo[b]:oo[b + 1]], cams[b * tuple_size:(b + 1) * tuple_size], pts[po[b]:po[b + 1]]) for b in range(B)], label, stats
@@ -847,12 +874,14 @@ def eval_bundle_adjust(tuple_size, data, result, tmp_dir, pose_errors, verbose=F
     return pose_errors
 
 
-def eval_bundle_adjust_batch(tuple_size, data, result, pose_errors, verbose=False, init="host", rel_pose_method="w8pt_ba", tracks=False):
+def eval_bundle_adjust_batch(tuple_size, data, result, pose_errors, verbose=False, init="host", rel_pose_method="w8pt_ba", tracks=False,
+                             repair_rounds=0):
     """``eval_bundle_adjust`` for every batch element through ``solve_tuple_poses_batch``: extends ``pose_errors = [max errors,
     translation errors, rotation errors]`` by ``B * T(T-1)/2`` entries, batch element outer, pairs in ``_pairs`` order inside
-    (for ``B = 1`` the entries ``eval_bundle_adjust`` appends, in its order).  ``init``, ``rel_pose_method``, ``tracks``: as
-    in ``solve_tuple_poses_batch``."""
-    extrinsics = solve_tuple_poses_batch(tuple_size, data, result, init=init, rel_pose_method=rel_pose_method, tracks=tracks)
+    (for ``B = 1`` the entries ``eval_bundle_adjust`` appends, in its order).  ``init``, ``rel_pose_method``, ``tracks``,
+    ``repair_rounds``: as in ``solve_tuple_poses_batch``."""
+    extrinsics = solve_tuple_poses_batch(tuple_size, data, result, init=init, rel_pose_method=rel_pose_method, tracks=tracks,
+                                         repair_rounds=repair_rounds)
     poses = np.stack([data["pose" + str(v)].cpu().numpy() for v in range(tuple_size)], 1)  # [B,T,4,4]: one copy per image
     for b, E in enumerate(extrinsics):
         err_t, err_R = tuple_pose_errors(E, poses[b])

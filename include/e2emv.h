@@ -317,6 +317,21 @@ int e2emv_mv_tuple_problem(e2emv_ctx* ctx, int B, int T, int N, const int32_t* c
 int e2emv_mv_tracks(e2emv_ctx* ctx, int B, int T, int N, const int32_t* n_kpts1, const int64_t* const* d_matches,
                     const float* const* d_conf, int conf_channels, float conf_thresh, int32_t* d_label, int32_t* d_stats,
                     void* stream);
+/* e2emv_mv_tracks with a repair stage in front of the labelling: instead of losing every component that holds two keypoints
+ * of one image, cut its weakest edges.  Edge id e = q * N + n (pair q in e2emv_mv_collect order, row n); every kept edge starts
+ * live.  One round: connected components over the live edges; in EVERY conflicting component the live edge with the smallest
+ * (confidence of channel 0 compared as floats with <, -0.0 = +0.0; then the smaller edge id) is cut - one per component per
+ * round.  The stage ends after `rounds` rounds, or when nothing conflicts; labels, tracks and conflicts are then those of
+ * e2emv_mv_tracks over the live edges (a component that still conflicts is dropped, a node without live edge is in no track).
+ * d_stats[b] = {tracks, observations, conflict components LEFT, LIVE edges}: cuts = the edge count of rounds 0 minus d_stats[b][3].
+ * rounds = 0 gives e2emv_mv_tracks' labels and stats bit for bit.  0 <= rounds <= 64, else E2EMV_EINVAL.  d_label / d_stats go to
+ * e2emv_mv_tuple_ba_tracks / e2emv_mv_tuple_problem_tracks unchanged: a node's confidence there stays the mean over the KEPT
+ * edges between it and the other members of its track, so a cut edge whose ends land in one valid track still counts.  One
+ * workgroup per tuple, labels, arg-min keys and the dead-edge bitmap in LDS; no floating-point atomics, the result does not depend
+ * on the batch position or the run.  One launch, no host synchronisation.  Same LIMIT of 16384 nodes, E2EMV_ESHAPE above it. */
+int e2emv_mv_tracks_repair(e2emv_ctx* ctx, int B, int T, int N, const int32_t* n_kpts1, const int64_t* const* d_matches,
+                           const float* const* d_conf, int conf_channels, float conf_thresh, int rounds, int32_t* d_label,
+                           int32_t* d_stats, void* stream);
 /* The counterpart of e2emv_mv_tuple_ba on the tracks: d_label [B,T,Nmax] DEVICE and stats [B,4] HOST copy of d_stats from
  * e2emv_mv_tracks on the same matches / confidences / threshold; d_kpts HOST array of T DEVICE pointers [B,n_kpts[t],2]
  * (the per-image keypoints), n_kpts HOST [T] (<= Nmax; the first image of a pair with matches has >= N); intrinsics and extr

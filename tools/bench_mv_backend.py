@@ -12,9 +12,13 @@ difference between the two forms' extrinsics.  ``--rel-pose-method`` selects the
 (``solve_tuple_poses_batch(..., tracks=True)``; the CSV path has no tracks and stays as it is, so the difference between the two
 paths' extrinsics is then the effect of the tracks); the line also carries the track counts and the time of the label launch
 and of labels + problem build + copy-out on their own (each synchronised), the share of the last stage the new kernels take.
+``--repair-rounds R`` (with ``--tracks``): the labels come from ``e2emv_mv_tracks_repair`` with up to R rounds (0, the default, is
+``e2emv_mv_tracks``).  ``--wrong F`` (with ``--tracks``): the identity-like matcher's matches are clean, so a repair has nothing to
+do on them; F > 0 replaces every matched keypoint with probability F by a uniform random target of confidence U(0, 0.5) (the
+``planted_scene`` recipe of tests/test_gpu_mv_tracks.py, ``default_rng(1000)``) before anything is timed, in both paths.
 
     python tools/bench_mv_backend.py [--batch 8] [--tuple-size 5] [--kpts 1024] [--reps 7] [--init host|device|both]
-                                     [--rel-pose-method w8pt_ba|ransac|ransac_ba] [--tracks]
+                                     [--rel-pose-method w8pt_ba|ransac|ransac_ba] [--tracks [--repair-rounds 0] [--wrong 0.0]]
 """
 import argparse
 import json
@@ -40,7 +44,11 @@ def main():
     ap.add_argument("--init", choices=("host", "device", "both"), default="both")
     ap.add_argument("--rel-pose-method", choices=("w8pt_ba", "ransac", "ransac_ba"), default="w8pt_ba")
     ap.add_argument("--tracks", action="store_true")
+    ap.add_argument("--repair-rounds", type=int, default=0)
+    ap.add_argument("--wrong", type=float, default=0.0)
     args = ap.parse_args()
+    if (args.repair_rounds or args.wrong) and not args.tracks:
+        ap.error("--repair-rounds / --wrong need --tracks")
     B, T, method = args.batch, args.tuple_size, args.rel_pose_method
     gpu = torch.device("cuda", 0)
     cfg = {"GNN_layers": ["self", "cross"] * 2, "sinkhorn_iterations": 50, "multi_frame_matching": True, "tuple_size": T}
@@ -51,6 +59,15 @@ def main():
         dev[f"intr{m}"] = data[f"intr{m}"]
     with torch.no_grad():
         result = model(dev)
+    if args.wrong:
+        rng = np.random.default_rng(1000)
+        result = {k: v.clone() for k, v in result.items()}
+        for j in range(T):
+            for i in range(j):
+                m, c = result[f"matches{i}_{i}_{j}"], result[f"conf_scores_{i}_{j}"]
+                hit = (m >= 0) & torch.from_numpy(rng.uniform(size=tuple(m.shape)) < args.wrong).to(gpu)
+                m[hit] = torch.from_numpy(rng.integers(0, args.kpts, tuple(m.shape))).to(gpu)[hit]
+                c[hit] = torch.from_numpy(rng.uniform(0.0, 0.5, tuple(m.shape))).to(c)[hit].reshape(-1, *c.shape[2:])
     slices = [({k: (v[b:b + 1] if torch.is_tensor(v) else v) for k, v in dev.items()}, {k: v[b:b + 1] for k, v in result.items()}) for b in range(B)]
 
     with tempfile.TemporaryDirectory() as tmp:
@@ -60,7 +77,8 @@ def main():
         forms = ("host", "device") if args.init == "both" else (args.init,)
 
         def batched(init, timings=None):
-            return multi_view.solve_tuple_poses_batch(T, dev, result, timings=timings, init=init, rel_pose_method=method, tracks=args.tracks)
+            return multi_view.solve_tuple_poses_batch(T, dev, result, timings=timings, init=init, rel_pose_method=method, tracks=args.tracks,
+                                                      repair_rounds=args.repair_rounds)
 
         def timed(fn):
             torch.cuda.synchronize()
@@ -85,14 +103,15 @@ def main():
                     stages[f].setdefault(k, []).append(v * 1e3)
         if args.tracks:
             intr, kdim, nb = multi_view._tuple_intrinsics(T, dev, gpu, B)
-            t_label = [timed(lambda: multi_view.match_tracks(T, dev, result))[0] for _ in range(args.reps + 1)][1:]
-            t_build = [timed(lambda: multi_view._tuple_problems_tracks(T, dev, result, 0., intr, kdim, nb, e_batch[forms[0]]))[0]
+            R = args.repair_rounds
+            t_label = [timed(lambda: multi_view.match_tracks(T, dev, result, repair_rounds=R))[0] for _ in range(args.reps + 1)][1:]
+            t_build = [timed(lambda: multi_view._tuple_problems_tracks(T, dev, result, 0., intr, kdim, nb, e_batch[forms[0]], repair_rounds=R))[0]
                        for _ in range(args.reps + 1)][1:]
-            track_stats = multi_view.match_tracks(T, dev, result)[1].cpu().numpy()
+            track_stats = multi_view.match_tracks(T, dev, result, repair_rounds=R)[1].cpu().numpy()
     stat = lambda ts: {"median": float(np.median(ts)), "min": float(np.min(ts)), "max": float(np.max(ts))}  # noqa: E731
     first = forms[0]  # the form the unsuffixed keys describe: the host form unless --init device
     line = {"batch": B, "tuple_size": T, "n_kpts": args.kpts, "reps": args.reps, "init": args.init, "rel_pose_method": method, "csv_path_ms": stat(t_csv),
-            "tracks": args.tracks, "batched_path_ms": stat(t_batch[first]), "batched_stage_ms": {k: float(np.median(v)) for k, v in stages[first].items()},
+            "tracks": args.tracks, "repair_rounds": args.repair_rounds, "wrong": args.wrong, "batched_path_ms": stat(t_batch[first]), "batched_stage_ms": {k: float(np.median(v)) for k, v in stages[first].items()},
             "max_abs_extrinsics_difference": float(np.abs(e_csv - e_batch[first]).max())}
     if args.init == "both":
         line["batched_path_device_init_ms"] = stat(t_batch["device"])
