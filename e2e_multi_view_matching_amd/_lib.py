@@ -107,6 +107,12 @@ SIGNATURES = {
                                          c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "e2emv_mv_tuple_problem_tracks": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, _PP, c_void_p, _PP, _PP, c_int, c_float,
                                               _PP, c_int, c_int, c_void_p] + [c_void_p] * 7),
+    "e2emv_mv_bundle_adjust_batch_loss": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                  c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, ctypes.c_double, c_void_p]),
+    "e2emv_mv_tuple_ba_loss": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, _PP, c_int, c_int, c_void_p, c_int,
+                                       c_void_p, c_void_p, c_int, ctypes.c_double, c_void_p, c_void_p]),
+    "e2emv_mv_tuple_ba_tracks_loss": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, _PP, c_void_p, _PP, _PP, c_int, c_float, _PP,
+                                              c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, ctypes.c_double, c_void_p, c_void_p]),
     "e2emv_mv_init_batch": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                     c_void_p]),
     "e2emv_mv_tuple_init": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),

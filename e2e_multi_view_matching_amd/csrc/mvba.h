@@ -18,9 +18,36 @@ struct MvbaArgs {
     double *cams, *pts;
     double *r, *Jc, *Jp, *Y, *Vinv, *gp, *dp, *scale_p, *cand;
     double* summary;  // [0] initial cost [1] final cost [2] iterations [3] termination code
+    double loss_a;    // scale of the robust loss in the units of the weighted residual (the tuple builds divide it on the device)
 };
 
 enum { kTermMaxIter = 0, kTermGradient = 1, kTermParameter = 2, kTermFunction = 3, kTermInvalid = 4, kTermRadius = 5 };
+
+// Robust loss of an observation (a ceres::LossFunction where the reference passes NULL): s = rx^2 + ry^2 of the WEIGHTED
+// residual, cost = 1/2 sum rho(s).  Both losses have rho'' <= 0, so Ceres' corrector scales the residual and both Jacobian
+// blocks of the observation by sqrt(rho'(s)) and nothing else.  The codes are those of include/e2emv.h.
+enum { kLossNone = E2EMV_LOSS_NONE, kLossHuber = E2EMV_LOSS_HUBER, kLossCauchy = E2EMV_LOSS_CAUCHY };
+
+// rho(s) and sqrt(rho'(s)) at scale a, a2 = a * a.  THE operation order (tests restate it):
+//   huber : s <= a2 ? (rho = s, sqrt(rho') = 1) : (t = sqrt(s); rho = 2 a t - a2; sqrt(rho') = sqrt(a / t))
+//   cauchy: q = s / a2; rho = a2 log1p(q); sqrt(rho') = sqrt(1 / (1 + q))
+// s = 0 takes Huber's first branch (no division); a NaN s fails the comparison and stays NaN through the second.
+template <int LOSS>
+__device__ __forceinline__ void mv_loss(double s, double a, double a2, double* rho, double* sq) {
+    if (LOSS == kLossHuber) {
+        if (s <= a2) {
+            *rho = s; *sq = 1.0;
+        } else {
+            const double t = sqrt(s);
+            *rho = 2.0 * a * t - a2; *sq = sqrt(a / t);
+        }
+    } else if (LOSS == kLossCauchy) {
+        const double q = s / a2;
+        *rho = a2 * log1p(q); *sq = sqrt(1.0 / (1.0 + q));
+    } else {
+        *rho = s; *sq = 1.0;
+    }
+}
 
 __device__ __forceinline__ double mv_wsum(double v) {
 #pragma unroll
@@ -107,8 +134,10 @@ struct MvLayout {
 MvLayout mv_layout(char* base, size_t n, size_t totC, size_t totP, size_t totO, size_t extra);
 // record of problem k: its sizes and its slices (c0 / p0 / o0 = cameras / points / observations of the problems before it)
 MvbaArgs mv_record(const MvLayout& L, size_t k, size_t c0, size_t p0, size_t o0, int C, int fixed, int P, int O, int max_iters,
-                   const double* intr);
-int mv_launch_ba(e2emv_ctx* ctx, const MvLayout& L, int n, hipStream_t s);
+                   const double* intr, double loss_a);
+int mv_launch_ba(e2emv_ctx* ctx, const MvLayout& L, int n, hipStream_t s, int loss);
+int mv_check_loss(e2emv_ctx* ctx, const char* who, int loss, double* scale);
+int mv_tuple_results(e2emv_ctx* ctx, const MvLayout& L, int B, int T, double* out_extr, double* summary, double* loss_a_out, hipStream_t s);
 void mv_extr_to_cam(const double* E /* 4x4 row-major */, double* cam);
 void mv_cam_to_extr(const double* cam, double* E);
 

@@ -17,6 +17,8 @@
 //   H  thread / observation : model cost change -m.(r + m/2), m = J d;  cost at the candidate
 //   I  thread 0             : step acceptance, trust-region radius, termination tests
 // All arithmetic fp64; every reduction has a fixed order (no atomics), so results are run-to-run identical.
+// Opt-in robust loss (Huber, Cauchy; mvba.h): the kernel is a template over it, phases A and H apply Ceres' corrector and sum rho(s);
+// without a loss it is the reference's squared loss (ba_problem.cpp:135,144 pass NULL) and the arithmetic it always was.
 // Quirk kept (ba_problem.cpp:129-137): observations of the fixed camera are predicted with the identity pose and that
 // camera's parameters are written back untouched.
 #include <algorithm>
@@ -117,8 +119,13 @@ __device__ __forceinline__ void mv_transform(const double* cam, bool identity, c
 // One workgroup per problem: blockIdx.x selects the problem's record (sizes, intrinsics, fixed camera and the addresses of
 // ITS slices of the shared index / data / scratch arrays and of its summary slot).  Nothing below knows of the other
 // workgroups: several problems may share a CU (24 KB of LDS, 8 waves each), none shares a byte of global memory.
+// LOSS: the robust loss (mvba.h).  Only phases A and H know of it: A stores the CORRECTED r, Jc, Jp (scaled by sqrt(rho')) and sums
+// rho(s) into the cost, H sums rho(s) at the candidate; B - G and the model cost change read the stored arrays as they are.  The
+// kLossNone instantiation is the kernel as it always was, operation for operation.
+template <int LOSS>
 __global__ __launch_bounds__(kMvThreads) void mvba_kernel(const MvbaArgs* __restrict__ recs) {
     const MvbaArgs& a = recs[blockIdx.x];
+    const double loss_a = LOSS != kLossNone ? a.loss_a : 0.0, loss_a2 = loss_a * loss_a;
     __shared__ double s_cams[kMvN], s_cand[kMvN], s_scale[kMvN], s_lam[kMvN], s_gc[kMvN], s_dc[kMvN], s_rhs[kMvN];
     __shared__ double s_U[kMvMaxCams * 36];
     __shared__ double s_S[kMvN * kMvN];
@@ -154,11 +161,20 @@ __global__ __launch_bounds__(kMvThreads) void mvba_kernel(const MvbaArgs* __rest
             const bool fixed = (c == a.fixed);
             mv_transform(&s_cams[6 * c], fixed, X, q, R, D, true);
             const double iz = 1.0 / q[2], wx = a.wts[2 * o], wy = a.wts[2 * o + 1];
-            const double rx = wx * (a.fx * q[0] * iz + a.cx - a.obs[2 * o]), ry = wy * (a.fy * q[1] * iz + a.cy - a.obs[2 * o + 1]);
-            a.r[2 * o] = rx; a.r[2 * o + 1] = ry;
-            red[0] += rx * rx + ry * ry;
+            double rx = wx * (a.fx * q[0] * iz + a.cx - a.obs[2 * o]), ry = wy * (a.fy * q[1] * iz + a.cy - a.obs[2 * o + 1]);
             // d(residual)/d(q): rows weighted
-            const double e00 = wx * a.fx * iz, e02 = -wx * a.fx * q[0] * iz * iz, e11 = wy * a.fy * iz, e12 = -wy * a.fy * q[1] * iz * iz;
+            double e00 = wx * a.fx * iz, e02 = -wx * a.fx * q[0] * iz * iz, e11 = wy * a.fy * iz, e12 = -wy * a.fy * q[1] * iz * iz;
+            if (LOSS == kLossNone) {
+                red[0] += rx * rx + ry * ry;
+            } else {
+                // the corrector: residual and both Jacobian blocks (through the rows of d(residual)/d(q)) times sqrt(rho')
+                double rho, sq;
+                mv_loss<LOSS>(rx * rx + ry * ry, loss_a, loss_a2, &rho, &sq);
+                red[0] += rho;
+                rx *= sq; ry *= sq;
+                e00 *= sq; e02 *= sq; e11 *= sq; e12 *= sq;
+            }
+            a.r[2 * o] = rx; a.r[2 * o + 1] = ry;
             double* jc = a.Jc + 12 * size_t(o);
             double* jp = a.Jp + 6 * size_t(o);
 #pragma unroll
@@ -427,7 +443,13 @@ __global__ __launch_bounds__(kMvThreads) void mvba_kernel(const MvbaArgs* __rest
                 mv_transform(&s_cand[6 * c], c == a.fixed, X, q, nullptr, nullptr, false);
                 const double iz = 1.0 / q[2];
                 const double rx = a.wts[2 * o] * (a.fx * q[0] * iz + a.cx - a.obs[2 * o]), ry = a.wts[2 * o + 1] * (a.fy * q[1] * iz + a.cy - a.obs[2 * o + 1]);
-                r4[3] += rx * rx + ry * ry;
+                if (LOSS == kLossNone) {
+                    r4[3] += rx * rx + ry * ry;
+                } else {
+                    double rho, sq;
+                    mv_loss<LOSS>(rx * rx + ry * ry, loss_a, loss_a2, &rho, &sq);
+                    r4[3] += rho;
+                }
             }
         }
         mv_block_reduce<4, 4>(r4, s_red);
@@ -564,6 +586,7 @@ struct MvBuildArgs {
     const double* proj;                                    // [B,T,3,4] world -> camera
     const MvPairRec* pairs;                                // [B*P]
     const MvbaArgs* recs;                                  // [B] the problems being built
+    double loss_scale;                                     // relative scale of the robust loss (0: no loss)
 };
 
 // Bundle-adjustment problem of every tuple from the collected matches (write_bundle_adjust_problem without the text): thread =
@@ -587,7 +610,11 @@ __global__ __launch_bounds__(kMvRowThreads) void mv_build_kernel(MvBuildArgs g) 
     sum = s_red[0];
     for (int w = 1; w < kMvRowThreads / 64; ++w) sum += s_red[w];
     const double half_total = 0.5 * (2.0 * sum + 1e-3);  // every confidence is seen by two observations (normalize_confidences)
-    if (blockIdx.x == 0 && blockIdx.y == b * g.P && tid == 0) const_cast<int*>(a.pt_start)[a.P] = 2 * a.P;
+    if (blockIdx.x == 0 && blockIdx.y == b * g.P && tid == 0) {
+        const_cast<int*>(a.pt_start)[a.P] = 2 * a.P;
+        // the loss acts on confidence x residual whatever the tuple's size: its scale is divided by what the confidences are
+        if (g.loss_scale > 0.0) const_cast<MvbaArgs&>(a).loss_a = g.loss_scale / half_total;
+    }
     const int m = blockIdx.x * kMvRowThreads + tid;
     if (m >= rec.count) return;
     const size_t row = size_t(pp) * g.N + m;
@@ -639,8 +666,9 @@ MvLayout mv_layout(char* base, size_t n, size_t totC, size_t totP, size_t totO, 
 
 // record of problem k: its sizes and its slices (c0 / p0 / o0 = cameras / points / observations of the problems before it)
 MvbaArgs mv_record(const MvLayout& L, size_t k, size_t c0, size_t p0, size_t o0, int C, int fixed, int P, int O, int max_iters,
-                   const double* intr) {
+                   const double* intr, double loss_a) {
     MvbaArgs a{};
+    a.loss_a = loss_a;
     a.C = C; a.fixed = fixed; a.P = P; a.O = O; a.max_iters = max_iters;
     a.fx = intr[0]; a.fy = intr[1]; a.cx = intr[2]; a.cy = intr[3];
     a.cam_idx = L.cam_idx + o0; a.pt_idx = L.pt_idx + o0; a.pt_obs = L.pt_obs + o0; a.cam_obs = L.cam_obs + o0;
@@ -653,11 +681,28 @@ MvbaArgs mv_record(const MvLayout& L, size_t k, size_t c0, size_t p0, size_t o0,
     return a;
 }
 
-int mv_launch_ba(e2emv_ctx* ctx, const MvLayout& L, int n, hipStream_t s) {
+int mv_launch_ba(e2emv_ctx* ctx, const MvLayout& L, int n, hipStream_t s, int loss) {
     prof_begin(ctx, PS_W8PT, s);
-    hipLaunchKernelGGL(mvba_kernel, dim3(n), dim3(kMvThreads), 0, s, L.recs);
+    if (loss == kLossHuber) hipLaunchKernelGGL(mvba_kernel<kLossHuber>, dim3(n), dim3(kMvThreads), 0, s, L.recs);
+    else if (loss == kLossCauchy) hipLaunchKernelGGL(mvba_kernel<kLossCauchy>, dim3(n), dim3(kMvThreads), 0, s, L.recs);
+    else hipLaunchKernelGGL(mvba_kernel<kLossNone>, dim3(n), dim3(kMvThreads), 0, s, L.recs);
     E2EMV_CHECK_LAUNCH(ctx, "mvba_kernel");
     prof_end(ctx, s);
+    return E2EMV_OK;
+}
+
+// what the tuple entry points bring back once the solver has run: cameras as extrinsics, summaries and (loss_a_out, may be
+// NULL) the loss scale each record carried, [B]
+int mv_tuple_results(e2emv_ctx* ctx, const MvLayout& L, int B, int T, double* out_extr, double* summary, double* loss_a_out, hipStream_t s) {
+    std::vector<double> cams(size_t(B) * T * 6), sm(size_t(B) * 4);
+    std::vector<MvbaArgs> recs(loss_a_out ? size_t(B) : 0);
+    E2EMV_HIP(ctx, hipMemcpyAsync(cams.data(), L.cams, sizeof(double) * cams.size(), hipMemcpyDeviceToHost, s));
+    E2EMV_HIP(ctx, hipMemcpyAsync(sm.data(), L.summary, sizeof(double) * sm.size(), hipMemcpyDeviceToHost, s));
+    if (loss_a_out) E2EMV_HIP(ctx, hipMemcpyAsync(recs.data(), L.recs, sizeof(MvbaArgs) * recs.size(), hipMemcpyDeviceToHost, s));
+    E2EMV_HIP(ctx, hipStreamSynchronize(s));
+    for (size_t v = 0; v < size_t(B) * T; ++v) mv_cam_to_extr(&cams[6 * v], out_extr + 16 * v);
+    if (summary) std::memcpy(summary, sm.data(), sizeof(double) * sm.size());
+    for (size_t b = 0; b < recs.size(); ++b) loss_a_out[b] = recs[b].loss_a;
     return E2EMV_OK;
 }
 
@@ -680,12 +725,24 @@ void mv_cam_to_extr(const double* cam, double* E) {
 
 using namespace e2emv;
 
-extern "C" int e2emv_mv_bundle_adjust_batch(e2emv_ctx* ctx, int n_problems, const int32_t* n_cams, const int32_t* fixed_cam,
-                                            const double* intr, const int64_t* pt_off, const int64_t* obs_off, const int32_t* cam_idx,
-                                            const int32_t* pt_idx, const double* obs_xy, const double* obs_w, double* cams, double* pts,
-                                            int max_iterations, double* summary, void* stream) {
+namespace e2emv {
+// the loss arguments of the *_loss entry points: a known code, and with a loss a finite scale > 0; *scale = 0 without a loss
+int mv_check_loss(e2emv_ctx* ctx, const char* who, int loss, double* scale) {
+    if (loss != kLossNone && loss != kLossHuber && loss != kLossCauchy) return set_err(ctx, E2EMV_EINVAL, "%s: unknown loss code %d", who, loss);
+    if (loss == kLossNone) { *scale = 0.0; return E2EMV_OK; }
+    if (!std::isfinite(*scale) || !(*scale > 0.0)) return set_err(ctx, E2EMV_EINVAL, "%s: the loss scale must be finite and > 0 (got %g)", who, *scale);
+    return E2EMV_OK;
+}
+}  // namespace e2emv
+
+extern "C" int e2emv_mv_bundle_adjust_batch_loss(e2emv_ctx* ctx, int n_problems, const int32_t* n_cams, const int32_t* fixed_cam,
+                                                 const double* intr, const int64_t* pt_off, const int64_t* obs_off, const int32_t* cam_idx,
+                                                 const int32_t* pt_idx, const double* obs_xy, const double* obs_w, double* cams, double* pts,
+                                                 int max_iterations, double* summary, int loss, double loss_scale, void* stream) {
     if (!ctx) return E2EMV_EINVAL;
     E2EMV_ENTER(ctx, stream);
+    const int lc = mv_check_loss(ctx, "mv_bundle_adjust_batch", loss, &loss_scale);
+    if (lc) return lc;
     if (n_problems < 1 || !n_cams || !fixed_cam || !intr || !pt_off || !obs_off || !cams)
         return set_err(ctx, E2EMV_EINVAL, "mv_bundle_adjust_batch: bad argument (n_problems >= 1, no NULL size / offset array)");
     const size_t n = size_t(n_problems);
@@ -728,7 +785,7 @@ extern "C" int e2emv_mv_bundle_adjust_batch(e2emv_ctx* ctx, int n_problems, cons
         for (int c = 0; c < C; ++c) cs[c + 1] += cs[c];
         std::vector<int> pf(ps, ps + P), cf(cs, cs + C);
         for (int o = 0; o < O; ++o) { pobs[o0 + pf[pi[o]]++] = o; cobs[o0 + cf[ci[o]]++] = o; }
-        recs[k] = mv_record(L, k, c0, p0, o0, C, fixed_cam[k], P, O, max_iterations, intr + 4 * k);
+        recs[k] = mv_record(L, k, c0, p0, o0, C, fixed_cam[k], P, O, max_iterations, intr + 4 * k, loss_scale);
         c0 += size_t(C);
     }
     E2EMV_HIP(ctx, hipMemcpyAsync(L.recs, recs.data(), sizeof(MvbaArgs) * n, hipMemcpyHostToDevice, s));
@@ -745,7 +802,7 @@ extern "C" int e2emv_mv_bundle_adjust_batch(e2emv_ctx* ctx, int n_problems, cons
         E2EMV_HIP(ctx, hipMemcpyAsync(L.cam_obs, cobs.data(), sizeof(int) * totO, hipMemcpyHostToDevice, s));
     }
     E2EMV_HIP(ctx, hipStreamSynchronize(s));  // the host staging vectors die at return
-    const int lrc = mv_launch_ba(ctx, L, n_problems, s);
+    const int lrc = mv_launch_ba(ctx, L, n_problems, s, loss);
     if (lrc) return lrc;
     E2EMV_HIP(ctx, hipMemcpyAsync(cams, L.cams, sizeof(double) * 6 * totC, hipMemcpyDeviceToHost, s));
     if (totP) E2EMV_HIP(ctx, hipMemcpyAsync(pts, L.pts, sizeof(double) * 3 * totP, hipMemcpyDeviceToHost, s));
@@ -754,6 +811,14 @@ extern "C" int e2emv_mv_bundle_adjust_batch(e2emv_ctx* ctx, int n_problems, cons
     E2EMV_HIP(ctx, hipStreamSynchronize(s));
     if (summary) std::memcpy(summary, sm.data(), sizeof(double) * 4 * n);
     return E2EMV_OK;
+}
+
+extern "C" int e2emv_mv_bundle_adjust_batch(e2emv_ctx* ctx, int n_problems, const int32_t* n_cams, const int32_t* fixed_cam,
+                                            const double* intr, const int64_t* pt_off, const int64_t* obs_off, const int32_t* cam_idx,
+                                            const int32_t* pt_idx, const double* obs_xy, const double* obs_w, double* cams, double* pts,
+                                            int max_iterations, double* summary, void* stream) {
+    return e2emv_mv_bundle_adjust_batch_loss(ctx, n_problems, n_cams, fixed_cam, intr, pt_off, obs_off, cam_idx, pt_idx, obs_xy, obs_w, cams, pts,
+                                             max_iterations, summary, kLossNone, 0.0, stream);
 }
 
 extern "C" int e2emv_mv_bundle_adjust(e2emv_ctx* ctx, int n_cams, int fixed_cam, int n_pts, int n_obs, const double* intr,
@@ -799,7 +864,7 @@ extern "C" int e2emv_mv_collect(e2emv_ctx* ctx, int B, int T, int N, const float
 // tuples in the workspace, described by *L
 static int mv_tuple_build(e2emv_ctx* ctx, const char* who, int B, int T, int N, const int32_t* counts, const float* d_mkpts0,
                           const float* d_mkpts1, const float* d_mconf, const float* const* d_intr, int kdim, int intr_batch,
-                          const double* extr, int max_iterations, MvLayout* L, size_t* totP_out, hipStream_t s) {
+                          const double* extr, int max_iterations, double loss_scale, MvLayout* L, size_t* totP_out, hipStream_t s) {
     if (B < 1 || N < 1 || !counts || !d_mkpts0 || !d_mkpts1 || !d_mconf || !d_intr || !extr)
         return set_err(ctx, E2EMV_EINVAL, "%s: bad argument (B, N >= 1, no NULL array)", who);
     if (T < 2 || T > kMvMaxCams) return set_err(ctx, E2EMV_EINVAL, "%s: tuple of %d images (2 <= T <= %d)", who, T, kMvMaxCams);
@@ -852,7 +917,7 @@ static int mv_tuple_build(e2emv_ctx* ctx, const char* who, int B, int T, int N, 
             std::memcpy(proj + (size_t(b) * T + t) * 12, E, 12 * sizeof(double));
             mv_extr_to_cam(E, cams + (size_t(b) * T + t) * 6);
         }
-        recs[b] = mv_record(*L, size_t(b), size_t(b) * T, p0, 2 * p0, T, 0, pts_b, 2 * pts_b, max_iterations, unit_intr);
+        recs[b] = mv_record(*L, size_t(b), size_t(b) * T, p0, 2 * p0, T, 0, pts_b, 2 * pts_b, max_iterations, unit_intr, 0.0);
         p0 += size_t(pts_b);
     }
     E2EMV_HIP(ctx, hipMemcpyAsync(ctx->d_ws, stage.data(), stage.size(), hipMemcpyHostToDevice, s));
@@ -864,32 +929,37 @@ static int mv_tuple_build(e2emv_ctx* ctx, const char* who, int B, int T, int N, 
     g.proj = reinterpret_cast<const double*>(L->extra);
     g.pairs = reinterpret_cast<const MvPairRec*>(L->extra + proj_bytes);
     g.recs = L->recs;
+    g.loss_scale = loss_scale;
     hipLaunchKernelGGL(mv_build_kernel, dim3((N + kMvRowThreads - 1) / kMvRowThreads, B * P), dim3(kMvRowThreads), 0, s, g);
     E2EMV_CHECK_LAUNCH(ctx, "mv_build_kernel");
     *totP_out = totP;
     return E2EMV_OK;
 }
 
-extern "C" int e2emv_mv_tuple_ba(e2emv_ctx* ctx, int B, int T, int N, const int32_t* counts, const float* d_mkpts0, const float* d_mkpts1,
-                                 const float* d_mconf, const float* const* d_intr, int kdim, int intr_batch, const double* extr,
-                                 int max_iterations, double* out_extr, double* summary, void* stream) {
+extern "C" int e2emv_mv_tuple_ba_loss(e2emv_ctx* ctx, int B, int T, int N, const int32_t* counts, const float* d_mkpts0,
+                                      const float* d_mkpts1, const float* d_mconf, const float* const* d_intr, int kdim, int intr_batch,
+                                      const double* extr, int max_iterations, double* out_extr, double* summary, int loss,
+                                      double loss_scale, double* loss_a_out, void* stream) {
     if (!ctx) return E2EMV_EINVAL;
     E2EMV_ENTER(ctx, stream);
     if (!out_extr) return set_err(ctx, E2EMV_EINVAL, "mv_tuple_ba: NULL output");
+    int rc = mv_check_loss(ctx, "mv_tuple_ba", loss, &loss_scale);
+    if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     MvLayout L;
     size_t totP = 0;
-    int rc = mv_tuple_build(ctx, "mv_tuple_ba", B, T, N, counts, d_mkpts0, d_mkpts1, d_mconf, d_intr, kdim, intr_batch, extr, max_iterations, &L, &totP, s);
+    rc = mv_tuple_build(ctx, "mv_tuple_ba", B, T, N, counts, d_mkpts0, d_mkpts1, d_mconf, d_intr, kdim, intr_batch, extr, max_iterations, loss_scale, &L, &totP, s);
     if (rc) return rc;
-    rc = mv_launch_ba(ctx, L, B, s);
+    rc = mv_launch_ba(ctx, L, B, s, loss);
     if (rc) return rc;
-    std::vector<double> cams(size_t(B) * T * 6), sm(size_t(B) * 4);
-    E2EMV_HIP(ctx, hipMemcpyAsync(cams.data(), L.cams, sizeof(double) * cams.size(), hipMemcpyDeviceToHost, s));
-    E2EMV_HIP(ctx, hipMemcpyAsync(sm.data(), L.summary, sizeof(double) * sm.size(), hipMemcpyDeviceToHost, s));
-    E2EMV_HIP(ctx, hipStreamSynchronize(s));
-    for (size_t v = 0; v < size_t(B) * T; ++v) mv_cam_to_extr(&cams[6 * v], out_extr + 16 * v);
-    if (summary) std::memcpy(summary, sm.data(), sizeof(double) * sm.size());
-    return E2EMV_OK;
+    return mv_tuple_results(ctx, L, B, T, out_extr, summary, loss_a_out, s);
+}
+
+extern "C" int e2emv_mv_tuple_ba(e2emv_ctx* ctx, int B, int T, int N, const int32_t* counts, const float* d_mkpts0, const float* d_mkpts1,
+                                 const float* d_mconf, const float* const* d_intr, int kdim, int intr_batch, const double* extr,
+                                 int max_iterations, double* out_extr, double* summary, void* stream) {
+    return e2emv_mv_tuple_ba_loss(ctx, B, T, N, counts, d_mkpts0, d_mkpts1, d_mconf, d_intr, kdim, intr_batch, extr, max_iterations, out_extr,
+                                  summary, kLossNone, 0.0, nullptr, stream);
 }
 
 extern "C" int e2emv_mv_tuple_problem(e2emv_ctx* ctx, int B, int T, int N, const int32_t* counts, const float* d_mkpts0,
@@ -902,7 +972,7 @@ extern "C" int e2emv_mv_tuple_problem(e2emv_ctx* ctx, int B, int T, int N, const
     hipStream_t s = (hipStream_t)stream;
     MvLayout L;
     size_t totP = 0;
-    const int rc = mv_tuple_build(ctx, "mv_tuple_problem", B, T, N, counts, d_mkpts0, d_mkpts1, d_mconf, d_intr, kdim, intr_batch, extr, 0, &L, &totP, s);
+    const int rc = mv_tuple_build(ctx, "mv_tuple_problem", B, T, N, counts, d_mkpts0, d_mkpts1, d_mconf, d_intr, kdim, intr_batch, extr, 0, 0.0, &L, &totP, s);
     if (rc) return rc;
     if (totP && (!cam_idx || !pt_idx || !obs_xy || !obs_w || !pts)) return set_err(ctx, E2EMV_EINVAL, "mv_tuple_problem: NULL output for %zu points", totP);
     E2EMV_HIP(ctx, hipMemcpyAsync(cams, L.cams, sizeof(double) * 6 * B * T, hipMemcpyDeviceToHost, s));

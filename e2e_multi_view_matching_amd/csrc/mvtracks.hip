@@ -349,6 +349,7 @@ struct MvEmitArgs {
     const double* proj;             // [B,T,3,4] world -> camera
     int* member;                    // [points of the batch,T] scratch: the keypoint of image t in the point, or -1
     const MvbaArgs* recs;           // [B] the problems being built
+    double loss_scale;              // relative scale of the robust loss (0: no loss)
 };
 
 // The track problem of one tuple per workgroup, from its labels.  Roots (label == own id) in ascending id are the points (ordered
@@ -543,6 +544,8 @@ __global__ __launch_bounds__(kMvRowThreads) void mv_tracks_emit_kernel(MvEmitArg
     double total = s_red[0];
     for (int w = 1; w < kMvRowThreads / 64; ++w) total += s_red[w];
     const double half_total = 0.5 * (total + 1e-3);
+    // the loss scale relative to the weights, as in mv_build_kernel
+    if (tid == 0 && g.loss_scale > 0.0) const_cast<MvbaArgs&>(a).loss_a = g.loss_scale / half_total;
     for (int o = tid; o < O; o += kMvRowThreads) {
         const double w = wts[2 * o] / half_total;
         wts[2 * o] = w; wts[2 * o + 1] = w;
@@ -576,7 +579,7 @@ static int mv_edge_args(e2emv_ctx* ctx, const char* who, int B, int T, int N, in
 static int mv_tracks_build(e2emv_ctx* ctx, const char* who, int B, int T, int N, int Nmax, const int32_t* d_label, const int32_t* stats,
                            const float* const* d_kpts, const int32_t* n_kpts, const int64_t* const* d_matches, const float* const* d_conf,
                            int channels, float thresh, const float* const* d_intr, int kdim, int intr_batch, const double* extr,
-                           int max_iterations, MvLayout* L, size_t* totP_out, size_t* totO_out, hipStream_t s) {
+                           int max_iterations, double loss_scale, MvLayout* L, size_t* totP_out, size_t* totO_out, hipStream_t s) {
     if (!d_label || !stats || !d_kpts || !n_kpts || !d_intr || !extr || Nmax < 1) return set_err(ctx, E2EMV_EINVAL, "%s: bad argument (Nmax >= 1, no NULL array)", who);
     if (T < 2 || T > kMvMaxCams) return set_err(ctx, E2EMV_EINVAL, "%s: tuple of %d images (2 <= T <= %d)", who, T, kMvMaxCams);
     if (kdim != 3 && kdim != 4) return set_err(ctx, E2EMV_ESHAPE, "%s: intrinsics must be 3x3 or 4x4", who);
@@ -623,7 +626,7 @@ static int mv_tracks_build(e2emv_ctx* ctx, const char* who, int B, int T, int N,
             std::memcpy(proj + (size_t(b) * T + t) * 12, E, 12 * sizeof(double));
             mv_extr_to_cam(E, cams + (size_t(b) * T + t) * 6);
         }
-        recs[b] = mv_record(*L, size_t(b), size_t(b) * T, p0, o0, T, 0, stats[4 * b], stats[4 * b + 1], max_iterations, unit_intr);
+        recs[b] = mv_record(*L, size_t(b), size_t(b) * T, p0, o0, T, 0, stats[4 * b], stats[4 * b + 1], max_iterations, unit_intr, 0.0);
         p0 += size_t(stats[4 * b]); o0 += size_t(stats[4 * b + 1]);
     }
     E2EMV_HIP(ctx, hipMemcpyAsync(ctx->d_ws, stage.data(), stage.size(), hipMemcpyHostToDevice, s));
@@ -633,6 +636,7 @@ static int mv_tracks_build(e2emv_ctx* ctx, const char* who, int B, int T, int N,
     g.proj = reinterpret_cast<const double*>(L->extra);
     g.member = reinterpret_cast<int*>(L->extra + proj_bytes);
     g.recs = L->recs;
+    g.loss_scale = loss_scale;
     const size_t lds = size_t(T) * Nmax * sizeof(unsigned short);
     rc = ensure_dynamic_lds(ctx, reinterpret_cast<const void*>(mv_tracks_emit_kernel), lds);
     if (rc) return rc;
@@ -683,29 +687,34 @@ extern "C" int e2emv_mv_tracks_repair(e2emv_ctx* ctx, int B, int T, int N, const
     return E2EMV_OK;
 }
 
+extern "C" int e2emv_mv_tuple_ba_tracks_loss(e2emv_ctx* ctx, int B, int T, int N, int Nmax, const int32_t* d_label, const int32_t* stats,
+                                             const float* const* d_kpts, const int32_t* n_kpts, const int64_t* const* d_matches,
+                                             const float* const* d_conf, int conf_channels, float conf_thresh, const float* const* d_intr,
+                                             int kdim, int intr_batch, const double* extr, int max_iterations, double* out_extr,
+                                             double* summary, int loss, double loss_scale, double* loss_a_out, void* stream) {
+    if (!ctx) return E2EMV_EINVAL;
+    E2EMV_ENTER(ctx, stream);
+    if (!out_extr) return set_err(ctx, E2EMV_EINVAL, "mv_tuple_ba_tracks: NULL output");
+    int rc = mv_check_loss(ctx, "mv_tuple_ba_tracks", loss, &loss_scale);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    MvLayout L;
+    size_t totP = 0, totO = 0;
+    rc = mv_tracks_build(ctx, "mv_tuple_ba_tracks", B, T, N, Nmax, d_label, stats, d_kpts, n_kpts, d_matches, d_conf, conf_channels,
+                         conf_thresh, d_intr, kdim, intr_batch, extr, max_iterations, loss_scale, &L, &totP, &totO, s);
+    if (rc) return rc;
+    rc = mv_launch_ba(ctx, L, B, s, loss);
+    if (rc) return rc;
+    return mv_tuple_results(ctx, L, B, T, out_extr, summary, loss_a_out, s);
+}
+
 extern "C" int e2emv_mv_tuple_ba_tracks(e2emv_ctx* ctx, int B, int T, int N, int Nmax, const int32_t* d_label, const int32_t* stats,
                                         const float* const* d_kpts, const int32_t* n_kpts, const int64_t* const* d_matches,
                                         const float* const* d_conf, int conf_channels, float conf_thresh, const float* const* d_intr,
                                         int kdim, int intr_batch, const double* extr, int max_iterations, double* out_extr,
                                         double* summary, void* stream) {
-    if (!ctx) return E2EMV_EINVAL;
-    E2EMV_ENTER(ctx, stream);
-    if (!out_extr) return set_err(ctx, E2EMV_EINVAL, "mv_tuple_ba_tracks: NULL output");
-    hipStream_t s = (hipStream_t)stream;
-    MvLayout L;
-    size_t totP = 0, totO = 0;
-    int rc = mv_tracks_build(ctx, "mv_tuple_ba_tracks", B, T, N, Nmax, d_label, stats, d_kpts, n_kpts, d_matches, d_conf, conf_channels,
-                             conf_thresh, d_intr, kdim, intr_batch, extr, max_iterations, &L, &totP, &totO, s);
-    if (rc) return rc;
-    rc = mv_launch_ba(ctx, L, B, s);
-    if (rc) return rc;
-    std::vector<double> cams(size_t(B) * T * 6), sm(size_t(B) * 4);
-    E2EMV_HIP(ctx, hipMemcpyAsync(cams.data(), L.cams, sizeof(double) * cams.size(), hipMemcpyDeviceToHost, s));
-    E2EMV_HIP(ctx, hipMemcpyAsync(sm.data(), L.summary, sizeof(double) * sm.size(), hipMemcpyDeviceToHost, s));
-    E2EMV_HIP(ctx, hipStreamSynchronize(s));
-    for (size_t v = 0; v < size_t(B) * T; ++v) mv_cam_to_extr(&cams[6 * v], out_extr + 16 * v);
-    if (summary) std::memcpy(summary, sm.data(), sizeof(double) * sm.size());
-    return E2EMV_OK;
+    return e2emv_mv_tuple_ba_tracks_loss(ctx, B, T, N, Nmax, d_label, stats, d_kpts, n_kpts, d_matches, d_conf, conf_channels, conf_thresh,
+                                         d_intr, kdim, intr_batch, extr, max_iterations, out_extr, summary, kLossNone, 0.0, nullptr, stream);
 }
 
 extern "C" int e2emv_mv_tuple_problem_tracks(e2emv_ctx* ctx, int B, int T, int N, int Nmax, const int32_t* d_label, const int32_t* stats,
@@ -720,7 +729,7 @@ extern "C" int e2emv_mv_tuple_problem_tracks(e2emv_ctx* ctx, int B, int T, int N
     MvLayout L;
     size_t totP = 0, totO = 0;
     const int rc = mv_tracks_build(ctx, "mv_tuple_problem_tracks", B, T, N, Nmax, d_label, stats, d_kpts, n_kpts, d_matches, d_conf,
-                                   conf_channels, conf_thresh, d_intr, kdim, intr_batch, extr, 0, &L, &totP, &totO, s);
+                                   conf_channels, conf_thresh, d_intr, kdim, intr_batch, extr, 0, 0.0, &L, &totP, &totO, s);
     if (rc) return rc;
     if (totP && (!cam_idx || !pt_idx || !obs_xy || !obs_w || !pts)) return set_err(ctx, E2EMV_EINVAL, "mv_tuple_problem_tracks: NULL output for %zu points", totP);
     E2EMV_HIP(ctx, hipMemcpyAsync(cams, L.cams, sizeof(double) * 6 * B * T, hipMemcpyDeviceToHost, s));

@@ -402,8 +402,33 @@ def run_bundle_adjuster(directory):
              _lib.stream_ptr(dev))
 
 
-def bundle_adjust(n_cams, fixed_cam, intr, cam_idx, pt_idx, obs_xy, obs_w, cams, pts, max_iterations=50):
-    """In-memory form of the device solver (``e2emv_mv_bundle_adjust``); returns ``(cams, pts, summary)``."""
+LOSSES = {None: 0, "huber": 1, "cauchy": 2}  # E2EMV_LOSS_* of include/e2emv.h
+
+
+def _check_loss(loss, loss_scale):
+    """``loss`` is ``None``, "huber" or "cauchy"; a loss needs a finite positive ``loss_scale`` and no loss takes none: checked on
+    the host before any device call.  Returns the code of the C ABI."""
+    if not (loss is None or isinstance(loss, str)) or loss not in LOSSES:
+        raise ValueError("loss must be None, \"huber\" or \"cauchy\", not {!r}".format(loss))
+    if loss is None:
+        if loss_scale is not None:
+            raise ValueError("loss_scale={!r} needs a loss: without one there is nothing to scale".format(loss_scale))
+        return 0
+    if loss_scale is None:
+        raise ValueError("loss={!r} needs a loss_scale".format(loss))
+    if isinstance(loss_scale, bool) or not isinstance(loss_scale, (int, float, np.integer, np.floating)) or not np.isfinite(loss_scale) or not loss_scale > 0:
+        raise ValueError("loss_scale must be a finite positive number, not {!r}".format(loss_scale))
+    return LOSSES[loss]
+
+
+def bundle_adjust(n_cams, fixed_cam, intr, cam_idx, pt_idx, obs_xy, obs_w, cams, pts, max_iterations=50, loss=None, loss_scale=None):
+    """In-memory form of the device solver (``e2emv_mv_bundle_adjust``); returns ``(cams, pts, summary)``.
+    ``loss``: ``None`` (default, the reference's squared loss), "huber" or "cauchy" with ``loss_scale`` = the scale ``a`` of the
+    ``ceres::LossFunction`` in the units of the WEIGHTED residual (the batch of one of ``bundle_adjust_batch``); the costs of the
+    summary are then ``1/2 sum rho``.  ``ValueError`` for another name, a loss without a scale, a scale without a loss, or a scale
+    that is not a finite positive number."""
+    if _check_loss(loss, loss_scale):
+        return bundle_adjust_batch([(n_cams, fixed_cam, intr, cam_idx, pt_idx, obs_xy, obs_w, cams, pts)], max_iterations, loss, loss_scale)[0]
     dev = _dev()
     ctx = _lib.context(dev)
     cam_idx, pt_idx = np.ascontiguousarray(cam_idx, np.int32), np.ascontiguousarray(pt_idx, np.int32)
@@ -421,11 +446,13 @@ def _ba_summary(summary):
     return dict(initial_cost=summary[0], final_cost=summary[1], iterations=int(summary[2]), termination=names[int(summary[3])])
 
 
-def bundle_adjust_batch(problems, max_iterations=50):
+def bundle_adjust_batch(problems, max_iterations=50, loss=None, loss_scale=None):
     """Many bundle adjustments in ONE kernel launch, one workgroup each (``e2emv_mv_bundle_adjust_batch``).  ``problems``: list
     of the argument tuples of ``bundle_adjust`` ``(n_cams, fixed_cam, intr, cam_idx, pt_idx, obs_xy, obs_w, cams, pts)``; they
     may differ in every size, have no point, or cameras without observations.  Returns one ``(cams, pts, summary)`` per problem,
-    bit for bit what ``bundle_adjust`` returns for it alone."""
+    bit for bit what ``bundle_adjust`` returns for it alone.  ``loss``, ``loss_scale``: as in ``bundle_adjust``, one loss and one
+    absolute scale for the batch (``e2emv_mv_bundle_adjust_batch_loss``)."""
+    code = _check_loss(loss, loss_scale)
     if not problems:
         return []
     dev = _dev()
@@ -441,8 +468,12 @@ def bundle_adjust_batch(problems, max_iterations=50):
     pt_off = np.concatenate([[0], np.cumsum(size(8, 3))]).astype(np.int64)
     obs_off = np.concatenate([[0], np.cumsum(size(3, 1))]).astype(np.int64)
     summary = np.zeros((n, 4))
-    ctx.call("e2emv_mv_bundle_adjust_batch", n, _p(n_cams), _p(fixed), _p(intr), _p(pt_off), _p(obs_off), _p(cam_idx), _p(pt_idx), _p(obs_xy),
-             _p(obs_w), _p(cams), _p(pts), int(max_iterations), _p(summary), _lib.stream_ptr(dev))
+    head = (n, _p(n_cams), _p(fixed), _p(intr), _p(pt_off), _p(obs_off), _p(cam_idx), _p(pt_idx), _p(obs_xy), _p(obs_w), _p(cams), _p(pts),
+            int(max_iterations), _p(summary))
+    if code:
+        ctx.call("e2emv_mv_bundle_adjust_batch_loss", *head, code, float(loss_scale), _lib.stream_ptr(dev))
+    else:
+        ctx.call("e2emv_mv_bundle_adjust_batch", *head, _lib.stream_ptr(dev))
     cam_off = np.concatenate([[0], np.cumsum(n_cams)])
     return [(cams[cam_off[k]:cam_off[k + 1]].copy(), pts[pt_off[k]:pt_off[k + 1]].copy(), _ba_summary(summary[k])) for k in range(n)]
 
@@ -703,7 +734,7 @@ def _check_rel_pose_method(rel_pose_method):
 
 
 def solve_tuple_poses_batch(tuple_size, data, result, conf_thresh=0., timings=None, init="host", rel_pose_method="w8pt_ba", seed=0, tracks=False,
-                            repair_rounds=0):
+                            repair_rounds=0, loss=None, loss_scale=None):
     """``solve_tuple_poses`` for EVERY batch element of the matcher result, in memory: returns the refined world-to-camera
     extrinsics ``float64 [B, tuple_size, 4, 4]``, camera 0 the gauge.  Stages: matches collected on the device (one launch) ->
     relative poses of all B * T(T-1)/2 pairs (``rel_pose_method``) -> one copy to the host, spanning tree and rotation /
@@ -728,14 +759,24 @@ def solve_tuple_poses_batch(tuple_size, data, result, conf_thresh=0., timings=No
     ``keypoints{t}`` in ``data`` (with per-pair keypoints only, a keypoint has no identity across pairs): ``ValueError``
     otherwise, before any device call.
     ``repair_rounds`` (int, 0 .. 64; must be 0 unless ``tracks=True``; ``ValueError`` otherwise, before any device call): 0
-    (default) drops the conflicting components as described; ``R > 0`` repairs them first as in ``match_tracks``."""
+    (default) drops the conflicting components as described; ``R > 0`` repairs them first as in ``match_tracks``.
+    ``loss``, ``loss_scale``: a robust loss in the last stage only (``None``, the default: the squared loss, the calls above;
+    "huber" / "cauchy": ``e2emv_mv_tuple_ba_loss`` / ``e2emv_mv_tuple_ba_tracks_loss``), with either ``init``, every
+    ``rel_pose_method`` and ``tracks`` / ``repair_rounds``.  ``loss_scale`` is RELATIVE here: the weights of a tuple are its
+    confidences over a per-tuple constant, the scale is divided by the same constant on the device, and the loss acts on
+    ``confidence x residual`` in normalised image coordinates - ``loss_scale`` = pixels / focal length at confidence 1 (one
+    pixel at f = 600: ``1 / 600``), whatever the tuple's number of matches.  ``ValueError`` as in ``bundle_adjust``, before any
+    device call."""
     import time
     _check_init(init)
+    loss_code = _check_loss(loss, loss_scale)
     _check_rel_pose_method(rel_pose_method)
     _check_repair_rounds(repair_rounds, tracks)
     if tracks:
         _check_tracks(tuple_size, data, rel_pose_method)
     ransac = rel_pose_method != "w8pt_ba"
+    # the last stage: without a loss the entry points and arguments it always had
+    ba_suffix, loss_tail = ("_loss", (loss_code, float(loss_scale), None)) if loss_code else ("", ())
     pairs = _pairs(tuple_size)
     P = len(pairs)
     clock = [time.perf_counter()]
@@ -771,10 +812,10 @@ def solve_tuple_poses_batch(tuple_size, data, result, conf_thresh=0., timings=No
         lap("initialisation")
         out, summary = np.zeros((B, tuple_size, 4, 4)), np.zeros((B, 4))
         if tracks:
-            _tracks_ba_call("e2emv_mv_tuple_ba_tracks", tuple_size, data, result, conf_thresh, intr, kdim, nb, start, 50, _p(out), _p(summary),
-                            repair_rounds=repair_rounds)
+            _tracks_ba_call("e2emv_mv_tuple_ba_tracks" + ba_suffix, tuple_size, data, result, conf_thresh, intr, kdim, nb, start, 50, _p(out),
+                            _p(summary), *loss_tail, repair_rounds=repair_rounds)
         else:
-            _tuple_ba_call("e2emv_mv_tuple_ba", tuple_size, collected, counts, intr, kdim, nb, start, 50, _p(out), _p(summary))
+            _tuple_ba_call("e2emv_mv_tuple_ba" + ba_suffix, tuple_size, collected, counts, intr, kdim, nb, start, 50, _p(out), _p(summary), *loss_tail)
         lap("build_and_bundle_adjust")
         return out
     # one device -> host copy for the whole batch: poses, inlier counts, match counts
@@ -797,10 +838,10 @@ def solve_tuple_poses_batch(tuple_size, data, result, conf_thresh=0., timings=No
     lap("initialisation")
     out, summary = np.zeros((B, tuple_size, 4, 4)), np.zeros((B, 4))
     if tracks:
-        _tracks_ba_call("e2emv_mv_tuple_ba_tracks", tuple_size, data, result, conf_thresh, intr, kdim, nb, start, 50, _p(out), _p(summary),
-                        repair_rounds=repair_rounds)
+        _tracks_ba_call("e2emv_mv_tuple_ba_tracks" + ba_suffix, tuple_size, data, result, conf_thresh, intr, kdim, nb, start, 50, _p(out),
+                        _p(summary), *loss_tail, repair_rounds=repair_rounds)
     else:
-        _tuple_ba_call("e2emv_mv_tuple_ba", tuple_size, collected, counts, intr, kdim, nb, start, 50, _p(out), _p(summary))
+        _tuple_ba_call("e2emv_mv_tuple_ba" + ba_suffix, tuple_size, collected, counts, intr, kdim, nb, start, 50, _p(out), _p(summary), *loss_tail)
     lap("build_and_bundle_adjust")
     return out
 
@@ -875,13 +916,13 @@ def eval_bundle_adjust(tuple_size, data, result, tmp_dir, pose_errors, verbose=F
 
 
 def eval_bundle_adjust_batch(tuple_size, data, result, pose_errors, verbose=False, init="host", rel_pose_method="w8pt_ba", tracks=False,
-                             repair_rounds=0):
+                             repair_rounds=0, loss=None, loss_scale=None):
     """``eval_bundle_adjust`` for every batch element through ``solve_tuple_poses_batch``: extends ``pose_errors = [max errors,
     translation errors, rotation errors]`` by ``B * T(T-1)/2`` entries, batch element outer, pairs in ``_pairs`` order inside
     (for ``B = 1`` the entries ``eval_bundle_adjust`` appends, in its order).  ``init``, ``rel_pose_method``, ``tracks``,
-    ``repair_rounds``: as in ``solve_tuple_poses_batch``."""
+    ``repair_rounds``, ``loss``, ``loss_scale``: as in ``solve_tuple_poses_batch``."""
     extrinsics = solve_tuple_poses_batch(tuple_size, data, result, init=init, rel_pose_method=rel_pose_method, tracks=tracks,
-                                         repair_rounds=repair_rounds)
+                                         repair_rounds=repair_rounds, loss=loss, loss_scale=loss_scale)
     poses = np.stack([data["pose" + str(v)].cpu().numpy() for v in range(tuple_size)], 1)  # [B,T,4,4]: one copy per image
     for b, E in enumerate(extrinsics):
         err_t, err_R = tuple_pose_errors(E, poses[b])

@@ -356,6 +356,37 @@ int e2emv_mv_tuple_problem_tracks(e2emv_ctx* ctx, int B, int T, int N, int Nmax,
                                   int kdim, int intr_batch, const double* extr, int32_t* cam_idx, int32_t* pt_idx,
                                   double* obs_xy, double* obs_w, double* cams, double* pts, void* stream);
 
+/* Robust loss in the multi-view bundle adjustment: a ceres::LossFunction where the reference passes NULL
+ * (ba_problem.cpp:135,144).  One residual block = one observation; s = rx^2 + ry^2 of the WEIGHTED residual; the cost is
+ * 1/2 sum rho(s) (also summary[0] and [1]); the linearisation is Ceres' corrector with rho'' <= 0: residual and both Jacobian
+ * blocks of the observation times sqrt(rho'(s)); the trust-region loop, its tolerances and termination codes are unchanged.
+ *   E2EMV_LOSS_HUBER  a: rho = s, rho' = 1 for s <= a^2, else rho = 2 a sqrt(s) - a^2, rho' = a / sqrt(s)
+ *   E2EMV_LOSS_CAUCHY a: rho = a^2 log1p(s / a^2), rho' = 1 / (1 + s / a^2)
+ * E2EMV_EINVAL for another code, or with a loss for a scale that is not finite and > 0.  E2EMV_LOSS_NONE ignores the scale
+ * and is the entry point without the suffix, launch for launch and bit for bit.                                          */
+#define E2EMV_LOSS_NONE 0
+#define E2EMV_LOSS_HUBER 1
+#define E2EMV_LOSS_CAUCHY 2
+/* e2emv_mv_bundle_adjust_batch with a loss; loss_scale = a in the units of the weighted residual, as in Ceres.          */
+int e2emv_mv_bundle_adjust_batch_loss(e2emv_ctx* ctx, int n_problems, const int32_t* n_cams, const int32_t* fixed_cam,
+                                      const double* intr, const int64_t* pt_off, const int64_t* obs_off, const int32_t* cam_idx,
+                                      const int32_t* pt_idx, const double* obs_xy, const double* obs_w, double* cams, double* pts,
+                                      int max_iterations, double* summary, int loss, double loss_scale, void* stream);
+/* e2emv_mv_tuple_ba / e2emv_mv_tuple_ba_tracks with a loss.  Their weights are confidence / half_total with a per-tuple
+ * half_total (0.5 (2 sum + 1e-3) over the matches, 0.5 (sum + 1e-3) over the track observations), so loss_scale is RELATIVE:
+ * tuple b runs with a_b = loss_scale / half_total_b - one fp64 division on the device by the denominator of its weights -
+ * and the loss acts on confidence x residual in normalised image coordinates: loss_scale = "pixels / focal length at
+ * confidence 1" whatever the tuple's size.  loss_a_out HOST [B] (may be NULL): the a_b used (0 without a loss).              */
+int e2emv_mv_tuple_ba_loss(e2emv_ctx* ctx, int B, int T, int N, const int32_t* counts, const float* d_mkpts0, const float* d_mkpts1,
+                           const float* d_mconf, const float* const* d_intr, int kdim, int intr_batch, const double* extr,
+                           int max_iterations, double* out_extr, double* summary, int loss, double loss_scale, double* loss_a_out,
+                           void* stream);
+int e2emv_mv_tuple_ba_tracks_loss(e2emv_ctx* ctx, int B, int T, int N, int Nmax, const int32_t* d_label, const int32_t* stats,
+                                  const float* const* d_kpts, const int32_t* n_kpts, const int64_t* const* d_matches,
+                                  const float* const* d_conf, int conf_channels, float conf_thresh, const float* const* d_intr,
+                                  int kdim, int intr_batch, const double* extr, int max_iterations, double* out_extr,
+                                  double* summary, int loss, double loss_scale, double* loss_a_out, void* stream);
+
 /* The global initialisation on the DEVICE (csrc/mvinit_device.hip): the solver of e2emv_mv_init with the same options,
  * fp64, one wave per problem, the problem and its working set in LDS; a problem's result depends on neither its
  * neighbours nor its position in the batch (bit for bit), and agrees with the host form to rounding (summation orders

@@ -16,9 +16,13 @@ and of labels + problem build + copy-out on their own (each synchronised), the s
 ``e2emv_mv_tracks``).  ``--wrong F`` (with ``--tracks``): the identity-like matcher's matches are clean, so a repair has nothing to
 do on them; F > 0 replaces every matched keypoint with probability F by a uniform random target of confidence U(0, 0.5) (the
 ``planted_scene`` recipe of tests/test_gpu_mv_tracks.py, ``default_rng(1000)``) before anything is timed, in both paths.
+``--loss huber|cauchy --loss-scale S``: the batched path's last stage runs with that robust loss at the relative scale S
+(``solve_tuple_poses_batch(..., loss=, loss_scale=)``; the CSV path has no loss, so the difference between the two paths'
+extrinsics is then the effect of the loss).  The last stage's median / min / max is in ``build_and_bundle_adjust_ms`` per form.
 
     python tools/bench_mv_backend.py [--batch 8] [--tuple-size 5] [--kpts 1024] [--reps 7] [--init host|device|both]
                                      [--rel-pose-method w8pt_ba|ransac|ransac_ba] [--tracks [--repair-rounds 0] [--wrong 0.0]]
+                                     [--loss huber|cauchy --loss-scale 0.00166667]
 """
 import argparse
 import json
@@ -46,7 +50,12 @@ def main():
     ap.add_argument("--tracks", action="store_true")
     ap.add_argument("--repair-rounds", type=int, default=0)
     ap.add_argument("--wrong", type=float, default=0.0)
+    ap.add_argument("--loss", choices=("huber", "cauchy"), default=None)
+    ap.add_argument("--loss-scale", type=float, default=None)
     args = ap.parse_args()
+    if (args.loss is None) != (args.loss_scale is None):
+        ap.error("--loss and --loss-scale go together")
+    loss_kw = dict(loss=args.loss, loss_scale=args.loss_scale) if args.loss else {}  # without a loss: the call as it always was
     if (args.repair_rounds or args.wrong) and not args.tracks:
         ap.error("--repair-rounds / --wrong need --tracks")
     B, T, method = args.batch, args.tuple_size, args.rel_pose_method
@@ -78,7 +87,7 @@ def main():
 
         def batched(init, timings=None):
             return multi_view.solve_tuple_poses_batch(T, dev, result, timings=timings, init=init, rel_pose_method=method, tracks=args.tracks,
-                                                      repair_rounds=args.repair_rounds)
+                                                      repair_rounds=args.repair_rounds, **loss_kw)
 
         def timed(fn):
             torch.cuda.synchronize()
@@ -112,7 +121,9 @@ def main():
     first = forms[0]  # the form the unsuffixed keys describe: the host form unless --init device
     line = {"batch": B, "tuple_size": T, "n_kpts": args.kpts, "reps": args.reps, "init": args.init, "rel_pose_method": method, "csv_path_ms": stat(t_csv),
             "tracks": args.tracks, "repair_rounds": args.repair_rounds, "wrong": args.wrong, "batched_path_ms": stat(t_batch[first]), "batched_stage_ms": {k: float(np.median(v)) for k, v in stages[first].items()},
-            "max_abs_extrinsics_difference": float(np.abs(e_csv - e_batch[first]).max())}
+            "max_abs_extrinsics_difference": float(np.abs(e_csv - e_batch[first]).max()),
+            "loss": args.loss, "loss_scale": args.loss_scale,
+            "build_and_bundle_adjust_ms": {f: stat(stages[f]["build_and_bundle_adjust"]) for f in forms}}
     if args.init == "both":
         line["batched_path_device_init_ms"] = stat(t_batch["device"])
         line["batched_stage_device_init_ms"] = {k: float(np.median(v)) for k, v in stages["device"].items()}
