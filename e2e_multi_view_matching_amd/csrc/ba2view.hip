@@ -15,7 +15,14 @@
 // (D^-1 J^T J + lambda I) d = D^-1 b.  All accumulation in fp64, reductions by wavefront shuffles,
 // the 6x6 solve by one lane.  Same LM control flow as the reference: update ALWAYS applied, best-residual
 // pose kept, lambda /= 3.5 on improvement else *= 1.5, n_iterations + 1 residual evaluations.
+//
+// Robust loss (e2emv_ba_2view_loss; a ceres::LossFunction in a solver that has none upstream): a residual block is one
+// observation, so a match has two - s0 = |r0|^2 in image 0, s1 = |r1|^2 in image 1, on the weighted residuals.  The cost the LM
+// bookkeeping compares is sum rho(s0) + sum rho(s1); the linearisation is Ceres' corrector for rho'' <= 0, applied once per block
+// in point_terms: r0, Jp0 times sqrt(rho'(s0)) and r1, Jp1, Jc times sqrt(rho'(s1)), so that the three passes, the positivity
+// check and the preconditioner's floor all see the system that is solved.  rho and sqrt(rho') are mv_loss of mvba.h.
 #include "common.h"
+#include "mvba.h"
 #include "small_linalg.h"
 
 namespace e2emv {
@@ -63,6 +70,8 @@ struct BaParams {
     uint8_t* valid;     // [B]
     double* X;          // workspace [B][N][3]
     float lm_inc, lm_dec;
+    double loss_scale;  // relative: pair b runs with a_b = loss_scale / cden_b, the denominator of its weights
+    double* summary;    // [B][4] or NULL: cost at the start, best cost, evaluations that improved, a_b
 };
 
 // per-point quantities for the current pose: residuals and Jacobian blocks (already confidence weighted)
@@ -70,8 +79,11 @@ struct PointTerms {
     double r0[2], r1[2];
     double Jp0[2][3], Jp1[2][3], Jc[2][6];
 };
-__device__ __forceinline__ void point_terms(const double* Rt, const double* X, double x0, double y0, double x1, double y1,
-                                            double c, PointTerms& q) {
+// Returns the match's share of the cost: |r0|^2 + |r1|^2 without a loss (today's expression), rho(s0) + rho(s1) with one - taken
+// BEFORE the corrector scales the blocks.
+template <int LOSS>
+__device__ __forceinline__ double point_terms(const double* Rt, const double* X, double x0, double y0, double x1, double y1,
+                                              double c, double la, double la2, PointTerms& q) {
     // camera 0: identity
     const double iz0 = 1.0 / X[2];
     q.r0[0] = c * (X[0] * iz0 - x0);
@@ -100,13 +112,31 @@ __device__ __forceinline__ void point_terms(const double* Rt, const double* X, d
     q.Jc[1][3] = -(j11 * a2 + j12 * (-a1));
     q.Jc[1][4] = -(j12 * a0);
     q.Jc[1][5] = -(j11 * (-a0));
+    if (LOSS == kLossNone) return q.r0[0] * q.r0[0] + q.r0[1] * q.r0[1] + q.r1[0] * q.r1[0] + q.r1[1] * q.r1[1];
+    double rho0, sq0, rho1, sq1;
+    mv_loss<LOSS>(q.r0[0] * q.r0[0] + q.r0[1] * q.r0[1], la, la2, &rho0, &sq0);
+    mv_loss<LOSS>(q.r1[0] * q.r1[0] + q.r1[1] * q.r1[1], la, la2, &rho1, &sq1);
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        q.r0[r] *= sq0;
+        q.r1[r] *= sq1;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { q.Jp0[r][k] *= sq0; q.Jp1[r][k] *= sq1; }
+#pragma unroll
+        for (int k = 0; k < 6; ++k) q.Jc[r][k] *= sq1;
+    }
+    return rho0 + rho1;
 }
 
+template <int LOSS>
 __global__ __launch_bounds__(256) void ba2view_kernel(BaParams p) {
     __shared__ double red[4 * 32];
     __shared__ double sRt[12], sBest[12], sDelta[6];
     __shared__ double sLam, sBestR;
+    __shared__ double sM6[6][7];
     __shared__ int sFlags;  // bit0: skip update this iteration
+    __shared__ int sImproved;
+    __shared__ double sStartR;
     const int b = blockIdx.x, tid = threadIdx.x;
     const int N = p.N;
     const float* k0 = p.k0 + (int64_t)b * N * 2;
@@ -123,15 +153,19 @@ __global__ __launch_bounds__(256) void ba2view_kernel(BaParams p) {
     const bool valid = st[1] > 6.5;
     if (tid < 16) p.Tout[(int64_t)b * 16 + tid] = Ti[tid];
     if (tid == 0) p.valid[b] = valid ? 1 : 0;
-    if (!valid) return;
+    if (!valid) {
+        if (p.summary && tid < 4) p.summary[(int64_t)b * 4 + tid] = 0.0;
+        return;
+    }
     const double cden = 0.5 * fmax(2.0 * st[0], 1e-6);
+    const double la = LOSS != kLossNone ? p.loss_scale / cden : 0.0, la2 = la * la;
 
     if (tid < 12) {
         const int r = tid < 9 ? tid / 3 : tid - 9, c = tid < 9 ? tid % 3 : 3;
         sRt[tid] = (double)Ti[r * 4 + c];   // R row-major (0..8), t (9..11)
         sBest[tid] = sRt[tid];
     }
-    if (tid == 0) { sLam = 0.1; sBestR = 0.0; sFlags = 0; }
+    if (tid == 0) { sLam = 0.1; sBestR = 0.0; sFlags = 0; sImproved = 0; sStartR = 0.0; }
     __syncthreads();
     for (int i = tid; i < N; i += 256)
         if (cf[i] > 0.f) triangulate_xyz(k0[2 * i], k0[2 * i + 1], k1[2 * i], k1[2 * i + 1], sRt, X + 3 * i);
@@ -148,8 +182,7 @@ __global__ __launch_bounds__(256) void ba2view_kernel(BaParams p) {
         for (int i = tid; i < N; i += 256) {
             if (!(cf[i] > 0.f)) continue;
             PointTerms q;
-            point_terms(Rt, X + 3 * i, k0[2 * i], k0[2 * i + 1], k1[2 * i], k1[2 * i + 1], (double)cf[i] / cden, q);
-            a[27] += q.r0[0] * q.r0[0] + q.r0[1] * q.r0[1] + q.r1[0] * q.r1[0] + q.r1[1] * q.r1[1];
+            a[27] += point_terms<LOSS>(Rt, X + 3 * i, k0[2 * i], k0[2 * i + 1], k1[2 * i], k1[2 * i + 1], (double)cf[i] / cden, la, la2, q);
             int idx = 0;
 #pragma unroll
             for (int u = 0; u < 6; ++u) {
@@ -170,8 +203,10 @@ __global__ __launch_bounds__(256) void ba2view_kernel(BaParams p) {
         if (tid == 0) {
             if (it == 0) {
                 sBestR = rn;
+                sStartR = rn;
             } else if (rn < sBestR) {
                 sBestR = rn;
+                ++sImproved;
 #pragma unroll
                 for (int k = 0; k < 12; ++k) sBest[k] = Rt[k];
                 sLam = sLam / (double)p.lm_dec;
@@ -195,7 +230,7 @@ __global__ __launch_bounds__(256) void ba2view_kernel(BaParams p) {
         for (int i = tid; i < N; i += 256) {
             if (!(cf[i] > 0.f)) continue;
             PointTerms q;
-            point_terms(Rt, X + 3 * i, k0[2 * i], k0[2 * i + 1], k1[2 * i], k1[2 * i + 1], (double)cf[i] / cden, q);
+            point_terms<LOSS>(Rt, X + 3 * i, k0[2 * i], k0[2 * i + 1], k1[2 * i], k1[2 * i + 1], (double)cf[i] / cden, la, la2, q);
             double Hpp[6], gp[3], Hcp[6][3], inv[6];
             int idx = 0;
 #pragma unroll
@@ -231,8 +266,9 @@ __global__ __launch_bounds__(256) void ba2view_kernel(BaParams p) {
         }
         block_sum_n<27>(s, red);
         if (tid == 0) {
-            // reduced 6x6 system, Gaussian elimination with partial pivoting (fp64)
-            double M6[6][7];
+            // reduced 6x6 system, Gaussian elimination with partial pivoting (fp64); in LDS: the pivot search indexes its rows
+            // at run time, which in a private array means scratch memory
+            double (&M6)[6][7] = sM6;
             int idx = 0;
             for (int u = 0; u < 6; ++u)
                 for (int v = u; v < 6; ++v) {
@@ -277,7 +313,7 @@ __global__ __launch_bounds__(256) void ba2view_kernel(BaParams p) {
         for (int i = tid; i < N; i += 256) {
             if (!(cf[i] > 0.f)) continue;
             PointTerms q;
-            point_terms(Rt, X + 3 * i, k0[2 * i], k0[2 * i + 1], k1[2 * i], k1[2 * i + 1], (double)cf[i] / cden, q);
+            point_terms<LOSS>(Rt, X + 3 * i, k0[2 * i], k0[2 * i + 1], k1[2 * i], k1[2 * i + 1], (double)cf[i] / cden, la, la2, q);
             double Hpp[6], rhs[3], inv[6];
             int idx = 0;
 #pragma unroll
@@ -328,28 +364,52 @@ __global__ __launch_bounds__(256) void ba2view_kernel(BaParams p) {
         const int r = tid < 9 ? tid / 3 : tid - 9, c = tid < 9 ? tid % 3 : 3;
         p.Tout[(int64_t)b * 16 + r * 4 + c] = (float)sBest[tid];
     }
+    if (p.summary && tid == 0) {
+        double* sm = p.summary + (int64_t)b * 4;
+        sm[0] = sStartR; sm[1] = sBestR; sm[2] = (double)sImproved; sm[3] = la;
+    }
 }
 
 }  // namespace e2emv
 
 using namespace e2emv;
 
-extern "C" int e2emv_ba_2view(e2emv_ctx* ctx, int B, int N, const float* d_kpts0n, const float* d_kpts1n, const float* d_conf,
-                              const float* d_T_init, int n_iterations, float* d_T_out, uint8_t* d_valid, void* stream) {
+// both entry points; `who` names the caller in error texts
+static int ba2view_run(e2emv_ctx* ctx, const char* who, int B, int N, const float* d_kpts0n, const float* d_kpts1n, const float* d_conf,
+                       const float* d_T_init, int n_iterations, float* d_T_out, uint8_t* d_valid, int loss, double loss_scale,
+                       double* d_summary, void* stream) {
     if (!ctx || !d_kpts0n || !d_kpts1n || !d_conf || !d_T_init || !d_T_out || !d_valid) return E2EMV_EINVAL;
     E2EMV_ENTER(ctx, stream);
-    if (B <= 0 || N <= 0 || n_iterations < 0) return set_err(ctx, E2EMV_ESHAPE, "ba_2view: B=%d N=%d iterations=%d", B, N, n_iterations);
+    int rc = mv_check_loss(ctx, who, loss, &loss_scale);
+    if (rc) return rc;
+    if (B <= 0 || N <= 0 || n_iterations < 0) return set_err(ctx, E2EMV_ESHAPE, "%s: B=%d N=%d iterations=%d", who, B, N, n_iterations);
     hipStream_t s = (hipStream_t)stream;
-    int rc = ws_reserve(ctx, (size_t)B * N * 3 * sizeof(double) + 256);
+    rc = ws_reserve(ctx, (size_t)B * N * 3 * sizeof(double) + 256);
     if (rc) return rc;
     BaParams p{};
     p.B = B; p.N = N; p.n_it = n_iterations;
     p.k0 = d_kpts0n; p.k1 = d_kpts1n; p.conf = d_conf; p.Tin = d_T_init; p.Tout = d_T_out; p.valid = d_valid;
     p.X = (double*)ctx->d_ws;
     p.lm_inc = 1.5f; p.lm_dec = 3.5f;
+    p.loss_scale = loss_scale; p.summary = d_summary;
     prof_begin(ctx, PS_W8PT, s);
-    hipLaunchKernelGGL(ba2view_kernel, dim3(B), dim3(256), 0, s, p);
+    if (loss == kLossHuber) hipLaunchKernelGGL(ba2view_kernel<kLossHuber>, dim3(B), dim3(256), 0, s, p);
+    else if (loss == kLossCauchy) hipLaunchKernelGGL(ba2view_kernel<kLossCauchy>, dim3(B), dim3(256), 0, s, p);
+    else hipLaunchKernelGGL(ba2view_kernel<kLossNone>, dim3(B), dim3(256), 0, s, p);
     prof_end(ctx, s);
     E2EMV_CHECK_LAUNCH(ctx, "ba2view_kernel");
     return E2EMV_OK;
+}
+
+extern "C" int e2emv_ba_2view(e2emv_ctx* ctx, int B, int N, const float* d_kpts0n, const float* d_kpts1n, const float* d_conf,
+                              const float* d_T_init, int n_iterations, float* d_T_out, uint8_t* d_valid, void* stream) {
+    return ba2view_run(ctx, "ba_2view", B, N, d_kpts0n, d_kpts1n, d_conf, d_T_init, n_iterations, d_T_out, d_valid, E2EMV_LOSS_NONE, 0.0,
+                       nullptr, stream);
+}
+
+extern "C" int e2emv_ba_2view_loss(e2emv_ctx* ctx, int B, int N, const float* d_kpts0n, const float* d_kpts1n, const float* d_conf,
+                                   const float* d_T_init, int n_iterations, float* d_T_out, uint8_t* d_valid, int loss, double loss_scale,
+                                   double* d_summary, void* stream) {
+    return ba2view_run(ctx, "ba_2view_loss", B, N, d_kpts0n, d_kpts1n, d_conf, d_T_init, n_iterations, d_T_out, d_valid, loss, loss_scale,
+                       d_summary, stream);
 }

@@ -74,9 +74,10 @@ __device__ __forceinline__ void triangulate_xyz(double x1, double y1, double x2,
         }
     jacobi_static<4>(G, V);
     int m = 0;
+    double gm = G[0][0];  // G[m][m] as a scalar: indexing G by m would put it in scratch memory
 #pragma unroll
     for (int i = 1; i < 4; ++i)
-        if (G[i][i] < G[m][m]) m = i;
+        if (G[i][i] < gm) { gm = G[i][i]; m = i; }
     double X[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) X[i] = (m == 0) ? V[i][0] : (m == 1) ? V[i][1] : (m == 2) ? V[i][2] : V[i][3];

@@ -26,7 +26,7 @@ import torch
 from scipy.sparse.csgraph import minimum_spanning_tree
 
 from . import _lib
-from .pose import mask_confidence, run_bundle_adjust_2_view
+from .pose import LOSSES, _check_loss, mask_confidence, run_bundle_adjust_2_view  # noqa: F401  (LOSSES: part of this module's names)
 from .ransac import MAX_MATCHES, estimate_poses_ransac, normalize_keypoints
 
 
@@ -40,11 +40,13 @@ def _p(a):
     return a.ctypes.data_as(ctypes.c_void_p)
 
 
-def _w8pt_ba_on_device(dev, d_n, d_k0, d_k1, d_cf, d_K0, d_K1, n_iterations=10):
+def _w8pt_ba_on_device(dev, d_n, d_k0, d_k1, d_cf, d_K0, d_K1, n_iterations=10, loss=None, loss_scale=None):
     """The launch sequence behind every "w8pt_ba" relative pose, on device buffers: ``e2emv_w8pt_ragged`` (``d_n`` [Pn] int32
     rows in use of ``d_k0`` / ``d_k1`` [Pn,N,2], ``d_cf`` [Pn,N]; intrinsics [Pn,k,k]) -> confidences of negative-depth matches
     zeroed -> two-view bundle adjustment.  A problem with fewer than 8 rows comes back as the identity with no inlier.
+    ``loss``, ``loss_scale``: the robust loss of the two-view bundle adjustment, as in ``run_bundle_adjust_2_view``.
     Returns ``(T [Pn,4,4] float32, inliers [Pn,N] uint8)`` on the device."""
+    loss_kw = dict(loss=loss, loss_scale=loss_scale) if _check_loss(loss, loss_scale) else {}  # without a loss: the call as it always was
     ctx = _lib.context(dev)
     Pn, N = d_k0.shape[:2]
     kdim = d_K0.shape[-1]
@@ -57,18 +59,20 @@ def _w8pt_ba_on_device(dev, d_n, d_k0, d_k1, d_cf, d_K0, d_K1, n_iterations=10):
     with torch.cuda.device(dev):
         ctx.call("e2emv_w8pt_ragged", Pn, N, P(d_n), P(d_k0), P(d_k1), P(d_K0), P(d_K1), kdim, Pn, P(d_cf), 0, P(None), 1, P(T),
                  P(k0n), P(k1n), P(cfn), P(inl), P(pos), P(None), P(status), _lib.stream_ptr(dev))
-    refined, ok = run_bundle_adjust_2_view(k0n, k1n, mask_confidence(cfn, pos), T, n_iterations=n_iterations)
+    refined, ok = run_bundle_adjust_2_view(k0n, k1n, mask_confidence(cfn, pos), T, n_iterations=n_iterations, **loss_kw)
     T[ok] = refined
     return T, inl
 
 
-def relative_poses_w8pt_ba(problems, n_iterations=10):
+def relative_poses_w8pt_ba(problems, n_iterations=10, loss=None, loss_scale=None):
     """Relative pose of MANY image pairs with different numbers of matches in one device pass: ragged weighted 8-point
     (``e2emv_w8pt_ragged``: every pair keeps its own Hartley statistics) -> confidences of negative-depth matches zeroed
     -> two-view bundle adjustment (zero-weight padding rows do not enter it).  ``problems`` = list of
     ``(intr0, intr1, mkpts0 [n,2], mkpts1 [n,2], conf [n,c])`` numpy tuples; returns one ``(success, R, t, inliers)`` per
     problem with the meaning of the reference's ``estimate_relative_pose_w8pt_ba`` (bundle_adjust_io.py:12-23):
-    ``success`` is False below 8 matches."""
+    ``success`` is False below 8 matches.  ``loss``, ``loss_scale``: the robust loss of the two-view bundle adjustment, as in
+    ``run_bundle_adjust_2_view`` (``ValueError`` before any device call)."""
+    _check_loss(loss, loss_scale)
     out = [(False, None, None, None)] * len(problems)
     live = [q for q, pr in enumerate(problems) if pr[2].shape[0] >= 8]
     if not live:
@@ -86,7 +90,7 @@ def relative_poses_w8pt_ba(problems, n_iterations=10):
         cf[r, :n_per[r]] = np.asarray(conf).reshape(n_per[r], -1)[:, 0]
         K0[r], K1[r] = intr0, intr1
     up = lambda a: torch.from_numpy(a).to(dev)  # noqa: E731
-    T, inl = _w8pt_ba_on_device(dev, up(n_per), up(k0), up(k1), up(cf), up(K0), up(K1), n_iterations)
+    T, inl = _w8pt_ba_on_device(dev, up(n_per), up(k0), up(k1), up(cf), up(K0), up(K1), n_iterations, loss, loss_scale)
     T_h, inl_h = T.cpu().numpy(), inl.cpu().numpy().astype(bool)
     for r, q in enumerate(live):
         out[q] = (True, T_h[r, :3, :3], T_h[r, :3, 3], inl_h[r, :n_per[r]])
@@ -99,13 +103,18 @@ def estimate_relative_pose_w8pt_ba(intr0, intr1, mkpts0, mkpts1, conf):
     return relative_poses_w8pt_ba([(intr0, intr1, mkpts0, mkpts1, conf)])[0]
 
 
-def relative_poses_ransac(problems, ba=False, n_iterations=10):
+def relative_poses_ransac(problems, ba=False, n_iterations=10, loss=None, loss_scale=None):
     """Relative pose of MANY image pairs by the RANSAC baseline in one device pass: ``estimate_pose(..., thresh=1.0)``
     (5-point RANSAC + recoverPose, ``ransac.py``) for all pairs, then with ``ba`` the two-view bundle adjustment of every
     solved pair on its RANSAC inliers only, weighted by their confidences and started from the RANSAC pose (one batched
     launch; zero-weight padding rows do not enter it).  ``problems`` = list of ``(intr0, intr1, mkpts0 [n,2], mkpts1 [n,2],
     conf [n,c])``; returns one ``(success, R, t, inliers)`` per problem with the meaning of the reference's
-    ``estimate_relative_pose_ransac`` / ``estimate_relative_pose_ransac_ba`` (bundle_adjust_io.py:25-58)."""
+    ``estimate_relative_pose_ransac`` / ``estimate_relative_pose_ransac_ba`` (bundle_adjust_io.py:25-58).  ``loss``,
+    ``loss_scale``: the robust loss of the two-view bundle adjustment, as in ``run_bundle_adjust_2_view``; they need ``ba=True``
+    (``ValueError`` before any device call: the RANSAC alone has no two-view bundle adjustment)."""
+    loss_kw = dict(loss=loss, loss_scale=loss_scale) if _check_loss(loss, loss_scale) else {}
+    if loss_kw and not ba:
+        raise ValueError("loss={!r} needs ba=True: the RANSAC alone has no two-view bundle adjustment".format(loss))
     poses = estimate_poses_ransac([(m0, m1, K0, K1) for K0, K1, m0, m1, _ in problems], thresh=1.0)
     out = [(False, None, None, None) if r is None else (True, r[0], r[1], r[2]) for r in poses]
     solved = [q for q, r in enumerate(poses) if r is not None]
@@ -126,7 +135,7 @@ def relative_poses_ransac(problems, ba=False, n_iterations=10):
         T0[r, :3, :3], T0[r, :3, 3] = R, t
     up = lambda a: torch.from_numpy(a).to(dev)  # noqa: E731
     T = up(T0)
-    refined, ok = run_bundle_adjust_2_view(up(k0), up(k1), up(cf), T, n_iterations=n_iterations)
+    refined, ok = run_bundle_adjust_2_view(up(k0), up(k1), up(cf), T, n_iterations=n_iterations, **loss_kw)
     T[ok] = refined
     T_h = T.cpu().numpy()
     for r, q in enumerate(solved):
@@ -402,25 +411,6 @@ def run_bundle_adjuster(directory):
              _lib.stream_ptr(dev))
 
 
-LOSSES = {None: 0, "huber": 1, "cauchy": 2}  # E2EMV_LOSS_* of include/e2emv.h
-
-
-def _check_loss(loss, loss_scale):
-    """``loss`` is ``None``, "huber" or "cauchy"; a loss needs a finite positive ``loss_scale`` and no loss takes none: checked on
-    the host before any device call.  Returns the code of the C ABI."""
-    if not (loss is None or isinstance(loss, str)) or loss not in LOSSES:
-        raise ValueError("loss must be None, \"huber\" or \"cauchy\", not {!r}".format(loss))
-    if loss is None:
-        if loss_scale is not None:
-            raise ValueError("loss_scale={!r} needs a loss: without one there is nothing to scale".format(loss_scale))
-        return 0
-    if loss_scale is None:
-        raise ValueError("loss={!r} needs a loss_scale".format(loss))
-    if isinstance(loss_scale, bool) or not isinstance(loss_scale, (int, float, np.integer, np.floating)) or not np.isfinite(loss_scale) or not loss_scale > 0:
-        raise ValueError("loss_scale must be a finite positive number, not {!r}".format(loss_scale))
-    return LOSSES[loss]
-
-
 def bundle_adjust(n_cams, fixed_cam, intr, cam_idx, pt_idx, obs_xy, obs_w, cams, pts, max_iterations=50, loss=None, loss_scale=None):
     """In-memory form of the device solver (``e2emv_mv_bundle_adjust``); returns ``(cams, pts, summary)``.
     ``loss``: ``None`` (default, the reference's squared loss), "huber" or "cauchy" with ``loss_scale`` = the scale ``a`` of the
@@ -581,18 +571,22 @@ def _tuple_init_launch(tuple_size, T_d, n_inl, weight, ba_count, min_matches, mi
     return start, np.ascontiguousarray(packed[:, tuple_size * 16:].astype(np.int32).reshape(-1))
 
 
-def _ransac_on_device(tuple_size, collected, intr, kdim, nb, ba=False, seed=0):
+def _ransac_on_device(tuple_size, collected, intr, kdim, nb, ba=False, seed=0, loss=None, loss_scale=None):
     """The launch sequence behind the "ransac" / "ransac_ba" relative poses of a batch of tuples, on the buffers of
     ``_collect_matches_batch`` and the intrinsics of ``_tuple_intrinsics``, nothing read back: ``e2emv_mv_ransac_prepare`` (fp64
     normalised keypoints, thresholds) -> ``e2emv_essential_ransac`` (threshold 1 pixel, conf 0.99999, 1000 iterations, as
     ``relative_poses_ransac``) -> ``e2emv_mv_ransac_filter`` (matches reduced to the inliers, pose as 4x4) -> with ``ba`` the
     two-view bundle adjustment of every solved pair on its inliers, 10 iterations started from the RANSAC pose
     (``e2emv_ba_2view`` directly: it returns the start of a pair it declares invalid, which is ``T[ok] = refined`` without the
-    host's boolean indexing and its synchronisation).  Per pair what ``relative_poses_ransac`` computes, bit for bit.  Returns a
+    host's boolean indexing and its synchronisation; with ``loss`` / ``loss_scale``, which need ``ba``, ``e2emv_ba_2view_loss`` with
+    that robust loss).  Per pair what ``relative_poses_ransac`` computes, bit for bit.  Returns a
     dict of device tensors: ``filtered`` (mkpts0, mkpts1 [B*P,N,2], conf [B*P,N]; a pair that was not solved keeps all its
     matches), ``T`` [B*P,4,4] float32 (the identity unless solved), ``ba_count`` (rows in use of ``filtered``), ``graph_w``
     (inliers of a solved pair, else 0) and the stages' own outputs ``kpts0n``, ``kpts1n``, ``thresh``, ``inliers``,
     ``n_inliers``, ``R``, ``t``, ``status``, ``T0``."""
+    loss_code = _check_loss(loss, loss_scale)
+    if loss_code and not ba:
+        raise ValueError("loss={!r} needs ba=True: the RANSAC alone has no two-view bundle adjustment".format(loss))
     o0, o1, oc, count = collected
     dev = o0.device
     ctx = _lib.context(dev)
@@ -619,7 +613,10 @@ def _ransac_on_device(tuple_size, collected, intr, kdim, nb, ba=False, seed=0):
         T = T0
         if ba:
             T, valid = new((Pn, 4, 4), f32), new((Pn,), torch.uint8)
-            ctx.call("e2emv_ba_2view", Pn, N, P(f0n), P(f1n), P(fcn), P(T0), 10, P(T), P(valid), s)
+            if loss_code:
+                ctx.call("e2emv_ba_2view_loss", Pn, N, P(f0n), P(f1n), P(fcn), P(T0), 10, P(T), P(valid), loss_code, float(loss_scale), P(None), s)
+            else:
+                ctx.call("e2emv_ba_2view", Pn, N, P(f0n), P(f1n), P(fcn), P(T0), 10, P(T), P(valid), s)
     del owner
     return dict(filtered=(f0, f1, fc), T=T, ba_count=ba_count, graph_w=graph_w, kpts0n=k0n, kpts1n=k1n, thresh=th, inliers=inl,
                 n_inliers=n_inl, R=R, t=t, status=status, T0=T0)
@@ -733,8 +730,15 @@ def _check_rel_pose_method(rel_pose_method):
         raise NotImplementedError("relative pose method {} is not defined".format(rel_pose_method))
 
 
+def _check_pair_loss(pair_loss, pair_loss_scale, rel_pose_method):
+    """The loss of the pairwise two-view stage: the rules of ``_check_loss``, and a method that has that stage."""
+    if _check_loss(pair_loss, pair_loss_scale) and rel_pose_method == "ransac":
+        raise ValueError("pair_loss={!r} needs rel_pose_method \"w8pt_ba\" or \"ransac_ba\": \"ransac\" has no two-view bundle "
+                         "adjustment".format(pair_loss))
+
+
 def solve_tuple_poses_batch(tuple_size, data, result, conf_thresh=0., timings=None, init="host", rel_pose_method="w8pt_ba", seed=0, tracks=False,
-                            repair_rounds=0, loss=None, loss_scale=None):
+                            repair_rounds=0, loss=None, loss_scale=None, pair_loss=None, pair_loss_scale=None):
     """``solve_tuple_poses`` for EVERY batch element of the matcher result, in memory: returns the refined world-to-camera
     extrinsics ``float64 [B, tuple_size, 4, 4]``, camera 0 the gauge.  Stages: matches collected on the device (one launch) ->
     relative poses of all B * T(T-1)/2 pairs (``rel_pose_method``) -> one copy to the host, spanning tree and rotation /
@@ -766,11 +770,17 @@ def solve_tuple_poses_batch(tuple_size, data, result, conf_thresh=0., timings=No
     confidences over a per-tuple constant, the scale is divided by the same constant on the device, and the loss acts on
     ``confidence x residual`` in normalised image coordinates - ``loss_scale`` = pixels / focal length at confidence 1 (one
     pixel at f = 600: ``1 / 600``), whatever the tuple's number of matches.  ``ValueError`` as in ``bundle_adjust``, before any
-    device call."""
+    device call.
+    ``pair_loss``, ``pair_loss_scale``: a robust loss in the PAIRWISE stage, the two-view bundle adjustment of "w8pt_ba" and
+    "ransac_ba" (``e2emv_ba_2view_loss``, see ``run_bundle_adjust_2_view``), independent of ``loss`` / ``loss_scale``; with
+    either ``init`` and with ``tracks`` / ``repair_rounds``.  The scale is relative in the same way, per pair: pixels / focal
+    length at confidence 1.  ``None`` (default): the calls above.  "ransac" has no two-view bundle adjustment: a ``pair_loss``
+    with it is a ``ValueError``, like every bad loss argument before any device call."""
     import time
     _check_init(init)
     loss_code = _check_loss(loss, loss_scale)
     _check_rel_pose_method(rel_pose_method)
+    _check_pair_loss(pair_loss, pair_loss_scale, rel_pose_method)
     _check_repair_rounds(repair_rounds, tracks)
     if tracks:
         _check_tracks(tuple_size, data, rel_pose_method)
@@ -797,11 +807,12 @@ def solve_tuple_poses_batch(tuple_size, data, result, conf_thresh=0., timings=No
     if ransac:
         # what the later stages see of a pair: its inliers (n_inl, also its weight in the match graph: 0 = not solved, no edge)
         # and the rows the bundle adjustment takes from the filtered buffers
-        st = _ransac_on_device(tuple_size, collected, intr, kdim, nb, ba=rel_pose_method == "ransac_ba", seed=seed)
+        st = _ransac_on_device(tuple_size, collected, intr, kdim, nb, ba=rel_pose_method == "ransac_ba", seed=seed, loss=pair_loss,
+                               loss_scale=pair_loss_scale)
         collected, T_d, n_inl_d, ba_count_d, min_matches = st["filtered"] + (None,), st["T"], st["graph_w"], st["ba_count"], 1
     else:
         per_pair = lambda side: torch.stack([intr[pr[side]].expand(B, kdim, kdim) for pr in pairs], 1).reshape(B * P, kdim, kdim).contiguous()  # noqa: E731
-        T_d, inl = _w8pt_ba_on_device(dev, count, o0, o1, oc, per_pair(0), per_pair(1))
+        T_d, inl = _w8pt_ba_on_device(dev, count, o0, o1, oc, per_pair(0), per_pair(1), loss=pair_loss, loss_scale=pair_loss_scale)
         ba_count_d, min_matches = count, 8  # success of estimate_relative_pose_w8pt_ba; the match count is the weight
     if init == "device":
         lap("relative_poses")
@@ -916,13 +927,14 @@ def eval_bundle_adjust(tuple_size, data, result, tmp_dir, pose_errors, verbose=F
 
 
 def eval_bundle_adjust_batch(tuple_size, data, result, pose_errors, verbose=False, init="host", rel_pose_method="w8pt_ba", tracks=False,
-                             repair_rounds=0, loss=None, loss_scale=None):
+                             repair_rounds=0, loss=None, loss_scale=None, pair_loss=None, pair_loss_scale=None):
     """``eval_bundle_adjust`` for every batch element through ``solve_tuple_poses_batch``: extends ``pose_errors = [max errors,
     translation errors, rotation errors]`` by ``B * T(T-1)/2`` entries, batch element outer, pairs in ``_pairs`` order inside
     (for ``B = 1`` the entries ``eval_bundle_adjust`` appends, in its order).  ``init``, ``rel_pose_method``, ``tracks``,
-    ``repair_rounds``, ``loss``, ``loss_scale``: as in ``solve_tuple_poses_batch``."""
+    ``repair_rounds``, ``loss``, ``loss_scale``, ``pair_loss``, ``pair_loss_scale``: as in ``solve_tuple_poses_batch``."""
     extrinsics = solve_tuple_poses_batch(tuple_size, data, result, init=init, rel_pose_method=rel_pose_method, tracks=tracks,
-                                         repair_rounds=repair_rounds, loss=loss, loss_scale=loss_scale)
+                                         repair_rounds=repair_rounds, loss=loss, loss_scale=loss_scale, pair_loss=pair_loss,
+                                         pair_loss_scale=pair_loss_scale)
     poses = np.stack([data["pose" + str(v)].cpu().numpy() for v in range(tuple_size)], 1)  # [B,T,4,4]: one copy per image
     for b, E in enumerate(extrinsics):
         err_t, err_R = tuple_pose_errors(E, poses[b])

@@ -9,6 +9,7 @@ the reference's library SVDs).  The pose is differentiable with respect to the c
 """
 import ctypes
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -342,11 +343,41 @@ def mask_confidence(confidence, mask):
     return out
 
 
+LOSSES = {None: 0, "huber": 1, "cauchy": 2}  # E2EMV_LOSS_* of include/e2emv.h
+
+
+def _check_loss(loss, loss_scale):
+    """``loss`` is ``None``, "huber" or "cauchy"; a loss needs a finite positive ``loss_scale`` and no loss takes none: checked on
+    the host before any device call.  Returns the code of the C ABI."""
+    if not (loss is None or isinstance(loss, str)) or loss not in LOSSES:
+        raise ValueError("loss must be None, \"huber\" or \"cauchy\", not {!r}".format(loss))
+    if loss is None:
+        if loss_scale is not None:
+            raise ValueError("loss_scale={!r} needs a loss: without one there is nothing to scale".format(loss_scale))
+        return 0
+    if loss_scale is None:
+        raise ValueError("loss={!r} needs a loss_scale".format(loss))
+    if isinstance(loss_scale, bool) or not isinstance(loss_scale, (int, float, np.integer, np.floating)) or not np.isfinite(loss_scale) or not loss_scale > 0:
+        raise ValueError("loss_scale must be a finite positive number, not {!r}".format(loss_scale))
+    return LOSSES[loss]
+
+
 def run_bundle_adjust_2_view(kpts0_norm, kpts1_norm, confidence, init_T021, n_iterations, check_lu_info_strict=False,
-                             check_precond_strict=False):
+                             check_precond_strict=False, loss=None, loss_scale=None, return_summary=False):
     """``run_bundle_adjust_2_view`` (estimate_relative_pose.py:138-144): returns ``(refined T_021 of the valid samples
     [n_valid,4,4], valid_batch [B] bool)`` so that ``pred_T021[valid] = refined`` works as at ``eval_pairs.py:252-255``.
-    The two ``*_strict`` flags only matter for singular systems, which the fp64 Schur solve reports the same way."""
+    The two ``*_strict`` flags only matter for singular systems, which the fp64 Schur solve reports the same way.
+    ``loss``: ``None`` (default: the reference's squared loss, ``e2emv_ba_2view`` as always), "huber" or "cauchy"
+    (``e2emv_ba_2view_loss``): a residual block is one observation - a match has one in each image -, the LM loop compares
+    ``sum rho`` and the blocks are linearised with Ceres' corrector.  ``loss_scale`` is RELATIVE, as in
+    ``multi_view.solve_tuple_poses_batch``: the weights of a pair are its confidences over a per-pair constant, the scale is
+    divided by the same constant on the device, and the loss acts on ``confidence x residual`` in normalised image coordinates -
+    ``loss_scale`` = pixels / focal length at confidence 1 (one pixel at f = 600: ``1 / 600``), whatever the number of matches.
+    ``ValueError`` before any device call for another name, a loss without a scale, a scale without a loss, or a scale that is
+    not a finite positive number.  ``return_summary``: a third value, ``float64 [B,4]`` on the device, for EVERY sample: cost at
+    the start, best cost, number of evaluations that improved, the absolute scale used (0 without a loss); zero for an invalid
+    sample."""
+    code = _check_loss(loss, loss_scale)
     dev = _dev_of(kpts0_norm, kpts1_norm, init_T021)
     ctx = _lib.context(dev)
     B, N = kpts0_norm.shape[:2]
@@ -355,8 +386,12 @@ def run_bundle_adjust_2_view(kpts0_norm, kpts1_norm, confidence, init_T021, n_it
     Ti = _prep(init_T021, dev)
     To = torch.empty((B, 4, 4), dtype=torch.float32, device=dev)
     valid = torch.empty((B,), dtype=torch.uint8, device=dev)
+    summary = torch.empty((B, 4), dtype=torch.float64, device=dev) if return_summary else None
+    head = (B, N, _lib.ptr(k0), _lib.ptr(k1), _lib.ptr(cf), _lib.ptr(Ti), int(n_iterations), _lib.ptr(To), _lib.ptr(valid))
     with torch.cuda.device(dev):
-        ctx.call("e2emv_ba_2view", B, N, _lib.ptr(k0), _lib.ptr(k1), _lib.ptr(cf), _lib.ptr(Ti), int(n_iterations),
-                 _lib.ptr(To), _lib.ptr(valid), _lib.stream_ptr(dev))
+        if code or return_summary:
+            ctx.call("e2emv_ba_2view_loss", *head, code, float(loss_scale) if code else 0.0, _lib.ptr(summary), _lib.stream_ptr(dev))
+        else:
+            ctx.call("e2emv_ba_2view", *head, _lib.stream_ptr(dev))
     vb = valid.bool()
-    return To[vb], vb
+    return (To[vb], vb, summary) if return_summary else (To[vb], vb)

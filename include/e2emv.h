@@ -386,6 +386,18 @@ int e2emv_mv_tuple_ba_tracks_loss(e2emv_ctx* ctx, int B, int T, int N, int Nmax,
                                   const float* const* d_conf, int conf_channels, float conf_thresh, const float* const* d_intr,
                                   int kdim, int intr_batch, const double* extr, int max_iterations, double* out_extr,
                                   double* summary, int loss, double loss_scale, double* loss_a_out, void* stream);
+/* e2emv_ba_2view with a loss: the two-view stage robust in the same way.  A residual block is one observation, so a match has
+ * two: s0 = |r0|^2 in image 0 and s1 = |r1|^2 in image 1, on the weighted residuals (weight = conf / cden_b, cden_b = 0.5
+ * max(2 sum conf, 1e-6) over the pair's positive confidences).  The cost that the LM loop compares - improvement, best pose,
+ * lambda - is sum rho(s0) + sum rho(s1); the corrector scales r0 and its point block by sqrt(rho'(s0)), r1 and its point and
+ * camera blocks by sqrt(rho'(s1)); the loop itself (update always applied, n_iterations + 1 evaluations, a singular system
+ * skips the update) is unchanged.  loss_scale is RELATIVE as above: pair b runs with a_b = loss_scale / cden_b, one fp64
+ * division on the device.  d_summary DEVICE [B][4] (may be NULL): cost at the start, best cost, number of evaluations that
+ * improved, a_b used (0 without a loss); all zero for a pair with d_valid[b] == 0.  E2EMV_LOSS_NONE with d_summary == NULL is
+ * e2emv_ba_2view, launch for launch and bit for bit; shape errors as there.                                                 */
+int e2emv_ba_2view_loss(e2emv_ctx* ctx, int B, int N, const float* d_kpts0n, const float* d_kpts1n, const float* d_conf,
+                        const float* d_T_init, int n_iterations, float* d_T_out, uint8_t* d_valid, int loss, double loss_scale,
+                        double* d_summary, void* stream);
 
 /* The global initialisation on the DEVICE (csrc/mvinit_device.hip): the solver of e2emv_mv_init with the same options,
  * fp64, one wave per problem, the problem and its working set in LDS; a problem's result depends on neither its

@@ -13,16 +13,22 @@ difference between the two forms' extrinsics.  ``--rel-pose-method`` selects the
 paths' extrinsics is then the effect of the tracks); the line also carries the track counts and the time of the label launch
 and of labels + problem build + copy-out on their own (each synchronised), the share of the last stage the new kernels take.
 ``--repair-rounds R`` (with ``--tracks``): the labels come from ``e2emv_mv_tracks_repair`` with up to R rounds (0, the default, is
-``e2emv_mv_tracks``).  ``--wrong F`` (with ``--tracks``): the identity-like matcher's matches are clean, so a repair has nothing to
+``e2emv_mv_tracks``).  ``--wrong F``: the identity-like matcher's matches are clean, so a repair has nothing to
 do on them; F > 0 replaces every matched keypoint with probability F by a uniform random target of confidence U(0, 0.5) (the
 ``planted_scene`` recipe of tests/test_gpu_mv_tracks.py, ``default_rng(1000)``) before anything is timed, in both paths.
 ``--loss huber|cauchy --loss-scale S``: the batched path's last stage runs with that robust loss at the relative scale S
 (``solve_tuple_poses_batch(..., loss=, loss_scale=)``; the CSV path has no loss, so the difference between the two paths'
 extrinsics is then the effect of the loss).  The last stage's median / min / max is in ``build_and_bundle_adjust_ms`` per form.
+``--pair-loss huber|cauchy --pair-loss-scale S``: the batched path's PAIRWISE stage, the two-view bundle adjustment of ``w8pt_ba`` /
+``ransac_ba``, runs with that robust loss (``solve_tuple_poses_batch(..., pair_loss=, pair_loss_scale=)``; not with ``ransac``, which
+has no such stage).  ``--wrong`` may be given without ``--tracks`` as well: wrong matches are what the losses are for.  The ``relative_poses`` stage's median / min / max is in
+``relative_poses_ms`` per form, and ``max_pose_error_deg`` per form is the largest rotation / translation angle error of any image
+pair of the batch against the ground truth.
 
     python tools/bench_mv_backend.py [--batch 8] [--tuple-size 5] [--kpts 1024] [--reps 7] [--init host|device|both]
                                      [--rel-pose-method w8pt_ba|ransac|ransac_ba] [--tracks [--repair-rounds 0] [--wrong 0.0]]
                                      [--loss huber|cauchy --loss-scale 0.00166667]
+                                     [--pair-loss huber|cauchy --pair-loss-scale 0.00166667 [--wrong 0.0]]
 """
 import argparse
 import json
@@ -52,12 +58,20 @@ def main():
     ap.add_argument("--wrong", type=float, default=0.0)
     ap.add_argument("--loss", choices=("huber", "cauchy"), default=None)
     ap.add_argument("--loss-scale", type=float, default=None)
+    ap.add_argument("--pair-loss", choices=("huber", "cauchy"), default=None)
+    ap.add_argument("--pair-loss-scale", type=float, default=None)
     args = ap.parse_args()
     if (args.loss is None) != (args.loss_scale is None):
         ap.error("--loss and --loss-scale go together")
+    if (args.pair_loss is None) != (args.pair_loss_scale is None):
+        ap.error("--pair-loss and --pair-loss-scale go together")
+    if args.pair_loss and args.rel_pose_method == "ransac":
+        ap.error("--pair-loss needs --rel-pose-method w8pt_ba or ransac_ba: ransac has no two-view bundle adjustment")
     loss_kw = dict(loss=args.loss, loss_scale=args.loss_scale) if args.loss else {}  # without a loss: the call as it always was
-    if (args.repair_rounds or args.wrong) and not args.tracks:
-        ap.error("--repair-rounds / --wrong need --tracks")
+    if args.pair_loss:
+        loss_kw.update(pair_loss=args.pair_loss, pair_loss_scale=args.pair_loss_scale)
+    if args.repair_rounds and not args.tracks:
+        ap.error("--repair-rounds needs --tracks")
     B, T, method = args.batch, args.tuple_size, args.rel_pose_method
     gpu = torch.device("cuda", 0)
     cfg = {"GNN_layers": ["self", "cross"] * 2, "sinkhorn_iterations": 50, "multi_frame_matching": True, "tuple_size": T}
@@ -117,12 +131,16 @@ def main():
             t_build = [timed(lambda: multi_view._tuple_problems_tracks(T, dev, result, 0., intr, kdim, nb, e_batch[forms[0]], repair_rounds=R))[0]
                        for _ in range(args.reps + 1)][1:]
             track_stats = multi_view.match_tracks(T, dev, result, repair_rounds=R)[1].cpu().numpy()
+    cam_to_world = np.linalg.inv(np.stack([data[f"pose{m}"].numpy().astype(np.float64) for m in range(T)], 1))  # [B,T,4,4]
+    worst = lambda E: float(max(np.nanmax(np.maximum(*multi_view.tuple_pose_errors(E[b], cam_to_world[b]))) for b in range(B)))  # noqa: E731
     stat = lambda ts: {"median": float(np.median(ts)), "min": float(np.min(ts)), "max": float(np.max(ts))}  # noqa: E731
     first = forms[0]  # the form the unsuffixed keys describe: the host form unless --init device
     line = {"batch": B, "tuple_size": T, "n_kpts": args.kpts, "reps": args.reps, "init": args.init, "rel_pose_method": method, "csv_path_ms": stat(t_csv),
             "tracks": args.tracks, "repair_rounds": args.repair_rounds, "wrong": args.wrong, "batched_path_ms": stat(t_batch[first]), "batched_stage_ms": {k: float(np.median(v)) for k, v in stages[first].items()},
             "max_abs_extrinsics_difference": float(np.abs(e_csv - e_batch[first]).max()),
-            "loss": args.loss, "loss_scale": args.loss_scale,
+            "loss": args.loss, "loss_scale": args.loss_scale, "pair_loss": args.pair_loss, "pair_loss_scale": args.pair_loss_scale,
+            "relative_poses_ms": {f: stat(stages[f]["relative_poses"]) for f in forms},
+            "max_pose_error_deg": dict({f: worst(e_batch[f]) for f in forms}, csv=worst(e_csv)),
             "build_and_bundle_adjust_ms": {f: stat(stages[f]["build_and_bundle_adjust"]) for f in forms}}
     if args.init == "both":
         line["batched_path_device_init_ms"] = stat(t_batch["device"])
