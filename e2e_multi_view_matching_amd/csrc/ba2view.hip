@@ -413,3 +413,694 @@ extern "C" int e2emv_ba_2view_loss(e2emv_ctx* ctx, int B, int N, const float* d_
     return ba2view_run(ctx, "ba_2view_loss", B, N, d_kpts0n, d_kpts1n, d_conf, d_T_init, n_iterations, d_T_out, d_valid, loss, loss_scale,
                        d_summary, stream);
 }
+
+// ---- backward pass of ba2view_kernel<kLossNone>: dLoss/dconf and dLoss/dT_init from dLoss/dT_out (e2emv_ba_2view_backward) ----
+//
+// Phase 1 replays the forward loop from the inputs - the statements of ba2view_kernel, on the same helpers, so that every accept /
+// reject decision is the forward's - and keeps a tape in the workspace: X_k of every evaluation, and per evaluation a record
+// (Rt_k, lambda_k, precond, skipped, dc_k).  k* = the evaluation whose pose became the result.  Phase 2 walks k = k*-1 .. 0 with the
+// adjoint state (Rt_bar in LDS, X_bar in the workspace).  One LM step solves M d = b, M = A + lambda D, A = J^T J, b = -J^T r, D =
+// diag(max(A_jj, 1e-12)) under precond, else I.  With d_bar = (adjoint of exp(dc) Rt_k w.r.t. dc, X_bar_{k+1}) and M w = d_bar -
+// the forward's Schur complement with another right-hand side -
+//     J_bar = -(J w) d^T - (J d + r) w^T - 2 lambda J diag(w o d) [columns with D_jj = A_jj],   r_bar = -J w,
+// per match (two observations, 6 camera + 3 point columns), taken back through point_terms to X_bar_k, Rt_bar_k and the weight's
+// adjoint.  After k = 0: the triangulation (first-order perturbation of the null vector of G = A^T A from the Jacobi eigenpairs,
+// then 1 / (X3 + 1e-8)) and the normalisation of the weights.  lambda, the comparisons and k* are piecewise constant.
+// The forward's text stays as it is (its results are pinned bit for bit), so its 6x6 elimination and its exponential are stated a
+// second time below, as functions.
+namespace e2emv {
+
+constexpr int kBaRec = 20;  // doubles per evaluation record: Rt (12), lambda, flags (1 precond, 2 update skipped), dc (6)
+
+struct BaBwdParams {
+    int B, N, n_it;
+    const float *k0, *k1, *conf, *Tin, *gT;
+    float* gconf;   // [B][N] or NULL
+    float* gTin;    // [B][4][4] or NULL
+    double* ws;     // per pair: X tape [n_it + 1][N][3], X_bar [N][3], c_bar [N], records [n_it + 1][kBaRec]
+    size_t stride;  // doubles per pair
+    float lm_inc, lm_dec;
+};
+
+// [M | rhs] of the reduced camera system in LDS and its solution by Gaussian elimination with partial pivoting, one lane: a = camera
+// block (21 packed, then 6 right-hand sides), s = what the point blocks take from it.  The statements of ba2view_kernel.
+__device__ __forceinline__ bool schur6_solve(double (&M6)[6][7], const double (&a)[27], const double (&s)[27], double lam, bool precond,
+                                             double* x) {
+    const int dpos[6] = {0, 6, 11, 15, 18, 20};
+    int idx = 0;
+    for (int u = 0; u < 6; ++u)
+        for (int v = u; v < 6; ++v) {
+            const double h = a[idx] - s[idx];
+            M6[u][v] = h;
+            M6[v][u] = h;
+            ++idx;
+        }
+    for (int u = 0; u < 6; ++u) {
+        M6[u][u] += lam * (precond ? fmax(a[dpos[u]], 1e-12) : 1.0);
+        M6[u][6] = a[21 + u] - s[21 + u];
+    }
+    bool ok = true;
+    for (int c = 0; c < 6 && ok; ++c) {
+        int piv = c;
+        for (int r = c + 1; r < 6; ++r)
+            if (fabs(M6[r][c]) > fabs(M6[piv][c])) piv = r;
+        if (!(fabs(M6[piv][c]) > 0.0)) { ok = false; break; }
+        if (piv != c)
+            for (int k = 0; k < 7; ++k) { const double t = M6[c][k]; M6[c][k] = M6[piv][k]; M6[piv][k] = t; }
+        for (int r = c + 1; r < 6; ++r) {
+            const double f = M6[r][c] / M6[c][c];
+            for (int k = c; k < 7; ++k) M6[r][k] -= f * M6[c][k];
+        }
+    }
+    if (ok) {
+        for (int c = 5; c >= 0; --c) {
+            double v = M6[c][6];
+            for (int k = c + 1; k < 6; ++k) v -= M6[c][k] * x[k];
+            x[c] = v / M6[c][c];
+            ok = ok && isfinite(x[c]);
+        }
+    }
+    return ok;
+}
+
+// pytorch3d's se3_exp_map with its 1e-4 clamp of |w|^2: coefficients and matrices of exp(dc), dc = (v, w)
+struct ExpTerms {
+    double th, f1, f2, f3;
+    bool clamped;
+    double Kx[9], K2[9], Rd[9], Vm[9];
+};
+__device__ __forceinline__ void se3_exp_terms(const double* dc, ExpTerms& e) {
+    const double wx = dc[3], wy = dc[4], wz = dc[5];
+    const double n2 = wx * wx + wy * wy + wz * wz;
+    const double th2 = fmax(n2, 1e-4), th = sqrt(th2);
+    e.clamped = n2 < 1e-4;
+    e.th = th;
+    e.f1 = sin(th) / th; e.f2 = (1.0 - cos(th)) / th2; e.f3 = (th - sin(th)) / (th2 * th);
+    const double Kx[9] = {0, -wz, wy, wz, 0, -wx, -wy, wx, 0};
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) e.K2[i * 3 + j] = Kx[i * 3] * Kx[j] + Kx[i * 3 + 1] * Kx[3 + j] + Kx[i * 3 + 2] * Kx[6 + j];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) {
+        const double d = (i % 4 == 0) ? 1.0 : 0.0;
+        e.Kx[i] = Kx[i];
+        e.Rd[i] = d + e.f1 * Kx[i] + e.f2 * e.K2[i];
+        e.Vm[i] = d + e.f2 * Kx[i] + e.f3 * e.K2[i];
+    }
+}
+// Rt <- exp(dc) Rt (R row-major 0..8, t 9..11); the expressions of ba2view_kernel
+__device__ __forceinline__ void se3_exp_left(const double* dc, const double* Rt, double* out) {
+    ExpTerms e;
+    se3_exp_terms(dc, e);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        const double td = e.Vm[i * 3] * dc[0] + e.Vm[i * 3 + 1] * dc[1] + e.Vm[i * 3 + 2] * dc[2];
+#pragma unroll
+        for (int j = 0; j < 3; ++j) out[i * 3 + j] = e.Rd[i * 3] * Rt[j] + e.Rd[i * 3 + 1] * Rt[3 + j] + e.Rd[i * 3 + 2] * Rt[6 + j];
+        out[9 + i] = e.Rd[i * 3] * Rt[9] + e.Rd[i * 3 + 1] * Rt[10] + e.Rd[i * 3 + 2] * Rt[11] + td;
+    }
+}
+// adjoint of se3_exp_left: nb = adjoint of the new pose -> dcb [6], and tb [12] = the part of the old pose's adjoint that comes
+// through the product.  In the clamped branch f1, f2, f3 are constants: the derivative flows through hat(w) only.
+__device__ __forceinline__ void se3_exp_left_reverse(const double* dc, const double* Rt, const double* nb, double* dcb, double* tb) {
+    ExpTerms e;
+    se3_exp_terms(dc, e);
+    double Rdb[9], Vmb[9], K2b[9], Kxb[9];
+    double f1b = 0.0, f2b = 0.0, f3b = 0.0;
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            Rdb[i * 3 + j] = nb[i * 3] * Rt[j * 3] + nb[i * 3 + 1] * Rt[j * 3 + 1] + nb[i * 3 + 2] * Rt[j * 3 + 2] + nb[9 + i] * Rt[9 + j];
+            Vmb[i * 3 + j] = nb[9 + i] * dc[j];
+        }
+#pragma unroll
+    for (int j = 0; j < 3; ++j) dcb[j] = e.Vm[j] * nb[9] + e.Vm[3 + j] * nb[10] + e.Vm[6 + j] * nb[11];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) {
+        f1b += Rdb[i] * e.Kx[i];
+        f2b += Rdb[i] * e.K2[i] + Vmb[i] * e.Kx[i];
+        f3b += Vmb[i] * e.K2[i];
+        K2b[i] = e.f2 * Rdb[i] + e.f3 * Vmb[i];
+    }
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            double v = e.f1 * Rdb[i * 3 + j] + e.f2 * Vmb[i * 3 + j];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) v += K2b[i * 3 + k] * e.Kx[j * 3 + k] + e.Kx[k * 3 + i] * K2b[k * 3 + j];  // K2b Kx^T + Kx^T K2b
+            Kxb[i * 3 + j] = v;
+        }
+    dcb[3] = Kxb[7] - Kxb[5];
+    dcb[4] = Kxb[2] - Kxb[6];
+    dcb[5] = Kxb[3] - Kxb[1];
+    if (!e.clamped) {
+        const double th = e.th, sn = sin(th), cs = cos(th), th2 = th * th;
+        const double thb = f1b * (th * cs - sn) / th2 + f2b * (th * sn - 2.0 * (1.0 - cs)) / (th2 * th) +
+                           f3b * ((1.0 - cs) * th - 3.0 * (th - sn)) / (th2 * th2);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) dcb[3 + k] += thb * dc[3 + k] / th;
+    }
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) tb[i * 3 + j] = e.Rd[i] * nb[j] + e.Rd[3 + i] * nb[3 + j] + e.Rd[6 + i] * nb[6 + j];
+        tb[9 + i] = e.Rd[i] * nb[9] + e.Rd[3 + i] * nb[10] + e.Rd[6 + i] * nb[11];
+    }
+}
+
+// adjoint of point_terms<kLossNone>: qb holds the adjoints of q's entries (those of the structural zeros are not read) -> Xb [3],
+// g [12] += the pose's share, returns the weight's adjoint
+__device__ __forceinline__ double point_terms_reverse(const double* Rt, const double* X, double x0, double y0, double x1, double y1, double c,
+                                                      const PointTerms& qb, double* Xb, double* g) {
+    const double iz0 = 1.0 / X[2];
+    double cb = qb.r0[0] * (X[0] * iz0 - x0) + qb.r0[1] * (X[1] * iz0 - y0) + (qb.Jp0[0][0] + qb.Jp0[1][1]) * iz0 -
+                (qb.Jp0[0][2] * X[0] + qb.Jp0[1][2] * X[1]) * iz0 * iz0;
+    Xb[0] = qb.r0[0] * c * iz0 - qb.Jp0[0][2] * c * iz0 * iz0;
+    Xb[1] = qb.r0[1] * c * iz0 - qb.Jp0[1][2] * c * iz0 * iz0;
+    const double iz0b = c * (qb.r0[0] * X[0] + qb.r0[1] * X[1]) + c * (qb.Jp0[0][0] + qb.Jp0[1][1]) -
+                        2.0 * c * iz0 * (qb.Jp0[0][2] * X[0] + qb.Jp0[1][2] * X[1]);
+    Xb[2] = -iz0b * iz0 * iz0;
+    const double a0 = Rt[0] * X[0] + Rt[1] * X[1] + Rt[2] * X[2] + Rt[9];
+    const double a1 = Rt[3] * X[0] + Rt[4] * X[1] + Rt[5] * X[2] + Rt[10];
+    const double a2 = Rt[6] * X[0] + Rt[7] * X[1] + Rt[8] * X[2] + Rt[11];
+    const double iz = 1.0 / a2;
+    const double j00 = c * iz, j02 = -c * a0 * iz * iz, j11 = c * iz, j12 = -c * a1 * iz * iz;
+    cb += qb.r1[0] * (a0 * iz - x1) + qb.r1[1] * (a1 * iz - y1);
+    double ab[3] = {qb.r1[0] * c * iz, qb.r1[1] * c * iz, 0.0};
+    double izb = c * (qb.r1[0] * a0 + qb.r1[1] * a1);
+    double j00b = qb.Jc[0][0] + qb.Jc[0][4] * a2 - qb.Jc[0][5] * a1;
+    double j02b = qb.Jc[0][2] + qb.Jc[0][3] * a1 - qb.Jc[0][4] * a0;
+    double j11b = qb.Jc[1][1] - qb.Jc[1][3] * a2 + qb.Jc[1][5] * a0;
+    double j12b = qb.Jc[1][2] + qb.Jc[1][3] * a1 - qb.Jc[1][4] * a0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        j00b += qb.Jp1[0][k] * Rt[k];
+        j02b += qb.Jp1[0][k] * Rt[6 + k];
+        j11b += qb.Jp1[1][k] * Rt[3 + k];
+        j12b += qb.Jp1[1][k] * Rt[6 + k];
+        g[k] += qb.Jp1[0][k] * j00;
+        g[3 + k] += qb.Jp1[1][k] * j11;
+        g[6 + k] += qb.Jp1[0][k] * j02 + qb.Jp1[1][k] * j12;
+    }
+    ab[0] += -qb.Jc[0][4] * j02 - qb.Jc[1][4] * j12 + qb.Jc[1][5] * j11;
+    ab[1] += qb.Jc[0][3] * j02 - qb.Jc[0][5] * j00 + qb.Jc[1][3] * j12;
+    ab[2] += qb.Jc[0][4] * j00 - qb.Jc[1][3] * j11;
+    cb += (j00b + j11b) * iz - (j02b * a0 + j12b * a1) * iz * iz;
+    izb += (j00b + j11b) * c - 2.0 * c * iz * (j02b * a0 + j12b * a1);
+    ab[0] -= j02b * c * iz * iz;
+    ab[1] -= j12b * c * iz * iz;
+    ab[2] -= izb * iz * iz;
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) g[3 * r + k] += ab[r] * X[k];
+        g[9 + r] += ab[r];
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) Xb[k] += ab[0] * Rt[k] + ab[1] * Rt[3 + k] + ab[2] * Rt[6 + k];
+    return cb;
+}
+
+// adjoint of triangulate_xyz w.r.t. the pose: g [12] += .  The null vector v of G = A^T A moves by dv = -sum_{j != m} v_j v_j^T dG v /
+// (l_j - l_m); with u = -sum_j v_j (v_j . v_bar) / (l_j - l_m) the adjoint of A is (A u) v^T + (A v) u^T, of which rows 2 and 3 hold the pose.
+__device__ __forceinline__ void triangulate_reverse(double x1, double y1, double x2, double y2, const double* Rt, const double* Xb, double* g) {
+    double Ar[4][4];
+    Ar[0][0] = -1.0; Ar[0][1] = 0.0; Ar[0][2] = x1; Ar[0][3] = 0.0;
+    Ar[1][0] = 0.0; Ar[1][1] = -1.0; Ar[1][2] = y1; Ar[1][3] = 0.0;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        Ar[2][j] = x2 * Rt[6 + j] - Rt[j];
+        Ar[3][j] = y2 * Rt[6 + j] - Rt[3 + j];
+    }
+    Ar[2][3] = x2 * Rt[11] - Rt[9];
+    Ar[3][3] = y2 * Rt[11] - Rt[10];
+    double G[4][4], V[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = i; j < 4; ++j) {
+            const double v = Ar[0][i] * Ar[0][j] + Ar[1][i] * Ar[1][j] + Ar[2][i] * Ar[2][j] + Ar[3][i] * Ar[3][j];
+            G[i][j] = v;
+            G[j][i] = v;
+        }
+    jacobi_static<4>(G, V);
+    int m = 0;
+    double gm = G[0][0];
+#pragma unroll
+    for (int i = 1; i < 4; ++i)
+        if (G[i][i] < gm) { gm = G[i][i]; m = i; }
+    double v[4], vb[4], u[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) v[i] = (m == 0) ? V[i][0] : (m == 1) ? V[i][1] : (m == 2) ? V[i][2] : V[i][3];
+    const bool big = fabs(v[3]) > 1e-8;
+    const double sc = big ? 1.0 / (v[3] + 1e-8) : 1.0;
+    vb[0] = Xb[0] * sc; vb[1] = Xb[1] * sc; vb[2] = Xb[2] * sc;
+    vb[3] = big ? -(Xb[0] * v[0] + Xb[1] * v[1] + Xb[2] * v[2]) * sc * sc : 0.0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const double gap = G[j][j] - gm;
+        if (j == m || !(fabs(gap) > 0.0)) continue;
+        const double coef = -(V[0][j] * vb[0] + V[1][j] * vb[1] + V[2][j] * vb[2] + V[3][j] * vb[3]) / gap;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) u[i] += coef * V[i][j];
+    }
+    double Au[2], Av[2];
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        Au[r] = Ar[2 + r][0] * u[0] + Ar[2 + r][1] * u[1] + Ar[2 + r][2] * u[2] + Ar[2 + r][3] * u[3];
+        Av[r] = Ar[2 + r][0] * v[0] + Ar[2 + r][1] * v[1] + Ar[2 + r][2] * v[2] + Ar[2 + r][3] * v[3];
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const double b2 = Au[0] * v[j] + Av[0] * u[j], b3 = Au[1] * v[j] + Av[1] * u[j];  // adjoint of Ar[2][j], Ar[3][j]
+        const int o = j < 3 ? j : 9;                                                        // R column j, or t
+        g[o] -= b2;
+        g[o + (j < 3 ? 3 : 1)] -= b3;
+        g[o + (j < 3 ? 6 : 2)] += x2 * b2 + y2 * b3;
+    }
+}
+
+__global__ __launch_bounds__(256) void ba2view_backward_kernel(BaBwdParams p) {
+    __shared__ double red[4 * 32];
+    __shared__ double sRt[12], sDelta[6], sRtBar[12], sDcBar[6];
+    __shared__ double sLam, sBestR;
+    __shared__ double sM6[6][7];
+    __shared__ int sFlags, sKstar;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int N = p.N;
+    const float* k0 = p.k0 + (int64_t)b * N * 2;
+    const float* k1 = p.k1 + (int64_t)b * N * 2;
+    const float* cf = p.conf + (int64_t)b * N;
+    const float* Ti = p.Tin + (int64_t)b * 16;
+    const float* gT = p.gT + (int64_t)b * 16;
+    double* tape = p.ws + (size_t)b * p.stride;                 // X_k at tape + k * N * 3
+    double* Xbar = tape + (size_t)(p.n_it + 1) * N * 3;
+    double* cbar = Xbar + (size_t)N * 3;
+    double* recs = cbar + N;
+    const size_t xs = (size_t)N * 3;
+
+    double st[2] = {0.0, 0.0};
+    for (int i = tid; i < N; i += 256)
+        if (cf[i] > 0.f) { st[0] += (double)cf[i]; st[1] += 1.0; }
+    block_sum_n<2>(st, red);
+    const bool valid = st[1] > 6.5;
+    const double cden = 0.5 * fmax(2.0 * st[0], 1e-6);
+
+    // ---- phase 1: the forward loop again, with the tape
+    if (valid) {
+        if (tid < 12) {
+            const int r = tid < 9 ? tid / 3 : tid - 9, c = tid < 9 ? tid % 3 : 3;
+            sRt[tid] = (double)Ti[r * 4 + c];
+        }
+        if (tid == 0) { sLam = 0.1; sBestR = 0.0; sFlags = 0; sKstar = 0; }
+        __syncthreads();
+        for (int i = tid; i < N; i += 256)
+            if (cf[i] > 0.f) triangulate_xyz(k0[2 * i], k0[2 * i + 1], k1[2 * i], k1[2 * i + 1], sRt, tape + 3 * i);
+        __syncthreads();
+    }
+    for (int it = 0; valid && it <= p.n_it; ++it) {
+        const double* X = tape + it * xs;
+        double* Xn = tape + (it + 1) * xs;  // written only when it < n_it
+        double Rt[12];
+#pragma unroll
+        for (int k = 0; k < 12; ++k) Rt[k] = sRt[k];
+        double a[29];
+#pragma unroll
+        for (int k = 0; k < 29; ++k) a[k] = 0.0;
+        for (int i = tid; i < N; i += 256) {
+            if (!(cf[i] > 0.f)) continue;
+            PointTerms q;
+            a[27] += point_terms<kLossNone>(Rt, X + 3 * i, k0[2 * i], k0[2 * i + 1], k1[2 * i], k1[2 * i + 1], (double)cf[i] / cden, 0.0, 0.0, q);
+            int idx = 0;
+#pragma unroll
+            for (int u = 0; u < 6; ++u) {
+#pragma unroll
+                for (int v = u; v < 6; ++v) a[idx++] += q.Jc[0][u] * q.Jc[0][v] + q.Jc[1][u] * q.Jc[1][v];
+                a[21 + u] -= q.Jc[0][u] * q.r1[0] + q.Jc[1][u] * q.r1[1];
+            }
+            bool pos = true;
+#pragma unroll
+            for (int k = 0; k < 3; ++k)
+                pos = pos && (q.Jp0[0][k] * q.Jp0[0][k] + q.Jp0[1][k] * q.Jp0[1][k] + q.Jp1[0][k] * q.Jp1[0][k] + q.Jp1[1][k] * q.Jp1[1][k]) > 0.0;
+            if (!pos) a[28] += 1.0;
+        }
+        block_sum_n<29>(a, red);
+        const double rn = a[27];
+        if (tid == 0) {
+            if (it == 0) {
+                sBestR = rn;
+            } else if (rn < sBestR) {
+                sBestR = rn;
+                sKstar = it;
+                sLam = sLam / (double)p.lm_dec;
+            } else {
+                sLam = sLam * (double)p.lm_inc;
+            }
+        }
+        __syncthreads();
+        if (it == p.n_it) break;
+        const double lam = sLam;
+        const int dpos[6] = {0, 6, 11, 15, 18, 20};
+        bool precond = a[28] < 0.5;
+#pragma unroll
+        for (int u = 0; u < 6; ++u) precond = precond && a[dpos[u]] > 0.0;
+
+        double s[27];
+#pragma unroll
+        for (int k = 0; k < 27; ++k) s[k] = 0.0;
+        for (int i = tid; i < N; i += 256) {
+            if (!(cf[i] > 0.f)) continue;
+            PointTerms q;
+            point_terms<kLossNone>(Rt, X + 3 * i, k0[2 * i], k0[2 * i + 1], k1[2 * i], k1[2 * i + 1], (double)cf[i] / cden, 0.0, 0.0, q);
+            double Hpp[6], gp[3], Hcp[6][3], inv[6];
+            int idx = 0;
+#pragma unroll
+            for (int u = 0; u < 3; ++u) {
+#pragma unroll
+                for (int v = u; v < 3; ++v)
+                    Hpp[idx++] = q.Jp0[0][u] * q.Jp0[0][v] + q.Jp0[1][u] * q.Jp0[1][v] + q.Jp1[0][u] * q.Jp1[0][v] + q.Jp1[1][u] * q.Jp1[1][v];
+                gp[u] = -(q.Jp0[0][u] * q.r0[0] + q.Jp0[1][u] * q.r0[1] + q.Jp1[0][u] * q.r1[0] + q.Jp1[1][u] * q.r1[1]);
+            }
+#pragma unroll
+            for (int u = 0; u < 6; ++u)
+#pragma unroll
+                for (int v = 0; v < 3; ++v) Hcp[u][v] = q.Jc[0][u] * q.Jp1[0][v] + q.Jc[1][u] * q.Jp1[1][v];
+            Hpp[0] += lam * (precond ? fmax(Hpp[0], 1e-12) : 1.0);
+            Hpp[3] += lam * (precond ? fmax(Hpp[3], 1e-12) : 1.0);
+            Hpp[5] += lam * (precond ? fmax(Hpp[5], 1e-12) : 1.0);
+            if (!inv3_sym(Hpp, inv)) continue;
+            double W[6][3];
+#pragma unroll
+            for (int u = 0; u < 6; ++u) {
+                W[u][0] = Hcp[u][0] * inv[0] + Hcp[u][1] * inv[1] + Hcp[u][2] * inv[2];
+                W[u][1] = Hcp[u][0] * inv[1] + Hcp[u][1] * inv[3] + Hcp[u][2] * inv[4];
+                W[u][2] = Hcp[u][0] * inv[2] + Hcp[u][1] * inv[4] + Hcp[u][2] * inv[5];
+            }
+            idx = 0;
+#pragma unroll
+            for (int u = 0; u < 6; ++u) {
+#pragma unroll
+                for (int v = u; v < 6; ++v) s[idx++] += W[u][0] * Hcp[v][0] + W[u][1] * Hcp[v][1] + W[u][2] * Hcp[v][2];
+                s[21 + u] += W[u][0] * gp[0] + W[u][1] * gp[1] + W[u][2] * gp[2];
+            }
+        }
+        block_sum_n<27>(s, red);
+        if (tid == 0) {
+            double a27[27];
+#pragma unroll
+            for (int k = 0; k < 27; ++k) a27[k] = a[k];
+            const bool ok = schur6_solve(sM6, a27, s, lam, precond, sDelta);
+            sFlags = ok ? 0 : 1;
+            double* rec = recs + (size_t)it * kBaRec;
+#pragma unroll
+            for (int k = 0; k < 12; ++k) rec[k] = Rt[k];
+            rec[12] = lam;
+            rec[13] = (double)((precond ? 1 : 0) | (ok ? 0 : 2));
+#pragma unroll
+            for (int k = 0; k < 6; ++k) rec[14 + k] = ok ? sDelta[k] : 0.0;
+        }
+        __syncthreads();
+        if (sFlags & 1) {  // the update is skipped: the next evaluation sees the same points
+            for (int i = tid; i < N; i += 256)
+                if (cf[i] > 0.f) { Xn[3 * i] = X[3 * i]; Xn[3 * i + 1] = X[3 * i + 1]; Xn[3 * i + 2] = X[3 * i + 2]; }
+            __syncthreads();
+            continue;
+        }
+        double dc[6];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) dc[k] = sDelta[k];
+        for (int i = tid; i < N; i += 256) {
+            if (!(cf[i] > 0.f)) continue;
+            PointTerms q;
+            point_terms<kLossNone>(Rt, X + 3 * i, k0[2 * i], k0[2 * i + 1], k1[2 * i], k1[2 * i + 1], (double)cf[i] / cden, 0.0, 0.0, q);
+            double Hpp[6], rhs[3], inv[6];
+            int idx = 0;
+#pragma unroll
+            for (int u = 0; u < 3; ++u) {
+#pragma unroll
+                for (int v = u; v < 3; ++v)
+                    Hpp[idx++] = q.Jp0[0][u] * q.Jp0[0][v] + q.Jp0[1][u] * q.Jp0[1][v] + q.Jp1[0][u] * q.Jp1[0][v] + q.Jp1[1][u] * q.Jp1[1][v];
+                double g = -(q.Jp0[0][u] * q.r0[0] + q.Jp0[1][u] * q.r0[1] + q.Jp1[0][u] * q.r1[0] + q.Jp1[1][u] * q.r1[1]);
+#pragma unroll
+                for (int w = 0; w < 6; ++w) g -= (q.Jc[0][w] * q.Jp1[0][u] + q.Jc[1][w] * q.Jp1[1][u]) * dc[w];
+                rhs[u] = g;
+            }
+            Hpp[0] += lam * (precond ? fmax(Hpp[0], 1e-12) : 1.0);
+            Hpp[3] += lam * (precond ? fmax(Hpp[3], 1e-12) : 1.0);
+            Hpp[5] += lam * (precond ? fmax(Hpp[5], 1e-12) : 1.0);
+            double d0 = 0.0, d1 = 0.0, d2 = 0.0;
+            if (inv3_sym(Hpp, inv)) {
+                d0 = inv[0] * rhs[0] + inv[1] * rhs[1] + inv[2] * rhs[2];
+                d1 = inv[1] * rhs[0] + inv[3] * rhs[1] + inv[4] * rhs[2];
+                d2 = inv[2] * rhs[0] + inv[4] * rhs[1] + inv[5] * rhs[2];
+            }
+            Xn[3 * i] = X[3 * i] + d0;
+            Xn[3 * i + 1] = X[3 * i + 1] + d1;
+            Xn[3 * i + 2] = X[3 * i + 2] + d2;
+        }
+        __syncthreads();
+        if (tid == 0) {
+            double Rn[12];
+            se3_exp_left(dc, Rt, Rn);
+#pragma unroll
+            for (int i = 0; i < 12; ++i) sRt[i] = Rn[i];
+        }
+        __syncthreads();
+    }
+    const int kstar = valid ? sKstar : 0;
+
+    // ---- phase 2: the steps k* - 1 .. 0 in reverse
+    if (tid < 12) {
+        const int r = tid < 9 ? tid / 3 : tid - 9, c = tid < 9 ? tid % 3 : 3;
+        sRtBar[tid] = (double)gT[r * 4 + c];
+    }
+    for (int i = tid; i < N; i += 256) {
+        Xbar[3 * i] = 0.0; Xbar[3 * i + 1] = 0.0; Xbar[3 * i + 2] = 0.0;
+        cbar[i] = 0.0;
+    }
+    for (int k = kstar - 1; k >= 0; --k) {
+        __syncthreads();
+        const double* rec = recs + (size_t)k * kBaRec;
+        const int flags = (int)rec[13];
+        if (flags & 2) continue;  // a skipped update is the identity
+        const double* X = tape + k * xs;
+        const bool precond = (flags & 1) != 0;
+        const double lam = rec[12];
+        double Rt[12], dc[6];
+#pragma unroll
+        for (int i = 0; i < 12; ++i) Rt[i] = rec[i];
+#pragma unroll
+        for (int i = 0; i < 6; ++i) dc[i] = rec[14 + i];
+        if (tid == 0) {
+            double nb[12], dcb[6], tb[12];
+#pragma unroll
+            for (int i = 0; i < 12; ++i) nb[i] = sRtBar[i];
+            se3_exp_left_reverse(dc, Rt, nb, dcb, tb);
+#pragma unroll
+            for (int i = 0; i < 12; ++i) sRtBar[i] = tb[i];
+#pragma unroll
+            for (int i = 0; i < 6; ++i) sDcBar[i] = dcb[i];
+        }
+        // pass A: M w = d_bar through the forward's Schur complement
+        double a[27], s[27];
+#pragma unroll
+        for (int i = 0; i < 27; ++i) { a[i] = 0.0; s[i] = 0.0; }
+        for (int i = tid; i < N; i += 256) {
+            if (!(cf[i] > 0.f)) continue;
+            PointTerms q;
+            point_terms<kLossNone>(Rt, X + 3 * i, k0[2 * i], k0[2 * i + 1], k1[2 * i], k1[2 * i + 1], (double)cf[i] / cden, 0.0, 0.0, q);
+            int idx = 0;
+#pragma unroll
+            for (int u = 0; u < 6; ++u)
+#pragma unroll
+                for (int v = u; v < 6; ++v) a[idx++] += q.Jc[0][u] * q.Jc[0][v] + q.Jc[1][u] * q.Jc[1][v];
+            double Hpp[6], Hcp[6][3], inv[6];
+            idx = 0;
+#pragma unroll
+            for (int u = 0; u < 3; ++u)
+#pragma unroll
+                for (int v = u; v < 3; ++v)
+                    Hpp[idx++] = q.Jp0[0][u] * q.Jp0[0][v] + q.Jp0[1][u] * q.Jp0[1][v] + q.Jp1[0][u] * q.Jp1[0][v] + q.Jp1[1][u] * q.Jp1[1][v];
+#pragma unroll
+            for (int u = 0; u < 6; ++u)
+#pragma unroll
+                for (int v = 0; v < 3; ++v) Hcp[u][v] = q.Jc[0][u] * q.Jp1[0][v] + q.Jc[1][u] * q.Jp1[1][v];
+            Hpp[0] += lam * (precond ? fmax(Hpp[0], 1e-12) : 1.0);
+            Hpp[3] += lam * (precond ? fmax(Hpp[3], 1e-12) : 1.0);
+            Hpp[5] += lam * (precond ? fmax(Hpp[5], 1e-12) : 1.0);
+            if (!inv3_sym(Hpp, inv)) continue;
+            const double xb0 = Xbar[3 * i], xb1 = Xbar[3 * i + 1], xb2 = Xbar[3 * i + 2];
+            idx = 0;
+#pragma unroll
+            for (int u = 0; u < 6; ++u) {
+                const double w0 = Hcp[u][0] * inv[0] + Hcp[u][1] * inv[1] + Hcp[u][2] * inv[2];
+                const double w1 = Hcp[u][0] * inv[1] + Hcp[u][1] * inv[3] + Hcp[u][2] * inv[4];
+                const double w2 = Hcp[u][0] * inv[2] + Hcp[u][1] * inv[4] + Hcp[u][2] * inv[5];
+#pragma unroll
+                for (int v = u; v < 6; ++v) s[idx++] += w0 * Hcp[v][0] + w1 * Hcp[v][1] + w2 * Hcp[v][2];
+                s[21 + u] += w0 * xb0 + w1 * xb1 + w2 * xb2;
+            }
+        }
+        block_sum_n<27>(a, red);
+        block_sum_n<27>(s, red);
+        if (tid == 0) {
+#pragma unroll
+            for (int u = 0; u < 6; ++u) a[21 + u] = sDcBar[u];
+            if (!schur6_solve(sM6, a, s, lam, precond, sDelta))
+                for (int u = 0; u < 6; ++u) sDelta[u] = 0.0;
+        }
+        __syncthreads();
+        const int dpos[6] = {0, 6, 11, 15, 18, 20};
+        double wc[6], wdc[6];  // w of the camera, and 2 lambda w o d on the columns whose damping follows the diagonal
+#pragma unroll
+        for (int u = 0; u < 6; ++u) {
+            wc[u] = sDelta[u];
+            wdc[u] = (precond && a[dpos[u]] >= 1e-12) ? 2.0 * lam * wc[u] * dc[u] : 0.0;
+        }
+        // pass B: the step and w per match, J_bar and r_bar, back through point_terms
+        double g[12];
+#pragma unroll
+        for (int i = 0; i < 12; ++i) g[i] = 0.0;
+        for (int i = tid; i < N; i += 256) {
+            if (!(cf[i] > 0.f)) continue;
+            const double c = (double)cf[i] / cden;
+            PointTerms q;
+            point_terms<kLossNone>(Rt, X + 3 * i, k0[2 * i], k0[2 * i + 1], k1[2 * i], k1[2 * i + 1], c, 0.0, 0.0, q);
+            double Hpp[6], inv[6], dp[3], wp[3], wdp[3];
+            const double xb[3] = {Xbar[3 * i], Xbar[3 * i + 1], Xbar[3 * i + 2]};
+            int idx = 0;
+#pragma unroll
+            for (int u = 0; u < 3; ++u) {
+#pragma unroll
+                for (int v = u; v < 3; ++v)
+                    Hpp[idx++] = q.Jp0[0][u] * q.Jp0[0][v] + q.Jp0[1][u] * q.Jp0[1][v] + q.Jp1[0][u] * q.Jp1[0][v] + q.Jp1[1][u] * q.Jp1[1][v];
+                double gd = -(q.Jp0[0][u] * q.r0[0] + q.Jp0[1][u] * q.r0[1] + q.Jp1[0][u] * q.r1[0] + q.Jp1[1][u] * q.r1[1]);
+                double gw = xb[u];
+#pragma unroll
+                for (int w = 0; w < 6; ++w) {
+                    const double h = q.Jc[0][w] * q.Jp1[0][u] + q.Jc[1][w] * q.Jp1[1][u];
+                    gd -= h * dc[w];
+                    gw -= h * wc[w];
+                }
+                dp[u] = gd;  // right-hand sides for now
+                wp[u] = gw;
+            }
+            const bool f0 = precond && Hpp[0] >= 1e-12, f1 = precond && Hpp[3] >= 1e-12, f2 = precond && Hpp[5] >= 1e-12;
+            Hpp[0] += lam * (precond ? fmax(Hpp[0], 1e-12) : 1.0);
+            Hpp[3] += lam * (precond ? fmax(Hpp[3], 1e-12) : 1.0);
+            Hpp[5] += lam * (precond ? fmax(Hpp[5], 1e-12) : 1.0);
+            if (!inv3_sym(Hpp, inv)) {  // the forward left this point where it was: only its camera columns took part
+#pragma unroll
+                for (int u = 0; u < 6; ++u) inv[u] = 0.0;
+            }
+            {
+                const double d0 = dp[0], d1 = dp[1], d2 = dp[2], w0 = wp[0], w1 = wp[1], w2 = wp[2];
+                dp[0] = inv[0] * d0 + inv[1] * d1 + inv[2] * d2;
+                dp[1] = inv[1] * d0 + inv[3] * d1 + inv[4] * d2;
+                dp[2] = inv[2] * d0 + inv[4] * d1 + inv[5] * d2;
+                wp[0] = inv[0] * w0 + inv[1] * w1 + inv[2] * w2;
+                wp[1] = inv[1] * w0 + inv[3] * w1 + inv[4] * w2;
+                wp[2] = inv[2] * w0 + inv[4] * w1 + inv[5] * w2;
+            }
+            wdp[0] = f0 ? 2.0 * lam * wp[0] * dp[0] : 0.0;
+            wdp[1] = f1 ? 2.0 * lam * wp[1] * dp[1] : 0.0;
+            wdp[2] = f2 ? 2.0 * lam * wp[2] * dp[2] : 0.0;
+            PointTerms qb;
+#pragma unroll
+            for (int r = 0; r < 2; ++r) {
+                double jd0 = 0.0, jw0 = 0.0, jd1 = 0.0, jw1 = 0.0;
+#pragma unroll
+                for (int u = 0; u < 3; ++u) {
+                    jd0 += q.Jp0[r][u] * dp[u];
+                    jw0 += q.Jp0[r][u] * wp[u];
+                    jd1 += q.Jp1[r][u] * dp[u];
+                    jw1 += q.Jp1[r][u] * wp[u];
+                }
+#pragma unroll
+                for (int u = 0; u < 6; ++u) {
+                    jd1 += q.Jc[r][u] * dc[u];
+                    jw1 += q.Jc[r][u] * wc[u];
+                }
+                const double e0 = jd0 + q.r0[r], e1 = jd1 + q.r1[r];
+                qb.r0[r] = -jw0;
+                qb.r1[r] = -jw1;
+#pragma unroll
+                for (int u = 0; u < 3; ++u) {
+                    qb.Jp0[r][u] = -jw0 * dp[u] - e0 * wp[u] - q.Jp0[r][u] * wdp[u];
+                    qb.Jp1[r][u] = -jw1 * dp[u] - e1 * wp[u] - q.Jp1[r][u] * wdp[u];
+                }
+#pragma unroll
+                for (int u = 0; u < 6; ++u) qb.Jc[r][u] = -jw1 * dc[u] - e1 * wc[u] - q.Jc[r][u] * wdc[u];
+            }
+            double Xb[3];
+            cbar[i] += point_terms_reverse(Rt, X + 3 * i, k0[2 * i], k0[2 * i + 1], k1[2 * i], k1[2 * i + 1], c, qb, Xb, g);
+            Xbar[3 * i] = xb[0] + Xb[0];
+            Xbar[3 * i + 1] = xb[1] + Xb[1];
+            Xbar[3 * i + 2] = xb[2] + Xb[2];
+        }
+        block_sum_n<12>(g, red);
+        if (tid < 12) sRtBar[tid] += g[tid];
+    }
+    __syncthreads();
+    double t2[2] = {0.0, 0.0};
+    if (kstar > 0) {
+        // the start points: X_0 = tri(Rt_0)
+        double Rt[12], g[12];
+#pragma unroll
+        for (int i = 0; i < 12; ++i) { Rt[i] = recs[i]; g[i] = 0.0; }
+        for (int i = tid; i < N; i += 256) {
+            if (!(cf[i] > 0.f)) continue;
+            triangulate_reverse(k0[2 * i], k0[2 * i + 1], k1[2 * i], k1[2 * i + 1], Rt, Xbar + 3 * i, g);
+            t2[0] += cbar[i] * ((double)cf[i] / cden);
+        }
+        block_sum_n<12>(g, red);
+        if (tid < 12) sRtBar[tid] += g[tid];
+        block_sum_n<2>(t2, red);
+    }
+    __syncthreads();
+    if (p.gconf) {
+        // weights c_i = conf_i / cden, cden = sum conf while 2 sum conf >= 1e-6 (a constant below that)
+        const double shift = 2.0 * st[0] >= 1e-6 ? t2[0] / cden : 0.0;
+        for (int i = tid; i < N; i += 256)
+            p.gconf[(int64_t)b * N + i] = (kstar > 0 && cf[i] > 0.f) ? (float)(cbar[i] / cden - shift) : 0.f;
+    }
+    if (p.gTin && tid < 16) {
+        const int r = tid >> 2, c = tid & 3;
+        p.gTin[(int64_t)b * 16 + tid] = r < 3 ? (float)sRtBar[c < 3 ? r * 3 + c : 9 + r] : 0.f;
+    }
+}
+
+}  // namespace e2emv
+
+extern "C" int e2emv_ba_2view_backward(e2emv_ctx* ctx, int B, int N, const float* d_kpts0n, const float* d_kpts1n, const float* d_conf,
+                                       const float* d_T_init, int n_iterations, const float* d_gT, float* d_gconf, float* d_gTinit,
+                                       void* stream) {
+    if (!ctx || !d_kpts0n || !d_kpts1n || !d_conf || !d_T_init || !d_gT) return E2EMV_EINVAL;
+    E2EMV_ENTER(ctx, stream);
+    if (B <= 0 || N <= 0 || n_iterations < 0) return set_err(ctx, E2EMV_ESHAPE, "ba_2view_backward: B=%d N=%d iterations=%d", B, N, n_iterations);
+    if (!d_gconf && !d_gTinit) return E2EMV_OK;
+    // doubles per pair: X tape (n + 1) N 3, X_bar N 3, c_bar N, records (n + 1) kBaRec - in size_t, and an overflow is an error
+    const size_t evals = (size_t)n_iterations + 1, cap = ~(size_t)0 / sizeof(double);
+    const size_t per_eval = (size_t)N * 3 + kBaRec;
+    if (evals > (cap - (size_t)N * 4) / per_eval)
+        return set_err(ctx, E2EMV_ENOMEM, "ba_2view_backward: the tape of N=%d, %d iterations does not fit a size_t", N, n_iterations);
+    const size_t stride = evals * per_eval + (size_t)N * 4;
+    if ((size_t)B > (cap - 32) / stride)
+        return set_err(ctx, E2EMV_ENOMEM, "ba_2view_backward: the tape of B=%d N=%d, %d iterations does not fit a size_t", B, N, n_iterations);
+    int rc = ws_reserve(ctx, (size_t)B * stride * sizeof(double) + 256);
+    if (rc) return rc;
+    BaBwdParams p{};
+    p.B = B; p.N = N; p.n_it = n_iterations;
+    p.k0 = d_kpts0n; p.k1 = d_kpts1n; p.conf = d_conf; p.Tin = d_T_init; p.gT = d_gT; p.gconf = d_gconf; p.gTin = d_gTinit;
+    p.ws = (double*)ctx->d_ws; p.stride = stride;
+    p.lm_inc = 1.5f; p.lm_dec = 3.5f;
+    hipStream_t s = (hipStream_t)stream;
+    prof_begin(ctx, PS_W8PT, s);
+    hipLaunchKernelGGL(ba2view_backward_kernel, dim3(B), dim3(256), 0, s, p);
+    prof_end(ctx, s);
+    E2EMV_CHECK_LAUNCH(ctx, "ba2view_backward_kernel");
+    return E2EMV_OK;
+}

@@ -331,7 +331,10 @@ def compute_translation_error_as_angle(T0, T1, reduce=True):
 
 def mask_confidence(confidence, mask):
     """``confidence[~mask] = 0`` as a new tensor, on the device (``e2emv_apply_mask``): the step between the weighted 8-point
-    solve and the two-view bundle adjustment (``eval_pairs.py:250-251``, ``bundle_adjust_io.py:18-19``)."""
+    solve and the two-view bundle adjustment (``eval_pairs.py:250-251``, ``bundle_adjust_io.py:18-19``).  Differentiable with respect
+    to ``confidence`` (``_MaskConfidence``: the same kernel on the incoming gradient)."""
+    if torch.is_grad_enabled() and confidence.requires_grad:
+        return _MaskConfidence.apply(confidence, mask)
     dev = _dev_of(confidence, mask)
     ctx = _lib.context(dev)
     c = _prep(confidence, dev)
@@ -341,6 +344,19 @@ def mask_confidence(confidence, mask):
         with torch.cuda.device(dev):
             ctx.call("e2emv_apply_mask", c.numel(), _lib.ptr(c), _lib.ptr(m), _lib.ptr(out), _lib.stream_ptr(dev))
     return out
+
+
+class _MaskConfidence(torch.autograd.Function):
+    """``mask_confidence`` with its gradient: ``e2emv_apply_mask`` forward, and on the incoming gradient backward."""
+
+    @staticmethod
+    def forward(fctx, confidence, mask):
+        fctx.mask = mask
+        return mask_confidence(confidence.detach(), mask)
+
+    @staticmethod
+    def backward(fctx, g):
+        return mask_confidence(g, fctx.mask), None
 
 
 LOSSES = {None: 0, "huber": 1, "cauchy": 2}  # E2EMV_LOSS_* of include/e2emv.h
@@ -366,6 +382,9 @@ def run_bundle_adjust_2_view(kpts0_norm, kpts1_norm, confidence, init_T021, n_it
                              check_precond_strict=False, loss=None, loss_scale=None, return_summary=False):
     """``run_bundle_adjust_2_view`` (estimate_relative_pose.py:138-144): returns ``(refined T_021 of the valid samples
     [n_valid,4,4], valid_batch [B] bool)`` so that ``pred_T021[valid] = refined`` works as at ``eval_pairs.py:252-255``.
+    Differentiable with respect to ``confidence`` and ``init_T021`` (``_Ba2ViewPose`` / ``e2emv_ba_2view_backward``: the exact reverse of
+    the LM loop; keypoints, lambda and the accept / reject decisions carry no gradient) - with ``loss=None`` only: a robust loss with a
+    graph requested raises ``NotImplementedError`` before any device call.
     The two ``*_strict`` flags only matter for singular systems, which the fp64 Schur solve reports the same way.
     ``loss``: ``None`` (default: the reference's squared loss, ``e2emv_ba_2view`` as always), "huber" or "cauchy"
     (``e2emv_ba_2view_loss``): a residual block is one observation - a match has one in each image -, the LM loop compares
@@ -378,10 +397,20 @@ def run_bundle_adjust_2_view(kpts0_norm, kpts1_norm, confidence, init_T021, n_it
     the start, best cost, number of evaluations that improved, the absolute scale used (0 without a loss); zero for an invalid
     sample."""
     code = _check_loss(loss, loss_scale)
+    graph = torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in (confidence, init_T021))
+    if graph and code:
+        raise NotImplementedError("run_bundle_adjust_2_view: no backward pass through loss={!r}; the gradient exists for the squared "
+                                  "loss only (loss=None) - detach confidence and init_T021 to refine without a graph".format(loss))
     dev = _dev_of(kpts0_norm, kpts1_norm, init_T021)
     ctx = _lib.context(dev)
     B, N = kpts0_norm.shape[:2]
     k0, k1 = _prep(kpts0_norm, dev), _prep(kpts1_norm, dev)
+    if graph:
+        holder = []
+        conf_in, T_in = confidence.reshape(B, -1), init_T021
+        To = _Ba2ViewPose.apply(conf_in, T_in, ctx, dev, k0, k1, int(n_iterations), bool(return_summary), holder)
+        vb, summary = holder
+        return (To[vb], vb, summary) if return_summary else (To[vb], vb)
     cf = _prep(confidence.reshape(B, -1), dev)
     Ti = _prep(init_T021, dev)
     To = torch.empty((B, 4, 4), dtype=torch.float32, device=dev)
@@ -395,3 +424,44 @@ def run_bundle_adjust_2_view(kpts0_norm, kpts1_norm, confidence, init_T021, n_it
             ctx.call("e2emv_ba_2view", *head, _lib.stream_ptr(dev))
     vb = valid.bool()
     return (To[vb], vb, summary) if return_summary else (To[vb], vb)
+
+
+class _Ba2ViewPose(torch.autograd.Function):
+    """T [B,4,4] = two-view BA of every sample (an invalid one keeps its start): ``e2emv_ba_2view`` forward, ``e2emv_ba_2view_backward`` for
+    dLoss/dconfidence and dLoss/dinit_T021.  ``holder`` receives ``valid_batch`` and the summary (or ``None``); the selection of the valid
+    samples stays a torch op on top."""
+
+    @staticmethod
+    def forward(fctx, conf, T_init, ctx, dev, k0, k1, n_iterations, want_summary, holder):
+        B, N = k0.shape[:2]
+        cf, Ti = _prep(conf, dev), _prep(T_init, dev)
+        To = torch.empty((B, 4, 4), dtype=torch.float32, device=dev)
+        valid = torch.empty((B,), dtype=torch.uint8, device=dev)
+        summary = torch.empty((B, 4), dtype=torch.float64, device=dev) if want_summary else None
+        head = (B, N, _lib.ptr(k0), _lib.ptr(k1), _lib.ptr(cf), _lib.ptr(Ti), n_iterations, _lib.ptr(To), _lib.ptr(valid))
+        with torch.cuda.device(dev):
+            if want_summary:
+                ctx.call("e2emv_ba_2view_loss", *head, 0, 0.0, _lib.ptr(summary), _lib.stream_ptr(dev))
+            else:
+                ctx.call("e2emv_ba_2view", *head, _lib.stream_ptr(dev))
+        holder.extend([valid.bool(), summary])
+        fctx.misc = (ctx, dev, n_iterations, conf.shape, conf.dtype, conf.device, T_init.dtype, T_init.device)
+        fctx.save_for_backward(k0, k1, cf, Ti)
+        return To
+
+    @staticmethod
+    def backward(fctx, gT):
+        k0, k1, cf, Ti = fctx.saved_tensors
+        ctx, dev, n_iterations, cshape, cdtype, cdev, tdtype, tdev = fctx.misc
+        B, N = k0.shape[:2]
+        g = _prep(gT, dev)
+        gconf = torch.empty((B, N), dtype=torch.float32, device=dev) if fctx.needs_input_grad[0] else None
+        gTi = torch.empty((B, 4, 4), dtype=torch.float32, device=dev) if fctx.needs_input_grad[1] else None
+        with torch.cuda.device(dev):
+            ctx.call("e2emv_ba_2view_backward", B, N, _lib.ptr(k0), _lib.ptr(k1), _lib.ptr(cf), _lib.ptr(Ti), n_iterations, _lib.ptr(g),
+                     _lib.ptr(gconf), _lib.ptr(gTi), _lib.stream_ptr(dev))
+        if gconf is not None:
+            gconf = gconf.reshape(cshape).to(cdev, cdtype)
+        if gTi is not None:
+            gTi = gTi.to(tdev, tdtype)
+        return gconf, gTi, None, None, None, None, None, None, None

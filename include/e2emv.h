@@ -398,6 +398,19 @@ int e2emv_mv_tuple_ba_tracks_loss(e2emv_ctx* ctx, int B, int T, int N, int Nmax,
 int e2emv_ba_2view_loss(e2emv_ctx* ctx, int B, int N, const float* d_kpts0n, const float* d_kpts1n, const float* d_conf,
                         const float* d_T_init, int n_iterations, float* d_T_out, uint8_t* d_valid, int loss, double loss_scale,
                         double* d_summary, void* stream);
+/* The reverse pass of e2emv_ba_2view (squared loss only): d_gT [B,4,4] = dLoss/d(d_T_out) -> d_gconf [B,N] = dLoss/d(d_conf) and
+ * d_gTinit [B,4,4] = dLoss/d(d_T_init); either output may be NULL.  One workgroup per pair, fp64: the LM loop is run again from the
+ * inputs with a tape in the workspace (the points and the step of every evaluation; (n_iterations + 1) * N * 3 doubles per pair, sized
+ * in size_t - E2EMV_ENOMEM when it cannot be reserved), then the steps k* - 1 .. 0 are reversed exactly, k* = the evaluation whose
+ * pose became d_T_out: the damped Schur system of the step solved with the adjoint as right-hand side, back through the residuals
+ * and Jacobians, the exponential with its |w|^2 >= 1e-4 clamp, the DLT triangulation of the start points and the normalisation of
+ * the weights.  lambda, the accept / reject comparisons and k* depend on comparisons only and carry no gradient; a skipped
+ * (singular) step is the identity.  Rows with d_conf <= 0 get 0; keypoints carry no gradient; row 3 of d_gTinit is 0 (the forward
+ * reads rows 0-2 of d_T_init only).  A pair with d_valid[b] == 0, n_iterations == 0 or no improving evaluation (k* = 0) returned
+ * d_T_init: d_gconf = 0, d_gTinit = rows 0-2 of d_gT.  Shape errors as in e2emv_ba_2view.                                   */
+int e2emv_ba_2view_backward(e2emv_ctx* ctx, int B, int N, const float* d_kpts0n, const float* d_kpts1n, const float* d_conf,
+                            const float* d_T_init, int n_iterations, const float* d_gT, float* d_gconf, float* d_gTinit,
+                            void* stream);
 
 /* The global initialisation on the DEVICE (csrc/mvinit_device.hip): the solver of e2emv_mv_init with the same options,
  * fp64, one wave per problem, the problem and its working set in LDS; a problem's result depends on neither its
