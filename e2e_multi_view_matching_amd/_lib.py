@@ -138,18 +138,22 @@ SIGNATURES = {
                               c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64,
                               c_int64, c_float, c_int, c_void_p]),
     "e2emv_attention": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    "e2emv_attention_v": (c_int, [c_void_p, c_int, c_int, c_int, ctypes.POINTER(c_int), c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "e2emv_set_precision": (c_int, [c_void_p, c_int]),
     "e2emv_get_precision": (c_int, [c_void_p, ctypes.POINTER(c_int)]),
     "e2emv_set_split_min_rows": (c_int, [c_void_p, c_int64]),
     "e2emv_gemm_bf16x3": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "e2emv_attention_bf16x3": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p,
                                        c_void_p]),
+    "e2emv_attention_bf16x3_v": (c_int, [c_void_p, c_int, c_int, c_int, ctypes.POINTER(c_int), c_int, c_int, c_void_p, c_int, c_void_p,
+                                         c_void_p]),
     "e2emv_set_f16x2_kernels": (c_int, [c_void_p, c_int]),
     "e2emv_set_attention_key_split": (c_int, [c_void_p, c_int]),
     "e2emv_gemm_p2": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                               c_void_p]),
     "e2emv_qkv_p2": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "e2emv_attention_p2": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    "e2emv_attention_p2_v": (c_int, [c_void_p, c_int, c_int, c_int, ctypes.POINTER(c_int), c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "e2emv_train_commit": (c_int, [c_void_p, ctypes.POINTER(ModelDesc)]),
     "e2emv_train_update": (c_int, [c_void_p, ctypes.POINTER(ModelDesc), c_int, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(c_void_p),
                            ctypes.POINTER(ctypes.c_int64), ctypes.c_float, c_void_p]),

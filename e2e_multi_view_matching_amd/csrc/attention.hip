@@ -198,13 +198,15 @@ __global__ __launch_bounds__(256, 3) void attention_kernel(AttnParams p) {
         if (lh == 0) { p.part_ml[slot * 2] = m_run; p.part_ml[slot * 2 + 1] = l_tot; }
         return;
     }
+    // padding queries of the last tile get zeros, not the softmax of whatever their q rows hold (attention_merge_kernel leaves them unwritten)
+    const bool pad = q_row >= p.nv[t];
     const float inv = 1.f / l_tot;
     float* op = p.out + ((int64_t)img * p.n_rows + q_row) * p.D + head * HD + 4 * lh;
 #pragma unroll
     for (int gq = 0; gq < 4; ++gq) {
         f32x4 a, c;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) { a[e] = O0[gq * 4 + e] * inv; c[e] = O1[gq * 4 + e] * inv; }
+        for (int e = 0; e < 4; ++e) { a[e] = pad ? 0.f : O0[gq * 4 + e] * inv; c[e] = pad ? 0.f : O1[gq * 4 + e] * inv; }
         *reinterpret_cast<f32x4*>(op + 8 * gq) = a;
         *reinterpret_cast<f32x4*>(op + 32 + 8 * gq) = c;
     }
@@ -292,15 +294,27 @@ int launch_attention(e2emv_ctx* ctx, int B, int T, int n_rows, const int* nv, in
 
 }  // namespace e2emv
 
-extern "C" int e2emv_attention(e2emv_ctx* ctx, int B, int T, int n_rows, int n_valid, int D, int H, const float* d_qkv,
-                               int cross, float* d_out, void* stream) {
-    if (!ctx || !d_qkv || !d_out) return E2EMV_EINVAL;
+static int attention_entry(e2emv_ctx* ctx, int B, int T, int n_rows, const int* nv, int D, int H, const float* d_qkv, int cross,
+                           float* d_out, void* stream) {
     E2EMV_ENTER(ctx, stream);
     e2emv::prof_begin(ctx, e2emv::PS_ATTN, (hipStream_t)stream);
-    if (T < 1 || T > E2EMV_MAX_TUPLE) return E2EMV_EINVAL;
-    int nv[E2EMV_MAX_TUPLE];
-    for (int t = 0; t < E2EMV_MAX_TUPLE; ++t) nv[t] = n_valid;
     int rc = e2emv::launch_attention(ctx, B, T, n_rows, nv, D, H, d_qkv, cross, d_out, (hipStream_t)stream);
     e2emv::prof_end(ctx, (hipStream_t)stream);
     return rc;
+}
+
+extern "C" int e2emv_attention(e2emv_ctx* ctx, int B, int T, int n_rows, int n_valid, int D, int H, const float* d_qkv,
+                               int cross, float* d_out, void* stream) {
+    if (!ctx || !d_qkv || !d_out) return E2EMV_EINVAL;
+    if (T < 1 || T > E2EMV_MAX_TUPLE) return E2EMV_EINVAL;
+    int nv[E2EMV_MAX_TUPLE];
+    for (int t = 0; t < E2EMV_MAX_TUPLE; ++t) nv[t] = n_valid;
+    return attention_entry(ctx, B, T, n_rows, nv, D, H, d_qkv, cross, d_out, stream);
+}
+
+extern "C" int e2emv_attention_v(e2emv_ctx* ctx, int B, int T, int n_rows, const int* n_valid_per_image, int D, int H,
+                                 const float* d_qkv, int cross, float* d_out, void* stream) {
+    if (!ctx || !d_qkv || !d_out || !n_valid_per_image) return E2EMV_EINVAL;
+    if (T < 1 || T > E2EMV_MAX_TUPLE) return E2EMV_EINVAL;
+    return attention_entry(ctx, B, T, n_rows, n_valid_per_image, D, H, d_qkv, cross, d_out, stream);
 }

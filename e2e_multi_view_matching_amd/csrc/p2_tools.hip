@@ -356,12 +356,14 @@ extern "C" int e2emv_qkv_p2(e2emv_ctx* ctx, int n_img, int n_rows, int D, int H,
     return E2EMV_OK;
 }
 
-extern "C" int e2emv_attention_p2(e2emv_ctx* ctx, int B, int T, int n_rows, int n_valid, int D, int H, const float* d_qkv, int flags,
-                                  float* d_out, void* stream) {
-    if (!ctx || !d_qkv || !d_out) return E2EMV_EINVAL;
+// body of e2emv_attention_p2 / e2emv_attention_p2_v: nv = valid keypoints of image t of a tuple, T entries
+static int attention_p2_entry(e2emv_ctx* ctx, int B, int T, int n_rows, const int* nv, int D, int H, const float* d_qkv, int flags,
+                              float* d_out, void* stream) {
     E2EMV_ENTER(ctx, stream);
     if (B <= 0 || T <= 0 || T > E2EMV_MAX_TUPLE || n_rows <= 0 || n_rows % 128 || D != 256 || H != 4)
         return set_err(ctx, E2EMV_ESHAPE, "attention_p2: n_rows %% 128 == 0, D = 256, H = 4");
+    for (int t = 0; t < T; ++t)  // (the launcher checks this too: here before the helper kernels run)
+        if (nv[t] <= 0 || nv[t] > n_rows) return set_err(ctx, E2EMV_ESHAPE, "attention_p2: image %d has %d keypoints (n_rows %d)", t, nv[t], n_rows);
     hipStream_t s = (hipStream_t)stream;
     const int64_t M = (int64_t)B * T * n_rows;
     const size_t szQK = al256((size_t)M * 2 * D * 4), szV = al256((size_t)M * D * 4), szO = al256((size_t)M * D * 4);
@@ -380,8 +382,6 @@ extern "C" int e2emv_attention_p2(e2emv_ctx* ctx, int B, int T, int n_rows, int 
     hipLaunchKernelGGL(qkv_to_planes_kernel, dim3(grid_for(M * (3 * D / 2))), dim3(256), 0, s, d_qkv, M, n_rows, D, H, qs, P2_VS, QK, VT, EQK, EVt);
     E2EMV_HIP(ctx, hipMemsetAsync(OP, 0, (size_t)M * D * 4, s));
     E2EMV_HIP(ctx, hipMemsetAsync(EO, 0, (size_t)(M / 64) * 4 * sizeof(int), s));
-    int nv[E2EMV_MAX_TUPLE];
-    for (int t = 0; t < E2EMV_MAX_TUPLE; ++t) nv[t] = n_valid;
     const int save_nw = ctx->attn_p2_nw;
     if (flags & 2) ctx->attn_p2_nw = 4;
     if (flags & 4) ctx->attn_p2_nw = 8;
@@ -395,4 +395,18 @@ extern "C" int e2emv_attention_p2(e2emv_ctx* ctx, int B, int T, int n_rows, int 
     ctx->attn_p2_nw = save_nw;
     if (rc) return rc;
     return launch_from_planes(ctx, OP, M, D, d_out, D, s, EO);
+}
+
+extern "C" int e2emv_attention_p2(e2emv_ctx* ctx, int B, int T, int n_rows, int n_valid, int D, int H, const float* d_qkv, int flags,
+                                  float* d_out, void* stream) {
+    if (!ctx || !d_qkv || !d_out) return E2EMV_EINVAL;
+    int nv[E2EMV_MAX_TUPLE];
+    for (int t = 0; t < E2EMV_MAX_TUPLE; ++t) nv[t] = n_valid;
+    return attention_p2_entry(ctx, B, T, n_rows, nv, D, H, d_qkv, flags, d_out, stream);
+}
+
+extern "C" int e2emv_attention_p2_v(e2emv_ctx* ctx, int B, int T, int n_rows, const int* n_valid_per_image, int D, int H,
+                                    const float* d_qkv, int flags, float* d_out, void* stream) {
+    if (!ctx || !d_qkv || !d_out || !n_valid_per_image) return E2EMV_EINVAL;
+    return attention_p2_entry(ctx, B, T, n_rows, n_valid_per_image, D, H, d_qkv, flags, d_out, stream);
 }

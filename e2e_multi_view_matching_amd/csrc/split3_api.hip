@@ -77,16 +77,16 @@ extern "C" int e2emv_gemm_bf16x3(e2emv_ctx* ctx, int M, int Nout, int K, const f
     return rc;
 }
 
-extern "C" int e2emv_attention_bf16x3(e2emv_ctx* ctx, int B, int T, int n_rows, int n_valid, int D, int H, const float* d_qkv,
-                                      int cross, float* d_out, void* stream) {
-    if (!ctx || !d_qkv || !d_out) return E2EMV_EINVAL;
+// body of e2emv_attention_bf16x3 / e2emv_attention_bf16x3_v: nv = valid keypoints of image t of a tuple, T entries
+static int attention_bf16x3_entry(e2emv_ctx* ctx, int B, int T, int n_rows, const int* nv, int D, int H, const float* d_qkv, int cross,
+                                  float* d_out, void* stream) {
     E2EMV_ENTER(ctx, stream);
     if (B <= 0 || T <= 0 || n_rows <= 0) return set_err(ctx, E2EMV_ESHAPE, "attention_bf16x3: empty problem");
     hipStream_t s = (hipStream_t)stream;
     const int64_t rows = (int64_t)B * T * n_rows;
     if (T < 1 || T > E2EMV_MAX_TUPLE) return E2EMV_EINVAL;
-    int nv[E2EMV_MAX_TUPLE];
-    for (int t = 0; t < E2EMV_MAX_TUPLE; ++t) nv[t] = n_valid;
+    for (int t = 0; t < T; ++t)  // (the launchers check this too: here before the helper kernels run)
+        if (nv[t] <= 0 || nv[t] > n_rows) return set_err(ctx, E2EMV_ESHAPE, "attention_bf16x3: image %d has %d keypoints (n_rows %d)", t, nv[t], n_rows);
     int rc;
     if (cross & 6) {  // the kernels of the forward pass: fp32 q|k|v in, planes made in the kernel (bit2: fp16 x 2 form)
         E2EMV_HIP(ctx, hipMemsetAsync(d_out, 0, (size_t)rows * D * sizeof(float), s));
@@ -108,4 +108,18 @@ extern "C" int e2emv_attention_bf16x3(e2emv_ctx* ctx, int B, int T, int n_rows, 
     prof_end(ctx, s);
     E2EMV_CHECK_LAUNCH(ctx, "bf16x3 helper kernels");
     return rc;
+}
+
+extern "C" int e2emv_attention_bf16x3(e2emv_ctx* ctx, int B, int T, int n_rows, int n_valid, int D, int H, const float* d_qkv,
+                                      int cross, float* d_out, void* stream) {
+    if (!ctx || !d_qkv || !d_out) return E2EMV_EINVAL;
+    int nv[E2EMV_MAX_TUPLE];
+    for (int t = 0; t < E2EMV_MAX_TUPLE; ++t) nv[t] = n_valid;
+    return attention_bf16x3_entry(ctx, B, T, n_rows, nv, D, H, d_qkv, cross, d_out, stream);
+}
+
+extern "C" int e2emv_attention_bf16x3_v(e2emv_ctx* ctx, int B, int T, int n_rows, const int* n_valid_per_image, int D, int H,
+                                        const float* d_qkv, int cross, float* d_out, void* stream) {
+    if (!ctx || !d_qkv || !d_out || !n_valid_per_image) return E2EMV_EINVAL;
+    return attention_bf16x3_entry(ctx, B, T, n_rows, n_valid_per_image, D, H, d_qkv, cross, d_out, stream);
 }

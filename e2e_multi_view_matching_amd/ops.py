@@ -1,4 +1,7 @@
 """Stand-alone operators of the hot path (thin ctypes wrappers, torch = memory only)."""
+import ctypes
+import operator
+
 import torch
 
 from . import _lib
@@ -59,16 +62,30 @@ def gemm_nt(A, W, bias=None, residual=None, A2=None, scale=1.0, relu=False):
     return C if batched else C[0]
 
 
+def _attention_counts(name, T, n_valid):
+    """(entry point, count argument) of an attention building block: an int is the uniform count of `name`, a sequence of
+    T ints the per-image counts of `name`_v (host array)."""
+    try:
+        return name, operator.index(n_valid)
+    except TypeError:
+        pass
+    nv = [operator.index(n) for n in n_valid]
+    if len(nv) != T:
+        raise ValueError(f"n_valid has {len(nv)} entries for a tuple of {T} images")
+    return name + "_v", (ctypes.c_int * T)(*nv)
+
+
 def attention(qkv, B, T, n_valid, H, cross):
-    """qkv [B*T, n_rows, 3D] head-major -> out [B*T, n_rows, D]."""
+    """qkv [B*T, n_rows, 3D] head-major -> out [B*T, n_rows, D].  n_valid: keypoints per image, an int or (ragged tuples) a
+    sequence of T ints, one per image of a tuple."""
     ctx = _ctx(qkv)
     q = qkv.contiguous().float()
     n_img, n_rows, D3 = q.shape
     D = D3 // 3
     out = torch.zeros((n_img, n_rows, D), dtype=torch.float32, device=q.device)
+    fn, nv = _attention_counts("e2emv_attention", T, n_valid)
     with torch.cuda.device(q.device):
-        ctx.call("e2emv_attention", B, T, n_rows, n_valid, D, H, _lib.ptr(q), 1 if cross else 0, _lib.ptr(out),
-                 _lib.stream_ptr(q.device))
+        ctx.call(fn, B, T, n_rows, nv, D, H, _lib.ptr(q), 1 if cross else 0, _lib.ptr(out), _lib.stream_ptr(q.device))
     return out
 
 
@@ -96,8 +113,9 @@ def attention_bf16x3(qkv, B, T, n_valid, H, cross, kernel="planes"):
     n_img, n_rows, D3 = q.shape
     D = D3 // 3
     out = torch.empty((n_img, n_rows, D), dtype=torch.float32, device=q.device)
+    fn, nv = _attention_counts("e2emv_attention_bf16x3", T, n_valid)
     with torch.cuda.device(q.device):
-        ctx.call("e2emv_attention_bf16x3", B, T, n_rows, n_valid, D, H, _lib.ptr(q),
+        ctx.call(fn, B, T, n_rows, nv, D, H, _lib.ptr(q),
                  (1 if cross else 0) | {"planes": 0, "fused": 2, "f16x2": 6}[kernel], _lib.ptr(out), _lib.stream_ptr(q.device))
     return out
 
@@ -143,6 +161,7 @@ def attention_p2(qkv, B, T, n_valid, H, cross, waves=0, reps=1):
     D = D3 // 3
     out = torch.empty((n_img, n_rows, D), dtype=torch.float32, device=q.device)
     flags = (1 if cross else 0) | {0: 0, 4: 2, 8: 4, 1: 8}[waves] | (int(reps) << 8 if reps > 1 else 0)
+    fn, nv = _attention_counts("e2emv_attention_p2", T, n_valid)
     with torch.cuda.device(q.device):
-        ctx.call("e2emv_attention_p2", B, T, n_rows, n_valid, D, H, _lib.ptr(q), flags, _lib.ptr(out), _lib.stream_ptr(q.device))
+        ctx.call(fn, B, T, n_rows, nv, D, H, _lib.ptr(q), flags, _lib.ptr(out), _lib.stream_ptr(q.device))
     return out

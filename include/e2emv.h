@@ -536,6 +536,12 @@ int e2emv_gemm_nt(e2emv_ctx* ctx, int batch, int M, int Nout, int K, int K1, con
  * n_valid keys/queries per image; output d_out [n_img, n_rows, D].                         */
 int e2emv_attention(e2emv_ctx* ctx, int B, int T, int n_rows, int n_valid, int D, int H, const float* d_qkv,
                     int cross, float* d_out, void* stream);
+/* The same with a keypoint count per image of a tuple, as the matcher forward runs the kernel on images whose counts differ:
+ * n_valid_per_image = HOST array of T ints (1 .. n_rows each; E2EMV_ESHAPE otherwise, E2EMV_EINVAL for NULL or
+ * T > E2EMV_MAX_TUPLE, nothing launched); image g = b*T + t has n_valid_per_image[t] queries and, as a source, that many
+ * keys.  Output rows at and beyond an image's count are written as zeros or not written. */
+int e2emv_attention_v(e2emv_ctx* ctx, int B, int T, int n_rows, const int* n_valid_per_image, int D, int H,
+                      const float* d_qkv, int cross, float* d_out, void* stream);
 
 /* The SuperPoint detector tail alone, on a score map the caller supplies: simple_nms -> threshold -> border removal -> top-k,
  * and (if d_dense is given) the descriptor sampling - the kernels, launch geometry and order e2emv_superpoint_forward runs
@@ -583,6 +589,9 @@ int e2emv_gemm_bf16x3(e2emv_ctx* ctx, int M, int Nout, int K, const float* d_A, 
  * planes made inside the kernel) instead of the pre-split building block, bit2 = its f16x2 form. */
 int e2emv_attention_bf16x3(e2emv_ctx* ctx, int B, int T, int n_rows, int n_valid, int D, int H, const float* d_qkv,
                            int cross, float* d_out, void* stream);
+/* ... with a keypoint count per image of a tuple (HOST array of T ints; the contract of e2emv_attention_v) */
+int e2emv_attention_bf16x3_v(e2emv_ctx* ctx, int B, int T, int n_rows, const int* n_valid_per_image, int D, int H,
+                             const float* d_qkv, int cross, float* d_out, void* stream);
 
 /* ---- f16x2 on plane activations (the default implementation of E2EMV_PRECISION_F16X2) ---------------------------
  * Activations live in HBM as the two fp16 planes of the f16x2 arithmetic (4 bytes per element like fp32, 32-column
@@ -616,6 +625,10 @@ int e2emv_qkv_p2(e2emv_ctx* ctx, int n_img, int n_rows, int D, int H, const floa
  * bits 4..7 reserved (ignored), bits 8.. = timed repetitions. */
 int e2emv_attention_p2(e2emv_ctx* ctx, int B, int T, int n_rows, int n_valid, int D, int H, const float* d_qkv, int flags,
                        float* d_out, void* stream);
+/* ... with a keypoint count per image of a tuple (HOST array of T ints; the contract of e2emv_attention_v, except that
+ * T > E2EMV_MAX_TUPLE is E2EMV_ESHAPE as in e2emv_attention_p2) */
+int e2emv_attention_p2_v(e2emv_ctx* ctx, int B, int T, int n_rows, const int* n_valid_per_image, int D, int H,
+                         const float* d_qkv, int flags, float* d_out, void* stream);
 
 /* The matched descriptors of the LAST e2emv_matcher_forward call on this context (upstream's mdesc0 / mdesc1 = final_proj
  * output, models/superglue.py:269 upstream; with multi_frame_matching off and T > 2: of its last pair): d_out

@@ -167,6 +167,46 @@ def test_images_with_different_keypoint_counts(gpu, precision):
         _compare(out, ref, pairs)
 
 
+@pytest.mark.parametrize("precision", PRECISIONS)
+def test_ragged_tuple3_above_the_256_key_switch(gpu, precision):
+    """A ragged 3-tuple whose cross layers walk sources of 300, 513 and 64 keypoints: above 256 keys the f16x2 forward runs
+    attention_p2w (tile exponents, source-to-source walk) on operands written by the q|k|v GEMM's epilogue - not by the helper
+    kernel of the stand-alone attention tests - with a source that ends exactly on a 64-key tile between two that do not."""
+    from e2e_multi_view_matching_amd import MultiViewMatcher
+    from e2e_multi_view_matching_amd.synthetic import identity_like_state, make_tuples
+    T, counts = 3, (300, 513, 64)
+    torch.manual_seed(5)
+    cfg = {"GNN_layers": ["self", "cross", "cross"], "sinkhorn_iterations": 15, "conf_mlp": True, "multi_frame_matching": True,
+           "tuple_size": T, "mfma_precision": precision}
+    model = identity_like_state(MultiViewMatcher(cfg).eval())
+    data = make_tuples(batch=1, tuple_size=T, n_kpts=max(counts), seed=19)
+    for m, n in enumerate(counts):  # truncate image m to its own keypoint count
+        data[f"keypoints{m}"] = data[f"keypoints{m}"][:, :n].contiguous()
+        data[f"scores{m}"] = data[f"scores{m}"][:, :n].contiguous()
+        data[f"descriptors{m}"] = data[f"descriptors{m}"][:, :, :n].contiguous()
+    ocfg = {k: v for k, v in model.config.items() if k != "mfma_precision"}
+    ocfg["full_output"] = True
+    ref = _ragged3_reference(data, {k: v.clone() for k, v in model.state_dict().items()}, ocfg)
+    model = model.to(gpu)
+    with torch.no_grad():
+        out = model({k: (v.to(gpu) if torch.is_tensor(v) else v) for k, v in data.items()})
+    pairs = [(0, 1), (0, 2), (1, 2)]
+    for i, j in pairs:
+        assert out[f"scores_{i}_{j}"].shape == (1, counts[i] + 1, counts[j] + 1)
+    _compare(out, ref, pairs)
+
+
+_RAGGED3_REF = []
+
+
+def _ragged3_reference(data, sd, ocfg):
+    """The oracle's forward of the case above: seconds on the CPU, the same for every precision - computed once."""
+    from oracle.matcher import matcher_forward
+    if not _RAGGED3_REF:
+        _RAGGED3_REF.append(matcher_forward(data, sd, ocfg))
+    return _RAGGED3_REF[0]
+
+
 def test_maximum_size_2048_keypoints_fp16_multi_frame(gpu):
     """BASELINE configs[4] shape at the library's maximum keypoint count: T = 3 joint matching, 2048 keypoints per image,
     fp16 descriptors, (self, cross, cross) schedule, both arithmetic modes - against the oracle fed the same fp16-rounded
