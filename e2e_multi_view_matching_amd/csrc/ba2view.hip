@@ -27,12 +27,6 @@
 
 namespace e2emv {
 
-__device__ __forceinline__ double wsum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 // block-wide sum of NV doubles (256 threads); result valid in every thread
 template <int NV>
 __device__ __forceinline__ void block_sum_n(double (&v)[NV], double* red /* [4][NV] */) {
@@ -40,7 +34,7 @@ __device__ __forceinline__ void block_sum_n(double (&v)[NV], double* red /* [4][
     __syncthreads();
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
-        const double s = wsum(v[i]);
+        const double s = wave_sum_d(v[i]);
         if (lane == 0) red[wave * NV + i] = s;
     }
     __syncthreads();
@@ -128,53 +122,194 @@ __device__ __forceinline__ double point_terms(const double* Rt, const double* X,
     return rho0 + rho1;
 }
 
-template <int LOSS>
-__global__ __launch_bounds__(256) void ba2view_kernel(BaParams p) {
-    __shared__ double red[4 * 32];
-    __shared__ double sRt[12], sBest[12], sDelta[6];
-    __shared__ double sLam, sBestR;
-    __shared__ double sM6[6][7];
-    __shared__ int sFlags;  // bit0: skip update this iteration
-    __shared__ int sImproved;
-    __shared__ double sStartR;
-    const int b = blockIdx.x, tid = threadIdx.x;
-    const int N = p.N;
-    const float* k0 = p.k0 + (int64_t)b * N * 2;
-    const float* k1 = p.k1 + (int64_t)b * N * 2;
-    const float* cf = p.conf + (int64_t)b * N;
-    const float* Ti = p.Tin + (int64_t)b * 16;
-    double* X = p.X + (int64_t)b * N * 3;
+// The point block of one match, as every pass over the matches forms it: Hpp = Jp^T Jp (symmetric 3x3, packed a00 a01 a02 a11 a12 a22)
+__device__ __forceinline__ void point_hpp(const PointTerms& q, double* Hpp) {
+    int idx = 0;
+#pragma unroll
+    for (int u = 0; u < 3; ++u)
+#pragma unroll
+        for (int v = u; v < 3; ++v)
+            Hpp[idx++] = q.Jp0[0][u] * q.Jp0[0][v] + q.Jp0[1][u] * q.Jp0[1][v] + q.Jp1[0][u] * q.Jp1[0][v] + q.Jp1[1][u] * q.Jp1[1][v];
+}
+// its damping: lambda times the (floored) diagonal under the Jacobi preconditioner, lambda I without
+__device__ __forceinline__ void point_damp(double* Hpp, double lam, bool precond) {
+    Hpp[0] += lam * (precond ? fmax(Hpp[0], 1e-12) : 1.0);
+    Hpp[3] += lam * (precond ? fmax(Hpp[3], 1e-12) : 1.0);
+    Hpp[5] += lam * (precond ? fmax(Hpp[5], 1e-12) : 1.0);
+}
+// gp = -Jp^T r
+__device__ __forceinline__ void point_gp(const PointTerms& q, double* gp) {
+#pragma unroll
+    for (int u = 0; u < 3; ++u) gp[u] = -(q.Jp0[0][u] * q.r0[0] + q.Jp0[1][u] * q.r0[1] + q.Jp1[0][u] * q.r1[0] + q.Jp1[1][u] * q.r1[1]);
+}
+// Hcp = Jc^T Jp1 (6x3): camera 0 is fixed, so only the observation in image 1 couples the pose and the point
+__device__ __forceinline__ void point_hcp(const PointTerms& q, double (&Hcp)[6][3]) {
+#pragma unroll
+    for (int u = 0; u < 6; ++u)
+#pragma unroll
+        for (int v = 0; v < 3; ++v) Hcp[u][v] = q.Jc[0][u] * q.Jp1[0][v] + q.Jc[1][u] * q.Jp1[1][v];
+}
+// one row of W = Hcp Hpp'^-1
+__device__ __forceinline__ void point_w_row(const double* h, const double* inv, double* w) {
+    w[0] = h[0] * inv[0] + h[1] * inv[1] + h[2] * inv[2];
+    w[1] = h[0] * inv[1] + h[1] * inv[3] + h[2] * inv[4];
+    w[2] = h[0] * inv[2] + h[1] * inv[4] + h[2] * inv[5];
+}
+// y = Hpp'^-1 x
+__device__ __forceinline__ void point_solve(const double* inv, const double* x, double* y) {
+    y[0] = inv[0] * x[0] + inv[1] * x[1] + inv[2] * x[2];
+    y[1] = inv[1] * x[0] + inv[3] * x[1] + inv[4] * x[2];
+    y[2] = inv[2] * x[0] + inv[4] * x[1] + inv[5] * x[2];
+}
 
+// [M | rhs] of the reduced camera system in LDS and its solution by Gaussian elimination with partial pivoting (fp64), one lane:
+// a = camera block (21 packed, then 6 right-hand sides), s = what the point blocks take from it.  M6 is in LDS because the pivot
+// search indexes its rows at run time, which in a private array means scratch memory.  A singular system or a non-finite
+// solution returns false: the reference skips the update when LU reports info != 0.
+template <int NA>
+__device__ __forceinline__ bool schur6_solve(double (&M6)[6][7], const double (&a)[NA], const double (&s)[27], double lam, bool precond,
+                                             double* x) {
+    const int dpos[6] = {0, 6, 11, 15, 18, 20};
+    int idx = 0;
+    for (int u = 0; u < 6; ++u)
+        for (int v = u; v < 6; ++v) {
+            const double h = a[idx] - s[idx];
+            M6[u][v] = h;
+            M6[v][u] = h;
+            ++idx;
+        }
+    for (int u = 0; u < 6; ++u) {
+        M6[u][u] += lam * (precond ? fmax(a[dpos[u]], 1e-12) : 1.0);
+        M6[u][6] = a[21 + u] - s[21 + u];
+    }
+    bool ok = true;
+    for (int c = 0; c < 6 && ok; ++c) {
+        int piv = c;
+        for (int r = c + 1; r < 6; ++r)
+            if (fabs(M6[r][c]) > fabs(M6[piv][c])) piv = r;
+        if (!(fabs(M6[piv][c]) > 0.0)) { ok = false; break; }
+        if (piv != c)
+            for (int k = 0; k < 7; ++k) { const double t = M6[c][k]; M6[c][k] = M6[piv][k]; M6[piv][k] = t; }
+        for (int r = c + 1; r < 6; ++r) {
+            const double f = M6[r][c] / M6[c][c];
+            for (int k = c; k < 7; ++k) M6[r][k] -= f * M6[c][k];
+        }
+    }
+    if (ok) {
+        for (int c = 5; c >= 0; --c) {
+            double v = M6[c][6];
+            for (int k = c + 1; k < 6; ++k) v -= M6[c][k] * x[k];
+            x[c] = v / M6[c][c];
+            ok = ok && isfinite(x[c]);
+        }
+    }
+    return ok;
+}
+
+// pytorch3d's se3_exp_map with its 1e-4 clamp of |w|^2 (:193-195): coefficients and matrices of exp(dc), dc = (v, w)
+struct ExpTerms {
+    double th, f1, f2, f3;
+    bool clamped;
+    double Kx[9], K2[9], Rd[9], Vm[9];
+};
+__device__ __forceinline__ void se3_exp_terms(const double* dc, ExpTerms& e) {
+    const double wx = dc[3], wy = dc[4], wz = dc[5];
+    const double n2 = wx * wx + wy * wy + wz * wz;
+    const double th2 = fmax(n2, 1e-4), th = sqrt(th2);
+    e.clamped = n2 < 1e-4;
+    e.th = th;
+    e.f1 = sin(th) / th; e.f2 = (1.0 - cos(th)) / th2; e.f3 = (th - sin(th)) / (th2 * th);
+    const double Kx[9] = {0, -wz, wy, wz, 0, -wx, -wy, wx, 0};
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) e.K2[i * 3 + j] = Kx[i * 3] * Kx[j] + Kx[i * 3 + 1] * Kx[3 + j] + Kx[i * 3 + 2] * Kx[6 + j];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) {
+        const double d = (i % 4 == 0) ? 1.0 : 0.0;
+        e.Kx[i] = Kx[i];
+        e.Rd[i] = d + e.f1 * Kx[i] + e.f2 * e.K2[i];
+        e.Vm[i] = d + e.f2 * Kx[i] + e.f3 * e.K2[i];
+    }
+}
+// extr1 <- exp(dc) extr1: out = exp(dc) Rt (R row-major 0..8, t 9..11)
+__device__ __forceinline__ void se3_exp_left(const double* dc, const double* Rt, double* out) {
+    ExpTerms e;
+    se3_exp_terms(dc, e);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        const double td = e.Vm[i * 3] * dc[0] + e.Vm[i * 3 + 1] * dc[1] + e.Vm[i * 3 + 2] * dc[2];
+#pragma unroll
+        for (int j = 0; j < 3; ++j) out[i * 3 + j] = e.Rd[i * 3] * Rt[j] + e.Rd[i * 3 + 1] * Rt[3 + j] + e.Rd[i * 3 + 2] * Rt[6 + j];
+        out[9 + i] = e.Rd[i * 3] * Rt[9] + e.Rd[i * 3 + 1] * Rt[10] + e.Rd[i * 3 + 2] * Rt[11] + td;
+    }
+}
+
+constexpr int kBaRec = 20;  // doubles per evaluation record: Rt (12), lambda, flags (1 precond, 2 update skipped), dc (6)
+
+// What the loop keeps besides the pose it moves: the forward the best pose and the figures of its summary, the tape k* alone
+template <bool TAPE>
+struct BaLmKept {
+    double best[12], startR;
+    int improved;
+};
+template <>
+struct BaLmKept<true> {
+    int kstar;  // the evaluation whose pose became the result
+};
+// LDS of one pair's workgroup
+template <bool TAPE>
+struct BaLmShared {
+    double red[4 * 32];
+    double Rt[12], delta[6];
+    double lam, bestR;
+    double M6[6][7];
+    int flags;  // bit0: skip update this iteration
+    BaLmKept<TAPE> kept;
+};
+
+// THE Levenberg-Marquardt loop of one pair, for the forward (TAPE = false) and for the replay in front of the reverse pass (TAPE =
+// true): the reverse pass is right only if the replay takes every accept / reject / skip decision as the forward did, and this being
+// one text is what guarantees it.  Evaluation `it` reads its points at Xs + it * xs and writes the moved ones at Xs + (it + 1) * xs:
+// xs = 0 updates them in place (forward), xs = 3 N keeps every X_k (tape), and a point or a step that is not moved is then copied.
+// The tape also writes one record of kBaRec doubles per evaluation to recs.  Returns the validity of the pair (more than 6 positive
+// confidences; nothing else is done without); csum = sum of the confidences, cden = the weights' denominator, la = the loss scale.
+template <int LOSS, bool TAPE>
+__device__ __forceinline__ bool ba2view_lm(BaLmShared<TAPE>& sh, int N, int n_it, const float* k0, const float* k1, const float* cf,
+                                           const float* Ti, double* Xs, size_t xs, double* recs, float lm_inc, float lm_dec,
+                                           double loss_scale, double& csum, double& cden, double& la) {
+    const int tid = threadIdx.x;
     // confidence normalisation (:45-48: each match = two observations) and validity (:132-136)
     double st[2] = {0.0, 0.0};
     for (int i = tid; i < N; i += 256)
         if (cf[i] > 0.f) { st[0] += (double)cf[i]; st[1] += 1.0; }
-    block_sum_n<2>(st, red);
-    const bool valid = st[1] > 6.5;
-    if (tid < 16) p.Tout[(int64_t)b * 16 + tid] = Ti[tid];
-    if (tid == 0) p.valid[b] = valid ? 1 : 0;
-    if (!valid) {
-        if (p.summary && tid < 4) p.summary[(int64_t)b * 4 + tid] = 0.0;
-        return;
-    }
-    const double cden = 0.5 * fmax(2.0 * st[0], 1e-6);
-    const double la = LOSS != kLossNone ? p.loss_scale / cden : 0.0, la2 = la * la;
+    block_sum_n<2>(st, sh.red);
+    csum = st[0];
+    cden = 0.5 * fmax(2.0 * st[0], 1e-6);
+    la = LOSS != kLossNone ? loss_scale / cden : 0.0;
+    const double la2 = la * la;
+    if (!(st[1] > 6.5)) return false;
 
     if (tid < 12) {
         const int r = tid < 9 ? tid / 3 : tid - 9, c = tid < 9 ? tid % 3 : 3;
-        sRt[tid] = (double)Ti[r * 4 + c];   // R row-major (0..8), t (9..11)
-        sBest[tid] = sRt[tid];
+        sh.Rt[tid] = (double)Ti[r * 4 + c];   // R row-major (0..8), t (9..11)
+        if constexpr (!TAPE) sh.kept.best[tid] = sh.Rt[tid];
     }
-    if (tid == 0) { sLam = 0.1; sBestR = 0.0; sFlags = 0; sImproved = 0; sStartR = 0.0; }
+    if (tid == 0) {
+        sh.lam = 0.1; sh.bestR = 0.0; sh.flags = 0;
+        if constexpr (TAPE) { sh.kept.kstar = 0; } else { sh.kept.improved = 0; sh.kept.startR = 0.0; }
+    }
     __syncthreads();
     for (int i = tid; i < N; i += 256)
-        if (cf[i] > 0.f) triangulate_xyz(k0[2 * i], k0[2 * i + 1], k1[2 * i], k1[2 * i + 1], sRt, X + 3 * i);
+        if (cf[i] > 0.f) triangulate_xyz(k0[2 * i], k0[2 * i + 1], k1[2 * i], k1[2 * i + 1], sh.Rt, Xs + 3 * i);
     __syncthreads();
 
-    for (int it = 0; it <= p.n_it; ++it) {
+    for (int it = 0; it <= n_it; ++it) {
+        const double* X = Xs + it * xs;
+        double* Xn = Xs + (it + 1) * xs;  // written only when it < n_it
         double Rt[12];
 #pragma unroll
-        for (int k = 0; k < 12; ++k) Rt[k] = sRt[k];
+        for (int k = 0; k < 12; ++k) Rt[k] = sh.Rt[k];
         // ---- pass 1: residual norm, camera block Hcc (21), gc (6), positivity of the diagonal
         double a[29];
 #pragma unroll
@@ -197,26 +332,30 @@ __global__ __launch_bounds__(256) void ba2view_kernel(BaParams p) {
                 pos = pos && (q.Jp0[0][k] * q.Jp0[0][k] + q.Jp0[1][k] * q.Jp0[1][k] + q.Jp1[0][k] * q.Jp1[0][k] + q.Jp1[1][k] * q.Jp1[1][k]) > 0.0;
             if (!pos) a[28] += 1.0;
         }
-        block_sum_n<29>(a, red);
+        block_sum_n<29>(a, sh.red);
         // ---- LM bookkeeping (:150-161), identical in every thread
         const double rn = a[27];
         if (tid == 0) {
             if (it == 0) {
-                sBestR = rn;
-                sStartR = rn;
-            } else if (rn < sBestR) {
-                sBestR = rn;
-                ++sImproved;
+                sh.bestR = rn;
+                if constexpr (!TAPE) sh.kept.startR = rn;
+            } else if (rn < sh.bestR) {
+                sh.bestR = rn;
+                if constexpr (TAPE) {
+                    sh.kept.kstar = it;
+                } else {
+                    ++sh.kept.improved;
 #pragma unroll
-                for (int k = 0; k < 12; ++k) sBest[k] = Rt[k];
-                sLam = sLam / (double)p.lm_dec;
+                    for (int k = 0; k < 12; ++k) sh.kept.best[k] = Rt[k];
+                }
+                sh.lam = sh.lam / (double)lm_dec;
             } else {
-                sLam = sLam * (double)p.lm_inc;
+                sh.lam = sh.lam * (double)lm_inc;
             }
         }
         __syncthreads();
-        if (it == p.n_it) break;
-        const double lam = sLam;
+        if (it == n_it) break;
+        const double lam = sh.lam;
         // camera diagonal positions in the packed upper triangle: 0, 6, 11, 15, 18, 20
         const int dpos[6] = {0, 6, 11, 15, 18, 20};
         bool precond = a[28] < 0.5;
@@ -232,31 +371,15 @@ __global__ __launch_bounds__(256) void ba2view_kernel(BaParams p) {
             PointTerms q;
             point_terms<LOSS>(Rt, X + 3 * i, k0[2 * i], k0[2 * i + 1], k1[2 * i], k1[2 * i + 1], (double)cf[i] / cden, la, la2, q);
             double Hpp[6], gp[3], Hcp[6][3], inv[6];
-            int idx = 0;
-#pragma unroll
-            for (int u = 0; u < 3; ++u) {
-#pragma unroll
-                for (int v = u; v < 3; ++v)
-                    Hpp[idx++] = q.Jp0[0][u] * q.Jp0[0][v] + q.Jp0[1][u] * q.Jp0[1][v] + q.Jp1[0][u] * q.Jp1[0][v] + q.Jp1[1][u] * q.Jp1[1][v];
-                gp[u] = -(q.Jp0[0][u] * q.r0[0] + q.Jp0[1][u] * q.r0[1] + q.Jp1[0][u] * q.r1[0] + q.Jp1[1][u] * q.r1[1]);
-            }
-#pragma unroll
-            for (int u = 0; u < 6; ++u)
-#pragma unroll
-                for (int v = 0; v < 3; ++v) Hcp[u][v] = q.Jc[0][u] * q.Jp1[0][v] + q.Jc[1][u] * q.Jp1[1][v];
-            Hpp[0] += lam * (precond ? fmax(Hpp[0], 1e-12) : 1.0);
-            Hpp[3] += lam * (precond ? fmax(Hpp[3], 1e-12) : 1.0);
-            Hpp[5] += lam * (precond ? fmax(Hpp[5], 1e-12) : 1.0);
+            point_hpp(q, Hpp);
+            point_gp(q, gp);
+            point_hcp(q, Hcp);
+            point_damp(Hpp, lam, precond);
             if (!inv3_sym(Hpp, inv)) continue;
-            // W = Hcp Hpp'^-1 (6x3)
             double W[6][3];
 #pragma unroll
-            for (int u = 0; u < 6; ++u) {
-                W[u][0] = Hcp[u][0] * inv[0] + Hcp[u][1] * inv[1] + Hcp[u][2] * inv[2];
-                W[u][1] = Hcp[u][0] * inv[1] + Hcp[u][1] * inv[3] + Hcp[u][2] * inv[4];
-                W[u][2] = Hcp[u][0] * inv[2] + Hcp[u][1] * inv[4] + Hcp[u][2] * inv[5];
-            }
-            idx = 0;
+            for (int u = 0; u < 6; ++u) point_w_row(Hcp[u], inv, W[u]);
+            int idx = 0;
 #pragma unroll
             for (int u = 0; u < 6; ++u) {
 #pragma unroll
@@ -264,109 +387,89 @@ __global__ __launch_bounds__(256) void ba2view_kernel(BaParams p) {
                 s[21 + u] += W[u][0] * gp[0] + W[u][1] * gp[1] + W[u][2] * gp[2];
             }
         }
-        block_sum_n<27>(s, red);
+        block_sum_n<27>(s, sh.red);
         if (tid == 0) {
-            // reduced 6x6 system, Gaussian elimination with partial pivoting (fp64); in LDS: the pivot search indexes its rows
-            // at run time, which in a private array means scratch memory
-            double (&M6)[6][7] = sM6;
-            int idx = 0;
-            for (int u = 0; u < 6; ++u)
-                for (int v = u; v < 6; ++v) {
-                    const double h = a[idx] - s[idx];
-                    M6[u][v] = h;
-                    M6[v][u] = h;
-                    ++idx;
-                }
-            for (int u = 0; u < 6; ++u) {
-                M6[u][u] += lam * (precond ? fmax(a[dpos[u]], 1e-12) : 1.0);
-                M6[u][6] = a[21 + u] - s[21 + u];
+            const bool ok = schur6_solve(sh.M6, a, s, lam, precond, sh.delta);
+            sh.flags = ok ? 0 : 1;
+            if constexpr (TAPE) {
+                double* rec = recs + (size_t)it * kBaRec;
+#pragma unroll
+                for (int k = 0; k < 12; ++k) rec[k] = Rt[k];
+                rec[12] = lam;
+                rec[13] = (double)((precond ? 1 : 0) | (ok ? 0 : 2));
+#pragma unroll
+                for (int k = 0; k < 6; ++k) rec[14 + k] = ok ? sh.delta[k] : 0.0;
             }
-            bool ok = true;
-            for (int c = 0; c < 6 && ok; ++c) {
-                int piv = c;
-                for (int r = c + 1; r < 6; ++r)
-                    if (fabs(M6[r][c]) > fabs(M6[piv][c])) piv = r;
-                if (!(fabs(M6[piv][c]) > 0.0)) { ok = false; break; }
-                if (piv != c)
-                    for (int k = 0; k < 7; ++k) { const double t = M6[c][k]; M6[c][k] = M6[piv][k]; M6[piv][k] = t; }
-                for (int r = c + 1; r < 6; ++r) {
-                    const double f = M6[r][c] / M6[c][c];
-                    for (int k = c; k < 7; ++k) M6[r][k] -= f * M6[c][k];
-                }
-            }
-            if (ok) {
-                for (int c = 5; c >= 0; --c) {
-                    double v = M6[c][6];
-                    for (int k = c + 1; k < 6; ++k) v -= M6[c][k] * sDelta[k];
-                    sDelta[c] = v / M6[c][c];
-                    ok = ok && isfinite(sDelta[c]);
-                }
-            }
-            sFlags = ok ? 0 : 1;
         }
         __syncthreads();
-        if (sFlags & 1) continue;  // singular system: the reference skips the update when LU reports info != 0
+        if (sh.flags & 1) {  // singular system: the update is skipped, the next evaluation sees the same points
+            if (Xn != X) {
+                for (int i = tid; i < N; i += 256)
+                    if (cf[i] > 0.f) { Xn[3 * i] = X[3 * i]; Xn[3 * i + 1] = X[3 * i + 1]; Xn[3 * i + 2] = X[3 * i + 2]; }
+                __syncthreads();
+            }
+            continue;
+        }
         double dc[6];
 #pragma unroll
-        for (int k = 0; k < 6; ++k) dc[k] = sDelta[k];
+        for (int k = 0; k < 6; ++k) dc[k] = sh.delta[k];
         // ---- pass 3: back-substitute the points with the OLD pose, then move the pose
         for (int i = tid; i < N; i += 256) {
             if (!(cf[i] > 0.f)) continue;
             PointTerms q;
             point_terms<LOSS>(Rt, X + 3 * i, k0[2 * i], k0[2 * i + 1], k1[2 * i], k1[2 * i + 1], (double)cf[i] / cden, la, la2, q);
-            double Hpp[6], rhs[3], inv[6];
-            int idx = 0;
+            double Hpp[6], rhs[3], Hcp[6][3], inv[6], d[3];
+            point_hpp(q, Hpp);
+            point_gp(q, rhs);
+            point_hcp(q, Hcp);
 #pragma unroll
-            for (int u = 0; u < 3; ++u) {
+            for (int u = 0; u < 3; ++u)
 #pragma unroll
-                for (int v = u; v < 3; ++v)
-                    Hpp[idx++] = q.Jp0[0][u] * q.Jp0[0][v] + q.Jp0[1][u] * q.Jp0[1][v] + q.Jp1[0][u] * q.Jp1[0][v] + q.Jp1[1][u] * q.Jp1[1][v];
-                double g = -(q.Jp0[0][u] * q.r0[0] + q.Jp0[1][u] * q.r0[1] + q.Jp1[0][u] * q.r1[0] + q.Jp1[1][u] * q.r1[1]);
-#pragma unroll
-                for (int w = 0; w < 6; ++w) g -= (q.Jc[0][w] * q.Jp1[0][u] + q.Jc[1][w] * q.Jp1[1][u]) * dc[w];
-                rhs[u] = g;
+                for (int w = 0; w < 6; ++w) rhs[u] -= Hcp[w][u] * dc[w];
+            point_damp(Hpp, lam, precond);
+            if (!inv3_sym(Hpp, inv)) {  // this point stays where it is
+                if (Xn != X) { Xn[3 * i] = X[3 * i]; Xn[3 * i + 1] = X[3 * i + 1]; Xn[3 * i + 2] = X[3 * i + 2]; }
+                continue;
             }
-            Hpp[0] += lam * (precond ? fmax(Hpp[0], 1e-12) : 1.0);
-            Hpp[3] += lam * (precond ? fmax(Hpp[3], 1e-12) : 1.0);
-            Hpp[5] += lam * (precond ? fmax(Hpp[5], 1e-12) : 1.0);
-            if (!inv3_sym(Hpp, inv)) continue;
-            X[3 * i] += inv[0] * rhs[0] + inv[1] * rhs[1] + inv[2] * rhs[2];
-            X[3 * i + 1] += inv[1] * rhs[0] + inv[3] * rhs[1] + inv[4] * rhs[2];
-            X[3 * i + 2] += inv[2] * rhs[0] + inv[4] * rhs[1] + inv[5] * rhs[2];
+            point_solve(inv, rhs, d);
+            Xn[3 * i] = X[3 * i] + d[0];
+            Xn[3 * i + 1] = X[3 * i + 1] + d[1];
+            Xn[3 * i + 2] = X[3 * i + 2] + d[2];
         }
         __syncthreads();
         if (tid == 0) {
-            // extr1 <- exp(dc) extr1, dc = (v, w): pytorch3d se3_exp_map with its 1e-4 clamp of |w|^2 (:193-195)
-            const double wx = dc[3], wy = dc[4], wz = dc[5];
-            const double th2 = fmax(wx * wx + wy * wy + wz * wz, 1e-4), th = sqrt(th2);
-            const double f1 = sin(th) / th, f2 = (1.0 - cos(th)) / th2, f3 = (th - sin(th)) / (th2 * th);
-            const double Kx[9] = {0, -wz, wy, wz, 0, -wx, -wy, wx, 0};
-            double K2[9], Rd[9], Vm[9];
-            for (int i = 0; i < 3; ++i)
-                for (int j = 0; j < 3; ++j) K2[i * 3 + j] = Kx[i * 3] * Kx[j] + Kx[i * 3 + 1] * Kx[3 + j] + Kx[i * 3 + 2] * Kx[6 + j];
-            for (int i = 0; i < 9; ++i) {
-                const double e = (i % 4 == 0) ? 1.0 : 0.0;
-                Rd[i] = e + f1 * Kx[i] + f2 * K2[i];
-                Vm[i] = e + f2 * Kx[i] + f3 * K2[i];
-            }
-            double td[3], Rn[9], tn[3];
-            for (int i = 0; i < 3; ++i) td[i] = Vm[i * 3] * dc[0] + Vm[i * 3 + 1] * dc[1] + Vm[i * 3 + 2] * dc[2];
-            for (int i = 0; i < 3; ++i) {
-                for (int j = 0; j < 3; ++j) Rn[i * 3 + j] = Rd[i * 3] * Rt[j] + Rd[i * 3 + 1] * Rt[3 + j] + Rd[i * 3 + 2] * Rt[6 + j];
-                tn[i] = Rd[i * 3] * Rt[9] + Rd[i * 3 + 1] * Rt[10] + Rd[i * 3 + 2] * Rt[11] + td[i];
-            }
-            for (int i = 0; i < 9; ++i) sRt[i] = Rn[i];
-            for (int i = 0; i < 3; ++i) sRt[9 + i] = tn[i];
+            double Rn[12];
+            se3_exp_left(dc, Rt, Rn);
+#pragma unroll
+            for (int i = 0; i < 12; ++i) sh.Rt[i] = Rn[i];
         }
         __syncthreads();
     }
+    return true;
+}
+
+template <int LOSS>
+__global__ __launch_bounds__(256) void ba2view_kernel(BaParams p) {
+    __shared__ BaLmShared<false> sh;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int N = p.N;
+    const float* Ti = p.Tin + (int64_t)b * 16;
+    if (tid < 16) p.Tout[(int64_t)b * 16 + tid] = Ti[tid];
+    double csum, cden, la;
+    const bool valid = ba2view_lm<LOSS, false>(sh, N, p.n_it, p.k0 + (int64_t)b * N * 2, p.k1 + (int64_t)b * N * 2, p.conf + (int64_t)b * N, Ti,
+                                               p.X + (int64_t)b * N * 3, 0, nullptr, p.lm_inc, p.lm_dec, p.loss_scale, csum, cden, la);
+    if (tid == 0) p.valid[b] = valid ? 1 : 0;
+    if (!valid) {
+        if (p.summary && tid < 4) p.summary[(int64_t)b * 4 + tid] = 0.0;
+        return;
+    }
     if (tid < 12) {
         const int r = tid < 9 ? tid / 3 : tid - 9, c = tid < 9 ? tid % 3 : 3;
-        p.Tout[(int64_t)b * 16 + r * 4 + c] = (float)sBest[tid];
+        p.Tout[(int64_t)b * 16 + r * 4 + c] = (float)sh.kept.best[tid];
     }
     if (p.summary && tid == 0) {
         double* sm = p.summary + (int64_t)b * 4;
-        sm[0] = sStartR; sm[1] = sBestR; sm[2] = (double)sImproved; sm[3] = la;
+        sm[0] = sh.kept.startR; sm[1] = sh.bestR; sm[2] = (double)sh.kept.improved; sm[3] = la;
     }
 }
 
@@ -416,9 +519,9 @@ extern "C" int e2emv_ba_2view_loss(e2emv_ctx* ctx, int B, int N, const float* d_
 
 // ---- backward pass of ba2view_kernel<kLossNone>: dLoss/dconf and dLoss/dT_init from dLoss/dT_out (e2emv_ba_2view_backward) ----
 //
-// Phase 1 replays the forward loop from the inputs - the statements of ba2view_kernel, on the same helpers, so that every accept /
-// reject decision is the forward's - and keeps a tape in the workspace: X_k of every evaluation, and per evaluation a record
-// (Rt_k, lambda_k, precond, skipped, dc_k).  k* = the evaluation whose pose became the result.  Phase 2 walks k = k*-1 .. 0 with the
+// Phase 1 replays the forward loop from the inputs - ba2view_lm<kLossNone, true>, the very function the forward kernel runs, so that
+// every accept / reject decision is the forward's - and keeps a tape in the workspace: X_k of every evaluation, and per evaluation a
+// record (Rt_k, lambda_k, precond, skipped, dc_k).  k* = the evaluation whose pose became the result.  Phase 2 walks k = k*-1 .. 0 with the
 // adjoint state (Rt_bar in LDS, X_bar in the workspace).  One LM step solves M d = b, M = A + lambda D, A = J^T J, b = -J^T r, D =
 // diag(max(A_jj, 1e-12)) under precond, else I.  With d_bar = (adjoint of exp(dc) Rt_k w.r.t. dc, X_bar_{k+1}) and M w = d_bar -
 // the forward's Schur complement with another right-hand side -
@@ -426,11 +529,9 @@ extern "C" int e2emv_ba_2view_loss(e2emv_ctx* ctx, int B, int N, const float* d_
 // per match (two observations, 6 camera + 3 point columns), taken back through point_terms to X_bar_k, Rt_bar_k and the weight's
 // adjoint.  After k = 0: the triangulation (first-order perturbation of the null vector of G = A^T A from the Jacobi eigenpairs,
 // then 1 / (X3 + 1e-8)) and the normalisation of the weights.  lambda, the comparisons and k* are piecewise constant.
-// The forward's text stays as it is (its results are pinned bit for bit), so its 6x6 elimination and its exponential are stated a
-// second time below, as functions.
+// Phase 2 forms the point blocks with the loop's helpers (point_hpp, point_damp, point_hcp, point_w_row, point_solve) and solves its
+// 6x6 system with the loop's schur6_solve.
 namespace e2emv {
-
-constexpr int kBaRec = 20;  // doubles per evaluation record: Rt (12), lambda, flags (1 precond, 2 update skipped), dc (6)
 
 struct BaBwdParams {
     int B, N, n_it;
@@ -442,85 +543,6 @@ struct BaBwdParams {
     float lm_inc, lm_dec;
 };
 
-// [M | rhs] of the reduced camera system in LDS and its solution by Gaussian elimination with partial pivoting, one lane: a = camera
-// block (21 packed, then 6 right-hand sides), s = what the point blocks take from it.  The statements of ba2view_kernel.
-__device__ __forceinline__ bool schur6_solve(double (&M6)[6][7], const double (&a)[27], const double (&s)[27], double lam, bool precond,
-                                             double* x) {
-    const int dpos[6] = {0, 6, 11, 15, 18, 20};
-    int idx = 0;
-    for (int u = 0; u < 6; ++u)
-        for (int v = u; v < 6; ++v) {
-            const double h = a[idx] - s[idx];
-            M6[u][v] = h;
-            M6[v][u] = h;
-            ++idx;
-        }
-    for (int u = 0; u < 6; ++u) {
-        M6[u][u] += lam * (precond ? fmax(a[dpos[u]], 1e-12) : 1.0);
-        M6[u][6] = a[21 + u] - s[21 + u];
-    }
-    bool ok = true;
-    for (int c = 0; c < 6 && ok; ++c) {
-        int piv = c;
-        for (int r = c + 1; r < 6; ++r)
-            if (fabs(M6[r][c]) > fabs(M6[piv][c])) piv = r;
-        if (!(fabs(M6[piv][c]) > 0.0)) { ok = false; break; }
-        if (piv != c)
-            for (int k = 0; k < 7; ++k) { const double t = M6[c][k]; M6[c][k] = M6[piv][k]; M6[piv][k] = t; }
-        for (int r = c + 1; r < 6; ++r) {
-            const double f = M6[r][c] / M6[c][c];
-            for (int k = c; k < 7; ++k) M6[r][k] -= f * M6[c][k];
-        }
-    }
-    if (ok) {
-        for (int c = 5; c >= 0; --c) {
-            double v = M6[c][6];
-            for (int k = c + 1; k < 6; ++k) v -= M6[c][k] * x[k];
-            x[c] = v / M6[c][c];
-            ok = ok && isfinite(x[c]);
-        }
-    }
-    return ok;
-}
-
-// pytorch3d's se3_exp_map with its 1e-4 clamp of |w|^2: coefficients and matrices of exp(dc), dc = (v, w)
-struct ExpTerms {
-    double th, f1, f2, f3;
-    bool clamped;
-    double Kx[9], K2[9], Rd[9], Vm[9];
-};
-__device__ __forceinline__ void se3_exp_terms(const double* dc, ExpTerms& e) {
-    const double wx = dc[3], wy = dc[4], wz = dc[5];
-    const double n2 = wx * wx + wy * wy + wz * wz;
-    const double th2 = fmax(n2, 1e-4), th = sqrt(th2);
-    e.clamped = n2 < 1e-4;
-    e.th = th;
-    e.f1 = sin(th) / th; e.f2 = (1.0 - cos(th)) / th2; e.f3 = (th - sin(th)) / (th2 * th);
-    const double Kx[9] = {0, -wz, wy, wz, 0, -wx, -wy, wx, 0};
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) e.K2[i * 3 + j] = Kx[i * 3] * Kx[j] + Kx[i * 3 + 1] * Kx[3 + j] + Kx[i * 3 + 2] * Kx[6 + j];
-#pragma unroll
-    for (int i = 0; i < 9; ++i) {
-        const double d = (i % 4 == 0) ? 1.0 : 0.0;
-        e.Kx[i] = Kx[i];
-        e.Rd[i] = d + e.f1 * Kx[i] + e.f2 * e.K2[i];
-        e.Vm[i] = d + e.f2 * Kx[i] + e.f3 * e.K2[i];
-    }
-}
-// Rt <- exp(dc) Rt (R row-major 0..8, t 9..11); the expressions of ba2view_kernel
-__device__ __forceinline__ void se3_exp_left(const double* dc, const double* Rt, double* out) {
-    ExpTerms e;
-    se3_exp_terms(dc, e);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        const double td = e.Vm[i * 3] * dc[0] + e.Vm[i * 3 + 1] * dc[1] + e.Vm[i * 3 + 2] * dc[2];
-#pragma unroll
-        for (int j = 0; j < 3; ++j) out[i * 3 + j] = e.Rd[i * 3] * Rt[j] + e.Rd[i * 3 + 1] * Rt[3 + j] + e.Rd[i * 3 + 2] * Rt[6 + j];
-        out[9 + i] = e.Rd[i * 3] * Rt[9] + e.Rd[i * 3 + 1] * Rt[10] + e.Rd[i * 3 + 2] * Rt[11] + td;
-    }
-}
 // adjoint of se3_exp_left: nb = adjoint of the new pose -> dcb [6], and tb [12] = the part of the old pose's adjoint that comes
 // through the product.  In the clamped branch f1, f2, f3 are constants: the derivative flows through hat(w) only.
 __device__ __forceinline__ void se3_exp_left_reverse(const double* dc, const double* Rt, const double* nb, double* dcb, double* tb) {
@@ -684,11 +706,9 @@ __device__ __forceinline__ void triangulate_reverse(double x1, double y1, double
 }
 
 __global__ __launch_bounds__(256) void ba2view_backward_kernel(BaBwdParams p) {
-    __shared__ double red[4 * 32];
-    __shared__ double sRt[12], sDelta[6], sRtBar[12], sDcBar[6];
-    __shared__ double sLam, sBestR;
-    __shared__ double sM6[6][7];
-    __shared__ int sFlags, sKstar;
+    __shared__ BaLmShared<true> sh;
+    __shared__ double sRtBar[12], sDcBar[6];
+    double* const red = sh.red;
     const int b = blockIdx.x, tid = threadIdx.x;
     const int N = p.N;
     const float* k0 = p.k0 + (int64_t)b * N * 2;
@@ -702,175 +722,10 @@ __global__ __launch_bounds__(256) void ba2view_backward_kernel(BaBwdParams p) {
     double* recs = cbar + N;
     const size_t xs = (size_t)N * 3;
 
-    double st[2] = {0.0, 0.0};
-    for (int i = tid; i < N; i += 256)
-        if (cf[i] > 0.f) { st[0] += (double)cf[i]; st[1] += 1.0; }
-    block_sum_n<2>(st, red);
-    const bool valid = st[1] > 6.5;
-    const double cden = 0.5 * fmax(2.0 * st[0], 1e-6);
-
     // ---- phase 1: the forward loop again, with the tape
-    if (valid) {
-        if (tid < 12) {
-            const int r = tid < 9 ? tid / 3 : tid - 9, c = tid < 9 ? tid % 3 : 3;
-            sRt[tid] = (double)Ti[r * 4 + c];
-        }
-        if (tid == 0) { sLam = 0.1; sBestR = 0.0; sFlags = 0; sKstar = 0; }
-        __syncthreads();
-        for (int i = tid; i < N; i += 256)
-            if (cf[i] > 0.f) triangulate_xyz(k0[2 * i], k0[2 * i + 1], k1[2 * i], k1[2 * i + 1], sRt, tape + 3 * i);
-        __syncthreads();
-    }
-    for (int it = 0; valid && it <= p.n_it; ++it) {
-        const double* X = tape + it * xs;
-        double* Xn = tape + (it + 1) * xs;  // written only when it < n_it
-        double Rt[12];
-#pragma unroll
-        for (int k = 0; k < 12; ++k) Rt[k] = sRt[k];
-        double a[29];
-#pragma unroll
-        for (int k = 0; k < 29; ++k) a[k] = 0.0;
-        for (int i = tid; i < N; i += 256) {
-            if (!(cf[i] > 0.f)) continue;
-            PointTerms q;
-            a[27] += point_terms<kLossNone>(Rt, X + 3 * i, k0[2 * i], k0[2 * i + 1], k1[2 * i], k1[2 * i + 1], (double)cf[i] / cden, 0.0, 0.0, q);
-            int idx = 0;
-#pragma unroll
-            for (int u = 0; u < 6; ++u) {
-#pragma unroll
-                for (int v = u; v < 6; ++v) a[idx++] += q.Jc[0][u] * q.Jc[0][v] + q.Jc[1][u] * q.Jc[1][v];
-                a[21 + u] -= q.Jc[0][u] * q.r1[0] + q.Jc[1][u] * q.r1[1];
-            }
-            bool pos = true;
-#pragma unroll
-            for (int k = 0; k < 3; ++k)
-                pos = pos && (q.Jp0[0][k] * q.Jp0[0][k] + q.Jp0[1][k] * q.Jp0[1][k] + q.Jp1[0][k] * q.Jp1[0][k] + q.Jp1[1][k] * q.Jp1[1][k]) > 0.0;
-            if (!pos) a[28] += 1.0;
-        }
-        block_sum_n<29>(a, red);
-        const double rn = a[27];
-        if (tid == 0) {
-            if (it == 0) {
-                sBestR = rn;
-            } else if (rn < sBestR) {
-                sBestR = rn;
-                sKstar = it;
-                sLam = sLam / (double)p.lm_dec;
-            } else {
-                sLam = sLam * (double)p.lm_inc;
-            }
-        }
-        __syncthreads();
-        if (it == p.n_it) break;
-        const double lam = sLam;
-        const int dpos[6] = {0, 6, 11, 15, 18, 20};
-        bool precond = a[28] < 0.5;
-#pragma unroll
-        for (int u = 0; u < 6; ++u) precond = precond && a[dpos[u]] > 0.0;
-
-        double s[27];
-#pragma unroll
-        for (int k = 0; k < 27; ++k) s[k] = 0.0;
-        for (int i = tid; i < N; i += 256) {
-            if (!(cf[i] > 0.f)) continue;
-            PointTerms q;
-            point_terms<kLossNone>(Rt, X + 3 * i, k0[2 * i], k0[2 * i + 1], k1[2 * i], k1[2 * i + 1], (double)cf[i] / cden, 0.0, 0.0, q);
-            double Hpp[6], gp[3], Hcp[6][3], inv[6];
-            int idx = 0;
-#pragma unroll
-            for (int u = 0; u < 3; ++u) {
-#pragma unroll
-                for (int v = u; v < 3; ++v)
-                    Hpp[idx++] = q.Jp0[0][u] * q.Jp0[0][v] + q.Jp0[1][u] * q.Jp0[1][v] + q.Jp1[0][u] * q.Jp1[0][v] + q.Jp1[1][u] * q.Jp1[1][v];
-                gp[u] = -(q.Jp0[0][u] * q.r0[0] + q.Jp0[1][u] * q.r0[1] + q.Jp1[0][u] * q.r1[0] + q.Jp1[1][u] * q.r1[1]);
-            }
-#pragma unroll
-            for (int u = 0; u < 6; ++u)
-#pragma unroll
-                for (int v = 0; v < 3; ++v) Hcp[u][v] = q.Jc[0][u] * q.Jp1[0][v] + q.Jc[1][u] * q.Jp1[1][v];
-            Hpp[0] += lam * (precond ? fmax(Hpp[0], 1e-12) : 1.0);
-            Hpp[3] += lam * (precond ? fmax(Hpp[3], 1e-12) : 1.0);
-            Hpp[5] += lam * (precond ? fmax(Hpp[5], 1e-12) : 1.0);
-            if (!inv3_sym(Hpp, inv)) continue;
-            double W[6][3];
-#pragma unroll
-            for (int u = 0; u < 6; ++u) {
-                W[u][0] = Hcp[u][0] * inv[0] + Hcp[u][1] * inv[1] + Hcp[u][2] * inv[2];
-                W[u][1] = Hcp[u][0] * inv[1] + Hcp[u][1] * inv[3] + Hcp[u][2] * inv[4];
-                W[u][2] = Hcp[u][0] * inv[2] + Hcp[u][1] * inv[4] + Hcp[u][2] * inv[5];
-            }
-            idx = 0;
-#pragma unroll
-            for (int u = 0; u < 6; ++u) {
-#pragma unroll
-                for (int v = u; v < 6; ++v) s[idx++] += W[u][0] * Hcp[v][0] + W[u][1] * Hcp[v][1] + W[u][2] * Hcp[v][2];
-                s[21 + u] += W[u][0] * gp[0] + W[u][1] * gp[1] + W[u][2] * gp[2];
-            }
-        }
-        block_sum_n<27>(s, red);
-        if (tid == 0) {
-            double a27[27];
-#pragma unroll
-            for (int k = 0; k < 27; ++k) a27[k] = a[k];
-            const bool ok = schur6_solve(sM6, a27, s, lam, precond, sDelta);
-            sFlags = ok ? 0 : 1;
-            double* rec = recs + (size_t)it * kBaRec;
-#pragma unroll
-            for (int k = 0; k < 12; ++k) rec[k] = Rt[k];
-            rec[12] = lam;
-            rec[13] = (double)((precond ? 1 : 0) | (ok ? 0 : 2));
-#pragma unroll
-            for (int k = 0; k < 6; ++k) rec[14 + k] = ok ? sDelta[k] : 0.0;
-        }
-        __syncthreads();
-        if (sFlags & 1) {  // the update is skipped: the next evaluation sees the same points
-            for (int i = tid; i < N; i += 256)
-                if (cf[i] > 0.f) { Xn[3 * i] = X[3 * i]; Xn[3 * i + 1] = X[3 * i + 1]; Xn[3 * i + 2] = X[3 * i + 2]; }
-            __syncthreads();
-            continue;
-        }
-        double dc[6];
-#pragma unroll
-        for (int k = 0; k < 6; ++k) dc[k] = sDelta[k];
-        for (int i = tid; i < N; i += 256) {
-            if (!(cf[i] > 0.f)) continue;
-            PointTerms q;
-            point_terms<kLossNone>(Rt, X + 3 * i, k0[2 * i], k0[2 * i + 1], k1[2 * i], k1[2 * i + 1], (double)cf[i] / cden, 0.0, 0.0, q);
-            double Hpp[6], rhs[3], inv[6];
-            int idx = 0;
-#pragma unroll
-            for (int u = 0; u < 3; ++u) {
-#pragma unroll
-                for (int v = u; v < 3; ++v)
-                    Hpp[idx++] = q.Jp0[0][u] * q.Jp0[0][v] + q.Jp0[1][u] * q.Jp0[1][v] + q.Jp1[0][u] * q.Jp1[0][v] + q.Jp1[1][u] * q.Jp1[1][v];
-                double g = -(q.Jp0[0][u] * q.r0[0] + q.Jp0[1][u] * q.r0[1] + q.Jp1[0][u] * q.r1[0] + q.Jp1[1][u] * q.r1[1]);
-#pragma unroll
-                for (int w = 0; w < 6; ++w) g -= (q.Jc[0][w] * q.Jp1[0][u] + q.Jc[1][w] * q.Jp1[1][u]) * dc[w];
-                rhs[u] = g;
-            }
-            Hpp[0] += lam * (precond ? fmax(Hpp[0], 1e-12) : 1.0);
-            Hpp[3] += lam * (precond ? fmax(Hpp[3], 1e-12) : 1.0);
-            Hpp[5] += lam * (precond ? fmax(Hpp[5], 1e-12) : 1.0);
-            double d0 = 0.0, d1 = 0.0, d2 = 0.0;
-            if (inv3_sym(Hpp, inv)) {
-                d0 = inv[0] * rhs[0] + inv[1] * rhs[1] + inv[2] * rhs[2];
-                d1 = inv[1] * rhs[0] + inv[3] * rhs[1] + inv[4] * rhs[2];
-                d2 = inv[2] * rhs[0] + inv[4] * rhs[1] + inv[5] * rhs[2];
-            }
-            Xn[3 * i] = X[3 * i] + d0;
-            Xn[3 * i + 1] = X[3 * i + 1] + d1;
-            Xn[3 * i + 2] = X[3 * i + 2] + d2;
-        }
-        __syncthreads();
-        if (tid == 0) {
-            double Rn[12];
-            se3_exp_left(dc, Rt, Rn);
-#pragma unroll
-            for (int i = 0; i < 12; ++i) sRt[i] = Rn[i];
-        }
-        __syncthreads();
-    }
-    const int kstar = valid ? sKstar : 0;
+    double csum, cden, la;
+    const bool valid = ba2view_lm<kLossNone, true>(sh, N, p.n_it, k0, k1, cf, Ti, tape, xs, recs, p.lm_inc, p.lm_dec, 0.0, csum, cden, la);
+    const int kstar = valid ? sh.kept.kstar : 0;
 
     // ---- phase 2: the steps k* - 1 .. 0 in reverse
     if (tid < 12) {
@@ -918,30 +773,19 @@ __global__ __launch_bounds__(256) void ba2view_backward_kernel(BaBwdParams p) {
 #pragma unroll
                 for (int v = u; v < 6; ++v) a[idx++] += q.Jc[0][u] * q.Jc[0][v] + q.Jc[1][u] * q.Jc[1][v];
             double Hpp[6], Hcp[6][3], inv[6];
-            idx = 0;
-#pragma unroll
-            for (int u = 0; u < 3; ++u)
-#pragma unroll
-                for (int v = u; v < 3; ++v)
-                    Hpp[idx++] = q.Jp0[0][u] * q.Jp0[0][v] + q.Jp0[1][u] * q.Jp0[1][v] + q.Jp1[0][u] * q.Jp1[0][v] + q.Jp1[1][u] * q.Jp1[1][v];
-#pragma unroll
-            for (int u = 0; u < 6; ++u)
-#pragma unroll
-                for (int v = 0; v < 3; ++v) Hcp[u][v] = q.Jc[0][u] * q.Jp1[0][v] + q.Jc[1][u] * q.Jp1[1][v];
-            Hpp[0] += lam * (precond ? fmax(Hpp[0], 1e-12) : 1.0);
-            Hpp[3] += lam * (precond ? fmax(Hpp[3], 1e-12) : 1.0);
-            Hpp[5] += lam * (precond ? fmax(Hpp[5], 1e-12) : 1.0);
+            point_hpp(q, Hpp);
+            point_hcp(q, Hcp);
+            point_damp(Hpp, lam, precond);
             if (!inv3_sym(Hpp, inv)) continue;
             const double xb0 = Xbar[3 * i], xb1 = Xbar[3 * i + 1], xb2 = Xbar[3 * i + 2];
             idx = 0;
 #pragma unroll
             for (int u = 0; u < 6; ++u) {
-                const double w0 = Hcp[u][0] * inv[0] + Hcp[u][1] * inv[1] + Hcp[u][2] * inv[2];
-                const double w1 = Hcp[u][0] * inv[1] + Hcp[u][1] * inv[3] + Hcp[u][2] * inv[4];
-                const double w2 = Hcp[u][0] * inv[2] + Hcp[u][1] * inv[4] + Hcp[u][2] * inv[5];
+                double w[3];
+                point_w_row(Hcp[u], inv, w);
 #pragma unroll
-                for (int v = u; v < 6; ++v) s[idx++] += w0 * Hcp[v][0] + w1 * Hcp[v][1] + w2 * Hcp[v][2];
-                s[21 + u] += w0 * xb0 + w1 * xb1 + w2 * xb2;
+                for (int v = u; v < 6; ++v) s[idx++] += w[0] * Hcp[v][0] + w[1] * Hcp[v][1] + w[2] * Hcp[v][2];
+                s[21 + u] += w[0] * xb0 + w[1] * xb1 + w[2] * xb2;
             }
         }
         block_sum_n<27>(a, red);
@@ -949,15 +793,15 @@ __global__ __launch_bounds__(256) void ba2view_backward_kernel(BaBwdParams p) {
         if (tid == 0) {
 #pragma unroll
             for (int u = 0; u < 6; ++u) a[21 + u] = sDcBar[u];
-            if (!schur6_solve(sM6, a, s, lam, precond, sDelta))
-                for (int u = 0; u < 6; ++u) sDelta[u] = 0.0;
+            if (!schur6_solve(sh.M6, a, s, lam, precond, sh.delta))
+                for (int u = 0; u < 6; ++u) sh.delta[u] = 0.0;
         }
         __syncthreads();
         const int dpos[6] = {0, 6, 11, 15, 18, 20};
         double wc[6], wdc[6];  // w of the camera, and 2 lambda w o d on the columns whose damping follows the diagonal
 #pragma unroll
         for (int u = 0; u < 6; ++u) {
-            wc[u] = sDelta[u];
+            wc[u] = sh.delta[u];
             wdc[u] = (precond && a[dpos[u]] >= 1e-12) ? 2.0 * lam * wc[u] * dc[u] : 0.0;
         }
         // pass B: the step and w per match, J_bar and r_bar, back through point_terms
@@ -969,42 +813,28 @@ __global__ __launch_bounds__(256) void ba2view_backward_kernel(BaBwdParams p) {
             const double c = (double)cf[i] / cden;
             PointTerms q;
             point_terms<kLossNone>(Rt, X + 3 * i, k0[2 * i], k0[2 * i + 1], k1[2 * i], k1[2 * i + 1], c, 0.0, 0.0, q);
-            double Hpp[6], inv[6], dp[3], wp[3], wdp[3];
+            double Hpp[6], Hcp[6][3], inv[6], gd[3], gw[3], dp[3], wp[3], wdp[3];
             const double xb[3] = {Xbar[3 * i], Xbar[3 * i + 1], Xbar[3 * i + 2]};
-            int idx = 0;
+            point_hpp(q, Hpp);
+            point_gp(q, gd);
+            point_hcp(q, Hcp);
 #pragma unroll
             for (int u = 0; u < 3; ++u) {
-#pragma unroll
-                for (int v = u; v < 3; ++v)
-                    Hpp[idx++] = q.Jp0[0][u] * q.Jp0[0][v] + q.Jp0[1][u] * q.Jp0[1][v] + q.Jp1[0][u] * q.Jp1[0][v] + q.Jp1[1][u] * q.Jp1[1][v];
-                double gd = -(q.Jp0[0][u] * q.r0[0] + q.Jp0[1][u] * q.r0[1] + q.Jp1[0][u] * q.r1[0] + q.Jp1[1][u] * q.r1[1]);
-                double gw = xb[u];
+                gw[u] = xb[u];
 #pragma unroll
                 for (int w = 0; w < 6; ++w) {
-                    const double h = q.Jc[0][w] * q.Jp1[0][u] + q.Jc[1][w] * q.Jp1[1][u];
-                    gd -= h * dc[w];
-                    gw -= h * wc[w];
+                    gd[u] -= Hcp[w][u] * dc[w];
+                    gw[u] -= Hcp[w][u] * wc[w];
                 }
-                dp[u] = gd;  // right-hand sides for now
-                wp[u] = gw;
             }
             const bool f0 = precond && Hpp[0] >= 1e-12, f1 = precond && Hpp[3] >= 1e-12, f2 = precond && Hpp[5] >= 1e-12;
-            Hpp[0] += lam * (precond ? fmax(Hpp[0], 1e-12) : 1.0);
-            Hpp[3] += lam * (precond ? fmax(Hpp[3], 1e-12) : 1.0);
-            Hpp[5] += lam * (precond ? fmax(Hpp[5], 1e-12) : 1.0);
+            point_damp(Hpp, lam, precond);
             if (!inv3_sym(Hpp, inv)) {  // the forward left this point where it was: only its camera columns took part
 #pragma unroll
                 for (int u = 0; u < 6; ++u) inv[u] = 0.0;
             }
-            {
-                const double d0 = dp[0], d1 = dp[1], d2 = dp[2], w0 = wp[0], w1 = wp[1], w2 = wp[2];
-                dp[0] = inv[0] * d0 + inv[1] * d1 + inv[2] * d2;
-                dp[1] = inv[1] * d0 + inv[3] * d1 + inv[4] * d2;
-                dp[2] = inv[2] * d0 + inv[4] * d1 + inv[5] * d2;
-                wp[0] = inv[0] * w0 + inv[1] * w1 + inv[2] * w2;
-                wp[1] = inv[1] * w0 + inv[3] * w1 + inv[4] * w2;
-                wp[2] = inv[2] * w0 + inv[4] * w1 + inv[5] * w2;
-            }
+            point_solve(inv, gd, dp);
+            point_solve(inv, gw, wp);
             wdp[0] = f0 ? 2.0 * lam * wp[0] * dp[0] : 0.0;
             wdp[1] = f1 ? 2.0 * lam * wp[1] * dp[1] : 0.0;
             wdp[2] = f2 ? 2.0 * lam * wp[2] * dp[2] : 0.0;
@@ -1063,7 +893,7 @@ __global__ __launch_bounds__(256) void ba2view_backward_kernel(BaBwdParams p) {
     __syncthreads();
     if (p.gconf) {
         // weights c_i = conf_i / cden, cden = sum conf while 2 sum conf >= 1e-6 (a constant below that)
-        const double shift = 2.0 * st[0] >= 1e-6 ? t2[0] / cden : 0.0;
+        const double shift = 2.0 * csum >= 1e-6 ? t2[0] / cden : 0.0;
         for (int i = tid; i < N; i += 256)
             p.gconf[(int64_t)b * N + i] = (kstar > 0 && cf[i] > 0.f) ? (float)(cbar[i] / cden - shift) : 0.f;
     }

@@ -2,6 +2,7 @@
 // mvtracks.hip: track merging and the track problem build).
 #pragma once
 #include "common.h"
+#include "small_linalg.h"
 
 namespace e2emv {
 
@@ -49,11 +50,6 @@ __device__ __forceinline__ void mv_loss(double s, double a, double a2, double* r
     }
 }
 
-__device__ __forceinline__ double mv_wsum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 __device__ __forceinline__ double mv_wmax(double v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));

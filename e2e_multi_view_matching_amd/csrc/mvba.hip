@@ -40,7 +40,7 @@ template <int NV, int NSUM>
 __device__ __forceinline__ void mv_block_reduce(double (&v)[NV], double* scratch /* [kMvWaves*NV] */) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
-    for (int k = 0; k < NV; ++k) v[k] = k < NSUM ? mv_wsum(v[k]) : mv_wmax(v[k]);
+    for (int k = 0; k < NV; ++k) v[k] = k < NSUM ? wave_sum_d(v[k]) : mv_wmax(v[k]);
     __syncthreads();
     if (lane == 0)
 #pragma unroll
@@ -220,9 +220,9 @@ __global__ __launch_bounds__(kMvThreads) void mvba_kernel(const MvbaArgs* __rest
                 }
             }
 #pragma unroll
-            for (int i = 0; i < 21; ++i) u[i] = mv_wsum(u[i]);
+            for (int i = 0; i < 21; ++i) u[i] = wave_sum_d(u[i]);
 #pragma unroll
-            for (int i = 0; i < 6; ++i) g[i] = mv_wsum(g[i]);
+            for (int i = 0; i < 6; ++i) g[i] = wave_sum_d(g[i]);
             if (lane == 0) {
                 int t = 0;
                 for (int i = 0; i < 6; ++i) {
@@ -341,10 +341,10 @@ __global__ __launch_bounds__(kMvThreads) void mvba_kernel(const MvbaArgs* __rest
                 }
             }
 #pragma unroll
-            for (int i = 0; i < 36; ++i) acc[i] = mv_wsum(acc[i]);
+            for (int i = 0; i < 36; ++i) acc[i] = wave_sum_d(acc[i]);
             if (fa == fb)
 #pragma unroll
-                for (int i = 0; i < 6; ++i) rh[i] = mv_wsum(rh[i]);
+                for (int i = 0; i < 6; ++i) rh[i] = wave_sum_d(rh[i]);
             if (lane == 0) {
                 for (int i = 0; i < 6; ++i) {
                     for (int j = 0; j < 6; ++j) {
@@ -604,7 +604,7 @@ __global__ __launch_bounds__(kMvRowThreads) void mv_build_kernel(MvBuildArgs g) 
         const float* cf = g.conf + size_t(b * g.P + q) * g.N;
         for (int m = tid; m < cnt; m += kMvRowThreads) sum += double(cf[m]);
     }
-    sum = mv_wsum(sum);
+    sum = wave_sum_d(sum);
     if (lane == 0) s_red[wave] = sum;
     __syncthreads();
     sum = s_red[0];

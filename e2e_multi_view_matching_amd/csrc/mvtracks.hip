@@ -538,7 +538,7 @@ __global__ __launch_bounds__(kMvRowThreads) void mv_tracks_emit_kernel(MvEmitArg
         __syncthreads();
     }
     // sum of the node confidences in a fixed order (points strided over the threads, then lanes, then waves), the weights
-    conf_sum = mv_wsum(conf_sum);
+    conf_sum = wave_sum_d(conf_sum);
     if (lane == 0) s_red[wave] = conf_sum;
     __syncthreads();
     double total = s_red[0];

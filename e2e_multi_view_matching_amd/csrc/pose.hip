@@ -131,12 +131,6 @@ __device__ double* jacobi9_parallel(double* A, double* B, double* V0, double* V1
     return Vc;
 }
 
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 struct W8Params {
     int B, N, kdim, intr_batch;
     const int* n_per;  // optional [B]: sample b uses its first n_per[b] <= N correspondences (rows stay N apart)

@@ -1,8 +1,16 @@
-// Small fp64 dense helpers shared by pose.hip and ba2view.hip (device-only, header-inline).
+// Small fp64 helpers shared by pose.hip, ba2view.hip, ransac.hip and mvba.h: the wavefront sum and dense linear algebra (device-only,
+// header-inline).
 #pragma once
 #include <hip/hip_runtime.h>
 
 namespace e2emv {
+
+// sum of v over the 64 lanes of the wavefront; result valid in every lane
+__device__ __forceinline__ double wave_sum_d(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
 
 template <int N>
 __device__ __forceinline__ void jacobi_static(double (&A)[N][N], double (&V)[N][N]) {
