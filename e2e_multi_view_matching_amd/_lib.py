@@ -165,6 +165,9 @@ SIGNATURES = {
     "e2emv_train_running_update": (c_int, [c_void_p, c_int, ctypes.POINTER(ctypes.c_char_p), _PP, _PP, c_void_p]),
     "e2emv_w8pt_backward": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "e2emv_pose_errors_backward": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "e2emv_w8pt_tuple_backward": (c_int, [c_void_p, c_int, c_int, c_int, _PP, _PP, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, _PP, c_void_p]),
+    "e2emv_pose_loss_tuple": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "e2emv_pose_loss_tuple_backward": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "e2emv_get_stats": (c_int, [c_void_p, ctypes.POINTER(ctypes.c_uint64), c_int, c_int]),
     "e2emv_set_sinkhorn_kernel": (c_int, [c_void_p, c_int]),
     "e2emv_sinkhorn_plan": (c_int, [c_void_p, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int), c_int]),

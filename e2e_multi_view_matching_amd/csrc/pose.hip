@@ -763,19 +763,14 @@ __global__ void pose_errors_kernel(int B, const float* T, const float* Tg, float
 
 // backward of pose_errors_kernel with respect to the FIRST pose: gT = g_rot d rot/dT + g_tr d tr/dT (zero where an angle is
 // clamped or the translation norms fail the 1e-6 test - exactly the entries the forward leaves out of its means)
-__global__ void pose_errors_backward_kernel(int B, const float* T, const float* Tg, const float* g_rot, const float* g_tr, float* gT) {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= B) return;
-    const float* A = T + (int64_t)b * 16;
-    const float* G = Tg + (int64_t)b * 16;
-    float* o = gT + (int64_t)b * 16;
+__device__ __forceinline__ void pose_errors_backward_one(const float* A, const float* G, float g_rot, float g_tr, float* o) {
     for (int i = 0; i < 16; ++i) o[i] = 0.f;
     double trc = 0.0;
     for (int i = 0; i < 3; ++i)
         for (int j = 0; j < 3; ++j) trc += (double)A[i * 4 + j] * G[i * 4 + j];
     const double ca = (trc - 1.0) * 0.5;
     if (ca > -1.0 && ca < 1.0) {
-        const double f = -(double)g_rot[b] * 0.5 / sqrt(1.0 - ca * ca);
+        const double f = -(double)g_rot * 0.5 / sqrt(1.0 - ca * ca);
         for (int i = 0; i < 3; ++i)
             for (int j = 0; j < 3; ++j) o[i * 4 + j] = (float)(f * G[i * 4 + j]);
     }
@@ -784,10 +779,16 @@ __global__ void pose_errors_backward_kernel(int B, const float* T, const float* 
     if ((float)n0 * (float)n1 > 1e-6f) {
         const double cd = (t0[0] * t1[0] + t0[1] * t1[1] + t0[2] * t1[2]) / (n0 * n1);
         if (cd > -1.0 && cd < 1.0) {
-            const double f = -(double)g_tr[b] / sqrt(1.0 - cd * cd);
+            const double f = -(double)g_tr / sqrt(1.0 - cd * cd);
             for (int i = 0; i < 3; ++i) o[i * 4 + 3] = (float)(f * (t1[i] / (n0 * n1) - cd * t0[i] / (n0 * n0)));
         }
     }
+}
+
+__global__ void pose_errors_backward_kernel(int B, const float* T, const float* Tg, const float* g_rot, const float* g_tr, float* gT) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    pose_errors_backward_one(T + (int64_t)b * 16, Tg + (int64_t)b * 16, g_rot[b], g_tr[b], gT + (int64_t)b * 16);
 }
 
 
@@ -847,11 +848,10 @@ __global__ void normalize_kpts_kernel(int N, int kdim, int intr_batch, const flo
     out[o + 1] = (kpts[o + 1] - K[kdim + 2]) / K[kdim + 1];
 }
 
-// means of the two angle errors: rotation over all B entries, translation over the entries whose norm product
-// exceeds 1e-6 (compute_pose_error.py:12,22; an empty selection gives NaN like torch's mean of nothing)
-__global__ __launch_bounds__(64) void pose_error_means_kernel(int B, const float* rot, const float* tr, const uint8_t* valid,
-                                                              float* out2) {
-    float sr = 0.f, st = 0.f, nv = 0.f;
+// the sums behind the means below, by one wave: every lane returns with the three sums over all B entries
+__device__ __forceinline__ void pose_error_sums(int B, const float* rot, const float* tr, const uint8_t* valid, float& sr, float& st,
+                                                float& nv) {
+    sr = 0.f; st = 0.f; nv = 0.f;
     for (int b = threadIdx.x; b < B; b += 64) {
         sr += rot[b];
         if (valid[b]) { st += tr[b]; nv += 1.f; }
@@ -862,9 +862,36 @@ __global__ __launch_bounds__(64) void pose_error_means_kernel(int B, const float
         st += __shfl_xor(st, o);
         nv += __shfl_xor(nv, o);
     }
+}
+
+// means of the two angle errors: rotation over all B entries, translation over the entries whose norm product
+// exceeds 1e-6 (compute_pose_error.py:12,22; an empty selection gives NaN like torch's mean of nothing)
+__global__ __launch_bounds__(64) void pose_error_means_kernel(int B, const float* rot, const float* tr, const uint8_t* valid,
+                                                              float* out2) {
+    float sr, st, nv;
+    pose_error_sums(B, rot, tr, valid, sr, st, nv);
     if (threadIdx.x == 0) {
         out2[0] = sr / (float)B;
         out2[1] = st / nv;  // 0 / 0 = NaN
+    }
+}
+
+// the pose term of helpers.run_matcher over the P pairs of a tuple batch (helpers.py:250-258): the means of pair q as above over
+// its B entries [q*B, (q+1)*B), added in fp32 in ascending q like `rot_loss = rot_loss + ...` (a pair without a valid
+// translation makes the translation sum NaN).  One wave.
+__global__ __launch_bounds__(64) void pose_loss_tuple_kernel(int P, int B, const float* rot, const float* tr, const uint8_t* valid,
+                                                             float* out2) {
+    float lr = 0.f, lt = 0.f;
+    for (int q = 0; q < P; ++q) {
+        const int64_t o = (int64_t)q * B;
+        float sr, st, nv;
+        pose_error_sums(B, rot + o, tr + o, valid + o, sr, st, nv);
+        lr = lr + sr / (float)B;
+        lt = lt + st / nv;
+    }
+    if (threadIdx.x == 0) {
+        out2[0] = lr;
+        out2[1] = lt;
     }
 }
 
@@ -902,14 +929,61 @@ __global__ void apply_mask_kernel(int64_t n, const float* x, const uint8_t* mask
     if (i < n) out[i] = mask[i] ? x[i] : 0.f;
 }
 
+__device__ __forceinline__ bool transl_valid(const float* A, const float* G) {
+    const float n0 = sqrtf(A[3] * A[3] + A[7] * A[7] + A[11] * A[11]);
+    const float n1 = sqrtf(G[3] * G[3] + G[7] * G[7] + G[11] * G[11]);
+    return n0 * n1 > 1e-6f;
+}
+
 __global__ void pose_error_valid_kernel(int B, const float* T, const float* Tg, uint8_t* valid) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
-    const float* A = T + (int64_t)b * 16;
-    const float* G = Tg + (int64_t)b * 16;
-    const float n0 = sqrtf(A[3] * A[3] + A[7] * A[7] + A[11] * A[11]);
-    const float n1 = sqrtf(G[3] * G[3] + G[7] * G[7] + G[11] * G[11]);
-    valid[b] = n0 * n1 > 1e-6f ? 1 : 0;
+    valid[b] = transl_valid(T + (int64_t)b * 16, Tg + (int64_t)b * 16) ? 1 : 0;
+}
+
+// backward of pose_loss_tuple_kernel and the error kernels in front of it: pair q = blockIdx.x (one wave) counts its valid
+// entries, then entry (q, b) gets pose_errors_backward with g_rot = g2[0] / B and g_tr = valid ? g2[1] / n_valid : 0, in fp32
+__global__ __launch_bounds__(64) void pose_loss_tuple_backward_kernel(int B, const float* T, const float* Tg, const float* g2, float* gT) {
+    const int64_t o = (int64_t)blockIdx.x * B;
+    float nv = 0.f;
+    for (int b = threadIdx.x; b < B; b += 64)
+        if (transl_valid(T + (o + b) * 16, Tg + (o + b) * 16)) nv += 1.f;
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) nv += __shfl_xor(nv, s);
+    const float g_rot = g2[0] / (float)B, g_tr = g2[1] / nv;
+    for (int b = threadIdx.x; b < B; b += 64) {
+        const float* A = T + (o + b) * 16;
+        const float* G = Tg + (o + b) * 16;
+        pose_errors_backward_one(A, G, g_rot, transl_valid(A, G) ? g_tr : 0.f, gT + (o + b) * 16);
+    }
+}
+
+// ---- backward of e2emv_w8pt_tuple with respect to the P confidence tensors: the reverse of tuple_gather_kernel's confidence path ----
+struct TupleConfParams {
+    int B, N;
+    const int64_t* matches[kMaxGroups];  // pair q: [B][N]
+    const float* conf[kMaxGroups];       // [B][N]
+    float* gconf[kMaxGroups];            // [B][N] out, or null: the pair is left out
+    float* cf;                           // [P*B][N] the confidences the forward's solve saw
+    const float* g;                      // [P*B][N] w8pt_backward_kernel's result for cf
+    const float* gcf;                    // [P*B][N] adjoint of the gathered confidences themselves, or null
+};
+
+// grid (ceil(N/256), B, P) like tuple_gather_kernel
+__global__ __launch_bounds__(256) void tuple_conf_gather_kernel(TupleConfParams p) {
+    const int b = blockIdx.y, q = blockIdx.z, n = blockIdx.x * 256 + threadIdx.x;
+    if (n >= p.N) return;
+    const int64_t src = (int64_t)b * p.N + n, dst = ((int64_t)q * p.B + b) * p.N + n;
+    p.cf[dst] = p.matches[q][src] >= 0 ? p.conf[q][src] : 0.f;
+}
+
+__global__ __launch_bounds__(256) void tuple_conf_scatter_kernel(TupleConfParams p) {
+    const int b = blockIdx.y, q = blockIdx.z, n = blockIdx.x * 256 + threadIdx.x;
+    if (n >= p.N || !p.gconf[q]) return;
+    const int64_t src = (int64_t)b * p.N + n, dst = ((int64_t)q * p.B + b) * p.N + n;
+    float g = p.g[dst];
+    if (p.gcf) g += p.gcf[dst];
+    p.gconf[q][src] = p.matches[q][src] >= 0 ? g : 0.f;
 }
 
 }  // namespace e2emv
@@ -1067,6 +1141,41 @@ extern "C" int e2emv_w8pt_tuple(e2emv_ctx* ctx, int B, int T, int N, const float
                     d_kpts0n, d_kpts1n, d_conf_n, d_inliers, d_posdepth, d_F, d_status, s);
 }
 
+extern "C" int e2emv_w8pt_tuple_backward(e2emv_ctx* ctx, int B, int T, int N, const int64_t* const* d_matches, const float* const* d_conf,
+                                         const float* d_kpts0n, const float* d_kpts1n, const float* d_T, const float* d_gT, const float* d_gcf,
+                                         float* const* d_gconf, void* stream) {
+    if (!ctx || !d_matches || !d_conf || !d_kpts0n || !d_kpts1n || !d_T || !d_gT || !d_gconf) return E2EMV_EINVAL;
+    E2EMV_ENTER(ctx, stream);
+    if (B <= 0 || T < 2 || T > E2EMV_MAX_TUPLE) return set_err(ctx, E2EMV_ESHAPE, "w8pt_tuple_backward: batch=%d tuple_size=%d", B, T);
+    if (N < 8) return set_err(ctx, E2EMV_ESHAPE, "w8pt_tuple_backward: fewer than 8 correspondences (N=%d)", N);
+    const int P = T * (T - 1) / 2;
+    const int PB = P * B;
+    TupleConfParams g{};
+    g.B = B; g.N = N;
+    for (int q = 0; q < P; ++q) {
+        if (!d_matches[q] || !d_conf[q]) return set_err(ctx, E2EMV_EINVAL, "w8pt_tuple_backward: null input for pair %d", q);
+        g.matches[q] = d_matches[q];
+        g.conf[q] = d_conf[q];
+        g.gconf[q] = d_gconf[q];
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const size_t sz_c = ((size_t)PB * N * 4 + 255) & ~size_t(255);
+    int rc = ws_reserve(ctx, 2 * sz_c);
+    if (rc) return rc;
+    g.cf = (float*)ctx->d_ws;
+    float* gw = (float*)(ctx->d_ws + sz_c);
+    g.g = gw;
+    g.gcf = d_gcf;
+    W8BwdParams p{};
+    p.B = PB; p.N = N; p.k0n = d_kpts0n; p.k1n = d_kpts1n; p.conf = g.cf; p.T = d_T; p.gT = d_gT; p.gconf = gw;
+    const dim3 grid((N + 255) / 256, B, P);
+    hipLaunchKernelGGL(tuple_conf_gather_kernel, grid, dim3(256), 0, s, g);
+    hipLaunchKernelGGL(w8pt_backward_kernel, dim3(PB), dim3(256), 0, s, p);
+    hipLaunchKernelGGL(tuple_conf_scatter_kernel, grid, dim3(256), 0, s, g);
+    E2EMV_CHECK_LAUNCH(ctx, "w8pt_tuple_backward kernels");
+    return E2EMV_OK;
+}
+
 extern "C" int e2emv_normalize_kpts(e2emv_ctx* ctx, int B, int N, const float* d_kpts, const float* d_intr, int kdim,
                                     int intr_batch, float* d_out, void* stream) {
     if (!ctx || !d_kpts || !d_intr || !d_out) return E2EMV_EINVAL;
@@ -1124,6 +1233,32 @@ extern "C" int e2emv_pose_errors_backward(e2emv_ctx* ctx, int B, const float* d_
     if (B <= 0) return set_err(ctx, E2EMV_ESHAPE, "pose_errors_backward: empty batch");
     hipLaunchKernelGGL(pose_errors_backward_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, B, d_T, d_T_gt, d_g_rot, d_g_transl, d_gT);
     E2EMV_CHECK_LAUNCH(ctx, "pose_errors_backward_kernel");
+    return E2EMV_OK;
+}
+
+extern "C" int e2emv_pose_loss_tuple(e2emv_ctx* ctx, int P, int B, const float* d_T, const float* d_T_gt, float* d_rot_err, float* d_transl_err,
+                                     uint8_t* d_transl_valid, float* d_losses2, void* stream) {
+    if (!ctx || !d_T || !d_T_gt || !d_rot_err || !d_transl_err || !d_transl_valid || !d_losses2) return E2EMV_EINVAL;
+    E2EMV_ENTER(ctx, stream);
+    if (P <= 0 || B <= 0 || (int64_t)P * B > INT32_MAX) return set_err(ctx, E2EMV_ESHAPE, "pose_loss_tuple: pairs=%d batch=%d", P, B);
+    const int PB = P * B;
+    hipStream_t s = (hipStream_t)stream;
+    prof_begin(ctx, PS_W8PT, s);
+    hipLaunchKernelGGL(pose_errors_kernel, dim3((PB + 63) / 64), dim3(64), 0, s, PB, d_T, d_T_gt, d_rot_err, d_transl_err);
+    hipLaunchKernelGGL(pose_error_valid_kernel, dim3((PB + 63) / 64), dim3(64), 0, s, PB, d_T, d_T_gt, d_transl_valid);
+    hipLaunchKernelGGL(pose_loss_tuple_kernel, dim3(1), dim3(64), 0, s, P, B, d_rot_err, d_transl_err, d_transl_valid, d_losses2);
+    prof_end(ctx, s);
+    E2EMV_CHECK_LAUNCH(ctx, "pose_loss_tuple kernels");
+    return E2EMV_OK;
+}
+
+extern "C" int e2emv_pose_loss_tuple_backward(e2emv_ctx* ctx, int P, int B, const float* d_T, const float* d_T_gt, const float* d_g2, float* d_gT,
+                                              void* stream) {
+    if (!ctx || !d_T || !d_T_gt || !d_g2 || !d_gT) return E2EMV_EINVAL;
+    E2EMV_ENTER(ctx, stream);
+    if (P <= 0 || B <= 0 || (int64_t)P * B > INT32_MAX) return set_err(ctx, E2EMV_ESHAPE, "pose_loss_tuple_backward: pairs=%d batch=%d", P, B);
+    hipLaunchKernelGGL(pose_loss_tuple_backward_kernel, dim3(P), dim3(64), 0, (hipStream_t)stream, B, d_T, d_T_gt, d_g2, d_gT);
+    E2EMV_CHECK_LAUNCH(ctx, "pose_loss_tuple_backward_kernel");
     return E2EMV_OK;
 }
 

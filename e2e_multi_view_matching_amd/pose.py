@@ -5,7 +5,8 @@ Same names, argument order, keyword names, ``info`` keys and ``None`` convention
 reference (``estimate_relative_pose.py:9-14, 16-31, 84-136``; ``compute_pose_error.py:3-22``);
 the arithmetic runs in the HIP kernels of ``csrc/pose.hip`` (fp64 Gram / Jacobi instead of
 the reference's library SVDs).  The pose is differentiable with respect to the confidences (training, the pose loss:
-``_W8ptPose`` / ``e2emv_w8pt_backward``); keypoints and the candidate choice carry no gradient.  No CPU fallback.
+``_W8ptPose`` / ``e2emv_w8pt_backward``; all pairs of a tuple at once: ``_W8ptTuplePose`` / ``e2emv_w8pt_tuple_backward`` and
+``pose_loss_tuple``); keypoints and the candidate choice carry no gradient.  No CPU fallback.
 """
 import ctypes
 
@@ -199,7 +200,10 @@ def run_weighted_8_point_tuple(data, result, choose_closest=False, targets=None,
     with 4 kernel launches per tuple batch instead of 4 per pair.  Returns ``{(id0, id1): (T_021 [B,4,4], info)}`` with
     the per-pair values of ``estimate_relative_pose_w8pt`` (views into the batched outputs) and ``(None, None)`` for a pair
     whose matches are missing.  ``targets``: ``{(id0, id1): T_021 [B,4,4]}`` when ``choose_closest``.  Images with
-    different keypoint counts (or per-pair keypoint keys) go through the per-pair call."""
+    different keypoint counts (or per-pair keypoint keys) go through the per-pair call.  With gradients enabled and a
+    ``conf_scores_{i}_{j}`` that requires grad, the poses are views of one ``_W8ptTuplePose`` output and carry the graph back to the
+    confidences of their pair (ONE ``e2emv_w8pt_tuple_backward``, bit-identical to the per-pair gradient; a pair that does not require
+    grad gets ``None``); ``info["confidence"]`` stays graph-free as in the per-pair function."""
     T = 0
     while "keypoints" + str(T) in data:
         T += 1
@@ -216,45 +220,107 @@ def run_weighted_8_point_tuple(data, result, choose_closest=False, targets=None,
             out[(i, j)] = run_weighted_8_point(data, result, i, j, choose_closest=choose_closest, target_T_021=tgt)
         return out
     dev = _dev_of(result[mkeys[0]], data["keypoints0"])
-    ctx = _lib.context(dev)
+    tg = [_prep(targets[p], dev) for p in pairs] if choose_closest else [None] * len(pairs)
+    st = _tuple_state(data, result, T, pairs, dev, tg, choose_closest, determine_inliers)
+    confs = [result["conf_scores_{}_{}".format(i, j)] for i, j in pairs]
+    if torch.is_grad_enabled() and any(c.requires_grad for c in confs):
+        # training: the poses are views of ONE output that carries the graph back to every pair's confidences (e2emv_w8pt_tuple_backward)
+        Tout = _W8ptTuplePose.apply(st, *confs)
+    else:
+        Tout = _w8pt_tuple_call(st, [_prep(c.reshape(st["B"], -1), dev) for c in confs])
+    o = st["out"]
+    out = {}
+    for q, p in enumerate(pairs):
+        info = {"kpts0_norm": o["k0n"][q], "kpts1_norm": o["k1n"][q], "confidence": o["cfn"][q].reshape(confs[q].shape),
+                "inliers": o["inl"][q] if o["inl"] is not None else None, "pos_depth_mask": o["pos"][q], "F": o["F"][q],
+                "status": o["status"][q]}
+        out[p] = (Tout[q], info)
+    return out
+
+
+def _tuple_state(data, result, T, pairs, dev, tg, choose_closest, determine_inliers, want_cf=False):
+    """The device inputs of ``e2emv_w8pt_tuple`` apart from the confidences, which the caller hands over on their own (they may carry a
+    graph).  ``tg``: one target [B,4,4] per pair (or ``None`` each); ``want_cf``: the solve also returns the gathered confidences."""
     B, N = data["keypoints0"].shape[:2]
-    P = len(pairs)
     kpts = [_prep(data["keypoints" + str(t)], dev) for t in range(T)]
     intr = [_intr_batch(_prep(data["intr" + str(t)], dev), B) for t in range(T)]
     kdim, nb = intr[0][1], intr[0][2]
     if any(k[1:] != (kdim, nb) for k in intr):
         raise AssertionError("intrinsics of a tuple must share their layout")
-    intr = [k[0] for k in intr]
-    matches = [result[k].to(dev, torch.int64).contiguous() for k in mkeys]
-    conf_shapes = [result["conf_scores_{}_{}".format(i, j)].shape for i, j in pairs]
-    conf = [_prep(result["conf_scores_{}_{}".format(i, j)].reshape(B, -1), dev) for i, j in pairs]
-    if any(c.shape != (B, N) for c in conf) or any(m.shape != (B, N) for m in matches):
+    matches = [result["matches{}_{}_{}".format(i, i, j)].to(dev, torch.int64).contiguous() for i, j in pairs]
+    if any(m.shape != (B, N) for m in matches) or any(result["conf_scores_{}_{}".format(i, j)].numel() != B * N for i, j in pairs):
         raise AssertionError("matches / conf_scores must be [B, N]")
-    tg = [_prep(targets[p], dev) for p in pairs] if choose_closest else [None] * P
-    Tout = torch.empty((P, B, 4, 4), dtype=torch.float32, device=dev)
-    k0n = torch.empty((P, B, N, 2), dtype=torch.float32, device=dev)
-    k1n = torch.empty_like(k0n)
-    cfn = torch.empty((P, B, N), dtype=torch.float32, device=dev)
-    inl = torch.empty((P, B, N), dtype=torch.bool, device=dev) if determine_inliers else None  # (0 / 1 bytes, see above)
-    pos = torch.empty((P, B, N), dtype=torch.bool, device=dev)
-    F = torch.empty((P, B, 3, 3), dtype=torch.float32, device=dev)
-    status = torch.empty((P, B), dtype=torch.int32, device=dev)
+    return {"ctx": _lib.context(dev), "dev": dev, "B": B, "T": T, "N": N, "P": len(pairs), "pairs": pairs, "kpts": kpts,
+            "intr": [k[0] for k in intr], "kdim": kdim, "nb": nb, "matches": matches, "tg": tg, "choose_closest": bool(choose_closest),
+            "determine_inliers": bool(determine_inliers), "want_cf": bool(want_cf)}
+
+
+def _w8pt_tuple_call(st, conf):
+    """One ``e2emv_w8pt_tuple`` on the prepared confidences ``conf`` ([B,N] fp32 per pair); the outputs go to ``st["out"]``, T [P,B,4,4] is
+    returned."""
+    ctx, dev, B, T, N, P = (st[k] for k in ("ctx", "dev", "B", "T", "N", "P"))
+    inliers = st["determine_inliers"]
+    o = {"T": torch.empty((P, B, 4, 4), dtype=torch.float32, device=dev),
+         "k0n": torch.empty((P, B, N, 2), dtype=torch.float32, device=dev),
+         "k1n": torch.empty((P, B, N, 2), dtype=torch.float32, device=dev),
+         "cfn": torch.empty((P, B, N), dtype=torch.float32, device=dev),
+         "inl": torch.empty((P, B, N), dtype=torch.bool, device=dev) if inliers else None,  # (0 / 1 bytes, see above)
+         "pos": torch.empty((P, B, N), dtype=torch.bool, device=dev),
+         "F": torch.empty((P, B, 3, 3), dtype=torch.float32, device=dev),
+         "status": torch.empty((P, B), dtype=torch.int32, device=dev)}
     keep, args = [], []
-    for lst in (kpts, intr, matches, conf, tg):
+    for lst in (st["kpts"], st["intr"], st["matches"], conf, st["tg"]):
         pa, arr = _lib.ptr_array(lst)
         keep.append(arr)
         args.append(pa)
     with torch.cuda.device(dev):
-        ctx.call("e2emv_w8pt_tuple", B, T, N, args[0], args[1], kdim, nb, args[2], args[3], 1 if choose_closest else 0, args[4],
-                 1 if determine_inliers else 0, _lib.ptr(Tout), _lib.ptr(k0n), _lib.ptr(k1n), _lib.ptr(cfn), _lib.ptr(inl),
-                 _lib.ptr(pos), _lib.ptr(F), _lib.ptr(status), _lib.stream_ptr(dev))
-    posb, inlb = pos, inl
-    out = {}
-    for q, p in enumerate(pairs):
-        info = {"kpts0_norm": k0n[q], "kpts1_norm": k1n[q], "confidence": cfn[q].reshape(conf_shapes[q]),
-                "inliers": inlb[q] if inlb is not None else None, "pos_depth_mask": posb[q], "F": F[q], "status": status[q]}
-        out[p] = (Tout[q], info)
-    return out
+        ctx.call("e2emv_w8pt_tuple", B, T, N, args[0], args[1], st["kdim"], st["nb"], args[2], args[3], 1 if st["choose_closest"] else 0,
+                 args[4], 1 if inliers else 0, _lib.ptr(o["T"]), _lib.ptr(o["k0n"]), _lib.ptr(o["k1n"]), _lib.ptr(o["cfn"]),
+                 _lib.ptr(o["inl"]), _lib.ptr(o["pos"]), _lib.ptr(o["F"]), _lib.ptr(o["status"]), _lib.stream_ptr(dev))
+    st["out"] = o
+    return o["T"]
+
+
+class _W8ptTuplePose(torch.autograd.Function):
+    """T [P,B,4,4] = w8pt of every pair of the tuple as a function of the P confidence tensors: ``e2emv_w8pt_tuple`` forward, ONE
+    ``e2emv_w8pt_tuple_backward`` for all dLoss/dconf_scores (keypoints, matches and the candidate choice carry no gradient).  With
+    ``st["want_cf"]`` a second output: the gathered confidences ``(matches >= 0) * conf_scores`` [P*B,N] of ``get_kpts``, written by
+    ``e2emv_gather_matched`` per pair (the per-pair path's numbers); their adjoint joins the backward call as ``d_gcf``."""
+
+    @staticmethod
+    def forward(fctx, st, *confs):
+        ctx, dev, B, N, P = (st[k] for k in ("ctx", "dev", "B", "N", "P"))
+        conf = [_prep(c.reshape(B, -1), dev) for c in confs]
+        cf = None
+        if st["want_cf"]:
+            cf = torch.empty((P * B, N), dtype=torch.float32, device=dev)
+            k1g = torch.empty((B, N, 2), dtype=torch.float32, device=dev)  # (the call's other output: not used here)
+            with torch.cuda.device(dev):
+                for q, (i, j) in enumerate(st["pairs"]):
+                    ctx.call("e2emv_gather_matched", B, N, N, _lib.ptr(st["kpts"][j]), _lib.ptr(st["matches"][q]), _lib.ptr(conf[q]),
+                             _lib.ptr(k1g), _lib.ptr(cf[q * B:(q + 1) * B]), _lib.stream_ptr(dev))
+        T = _w8pt_tuple_call(st, conf)
+        fctx.st = {k: v for k, v in st.items() if k != "out"}  # (the outputs reach the backward as saved tensors only: no cycle through T)
+        fctx.meta =[(c.shape, c.dtype, c.device) for c in confs]
+        fctx.save_for_backward(T, st["out"]["k0n"], st["out"]["k1n"], *conf)
+        return (T, cf) if st["want_cf"] else T
+
+    @staticmethod
+    def backward(fctx, gT, gcf=None):
+        st = fctx.st
+        ctx, dev, B, T_, N, P = (st[k] for k in ("ctx", "dev", "B", "T", "N", "P"))
+        T, k0n, k1n = fctx.saved_tensors[:3]
+        conf = list(fctx.saved_tensors[3:])
+        g = _prep(gT, dev)
+        gc = _prep(gcf, dev) if gcf is not None else None
+        gconf = [torch.empty((B, N), dtype=torch.float32, device=dev) if fctx.needs_input_grad[1 + q] else None for q in range(P)]
+        pm, keep_m = _lib.ptr_array(st["matches"])
+        pc, keep_c = _lib.ptr_array(conf)
+        pg, keep_g = _lib.ptr_array(gconf)
+        with torch.cuda.device(dev):
+            ctx.call("e2emv_w8pt_tuple_backward", B, T_, N, pm, pc, _lib.ptr(k0n), _lib.ptr(k1n), _lib.ptr(T), _lib.ptr(g), _lib.ptr(gc), pg,
+                     _lib.stream_ptr(dev))
+        return (None,) + tuple(None if gq is None else gq.reshape(shape).to(cdev, dtype) for gq, (shape, dtype, cdev) in zip(gconf, fctx.meta))
 
 
 def _pose_error_buffers(T0, T1, means):
@@ -465,3 +531,96 @@ class _Ba2ViewPose(torch.autograd.Function):
         if gTi is not None:
             gTi = gTi.to(tdev, tdtype)
         return gconf, gTi, None, None, None, None, None, None, None
+
+
+class _PoseLossTuple(torch.autograd.Function):
+    """losses2 [2] = (sum over the pairs of the mean rotation error, sum over the pairs of the mean translation-angle error over the valid
+    entries) of T [P*B,4,4] against the targets: ``e2emv_pose_loss_tuple`` forward, ``e2emv_pose_loss_tuple_backward`` for dLoss/dT - the
+    incoming gradient stays on the device."""
+
+    @staticmethod
+    def forward(fctx, T, Tgt, ctx, dev, P, B):
+        a = _prep(T, dev)
+        l2 = _pose_loss_tuple_call(ctx, dev, P, B, a, Tgt)
+        fctx.misc = (ctx, dev, P, B, T.shape)
+        fctx.save_for_backward(a, Tgt)
+        return l2
+
+    @staticmethod
+    def backward(fctx, g2):
+        a, Tgt = fctx.saved_tensors
+        ctx, dev, P, B, shape = fctx.misc
+        g = _prep(g2, dev)
+        gT = torch.empty((P * B, 4, 4), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            ctx.call("e2emv_pose_loss_tuple_backward", P, B, _lib.ptr(a), _lib.ptr(Tgt), _lib.ptr(g), _lib.ptr(gT), _lib.stream_ptr(dev))
+        return gT.reshape(shape), None, None, None, None, None
+
+
+def _pose_loss_tuple_call(ctx, dev, P, B, T, Tgt):
+    rot = torch.empty((P * B,), dtype=torch.float32, device=dev)
+    tr = torch.empty((P * B,), dtype=torch.float32, device=dev)
+    valid = torch.empty((P * B,), dtype=torch.uint8, device=dev)
+    l2 = torch.empty((2,), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        ctx.call("e2emv_pose_loss_tuple", P, B, _lib.ptr(T), _lib.ptr(Tgt), _lib.ptr(rot), _lib.ptr(tr), _lib.ptr(valid), _lib.ptr(l2),
+                 _lib.stream_ptr(dev))
+    return l2
+
+
+def pose_loss_tuple(data, result, ba_iterations=0):
+    """The pose term of ``helpers.run_matcher`` (helpers.py:243-260) for ALL pairs of the tuple at once: per pair the target
+    ``inv(pose_j) @ pose_i``, ``run_weighted_8_point(..., choose_closest=True)``, rotation plus translation-angle error, summed over the
+    pairs.  Returns ``{"rot_loss", "transl_loss", "poses": {(i, j): T_021 [B,4,4]}}``; the two losses are 0-dim device tensors that
+    carry the graph back to every ``conf_scores_{i}_{j}`` that requires grad.  A fixed number of device calls whatever the batch size,
+    and no host synchronisation: P ``e2emv_relative_pose`` into one target buffer, ``e2emv_w8pt_tuple``, ``e2emv_pose_loss_tuple``
+    forward; ``e2emv_pose_loss_tuple_backward`` and ``e2emv_w8pt_tuple_backward`` backward.  ``ba_iterations > 0``: the loss is taken
+    on the pose refined by the two-view bundle adjustment (squared loss) of all P*B samples in one call - the gathered confidences
+    (P ``e2emv_gather_matched``), ``mask_confidence`` with the positive-depth mask, ``e2emv_ba_2view`` / ``e2emv_ba_2view_backward``; a
+    sample with fewer than 7 usable matches keeps its w8pt pose and passes its gradient through.  ``ValueError`` before any device
+    call: fewer than 8 keypoints, images with different keypoint counts, a missing ``pose{t}``, a missing pair in ``result``, a
+    negative ``ba_iterations``."""
+    T = 0
+    while "keypoints" + str(T) in data:
+        T += 1
+    if T < 2 or T > _lib.MAX_TUPLE:
+        raise ValueError("pose_loss_tuple takes tuples of 2..{} images, not {}".format(_lib.MAX_TUPLE, T))
+    if isinstance(ba_iterations, bool) or int(ba_iterations) != ba_iterations or ba_iterations < 0:
+        raise ValueError("ba_iterations must be a non-negative integer, not {!r}".format(ba_iterations))
+    ba_iterations = int(ba_iterations)
+    shapes = {tuple(data["keypoints" + str(t)].shape) for t in range(T)}
+    if len(shapes) != 1:
+        raise ValueError("pose_loss_tuple needs the same number of keypoints in every image, got {}".format(sorted(shapes)))
+    if next(iter(shapes))[1] < 8:
+        raise ValueError("pose_loss_tuple needs at least 8 keypoints per image, got {}".format(next(iter(shapes))[1]))
+    missing = ["pose" + str(t) for t in range(T) if "pose" + str(t) not in data]
+    pairs = [(i, j) for j in range(T) for i in range(j)]
+    missing += [k for i, j in pairs for k in ("matches{}_{}_{}".format(i, i, j), "conf_scores_{}_{}".format(i, j)) if k not in result]
+    if missing:
+        raise ValueError("pose_loss_tuple: missing {}".format(", ".join(missing)))
+    dev = _dev_of(result["matches0_0_1"], data["keypoints0"])
+    ctx = _lib.context(dev)
+    B = data["keypoints0"].shape[0]
+    P = len(pairs)
+    poses = [_prep(data["pose" + str(t)], dev) for t in range(T)]
+    Tgt = torch.empty((P * B, 4, 4), dtype=torch.float32, device=dev)
+    tg = [Tgt[q * B:(q + 1) * B] for q in range(P)]
+    with torch.cuda.device(dev):
+        for q, (i, j) in enumerate(pairs):  # target of pair (i, j): inv(pose_j) @ pose_i (helpers.py:254)
+            ctx.call("e2emv_relative_pose", B, _lib.ptr(poses[i]), _lib.ptr(poses[j]), _lib.ptr(tg[q]), _lib.stream_ptr(dev))
+    st = _tuple_state(data, result, T, pairs, dev, tg, True, False, want_cf=ba_iterations > 0)
+    confs = [result["conf_scores_{}_{}".format(i, j)] for i, j in pairs]
+    graph = torch.is_grad_enabled() and any(c.requires_grad for c in confs)
+    with torch.set_grad_enabled(graph):
+        solved = _W8ptTuplePose.apply(st, *confs)
+        o = st["out"]
+        if ba_iterations > 0:
+            Tw, cf = solved
+            cm = mask_confidence(cf, o["pos"].reshape(P * B, -1))
+            Tp = _Ba2ViewPose.apply(cm, Tw.reshape(P * B, 4, 4), ctx, dev, o["k0n"].reshape(P * B, -1, 2), o["k1n"].reshape(P * B, -1, 2),
+                                    ba_iterations, False, [])
+        else:
+            Tp = solved.reshape(P * B, 4, 4)
+        l2 = _PoseLossTuple.apply(Tp, Tgt, ctx, dev, P, B) if graph else _pose_loss_tuple_call(ctx, dev, P, B, Tp, Tgt)
+    Tq = Tp.reshape(P, B, 4, 4)
+    return {"rot_loss": l2[0], "transl_loss": l2[1], "poses": {p: Tq[q] for q, p in enumerate(pairs)}}

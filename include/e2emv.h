@@ -750,6 +750,31 @@ int e2emv_w8pt_backward(e2emv_ctx* ctx, int B, int N, const float* d_kpts0n, con
 int e2emv_pose_errors_backward(e2emv_ctx* ctx, int B, const float* d_T, const float* d_T_gt, const float* d_g_rot, const float* d_g_transl,
                                float* d_gT, void* stream);
 
+/* Backward of e2emv_w8pt_tuple with respect to the P = T(T-1)/2 confidence tensors, in the forward's pair order and pair-major
+ * indexing.  d_matches[q] / d_conf[q] [B,N]: the forward's inputs; d_kpts0n / d_kpts1n [P*B,N,2] and d_T [P*B,4,4]: its outputs;
+ * d_gT [P*B,4,4] = dLoss/dT.  Element (q, b) is e2emv_w8pt_backward for the confidences the forward's solve saw,
+ * c = matches >= 0 ? conf : 0; d_gcf [P*B,N] (may be NULL), the adjoint of those gathered confidences themselves, is added to its
+ * result g, and d_gconf[q][b,n] = matches >= 0 ? g : 0.  A NULL d_gconf[q] leaves that pair out.  One gather, the backward kernel
+ * of e2emv_w8pt_backward on all P*B samples, one masked scatter.  Errors as e2emv_w8pt_tuple: E2EMV_ESHAPE for B <= 0, T outside
+ * 2..E2EMV_MAX_TUPLE or N < 8, E2EMV_EINVAL for a NULL table or a NULL entry of d_matches / d_conf; nothing is launched then. */
+int e2emv_w8pt_tuple_backward(e2emv_ctx* ctx, int B, int T, int N, const int64_t* const* d_matches, const float* const* d_conf,
+                              const float* d_kpts0n, const float* d_kpts1n, const float* d_T, const float* d_gT, const float* d_gcf,
+                              float* const* d_gconf, void* stream);
+
+/* The pose term of helpers.run_matcher (helpers.py:250-258) for the P pairs of a tuple batch, reduced on the device: d_T / d_T_gt
+ * [P*B,4,4] pair-major; per-element errors and validity [P*B] as e2emv_pose_error_means; d_losses2[0] = sum over q of the mean
+ * rotation error of pair q over its B entries, d_losses2[1] = sum over q of the mean translation error over the valid entries of
+ * pair q (NaN for a pair with none, which makes the sum NaN like the reference's mean of an empty selection).  Each mean with the
+ * arithmetic of e2emv_pose_error_means, the pairs added in fp32 in ascending q. */
+int e2emv_pose_loss_tuple(e2emv_ctx* ctx, int P, int B, const float* d_T, const float* d_T_gt, float* d_rot_err, float* d_transl_err,
+                          uint8_t* d_transl_valid, float* d_losses2, void* stream);
+
+/* Backward of e2emv_pose_loss_tuple with respect to d_T: d_g2 = DEVICE pointer to {dL/d losses2[0], dL/d losses2[1]}; d_gT [P*B,4,4]
+ * is e2emv_pose_errors_backward with g_rot[q,b] = g2[0] / (float)B and g_transl[q,b] = valid ? g2[1] / (float)n_valid_q : 0, both
+ * formed in fp32 on the device (no host synchronisation). */
+int e2emv_pose_loss_tuple_backward(e2emv_ctx* ctx, int P, int B, const float* d_T, const float* d_T_gt, const float* d_g2, float* d_gT,
+                                   void* stream);
+
 /* ---- timing hooks used by bench.py (HIP events on the caller's stream) -------------
  * After e2emv_profile(ctx, 1) every kernel family launched by the library is bracketed by
  * HIP events on its stream; e2emv_profile_read returns accumulated milliseconds and launch
