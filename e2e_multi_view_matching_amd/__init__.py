@@ -17,9 +17,9 @@ from .pose import (compute_rotation_error, compute_translation_error_as_angle, e
 from .ransac import estimate_pose, estimate_poses_ransac  # noqa: F401,E402
 from .superpoint import SuperPoint  # noqa: F401,E402
 from .targets import (compute_gt_matches_of_image_pair, compute_match_loss, gt_matches_for_tuple,  # noqa: F401,E402
-                      relative_pose)
+                      gt_matches_tuple, match_loss_tuple, relative_pose)
 
-__all__ = ["SuperPoint", "compute_gt_matches_of_image_pair", "compute_match_loss", "gt_matches_for_tuple", "relative_pose",
+__all__ = ["SuperPoint", "compute_gt_matches_of_image_pair", "compute_match_loss", "gt_matches_for_tuple", "gt_matches_tuple", "match_loss_tuple", "relative_pose",
            "run_weighted_8_point_tuple", "pose_loss_tuple", "MultiViewMatcher", "SuperGlue", "estimate_relative_pose_w8pt", "run_weighted_8_point", "get_kpts",
            "run_bundle_adjust_2_view", "normalize", "compute_rotation_error", "compute_translation_error_as_angle", "pose_errors", "pose_auc",
            "compute_pose_error", "log_optimal_transport", "extract_matches", "gemm_nt", "attention", "estimate_pose",

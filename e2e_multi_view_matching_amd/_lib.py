@@ -168,6 +168,10 @@ SIGNATURES = {
     "e2emv_w8pt_tuple_backward": (c_int, [c_void_p, c_int, c_int, c_int, _PP, _PP, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, _PP, c_void_p]),
     "e2emv_pose_loss_tuple": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "e2emv_pose_loss_tuple_backward": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "e2emv_gt_matches_tuple": (c_int, [c_void_p, c_int, c_int, c_int, _PP, _PP, _PP, _PP, c_int, c_int, c_float, c_float, c_void_p, c_void_p,
+                                       c_void_p]),
+    "e2emv_match_loss_tuple": (c_int, [c_void_p, c_int, c_int, c_int, _PP, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "e2emv_match_loss_tuple_backward": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, _PP, c_void_p]),
     "e2emv_get_stats": (c_int, [c_void_p, ctypes.POINTER(ctypes.c_uint64), c_int, c_int]),
     "e2emv_set_sinkhorn_kernel": (c_int, [c_void_p, c_int]),
     "e2emv_sinkhorn_plan": (c_int, [c_void_p, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int), c_int]),

@@ -900,28 +900,7 @@ __global__ __launch_bounds__(64) void pose_loss_tuple_kernel(int P, int B, const
 __global__ void relative_pose_kernel(int B, const float* pose_a, const float* pose_b, float* out) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
-    double M[4][8];
-    for (int r = 0; r < 4; ++r)
-        for (int c = 0; c < 4; ++c) {
-            M[r][c] = pose_b[(int64_t)b * 16 + r * 4 + c];
-            M[r][4 + c] = pose_a[(int64_t)b * 16 + r * 4 + c];
-        }
-    for (int c = 0; c < 4; ++c) {
-        int piv = c;
-        for (int r = c + 1; r < 4; ++r)
-            if (fabs(M[r][c]) > fabs(M[piv][c])) piv = r;
-        if (piv != c)
-            for (int k = 0; k < 8; ++k) { const double t = M[c][k]; M[c][k] = M[piv][k]; M[piv][k] = t; }
-        const double d = 1.0 / M[c][c];
-        for (int k = 0; k < 8; ++k) M[c][k] *= d;
-        for (int r = 0; r < 4; ++r)
-            if (r != c) {
-                const double f = M[r][c];
-                for (int k = 0; k < 8; ++k) M[r][k] -= f * M[c][k];
-            }
-    }
-    for (int r = 0; r < 4; ++r)
-        for (int c = 0; c < 4; ++c) out[(int64_t)b * 16 + r * 4 + c] = (float)M[r][4 + c];
+    relative_pose_one(pose_a + (int64_t)b * 16, pose_b + (int64_t)b * 16, out + (int64_t)b * 16);
 }
 
 __global__ void apply_mask_kernel(int64_t n, const float* x, const uint8_t* mask, float* out) {

@@ -93,4 +93,32 @@ __device__ __forceinline__ void triangulate_xyz(double x1, double y1, double x2,
     Xo[0] = X[0] * sc; Xo[1] = X[1] * sc; Xo[2] = X[2] * sc;
 }
 
+// out = inv(pose_b) @ pose_a for general 4x4 matrices (helpers.py:219, 254): Gauss-Jordan with partial pivoting in fp64, rounded
+// once to fp32.  One statement for e2emv_relative_pose (pose.hip) and for the targets of a whole tuple (gtmatch.hip), which
+// have to agree to the bit.
+__device__ __forceinline__ void relative_pose_one(const float* pose_a, const float* pose_b, float* out) {
+    double M[4][8];
+    for (int r = 0; r < 4; ++r)
+        for (int c = 0; c < 4; ++c) {
+            M[r][c] = pose_b[r * 4 + c];
+            M[r][4 + c] = pose_a[r * 4 + c];
+        }
+    for (int c = 0; c < 4; ++c) {
+        int piv = c;
+        for (int r = c + 1; r < 4; ++r)
+            if (fabs(M[r][c]) > fabs(M[piv][c])) piv = r;
+        if (piv != c)
+            for (int k = 0; k < 8; ++k) { const double t = M[c][k]; M[c][k] = M[piv][k]; M[piv][k] = t; }
+        const double d = 1.0 / M[c][c];
+        for (int k = 0; k < 8; ++k) M[c][k] *= d;
+        for (int r = 0; r < 4; ++r)
+            if (r != c) {
+                const double f = M[r][c];
+                for (int k = 0; k < 8; ++k) M[r][k] -= f * M[c][k];
+            }
+    }
+    for (int r = 0; r < 4; ++r)
+        for (int c = 0; c < 4; ++c) out[r * 4 + c] = (float)M[r][4 + c];
+}
+
 }  // namespace e2emv

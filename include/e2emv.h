@@ -775,6 +775,36 @@ int e2emv_pose_loss_tuple(e2emv_ctx* ctx, int P, int B, const float* d_T, const 
 int e2emv_pose_loss_tuple_backward(e2emv_ctx* ctx, int P, int B, const float* d_T, const float* d_T_gt, const float* d_g2, float* d_gT,
                                    void* stream);
 
+/* ---- the match term of a training step for all pairs of a tuple (helpers.run_matcher, helpers.py:243-253) ----
+ * Pair order as everywhere: q counts (i, j) for j in range(T): for i in range(j); P = T(T-1)/2; pair-major buffers [P,B,...].
+ *
+ * e2emv_gt_matches of every pair of B tuples of T images in one call: d_kpts / d_K / d_pose / d_depth are HOST arrays of T DEVICE
+ * pointers (image t: [B,N,2], [B,4,4], [B,4,4] = data["pose t"], [B,H,W]).  The relative pose of pair (i, j), inv(pose_j) @ pose_i,
+ * is formed on the device with the arithmetic of e2emv_relative_pose and rounded to fp32 as that entry stores it; the three
+ * kernels of e2emv_gt_matches then run with the pair as one more grid dimension.  d_indices [P,B,2,N+1] int64 and d_weights
+ * [P,B,2,N+1] fp32 are, bit for bit, the stacked outputs of e2emv_relative_pose + e2emv_gt_matches per pair.  Four launches
+ * whatever P and B, no host synchronisation.  E2EMV_ESHAPE: T outside 2..E2EMV_MAX_TUPLE or B, N, H, W <= 0; E2EMV_EINVAL: a NULL
+ * context, table, table entry or output; nothing is launched then. */
+int e2emv_gt_matches_tuple(e2emv_ctx* ctx, int B, int T, int N, const float* const* d_kpts, const float* const* d_K,
+                           const float* const* d_pose, const float* const* d_depth, int H, int W, float max_matched_reproj_err,
+                           float min_unmatched_reproj_err, int64_t* d_indices, float* d_weights, void* stream);
+
+/* d_logZ = HOST array of P DEVICE pointers [B,N+1,N+1]; d_indices / d_weights [P,B,2,N+1] as above.  The loss of pair q is
+ * e2emv_match_loss to the bit (fp64 partial sums per batch element, folded in ascending b, divided by B, cast to fp32) and goes
+ * to d_pair_loss[q] (DEVICE, [P], may be NULL); d_loss[0] is their fp32 sum in ascending q starting from 0.0f, the order of
+ * `match_loss = match_loss + ...`.  Two launches.  E2EMV_ESHAPE: P outside 1..28 or B, N <= 0. */
+int e2emv_match_loss_tuple(e2emv_ctx* ctx, int P, int B, int N, const float* const* d_logZ, const int64_t* d_indices,
+                           const float* d_weights, float* d_loss, float* d_pair_loss, void* stream);
+
+/* Backward of e2emv_match_loss_tuple to the scores, one launch that does not read them: d_g = DEVICE pointer to dL/d loss;
+ * d_glogZ = HOST array of P DEVICE pointers [B,N+1,N+1] (4-byte alignment suffices; a NULL entry leaves that pair out).  With
+ * ft = N+1, gb = g / (float)B in fp32, col0(r) = idx0[r] < 0 ? idx0[r] + ft : idx0[r] and row1(c) likewise from idx1[c]:
+ *   d_glogZ[q][b][r][c] = (c == col0(r) ? -(gb * w0[r]) : 0) + (r == row1(c) ? -(gb * w1[c]) : 0)
+ * EVERY element is written (the buffers may hold anything on entry; no memset, no atomics); an index outside [-ft, ft) contributes
+ * nothing.  E2EMV_ESHAPE: P outside 1..28, B outside 1..16383, N outside 1..46338. */
+int e2emv_match_loss_tuple_backward(e2emv_ctx* ctx, int P, int B, int N, const int64_t* d_indices, const float* d_weights,
+                                    const float* d_g, float* const* d_glogZ, void* stream);
+
 /* ---- timing hooks used by bench.py (HIP events on the caller's stream) -------------
  * After e2emv_profile(ctx, 1) every kernel family launched by the library is bracketed by
  * HIP events on its stream; e2emv_profile_read returns accumulated milliseconds and launch
