@@ -300,12 +300,13 @@ class Context:
                 "sinkhorn_timeouts": int(v[4]),  # (of the rescued: given up on a wait - contention -, not on range)
                 "sinkhorn_rows128_calls": int(v[5])}  # (Sinkhorn calls on 128-row workgroups: fewer rounds for a large batch)
 
-    SINKHORN_KERNELS = {None: 0, "auto": 0, "rows64": 1, "rows128": 2, "stream": 3}
+    SINKHORN_KERNELS = {None: 0, "auto": 0, "rows64": 1, "rows128": 2, "stream": 3, "rows128w": 4}
 
     def set_sinkhorn_kernel(self, kernel=None):
         """Pins the Sinkhorn kernel of every later call on this context: None / "auto" = by shape and batch size (default),
-        "rows64" / "rows128" = one resident kernel kind (a problem's result is then independent of its batch neighbours, bit
-        for bit), "stream" = the log-domain launch chain.  The E2EMV_SINKHORN variable only sets the value a context starts with."""
+        "rows64" / "rows128" / "rows128w" = one resident kernel kind (a problem's result is then independent of its batch
+        neighbours, bit for bit; "rows128w" = the 128-row kernel on 8 waves, the one "auto" takes at 513 .. 1024 columns),
+        "stream" = the log-domain launch chain.  The E2EMV_SINKHORN variable only sets the value a context starts with."""
         self.call("e2emv_set_sinkhorn_kernel", self.SINKHORN_KERNELS[kernel])
         self.sinkhorn_kernel_pin = self.SINKHORN_KERNELS[kernel]
 
@@ -329,6 +330,7 @@ class Context:
         self.default_precision = other.default_precision
         self.default_f16x2_kernels = other.default_f16x2_kernels
         self.call("e2emv_set_sinkhorn_kernel", getattr(other, "sinkhorn_kernel_pin", 0))
+        self.sinkhorn_kernel_pin = getattr(other, "sinkhorn_kernel_pin", 0)
         self.call("e2emv_set_attention_key_split", 1 if getattr(other, "attention_key_split", True) else 0)
         want = getattr(other, "split_min_rows", -1)
         if getattr(self, "split_min_rows", -1) != want:

@@ -133,6 +133,7 @@ int e2emv_create(e2emv_ctx** out, int device) {
 
     if (const char* e = getenv("E2EMV_SINKHORN")) {  // the Sinkhorn kernel pin (e2emv_set_sinkhorn_kernel): read here, once
         ctx->sinkhorn_kernel = strcmp(e, "rows64") == 0 ? E2EMV_SINKHORN_ROWS64 : strcmp(e, "rows128") == 0 ? E2EMV_SINKHORN_ROWS128
+                               : strcmp(e, "rows128w") == 0 ? E2EMV_SINKHORN_ROWS128W
                                : strcmp(e, "stream") == 0 ? E2EMV_SINKHORN_STREAM : E2EMV_SINKHORN_AUTO;
     }
 

@@ -13,6 +13,8 @@
 //                                by number (v64 - v255, a64 - a255; the compiler confined to 56), 8 in LDS - 32 problems resident
 //   sinkhorn_resident2k          the same for <= 2048 columns, 64 rows per workgroup - 8 problems resident instead of 4
 //                                (both: sinkhorn_regs.hip)
+//   sinkhorn_resident128w        128 rows x <= 1024 columns on 8 waves, two per SIMD: 12 of a wave's 16 rows in v64 - v255, 4 in
+//                                LDS, no accumulation registers (sinkhorn_regs2.hip) - the launcher's 128-row kernel of choice
 // followed by sinkhorn_rescue (problems that left fp32's range or gave up on a wait: re-solved in the log domain) and the final
 // sweep of the log-domain launch chain (sinkhorn_stream.hip), which is also the fallback for everything the plan does not take.
 #include <algorithm>
@@ -83,6 +85,13 @@ size_t sinkhorn_ws_bytes(int B, int M, int N) { return carve_workspace(nullptr, 
 // ---- the launcher's plan, shared by launch_sinkhorn and the e2emv_sinkhorn_plan query (bench.py reports it instead of re-deriving it)
 struct SkSegment { int b0 = 0, n = 0; SkKernel k; int resident = 0; };
 struct SkPlan { int n_seg = 0; SkSegment seg[2]; };  // n_seg == 0: the log-domain launch chain
+// sinkhorn_resident128w as the automatic 128-row kernel at 513 .. 1024 columns (0.71 against 0.87 ms of the default workload's
+// step), and what one round of it costs in eighths of a round of the 64-row kernel.  Measured at 1024 x 1024, 100 iterations, ms
+// per call: 16 problems 0.619 against 0.574 on the 64-row kernel (1.08), 32 problems 0.661 (1.22 of a full 64-row round of 0.54);
+// 80 problems as 64 + 16 on the 64-row kernel 1.874, all three rounds on this kernel 1.921 - a remainder of one 64-row round
+// stays there, two or more go to one more round of this kernel (profiles/sinkhorn_rows128w.log)
+constexpr bool SK_AUTO_ROWS128W = true;
+constexpr int SK_ROWS128W_ROUND_8THS = 10;  // 1.22, rounded up
 
 // `count`: this is a real call (the demotion counters of the context advance); false for the query
 static int plan_sinkhorn(e2emv_ctx* ctx, int B, int M, int N, int64_t ldS, int iters, bool count, SkPlan& plan) {
@@ -102,13 +111,17 @@ static int plan_sinkhorn(e2emv_ctx* ctx, int B, int M, int N, int64_t ldS, int i
     }
     if (!resident) return E2EMV_OK;
     // A call is served by one or two resident launches (segments of the batch): the kernels with K in registers addressed by number
-    // (sinkhorn_resident128 at 513 .. 1024 columns, sinkhorn_resident2k at 1025 .. 2048: twice the rows per workgroup, twice the
-    // problems resident, a round 1.6 - 1.75 times as long - measured 0.83 - 0.94 against 0.51 - 0.53 ms per 100 iterations at
+    // (sinkhorn_resident128 / 128w at 513 .. 1024 columns, sinkhorn_resident2k at 1025 .. 2048: twice the rows per workgroup, twice the
+    // problems resident, a round 1.6 - 1.75 times as long (sinkhorn_resident128w: 1.1 - 1.25) - measured 0.83 - 0.94 against 0.51 - 0.53 ms per 100 iterations at
     // 1024 x 1024, 1.21 against 0.80 at 2048 x 2048) take every FULL round of theirs, the remainder goes to whichever is cheaper:
     // rounds of the compiler-allocated kernel, or one more round of the big one.  80 problems of 1024 x 1024 = 64 + 16.
     // Pin rows64: never the big kernels; rows128: the big kernel for the whole batch whenever the shape allows it - with a pin a
     // problem's result does not depend on its batch neighbours (tests compare a problem alone with the same problem in a batch).
+    // At 513 .. 1024 columns there are two 128-row kernels: sinkhorn_resident128 (4 waves) is what the pin rows128 means,
+    // sinkhorn_resident128w (8 waves, two per SIMD: the row pass at the full rate of the vector pipe) is the pin rows128w and what
+    // the launcher takes by itself (SK_AUTO_ROWS128W).  The two add a workgroup's column partials in different orders.
     SkKernel kbase, kbig;
+    const bool wide = pin == E2EMV_SINKHORN_ROWS128W || (pin == E2EMV_SINKHORN_AUTO && SK_AUTO_ROWS128W);
     const bool full = N == ldS && N == KT_of(ldS) * 256;
     // granule pairs (16-byte exchange stores / loads): a thread must own an even number of columns and a consumer's column
     // slice must be even
@@ -117,7 +130,7 @@ static int plan_sinkhorn(e2emv_ctx* ctx, int B, int M, int N, int64_t ldS, int i
     kbase = sinkhorn_resident_kernel(KT_of(ldS), full, pairs);
     if (KT_of(ldS) == 4) {
         const int G128 = (M + 127) / 128, cs128 = (N + G128 - 1) / G128;
-        if (cs128 % 2 == 0 && G128 <= 16) kbig = sinkhorn_regs_kernel(4, full && M % 128 == 0);  // (full rows AND columns)
+        if (cs128 % 2 == 0 && G128 <= 16) kbig = wide ? sinkhorn_regs2_kernel(full && M % 128 == 0, G128) : sinkhorn_regs_kernel(4, full && M % 128 == 0);  // (full rows AND columns)
     } else if (KT_of(ldS) == 8) {
         const int G2k = (M + 63) / 64, cs2k = (N + G2k - 1) / G2k;
         if (cs2k % 2 == 0 && G2k <= 64) kbig = sinkhorn_regs_kernel(8, full && M % 64 == 0);
@@ -151,13 +164,16 @@ static int plan_sinkhorn(e2emv_ctx* ctx, int B, int M, int N, int64_t ldS, int i
     };
     if (!kbig.fn || kbase.big || pin == E2EMV_SINKHORN_ROWS64) {
         add(0, B, kbase);
-    } else if (pin == E2EMV_SINKHORN_ROWS128) {
+    } else if (pin == E2EMV_SINKHORN_ROWS128 || pin == E2EMV_SINKHORN_ROWS128W) {
         add(0, B, kbig);
     } else {
         const int res_big = res_of(kbig), res_base = res_of(kbase);
         int n_big = (B / res_big) * res_big;   // every full round of the big kernel (it holds twice the problems at < 2 x the time)
         const int rem = B - n_big;
-        if (rem > 0 && 8 * ((rem + res_base - 1) / res_base) > 13) n_big = B;  // the remainder too: one round of 1.6 against two or more of 1
+        // the remainder too: one round of the big kernel (1.6 base rounds; sinkhorn_resident128w: SK_ROWS128W_ROUND_8THS / 8) against
+        // two or more of the base kernel
+        const int big_round_8ths = (wide && KT_of(ldS) == 4) ? SK_ROWS128W_ROUND_8THS : 13;
+        if (rem > 0 && 8 * ((rem + res_base - 1) / res_base) > big_round_8ths) n_big = B;
         if (n_big > 0) add(0, n_big, kbig);
         if (n_big < B) add(n_big, B - n_big, kbase);
     }
@@ -259,7 +275,7 @@ using namespace e2emv;
 extern "C" int e2emv_set_sinkhorn_kernel(e2emv_ctx* ctx, int kernel) {
     if (!ctx) return E2EMV_EINVAL;
     E2EMV_LOCK(ctx);
-    if (kernel < E2EMV_SINKHORN_AUTO || kernel > E2EMV_SINKHORN_STREAM) return set_err(ctx, E2EMV_EINVAL, "set_sinkhorn_kernel: %d (E2EMV_SINKHORN_AUTO .. _STREAM)", kernel);
+    if (kernel < E2EMV_SINKHORN_AUTO || kernel > E2EMV_SINKHORN_ROWS128W) return set_err(ctx, E2EMV_EINVAL, "set_sinkhorn_kernel: %d (E2EMV_SINKHORN_AUTO .. _ROWS128W)", kernel);
     ctx->sinkhorn_kernel = kernel;
     return E2EMV_OK;
 }

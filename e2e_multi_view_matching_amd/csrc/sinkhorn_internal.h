@@ -1,6 +1,6 @@
 // Sinkhorn, internal: what the files of the family share on the host side.  sinkhorn.hip (workspace, plan, launch) calls the
 // log-domain chain and the match block of sinkhorn_stream.hip through the functions below and gets the resident kernels of
-// sinkhorn_resident.hip / sinkhorn_regs.hip as SkKernel descriptions.  (Other files need only common.h: sinkhorn_ws_bytes,
+// sinkhorn_resident.hip / sinkhorn_regs.hip / sinkhorn_regs2.hip as SkKernel descriptions.  (Other files need only common.h: sinkhorn_ws_bytes,
 // launch_sinkhorn, SinkhornOut.)
 #pragma once
 #include "common.h"
@@ -64,5 +64,8 @@ struct SkKernel { const void* fn = nullptr; int rows = 0, threads = 512, wg_per_
 SkKernel sinkhorn_resident_kernel(int KT, bool full, bool pairs);
 // sinkhorn_regs.hip: sinkhorn_resident128 (KT == 4) / sinkhorn_resident2k (KT == 8), full = full rows AND columns; fn, rows, threads, lds, big
 SkKernel sinkhorn_regs_kernel(int KT, bool full);
+// sinkhorn_regs2.hip: sinkhorn_resident128w (KT == 4: 128 rows per workgroup on 8 waves, two per SIMD), full as above, G = workgroups
+// per problem (the instance's stage-A lane mapping follows the width of a column slice); fn, rows, threads, lds, big
+SkKernel sinkhorn_regs2_kernel(bool full, int G);
 
 }  // namespace e2emv

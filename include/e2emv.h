@@ -656,14 +656,18 @@ int e2emv_get_stats(e2emv_ctx* ctx, uint64_t* stats, int n, int reset);
  * /root/reference/helpers.py:246, eval_pairs.py:212) --------------------------------------------------------------------------
  * E2EMV_SINKHORN_AUTO (default): by shape AND batch size - the kernels with the couplings in registers addressed by number take
  * their full rounds, the remainder goes to the compiler-allocated kernel.  The kernels sum in different orders: a
- * problem's log-assignment can differ by < 2e-5 between two batch compositions.  ROWS64 / ROWS128 pin one kernel kind for every
- * call of the context: a problem's result then does not depend on its batch neighbours, bit for bit.  STREAM = the log-domain
- * launch chain (no resident kernel; also taken for iters == 0).  The initial value comes from the environment variable
- * E2EMV_SINKHORN = rows64 | rows128 | stream, read ONCE at e2emv_create. */
+ * problem's log-assignment can differ by < 2e-5 between two batch compositions.  ROWS64 / ROWS128 / ROWS128W pin one kernel kind
+ * for every call of the context: a problem's result then does not depend on its batch neighbours, bit for bit.  At 513 .. 1024
+ * columns there are two kernels of 128 rows per workgroup: ROWS128 = sinkhorn_resident128 (4 waves, couplings in vector and
+ * accumulation registers), ROWS128W = sinkhorn_resident128w (8 waves, two per SIMD, vector registers only - the one AUTO takes);
+ * elsewhere the two pins mean the same.  STREAM = the log-domain launch chain (no resident kernel; also taken for iters == 0).
+ * The initial value comes from the environment variable E2EMV_SINKHORN = rows64 | rows128 | rows128w | stream, read ONCE at
+ * e2emv_create. */
 #define E2EMV_SINKHORN_AUTO 0
 #define E2EMV_SINKHORN_ROWS64 1
 #define E2EMV_SINKHORN_ROWS128 2
 #define E2EMV_SINKHORN_STREAM 3
+#define E2EMV_SINKHORN_ROWS128W 4
 int e2emv_set_sinkhorn_kernel(e2emv_ctx* ctx, int kernel);
 /* The launcher's plan for a batch of B problems of M x N scores and `iters` iterations on this context (what e2emv_sinkhorn /
  * e2emv_matcher_forward would launch now; nothing is launched): plan[0] = number of resident launches (0 = the log-domain chain, 1
