@@ -99,10 +99,16 @@ SIGNATURES = {
                                        c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "e2emv_mv_bundle_adjust_batch": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                              c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "e2emv_mv_bundle_adjust_batch_backward": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                      c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                      c_void_p, c_void_p]),
     "e2emv_mv_collect": (c_int, [c_void_p, c_int, c_int, c_int, _PP, _PP, c_void_p, _PP, _PP, c_int, c_float, c_void_p, c_void_p, c_void_p,
                                  c_void_p, c_void_p]),
     "e2emv_mv_tuple_ba": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, _PP, c_int, c_int, c_void_p, c_int,
                                   c_void_p, c_void_p, c_void_p]),
+    "e2emv_mv_tuple_ba_backward": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, _PP, c_int, c_int, c_void_p, c_int,
+                                           c_void_p, c_void_p, c_void_p]),
+    "e2emv_mv_collect_backward": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, _PP, _PP, c_int, c_float, c_void_p, _PP, c_void_p]),
     "e2emv_mv_tuple_problem": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, _PP, c_int, c_int, c_void_p,
                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "e2emv_mv_tracks": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, _PP, _PP, c_int, c_float, c_void_p, c_void_p, c_void_p]),

@@ -35,472 +35,7 @@
 
 namespace e2emv {
 
-// block-wide reduction of up to 4 values (sum for k < nsum, max for the rest); all threads get the result
-template <int NV, int NSUM>
-__device__ __forceinline__ void mv_block_reduce(double (&v)[NV], double* scratch /* [kMvWaves*NV] */) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < NV; ++k) v[k] = k < NSUM ? wave_sum_d(v[k]) : mv_wmax(v[k]);
-    __syncthreads();
-    if (lane == 0)
-#pragma unroll
-        for (int k = 0; k < NV; ++k) scratch[wave * NV + k] = v[k];
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < NV; ++k) {
-        double a = scratch[k];
-        for (int w = 1; w < kMvWaves; ++w) a = k < NSUM ? a + scratch[w * NV + k] : fmax(a, scratch[w * NV + k]);
-        v[k] = a;
-    }
-}
-
-// p = R(w) X + t and (optionally) R and dp/dw (ceres::AngleAxisRotatePoint under autodiff: Rodrigues for theta^2 > eps,
-// first-order X + w x X below).  identity: the fixed camera.
-__device__ __forceinline__ void mv_transform(const double* cam, bool identity, const double X[3], double p[3], double R[9] /*row-major*/,
-                                             double D[9] /* dp/dw row-major */, bool jac) {
-    if (identity) {
-        p[0] = X[0]; p[1] = X[1]; p[2] = X[2];
-        if (jac) {
-            R[0] = 1; R[1] = 0; R[2] = 0; R[3] = 0; R[4] = 1; R[5] = 0; R[6] = 0; R[7] = 0; R[8] = 1;
-#pragma unroll
-            for (int i = 0; i < 9; ++i) D[i] = 0;
-        }
-        return;
-    }
-    const double w0 = cam[0], w1 = cam[1], w2 = cam[2];
-    const double t2 = w0 * w0 + w1 * w1 + w2 * w2;
-    double Rl[9];
-    const bool big = t2 > 2.220446049250313e-16;
-    if (big) {
-        const double th = sqrt(t2), k0 = w0 / th, k1 = w1 / th, k2 = w2 / th;
-        const double s = sin(th), c = cos(th), v = 1.0 - c;
-        // R = I + s K + v K^2
-        Rl[0] = 1 - v * (k1 * k1 + k2 * k2); Rl[1] = -s * k2 + v * k0 * k1;       Rl[2] = s * k1 + v * k0 * k2;
-        Rl[3] = s * k2 + v * k0 * k1;        Rl[4] = 1 - v * (k0 * k0 + k2 * k2); Rl[5] = -s * k0 + v * k1 * k2;
-        Rl[6] = -s * k1 + v * k0 * k2;       Rl[7] = s * k0 + v * k1 * k2;        Rl[8] = 1 - v * (k0 * k0 + k1 * k1);
-    } else {
-        Rl[0] = 1; Rl[1] = -w2; Rl[2] = w1; Rl[3] = w2; Rl[4] = 1; Rl[5] = -w0; Rl[6] = -w1; Rl[7] = w0; Rl[8] = 1;
-    }
-#pragma unroll
-    for (int i = 0; i < 3; ++i) p[i] = Rl[3 * i] * X[0] + Rl[3 * i + 1] * X[1] + Rl[3 * i + 2] * X[2] + cam[3 + i];
-    if (!jac) return;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) R[i] = Rl[i];
-    // [X]x
-    const double Xh[9] = {0, -X[2], X[1], X[2], 0, -X[0], -X[1], X[0], 0};
-    if (!big) {
-#pragma unroll
-        for (int i = 0; i < 9; ++i) D[i] = -Xh[i];
-        return;
-    }
-    // G = (w w^T + (R^T - I) [w]x) / theta^2 ;  D = -R [X]x G
-    const double wh[9] = {0, -w2, w1, w2, 0, -w0, -w1, w0, 0};
-    const double w[3] = {w0, w1, w2};
-    double G[9], T[9];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            double a = w[i] * w[j];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) a += (Rl[3 * k + i] - (k == i ? 1.0 : 0.0)) * wh[3 * k + j];
-            G[3 * i + j] = a / t2;
-        }
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) T[3 * i + j] = Xh[3 * i] * G[j] + Xh[3 * i + 1] * G[3 + j] + Xh[3 * i + 2] * G[6 + j];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) D[3 * i + j] = -(Rl[3 * i] * T[j] + Rl[3 * i + 1] * T[3 + j] + Rl[3 * i + 2] * T[6 + j]);
-}
-
-// One workgroup per problem: blockIdx.x selects the problem's record (sizes, intrinsics, fixed camera and the addresses of
-// ITS slices of the shared index / data / scratch arrays and of its summary slot).  Nothing below knows of the other
-// workgroups: several problems may share a CU (24 KB of LDS, 8 waves each), none shares a byte of global memory.
-// LOSS: the robust loss (mvba.h).  Only phases A and H know of it: A stores the CORRECTED r, Jc, Jp (scaled by sqrt(rho')) and sums
-// rho(s) into the cost, H sums rho(s) at the candidate; B - G and the model cost change read the stored arrays as they are.  The
-// kLossNone instantiation is the kernel as it always was, operation for operation.
-template <int LOSS>
-__global__ __launch_bounds__(kMvThreads) void mvba_kernel(const MvbaArgs* __restrict__ recs) {
-    const MvbaArgs& a = recs[blockIdx.x];
-    const double loss_a = LOSS != kLossNone ? a.loss_a : 0.0, loss_a2 = loss_a * loss_a;
-    __shared__ double s_cams[kMvN], s_cand[kMvN], s_scale[kMvN], s_lam[kMvN], s_gc[kMvN], s_dc[kMvN], s_rhs[kMvN];
-    __shared__ double s_U[kMvMaxCams * 36];
-    __shared__ double s_S[kMvN * kMvN];
-    __shared__ double s_red[kMvWaves * 4];
-    __shared__ double s_ctl[8];  // 0 radius 1 decrease 2 cost 3 - 4 - 5 solve ok
-    __shared__ int s_fidx[kMvMaxCams], s_free[kMvMaxCams], s_state[4];  // state: 0 stop flag, 1 iterations, 2 termination, 3 invalid count
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int C = a.C, P = a.P, O = a.O;
-
-    if (tid < 6 * C) s_cams[tid] = a.cams[tid];
-    if (tid == 0) {
-        int F = 0;
-        for (int c = 0; c < C; ++c) {
-            s_fidx[c] = (c == a.fixed) ? -1 : F;
-            if (c != a.fixed) s_free[F++] = c;
-        }
-        s_state[0] = 0; s_state[1] = 0; s_state[2] = kTermMaxIter; s_state[3] = 0;
-        s_ctl[0] = 1e4; s_ctl[1] = 2.0;
-    }
-    __syncthreads();
-    int F = 0;
-    for (int c = 0; c < C; ++c) F += (c != a.fixed);
-    const int n = 6 * F;
-    bool first = true;
-
-    while (true) {
-        // ---- A: residuals, Jacobians, cost at the current iterate ------------------------------------------------
-        double red[4] = {0, 0, 0, 0};
-        for (int o = tid; o < O; o += kMvThreads) {
-            const int c = a.cam_idx[o], p = a.pt_idx[o];
-            const double X[3] = {a.pts[3 * p], a.pts[3 * p + 1], a.pts[3 * p + 2]};
-            double q[3], R[9], D[9];
-            const bool fixed = (c == a.fixed);
-            mv_transform(&s_cams[6 * c], fixed, X, q, R, D, true);
-            const double iz = 1.0 / q[2], wx = a.wts[2 * o], wy = a.wts[2 * o + 1];
-            double rx = wx * (a.fx * q[0] * iz + a.cx - a.obs[2 * o]), ry = wy * (a.fy * q[1] * iz + a.cy - a.obs[2 * o + 1]);
-            // d(residual)/d(q): rows weighted
-            double e00 = wx * a.fx * iz, e02 = -wx * a.fx * q[0] * iz * iz, e11 = wy * a.fy * iz, e12 = -wy * a.fy * q[1] * iz * iz;
-            if (LOSS == kLossNone) {
-                red[0] += rx * rx + ry * ry;
-            } else {
-                // the corrector: residual and both Jacobian blocks (through the rows of d(residual)/d(q)) times sqrt(rho')
-                double rho, sq;
-                mv_loss<LOSS>(rx * rx + ry * ry, loss_a, loss_a2, &rho, &sq);
-                red[0] += rho;
-                rx *= sq; ry *= sq;
-                e00 *= sq; e02 *= sq; e11 *= sq; e12 *= sq;
-            }
-            a.r[2 * o] = rx; a.r[2 * o + 1] = ry;
-            double* jc = a.Jc + 12 * size_t(o);
-            double* jp = a.Jp + 6 * size_t(o);
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                jc[k] = fixed ? 0.0 : e00 * D[k] + e02 * D[6 + k];
-                jc[6 + k] = fixed ? 0.0 : e11 * D[3 + k] + e12 * D[6 + k];
-                jp[k] = e00 * R[k] + e02 * R[6 + k];
-                jp[3 + k] = e11 * R[3 + k] + e12 * R[6 + k];
-            }
-            jc[3] = fixed ? 0.0 : e00; jc[4] = 0.0; jc[5] = fixed ? 0.0 : e02;
-            jc[9] = 0.0; jc[10] = fixed ? 0.0 : e11; jc[11] = fixed ? 0.0 : e12;
-        }
-        {
-            double v[1] = {red[0]};
-            mv_block_reduce<1, 1>(v, s_red);
-            if (tid == 0) {
-                s_ctl[2] = 0.5 * v[0];
-                if (first) a.summary[0] = 0.5 * v[0];
-            }
-        }
-        // ---- C: camera blocks U_c, g_c (a wave per free camera) -------------------------------------------------
-        __syncthreads();  // Jc / r of all observations are in memory
-        for (int f = wave; f < F; f += kMvWaves) {
-            const int c = s_free[f];
-            double u[21], g[6];
-#pragma unroll
-            for (int i = 0; i < 21; ++i) u[i] = 0;
-#pragma unroll
-            for (int i = 0; i < 6; ++i) g[i] = 0;
-            for (int k = a.cam_start[c] + lane; k < a.cam_start[c + 1]; k += 64) {
-                const int o = a.cam_obs[k];
-                const double* jc = a.Jc + 12 * size_t(o);
-                double j0[6], j1[6];
-#pragma unroll
-                for (int i = 0; i < 6; ++i) { j0[i] = jc[i]; j1[i] = jc[6 + i]; }
-                const double rx = a.r[2 * o], ry = a.r[2 * o + 1];
-                int t = 0;
-#pragma unroll
-                for (int i = 0; i < 6; ++i) {
-                    g[i] += j0[i] * rx + j1[i] * ry;
-#pragma unroll
-                    for (int j = 0; j <= i; ++j) u[t++] += j0[i] * j0[j] + j1[i] * j1[j];
-                }
-            }
-#pragma unroll
-            for (int i = 0; i < 21; ++i) u[i] = wave_sum_d(u[i]);
-#pragma unroll
-            for (int i = 0; i < 6; ++i) g[i] = wave_sum_d(g[i]);
-            if (lane == 0) {
-                int t = 0;
-                for (int i = 0; i < 6; ++i) {
-                    s_gc[6 * f + i] = g[i];
-                    for (int j = 0; j <= i; ++j) { s_U[36 * f + 6 * i + j] = u[t]; s_U[36 * f + 6 * j + i] = u[t]; ++t; }
-                }
-            }
-        }
-        __syncthreads();
-        // ---- D: camera scaling / damping, camera part of the gradient norm --------------------------------------
-        double gmax = 0.0;
-        if (tid < n) {
-            const double d = s_U[36 * (tid / 6) + 7 * (tid % 6)];
-            if (first) s_scale[tid] = 1.0 / (1.0 + sqrt(d));
-            const double sc = s_scale[tid];
-            s_lam[tid] = fmin(fmax(d * sc * sc, 1e-6), 1e32) / s_ctl[0] / (sc * sc);
-            gmax = fabs(s_gc[tid]);
-        }
-        // ---- B: point blocks ---------------------------------------------------------------------------------------
-        const double radius = s_ctl[0];
-        for (int p = tid; p < P; p += kMvThreads) {
-            double V[6] = {0, 0, 0, 0, 0, 0}, g[3] = {0, 0, 0};  // V: 00 10 11 20 21 22
-            for (int k = a.pt_start[p]; k < a.pt_start[p + 1]; ++k) {
-                const int o = a.pt_obs[k];
-                const double* jp = a.Jp + 6 * size_t(o);
-                const double rx = a.r[2 * o], ry = a.r[2 * o + 1];
-                V[0] += jp[0] * jp[0] + jp[3] * jp[3];
-                V[1] += jp[1] * jp[0] + jp[4] * jp[3];
-                V[2] += jp[1] * jp[1] + jp[4] * jp[4];
-                V[3] += jp[2] * jp[0] + jp[5] * jp[3];
-                V[4] += jp[2] * jp[1] + jp[5] * jp[4];
-                V[5] += jp[2] * jp[2] + jp[5] * jp[5];
-                g[0] += jp[0] * rx + jp[3] * ry;
-                g[1] += jp[1] * rx + jp[4] * ry;
-                g[2] += jp[2] * rx + jp[5] * ry;
-            }
-            const double d[3] = {V[0], V[2], V[5]};
-            double lam[3];
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                double sc;
-                if (first) { sc = 1.0 / (1.0 + sqrt(d[i])); a.scale_p[3 * p + i] = sc; }
-                else sc = a.scale_p[3 * p + i];
-                lam[i] = fmin(fmax(d[i] * sc * sc, 1e-6), 1e32) / radius / (sc * sc);
-                gmax = fmax(gmax, fabs(g[i]));
-                a.gp[3 * p + i] = g[i];
-            }
-            const double m00 = V[0] + lam[0], m10 = V[1], m11 = V[2] + lam[1], m20 = V[3], m21 = V[4], m22 = V[5] + lam[2];
-            // inverse of the symmetric 3x3 through its adjugate
-            const double c00 = m11 * m22 - m21 * m21, c10 = m20 * m21 - m10 * m22, c20 = m10 * m21 - m20 * m11;
-            const double det = m00 * c00 + m10 * c10 + m20 * c20, id = 1.0 / det;
-            const double i00 = c00 * id, i10 = c10 * id, i20 = c20 * id, i11 = (m00 * m22 - m20 * m20) * id, i21 = (m10 * m20 - m00 * m21) * id,
-                         i22 = (m00 * m11 - m10 * m10) * id;
-            double* vi = a.Vinv + 6 * size_t(p);
-            vi[0] = i00; vi[1] = i10; vi[2] = i11; vi[3] = i20; vi[4] = i21; vi[5] = i22;
-            for (int k = a.pt_start[p]; k < a.pt_start[p + 1]; ++k) {
-                const int o = a.pt_obs[k];
-                if (a.cam_idx[o] == a.fixed) continue;
-                const double* jc = a.Jc + 12 * size_t(o);
-                const double* jp = a.Jp + 6 * size_t(o);
-                double* y = a.Y + 18 * size_t(o);
-#pragma unroll
-                for (int i = 0; i < 6; ++i) {
-                    const double w0 = jc[i] * jp[0] + jc[6 + i] * jp[3], w1 = jc[i] * jp[1] + jc[6 + i] * jp[4], w2 = jc[i] * jp[2] + jc[6 + i] * jp[5];
-                    y[3 * i] = w0 * i00 + w1 * i10 + w2 * i20;
-                    y[3 * i + 1] = w0 * i10 + w1 * i11 + w2 * i21;
-                    y[3 * i + 2] = w0 * i20 + w1 * i21 + w2 * i22;
-                }
-            }
-        }
-        {
-            double v[1] = {gmax};
-            mv_block_reduce<1, 0>(v, s_red);  // also orders the Y / Vinv / gp writes before phase E
-            if (tid == 0) {
-                if (v[0] <= 1e-10) { s_state[0] = 1; s_state[2] = kTermGradient; }
-                else if (s_state[1] >= a.max_iters) { s_state[0] = 1; }
-                else s_state[1] += 1;
-            }
-        }
-        first = false;
-        __syncthreads();
-        if (s_state[0]) break;
-        // ---- E: reduced camera system (a wave per block of the upper triangle) ----------------------------------
-        const int nblk = F * (F + 1) / 2;
-        for (int blk = wave; blk < nblk; blk += kMvWaves) {
-            int fa = 0, rem = blk;
-            while (rem >= F - fa) { rem -= F - fa; ++fa; }
-            const int fb = fa + rem, ca = s_free[fa], cb = s_free[fb];
-            double acc[36], rh[6];
-#pragma unroll
-            for (int i = 0; i < 36; ++i) acc[i] = 0;
-#pragma unroll
-            for (int i = 0; i < 6; ++i) rh[i] = 0;
-            for (int k = a.cam_start[ca] + lane; k < a.cam_start[ca + 1]; k += 64) {
-                const int o = a.cam_obs[k], p = a.pt_idx[o];
-                double y[18];
-                const double* yo = a.Y + 18 * size_t(o);
-#pragma unroll
-                for (int i = 0; i < 18; ++i) y[i] = yo[i];
-                if (fa == fb) {
-                    const double g0 = a.gp[3 * p], g1 = a.gp[3 * p + 1], g2 = a.gp[3 * p + 2];
-#pragma unroll
-                    for (int i = 0; i < 6; ++i) rh[i] += y[3 * i] * g0 + y[3 * i + 1] * g1 + y[3 * i + 2] * g2;
-                }
-                for (int k2 = a.pt_start[p]; k2 < a.pt_start[p + 1]; ++k2) {
-                    const int o2 = a.pt_obs[k2];
-                    if (a.cam_idx[o2] != cb) continue;
-                    const double* jc = a.Jc + 12 * size_t(o2);
-                    const double* jp = a.Jp + 6 * size_t(o2);
-#pragma unroll
-                    for (int j = 0; j < 6; ++j) {
-                        const double w0 = jc[j] * jp[0] + jc[6 + j] * jp[3], w1 = jc[j] * jp[1] + jc[6 + j] * jp[4], w2 = jc[j] * jp[2] + jc[6 + j] * jp[5];
-#pragma unroll
-                        for (int i = 0; i < 6; ++i) acc[6 * i + j] += y[3 * i] * w0 + y[3 * i + 1] * w1 + y[3 * i + 2] * w2;
-                    }
-                }
-            }
-#pragma unroll
-            for (int i = 0; i < 36; ++i) acc[i] = wave_sum_d(acc[i]);
-            if (fa == fb)
-#pragma unroll
-                for (int i = 0; i < 6; ++i) rh[i] = wave_sum_d(rh[i]);
-            if (lane == 0) {
-                for (int i = 0; i < 6; ++i) {
-                    for (int j = 0; j < 6; ++j) {
-                        double v = -acc[6 * i + j];
-                        if (fa == fb) v += s_U[36 * fa + 6 * i + j] + (i == j ? s_lam[6 * fa + i] : 0.0);
-                        s_S[(6 * fa + i) * kMvN + 6 * fb + j] = v;
-                        if (fa != fb) s_S[(6 * fb + j) * kMvN + 6 * fa + i] = v;
-                    }
-                    if (fa == fb) s_rhs[6 * fa + i] = -s_gc[6 * fa + i] + rh[i];
-                }
-            }
-        }
-        __syncthreads();
-        // ---- F: Cholesky + solves by wave 0 (lane = row) -------------------------------------------------------
-        if (wave == 0) {
-            bool ok = true;
-            // a camera without observations has an all-zero row: keep it at zero step
-            for (int j = 0; j < n && ok; ++j) {
-                double s = 0.0;
-                if (lane >= j && lane < n) {
-                    s = s_S[lane * kMvN + j];
-                    for (int k = 0; k < j; ++k) s -= s_S[lane * kMvN + k] * s_S[j * kMvN + k];
-                }
-                const double d = __shfl(s, j);
-                if (!(d > 0.0)) { ok = false; break; }
-                const double sd = sqrt(d);
-                if (lane >= j && lane < n) s_S[lane * kMvN + j] = (lane == j) ? sd : s / sd;
-                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-            }
-            if (ok) {
-                double b = lane < n ? s_rhs[lane] : 0.0;
-                for (int j = 0; j < n; ++j) {  // L y = b
-                    const double yj = __shfl(b, j) / s_S[j * kMvN + j];
-                    if (lane == j) b = yj;
-                    else if (lane > j && lane < n) b -= s_S[lane * kMvN + j] * yj;
-                }
-                for (int j = n - 1; j >= 0; --j) {  // L^T x = y
-                    const double xj = __shfl(b, j) / s_S[j * kMvN + j];
-                    if (lane == j) b = xj;
-                    else if (lane < j) b -= s_S[j * kMvN + lane] * xj;
-                }
-                if (lane < n) s_dc[lane] = b;
-            }
-            if (lane == 0) s_ctl[5] = ok ? 1.0 : 0.0;
-        }
-        __syncthreads();
-        const bool solved = s_ctl[5] != 0.0;
-        double r4[4] = {0, 0, 0, 0};  // step norm^2, x norm^2, model change, candidate cost*2
-        if (solved) {
-            if (tid < n) {
-                const int c = s_free[tid / 6];
-                s_cand[6 * c + tid % 6] = s_cams[6 * c + tid % 6] + s_dc[tid];
-                r4[0] += s_dc[tid] * s_dc[tid];
-                r4[1] += s_cams[6 * c + tid % 6] * s_cams[6 * c + tid % 6];
-            }
-            if (tid < 6 && a.fixed >= 0 && a.fixed < C) s_cand[6 * a.fixed + tid] = s_cams[6 * a.fixed + tid];
-            // ---- G: point steps ------------------------------------------------------------------------------------
-            for (int p = tid; p < P; p += kMvThreads) {
-                double g0 = a.gp[3 * p], g1 = a.gp[3 * p + 1], g2 = a.gp[3 * p + 2];
-                for (int k = a.pt_start[p]; k < a.pt_start[p + 1]; ++k) {
-                    const int o = a.pt_obs[k], f = s_fidx[a.cam_idx[o]];
-                    if (f < 0) continue;
-                    const double* jc = a.Jc + 12 * size_t(o);
-                    const double* jp = a.Jp + 6 * size_t(o);
-                    double q0 = 0, q1 = 0;
-#pragma unroll
-                    for (int i = 0; i < 6; ++i) { q0 += jc[i] * s_dc[6 * f + i]; q1 += jc[6 + i] * s_dc[6 * f + i]; }
-                    g0 += jp[0] * q0 + jp[3] * q1;
-                    g1 += jp[1] * q0 + jp[4] * q1;
-                    g2 += jp[2] * q0 + jp[5] * q1;
-                }
-                const double* vi = a.Vinv + 6 * size_t(p);
-                const double d0 = -(vi[0] * g0 + vi[1] * g1 + vi[3] * g2), d1 = -(vi[1] * g0 + vi[2] * g1 + vi[4] * g2),
-                             d2 = -(vi[3] * g0 + vi[4] * g1 + vi[5] * g2);
-                a.dp[3 * p] = d0; a.dp[3 * p + 1] = d1; a.dp[3 * p + 2] = d2;
-                const double x0 = a.pts[3 * p], x1 = a.pts[3 * p + 1], x2 = a.pts[3 * p + 2];
-                a.cand[3 * p] = x0 + d0; a.cand[3 * p + 1] = x1 + d1; a.cand[3 * p + 2] = x2 + d2;
-                r4[0] += d0 * d0 + d1 * d1 + d2 * d2;
-                r4[1] += x0 * x0 + x1 * x1 + x2 * x2;
-            }
-            __syncthreads();
-            // ---- H: model cost change and candidate cost ----------------------------------------------------------
-            for (int o = tid; o < O; o += kMvThreads) {
-                const int c = a.cam_idx[o], p = a.pt_idx[o], f = s_fidx[c];
-                const double* jc = a.Jc + 12 * size_t(o);
-                const double* jp = a.Jp + 6 * size_t(o);
-                const double d0 = a.dp[3 * p], d1 = a.dp[3 * p + 1], d2 = a.dp[3 * p + 2];
-                double m0 = jp[0] * d0 + jp[1] * d1 + jp[2] * d2, m1 = jp[3] * d0 + jp[4] * d1 + jp[5] * d2;
-                if (f >= 0)
-#pragma unroll
-                    for (int i = 0; i < 6; ++i) { m0 += jc[i] * s_dc[6 * f + i]; m1 += jc[6 + i] * s_dc[6 * f + i]; }
-                r4[2] -= m0 * (a.r[2 * o] + 0.5 * m0) + m1 * (a.r[2 * o + 1] + 0.5 * m1);
-                const double X[3] = {a.cand[3 * p], a.cand[3 * p + 1], a.cand[3 * p + 2]};
-                double q[3];
-                mv_transform(&s_cand[6 * c], c == a.fixed, X, q, nullptr, nullptr, false);
-                const double iz = 1.0 / q[2];
-                const double rx = a.wts[2 * o] * (a.fx * q[0] * iz + a.cx - a.obs[2 * o]), ry = a.wts[2 * o + 1] * (a.fy * q[1] * iz + a.cy - a.obs[2 * o + 1]);
-                if (LOSS == kLossNone) {
-                    r4[3] += rx * rx + ry * ry;
-                } else {
-                    double rho, sq;
-                    mv_loss<LOSS>(rx * rx + ry * ry, loss_a, loss_a2, &rho, &sq);
-                    r4[3] += rho;
-                }
-            }
-        }
-        mv_block_reduce<4, 4>(r4, s_red);
-        // ---- I: trust-region bookkeeping (thread 0) --------------------------------------------------------------
-        if (tid == 0) {
-            const double cost = s_ctl[2], model = r4[2], cand_cost = 0.5 * r4[3];
-            s_ctl[6] = 0.0;  // accept flag
-            if (!solved || !(model > 0.0)) {
-                s_state[3] += 1;
-                if (s_state[3] >= 5) { s_state[0] = 1; s_state[2] = kTermInvalid; }
-                s_ctl[0] /= s_ctl[1];
-                s_ctl[1] *= 2.0;
-            } else {
-                s_state[3] = 0;
-                if (sqrt(r4[0]) <= 1e-8 * (sqrt(r4[1]) + 1e-8)) {
-                    s_state[0] = 1; s_state[2] = kTermParameter;
-                } else {
-                    const double change = cost - cand_cost, rho = change / model;
-                    if (fabs(change) <= 1e-6 * cost) {
-                        // Ceres checks the function tolerance before the accept test: the iterate stays where it was
-                        s_state[0] = 1; s_state[2] = kTermFunction;
-                    } else {
-                        if (rho > 1e-3) {
-                            s_ctl[6] = 1.0;
-                            s_ctl[2] = cand_cost;
-                            s_ctl[0] = fmin(1e16, s_ctl[0] / fmax(1.0 / 3.0, 1.0 - (2.0 * rho - 1.0) * (2.0 * rho - 1.0) * (2.0 * rho - 1.0)));
-                            s_ctl[1] = 2.0;
-                        } else {
-                            s_ctl[0] /= s_ctl[1];
-                            s_ctl[1] *= 2.0;
-                        }
-                        if (s_ctl[0] < 1e-32) { s_state[0] = 1; s_state[2] = kTermRadius; }
-                    }
-                }
-            }
-        }
-        __syncthreads();
-        if (s_ctl[6] != 0.0) {
-            if (tid < 6 * C) s_cams[tid] = s_cand[tid];
-            for (int i = tid; i < 3 * P; i += kMvThreads) a.pts[i] = a.cand[i];
-        }
-        __syncthreads();
-        if (s_state[0]) break;
-    }
-    if (tid < 6 * C) a.cams[tid] = s_cams[tid];
-    if (tid == 0) {
-        a.summary[1] = s_ctl[2];
-        a.summary[2] = double(s_state[1]);
-        a.summary[3] = double(s_state[2]);
-    }
-}
+// (mv_block_reduce, mv_transform and mvba_kernel<LOSS, MODE> itself: mvba.h - the backward pass, mvba_backward.hip, replays the same statement)
 
 // one thread per point
 __global__ void mv_triangulate_kernel(int n, const double* P0, const double* P1, const double* x0, const double* x1, double* xyz) {
@@ -521,22 +56,29 @@ struct MvCollectArgs {
     const float* conf[kMvMaxPairs];    // [B,N,channels]
     float *o0, *o1, *oc;               // [B*P,N,2] x2, [B*P,N]
     int* count;                        // [B*P]
+    const float* gin;                  // backward: [B*P,N] dLoss/d(oc)
+    float* gout[kMvMaxPairs];          // backward: [B,N,channels] dLoss/d(conf) or NULL (pair left out)
 };
 
 // Ordered compaction, one workgroup per problem: keypoint n of the first image is kept when it has a match and every confidence
 // channel is above the threshold; the kept rows keep their order (ballot prefix inside a wave, wave totals through LDS, a
 // running base across the chunks of 256) because every later sum runs over them in that order.  Rows behind the count read 0.
+// BWD: the same walk scatters gin back: row n of a kept match gets the value at its slot in channel 0, everything else of gout 0.
+template <bool BWD>
 __global__ __launch_bounds__(kMvRowThreads) void mv_collect_kernel(MvCollectArgs a) {
     __shared__ int s_wave[kMvRowThreads / 64];
     const int pp = blockIdx.x, b = pp / a.P, q = pp - b * a.P, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int N = a.N, n1 = a.n1[q];
     const int64_t* match = a.match[q] ? a.match[q] + size_t(b) * N : nullptr;
     const float* conf = a.conf[q] + size_t(b) * N * a.channels;
-    const float* k0 = a.k0[q] + size_t(b) * N * 2;
-    const float* k1 = a.k1[q] + size_t(b) * n1 * 2;
-    float* o0 = a.o0 + size_t(pp) * N * 2;
-    float* o1 = a.o1 + size_t(pp) * N * 2;
-    float* oc = a.oc + size_t(pp) * N;
+    if (BWD && !a.gout[q]) return;  // (the whole workgroup)
+    const float* k0 = BWD ? nullptr : a.k0[q] + size_t(b) * N * 2;
+    const float* k1 = BWD ? nullptr : a.k1[q] + size_t(b) * n1 * 2;
+    float* o0 = BWD ? nullptr : a.o0 + size_t(pp) * N * 2;
+    float* o1 = BWD ? nullptr : a.o1 + size_t(pp) * N * 2;
+    float* oc = BWD ? nullptr : a.oc + size_t(pp) * N;
+    const float* gin = BWD ? a.gin + size_t(pp) * N : nullptr;
+    float* gout = BWD ? a.gout[q] + size_t(b) * N * a.channels : nullptr;
     int base = 0;
     if (match) {
         for (int c0 = 0; c0 < N; c0 += kMvRowThreads) {
@@ -556,7 +98,10 @@ __global__ __launch_bounds__(kMvRowThreads) void mv_collect_kernel(MvCollectArgs
                 if (w < wave) off += s_wave[w];
                 total += s_wave[w];
             }
-            if (keep) {
+            if (BWD) {
+                if (n < N)
+                    for (int c = 0; c < a.channels; ++c) gout[size_t(n) * a.channels + c] = (keep && c == 0) ? gin[off] : 0.f;
+            } else if (keep) {
                 o0[2 * off] = k0[2 * n]; o0[2 * off + 1] = k0[2 * n + 1];
                 o1[2 * off] = k1[2 * m]; o1[2 * off + 1] = k1[2 * m + 1];
                 oc[off] = conf[size_t(n) * a.channels];
@@ -564,6 +109,11 @@ __global__ __launch_bounds__(kMvRowThreads) void mv_collect_kernel(MvCollectArgs
             base += total;
             __syncthreads();
         }
+    }
+    if (BWD) {
+        if (!match)
+            for (int i = tid; i < N * a.channels; i += kMvRowThreads) gout[i] = 0.f;
+        return;
     }
     for (int n = base + tid; n < N; n += kMvRowThreads) {
         o0[2 * n] = 0.f; o0[2 * n + 1] = 0.f; o1[2 * n] = 0.f; o1[2 * n + 1] = 0.f; oc[n] = 0.f;
@@ -644,6 +194,52 @@ __global__ __launch_bounds__(kMvRowThreads) void mv_build_kernel(MvBuildArgs g) 
     mv_dlt(g.proj + size_t(b * g.T + rec.i) * 12, g.proj + size_t(b * g.T + rec.j) * 12, x[0], x[1], x[2], x[3], a.pts + 3 * size_t(pt));
 }
 
+// Reverse of the weights mv_build_kernel hands the solver: w = conf / H on the four weight entries of a match (x, y of both
+// observations), H = 0.5 (2 sum conf + 1e-3) with the tuple's sum.  With s_m the sum of the four dLoss/dw of match m:
+// dLoss/dconf_m = s_m / H - (sum_m' s_m' conf_m') / H^2.  One workgroup per tuple, the sums in the build's order; rows behind the
+// count get 0.
+struct MvWeightsBwdArgs {
+    int P, N;
+    const float* conf;          // collected [B*P,N]
+    const MvPairRec* pairs;     // [B*P]
+    const MvbaBwdArgs* bw;      // [B]: g_w
+    float* gconf;               // [B*P,N]
+};
+__global__ __launch_bounds__(kMvRowThreads) void mv_weights_backward_kernel(MvWeightsBwdArgs g) {
+    __shared__ double s_red[2 * (kMvRowThreads / 64)];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const double* gw = g.bw[b].g_w;
+    double sum = 0.0, dot = 0.0;
+    for (int q = 0; q < g.P; ++q) {
+        const MvPairRec rec = g.pairs[b * g.P + q];
+        const float* cf = g.conf + size_t(b * g.P + q) * g.N;
+        for (int m = tid; m < rec.count; m += kMvRowThreads) {
+            const size_t oi = 2 * size_t(rec.pt_base) + m, oj = oi + rec.count;
+            const double c = double(cf[m]);
+            sum += c;
+            dot += (gw[2 * oi] + gw[2 * oi + 1] + gw[2 * oj] + gw[2 * oj + 1]) * c;
+        }
+    }
+    sum = wave_sum_d(sum); dot = wave_sum_d(dot);
+    if (lane == 0) { s_red[wave] = sum; s_red[kMvRowThreads / 64 + wave] = dot; }
+    __syncthreads();
+    sum = s_red[0]; dot = s_red[kMvRowThreads / 64];
+    for (int w = 1; w < kMvRowThreads / 64; ++w) { sum += s_red[w]; dot += s_red[kMvRowThreads / 64 + w]; }
+    const double H = 0.5 * (2.0 * sum + 1e-3);
+    for (int q = 0; q < g.P; ++q) {
+        const MvPairRec rec = g.pairs[b * g.P + q];
+        float* out = g.gconf + size_t(b * g.P + q) * g.N;
+        for (int m = tid; m < g.N; m += kMvRowThreads) {
+            float v = 0.f;
+            if (m < rec.count) {
+                const size_t oi = 2 * size_t(rec.pt_base) + m, oj = oi + rec.count;
+                v = float((gw[2 * oi] + gw[2 * oi + 1] + gw[2 * oj] + gw[2 * oj + 1]) / H - dot / (H * H));
+            }
+            out[m] = v;
+        }
+    }
+}
+
 // (MvLayout: mvba.h)
 MvLayout mv_layout(char* base, size_t n, size_t totC, size_t totP, size_t totO, size_t extra) {
     MvLayout L{};
@@ -683,9 +279,9 @@ MvbaArgs mv_record(const MvLayout& L, size_t k, size_t c0, size_t p0, size_t o0,
 
 int mv_launch_ba(e2emv_ctx* ctx, const MvLayout& L, int n, hipStream_t s, int loss) {
     prof_begin(ctx, PS_W8PT, s);
-    if (loss == kLossHuber) hipLaunchKernelGGL(mvba_kernel<kLossHuber>, dim3(n), dim3(kMvThreads), 0, s, L.recs);
-    else if (loss == kLossCauchy) hipLaunchKernelGGL(mvba_kernel<kLossCauchy>, dim3(n), dim3(kMvThreads), 0, s, L.recs);
-    else hipLaunchKernelGGL(mvba_kernel<kLossNone>, dim3(n), dim3(kMvThreads), 0, s, L.recs);
+    if (loss == kLossHuber) hipLaunchKernelGGL((mvba_kernel<kLossHuber, kLmRun>), dim3(n), dim3(kMvThreads), 0, s, L.recs, (const MvbaBwdArgs*)nullptr);
+    else if (loss == kLossCauchy) hipLaunchKernelGGL((mvba_kernel<kLossCauchy, kLmRun>), dim3(n), dim3(kMvThreads), 0, s, L.recs, (const MvbaBwdArgs*)nullptr);
+    else hipLaunchKernelGGL((mvba_kernel<kLossNone, kLmRun>), dim3(n), dim3(kMvThreads), 0, s, L.recs, (const MvbaBwdArgs*)nullptr);
     E2EMV_CHECK_LAUNCH(ctx, "mvba_kernel");
     prof_end(ctx, s);
     return E2EMV_OK;
@@ -735,38 +331,42 @@ int mv_check_loss(e2emv_ctx* ctx, const char* who, int loss, double* scale) {
 }
 }  // namespace e2emv
 
-extern "C" int e2emv_mv_bundle_adjust_batch_loss(e2emv_ctx* ctx, int n_problems, const int32_t* n_cams, const int32_t* fixed_cam,
-                                                 const double* intr, const int64_t* pt_off, const int64_t* obs_off, const int32_t* cam_idx,
-                                                 const int32_t* pt_idx, const double* obs_xy, const double* obs_w, double* cams, double* pts,
-                                                 int max_iterations, double* summary, int loss, double loss_scale, void* stream) {
-    if (!ctx) return E2EMV_EINVAL;
-    E2EMV_ENTER(ctx, stream);
-    const int lc = mv_check_loss(ctx, "mv_bundle_adjust_batch", loss, &loss_scale);
-    if (lc) return lc;
+namespace e2emv {
+int mv_batch_check(e2emv_ctx* ctx, const char* who, int n_problems, const int32_t* n_cams, const int32_t* fixed_cam, const double* intr,
+                   const int64_t* pt_off, const int64_t* obs_off, const int32_t* cam_idx, const int32_t* pt_idx, const double* obs_xy,
+                   const double* obs_w, const double* cams, const double* pts, size_t* totC_out, size_t* totP_out, size_t* totO_out) {
     if (n_problems < 1 || !n_cams || !fixed_cam || !intr || !pt_off || !obs_off || !cams)
-        return set_err(ctx, E2EMV_EINVAL, "mv_bundle_adjust_batch: bad argument (n_problems >= 1, no NULL size / offset array)");
+        return set_err(ctx, E2EMV_EINVAL, "%s: bad argument (n_problems >= 1, no NULL size / offset array)", who);
     const size_t n = size_t(n_problems);
-    if (pt_off[0] != 0 || obs_off[0] != 0) return set_err(ctx, E2EMV_ESHAPE, "mv_bundle_adjust_batch: offsets must start at 0");
+    if (pt_off[0] != 0 || obs_off[0] != 0) return set_err(ctx, E2EMV_ESHAPE, "%s: offsets must start at 0", who);
     size_t totC = 0;
     for (size_t k = 0; k < n; ++k) {
         if (n_cams[k] < 1 || n_cams[k] > kMvMaxCams)
-            return set_err(ctx, E2EMV_EINVAL, "mv_bundle_adjust_batch: problem %zu has %d cameras (1 <= n_cams <= %d)", k, n_cams[k], kMvMaxCams);
+            return set_err(ctx, E2EMV_EINVAL, "%s: problem %zu has %d cameras (1 <= n_cams <= %d)", who, k, n_cams[k], kMvMaxCams);
         if (pt_off[k + 1] < pt_off[k] || obs_off[k + 1] < obs_off[k] || pt_off[k + 1] - pt_off[k] > INT32_MAX / 8 || obs_off[k + 1] - obs_off[k] > INT32_MAX / 32)
-            return set_err(ctx, E2EMV_ESHAPE, "mv_bundle_adjust_batch: offsets of problem %zu are not monotone (or the problem is too large)", k);
+            return set_err(ctx, E2EMV_ESHAPE, "%s: offsets of problem %zu are not monotone (or the problem is too large)", who, k);
         totC += size_t(n_cams[k]);
     }
     const size_t totP = size_t(pt_off[n]), totO = size_t(obs_off[n]);
     if ((totP && !pts) || (totO && (!cam_idx || !pt_idx || !obs_xy || !obs_w)))
-        return set_err(ctx, E2EMV_EINVAL, "mv_bundle_adjust_batch: NULL array for %zu points / %zu observations", totP, totO);
+        return set_err(ctx, E2EMV_EINVAL, "%s: NULL array for %zu points / %zu observations", who, totP, totO);
     for (size_t k = 0; k < n; ++k) {
         const int C = n_cams[k], P = int(pt_off[k + 1] - pt_off[k]);
         for (int64_t o = obs_off[k]; o < obs_off[k + 1]; ++o)
             if (cam_idx[o] < 0 || cam_idx[o] >= C || pt_idx[o] < 0 || pt_idx[o] >= P)
-                return set_err(ctx, E2EMV_EINVAL, "mv_bundle_adjust_batch: observation %lld of problem %zu refers to camera %d / point %d",
+                return set_err(ctx, E2EMV_EINVAL, "%s: observation %lld of problem %zu refers to camera %d / point %d", who,
                                (long long)(o - obs_off[k]), k, cam_idx[o], pt_idx[o]);
     }
-    hipStream_t s = (hipStream_t)stream;
-    const int rc = ws_reserve(ctx, mv_layout(nullptr, n, totC, totP, totO, 0).bytes);
+    *totC_out = totC; *totP_out = totP; *totO_out = totO;
+    return E2EMV_OK;
+}
+
+int mv_batch_upload(e2emv_ctx* ctx, int n_problems, const int32_t* n_cams, const int32_t* fixed_cam, const double* intr, const int64_t* pt_off,
+                    const int64_t* obs_off, const int32_t* cam_idx, const int32_t* pt_idx, const double* obs_xy, const double* obs_w,
+                    const double* cams, const double* pts, int max_iterations, double loss_scale, size_t totC, size_t totP, size_t totO,
+                    size_t tail, MvLayout* Lout, hipStream_t s) {
+    const size_t n = size_t(n_problems);
+    const int rc = ws_reserve(ctx, mv_layout(nullptr, n, totC, totP, totO, 0).bytes + tail);
     if (rc) return rc;
     const MvLayout L = mv_layout(ctx->d_ws, n, totC, totP, totO, 0);
     // observation lists per point and per camera (stable order -> deterministic sums), indices local to their problem
@@ -802,6 +402,29 @@ extern "C" int e2emv_mv_bundle_adjust_batch_loss(e2emv_ctx* ctx, int n_problems,
         E2EMV_HIP(ctx, hipMemcpyAsync(L.cam_obs, cobs.data(), sizeof(int) * totO, hipMemcpyHostToDevice, s));
     }
     E2EMV_HIP(ctx, hipStreamSynchronize(s));  // the host staging vectors die at return
+    *Lout = L;
+    return E2EMV_OK;
+}
+}  // namespace e2emv
+
+extern "C" int e2emv_mv_bundle_adjust_batch_loss(e2emv_ctx* ctx, int n_problems, const int32_t* n_cams, const int32_t* fixed_cam,
+                                                 const double* intr, const int64_t* pt_off, const int64_t* obs_off, const int32_t* cam_idx,
+                                                 const int32_t* pt_idx, const double* obs_xy, const double* obs_w, double* cams, double* pts,
+                                                 int max_iterations, double* summary, int loss, double loss_scale, void* stream) {
+    if (!ctx) return E2EMV_EINVAL;
+    E2EMV_ENTER(ctx, stream);
+    const int lc = mv_check_loss(ctx, "mv_bundle_adjust_batch", loss, &loss_scale);
+    if (lc) return lc;
+    size_t totC = 0, totP = 0, totO = 0;
+    int rc = mv_batch_check(ctx, "mv_bundle_adjust_batch", n_problems, n_cams, fixed_cam, intr, pt_off, obs_off, cam_idx, pt_idx, obs_xy, obs_w, cams, pts,
+                            &totC, &totP, &totO);
+    if (rc) return rc;
+    const size_t n = size_t(n_problems);
+    hipStream_t s = (hipStream_t)stream;
+    MvLayout L;
+    rc = mv_batch_upload(ctx, n_problems, n_cams, fixed_cam, intr, pt_off, obs_off, cam_idx, pt_idx, obs_xy, obs_w, cams, pts, max_iterations, loss_scale,
+                         totC, totP, totO, 0, &L, s);
+    if (rc) return rc;
     const int lrc = mv_launch_ba(ctx, L, n_problems, s, loss);
     if (lrc) return lrc;
     E2EMV_HIP(ctx, hipMemcpyAsync(cams, L.cams, sizeof(double) * 6 * totC, hipMemcpyDeviceToHost, s));
@@ -855,16 +478,17 @@ extern "C" int e2emv_mv_collect(e2emv_ctx* ctx, int B, int T, int N, const float
         a.k0[q] = d_kpts0[q]; a.k1[q] = d_kpts1[q]; a.match[q] = d_matches[q]; a.conf[q] = d_conf[q]; a.n1[q] = n_kpts1[q];
     }
     a.o0 = d_mkpts0; a.o1 = d_mkpts1; a.oc = d_mconf; a.count = d_count;
-    hipLaunchKernelGGL(mv_collect_kernel, dim3(B * a.P), dim3(kMvRowThreads), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(mv_collect_kernel<false>, dim3(B * a.P), dim3(kMvRowThreads), 0, (hipStream_t)stream, a);
     E2EMV_CHECK_LAUNCH(ctx, "mv_collect_kernel");
     return E2EMV_OK;
 }
 
 // stage 4 (and the uploads in front of it) shared by e2emv_mv_tuple_ba and e2emv_mv_tuple_problem; leaves the problems of the B
 // tuples in the workspace, described by *L
-static int mv_tuple_build(e2emv_ctx* ctx, const char* who, int B, int T, int N, const int32_t* counts, const float* d_mkpts0,
-                          const float* d_mkpts1, const float* d_mconf, const float* const* d_intr, int kdim, int intr_batch,
-                          const double* extr, int max_iterations, double loss_scale, MvLayout* L, size_t* totP_out, hipStream_t s) {
+namespace e2emv {
+int mv_tuple_build(e2emv_ctx* ctx, const char* who, int B, int T, int N, const int32_t* counts, const float* d_mkpts0, const float* d_mkpts1,
+                   const float* d_mconf, const float* const* d_intr, int kdim, int intr_batch, const double* extr, int max_iterations,
+                   double loss_scale, size_t tail, MvLayout* L, size_t* totP_out, hipStream_t s) {
     if (B < 1 || N < 1 || !counts || !d_mkpts0 || !d_mkpts1 || !d_mconf || !d_intr || !extr)
         return set_err(ctx, E2EMV_EINVAL, "%s: bad argument (B, N >= 1, no NULL array)", who);
     if (T < 2 || T > kMvMaxCams) return set_err(ctx, E2EMV_EINVAL, "%s: tuple of %d images (2 <= T <= %d)", who, T, kMvMaxCams);
@@ -881,7 +505,7 @@ static int mv_tuple_build(e2emv_ctx* ctx, const char* who, int B, int T, int N, 
     if (size_t(B) * P * N > size_t(INT32_MAX) / 64) return set_err(ctx, E2EMV_ESHAPE, "%s: B * pairs * N = %zu is too large", who, size_t(B) * P * N);
     const size_t n = size_t(B), totC = n * T, totO = 2 * totP;
     const size_t proj_bytes = (totC * 12 * 8 + 255) & ~size_t(255), extra = proj_bytes + n * P * sizeof(MvPairRec);
-    const int rc = ws_reserve(ctx, mv_layout(nullptr, n, totC, totP, totO, extra).bytes);
+    const int rc = ws_reserve(ctx, mv_layout(nullptr, n, totC, totP, totO, extra).bytes + tail);
     if (rc) return rc;
     *L = mv_layout(ctx->d_ws, n, totC, totP, totO, extra);
     // everything the host contributes in one staging block = one copy: records, start cameras, camera list starts, projection
@@ -935,6 +559,7 @@ static int mv_tuple_build(e2emv_ctx* ctx, const char* who, int B, int T, int N, 
     *totP_out = totP;
     return E2EMV_OK;
 }
+}  // namespace e2emv
 
 extern "C" int e2emv_mv_tuple_ba_loss(e2emv_ctx* ctx, int B, int T, int N, const int32_t* counts, const float* d_mkpts0,
                                       const float* d_mkpts1, const float* d_mconf, const float* const* d_intr, int kdim, int intr_batch,
@@ -948,7 +573,7 @@ extern "C" int e2emv_mv_tuple_ba_loss(e2emv_ctx* ctx, int B, int T, int N, const
     hipStream_t s = (hipStream_t)stream;
     MvLayout L;
     size_t totP = 0;
-    rc = mv_tuple_build(ctx, "mv_tuple_ba", B, T, N, counts, d_mkpts0, d_mkpts1, d_mconf, d_intr, kdim, intr_batch, extr, max_iterations, loss_scale, &L, &totP, s);
+    rc = mv_tuple_build(ctx, "mv_tuple_ba", B, T, N, counts, d_mkpts0, d_mkpts1, d_mconf, d_intr, kdim, intr_batch, extr, max_iterations, loss_scale, 0, &L, &totP, s);
     if (rc) return rc;
     rc = mv_launch_ba(ctx, L, B, s, loss);
     if (rc) return rc;
@@ -972,7 +597,7 @@ extern "C" int e2emv_mv_tuple_problem(e2emv_ctx* ctx, int B, int T, int N, const
     hipStream_t s = (hipStream_t)stream;
     MvLayout L;
     size_t totP = 0;
-    const int rc = mv_tuple_build(ctx, "mv_tuple_problem", B, T, N, counts, d_mkpts0, d_mkpts1, d_mconf, d_intr, kdim, intr_batch, extr, 0, 0.0, &L, &totP, s);
+    const int rc = mv_tuple_build(ctx, "mv_tuple_problem", B, T, N, counts, d_mkpts0, d_mkpts1, d_mconf, d_intr, kdim, intr_batch, extr, 0, 0.0, 0, &L, &totP, s);
     if (rc) return rc;
     if (totP && (!cam_idx || !pt_idx || !obs_xy || !obs_w || !pts)) return set_err(ctx, E2EMV_EINVAL, "mv_tuple_problem: NULL output for %zu points", totP);
     E2EMV_HIP(ctx, hipMemcpyAsync(cams, L.cams, sizeof(double) * 6 * B * T, hipMemcpyDeviceToHost, s));
@@ -984,6 +609,75 @@ extern "C" int e2emv_mv_tuple_problem(e2emv_ctx* ctx, int B, int T, int N, const
         E2EMV_HIP(ctx, hipMemcpyAsync(pts, L.pts, sizeof(double) * 3 * totP, hipMemcpyDeviceToHost, s));
     }
     E2EMV_HIP(ctx, hipStreamSynchronize(s));
+    return E2EMV_OK;
+}
+
+extern "C" int e2emv_mv_tuple_ba_backward(e2emv_ctx* ctx, int B, int T, int N, const int32_t* counts, const float* d_mkpts0,
+                                          const float* d_mkpts1, const float* d_mconf, const float* const* d_intr, int kdim, int intr_batch,
+                                          const double* extr, int max_iterations, const double* g_out_extr, float* d_gmconf, void* stream) {
+    if (!ctx) return E2EMV_EINVAL;
+    E2EMV_ENTER(ctx, stream);
+    const char* who = "mv_tuple_ba_backward";
+    if (!g_out_extr || !d_gmconf) return set_err(ctx, E2EMV_EINVAL, "%s: NULL g_out_extr / d_gmconf", who);
+    if (B < 1 || T < 2 || T > kMvMaxCams || N < 1 || !counts) return set_err(ctx, E2EMV_EINVAL, "%s: bad argument (B, N >= 1, 2 <= T <= %d, counts)", who, kMvMaxCams);
+    const int P = T * (T - 1) / 2;
+    std::vector<int> Cs(B, T), Ps(B, 0), Os(B, 0);
+    for (int b = 0; b < B; ++b) {
+        for (int q = 0; q < P; ++q) {
+            const int c = counts[size_t(b) * P + q];
+            if (c < 0 || c > N) return set_err(ctx, E2EMV_EINVAL, "%s: count %d of pair block %d is outside [0, N = %d]", who, c, b * P + q, N);
+            Ps[b] += c;
+        }
+        Os[b] = 2 * Ps[b];
+    }
+    bool overflow = false;
+    const size_t tail = mv_bwd_bytes(Cs, Ps, Os, max_iterations, &overflow);
+    int rc = mv_bwd_fits(ctx, who, tail, overflow);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    MvLayout L;
+    size_t totP = 0;
+    rc = mv_tuple_build(ctx, who, B, T, N, counts, d_mkpts0, d_mkpts1, d_mconf, d_intr, kdim, intr_batch, extr, max_iterations, 0.0, tail, &L, &totP, s);
+    if (rc) return rc;
+    MvBwdLayout W;
+    rc = mv_bwd_carve(ctx, ctx->d_ws + L.bytes, Cs, Ps, Os, max_iterations, true, &W, s);
+    if (rc) return rc;
+    const size_t totC = size_t(B) * T;
+    E2EMV_HIP(ctx, hipMemsetAsync(W.cams_bar, 0, sizeof(double) * 6 * totC, s));
+    if (totP) E2EMV_HIP(ctx, hipMemsetAsync(W.pts_bar, 0, sizeof(double) * 3 * totP, s));
+    E2EMV_HIP(ctx, hipMemcpyAsync(W.g_extr, g_out_extr, sizeof(double) * 16 * totC, hipMemcpyHostToDevice, s));
+    E2EMV_HIP(ctx, hipStreamSynchronize(s));  // g_out_extr is the caller's
+    rc = mv_launch_ba_backward(ctx, L, W, B, s);
+    if (rc) return rc;
+    MvWeightsBwdArgs g{};
+    g.P = P; g.N = N; g.conf = d_mconf; g.bw = W.recs; g.gconf = d_gmconf;
+    const size_t proj_bytes = (totC * 12 * 8 + 255) & ~size_t(255);  // (mv_tuple_build: the pair records lie behind the projections)
+    g.pairs = reinterpret_cast<const MvPairRec*>(L.extra + proj_bytes);
+    hipLaunchKernelGGL(mv_weights_backward_kernel, dim3(B), dim3(kMvRowThreads), 0, s, g);
+    E2EMV_CHECK_LAUNCH(ctx, "mv_weights_backward_kernel");
+    E2EMV_HIP(ctx, hipStreamSynchronize(s));
+    return E2EMV_OK;
+}
+
+extern "C" int e2emv_mv_collect_backward(e2emv_ctx* ctx, int B, int T, int N, const int32_t* n_kpts1, const int64_t* const* d_matches,
+                                         const float* const* d_conf, int conf_channels, float conf_thresh, const float* d_gmconf,
+                                         float* const* d_gconf, void* stream) {
+    if (!ctx) return E2EMV_EINVAL;
+    E2EMV_ENTER(ctx, stream);
+    if (B < 1 || N < 1 || conf_channels < 1 || !n_kpts1 || !d_matches || !d_conf || !d_gmconf || !d_gconf)
+        return set_err(ctx, E2EMV_EINVAL, "mv_collect_backward: bad argument (B, N, conf_channels >= 1, no NULL array)");
+    if (T < 2 || T > kMvMaxCams) return set_err(ctx, E2EMV_EINVAL, "mv_collect_backward: tuple of %d images (2 <= T <= %d)", T, kMvMaxCams);
+    MvCollectArgs a{};
+    a.B = B; a.P = T * (T - 1) / 2; a.N = N; a.channels = conf_channels; a.thresh = conf_thresh;
+    if (size_t(B) * a.P * N > size_t(INT32_MAX) / 2) return set_err(ctx, E2EMV_ESHAPE, "mv_collect_backward: B * pairs * N = %zu is too large", size_t(B) * a.P * N);
+    for (int q = 0; q < a.P; ++q) {
+        if (d_gconf[q] && d_matches[q] && (!d_conf[q] || n_kpts1[q] < 1))
+            return set_err(ctx, E2EMV_EINVAL, "mv_collect_backward: pair %d has matches but no confidences", q);
+        a.match[q] = d_matches[q]; a.conf[q] = d_conf[q]; a.n1[q] = n_kpts1[q]; a.gout[q] = d_gconf[q];
+    }
+    a.gin = d_gmconf;
+    hipLaunchKernelGGL(mv_collect_kernel<true>, dim3(B * a.P), dim3(kMvRowThreads), 0, (hipStream_t)stream, a);
+    E2EMV_CHECK_LAUNCH(ctx, "mv_collect_kernel<backward>");
     return E2EMV_OK;
 }
 

@@ -468,6 +468,151 @@ def bundle_adjust_batch(problems, max_iterations=50, loss=None, loss_scale=None)
     return [(cams[cam_off[k]:cam_off[k + 1]].copy(), pts[pt_off[k]:pt_off[k + 1]].copy(), _ba_summary(summary[k])) for k in range(n)]
 
 
+def _check_iterations(who, max_iterations):
+    if isinstance(max_iterations, bool) or not isinstance(max_iterations, (int, np.integer)) or max_iterations < 0:
+        raise ValueError(f"{who}: max_iterations must be an integer >= 0 (got {max_iterations!r})")
+    return int(max_iterations)
+
+
+def bundle_adjust_batch_backward(problems, grads, max_iterations=50):
+    """The reverse pass of ``bundle_adjust_batch`` (squared loss; ``e2emv_mv_bundle_adjust_batch_backward``, one launch for the batch).
+    ``problems``: the argument of ``bundle_adjust_batch`` (the START cameras and points); ``grads[k] = (g_cams [C,6], g_pts [P,3] or
+    None)`` = dLoss/d(what ``bundle_adjust_batch`` returned for problem k).  Returns one ``(g_obs_w [O,2], g_cams0 [C,6], g_pts0 [P,3])``
+    per problem, numpy float64: the exact adjoint of the loop the device ran, its decisions, radius and Jacobi scales frozen.
+    ``ValueError`` before any device call for arrays that disagree in length, a ``grads`` entry of the wrong shape and a negative or
+    non-integer ``max_iterations``."""
+    max_iterations = _check_iterations("bundle_adjust_batch_backward", max_iterations)
+    if len(grads) != len(problems):
+        raise ValueError(f"bundle_adjust_batch_backward: {len(problems)} problems but {len(grads)} grads entries")
+    if not problems:
+        return []
+    n = len(problems)
+    cat = lambda k, dt, w: np.ascontiguousarray(np.concatenate([np.asarray(pr[k], dt).reshape(-1, w) for pr in problems]))  # noqa: E731
+    n_cams, fixed = np.array([pr[0] for pr in problems], np.int32), np.array([pr[1] for pr in problems], np.int32)
+    intr, cam_idx, pt_idx = cat(2, np.float64, 4), cat(3, np.int32, 1), cat(4, np.int32, 1)
+    obs_xy, obs_w, cams, pts = cat(5, np.float64, 2), cat(6, np.float64, 2), cat(7, np.float64, 6), cat(8, np.float64, 3)
+    size = lambda k, w: [np.asarray(pr[k]).size // w for pr in problems]  # noqa: E731
+    if size(7, 6) != list(n_cams) or size(4, 1) != size(3, 1) or size(5, 2) != size(3, 1) or size(6, 2) != size(3, 1):
+        raise ValueError("bundle_adjust_batch_backward: a problem's arrays disagree in length")
+    g_cams, g_pts = [], []
+    for k, (g, C, P) in enumerate(zip(grads, size(7, 6), size(8, 3))):
+        if len(g) != 2:
+            raise ValueError(f"bundle_adjust_batch_backward: grads[{k}] must be a pair (g_cams, g_pts or None)")
+        gc = np.asarray(g[0], np.float64)
+        gp = np.zeros((P, 3)) if g[1] is None else np.asarray(g[1], np.float64)
+        if gc.shape != (C, 6) or gp.shape != (P, 3):
+            raise ValueError(f"bundle_adjust_batch_backward: grads[{k}] must be (g_cams [{C},6], g_pts [{P},3] or None)")
+        g_cams.append(gc); g_pts.append(gp)
+    g_cams, g_pts = np.ascontiguousarray(np.concatenate(g_cams)), np.ascontiguousarray(np.concatenate(g_pts))
+    pt_off = np.concatenate([[0], np.cumsum(size(8, 3))]).astype(np.int64)
+    obs_off = np.concatenate([[0], np.cumsum(size(3, 1))]).astype(np.int64)
+    cam_off = np.concatenate([[0], np.cumsum(n_cams)])
+    g_w, g_c0, g_p0 = np.zeros_like(obs_w), np.zeros_like(cams), np.zeros_like(pts)
+    dev = _dev()
+    ctx = _lib.context(dev)
+    ctx.call("e2emv_mv_bundle_adjust_batch_backward", n, _p(n_cams), _p(fixed), _p(intr), _p(pt_off), _p(obs_off), _p(cam_idx), _p(pt_idx),
+             _p(obs_xy), _p(obs_w), _p(cams), _p(pts), max_iterations, _p(g_cams), _p(g_pts), _p(g_w), _p(g_c0), _p(g_p0), _lib.stream_ptr(dev))
+    return [(g_w[obs_off[k]:obs_off[k + 1]].copy(), g_c0[cam_off[k]:cam_off[k + 1]].copy(), g_p0[pt_off[k]:pt_off[k + 1]].copy()) for k in range(n)]
+
+
+class _BundleAdjust(torch.autograd.Function):
+    """``bundle_adjust`` forward, ``bundle_adjust_batch_backward`` for the graph (both on host arrays: the solver's interface)."""
+
+    @staticmethod
+    def forward(ctx, obs_w, cams, pts, head, max_iterations):
+        n_cams, fixed_cam, intr, cam_idx, pt_idx, obs_xy = head
+        w, c, p = (t.detach().cpu().numpy() for t in (obs_w, cams, pts))
+        ctx.problem = (n_cams, fixed_cam, intr, cam_idx, pt_idx, obs_xy, w, c, p)
+        ctx.max_iterations = max_iterations
+        ctx.like = [(t.shape, t.device, t.dtype) for t in (obs_w, cams, pts)]
+        co, po, _ = bundle_adjust(*ctx.problem, max_iterations=max_iterations)
+        return torch.from_numpy(co), torch.from_numpy(po)
+
+    @staticmethod
+    def backward(ctx, g_cams, g_pts):
+        gw, gc, gp = bundle_adjust_batch_backward([ctx.problem], [(g_cams.detach().cpu().numpy(), g_pts.detach().cpu().numpy())], ctx.max_iterations)[0]
+        back = lambda g, t: torch.from_numpy(g).reshape(t[0]).to(t[1], t[2])  # noqa: E731
+        need = ctx.needs_input_grad
+        return tuple(back(g, t) if need[i] else None for i, (g, t) in enumerate(zip((gw, gc, gp), ctx.like))) + (None, None)
+
+
+def bundle_adjust_torch(n_cams, fixed_cam, intr, cam_idx, pt_idx, obs_xy, obs_w, cams, pts, max_iterations=50, loss=None, loss_scale=None):
+    """``bundle_adjust`` on tensors: returns ``(cams_out [C,6], pts_out [P,3])`` float64 and carries a graph to whichever of ``obs_w``,
+    ``cams``, ``pts`` requires grad (``e2emv_mv_bundle_adjust_batch_backward``: the exact adjoint of the LM loop the device ran, squared
+    loss only).  Without a graph it returns what ``bundle_adjust`` returns, bit for bit - with a loss too.  ``NotImplementedError`` for a
+    graph together with ``loss="huber" | "cauchy"``; ``ValueError`` as ``bundle_adjust_batch_backward``; both before any device call."""
+    max_iterations = _check_iterations("bundle_adjust_torch", max_iterations)
+    code = _check_loss(loss, loss_scale)
+    tens = [torch.as_tensor(t) for t in (obs_w, cams, pts)]
+    graph = torch.is_grad_enabled() and any(t.requires_grad for t in tens)
+    if graph and code:
+        raise NotImplementedError("bundle_adjust_torch: no gradient through a robust loss (loss=%r): the backward pass is that of the squared loss" % (loss,))
+    O = np.asarray(cam_idx).size
+    if np.asarray(pt_idx).size != O or np.asarray(obs_xy).size != 2 * O or tens[0].numel() != 2 * O or tens[1].numel() != 6 * int(n_cams) or tens[2].numel() % 3:
+        raise ValueError("bundle_adjust_torch: the problem's arrays disagree in length")
+    if not graph:
+        co, po, _ = bundle_adjust(n_cams, fixed_cam, intr, cam_idx, pt_idx, obs_xy, *(t.detach().cpu().numpy() for t in tens), max_iterations=max_iterations,
+                                  loss=loss, loss_scale=loss_scale)
+        return torch.from_numpy(co), torch.from_numpy(po)
+    head = (int(n_cams), int(fixed_cam), np.asarray(intr, np.float64), np.asarray(cam_idx, np.int32), np.asarray(pt_idx, np.int32), np.asarray(obs_xy, np.float64))
+    return _BundleAdjust.apply(tens[0], tens[1], tens[2], head, max_iterations)
+
+
+class _RefineTuple(torch.autograd.Function):
+    """Attaches the graph of ``refine_tuple_poses_batch``: the forward result is computed by the caller; the backward runs
+    ``e2emv_mv_tuple_ba_backward`` and ``e2emv_mv_collect_backward``."""
+
+    @staticmethod
+    def forward(ctx, state, *confs):
+        ctx.state = state
+        ctx.meta = [(c.shape, c.dtype, c.device) for c in confs]
+        return torch.from_numpy(state["out"])
+
+    @staticmethod
+    def backward(ctx, g):
+        st = ctx.state
+        inp, collected = st["inp"], st["collected"]
+        dev, B, N = inp["dev"], inp["B"], inp["N"]
+        g = np.ascontiguousarray(g.detach().cpu().numpy(), np.float64)
+        gm = torch.zeros_like(collected[2])
+        _tuple_ba_call("e2emv_mv_tuple_ba_backward", st["tuple_size"], collected, st["counts"], st["intr"], st["kdim"], st["nb"], st["start"],
+                       st["max_iterations"], _p(g), _lib.ptr(gm))
+        gouts = [None if c is None else torch.empty_like(c) for c in inp["cs"]]
+        ptrs = [_lib.ptr_array(lst) for lst in (inp["ms"], inp["cs"], gouts)]
+        with torch.cuda.device(dev):
+            _lib.context(dev).call("e2emv_mv_collect_backward", B, st["tuple_size"], N, _p(inp["n1"]), ptrs[0][0], ptrs[1][0], inp["channels"],
+                                   float(st["conf_thresh"]), _lib.ptr(gm), ptrs[2][0], _lib.stream_ptr(dev))
+        have = [go for go in gouts if go is not None]
+        return (None,) + tuple(go.reshape(shape).to(device, dtype) for go, (shape, dtype, device) in zip(have, ctx.meta))
+
+
+def refine_tuple_poses_batch(tuple_size, data, result, extrinsics, conf_thresh=0., max_iterations=50):
+    """The last stage of ``solve_tuple_poses_batch(..., tracks=False)`` from given start poses, with a graph: ``extrinsics`` [B,T,4,4]
+    world-to-camera start (a constant; the DLT start points made from it are constants too) -> the bundle-adjusted extrinsics, ``float64
+    [B,T,4,4]`` on the host, differentiable with respect to every ``conf_scores_{i}_{j}`` of ``result`` that requires grad (squared loss;
+    ``e2emv_mv_collect`` + ``e2emv_mv_tuple_ba`` forward, ``e2emv_mv_tuple_ba_backward`` + ``e2emv_mv_collect_backward`` backward: the
+    gradient reaches channel 0 of the rows ``conf_thresh`` keeps, everything else gets 0).  Without a graph it returns what that last
+    stage returns for the same start.  ``ValueError`` for a start of another shape and a negative or non-integer ``max_iterations``."""
+    max_iterations = _check_iterations("refine_tuple_poses_batch", max_iterations)
+    start = np.ascontiguousarray(extrinsics.detach().cpu().numpy() if torch.is_tensor(extrinsics) else extrinsics, np.float64)
+    if start.ndim != 4 or start.shape[1:] != (tuple_size, 4, 4):
+        raise ValueError(f"refine_tuple_poses_batch: extrinsics must be [B,{tuple_size},4,4] (got {start.shape})")
+    inp = _collect_inputs(tuple_size, data, result)
+    if len(start) != inp["B"]:
+        raise ValueError(f"refine_tuple_poses_batch: {len(start)} start tuples for a batch of {inp['B']}")
+    collected = _collect_call(tuple_size, inp, conf_thresh)
+    counts = collected[3].cpu().numpy()
+    intr, kdim, nb = _tuple_intrinsics(tuple_size, data, inp["dev"], inp["B"])
+    out, summary = np.zeros_like(start), np.zeros((len(start), 4))
+    _tuple_ba_call("e2emv_mv_tuple_ba", tuple_size, collected, counts, intr, kdim, nb, start, max_iterations, _p(out), _p(summary))
+    confs = [result[_key("conf_scores_", i, j)] for (i, j), c in zip(inp["pairs"], inp["cs"]) if c is not None]
+    if not (torch.is_grad_enabled() and any(c.requires_grad for c in confs)):
+        return torch.from_numpy(out)
+    state = dict(out=out, inp=inp, collected=collected, counts=counts, intr=intr, kdim=kdim, nb=nb, start=start, tuple_size=tuple_size,
+                 conf_thresh=conf_thresh, max_iterations=max_iterations)
+    return _RefineTuple.apply(state, *confs)
+
+
 def solve_tuple_poses(tuple_size, data, result, tmp_dir, rel_pose_method="w8pt_ba"):
     """Pairwise poses (``rel_pose_method`` as in ``initialize_bundle_adjust``) -> averaging -> weighted bundle adjustment for
     one tuple through the reference's four CSV files in ``tmp_dir``; returns the refined world-to-camera extrinsics
@@ -486,6 +631,12 @@ def _collect_matches_batch(tuple_size, data, result, conf_thresh):
     """``_collect_matches`` for every batch element at once and on the device (``e2emv_mv_collect``): returns ``(mkpts0, mkpts1
     [B*P,N,2], conf [B*P,N], count [B*P] int32)`` device tensors, problem (b, pair q) at row ``b * P + q``, the kept matches in
     ascending keypoint order, rows behind the count zero.  A pair without a ``matches`` entry has count 0."""
+    return _collect_call(tuple_size, _collect_inputs(tuple_size, data, result), conf_thresh)
+
+
+def _collect_inputs(tuple_size, data, result):
+    """What ``e2emv_mv_collect`` and ``e2emv_mv_collect_backward`` read: per pair the keypoints, matches and confidences as contiguous
+    device tensors (``None`` for a pair without a ``matches`` entry), the keypoint counts of the second images and the shapes."""
     pairs = _pairs(tuple_size)
     keys = [_key("matches", str(i), i, j) for i, j in pairs]
     have = [k for k in keys if k in result]
@@ -494,7 +645,6 @@ def _collect_matches_batch(tuple_size, data, result, conf_thresh):
     dev = result[have[0]].device
     if dev.type != "cuda":
         dev = _dev()
-    ctx = _lib.context(dev)
     B, N = result[have[0]].shape[:2]
     prep = lambda t, dt: t.to(dev, dt).contiguous()  # noqa: E731
     k0s, k1s, ms, cs, n1, channels = [], [], [], [], [], None
@@ -513,11 +663,16 @@ def _collect_matches_batch(tuple_size, data, result, conf_thresh):
             raise ValueError("matches / keypoints / conf_scores of pair {} disagree in shape".format((i, j)))
         channels = c.shape[2]
         k0s.append(k0); k1s.append(k1); ms.append(m); cs.append(c); n1.append(k1.shape[1])
+    return dict(dev=dev, B=B, N=N, pairs=pairs, k0s=k0s, k1s=k1s, ms=ms, cs=cs, n1=np.array(n1, np.int32), channels=channels)
+
+
+def _collect_call(tuple_size, inp, conf_thresh):
+    dev, B, N, pairs, k0s, k1s, ms, cs, n1, channels = (inp[k] for k in ("dev", "B", "N", "pairs", "k0s", "k1s", "ms", "cs", "n1", "channels"))
+    ctx = _lib.context(dev)
     Pn = B * len(pairs)
     o0 = torch.empty((Pn, N, 2), dtype=torch.float32, device=dev)
     o1, oc = torch.empty_like(o0), torch.empty((Pn, N), dtype=torch.float32, device=dev)
     count = torch.empty((Pn,), dtype=torch.int32, device=dev)
-    n1 = np.array(n1, np.int32)
     ptrs = [_lib.ptr_array(lst) for lst in (k0s, k1s, ms, cs)]  # (pointer, owner) pairs: the owners live until the call returns
     with torch.cuda.device(dev):
         ctx.call("e2emv_mv_collect", B, tuple_size, N, ptrs[0][0], ptrs[1][0], _p(n1), ptrs[2][0], ptrs[3][0], channels, float(conf_thresh),

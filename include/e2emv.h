@@ -269,6 +269,25 @@ int e2emv_mv_bundle_adjust_batch(e2emv_ctx* ctx, int n_problems, const int32_t* 
                                  const double* intr, const int64_t* pt_off, const int64_t* obs_off, const int32_t* cam_idx,
                                  const int32_t* pt_idx, const double* obs_xy, const double* obs_w, double* cams, double* pts,
                                  int max_iterations, double* summary, void* stream);
+/* The reverse pass of e2emv_mv_bundle_adjust_batch (squared loss only).  The inputs of that entry, all HOST; cams and pts are the
+ * START values and are read-only.  g_cams [sum C,6] = dLoss/d(cams out), g_pts [sum P,3] = dLoss/d(pts out) (NULL: zeros) ->
+ * g_obs_w [sum O,2], g_cams0 [sum C,6], g_pts0 [sum P,3] = dLoss/d(obs_w, cams start, pts start); any output may be NULL.  One
+ * workgroup per problem, fp64, one launch: the LM loop is run again from the inputs with a tape behind the solver's workspace (per
+ * pass the radius, the solved and the accept flag, per accepted step the iterate before it: max_iterations * (3 + 6 C + 3 P) doubles
+ * per problem, sized in size_t - E2EMV_ENOMEM when it cannot be reserved), then the accepted steps are reversed exactly from last to
+ * first: the damped system of the step solved by the forward's Schur complement and Cholesky factor with the adjoint as right-hand
+ * side, back through the residuals and their analytic Jacobians (second derivatives of the rotation in the branch the forward took).
+ * NO GRADIENT is carried by the radius (its rho-dependent update included), the Jacobi scales of the first iterate, the accept /
+ * reject comparisons, the termination tests, obs_xy and the intrinsics; a damping that sits on its clamp (1e-6, 1e32) is a
+ * constant; an unsolved or rejected step is the identity.  The fixed camera's row and the row of a camera without observations pass
+ * through (g_cams0 = g_cams there); a problem that stopped before any accepted step returns g_obs_w = 0, g_cams0 = g_cams, g_pts0
+ * = g_pts.  A problem's result does not depend on its neighbours or its position.  Shape errors as in the forward entry.
+ * Synchronous.                                                                                                                */
+int e2emv_mv_bundle_adjust_batch_backward(e2emv_ctx* ctx, int n_problems, const int32_t* n_cams, const int32_t* fixed_cam,
+                                          const double* intr, const int64_t* pt_off, const int64_t* obs_off, const int32_t* cam_idx,
+                                          const int32_t* pt_idx, const double* obs_xy, const double* obs_w, const double* cams,
+                                          const double* pts, int max_iterations, const double* g_cams, const double* g_pts,
+                                          double* g_obs_w, double* g_cams0, double* g_pts0, void* stream);
 /* `ba_in.csv` -> `ba_out.csv` (bundle_adjuster.cpp:7-23; parser ba_problem.cpp:8-88, writer :98-113), 50 iterations. */
 int e2emv_mv_bundle_adjust_files(e2emv_ctx* ctx, const char* in_csv, const char* out_csv, void* stream);
 /* cv2.triangulatePoints as used by write_bundle_adjust_problem (bundle_adjust_io.py:226-227): homogeneous DLT of
@@ -297,6 +316,25 @@ int e2emv_mv_collect(e2emv_ctx* ctx, int B, int T, int N, const float* const* d_
 int e2emv_mv_tuple_ba(e2emv_ctx* ctx, int B, int T, int N, const int32_t* counts, const float* d_mkpts0, const float* d_mkpts1,
                       const float* d_mconf, const float* const* d_intr, int kdim, int intr_batch, const double* extr,
                       int max_iterations, double* out_extr, double* summary, void* stream);
+/* The reverse pass of e2emv_mv_tuple_ba (squared loss only): its inputs, and g_out_extr HOST [B,T,4,4] = dLoss/d(out_extr) ->
+ * d_gmconf DEVICE [B*P,N] fp32 = dLoss/d(d_mconf), rows behind the count 0.  It goes through the 4x4 <-> angle-axis conversion of the
+ * result (the rotation's derivative in the branch its value takes; row 3 of g_out_extr is ignored), the solver backward
+ * (e2emv_mv_bundle_adjust_batch_backward's kernel on the problems built on the device), the two observations of a match with their x
+ * and y weight, and the weight normalisation conf / (0.5 (2 sum conf + 1e-3)) including the tuple's sum.  CONSTANTS here: the start
+ * extrinsics `extr` and the DLT start points made from them - the averaging that produces the start is not differentiable - and the
+ * keypoints and intrinsics.  The tape is sized in size_t, E2EMV_ENOMEM when it cannot be reserved.  Errors as e2emv_mv_tuple_ba.
+ * Synchronous.                                                                                                                  */
+int e2emv_mv_tuple_ba_backward(e2emv_ctx* ctx, int B, int T, int N, const int32_t* counts, const float* d_mkpts0, const float* d_mkpts1,
+                               const float* d_mconf, const float* const* d_intr, int kdim, int intr_batch, const double* extr,
+                               int max_iterations, const double* g_out_extr, float* d_gmconf, void* stream);
+/* The reverse of e2emv_mv_collect for the confidences: d_gmconf DEVICE [B*P,N] = dLoss/d(d_mconf) is scattered to d_gconf, a HOST
+ * array of P DEVICE pointers [B,N,conf_channels] (a NULL entry leaves that pair out), with the keep rule and the ascending order of
+ * e2emv_mv_collect (same B, T, N, n_kpts1, d_matches, d_conf, conf_channels, conf_thresh): the k-th kept row of a pair block gets slot k
+ * in channel 0; rows not kept, the other channels and every row of a pair without matches get 0.  One launch, no host
+ * synchronisation.                                                                                                              */
+int e2emv_mv_collect_backward(e2emv_ctx* ctx, int B, int T, int N, const int32_t* n_kpts1, const int64_t* const* d_matches,
+                              const float* const* d_conf, int conf_channels, float conf_thresh, const float* d_gmconf,
+                              float* const* d_gconf, void* stream);
 /* The problems e2emv_mv_tuple_ba would solve, copied out instead (HOST, concatenated in the layout
  * e2emv_mv_bundle_adjust_batch takes; tuple b owns n_b = sum of its counts points and 2 n_b observations): cam_idx, pt_idx
  * [2n], obs_xy, obs_w [2n,2], cams [B*T,6], pts [n,3].                                                                  */
