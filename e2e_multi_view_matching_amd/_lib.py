@@ -115,6 +115,8 @@ SIGNATURES = {
     "e2emv_mv_tracks_repair": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, _PP, _PP, c_int, c_float, c_int, c_void_p, c_void_p, c_void_p]),
     "e2emv_mv_tuple_ba_tracks": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, _PP, c_void_p, _PP, _PP, c_int, c_float, _PP,
                                          c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "e2emv_mv_tuple_ba_tracks_backward": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, _PP, c_void_p, _PP, _PP, c_int, c_float,
+                                                  _PP, c_int, c_int, c_void_p, c_int, c_void_p, _PP, c_void_p]),
     "e2emv_mv_tuple_problem_tracks": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, _PP, c_void_p, _PP, _PP, c_int, c_float,
                                               _PP, c_int, c_int, c_void_p] + [c_void_p] * 7),
     "e2emv_mv_bundle_adjust_batch_loss": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

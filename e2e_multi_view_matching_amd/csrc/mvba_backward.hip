@@ -8,8 +8,9 @@
 // and whether the step was solved and accepted, and per accepted step the iterate it started from.  When the run has ended the same
 // kernel walks the accepted steps backwards: this file holds what it calls there (mv_reverse_begin, mv_reverse_next, mv_reverse_step),
 // the only instantiation of that kernel (mv_launch_ba_backward), the reverse pass' share of the workspace and the C entry of the solver
-// level.  The tuple level (e2emv_mv_tuple_ba_backward, e2emv_mv_collect_backward) sits with the tuple build in mvba.hip; its
-// dLoss/d(extrinsics) enters here, in mv_reverse_begin, at the cameras the run ended with.
+// level.  The tuple level (e2emv_mv_tuple_ba_backward, e2emv_mv_collect_backward) sits with the tuple build in mvba.hip, that of the
+// track route (e2emv_mv_tuple_ba_tracks_backward) with the track build in mvtracks.hip; their dLoss/d(extrinsics) enters here, in
+// mv_reverse_begin, at the cameras the run ended with.
 //
 // REVERSE.  The accepted steps are walked from last to first with the adjoint state cams_bar (LDS) and pts_bar (workspace).  An
 // accepted step is x+ = x + d,  d = -M^-1 g,  M = J^T J + Lambda,  g = J^T r,  Lambda_ii = clamp(diag(J^T J)_ii s_i^2) / radius / s_i^2:

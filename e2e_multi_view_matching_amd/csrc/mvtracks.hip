@@ -552,6 +552,115 @@ __global__ __launch_bounds__(kMvRowThreads) void mv_tracks_emit_kernel(MvEmitArg
     }
 }
 
+// Reverse of the weights mv_tracks_emit_kernel hands the solver ("Backward pass of the track route").  Observation o is a
+// node of a track; c_o = the mean of its e_o kept edges inside the track, H = 0.5 (sum_o c_o + 1e-3), w_o = c_o / H on both weight
+// entries.  With G_o = g_w[2o] + g_w[2o+1] of the solver's reverse pass and D = sum_o G_o w_o:
+//     cbar_o = (G_o - 0.5 D) / H,     confbar of an edge inside a track = cbar_o / e_o of its one end + cbar_o / e_o of the other.
+// Every decision is the forward's: the labels, the keep rule (mv_edge), the members of a point (`member`, as the emit kernel left
+// it in the workspace) and the observation offsets (pt_start).  One workgroup per tuple, fp64, no atomics.
+//   pass 1  over the points, strided over the threads like the emit kernel's chunks: e_o recounted as that kernel counts `ce`, the sum
+//           of the node confidences and D in its order (a thread's points ascending, then lanes, then waves - H has the forward's
+//           bits); `share[o]` = cbar_o / e_o; `node_obs` = the observation of a node, -1 for a node in no track
+//   pass 2  thread = (pair, row): an edge the keep rule keeps whose ends carry the same label >= 0 gathers the shares of its two ends
+//           into channel 0; every other element of d_gconf[q][b] is written 0 (a NULL d_gconf[q] leaves the pair out)
+// A tuple without tracks (P = 0) reads nothing of its empty problem and writes zeros.  Every index is bounded by the record's sizes:
+// labels that disagree with the counts give a wrong gradient, not an access outside the workspace.
+struct MvTracksBwdArgs {
+    MvEdgeArgs e;
+    const int* label;              // [B,T,Nmax]
+    const int* member;             // [points of the batch,T] of the emit kernel
+    const MvbaArgs* recs;          // [B]
+    const MvbaBwdArgs* bw;         // [B]: g_w
+    double* share;                 // [observations of the batch]
+    int* node_obs;                 // [B,T,Nmax]
+    float* gconf[kMvMaxPairs];     // [B,N,channels] or NULL
+};
+__global__ __launch_bounds__(kMvRowThreads) void mv_tracks_weights_backward_kernel(MvTracksBwdArgs g) {
+    __shared__ double s_red[2 * (kMvRowThreads / 64)];
+    const MvEdgeArgs& e = g.e;
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int T = e.T, Nmax = e.Nmax, nodes = T * Nmax;
+    const MvbaArgs& a = g.recs[b];
+    const int P = a.P, O = a.O;
+    const int* member = g.member + size_t(a.pts - g.recs[0].pts) / 3 * T;
+    const int* label = g.label + size_t(b) * nodes;
+    int* node_obs = g.node_obs + size_t(b) * nodes;
+    double* share = g.share + size_t(a.obs - g.recs[0].obs) / 2;
+    const double* gw = g.bw[b].g_w;
+    for (int x = tid; x < nodes; x += kMvRowThreads) node_obs[x] = -1;
+    for (int o = tid; o < O; o += kMvRowThreads) share[o] = 0.0;
+    __syncthreads();
+    double conf_sum = 0.0, dot = 0.0;
+    for (int p = tid; p < P; p += kMvRowThreads) {
+        int mem[kMvMaxCams], k = 0;
+#pragma unroll
+        for (int t = 0; t < kMvMaxCams; ++t) {
+            mem[t] = t < T ? member[p * T + t] : -1;
+            if (mem[t] >= Nmax) mem[t] = -1;
+            k += mem[t] >= 0;
+        }
+        int o = a.pt_start[p];
+        if (o < 0 || o + k > O) continue;
+#pragma unroll
+        for (int t = 0; t < kMvMaxCams; ++t) {
+            if (mem[t] < 0) continue;
+            // confidence of the node: mean of its kept edges, other image ascending (mv_tracks_emit_kernel)
+            double cs = 0.0;
+            int ce = 0;
+#pragma unroll
+            for (int u = 0; u < kMvMaxCams; ++u) {
+                if (u == t || mem[u] < 0) continue;
+                float c = 0.f;
+                int m = -1;
+                if (u < t) {
+                    if (mem[u] < e.N) m = mv_edge(e, b, mv_pair_index(u, t), mem[u], &c);
+                    if (m != mem[t]) continue;
+                } else {
+                    if (mem[t] < e.N) m = mv_edge(e, b, mv_pair_index(t, u), mem[t], &c);
+                    if (m != mem[u]) continue;
+                }
+                cs += double(c);
+                ++ce;
+            }
+            conf_sum += ce ? cs / double(ce) : 0.0;
+            dot += (gw[2 * o] + gw[2 * o + 1]) * a.wts[2 * o];
+            share[o] = double(ce);
+            node_obs[t * Nmax + mem[t]] = o;
+            ++o;
+        }
+    }
+    conf_sum = wave_sum_d(conf_sum); dot = wave_sum_d(dot);
+    if (lane == 0) { s_red[wave] = conf_sum; s_red[kMvRowThreads / 64 + wave] = dot; }
+    __syncthreads();  // also: every share and node_obs of pass 1 is written
+    double total = s_red[0];
+    dot = s_red[kMvRowThreads / 64];
+    for (int w = 1; w < kMvRowThreads / 64; ++w) { total += s_red[w]; dot += s_red[kMvRowThreads / 64 + w]; }
+    const double H = 0.5 * (total + 1e-3);
+    for (int o = tid; o < O; o += kMvRowThreads) {
+        const double ce = share[o];
+        share[o] = ce > 0.0 ? (gw[2 * o] + gw[2 * o + 1] - 0.5 * dot) / H / ce : 0.0;
+    }
+    __syncthreads();
+    for (int q = 0; q < e.P; ++q) {
+        float* out = g.gconf[q];
+        if (!out) continue;
+        for (int n = tid; n < e.N; n += kMvRowThreads) {
+            float v = 0.f;
+            const int m = mv_edge(e, b, q, n, nullptr);
+            if (m >= 0) {
+                const int x = e.pi[q] * Nmax + n, y = e.pj[q] * Nmax + m, L = label[x];
+                if (L >= 0 && L == label[y]) {
+                    const int ox = node_obs[x], oy = node_obs[y];
+                    if (ox >= 0 && oy >= 0) v = float(share[ox] + share[oy]);
+                }
+            }
+            float* row = out + (size_t(b) * e.N + n) * e.channels;
+            row[0] = v;
+            for (int c = 1; c < e.channels; ++c) row[c] = 0.f;
+        }
+    }
+}
+
 // argument checks and the edge description shared by the three entry points
 static int mv_edge_args(e2emv_ctx* ctx, const char* who, int B, int T, int N, int Nmax, const int32_t* n1, const int64_t* const* d_matches,
                         const float* const* d_conf, int channels, float thresh, MvEdgeArgs* a) {
@@ -575,11 +684,13 @@ static int mv_edge_args(e2emv_ctx* ctx, const char* who, int B, int T, int N, in
     return E2EMV_OK;
 }
 
-// the track problems of the B tuples in the workspace, described by *L (the counterpart of mv_tuple_build)
+// the track problems of the B tuples in the workspace, described by *L (the counterpart of mv_tuple_build): `tail` bytes are reserved
+// behind the layout; emit_out (may be NULL) receives what the emit kernel was launched with - the edges, the labels, `member`, the records
 static int mv_tracks_build(e2emv_ctx* ctx, const char* who, int B, int T, int N, int Nmax, const int32_t* d_label, const int32_t* stats,
                            const float* const* d_kpts, const int32_t* n_kpts, const int64_t* const* d_matches, const float* const* d_conf,
                            int channels, float thresh, const float* const* d_intr, int kdim, int intr_batch, const double* extr,
-                           int max_iterations, double loss_scale, MvLayout* L, size_t* totP_out, size_t* totO_out, hipStream_t s) {
+                           int max_iterations, double loss_scale, size_t tail, MvLayout* L, size_t* totP_out, size_t* totO_out, MvEmitArgs* emit_out,
+                           hipStream_t s) {
     if (!d_label || !stats || !d_kpts || !n_kpts || !d_intr || !extr || Nmax < 1) return set_err(ctx, E2EMV_EINVAL, "%s: bad argument (Nmax >= 1, no NULL array)", who);
     if (T < 2 || T > kMvMaxCams) return set_err(ctx, E2EMV_EINVAL, "%s: tuple of %d images (2 <= T <= %d)", who, T, kMvMaxCams);
     if (kdim != 3 && kdim != 4) return set_err(ctx, E2EMV_ESHAPE, "%s: intrinsics must be 3x3 or 4x4", who);
@@ -609,7 +720,7 @@ static int mv_tracks_build(e2emv_ctx* ctx, const char* who, int B, int T, int N,
     }
     const size_t n = size_t(B), totC = n * T;
     const size_t proj_bytes = (totC * 12 * 8 + 255) & ~size_t(255), extra = proj_bytes + totP * T * sizeof(int);
-    rc = ws_reserve(ctx, mv_layout(nullptr, n, totC, totP, totO, extra).bytes);
+    rc = ws_reserve(ctx, mv_layout(nullptr, n, totC, totP, totO, extra).bytes + tail);
     if (rc) return rc;
     *L = mv_layout(ctx->d_ws, n, totC, totP, totO, extra);
     // one staging block = one copy: records, start cameras, (zero) camera list starts, projection matrices
@@ -643,6 +754,7 @@ static int mv_tracks_build(e2emv_ctx* ctx, const char* who, int B, int T, int N,
     hipLaunchKernelGGL(mv_tracks_emit_kernel, dim3(B), dim3(kMvRowThreads), lds, s, g);
     E2EMV_CHECK_LAUNCH(ctx, "mv_tracks_emit_kernel");
     *totP_out = totP; *totO_out = totO;
+    if (emit_out) *emit_out = g;
     return E2EMV_OK;
 }
 
@@ -701,7 +813,7 @@ extern "C" int e2emv_mv_tuple_ba_tracks_loss(e2emv_ctx* ctx, int B, int T, int N
     MvLayout L;
     size_t totP = 0, totO = 0;
     rc = mv_tracks_build(ctx, "mv_tuple_ba_tracks", B, T, N, Nmax, d_label, stats, d_kpts, n_kpts, d_matches, d_conf, conf_channels,
-                         conf_thresh, d_intr, kdim, intr_batch, extr, max_iterations, loss_scale, &L, &totP, &totO, s);
+                         conf_thresh, d_intr, kdim, intr_batch, extr, max_iterations, loss_scale, 0, &L, &totP, &totO, nullptr, s);
     if (rc) return rc;
     rc = mv_launch_ba(ctx, L, B, s, loss);
     if (rc) return rc;
@@ -729,7 +841,7 @@ extern "C" int e2emv_mv_tuple_problem_tracks(e2emv_ctx* ctx, int B, int T, int N
     MvLayout L;
     size_t totP = 0, totO = 0;
     const int rc = mv_tracks_build(ctx, "mv_tuple_problem_tracks", B, T, N, Nmax, d_label, stats, d_kpts, n_kpts, d_matches, d_conf,
-                                   conf_channels, conf_thresh, d_intr, kdim, intr_batch, extr, 0, 0.0, &L, &totP, &totO, s);
+                                   conf_channels, conf_thresh, d_intr, kdim, intr_batch, extr, 0, 0.0, 0, &L, &totP, &totO, nullptr, s);
     if (rc) return rc;
     if (totP && (!cam_idx || !pt_idx || !obs_xy || !obs_w || !pts)) return set_err(ctx, E2EMV_EINVAL, "mv_tuple_problem_tracks: NULL output for %zu points", totP);
     E2EMV_HIP(ctx, hipMemcpyAsync(cams, L.cams, sizeof(double) * 6 * B * T, hipMemcpyDeviceToHost, s));
@@ -740,6 +852,62 @@ extern "C" int e2emv_mv_tuple_problem_tracks(e2emv_ctx* ctx, int B, int T, int N
         E2EMV_HIP(ctx, hipMemcpyAsync(obs_w, L.wts, sizeof(double) * 2 * totO, hipMemcpyDeviceToHost, s));
         E2EMV_HIP(ctx, hipMemcpyAsync(pts, L.pts, sizeof(double) * 3 * totP, hipMemcpyDeviceToHost, s));
     }
+    E2EMV_HIP(ctx, hipStreamSynchronize(s));
+    return E2EMV_OK;
+}
+
+extern "C" int e2emv_mv_tuple_ba_tracks_backward(e2emv_ctx* ctx, int B, int T, int N, int Nmax, const int32_t* d_label, const int32_t* stats,
+                                                 const float* const* d_kpts, const int32_t* n_kpts, const int64_t* const* d_matches,
+                                                 const float* const* d_conf, int conf_channels, float conf_thresh, const float* const* d_intr,
+                                                 int kdim, int intr_batch, const double* extr, int max_iterations, const double* g_out_extr,
+                                                 float* const* d_gconf, void* stream) {
+    if (!ctx) return E2EMV_EINVAL;
+    E2EMV_ENTER(ctx, stream);
+    const char* who = "mv_tuple_ba_tracks_backward";
+    if (!g_out_extr || !d_gconf) return set_err(ctx, E2EMV_EINVAL, "%s: NULL g_out_extr / d_gconf", who);
+    if (B < 1 || T < 2 || T > kMvMaxCams || Nmax < 1 || !stats) return set_err(ctx, E2EMV_EINVAL, "%s: bad argument (B, Nmax >= 1, 2 <= T <= %d, stats)", who, kMvMaxCams);
+    // the tape is sized from the counts the labels were made with (mv_tracks_build's rule for them)
+    std::vector<int> Cs(B, T), Ps(B, 0), Os(B, 0);
+    for (int b = 0; b < B; ++b) {
+        const int Pb = stats[4 * b], Ob = stats[4 * b + 1];
+        if (Pb < 0 || Ob < 2 * Pb || Ob > T * Pb || size_t(Ob) > size_t(T) * size_t(Nmax))
+            return set_err(ctx, E2EMV_EINVAL, "%s: tuple %d counts %d tracks / %d observations (2 .. %d views per track, at most %zu nodes)", who, b, Pb, Ob, T, size_t(T) * Nmax);
+        Ps[b] = Pb; Os[b] = Ob;
+    }
+    bool overflow = false;
+    const size_t tape = mv_bwd_bytes(Cs, Ps, Os, max_iterations, &overflow);
+    int rc = mv_bwd_fits(ctx, who, tape, overflow);
+    if (rc) return rc;
+    // behind the solver's share: cbar_o / e_o per observation and the observation of every node
+    size_t sumO = 0;
+    for (int b = 0; b < B; ++b) sumO += size_t(Os[b]);
+    const size_t tape_al = (tape + 255) & ~size_t(255), share_bytes = (sumO * sizeof(double) + 255) & ~size_t(255);
+    const size_t tail = tape_al + share_bytes + size_t(B) * T * size_t(Nmax) * sizeof(int);
+    hipStream_t s = (hipStream_t)stream;
+    MvLayout L;
+    MvEmitArgs emit{};
+    size_t totP = 0, totO = 0;
+    rc = mv_tracks_build(ctx, who, B, T, N, Nmax, d_label, stats, d_kpts, n_kpts, d_matches, d_conf, conf_channels, conf_thresh, d_intr, kdim,
+                         intr_batch, extr, max_iterations, 0.0, tail, &L, &totP, &totO, &emit, s);
+    if (rc) return rc;
+    char* base = ctx->d_ws + L.bytes;
+    MvBwdLayout W;
+    rc = mv_bwd_carve(ctx, base, Cs, Ps, Os, max_iterations, true, &W, s);
+    if (rc) return rc;
+    const size_t totC = size_t(B) * T;
+    E2EMV_HIP(ctx, hipMemsetAsync(W.cams_bar, 0, sizeof(double) * 6 * totC, s));
+    if (totP) E2EMV_HIP(ctx, hipMemsetAsync(W.pts_bar, 0, sizeof(double) * 3 * totP, s));
+    E2EMV_HIP(ctx, hipMemcpyAsync(W.g_extr, g_out_extr, sizeof(double) * 16 * totC, hipMemcpyHostToDevice, s));
+    E2EMV_HIP(ctx, hipStreamSynchronize(s));  // g_out_extr is the caller's
+    rc = mv_launch_ba_backward(ctx, L, W, B, s);
+    if (rc) return rc;
+    MvTracksBwdArgs g{};
+    g.e = emit.e; g.label = emit.label; g.member = emit.member; g.recs = L.recs; g.bw = W.recs;
+    g.share = reinterpret_cast<double*>(base + tape_al);
+    g.node_obs = reinterpret_cast<int*>(base + tape_al + share_bytes);
+    for (int q = 0; q < g.e.P; ++q) g.gconf[q] = d_gconf[q];
+    hipLaunchKernelGGL(mv_tracks_weights_backward_kernel, dim3(B), dim3(kMvRowThreads), 0, s, g);
+    E2EMV_CHECK_LAUNCH(ctx, "mv_tracks_weights_backward_kernel");
     E2EMV_HIP(ctx, hipStreamSynchronize(s));
     return E2EMV_OK;
 }

@@ -586,17 +586,69 @@ class _RefineTuple(torch.autograd.Function):
         return (None,) + tuple(go.reshape(shape).to(device, dtype) for go, (shape, dtype, device) in zip(have, ctx.meta))
 
 
-def refine_tuple_poses_batch(tuple_size, data, result, extrinsics, conf_thresh=0., max_iterations=50):
-    """The last stage of ``solve_tuple_poses_batch(..., tracks=False)`` from given start poses, with a graph: ``extrinsics`` [B,T,4,4]
-    world-to-camera start (a constant; the DLT start points made from it are constants too) -> the bundle-adjusted extrinsics, ``float64
-    [B,T,4,4]`` on the host, differentiable with respect to every ``conf_scores_{i}_{j}`` of ``result`` that requires grad (squared loss;
-    ``e2emv_mv_collect`` + ``e2emv_mv_tuple_ba`` forward, ``e2emv_mv_tuple_ba_backward`` + ``e2emv_mv_collect_backward`` backward: the
-    gradient reaches channel 0 of the rows ``conf_thresh`` keeps, everything else gets 0).  Without a graph it returns what that last
-    stage returns for the same start.  ``ValueError`` for a start of another shape and a negative or non-integer ``max_iterations``."""
+class _RefineTupleTracks(torch.autograd.Function):
+    """Attaches the graph of ``refine_tuple_poses_batch(..., tracks=True)``: the forward result is computed by the caller; the backward
+    runs ``e2emv_mv_tuple_ba_tracks_backward`` on the labels and counts the forward ran with."""
+
+    @staticmethod
+    def forward(ctx, state, *confs):
+        ctx.state = state
+        ctx.meta = [(c.shape, c.dtype, c.device) for c in confs]
+        return torch.from_numpy(state["out"])
+
+    @staticmethod
+    def backward(ctx, g):
+        st = ctx.state
+        inp = st["inp"]
+        g = np.ascontiguousarray(g.detach().cpu().numpy(), np.float64)
+        gouts = [None if c is None else torch.empty_like(c) for c in inp["conf"]]
+        pg, owner = _lib.ptr_array(gouts)
+        _tracks_entry_call("e2emv_mv_tuple_ba_tracks_backward", st["tuple_size"], inp, st["label"], st["stats"], st["conf_thresh"], st["intr"],
+                           st["kdim"], st["nb"], st["start"], st["max_iterations"], _p(g), pg)
+        del owner
+        have = [go for go in gouts if go is not None]
+        return (None,) + tuple(go.reshape(shape).to(device, dtype) for go, (shape, dtype, device) in zip(have, ctx.meta))
+
+
+def _refine_tuple_tracks(tuple_size, data, result, start, conf_thresh, max_iterations, repair_rounds):
+    inp, label, stats = _tracks_labels(tuple_size, data, result, conf_thresh, repair_rounds)
+    if len(start) != inp["B"]:
+        raise ValueError(f"refine_tuple_poses_batch: {len(start)} start tuples for a batch of {inp['B']}")
+    intr, kdim, nb = _tuple_intrinsics(tuple_size, data, inp["dev"], inp["B"])
+    out, summary = np.zeros_like(start), np.zeros((len(start), 4))
+    _tracks_entry_call("e2emv_mv_tuple_ba_tracks", tuple_size, inp, label, stats, conf_thresh, intr, kdim, nb, start, max_iterations, _p(out),
+                       _p(summary))
+    confs = [result[_key("conf_scores_", i, j)] for (i, j), c in zip(_pairs(tuple_size), inp["conf"]) if c is not None]
+    if not (torch.is_grad_enabled() and any(c.requires_grad for c in confs)):
+        return torch.from_numpy(out)
+    state = dict(out=out, inp=inp, label=label, stats=stats, intr=intr, kdim=kdim, nb=nb, start=start, tuple_size=tuple_size,
+                 conf_thresh=conf_thresh, max_iterations=max_iterations)
+    return _RefineTupleTracks.apply(state, *confs)
+
+
+def refine_tuple_poses_batch(tuple_size, data, result, extrinsics, conf_thresh=0., max_iterations=50, tracks=False, repair_rounds=0):
+    """The last stage of ``solve_tuple_poses_batch`` from given start poses, with a graph: ``extrinsics`` [B,T,4,4] world-to-camera start
+    (a constant; the DLT start points made from it are constants too) -> the bundle-adjusted extrinsics, ``float64 [B,T,4,4]`` on the
+    host, differentiable with respect to every ``conf_scores_{i}_{j}`` of ``result`` that requires grad (squared loss).
+    ``tracks=False`` (default), the pair route: ``e2emv_mv_collect`` + ``e2emv_mv_tuple_ba`` forward, ``e2emv_mv_tuple_ba_backward`` +
+    ``e2emv_mv_collect_backward`` backward: the gradient reaches channel 0 of the rows ``conf_thresh`` keeps, everything else gets 0.
+    ``tracks=True``, the track route (needs per-image ``keypoints{t}``, as in ``solve_tuple_poses_batch``): the labels of
+    ``match_tracks(..., repair_rounds=)`` are computed once, ``e2emv_mv_tuple_ba_tracks`` runs on them and
+    ``e2emv_mv_tuple_ba_tracks_backward`` reverses it ON THE SAME LABELS: labels, keep rule and cuts are frozen; the gradient reaches
+    channel 0 of every kept edge whose two keypoints lie in one track (a cut edge inside its final track included), everything else -
+    dropped conflicts, edges between two tracks, rows the threshold drops, the other channels - gets exactly 0.
+    Without a graph it returns what that last stage returns for the same start.  ``ValueError``, before any device call, for a start of
+    another shape, a negative or non-integer ``max_iterations``, ``tracks=True`` without ``keypoints{t}``, and a ``repair_rounds``
+    outside 0 .. 64 or non-zero without ``tracks``."""
     max_iterations = _check_iterations("refine_tuple_poses_batch", max_iterations)
+    _check_repair_rounds(repair_rounds, tracks)
+    if tracks:
+        _check_tracks(tuple_size, data)
     start = np.ascontiguousarray(extrinsics.detach().cpu().numpy() if torch.is_tensor(extrinsics) else extrinsics, np.float64)
     if start.ndim != 4 or start.shape[1:] != (tuple_size, 4, 4):
         raise ValueError(f"refine_tuple_poses_batch: extrinsics must be [B,{tuple_size},4,4] (got {start.shape})")
+    if tracks:
+        return _refine_tuple_tracks(tuple_size, data, result, start, conf_thresh, max_iterations, repair_rounds)
     inp = _collect_inputs(tuple_size, data, result)
     if len(start) != inp["B"]:
         raise ValueError(f"refine_tuple_poses_batch: {len(start)} start tuples for a batch of {inp['B']}")
@@ -858,20 +910,31 @@ def match_tracks(tuple_size, data, result, conf_thresh=0., _inputs=None, repair_
     return label, stats
 
 
-def _tracks_ba_call(name, tuple_size, data, result, conf_thresh, intr, kdim, nb, extrinsics, *tail, repair_rounds=0):
-    """Labels (``match_tracks``), the one small copy of their counts to the host, then the track entry point ``name``.  Returns
-    ``(label, stats)``, the counts as a host array.  ``repair_rounds``: as in ``match_tracks``; the entry point takes the repaired
-    labels like any others (it weighs a node by the KEPT edges between the members of its track, cut or not)."""
+def _tracks_labels(tuple_size, data, result, conf_thresh, repair_rounds=0):
+    """``(inp, label, stats)``: the device arrays of ``_track_inputs``, the labels of ``match_tracks`` on them and the one small copy of
+    their counts to the host (tracks and observations per tuple lay out the workspace)."""
     _check_repair_rounds(repair_rounds)
     inp = _track_inputs(tuple_size, data, result)
-    dev = inp["dev"]
     label, stats_d = match_tracks(tuple_size, data, result, conf_thresh, _inputs=inp, repair_rounds=repair_rounds)
-    stats = np.ascontiguousarray(stats_d.cpu().numpy())  # tracks and observations per tuple lay out the workspace
+    return inp, label, np.ascontiguousarray(stats_d.cpu().numpy())
+
+
+def _tracks_entry_call(name, tuple_size, inp, label, stats, conf_thresh, intr, kdim, nb, extrinsics, *tail):
+    """The track entry point ``name`` on given labels and counts (forward and backward run on the SAME ones)."""
+    dev = inp["dev"]
     extrinsics = np.ascontiguousarray(extrinsics, np.float64)
     pk, pm, pc, pi = (_lib.ptr_array(lst) for lst in (inp["kpts"], inp["matches"], inp["conf"], intr))
     with torch.cuda.device(dev):
         _lib.context(dev).call(name, inp["B"], tuple_size, inp["N"], inp["Nmax"], _lib.ptr(label), _p(stats), pk[0], _p(inp["n_kpts"]), pm[0], pc[0],
                                inp["channels"], float(conf_thresh), pi[0], kdim, nb, _p(extrinsics), *tail, _lib.stream_ptr(dev))
+
+
+def _tracks_ba_call(name, tuple_size, data, result, conf_thresh, intr, kdim, nb, extrinsics, *tail, repair_rounds=0):
+    """Labels (``match_tracks``), the one small copy of their counts to the host, then the track entry point ``name``.  Returns
+    ``(label, stats)``, the counts as a host array.  ``repair_rounds``: as in ``match_tracks``; the entry point takes the repaired
+    labels like any others (it weighs a node by the KEPT edges between the members of its track, cut or not)."""
+    inp, label, stats = _tracks_labels(tuple_size, data, result, conf_thresh, repair_rounds)
+    _tracks_entry_call(name, tuple_size, inp, label, stats, conf_thresh, intr, kdim, nb, extrinsics, *tail)
     return label, stats
 
 

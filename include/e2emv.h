@@ -393,6 +393,23 @@ int e2emv_mv_tuple_problem_tracks(e2emv_ctx* ctx, int B, int T, int N, int Nmax,
                                   const float* const* d_conf, int conf_channels, float conf_thresh, const float* const* d_intr,
                                   int kdim, int intr_batch, const double* extr, int32_t* cam_idx, int32_t* pt_idx,
                                   double* obs_xy, double* obs_w, double* cams, double* pts, void* stream);
+/* The reverse pass of e2emv_mv_tuple_ba_tracks (squared loss only): its inputs - the SAME d_label and stats the forward ran with - and
+ * g_out_extr HOST [B,T,4,4] = dLoss/d(out_extr) -> d_gconf, a HOST array of P DEVICE pointers [B,N,conf_channels] fp32 = dLoss/d(d_conf)
+ * (a NULL entry leaves that pair out; every element of the others is written, the caller need not clear them).  It goes through the
+ * 4x4 <-> angle-axis conversion and the solver backward as e2emv_mv_tuple_ba_backward does, then through the track weights: with c_o the
+ * mean of the e_o kept edges between observation o's node and the other members of its track, H = 0.5 (sum c_o + 1e-3), w_o = c_o / H,
+ * G_o the sum of the two dLoss/dw of o and D = sum G_o w_o:  cbar_o = (G_o - D / 2) / H,  and an edge whose two nodes carry the same
+ * label >= 0 gets cbar / e of its one node + cbar / e of the other in channel 0 - a cut edge inside its final track included.  Exactly 0:
+ * rows the keep rule drops, edges of unlabelled nodes (dropped conflicts), edges between two tracks, the other channels, every row of a
+ * tuple without tracks.  FROZEN: labels, keep rule, cuts, and what the solver backward freezes.  CONSTANTS: extr, the DLT start points,
+ * keypoints and intrinsics.  One workgroup per tuple, fp64, no atomics: the same words alone, at any batch position and run to run.
+ * Errors as e2emv_mv_tuple_ba_tracks; E2EMV_EINVAL for a NULL g_out_extr / d_gconf; the tape is sized in size_t, E2EMV_ENOMEM when it
+ * cannot be reserved.  Synchronous.                                                                                            */
+int e2emv_mv_tuple_ba_tracks_backward(e2emv_ctx* ctx, int B, int T, int N, int Nmax, const int32_t* d_label, const int32_t* stats,
+                                      const float* const* d_kpts, const int32_t* n_kpts, const int64_t* const* d_matches,
+                                      const float* const* d_conf, int conf_channels, float conf_thresh, const float* const* d_intr,
+                                      int kdim, int intr_batch, const double* extr, int max_iterations, const double* g_out_extr,
+                                      float* const* d_gconf, void* stream);
 
 /* Robust loss in the multi-view bundle adjustment: a ceres::LossFunction where the reference passes NULL
  * (ba_problem.cpp:135,144).  One residual block = one observation; s = rx^2 + ry^2 of the WEIGHTED residual; the cost is
