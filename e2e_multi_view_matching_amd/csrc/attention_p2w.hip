@@ -10,8 +10,20 @@
 //     segment X(j):  matrix pipe  P_0(j) V(j) -> O_0,   K(j+1) Q_0 -> S_0(j+1)      vector pipe  softmax of S_1(j)   -> P_1(j)
 //     segment Y(j):  matrix pipe  P_1(j) V(j) -> O_1,   K(j+1) Q_1 -> S_1(j+1)      vector pipe  softmax of S_0(j+1) -> P_0(j+1)
 //
-// one MFMA per slot with three vector instructions of the OTHER stream's softmax, one fragment read and (now and then) one
+// one MFMA per slot with three vector instructions of the OTHER stream's softmax, in X one fragment read and (now and then) one
 // LDS-direct load behind it, fenced by sched_barrier so that the order of the source is the order of the machine code.
+//
+// Both segments of a tile multiply by the SAME 32 fragments - 16 of V(j), 16 of K(j+1) - and each is read from LDS ONCE, by
+// segment X, into a HOME of its own in the accumulator file: FA[8][4], 128 registers beside O (64) and the Q fragments (64),
+// all 256 of the file.  An MFMA takes its A operand from there at no cost, so segment Y issues no fragment read for itself.
+// The reads are asm ds_read_b128 (hipcc has no other way to load into that file) and therefore waited for by hand:
+//   - X reads group g + 2 (6 MFMAs = one 16-column step of V^T or K) in slots 1..4 of its group g, and waits at the head of
+//     group g with lgkmcnt(4) - LDS answers in order, and only the four reads of group g + 1 are younger than group g's -
+//     and with lgkmcnt(0) at the head of its last group.  Behind that wait every home is valid for all of Y.
+//   - Y reads only groups 0 and 1 of X(j+1), in its own groups 6 and 7: behind the tile's barrier, from the region the barrier
+//     has made valid.  Region j % 3 is not read during Y(j) at all.
+//   - A home is rewritten 32 MFMA slots after the last MFMA of Y that named it was issued (never sooner than 12).
+// The barrier and the counted vmcnt of the LDS-direct loads stand where they stood.
 // The softmax of a tile has no row maximum on its fast path: the numerators are formed against the running maximum of the
 // stream, their sum is checked at the end of the segment (every p <= sum < 60000 stays inside fp16), and only a tile
 // that fails the check - the first one, and one whose scores outgrow the running maximum by more than ~2^5 - is redone on
@@ -20,7 +32,7 @@
 // LDS: three regions of 32 KB, region j % 3 = [ V(j) | K(j+1) ], filled by LDS-direct loads TWO tiles ahead (issued in
 // segment X(j-2), awaited with a counted vmcnt at the one barrier of a tile, slot 36 of segment Y(j-1): the workgroups of
 // an (image, head) walk its keys in lock step, so every tile is an L2 miss for all of them - one tile of lead did not cover
-// it); fragment reads run two groups of 6 MFMAs ahead, across segment and tile boundaries.
+// it); fragment reads run two groups of 6 MFMAs ahead of their first use, across the tile boundary.
 #include <algorithm>
 #include <type_traits>
 
@@ -109,8 +121,32 @@ __device__ __forceinline__ void aw_mfma_s(aw_f32x16& c, p2_f16x8 a, p2_f16x8 b) 
 __device__ __forceinline__ void aw_mfma_s0(aw_f32x16& c, p2_f16x8 a, p2_f16x8 b) {  // S = K Q^T (zero C operand)
     asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, 0" : "=&v"(c) : "v"(a), "a"(b));
 }
-__device__ __forceinline__ void aw_mfma_o(aw_f32x16& c, p2_f16x8 a, p2_u32x4 b) {   // O += V^T P^T: C in AGPRs
-    asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+a"(c) : "v"(a), "v"(b));
+// the segments' MFMAs take their A operand (a K or V^T fragment) from its HOME in the accumulator file as well (header)
+__device__ __forceinline__ void aw_mfma_sa(aw_f32x16& c, p2_f16x8 a, p2_f16x8 b) {  // S += K Q^T: A and B in AGPRs
+    asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(c) : "a"(a), "a"(b));
+}
+__device__ __forceinline__ void aw_mfma_sa0(aw_f32x16& c, p2_f16x8 a, p2_f16x8 b) {  // S = K Q^T (zero C operand)
+    asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, 0" : "=&v"(c) : "a"(a), "a"(b));
+}
+__device__ __forceinline__ void aw_mfma_oa(aw_f32x16& c, p2_f16x8 a, p2_u32x4 b) {  // O += V^T P^T: C and A in AGPRs, P in VGPRs
+    asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+a"(c) : "a"(a), "v"(b));
+}
+// One fragment (16 bytes per lane) from LDS into its home.  IMM = (V | K) x AW_TILEB + row block x 8192 is the instruction's
+// immediate offset.  Like aw_load_q an asm load is not counted by hipcc: aw_wait_frag is the wait.
+template <int IMM>
+__device__ __forceinline__ void aw_read_frag(p2_f16x8& d, unsigned addr) {
+    static_assert(IMM >= 0 && IMM < 65536, "ds_read offset: 16 bits");
+    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=a"(d) : "v"(addr), "n"(IMM));
+}
+// The wait in front of a group's first MFMA, naming the group's four homes: LDS answers in order, so with N reads issued
+// behind the group's own, lgkmcnt(N) says that these four have landed.  Whatever else is in flight on the same counter -
+// the {e_k, e_v} pair of read_e, the scalar loads of cur_next, both issued and counted by hipcc - only adds to the count, and
+// the wait then asks for MORE completions than it needs (a scalar load that answers out of order still leaves at most N
+// operations outstanding, of which the N youngest LDS reads are the ones behind this group's); hipcc's own waits for those
+// operations count without the asm reads and are stricter for the same reason.
+template <int N>
+__device__ __forceinline__ void aw_wait_frag(p2_f16x8 (&f)[4]) {
+    asm volatile("s_waitcnt lgkmcnt(%4)" : "+a"(f[0]), "+a"(f[1]), "+a"(f[2]), "+a"(f[3]) : "n"(N));
 }
 // the 8 fragments of a query row (2 planes x 4 steps of 16 dims), loaded from global memory straight INTO the accumulator
 // file, where they stay.  An asm load is not counted by hipcc: aw_wait_q, which names every destination, is the wait (it
@@ -403,17 +439,22 @@ __global__ __launch_bounds__(256, 1) void attention_p2w_kernel(AttnP2Params p) {
         for (int pl = 0; pl < 2; ++pl) R[s][pl] -= 2 * AW_REGB;  // region 0
     int reg_cur = 0, seg_tile = 0;
 
-    // fragment registers: group g of a segment (6 MFMAs: one 16-key step of V^T, or one 16-dim step of K) uses F[g & 3]; the
-    // reads run TWO groups (12 MFMAs) ahead of their use - one group ahead the matrix pipe waited for LDS (measured)
-    p2_f16x8 F[4][4];  // [buffer][2 x + pl], x = row block (dims 0-31 / 32-63 of V^T, keys 0-31 / 32-63 of K)
-    // read number n (0..3) of a group, in the order the group's MFMAs need them: (x0, lo) (x1, lo) (x0, hi) (x1, hi)
-    auto read_frag = [&](int buf, int n, int s, int kpart) __attribute__((always_inline)) {
-        const int x = n & 1, pl = n < 2 ? 1 : 0;
-        F[buf][2 * x + pl] = frag(s, pl, kpart * AW_TILEB + x * 8192);
+    // fragment homes: group g of a segment (6 MFMAs: one 16-key step of V^T, g < 4, or one 16-dim step of K, g >= 4) has the
+    // four register quads FA[g] of the accumulator file for its own; segment X fills them, X and Y both multiply out of them.
+    // The reads run TWO groups (12 MFMAs) ahead of their first use - one group ahead the matrix pipe waited for LDS (measured)
+    p2_f16x8 FA[8][4];  // [group][n], n = the order the group's MFMAs need them: (x0, lo) (x1, lo) (x0, hi) (x1, hi),
+                        // x = row block (dims 0-31 / 32-63 of V^T, keys 0-31 / 32-63 of K)
+    // read number N of group G: 16-column step S of V (KPART = 0) or K (KPART = 1) of the region R points at
+    auto read_frag = [&](auto GG, auto NN, auto SS, auto KK) __attribute__((always_inline)) {
+        constexpr int G = decltype(GG)::value, N = decltype(NN)::value, S = decltype(SS)::value, KPART = decltype(KK)::value;
+        constexpr int x = N & 1, pl = N < 2 ? 1 : 0;
+        aw_read_frag<KPART * AW_TILEB + x * 8192>(FA[G][N], R[S][pl]);
     };
-    // groups 0 and 1 of segment X(0): V(0), 16-key steps 0 and 1
-#pragma unroll
-    for (int n = 0; n < 4; ++n) { read_frag(0, n, 0, 0); read_frag(1, n, 1, 0); }
+    // groups 0 and 1 of segment X(0): V(0), 16-key steps 0 and 1 - group by group, the order the counted waits of X assume
+    aw_for<0, 8>([&](auto II) __attribute__((always_inline)) {
+        constexpr int g = decltype(II)::value / 4, n = decltype(II)::value % 4;
+        read_frag(std::integral_constant<int, g>{}, std::integral_constant<int, n>{}, std::integral_constant<int, g>{}, std::integral_constant<int, 0>{});
+    });
 
     // ---- one segment.  A = the stream on the matrix pipe, B = 1 - A the stream whose softmax runs beside it; LAST = the last
     // tile (no K(j+1) left: 24 MFMAs; segment Y then has no softmax either)
@@ -511,14 +552,18 @@ __global__ __launch_bounds__(256, 1) void attention_p2w_kernel(AttnP2Params p) {
         aw_for<0, NSLOT>([&](auto II) __attribute__((always_inline)) {
             constexpr int i = decltype(II)::value;
             constexpr int gq = i / 6, w = i % 6;
-            // (1) the slot's MFMA
+            // (0) segment X, head of a group: the group's four fragments have landed in their homes.  They were read two groups
+            // back; behind them only the next group's four reads have been issued (this group's slots 1..4 come after the
+            // wait), and behind the LAST group's nothing.  That last wait makes every home valid for all of segment Y.
+            if constexpr (A == 0 && w == 0) aw_wait_frag<(gq + 1 < NG ? 4 : 0)>(FA[gq]);
+            // (1) the slot's MFMA: plane PA[q] of row block x sits in the group's home number x + 2 (1 - PA[q])
             if constexpr (i < 24) {
                 constexpr int u = i / 6, q = (i % 6) / 2, db = i % 2;
-                aw_mfma_o(O[A][db], F[u & 3][2 * db + PA[q]], Pf[A][PB[q]][u]);
+                aw_mfma_oa(O[A][db], FA[u][db + 2 * (1 - PA[q])], Pf[A][PB[q]][u]);
             } else {
                 constexpr int s = (i - 24) / 6, q = (i % 6) / 2, kb = i % 2;
-                if constexpr (s == 0 && q == 0) aw_mfma_s0(S[A][kb], F[(4 + s) & 3][2 * kb + PA[q]], Qf[A][PB[q]][s]);
-                else aw_mfma_s(S[A][kb], F[(4 + s) & 3][2 * kb + PA[q]], Qf[A][PB[q]][s]);
+                if constexpr (s == 0 && q == 0) aw_mfma_sa0(S[A][kb], FA[4 + s][kb + 2 * (1 - PA[q])], Qf[A][PB[q]][s]);
+                else aw_mfma_sa(S[A][kb], FA[4 + s][kb + 2 * (1 - PA[q])], Qf[A][PB[q]][s]);
             }
             // (2) the other stream's softmax.  A full segment runs its 50 micro-steps in slots 0 .. 45 (two in four of the first
             // nine), sums up in slot 46 and evaluates the range check in slot 47 - INSIDE the stream: behind the last MFMA of a
@@ -544,7 +589,8 @@ __global__ __launch_bounds__(256, 1) void attention_p2w_kernel(AttnP2Params p) {
                 }
             }
             // (3) the tile's barrier (segment Y only, head of group 6): the pieces issued in X(j) have landed, everybody's; nobody
-            // reads region j % 3 any more (the fragments of this segment's last groups were read in slots 25..34)
+            // reads region j % 3 any more (segment Y reads no fragment of it at all: X's last reads of it were waited for at the
+            // head of X's group 7)
             if constexpr (A == 1 && !LAST && i == 36) {
                 // counted: the 8 pieces issued in X(j) - the tile after next - stay in flight
                 asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)\n\ts_barrier" ::: "memory");
@@ -555,15 +601,19 @@ __global__ __launch_bounds__(256, 1) void attention_p2w_kernel(AttnP2Params p) {
                     for (int pl = 0; pl < 2; ++pl) R[s][pl] += d;
                 reg_cur = reg_cur == 2 ? 0 : reg_cur + 1;
             }
-            // (4) fragment reads of the group after next (slots 1..4 of a group); past this segment's last group they are
-            // groups 0 / 1 of the NEXT segment - behind the barrier where that is the next tile
+            // (4) fragment reads (slots 1..4 of a group).  Segment X: the group after next of this tile, into its home.  Segment
+            // Y has every operand in the homes already; it reads groups 0 / 1 of X(j+1) - V(j+1), steps 0 / 1, from the region
+            // R moved to at the barrier - in its groups 6 / 7, behind that barrier.  A home is rewritten 32 slots after its
+            // last MFMA in Y was issued (group g + 2 <= 7: Y's slot 6 g + 17, X's slot 6 g + 1; groups 0 / 1: Y's slots 5 / 11
+            // and 37 / 43), and an MFMA has read its operands long before that.
             if constexpr (w >= 1 && w <= 4) {
                 constexpr int gn = gq + 2;
-                if constexpr (gn < NG) {
-                    if constexpr (gn < 4) read_frag(gn & 3, w - 1, gn, 0);       // V(j), 16-key step gn
-                    else read_frag(gn & 3, w - 1, gn - 4, 1);                    // K(j+1), 16-dim step gn - 4
-                } else if constexpr (!(LAST && A == 1)) {
-                    read_frag((gn - NG) & 3, w - 1, gn - NG, 0);                 // V of the next segment, steps 0 / 1
+                constexpr auto N = std::integral_constant<int, w - 1>{};
+                if constexpr (A == 0 && gn < NG) {
+                    if constexpr (gn < 4) read_frag(std::integral_constant<int, gn>{}, N, std::integral_constant<int, gn>{}, std::integral_constant<int, 0>{});  // V(j), 16-key step gn
+                    else read_frag(std::integral_constant<int, gn>{}, N, std::integral_constant<int, gn - 4>{}, std::integral_constant<int, 1>{});             // K(j+1), 16-dim step gn - 4
+                } else if constexpr (A == 1 && !LAST && gn >= NG) {
+                    read_frag(std::integral_constant<int, gn - NG>{}, N, std::integral_constant<int, gn - NG>{}, std::integral_constant<int, 0>{});
                 }
             }
             // (5) LDS-direct loads of the next tile (segment X): one piece every fourth slot (a piece costs the wave 60 - 180
