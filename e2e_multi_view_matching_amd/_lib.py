@@ -180,6 +180,9 @@ SIGNATURES = {
                                        c_void_p]),
     "e2emv_match_loss_tuple": (c_int, [c_void_p, c_int, c_int, c_int, _PP, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "e2emv_match_loss_tuple_backward": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, _PP, c_void_p]),
+    "e2emv_grads_finite": (c_int, [c_void_p, c_int, _PP, ctypes.POINTER(c_int64), c_void_p, c_void_p]),
+    "e2emv_adam_step": (c_int, [c_void_p, c_int, _PP, _PP, _PP, _PP, _PP, ctypes.POINTER(c_int64), ctypes.POINTER(c_float), ctypes.c_double,
+                                ctypes.c_double, ctypes.c_double, c_float, c_int, c_void_p, c_void_p]),
     "e2emv_get_stats": (c_int, [c_void_p, ctypes.POINTER(ctypes.c_uint64), c_int, c_int]),
     "e2emv_set_sinkhorn_kernel": (c_int, [c_void_p, c_int]),
     "e2emv_sinkhorn_plan": (c_int, [c_void_p, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int), c_int]),

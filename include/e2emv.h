@@ -864,6 +864,31 @@ int e2emv_match_loss_tuple(e2emv_ctx* ctx, int P, int B, int N, const float* con
 int e2emv_match_loss_tuple_backward(e2emv_ctx* ctx, int P, int B, int N, const int64_t* d_indices, const float* d_weights,
                                     const float* d_g, float* const* d_glogZ, void* stream);
 
+/* ---- the optimiser step of the training loop (train.py:419-426: has_finite_gradients, clip_grad_value_, Adam.step) -------------
+ * All parameter tensors of a call in at most three launches and one memset, stream-ordered, no host synchronisation.  The tensor
+ * table and chunk list of a call live in a buffer the context keeps for them (not the shared workspace) and are uploaded only
+ * when they differ from the previous call's (such a call waits for the copy of the previous table, long done, to leave the pinned
+ * staging buffer, and a call with a larger table than any before allocates; a call with the same pointers does neither). */
+#define E2EMV_OPTIM_CHUNK 4096   /* elements one workgroup handles at a time; a chunk never crosses a tensor */
+
+/* *d_flag (device int32) = 1 if any element of any of the n tensors is NaN or +-inf, else 0.  Host arrays of n device
+ * pointers / element counts; stream-ordered, no synchronisation.  n == 0: flag = 0.  A tensor with numel == 0 is skipped.
+ * E2EMV_EINVAL: NULL context, array, entry (of a tensor that has elements) or flag; E2EMV_ESHAPE: n < 0, a negative numel, more chunks than an int counts. */
+int e2emv_grads_finite(e2emv_ctx* ctx, int n, const float* const* d_grad, const int64_t* numel, int32_t* d_flag, void* stream);
+
+/* One Adam step (torch.optim.Adam: no weight decay, no amsgrad, not maximising) for n tensors in place.
+ * d_step[i]: device float32 scalar, the number of steps tensor i has taken (torch's capturable layout).
+ * lr[i]: host, per tensor.  clip_value > 0: the gradient is clamped to [-clip_value, clip_value] first (clip_grad_value_); <= 0: no clip.
+ * skip_nonfinite != 0: if any gradient element of the CALL is non-finite, nothing is written - no parameter, moment or step
+ * changes by a bit - and d_counters[1] += 1; otherwise every tensor is updated, d_step[i] += 1, d_counters[0] += 1.
+ * skip_nonfinite == 0: always updated (a NaN gradient reaches its own element, as in torch).  d_counters: device int32 [2] or NULL.
+ * Per element, fp32, with t = step + 1:  g = clamp(g);  m += (g - m)(1 - beta1);  v = beta2 v + (1 - beta2) g^2;
+ * p -= (lr / (1 - beta1^t)) * (m / (sqrt(v) / sqrt(1 - beta2^t) + eps)) - the two bias corrections in fp64 from the device's
+ * step value.  Errors as above, nothing launched. */
+int e2emv_adam_step(e2emv_ctx* ctx, int n, float* const* d_param, const float* const* d_grad, float* const* d_exp_avg,
+                    float* const* d_exp_avg_sq, float* const* d_step, const int64_t* numel, const float* lr,
+                    double beta1, double beta2, double eps, float clip_value, int skip_nonfinite, int32_t* d_counters, void* stream);
+
 /* ---- timing hooks used by bench.py (HIP events on the caller's stream) -------------
  * After e2emv_profile(ctx, 1) every kernel family launched by the library is bracketed by
  * HIP events on its stream; e2emv_profile_read returns accumulated milliseconds and launch
