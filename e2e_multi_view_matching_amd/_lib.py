@@ -157,6 +157,8 @@ SIGNATURES = {
                                          c_void_p]),
     "e2emv_set_f16x2_kernels": (c_int, [c_void_p, c_int]),
     "e2emv_set_attention_key_split": (c_int, [c_void_p, c_int]),
+    "e2emv_set_kenc_fused": (c_int, [c_void_p, c_int]),
+    "e2emv_encode_planes": (c_int, [c_void_p, ctypes.POINTER(ForwardDesc), _PP, _PP, _PP, c_void_p, c_void_p, c_void_p, c_void_p]),
     "e2emv_gemm_p2": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                               c_void_p]),
     "e2emv_qkv_p2": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
@@ -231,7 +233,12 @@ def load_library():
             print(f"[e2emv] E2EMV_LIBRARY is set: loading {LIB_PATH} instead of the product library", file=sys.stderr)
         lib = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in SIGNATURES.items():
-            fn = getattr(lib, name)  # AttributeError if the symbol is not exported
+            try:
+                fn = getattr(lib, name)  # AttributeError if the symbol is not exported
+            except AttributeError:
+                if os.environ.get("E2EMV_LIBRARY"):  # an earlier build (an A/B arm): entry points added since are absent there
+                    continue
+                raise
             fn.restype, fn.argtypes = res, args
         if lib.e2emv_version() != 1:
             raise ImportError("libe2emv.so ABI version mismatch")
@@ -294,6 +301,32 @@ class Context:
         self.call("e2emv_set_attention_key_split", 1 if on else 0)
         self.attention_key_split = bool(on)
 
+    def set_kenc_fused(self, on=True):
+        """f16x2 plane forward: ingest, keypoint encoder and plane conversion in one launch (default on) or as the launch per
+        stage it replaces; the same bits either way.  The E2EMV_KENC=unfused variable only sets the value a context starts with."""
+        self.call("e2emv_set_kenc_fused", 1 if on else 0)
+        self.kenc_fused = bool(on)
+
+    def encode_planes(self, fd, kpts, scores, descs):
+        """What the front of the f16x2 plane forward hands to the GNN for the inputs of a forward call (ForwardDesc and the
+        per-image device tensors e2emv_matcher_forward takes; the committed weights are used): (x as scaled planes
+        [M][512] int16, tile exponents [M / 64][4] int32, block maxima [M / 64][4] float32), M = B * T * (N rounded up to
+        128).  By the path set_kenc_fused selects."""
+        dev = kpts[0].device
+        n_rows = (max(int(k.shape[1]) for k in kpts) + 127) // 128 * 128
+        M = int(fd.batch) * int(fd.tuple_size) * n_rows
+        xp = torch.empty((M, 512), dtype=torch.int16, device=dev)
+        ex = torch.empty((M // 64, 4), dtype=torch.int32, device=dev)
+        ax = torch.empty((M // 64, 4), dtype=torch.float32, device=dev)
+        keep, args = [], []
+        for lst in (kpts, scores, descs):
+            p, arr = ptr_array(lst)
+            keep.append(arr)
+            args.append(p)
+        with torch.cuda.device(dev):
+            self.call("e2emv_encode_planes", ctypes.byref(fd), *args, ptr(xp), ptr(ex), ptr(ax), stream_ptr(dev))
+        return xp, ex, ax
+
     def select_f16x2_kernels(self, generation=None):
         """The generation every model on this device runs from now on (forward() re-selects `default_f16x2_kernels` on each
         call, so `set_f16x2_kernels` alone lasts one call).  None = back to what E2EMV_F16X2_KERNELS chose at creation."""
@@ -305,11 +338,12 @@ class Context:
         non-finite scores, 'sinkhorn_rescued': problems re-solved in the log domain behind the resident kernel (correct
         outputs), 'attention_slow_tiles': (wave, stream, key tile) softmaxes attention_p2w redid on its slow path - a row
         maximum outgrew the running one by more than ~2^9} since the last reset (host-synchronising)."""
-        v = (ctypes.c_uint64 * 6)()
-        self.call("e2emv_get_stats", v, 6, 1 if reset else 0)
+        v = (ctypes.c_uint64 * 7)()
+        self.call("e2emv_get_stats", v, 7, 1 if reset else 0)
         return {"rescaled_blocks": int(v[0]), "sinkhorn_bad": int(v[1]), "sinkhorn_rescued": int(v[2]), "attention_slow_tiles": int(v[3]),
                 "sinkhorn_timeouts": int(v[4]),  # (of the rescued: given up on a wait - contention -, not on range)
-                "sinkhorn_rows128_calls": int(v[5])}  # (Sinkhorn calls on 128-row workgroups: fewer rounds for a large batch)
+                "sinkhorn_rows128_calls": int(v[5]),
+                "kenc_fused_launches": int(v[6])}  # (launches of the fused keypoint-encoder front, kenc_fused.hip)  # (Sinkhorn calls on 128-row workgroups: fewer rounds for a large batch)
 
     SINKHORN_KERNELS = {None: 0, "auto": 0, "rows64": 1, "rows128": 2, "stream": 3, "rows128w": 4}
 
@@ -343,6 +377,8 @@ class Context:
         self.call("e2emv_set_sinkhorn_kernel", getattr(other, "sinkhorn_kernel_pin", 0))
         self.sinkhorn_kernel_pin = getattr(other, "sinkhorn_kernel_pin", 0)
         self.call("e2emv_set_attention_key_split", 1 if getattr(other, "attention_key_split", True) else 0)
+        if hasattr(other, "kenc_fused"):  # (never set: both keep what E2EMV_KENC chose at creation)
+            self.set_kenc_fused(other.kenc_fused)
         want = getattr(other, "split_min_rows", -1)
         if getattr(self, "split_min_rows", -1) != want:
             self.set_split_min_rows(want)

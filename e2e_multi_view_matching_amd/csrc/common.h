@@ -70,6 +70,8 @@ struct e2emv_ctx {
     int64_t split_min_rows = -1;  // split-operand kernels from this many keypoint rows per call (-1: half a 128-row tile per CU)
     int gemm_chain = 1;      // f16x2 kernel generation 5 (default): MLP0 -> MLP1 -> next q|k|v chained in one launch (gemm_p2c.hip); 0 = generation 4 (a launch per GEMM), 2 = chained whenever the shapes allow (e2emv_set_f16x2_kernels(105))
     bool attn_key_split = true;  // attention_p2w: a half-empty last round of workgroups is split along the keys (attention_p2w.hip)
+    bool kenc_fused = true;      // F16X2_PLANES with the {3, 32, 64, 128, 256, 256} encoder: ingest, encoder and plane conversion in one launch (kenc_fused.hip)
+    uint64_t stat_kenc_fused = 0;  // launches of it so far (e2emv_get_stats)
     int attn_p2_nw = 0;      // attention on planes: 0 = by key count, 4 | 8 = attention_p2 with that many waves, 1 = attention_p2w (micro-benchmarks)
     // keypoint encoder: layer 0 (3->c0) used by the ingest kernel, the rest through the GEMM
     const float* kenc_w0 = nullptr;  // [c0][3] folded

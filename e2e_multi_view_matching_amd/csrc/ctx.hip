@@ -131,6 +131,9 @@ int e2emv_create(e2emv_ctx** out, int device) {
         if (strcmp(e, "r4") == 0) ctx->gemm_chain = 0;
     }
 
+    if (const char* e = getenv("E2EMV_KENC")) {  // unfused: the keypoint encoder as a launch per stage (the fused kernel's A/B arm)
+        if (strcmp(e, "unfused") == 0) ctx->kenc_fused = false;
+    }
     if (const char* e = getenv("E2EMV_SINKHORN")) {  // the Sinkhorn kernel pin (e2emv_set_sinkhorn_kernel): read here, once
         ctx->sinkhorn_kernel = strcmp(e, "rows64") == 0 ? E2EMV_SINKHORN_ROWS64 : strcmp(e, "rows128") == 0 ? E2EMV_SINKHORN_ROWS128
                                : strcmp(e, "rows128w") == 0 ? E2EMV_SINKHORN_ROWS128W
@@ -259,14 +262,16 @@ int e2emv_get_stats(e2emv_ctx* ctx, uint64_t* stats, int n, int reset) {
     if (ctx->d_flags) E2EMV_HIP(ctx, hipMemcpy(f, ctx->d_flags, sizeof(f), hipMemcpyDeviceToHost));
     ctx->stat_sinkhorn_bad += f[1];
     if (ctx->d_flags) note_rescues(ctx, f[3], f[6]);
-    const uint64_t v[6] = {(uint64_t)f[2], ctx->stat_sinkhorn_bad, ctx->stat_sinkhorn_rescued, (uint64_t)f[5], ctx->stat_sinkhorn_timeouts, ctx->stat_sinkhorn_rows128};
-    for (int i = 0; i < n; ++i) stats[i] = i < 6 ? v[i] : 0;
+    const uint64_t v[7] = {(uint64_t)f[2], ctx->stat_sinkhorn_bad, ctx->stat_sinkhorn_rescued, (uint64_t)f[5], ctx->stat_sinkhorn_timeouts, ctx->stat_sinkhorn_rows128,
+                           ctx->stat_kenc_fused};
+    for (int i = 0; i < n; ++i) stats[i] = i < 7 ? v[i] : 0;
     if (ctx->d_flags && f[1]) E2EMV_HIP(ctx, hipMemset(ctx->d_flags + 1, 0, sizeof(unsigned)));  // moved into the host-side total
     if (reset) {
         ctx->stat_sinkhorn_bad = 0;
         ctx->stat_sinkhorn_rescued = 0;
         ctx->stat_sinkhorn_timeouts = 0;
         ctx->stat_sinkhorn_rows128 = 0;
+        ctx->stat_kenc_fused = 0;
         ctx->sk_range_strikes = 0;
         ctx->sk_stream_calls = 0;
         ctx->sinkhorn_stream = false;  // (a reset also returns the Sinkhorn to the resident kernel)
@@ -292,6 +297,13 @@ int e2emv_set_attention_key_split(e2emv_ctx* ctx, int on) {
     if (!ctx) return E2EMV_EINVAL;
     E2EMV_LOCK(ctx);
     ctx->attn_key_split = on != 0;
+    return E2EMV_OK;
+}
+
+int e2emv_set_kenc_fused(e2emv_ctx* ctx, int on) {
+    if (!ctx) return E2EMV_EINVAL;
+    E2EMV_LOCK(ctx);
+    ctx->kenc_fused = on != 0;
     return E2EMV_OK;
 }
 

@@ -147,6 +147,7 @@ struct FwdPlan {
     bool uniform, full;       // every image has N keypoints; E2EMV_FLAG_FULL_OUTPUT
     int64_t Mtot;             // rows of an activation buffer
     FwdMode mode;
+    bool kenc_fused;          // F16X2_PLANES: ingest, keypoint encoder and the plane conversion of x in one launch (kenc_fused.hip)
     bool chain;               // F16X2_PLANES: MLP0, MLP1 and the next q | k | v (or final_proj) in one launch (gemm_p2c.hip)
     float *x, *att, *msg, *qkv, *hid, *S;
     char* skws;
@@ -185,6 +186,13 @@ static int plan_forward(e2emv_ctx* ctx, const e2emv_forward_desc* fd, FwdPlan& p
     if (ctx->precision == E2EMV_PRECISION_F32 || Mtot < split_min) p.mode = FwdMode::F32;
     else if (ctx->precision != E2EMV_PRECISION_F16X2) p.mode = FwdMode::BF16X3;
     else p.mode = planes ? FwdMode::F16X2_PLANES : FwdMode::F16X2;
+
+    // the front of the plane path in one launch: the encoder widths that kernel is written for, its wide layers with their fp16 x 2
+    // planes (the forward's ingest never records the training tape's `inp`); every other call runs the launch per stage
+    static const int kFusedDims[6] = {3, 32, 64, 128, 256, 256};
+    const std::vector<int>& kd = ctx->kenc_dims;
+    p.kenc_fused = p.mode == FwdMode::F16X2_PLANES && ctx->kenc_fused && kd.size() == 6 && std::equal(kd.begin(), kd.end(), kFusedDims) &&
+                   ctx->kenc.size() == 4 && ctx->kenc[2].wh && ctx->kenc[3].wh;
 
     // f16x2 kernel generation 5: the row-local GEMMs between two attentions - MLP0, MLP1 of layer l and q | k | v of layer l + 1
     // (final_proj behind the last layer) - chained per 256-row block in ONE launch (gemm_p2c.hip).  A workgroup then walks 6 tiles
@@ -253,6 +261,19 @@ static int gemm_fp32_act(e2emv_ctx* ctx, const FwdPlan& p, const GemmArgs& g, co
     return rc;
 }
 
+// the caller's inputs and layer 0 of the keypoint encoder as the ingest kernels take them
+static IngestParams ingest_params(e2emv_ctx* ctx, const FwdPlan& p, const e2emv_forward_desc* fd, const float* const* d_kpts,
+                                  const float* const* d_kscores, const void* const* d_desc) {
+    IngestParams ip{};
+    for (int t = 0; t < p.T; ++t) {
+        ip.kpts[t] = d_kpts[t]; ip.ksc[t] = d_kscores[t]; ip.desc[t] = d_desc[t];
+        ip.img_w[t] = fd->img_w[t]; ip.img_h[t] = fd->img_h[t]; ip.Nimg[t] = p.Nt[t];
+    }
+    ip.B = p.B; ip.T = p.T; ip.n_rows = p.n_rows; ip.D = p.D; ip.c0 = ctx->kenc_dims[1]; ip.f16 = fd->desc_dtype == E2EMV_DESC_F16;
+    ip.w0 = ctx->kenc_w0; ip.b0 = ctx->kenc_b0;
+    return ip;
+}
+
 // ingest, then keypoint encoder layers 1..n through the GEMM; the last adds the descriptors: x = the GNN's input
 static int encode(e2emv_ctx* ctx, const FwdPlan& p, const e2emv_forward_desc* fd, const float* const* d_kpts,
                   const float* const* d_kscores, const void* const* d_desc, hipStream_t s) {
@@ -261,13 +282,8 @@ static int encode(e2emv_ctx* ctx, const FwdPlan& p, const e2emv_forward_desc* fd
     int64_t tot = 0;
     for (size_t i = 1; i + 1 < kd.size(); ++i) tot += kd[i];
     if (tot > 2 * p.D) return set_err(ctx, E2EMV_ESHAPE, "keypoint_encoder too wide for the workspace plan");
-    IngestParams ip{};
-    for (int t = 0; t < p.T; ++t) {
-        ip.kpts[t] = d_kpts[t]; ip.ksc[t] = d_kscores[t]; ip.desc[t] = d_desc[t];
-        ip.img_w[t] = fd->img_w[t]; ip.img_h[t] = fd->img_h[t]; ip.Nimg[t] = p.Nt[t];
-    }
-    ip.B = p.B; ip.T = p.T; ip.n_rows = p.n_rows; ip.D = p.D; ip.c0 = c0; ip.f16 = fd->desc_dtype == E2EMV_DESC_F16;
-    ip.w0 = ctx->kenc_w0; ip.b0 = ctx->kenc_b0; ip.x0 = p.x; ip.h0 = p.hid;
+    IngestParams ip = ingest_params(ctx, p, fd, d_kpts, d_kscores, d_desc);
+    ip.x0 = p.x; ip.h0 = p.hid;
     prof_begin(ctx, PS_INGEST, s);
     hipLaunchKernelGGL(ingest_transpose, dim3(p.n_rows / 64, p.D / 64, p.B * p.T), dim3(256), 0, s, ip);
     hipLaunchKernelGGL(ingest_kenc0, dim3((p.n_rows + 255) / 256, p.B * p.T), dim3(256), 0, s, ip);
@@ -321,7 +337,32 @@ static int gnn_fp32_activations(e2emv_ctx* ctx, const FwdPlan& p, hipStream_t s)
     return gemm_fp32_act(ctx, p, g, ctx->final_proj, s);
 }
 
-// F16X2_PLANES: x to planes, the GNN layers - a launch per GEMM or chained - and final_proj on planes
+// F16X2_PLANES: x, the GNN's input, as scaled planes with their tile exponents (in p.msg, p.e_x, p.a_x) - layer 0 and then the
+// rest of the front in one launch from the caller's inputs (kenc_fused.hip), or encode() and the conversion of the fp32 x it
+// leaves in p.x.  Bit-identical.
+static int encode_planes(e2emv_ctx* ctx, const FwdPlan& p, const e2emv_forward_desc* fd, const float* const* d_kpts,
+                         const float* const* d_kscores, const void* const* d_desc, hipStream_t s) {
+    if (!p.kenc_fused)
+        if (int rc = encode(ctx, p, fd, d_kpts, d_kscores, d_desc, s)) return rc;
+    uint16_t* xp = (uint16_t*)p.msg;
+    prof_begin(ctx, PS_INGEST, s);
+    // (the attention skips query tiles beyond the keypoints of an image: their exponent entries must not be stale)
+    E2EMV_HIP(ctx, hipMemsetAsync(p.e_x, 0, (size_t)(p.Mtot / 64) * 28 * sizeof(int), s));
+    int rc;
+    if (p.kenc_fused) {
+        IngestParams ip = ingest_params(ctx, p, fd, d_kpts, d_kscores, d_desc);
+        ip.h0 = p.hid;  // layer 0 keeps its launch (kenc_fused.hip says why); the fused kernel takes it from there
+        hipLaunchKernelGGL(ingest_kenc0, dim3((p.n_rows + 255) / 256, p.B * p.T), dim3(256), 0, s, ip);
+        E2EMV_CHECK_LAUNCH(ctx, "ingest_kenc0");
+        rc = launch_kenc_fused(ctx, ip, ctx->kenc.data(), xp, p.e_x, p.a_x, s);
+    } else {
+        rc = launch_to_planes(ctx, p.x, p.Mtot, p.D, p.D, xp, s, p.e_x, p.a_x);
+    }
+    prof_end(ctx, s);
+    return rc;
+}
+
+// F16X2_PLANES: the GNN layers - a launch per GEMM or chained - and final_proj on the planes of x
 static int gnn_planes(e2emv_ctx* ctx, const FwdPlan& p, hipStream_t s) {
     const int D = p.D, H = p.H, M = (int)p.Mtot;
     uint16_t* xp = (uint16_t*)p.msg;       // x as scaled planes (msg is free until the conf head)
@@ -329,12 +370,7 @@ static int gnn_planes(e2emv_ctx* ctx, const FwdPlan& p, hipStream_t s) {
     uint16_t* qkp = (uint16_t*)p.qkv;      // q | k plain planes [Mtot][2D]
     uint16_t* vtp = qkp + p.Mtot * 4 * D;  // V^T plain planes [n_img][H][64][n_rows]
     uint16_t* hidp = (uint16_t*)p.hid;     // hidden as scaled planes [Mtot][2D]
-    prof_begin(ctx, PS_INGEST, s);
-    // (the attention skips query tiles beyond the keypoints of an image: their exponent entries must not be stale)
-    E2EMV_HIP(ctx, hipMemsetAsync(p.e_x, 0, (size_t)(p.Mtot / 64) * 28 * sizeof(int), s));
-    int rc = launch_to_planes(ctx, p.x, p.Mtot, D, D, xp, s, p.e_x, p.a_x);
-    prof_end(ctx, s);
-    if (rc) return rc;
+    int rc;
     auto qkv_args = [&](const LayerWeights& L) {
         GemmP2Args q = dense_gemm_p2(L.qkv, M);
         q.A = xp; q.lda = D; q.out = P2_OUT_QKV; q.Cp = qkp; q.Vt = vtp; q.n_rows = p.n_rows; q.heads = H;
@@ -497,20 +533,22 @@ static int forward_joint(e2emv_ctx* ctx, const e2emv_forward_desc* fd, const flo
                          float* const* d_conf, hipStream_t s) {
     FwdPlan p;
     if (int rc = plan_forward(ctx, fd, p)) return rc;
-    if (int rc = encode(ctx, p, fd, d_kpts, d_kscores, d_desc, s)) return rc;
-    if (int rc = p.mode == FwdMode::F16X2_PLANES ? gnn_planes(ctx, p, s) : gnn_fp32_activations(ctx, p, s)) return rc;
+    if (p.mode == FwdMode::F16X2_PLANES) {
+        if (int rc = encode_planes(ctx, p, fd, d_kpts, d_kscores, d_desc, s)) return rc;
+        if (int rc = gnn_planes(ctx, p, s)) return rc;
+    } else {
+        if (int rc = encode(ctx, p, fd, d_kpts, d_kscores, d_desc, s)) return rc;
+        if (int rc = gnn_fp32_activations(ctx, p, s)) return rc;
+    }
     ctx->last_mdesc = p.att; ctx->md_imgs = p.B * p.T; ctx->md_rows = p.n_rows; ctx->md_n = p.N; ctx->md_dim = p.D;  // (e2emv_get_descriptors)
     SinkhornOut so;
     if (int rc = match_pairs(ctx, p, fd, d_logZ, d_m0, d_m1, d_ms0, d_ms1, d_conf, so, s)) return rc;
     return conf_heads(ctx, p, so, d_conf, s);
 }
 
-extern "C" int e2emv_matcher_forward(e2emv_ctx* ctx, const e2emv_forward_desc* fd, const float* const* d_kpts,
-                                     const float* const* d_kscores, const void* const* d_desc, float* const* d_logZ,
-                                     int64_t* const* d_matches0, int64_t* const* d_matches1, float* const* d_mscores0,
-                                     float* const* d_mscores1, float* const* d_conf, void* stream) {
-    if (!ctx || !fd || !d_kpts || !d_kscores || !d_desc) return E2EMV_EINVAL;
-    E2EMV_ENTER(ctx, stream);
+// the checks of a forward descriptor and its inputs that every entry point below starts with
+static int check_forward_inputs(e2emv_ctx* ctx, const e2emv_forward_desc* fd, const float* const* d_kpts, const float* const* d_kscores,
+                                const void* const* d_desc) {
     if (!ctx->committed) return set_err(ctx, E2EMV_ESTATE, "matcher_forward: weights not committed");
     const int B = fd->batch, T = fd->tuple_size;
     if (B <= 0 || T < 2 || T > E2EMV_MAX_TUPLE) return set_err(ctx, E2EMV_ESHAPE, "matcher_forward: batch=%d tuple_size=%d", B, T);
@@ -522,6 +560,17 @@ extern "C" int e2emv_matcher_forward(e2emv_ctx* ctx, const e2emv_forward_desc* f
     if (fd->sinkhorn_iters < 0) return set_err(ctx, E2EMV_EINVAL, "negative sinkhorn_iters");
     for (int t = 0; t < T; ++t)
         if (!d_kpts[t] || !d_kscores[t] || !d_desc[t]) return set_err(ctx, E2EMV_EINVAL, "matcher_forward: null input for image %d", t);
+    return E2EMV_OK;
+}
+
+extern "C" int e2emv_matcher_forward(e2emv_ctx* ctx, const e2emv_forward_desc* fd, const float* const* d_kpts,
+                                     const float* const* d_kscores, const void* const* d_desc, float* const* d_logZ,
+                                     int64_t* const* d_matches0, int64_t* const* d_matches1, float* const* d_mscores0,
+                                     float* const* d_mscores1, float* const* d_conf, void* stream) {
+    if (!ctx || !fd || !d_kpts || !d_kscores || !d_desc) return E2EMV_EINVAL;
+    E2EMV_ENTER(ctx, stream);
+    if (int rc = check_forward_inputs(ctx, fd, d_kpts, d_kscores, d_desc)) return rc;
+    const int T = fd->tuple_size;
     (void)hipSetDevice(ctx->device);
     hipStream_t s = (hipStream_t)stream;
     if (T == 2 || (fd->flags & E2EMV_FLAG_MULTI_FRAME))
@@ -548,6 +597,26 @@ extern "C" int e2emv_matcher_forward(e2emv_ctx* ctx, const e2emv_forward_desc* f
             int rc = forward_joint(ctx, &f2, kp, ks, de, lz, m0, m1, s0, s1, cf, s);
             if (rc) return rc;
         }
+    return E2EMV_OK;
+}
+
+// What the front of the plane forward hands to the GNN (e2emv.h): the planes of x, their tile exponents and block maxima, by the
+// path e2emv_set_kenc_fused selects - a test compares the two without running a GNN.
+extern "C" int e2emv_encode_planes(e2emv_ctx* ctx, const e2emv_forward_desc* fd, const float* const* d_kpts, const float* const* d_kscores,
+                                   const void* const* d_desc, uint16_t* d_xp, int32_t* d_ex, float* d_ax, void* stream) {
+    if (!ctx || !fd || !d_kpts || !d_kscores || !d_desc || !d_xp || !d_ex || !d_ax) return E2EMV_EINVAL;
+    E2EMV_ENTER(ctx, stream);
+    if (int rc = check_forward_inputs(ctx, fd, d_kpts, d_kscores, d_desc)) return rc;
+    (void)hipSetDevice(ctx->device);
+    hipStream_t s = (hipStream_t)stream;
+    FwdPlan p;
+    if (int rc = plan_forward(ctx, fd, p)) return rc;
+    if (p.mode != FwdMode::F16X2_PLANES) return set_err(ctx, E2EMV_ESTATE, "encode_planes: this call would not run on the plane kernels");
+    if (int rc = encode_planes(ctx, p, fd, d_kpts, d_kscores, d_desc, s)) return rc;
+    const size_t blocks = (size_t)(p.Mtot / 64) * (p.D / 64);
+    E2EMV_HIP(ctx, hipMemcpyAsync(d_xp, p.msg, (size_t)p.Mtot * p.D * 4, hipMemcpyDeviceToDevice, s));
+    E2EMV_HIP(ctx, hipMemcpyAsync(d_ex, p.e_x, blocks * sizeof(int), hipMemcpyDeviceToDevice, s));
+    E2EMV_HIP(ctx, hipMemcpyAsync(d_ax, p.a_x, blocks * sizeof(float), hipMemcpyDeviceToDevice, s));
     return E2EMV_OK;
 }
 

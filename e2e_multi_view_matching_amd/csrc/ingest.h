@@ -23,4 +23,11 @@ __global__ void ingest_transpose(IngestParams p);
 // keypoint normalisation + kenc layer 0 (3 -> c0, BN folded, ReLU); rows >= N := 0
 __global__ void ingest_kenc0(IngestParams p);
 
+// kenc_fused.hip: layers 1..4 of the keypoint encoder {3, 32, 64, 128, 256, 256}, the descriptor residual and the plane conversion
+// of x in ONE launch, bit for bit what ingest_transpose + the four GEMMs + to_planes_exp_kernel make.  in = the inputs as
+// ingest_kenc0 took them: in.h0 [n_img * n_rows][32] holds its output, the descriptors are read from in.desc (x0 / inp unused);
+// kenc = layers 1..4 (fp32 weights for the first two, fp16 x 2 planes `wh` for the wide ones); outputs: x as scaled planes
+// [n_img * n_rows][D], its tile exponents e_x and block maxima a_x [rows / 64][D / 64].
+int launch_kenc_fused(e2emv_ctx* ctx, const IngestParams& in, const DenseWeights* kenc, uint16_t* xp, int* e_x, float* a_x, hipStream_t s);
+
 }  // namespace e2emv

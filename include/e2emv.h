@@ -665,6 +665,18 @@ int e2emv_set_f16x2_kernels(e2emv_ctx* ctx, int generation);
  * reference's shapes: eval_multi_view.py:154-162).  Results differ from the unsplit kernel by the order of the softmax sums only
  * (~1e-7 relative).  on = 0: never (A/B runs, tests). */
 int e2emv_set_attention_key_split(e2emv_ctx* ctx, int on);
+/* The front of the f16x2 plane forward - descriptor transpose, keypoint normalisation, the keypoint encoder and the conversion
+ * of its output to planes - as ONE launch that keeps every intermediate on chip (kenc_fused.hip; on = 1, default) or as the
+ * launch per stage it replaces (on = 0: A/B runs, tests).  The two compute the same bits.  The fused launch serves the plane
+ * kernels with the keypoint encoder {3, 32, 64, 128, 256, 256}; every other call runs the stages whatever the switch says.
+ * Also E2EMV_KENC=unfused at e2emv_create (other values are ignored). */
+int e2emv_set_kenc_fused(e2emv_ctx* ctx, int on);
+/* What that front hands to the GNN, for a call e2emv_matcher_forward would run on the plane kernels (else E2EMV_ESTATE): with
+ * n_rows = N rounded up to 128 and M = B * T * n_rows, d_xp [M][2 * 256] halves = x as scaled planes (p2.h), d_ex [M / 64][4]
+ * int32 = the tile exponents, d_ax [M / 64][4] f32 = the blocks' max |x|.  Honours e2emv_set_kenc_fused: a test compares the
+ * two paths with it, without running a GNN.  Inputs as for e2emv_matcher_forward. */
+int e2emv_encode_planes(e2emv_ctx* ctx, const e2emv_forward_desc* fd, const float* const* d_kpts, const float* const* d_kscores,
+                        const void* const* d_desc, uint16_t* d_xp, int32_t* d_ex, float* d_ax, void* stream);
 /* building blocks on fp32 buffers (conversion to / from planes done by helper kernels; for tests and micro-benchmarks):
  * C = act([A | A2] W^T + bias) (+ R); A [M,K1], A2 [M,K-K1] or NULL, W [N,K], R [M,N] or NULL.  flags: bit0 relu, bit1 the
  * kernel writes planes (converted back to fp32 afterwards) instead of fp32, bit2 = with the tile exponents of the range
@@ -704,7 +716,8 @@ int e2emv_get_descriptors(e2emv_ctx* ctx, float* d_out, int64_t capacity_floats,
  * in e2emv_sync) of calls with range rescues moves the context to the log-domain launch chain - after 16 calls on it the
  * resident kernel gets another try -, rescues behind a timeout (stats[4] counts those) never do; stats[5] = Sinkhorn calls served by the 128-rows-per-workgroup
  * kernel (a batch of 513 .. 1024-column problems that it brings through in fewer rounds); stats[3] = (wave, stream, 64-key tile) softmaxes that
- * attention_p2w redid on its slow path (a performance counter: results are the same).  Host-synchronising. */
+ * attention_p2w redid on its slow path (a performance counter: results are the same); stats[6] = launches of the fused
+ * keypoint-encoder front (e2emv_set_kenc_fused).  Host-synchronising. */
 int e2emv_get_stats(e2emv_ctx* ctx, uint64_t* stats, int n, int reset);
 
 /* ---- which Sinkhorn kernel serves a call (upstream log_optimal_transport: models/superglue.py:156-186; reference call sites
