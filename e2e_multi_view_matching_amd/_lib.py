@@ -48,6 +48,14 @@ class SuperPointDesc(ctypes.Structure):
                 ("valid_width", ctypes.c_int32)]
 
 
+class ImageFrontDesc(ctypes.Structure):
+    _fields_ = [("batch", ctypes.c_int32), ("in_height", ctypes.c_int32), ("in_width", ctypes.c_int32), ("win_top", ctypes.c_int32),
+                ("win_left", ctypes.c_int32), ("win_height", ctypes.c_int32), ("win_width", ctypes.c_int32), ("out_height", ctypes.c_int32),
+                ("out_width", ctypes.c_int32), ("antialias", ctypes.c_int32)]
+
+
+IMAGE_FRONT_TILE, IMAGE_FRONT_TILE_ROWS, IMAGE_FRONT_STRIP = 64, 16, 384
+
 # every symbol include/e2emv.h declares: name -> (restype, argtypes)
 _PP = ctypes.POINTER(c_void_p)
 SIGNATURES = {
@@ -185,6 +193,8 @@ SIGNATURES = {
     "e2emv_grads_finite": (c_int, [c_void_p, c_int, _PP, ctypes.POINTER(c_int64), c_void_p, c_void_p]),
     "e2emv_adam_step": (c_int, [c_void_p, c_int, _PP, _PP, _PP, _PP, _PP, ctypes.POINTER(c_int64), ctypes.POINTER(c_float), ctypes.c_double,
                                 ctypes.c_double, ctypes.c_double, c_float, c_int, c_void_p, c_void_p]),
+    "e2emv_image_front": (c_int, [c_void_p, ctypes.POINTER(ImageFrontDesc), c_void_p, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(c_float),
+                                  c_void_p, c_void_p, c_void_p]),
     "e2emv_get_stats": (c_int, [c_void_p, ctypes.POINTER(ctypes.c_uint64), c_int, c_int]),
     "e2emv_set_sinkhorn_kernel": (c_int, [c_void_p, c_int]),
     "e2emv_sinkhorn_plan": (c_int, [c_void_p, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int), c_int]),

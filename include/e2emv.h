@@ -902,6 +902,44 @@ int e2emv_adam_step(e2emv_ctx* ctx, int n, float* const* d_param, const float* c
                     float* const* d_exp_avg_sq, float* const* d_step, const int64_t* numel, const float* lr,
                     double beta1, double beta2, double eps, float clip_value, int skip_nonfinite, int32_t* d_counters, void* stream);
 
+/* ---- the image front of a tuple (MatchingDataset.__getitem__, datasets/matching_dataset.py:182-211) -------------
+ * ToTensor (u8 / 255, a true fp32 division), ONE source window, the bilinear resize, ColorJitter with one parameter row per
+ * image and rgb_to_grayscale: d_rgb uint8 [B][in_height][in_width][3] (interleaved, what a JPEG decoder hands out) ->
+ * d_gray float32 [B][1][out_height][out_width], the tensor e2emv_superpoint_forward takes.
+ * Window: the rectangle (win_top, win_left, win_height, win_width) in source coordinates; it may reach outside the image, where
+ * it reads zeros - the 2-row padding of the large ScanNet frames is win_top = -2, win_height = in_height + 4, the square crop
+ * of MegaDepth a window inside the image.  The window is resized to the output size with the semantics of
+ * torch.nn.functional.interpolate(mode="bilinear", align_corners=False, antialias=antialias) (tap tables in fp64 on the host,
+ * once per shape); a window of the output's size is copied, no arithmetic touches the values.
+ * LIMIT: the source columns that E2EMV_IMAGE_FRONT_TILE neighbouring output columns need (about 64 * scale + 2 * scale + 1 with
+ * antialias, 64 * scale + 2 without) must not exceed E2EMV_IMAGE_FRONT_STRIP - a horizontal down-scale up to about 5.8;
+ * E2EMV_ESHAPE beyond it.  The vertical scale is not limited.
+ * Jitter: order / factors are HOST arrays [B][4] (both or neither; NULL = no jitter): order[b][slot] names the op of the slot
+ * (0 brightness, 1 contrast, 2 saturation, 3 hue, -1 = the slot is skipped), factors[b] = (brightness, contrast, saturation,
+ * hue).  The ops are torchvision's tensor forms on values in [0, 1]; the contrast blend takes the mean gray value of the whole
+ * image as it stands at that slot (a fixed-order two-stage sum: the same call gives the same bytes every time).
+ * d_rgb_out: optional [B][3][out_height][out_width], the jittered colour image the gray value is taken of (audits); may be NULL.
+ * Launches: one when no image of the call has a contrast slot, else three (the resample with the partial sums, the means,
+ * the jitter); stream-ordered, no host synchronisation; tap tables, the workspaces of a call with a contrast slot (one partial
+ * sum per tile and the resized colour image as fp32, 12 bytes per output pixel of the call; E2EMV_ENOMEM if they cannot be
+ * reserved) and the parameter rows live in the context - nothing is allocated after the first call of a shape.  The
+ * parameter rows (48 bytes per image) are copied from a pinned ring of the context.
+ * E2EMV_EINVAL, with a message and nothing launched: a NULL context, descriptor, d_rgb or d_gray; order without factors or the
+ * reverse; a non-positive size; an empty window; antialias other than 0 | 1; an order entry outside -1..3 or an op named twice;
+ * a factor that is not finite; a negative brightness, contrast or saturation factor; a hue factor outside [-0.5, 0.5]. */
+#define E2EMV_IMAGE_FRONT_TILE 64    /* output columns of a tile (its rows: 16) */
+#define E2EMV_IMAGE_FRONT_STRIP 384  /* source columns a tile may span */
+typedef struct {
+    int32_t batch;                  /* B                                              */
+    int32_t in_height, in_width;    /* Hin, Win                                       */
+    int32_t win_top, win_left;      /* the window's first row / column, may be < 0    */
+    int32_t win_height, win_width;  /* > 0; may reach beyond the image                */
+    int32_t out_height, out_width;  /* Hout, Wout                                     */
+    int32_t antialias;              /* 0 | 1                                          */
+} e2emv_image_front_desc;
+int e2emv_image_front(e2emv_ctx* ctx, const e2emv_image_front_desc* desc, const uint8_t* d_rgb, const int32_t* order,
+                      const float* factors, float* d_gray, float* d_rgb_out, void* stream);
+
 /* ---- timing hooks used by bench.py (HIP events on the caller's stream) -------------
  * After e2emv_profile(ctx, 1) every kernel family launched by the library is bracketed by
  * HIP events on its stream; e2emv_profile_read returns accumulated milliseconds and launch
