@@ -4,11 +4,13 @@ Python surface (mirrors the reference's callables):
   MultiViewMatcher / SuperGlue, estimate_relative_pose_w8pt, run_weighted_8_point, get_kpts,
   normalize, compute_rotation_error, compute_translation_error_as_angle, pose_auc,
   estimate_pose / estimate_poses_ransac (the RANSAC baseline), Adam / has_finite_gradients (the optimiser step of train.py),
-  prepare_images / color_jitter_params / window_intrinsics (the image stage of MatchingDataset.__getitem__).
+  prepare_images / color_jitter_params / window_intrinsics (the image stage of MatchingDataset.__getitem__),
+  prepare_pair_images / pair_out_size / pair_intrinsics (the image stage of PairMatchingDataset.__getitem__, eval_pairs.py).
 Everything computes in libe2emv.so (hand-written HIP for gfx950) through ctypes.
 """
 from .matcher import MultiViewMatcher, SuperGlue, last_descriptors  # noqa: F401
-from .images import color_jitter_params, prepare_images, window_intrinsics  # noqa: F401
+from .images import (color_jitter_params, pair_intrinsics, pair_out_size, prepare_images, prepare_pair_images,  # noqa: F401
+                     window_intrinsics)
 from .metrics import compute_pose_error, pose_auc  # noqa: F401
 from .ops import (attention, attention_bf16x3, attention_p2, extract_matches, gemm_bf16x3, gemm_nt, gemm_p2,  # noqa: F401
                   log_optimal_transport, qkv_p2)
@@ -27,4 +29,4 @@ __all__ = ["SuperPoint", "compute_gt_matches_of_image_pair", "compute_match_loss
            "run_bundle_adjust_2_view", "normalize", "compute_rotation_error", "compute_translation_error_as_angle", "pose_errors", "pose_auc",
            "compute_pose_error", "log_optimal_transport", "extract_matches", "gemm_nt", "attention", "estimate_pose",
            "estimate_poses_ransac", "Adam", "has_finite_gradients", "prepare_images", "color_jitter_params",
-           "window_intrinsics"]
+           "window_intrinsics", "prepare_pair_images", "pair_out_size", "pair_intrinsics"]

@@ -56,6 +56,13 @@ class ImageFrontDesc(ctypes.Structure):
 
 IMAGE_FRONT_TILE, IMAGE_FRONT_TILE_ROWS, IMAGE_FRONT_STRIP = 64, 16, 384
 
+
+class GrayImage(ctypes.Structure):  # e2emv_gray_image
+    _fields_ = [("data", ctypes.c_void_p), ("height", ctypes.c_int32), ("width", ctypes.c_int32), ("rot", ctypes.c_int32)]
+
+
+IMAGE_FRONT_GRAY_TILE_ROWS, IMAGE_FRONT_GRAY_TILE_COLS, IMAGE_FRONT_GRAY_MAX_IMAGES = 32, 32, 256
+
 # every symbol include/e2emv.h declares: name -> (restype, argtypes)
 _PP = ctypes.POINTER(c_void_p)
 SIGNATURES = {
@@ -195,6 +202,8 @@ SIGNATURES = {
                                 ctypes.c_double, ctypes.c_double, c_float, c_int, c_void_p, c_void_p]),
     "e2emv_image_front": (c_int, [c_void_p, ctypes.POINTER(ImageFrontDesc), c_void_p, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(c_float),
                                   c_void_p, c_void_p, c_void_p]),
+    "e2emv_image_front_gray_size": (c_int, [c_int, c_int, c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+    "e2emv_image_front_gray": (c_int, [c_void_p, c_int, ctypes.POINTER(GrayImage), c_int, c_void_p, c_void_p]),
     "e2emv_get_stats": (c_int, [c_void_p, ctypes.POINTER(ctypes.c_uint64), c_int, c_int]),
     "e2emv_set_sinkhorn_kernel": (c_int, [c_void_p, c_int]),
     "e2emv_sinkhorn_plan": (c_int, [c_void_p, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int), c_int]),

@@ -115,6 +115,7 @@ struct e2emv_ctx {
     float train_bn_momentum = 0.1f;
     void* optim = nullptr;  // e2emv::OptimState (optim.hip): the tensor table / chunk list of the optimiser calls and their flag word
     void* image_front = nullptr;  // e2emv::ImageFrontState (image_front.hip): tap tables per call shape, partial sums, parameter rows
+    void* image_front_gray = nullptr;  // e2emv::GrayFrontState (image_front_pairs.hip): the image table of a call and its pinned ring
     // matched descriptors (final_proj output) of the last forward_joint call, in the workspace: [md_imgs][md_rows][md_dim] fp32
     const float* last_mdesc = nullptr;
     int md_imgs = 0, md_rows = 0, md_n = 0, md_dim = 0;
@@ -178,6 +179,7 @@ int ws_reserve(e2emv_ctx* ctx, size_t bytes);
 void train_free(e2emv_ctx* ctx);  // train.hip
 void optim_free(e2emv_ctx* ctx);  // optim.hip
 void image_front_free(e2emv_ctx* ctx);  // image_front.hip
+void image_front_gray_free(e2emv_ctx* ctx);  // image_front_pairs.hip
 // ctx->d_flags (device words: [0] Sinkhorn give-up flag, [1] its sticky count, [2] plane blocks that needed a tile exponent,
 // [3] Sinkhorn problems rescued after a range event, [6] after a timeout, [4] give-ups of the resident kernel's waits,
 // [5] (wave, tile) softmaxes attention_p2w redid on its slow path)

@@ -160,6 +160,7 @@ void e2emv_destroy(e2emv_ctx* ctx) {
     e2emv::train_free(ctx);
     e2emv::optim_free(ctx);
     e2emv::image_front_free(ctx);
+    e2emv::image_front_gray_free(ctx);
     if (ctx->d_ws) (void)hipFree(ctx->d_ws);
     if (ctx->d_warena) (void)hipFree(ctx->d_warena);
     if (ctx->d_w3arena) (void)hipFree(ctx->d_w3arena);

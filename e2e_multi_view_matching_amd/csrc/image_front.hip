@@ -35,6 +35,7 @@
 #include <memory>
 
 #include "common.h"
+#include "u8_over_255.h"
 
 namespace e2emv {
 
@@ -150,14 +151,7 @@ __device__ __forceinline__ bool has_contrast(const ImgParam& P) {
     return P.order[0] == 1 || P.order[1] == 1 || P.order[2] == 1 || P.order[3] == 1;
 }
 
-// ToTensor's u8 / 255 - a true fp32 division (x * (1 / 255) alone differs on 126 of the 256 values): the product and one fused
-// correction step give the correctly rounded quotient for every byte (checked against the division for all 256 on the host,
-// and by the byte test on the device)
-__device__ __forceinline__ float u8_over_255(unsigned byte) {
-    const float x = float(byte), rcp = 1.0f / 255.0f;
-    const float q = __fmul_rn(x, rcp);
-    return fmaf(fmaf(-q, 255.0f, x), rcp, q);
-}
+// (ToTensor's u8 / 255 with the bytes of the true fp32 division: u8_over_255 of u8_over_255.h, shared with image_front_pairs.hip)
 
 typedef unsigned int u4 __attribute__((ext_vector_type(4)));
 typedef float f4 __attribute__((ext_vector_type(4)));

@@ -7,6 +7,14 @@ source window), ``resize`` to the depth map's size, ``ColorJitter`` with one par
 * ``color_jitter_params`` - the draw of ``get_color_jitter_params`` (``matching_dataset.py:125-130``, ``167-169``): one per tuple.
 * ``window_intrinsics``   - the change of the intrinsics that goes with a window and an output size.
 
+And the image stage of its pair loader (``PairMatchingDataset.__getitem__``, ``eval_pairs.py:85-108``): ``np.rot90``, ``cv2.resize``
+to ``img_size``, ``/ 255.`` for a list of decoded gray frames of any sizes, one launch.
+
+* ``prepare_pair_images`` - list of uint8 gray ``[H,W]`` on the device, one turn each -> float32 ``[1,1,h_out,w_out]`` each
+  (``e2emv_image_front_gray``, csrc/image_front_pairs.hip).
+* ``pair_out_size``       - the output size of ``eval_pairs.py:96-102``, in its own arithmetic.
+* ``pair_intrinsics``     - ``rotate_intrinsics`` + ``resize_intrinsics`` as ``eval_pairs.py:91-104`` applies them.
+
 No torch op computes anything on the images; no CPU fallback.
 """
 import ctypes
@@ -160,3 +168,121 @@ def window_intrinsics(K, window, out_size):
     K[..., 0, 2] *= fact_x
     K[..., 1, 2] *= fact_y
     return K
+
+
+# ---------------------------------------------------------------- pair evaluation (PairMatchingDataset.__getitem__, eval_pairs.py:85-108)
+def _rot(rot):
+    if isinstance(rot, bool) or not isinstance(rot, (int, np.integer)):
+        raise ValueError(f"a turn is an int in 0..3 (quarter turns counter-clockwise, np.rot90's k), got {rot!r}")
+    if not 0 <= rot <= 3:
+        raise ValueError(f"a turn is 0..3 quarter turns, got {rot}")
+    return int(rot)
+
+
+def pair_out_size(shape, rot, img_size):
+    """``(h_out, w_out)`` of a frame of ``shape`` = (H, W) as decoded, turned by ``rot`` quarter turns and resized to ``img_size``:
+    ``eval_pairs.py:96-102`` in its own arithmetic.  The turned image ``h x w`` keeps its size when ``img_size == max(h, w)``;
+    otherwise ``h >= w`` gives ``(img_size, int((w / h) * img_size))`` and ``h < w`` gives ``(int((h / w) * img_size), img_size)`` -
+    Python's doubles and truncation, not an integer division: 10 x 7 at 720 is 503 columns."""
+    H, W = int(shape[0]), int(shape[1])
+    img_size = int(img_size)
+    if H <= 0 or W <= 0 or img_size <= 0:
+        raise ValueError(f"pair_out_size: shape {tuple(shape)!r} and img_size {img_size} must be positive")
+    h, w = (W, H) if _rot(rot) % 2 else (H, W)
+    if img_size == max(h, w):
+        return h, w
+    if h >= w:
+        ar = w / h
+        return img_size, int(ar * img_size)
+    ar = h / w
+    return int(ar * img_size), img_size
+
+
+def pair_intrinsics(K, shape, rot, img_size):
+    """The 3 x 3 intrinsics of the image ``prepare_pair_images`` makes of a frame of ``shape`` = (H, W) as decoded
+    (``eval_pairs.py:91-104``): for ``rot != 0`` ``rotate_intrinsics(K, turned_shape, rot)`` of ``metrics.py``, then
+    ``resize_intrinsics(K, w_out / w, h_out / h)``.  ``K``: array or tensor; a new one is returned, the input is left as it is."""
+    from .metrics import rotate_intrinsics
+    tensor = torch.is_tensor(K)
+    Kn = K.detach().cpu().numpy().copy() if tensor else np.array(K, copy=True)
+    if tuple(Kn.shape) != (3, 3):
+        raise ValueError(f"K must be [3,3], got {tuple(Kn.shape)}")
+    H, W = int(shape[0]), int(shape[1])
+    rot = _rot(rot)
+    h, w = (W, H) if rot % 2 else (H, W)
+    h_out, w_out = pair_out_size((H, W), rot, img_size)
+    if rot != 0:
+        Kn = rotate_intrinsics(Kn, (h, w), rot)
+    if (h_out, w_out) != (h, w):
+        fact_x, fact_y = w_out / w, h_out / h
+        Kn[0, 0] *= fact_x
+        Kn[1, 1] *= fact_y
+        Kn[0, 2] *= fact_x
+        Kn[1, 2] *= fact_y
+    return torch.from_numpy(Kn).to(device=K.device, dtype=K.dtype) if tensor else Kn
+
+
+def prepare_pair_images(frames, img_size, rots=None, merge=False):
+    """The image stage of pair evaluation (``eval_pairs.py:89-106``) for a list of decoded gray frames, as one launch:
+    ``np.rot90(img, k=rot)``, ``cv2.resize`` to ``pair_out_size`` (``INTER_LINEAR`` on the float32 image) and ``/ 255.``.
+
+    ``frames``   list of uint8 ``[H,W]`` tensors on the device (``cv2.imread(.., IMREAD_GRAYSCALE)``), of any sizes; a
+                 non-contiguous one is made contiguous.
+    ``img_size`` the longer side of every output (``eval_pairs.py``'s ``--img_size``: 720 for ScanNet, 1600 for MegaDepth / YFCC).
+    ``rots``     one int per frame, 0..3 quarter turns counter-clockwise (the ``rots`` of the YFCC pair list); default all 0.
+    ``merge``    ``False``: a list of contiguous float32 ``[1,1,h_out,w_out]`` tensors, views of one allocation in list order.
+                 ``True``: one ``[n,1,h_out,w_out]`` tensor, ``ValueError`` when the output sizes differ - ``run_super_point``'s
+                 ``merge`` flag (``eval_pairs.py:131-146``): ScanNet pairs merge, MegaDepth and YFCC pairs do not.
+
+    A frame that already has ``img_size`` as its longer side is not resized: ``uint8 / 255`` with the bytes of the fp32 division.
+    No torch op computes anything on the images, no host synchronisation, no CPU fallback; the same call gives the same bytes."""
+    if not isinstance(frames, (list, tuple)):
+        raise TypeError(f"prepare_pair_images takes a list of tensors, got {type(frames).__name__}")
+    if len(frames) == 0:
+        raise ValueError("prepare_pair_images: an empty list")
+    for f in frames:
+        if not torch.is_tensor(f):
+            raise TypeError(f"prepare_pair_images takes tensors, got {type(f).__name__}")
+        if f.dtype != torch.uint8:
+            raise TypeError(f"prepare_pair_images takes uint8 frames (the decoder's output), got {f.dtype}")
+    for f in frames:
+        if f.dim() != 2 or f.shape[0] <= 0 or f.shape[1] <= 0:
+            raise ValueError(f"prepare_pair_images takes gray frames [H,W], got {tuple(f.shape)}")
+    n = len(frames)
+    if n > _lib.IMAGE_FRONT_GRAY_MAX_IMAGES:
+        raise ValueError(f"prepare_pair_images: {n} frames, a call takes up to {_lib.IMAGE_FRONT_GRAY_MAX_IMAGES}")
+    if rots is None:
+        rots = [0] * n
+    if len(rots) != n:
+        raise ValueError(f"prepare_pair_images: {n} frames and {len(rots)} turns")
+    rots = [_rot(r) for r in rots]
+    img_size = int(img_size)
+    if img_size <= 0:
+        raise ValueError(f"img_size must be positive, got {img_size}")
+    sizes = [pair_out_size(f.shape, r, img_size) for f, r in zip(frames, rots)]
+    for (h, w), f, r in zip(sizes, frames, rots):
+        if h <= 0 or w <= 0:
+            raise ValueError(f"a frame of {tuple(f.shape)} turned by {r} has an output side of 0 at img_size {img_size}")
+    if merge and any(s != sizes[0] for s in sizes):
+        raise ValueError(f"merge=True needs one output size, got {sorted(set(sizes))}")
+    if not all(f.is_cuda for f in frames):
+        raise RuntimeError("prepare_pair_images needs its frames on an MI355X (no CPU fallback)")
+    dev = frames[0].device
+    if any(f.device != dev for f in frames):
+        raise RuntimeError("prepare_pair_images: the frames of a call are on one device")
+    frames = [f.contiguous() for f in frames]
+    numel = [h * w for h, w in sizes]
+    out = torch.empty(sum(numel), dtype=torch.float32, device=dev)
+    recs = (_lib.GrayImage * n)()
+    for rec, f, r in zip(recs, frames, rots):
+        rec.data, rec.height, rec.width, rec.rot = f.data_ptr(), int(f.shape[0]), int(f.shape[1]), r
+    ctx = _lib.context(dev)
+    with torch.cuda.device(dev):
+        ctx.call("e2emv_image_front_gray", n, recs, img_size, _lib.ptr(out), _lib.stream_ptr(dev))
+    if merge:
+        return out.view(n, 1, sizes[0][0], sizes[0][1])
+    views, at = [], 0
+    for (h, w), k in zip(sizes, numel):
+        views.append(out[at:at + k].view(1, 1, h, w))
+        at += k
+    return views

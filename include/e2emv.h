@@ -940,6 +940,43 @@ typedef struct {
 int e2emv_image_front(e2emv_ctx* ctx, const e2emv_image_front_desc* desc, const uint8_t* d_rgb, const int32_t* order,
                       const float* factors, float* d_gray, float* d_rgb_out, void* stream);
 
+/* ---- the image front of pair evaluation (PairMatchingDataset.__getitem__, eval_pairs.py:85-108) -------------
+ * Per image: the decoded gray frame, uint8 [height][width] on the device (cv2.imread(.., IMREAD_GRAYSCALE)), is turned by
+ * `rot` quarter turns counter-clockwise (np.rot90(img, k=rot); the turned image is never made, the turn is part of the source
+ * addressing), resized so that its longer side is img_size (e2emv_image_front_gray_size; no resize when it already is) and
+ * divided by 255: float32 [h_out][w_out], what e2emv_superpoint_forward takes.  images: a HOST array of n records; d_out: ONE
+ * device buffer in which image i's h_out_i * w_out_i floats follow image i - 1's.  The images of a call may all differ in
+ * size and turn.
+ * Resize: cv2.resize's INTER_LINEAR on a float32 image - two taps per axis, half-pixel centres, no antialiasing; per axis, with
+ * scale = 1.0 / (double(n_out) / double(n_in)), output index d reads f = float32((d + 0.5) * scale - 0.5) (the product and the
+ * difference in double, one rounding to float32), s = floor(f), f -= s; s < 0: s = 0, f = 0; s >= n_in - 1: s = n_in - 1, f = 0;
+ * weights (float32(1) - f, f) on the pixels s and min(s + 1, n_in - 1); the horizontal taps first, on the values 0..255, then
+ * the vertical ones, then the fp32 division by 255.  The tap positions are computed in the kernel, in exactly this arithmetic.
+ * An image that is not resized is u8 / 255 with the bytes of the true fp32 division.
+ * One launch per call whatever n and the sizes are; stream-ordered, no host synchronisation; no atomics: the same call gives
+ * the same bytes.  The table of the call (64 bytes per image) is copied from a pinned ring of the context; everything the call
+ * needs is reserved by the first call of a context.
+ * LIMITS (E2EMV_ESHAPE with a message, nothing launched): a side of a frame, or img_size, above 16384; an image whose tiles need
+ * more of the source than the 24 KB a workgroup stages: a tile of E2EMV_IMAGE_FRONT_GRAY_TILE_ROWS x _TILE_COLS output pixels
+ * keeps at most 64 source lines of (32 * scale + 2) bytes (+ up to 30 of alignment) - a reduction up to about 10 on either
+ * axis, 8 guaranteed; enlargements are not limited.
+ * E2EMV_EINVAL, with a message and nothing launched: a NULL context, images, d_out or frame pointer; n <= 0 or n above
+ * E2EMV_IMAGE_FRONT_GRAY_MAX_IMAGES; a non-positive height, width or img_size; rot outside 0..3; an output side that truncates to 0.
+ * e2emv_image_front_gray_size: host only - the output size of a stored height x width frame turned by rot, in the reference's
+ * own arithmetic (eval_pairs.py:96-102): the turned image h x w is kept when img_size == max(h, w); else, h >= w:
+ * (img_size, int((w / h) * img_size)), otherwise (int((h / w) * img_size), img_size) - Python's doubles and truncation, not an
+ * integer division (10 x 7 at 720: 503 columns).  E2EMV_EINVAL for the arguments named above. */
+#define E2EMV_IMAGE_FRONT_GRAY_TILE_ROWS 32    /* output rows of a tile */
+#define E2EMV_IMAGE_FRONT_GRAY_TILE_COLS 32    /* output columns of a tile */
+#define E2EMV_IMAGE_FRONT_GRAY_MAX_IMAGES 256  /* images of one call */
+typedef struct {
+    const uint8_t* data;    /* device, [height][width], rows contiguous, any alignment */
+    int32_t height, width;  /* as stored (before the turn)                             */
+    int32_t rot;            /* 0..3 quarter turns counter-clockwise                    */
+} e2emv_gray_image;
+int e2emv_image_front_gray_size(int height, int width, int rot, int img_size, int* h_out, int* w_out);
+int e2emv_image_front_gray(e2emv_ctx* ctx, int n, const e2emv_gray_image* images, int img_size, float* d_out, void* stream);
+
 /* ---- timing hooks used by bench.py (HIP events on the caller's stream) -------------
  * After e2emv_profile(ctx, 1) every kernel family launched by the library is bracketed by
  * HIP events on its stream; e2emv_profile_read returns accumulated milliseconds and launch
