@@ -157,6 +157,8 @@ SIGNATURES = {
                                          c_void_p, c_void_p]),
     "e2emv_superpoint_detect": (c_int, [c_void_p, ctypes.POINTER(SuperPointDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                         c_void_p, c_void_p, c_void_p]),
+    "e2emv_superpoint_encode": (c_int, [c_void_p, ctypes.POINTER(SuperPointDesc), c_void_p, c_void_p, c_void_p, _PP, c_void_p]),
+    "e2emv_conv3x3_nhwc": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "e2emv_gemm_nt": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int64, c_int64, c_void_p, c_int64,
                               c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64,
                               c_int64, c_float, c_int, c_void_p]),

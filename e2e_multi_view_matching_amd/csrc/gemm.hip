@@ -322,6 +322,9 @@ int launch_gemm_nt(e2emv_ctx* ctx, const GemmArgs& a, hipStream_t s) {
     p.vec_store = (a.N % 4 == 0) && (a.ldc % 4 == 0) && ((uintptr_t)a.C % 16 == 0) && (a.sC % 4 == 0) &&
                   (!a.bias || (uintptr_t)a.bias % 16 == 0) &&
                   (!a.R || ((a.ldr % 4 == 0) && ((uintptr_t)a.R % 16 == 0) && (a.sR % 4 == 0)));
+    // the pool lives in the 16-byte epilogue only: the scalar epilogue would write all M unpooled rows into an M/4-row output
+    if (a.conv_pool && !p.vec_store)
+        return set_err(ctx, E2EMV_ESHAPE, "gemm: fused 2x2 max-pool needs 16-byte aligned output and bias and ldc %% 4 == 0");
     const int per_xcd = (p.total + 7) / 8;
     // K tile: 32.  A 64-deep tile (half the barrier / staging episodes per MFMA, 2 workgroups per CU) was measured
     // 1-5 % SLOWER at every shape; so were 1 or 2 workgroups per CU and s_setprio around the MFMA block: the main

@@ -385,20 +385,30 @@ extern "C" int e2emv_superpoint_commit(e2emv_ctx* ctx) {
 
 namespace {
 
-int sp_conv3x3(e2emv_ctx* ctx, int layer, const float* in, float* out, int imgs, int H, int W, hipStream_t s, bool pool = false) {
+// The CONV mode of launch_gemm_nt (gemm.hip), the one statement of its argument fill: a 3x3 / pad 1 / stride 1 convolution of
+// NHWC input [imgs,H,W,Cin] with weights [Cout][9*Cin] ordered (ky, kx, cin); pool: the 2x2 max-pool fused into the epilogue
+// (output [imgs,H/2,W/2,Cout]).  The launcher's shape checks are the argument checks.
+int conv3x3_nhwc(e2emv_ctx* ctx, const float* in, const float* w, const float* bias, float* out, int imgs, int H, int W, int Cin, int Cout, bool relu,
+                 bool pool, hipStream_t s) {
+    if (imgs <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || (int64_t)imgs * H * W >= (int64_t(1) << 31) || (int64_t)Cin * 9 >= (int64_t(1) << 31))
+        return set_err(ctx, E2EMV_ESHAPE, "conv3x3: %d images of %dx%d, %d -> %d channels (imgs*H*W < 2^31)", imgs, H, W, Cin, Cout);
     GemmArgs g;
-    g.M = imgs * H * W; g.N = kSpCout[layer]; g.K = 9 * kSpCin[layer];
-    g.A = in; g.lda = kSpCin[layer];
-    g.W = ctx->sp_w[layer]; g.ldw = g.K;
-    g.bias = ctx->sp_b[layer];
+    g.M = imgs * H * W; g.N = Cout; g.K = 9 * Cin;
+    g.A = in; g.lda = Cin;
+    g.W = w; g.ldw = g.K;
+    g.bias = bias;
     g.C = out; g.ldc = g.N;
-    g.relu = true;
-    g.conv_h = H; g.conv_w = W; g.conv_c = kSpCin[layer];
+    g.relu = relu;
+    g.conv_h = H; g.conv_w = W; g.conv_c = Cin;
     g.conv_pool = pool;
     prof_begin(ctx, PS_GEMM, s);
     const int rc = launch_gemm_nt(ctx, g, s);
     prof_end(ctx, s);
     return rc;
+}
+
+int sp_conv3x3(e2emv_ctx* ctx, int layer, const float* in, float* out, int imgs, int H, int W, hipStream_t s, bool pool = false) {
+    return conv3x3_nhwc(ctx, in, ctx->sp_w[layer], ctx->sp_b[layer], out, imgs, H, W, kSpCin[layer], kSpCout[layer], true, pool, s);
 }
 
 // Images whose height / width is not a multiple of 8 (upstream: the convolutions see the whole image, every max-pool floors):
@@ -478,46 +488,66 @@ int sp_sample(e2emv_ctx* ctx, const float* dense, const float* d_kpts, const int
     return E2EMV_OK;
 }
 
-}  // namespace
+// The sizes of one call: the (padded) storage grid, the images themselves, the score map and the cell grid behind the three pools.
+struct SpGeom {
+    int B, Hp, Wp, Hv, Wv, H, W, Hc, Wc;
+    bool padded;
+    int64_t npix_p, npix, cells;
+};
+int sp_geometry(e2emv_ctx* ctx, const e2emv_superpoint_desc* d, const char* who, SpGeom& g) {
+    g.B = d->batch; g.Hp = d->height; g.Wp = d->width;
+    if (g.B < 1 || g.Hp < 16 || g.Wp < 16 || g.Hp % 8 || g.Wp % 8) return set_err(ctx, E2EMV_ESHAPE, "%s: image %dx%d must be a multiple of 8 (>= 16)", who, g.Hp, g.Wp);
+    g.Hv = d->valid_height > 0 ? d->valid_height : g.Hp; g.Wv = d->valid_width > 0 ? d->valid_width : g.Wp;  // the image itself
+    if (g.Hv > g.Hp || g.Wv > g.Wp || g.Hp - g.Hv >= 8 || g.Wp - g.Wv >= 8 || g.Hv < 16 || g.Wv < 16)
+        return set_err(ctx, E2EMV_ESHAPE, "%s: valid size %dx%d must lie within 7 pixels below the padded %dx%d", who, g.Hv, g.Wv, g.Hp, g.Wp);
+    g.padded = g.Hv != g.Hp || g.Wv != g.Wp;
+    g.H = g.Hv / 8 * 8; g.W = g.Wv / 8 * 8;  // size of the score map = what every stage behind the encoder works on
+    if ((int64_t)g.B * g.Hp * g.Wp >= (int64_t(1) << 31)) return set_err(ctx, E2EMV_ESHAPE, "%s: batch too large for one call (B*H*W < 2^31)", who);
+    g.npix_p = (int64_t)g.B * g.Hp * g.Wp;
+    g.npix = (int64_t)g.B * g.H * g.W; g.cells = g.npix / 64;
+    g.Hc = g.H / 8; g.Wc = g.W / 8;
+    return E2EMV_OK;
+}
 
-extern "C" int e2emv_superpoint_forward(e2emv_ctx* ctx, const e2emv_superpoint_desc* d, const float* d_images, float* d_kpts, float* d_scores,
-                                        float* d_desc, int32_t* d_count, float* d_score_map, void* stream) {
-    if (!ctx) return E2EMV_EINVAL;
-    E2EMV_ENTER(ctx, stream);
-    if (!d || !d_images || !d_kpts || !d_scores || !d_desc || !d_count) return set_err(ctx, E2EMV_EINVAL, "superpoint_forward: NULL argument");
-    if (!ctx->sp_committed) return set_err(ctx, E2EMV_ESTATE, "superpoint_forward: weights not committed (e2emv_superpoint_commit)");
-    const int B = d->batch, K = d->max_keypoints, r = d->nms_radius;
-    const int Hp = d->height, Wp = d->width;  // the (padded) grid the images are stored on
-    if (B < 1 || Hp < 16 || Wp < 16 || Hp % 8 || Wp % 8) return set_err(ctx, E2EMV_ESHAPE, "superpoint_forward: image %dx%d must be a multiple of 8 (>= 16)", Hp, Wp);
-    const int Hv = d->valid_height > 0 ? d->valid_height : Hp, Wv = d->valid_width > 0 ? d->valid_width : Wp;  // the image itself
-    if (Hv > Hp || Wv > Wp || Hp - Hv >= 8 || Wp - Wv >= 8 || Hv < 16 || Wv < 16)
-        return set_err(ctx, E2EMV_ESHAPE, "superpoint_forward: valid size %dx%d must lie within 7 pixels below the padded %dx%d", Hv, Wv, Hp, Wp);
-    const bool padded = Hv != Hp || Wv != Wp;
-    const int H = Hv / 8 * 8, W = Wv / 8 * 8;  // size of the score map = what every stage behind the encoder works on
-    if (K < 1 || K > kSelMaxK) return set_err(ctx, E2EMV_ESHAPE, "superpoint_forward: max_keypoints %d outside 1..%d", K, kSelMaxK);
-    if (r < 0 || r > 16 || d->remove_borders < 0) return set_err(ctx, E2EMV_EINVAL, "superpoint_forward: nms_radius %d / remove_borders %d", r, d->remove_borders);
-    if ((int64_t)B * Hp * Wp >= (int64_t(1) << 31)) return set_err(ctx, E2EMV_ESHAPE, "superpoint_forward: batch too large for one call (B*H*W < 2^31)");
-    hipStream_t s = (hipStream_t)stream;
-    const int64_t npix_p = (int64_t)B * Hp * Wp;
-    const int64_t npix = (int64_t)B * H * W, cells = npix / 64;
-    const int Hc = H / 8, Wc = W / 8;
-    auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
-    // workspace: two full-resolution 64-channel buffers (ping-pong for the whole encoder), heads, 5 score-sized maps, lists
-    const size_t big = al(sizeof(float) * npix_p * 64);
-    const size_t sz_x = al(sizeof(float) * cells * 128), sz_p = al(sizeof(float) * cells * 256), sz_65 = al(sizeof(float) * cells * 65);
-    const size_t sz_map = al(sizeof(float) * npix);
-    const size_t bytes = 2 * big + sz_x + 2 * sz_p + sz_65 + 7 * sz_map;
-    int rc = ws_reserve(ctx, bytes);
-    if (rc) return rc;
-    char* p = ctx->d_ws;
-    auto take = [&](size_t b) { char* q = p; p += b; return q; };
-    float* A = (float*)take(big); float* Bf = (float*)take(big);
-    float* X = (float*)take(sz_x); float* P1 = (float*)take(sz_p); float* P2 = (float*)take(sz_p); float* S65 = (float*)take(sz_65);
-    float* score = (float*)take(sz_map); float* mask = (float*)take(sz_map); float* supp = (float*)take(sz_map); float* ss = (float*)take(sz_map);
-    float* nms = d_score_map ? d_score_map : (float*)take(sz_map);
-    if (d_score_map) take(sz_map);
-    int* lidx = (int*)take(sz_map); float* lsc = (float*)take(sz_map);
+// The encoder's workspace: two full-resolution 64-channel buffers (ping-pong for the whole encoder), the heads, the score map.
+struct SpEncWs {
+    float *A, *Bf, *X, *P1, *P2, *S65, *score;
+};
+inline size_t sp_al(size_t b) { return (b + 255) & ~size_t(255); }
+inline size_t sp_map_bytes(const SpGeom& g) { return sp_al(sizeof(float) * g.npix); }
+inline size_t sp_enc_bytes(const SpGeom& g) {
+    return 2 * sp_al(sizeof(float) * g.npix_p * 64) + sp_al(sizeof(float) * g.cells * 128) + 2 * sp_al(sizeof(float) * g.cells * 256) +
+           sp_al(sizeof(float) * g.cells * 65) + sp_map_bytes(g);
+}
+inline char* sp_enc_carve(char* p, const SpGeom& g, SpEncWs& w) {
+    auto take = [&](size_t b) { char* q = p; p += b; return (float*)q; };
+    const size_t big = sp_al(sizeof(float) * g.npix_p * 64), sz_p = sp_al(sizeof(float) * g.cells * 256);
+    w.A = take(big); w.Bf = take(big);
+    w.X = take(sp_al(sizeof(float) * g.cells * 128)); w.P1 = take(sz_p); w.P2 = take(sz_p); w.S65 = take(sp_al(sizeof(float) * g.cells * 65));
+    w.score = take(sp_map_bytes(g));
+    return p;
+}
 
+// The head of the network, image -> score map + dense descriptors: THE list of launches (e2emv_superpoint_forward and
+// e2emv_superpoint_encode both run it).  score [B,H,W] receives the map simple_nms takes, dense [B,Hc,Wc,256] the unnormalised
+// output of the descriptor head.  after_score (optional) runs between the softmax and the descriptor head, inside the softmax's
+// profiling scope: forward's detector tail.  taps (optional, HOST array of 12 device pointers, NULL entries skipped): tap l
+// receives layer l's output as the next stage reads it - after the fused pool, the masking to the valid size and (layer 5) the
+// crop - by a device-to-device copy on the stream right behind that point.
+template <class AfterScore>
+int sp_encode(e2emv_ctx* ctx, const SpGeom& g, SpEncWs w, const float* d_images, float* score, float* dense, float* const* taps, hipStream_t s,
+              AfterScore after_score) {
+    const int B = g.B, Hp = g.Hp, Wp = g.Wp, Hv = g.Hv, Wv = g.Wv, Hc = g.Hc, Wc = g.Wc;
+    const bool padded = g.padded;
+    const int64_t npix_p = g.npix_p, cells = g.cells;
+    float *A = w.A, *Bf = w.Bf, *X = w.X, *P1 = w.P1, *S65 = w.S65;
+    int rc;
+    auto tap = [&](int l, const float* src, int64_t elems) -> int {
+        if (!taps || !taps[l]) return E2EMV_OK;
+        if (hipMemcpyAsync(taps[l], src, sizeof(float) * (size_t)elems, hipMemcpyDeviceToDevice, s) != hipSuccess)
+            return set_err(ctx, E2EMV_EHIP, "superpoint: copy of tap %d failed", l);
+        return E2EMV_OK;
+    };
     // ---- encoder ----
     prof_begin(ctx, PS_INGEST, s);
     hipLaunchKernelGGL(sp_conv1a_kernel, dim3((unsigned)((npix_p + 15) / 16)), dim3(256), 0, s, d_images, ctx->sp_w[0], ctx->sp_b[0], A, Hp, Wp, npix_p);
@@ -532,14 +562,19 @@ extern "C" int e2emv_superpoint_forward(e2emv_ctx* ctx, const e2emv_superpoint_d
     };
     // conv_b of blocks 1-3 write their 2x2 max-pooled output directly (fused epilogue)
     zero_outside(A, 1, 64);
+    if ((rc = tap(0, A, npix_p * 64))) return rc;
     if ((rc = sp_conv3x3(ctx, 1, A, Bf, B, Hp, Wp, s, true))) return rc;
     zero_outside(Bf, 2, 64);
+    if ((rc = tap(1, Bf, npix_p / 4 * 64))) return rc;
     if ((rc = sp_conv3x3(ctx, 2, Bf, A, B, Hp / 2, Wp / 2, s))) return rc;
     zero_outside(A, 2, 64);
+    if ((rc = tap(2, A, npix_p / 4 * 64))) return rc;
     if ((rc = sp_conv3x3(ctx, 3, A, Bf, B, Hp / 2, Wp / 2, s, true))) return rc;
     zero_outside(Bf, 4, 64);
+    if ((rc = tap(3, Bf, npix_p / 16 * 64))) return rc;
     if ((rc = sp_conv3x3(ctx, 4, Bf, A, B, Hp / 4, Wp / 4, s))) return rc;
     zero_outside(A, 4, 128);
+    if ((rc = tap(4, A, npix_p / 16 * 128))) return rc;
     if ((rc = sp_conv3x3(ctx, 5, A, Bf, B, Hp / 4, Wp / 4, s, true))) return rc;
     if (padded && (Hc != Hp / 8 || Wc != Wp / 8)) {  // the valid block of the third pool's output, unpadded from here on
         const int64_t total = (int64_t)B * Hc * Wc * 32;
@@ -547,21 +582,84 @@ extern "C" int e2emv_superpoint_forward(e2emv_ctx* ctx, const e2emv_superpoint_d
         E2EMV_CHECK_LAUNCH(ctx, "sp_crop_kernel");
         std::swap(A, Bf);
     }
+    if ((rc = tap(5, Bf, cells * 128))) return rc;
     if ((rc = sp_conv3x3(ctx, 6, Bf, A, B, Hc, Wc, s))) return rc;
+    if ((rc = tap(6, A, cells * 128))) return rc;
     if ((rc = sp_conv3x3(ctx, 7, A, X, B, Hc, Wc, s))) return rc;
+    if ((rc = tap(7, X, cells * 128))) return rc;
     // ---- detector head ----
     if ((rc = sp_conv3x3(ctx, 8, X, P1, B, Hc, Wc, s))) return rc;
+    if ((rc = tap(8, P1, cells * 256))) return rc;
     if ((rc = sp_conv1x1(ctx, 9, P1, S65, cells, s))) return rc;
+    if ((rc = tap(9, S65, cells * 65))) return rc;
     prof_begin(ctx, PS_MATCH, s);
     hipLaunchKernelGGL(sp_softmax_d2s_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, s, S65, score, Hc, Wc, cells);
     E2EMV_CHECK_LAUNCH(ctx, "sp_softmax_d2s_kernel");
-    if ((rc = sp_detect(ctx, d, score, mask, supp, ss, nms, lidx, lsc, B, H, W, d_kpts, d_scores, d_count, s))) return rc;
+    if ((rc = after_score())) return rc;
     prof_end(ctx, s);
     // ---- descriptor head ----
     if ((rc = sp_conv3x3(ctx, 10, X, P1, B, Hc, Wc, s))) return rc;
-    if ((rc = sp_conv1x1(ctx, 11, P1, P2, cells, s))) return rc;
-    if ((rc = sp_sample(ctx, P2, d_kpts, d_count, d_desc, B, Hc, Wc, K, s))) return rc;
+    if ((rc = tap(10, P1, cells * 256))) return rc;
+    if ((rc = sp_conv1x1(ctx, 11, P1, dense, cells, s))) return rc;
+    if ((rc = tap(11, dense, cells * 256))) return rc;
     return E2EMV_OK;
+}
+
+}  // namespace
+
+extern "C" int e2emv_superpoint_forward(e2emv_ctx* ctx, const e2emv_superpoint_desc* d, const float* d_images, float* d_kpts, float* d_scores,
+                                        float* d_desc, int32_t* d_count, float* d_score_map, void* stream) {
+    if (!ctx) return E2EMV_EINVAL;
+    E2EMV_ENTER(ctx, stream);
+    if (!d || !d_images || !d_kpts || !d_scores || !d_desc || !d_count) return set_err(ctx, E2EMV_EINVAL, "superpoint_forward: NULL argument");
+    if (!ctx->sp_committed) return set_err(ctx, E2EMV_ESTATE, "superpoint_forward: weights not committed (e2emv_superpoint_commit)");
+    SpGeom g;
+    int rc = sp_geometry(ctx, d, "superpoint_forward", g);
+    if (rc) return rc;
+    const int K = d->max_keypoints, r = d->nms_radius;
+    if (K < 1 || K > kSelMaxK) return set_err(ctx, E2EMV_ESHAPE, "superpoint_forward: max_keypoints %d outside 1..%d", K, kSelMaxK);
+    if (r < 0 || r > 16 || d->remove_borders < 0) return set_err(ctx, E2EMV_EINVAL, "superpoint_forward: nms_radius %d / remove_borders %d", r, d->remove_borders);
+    hipStream_t s = (hipStream_t)stream;
+    // workspace: the encoder's, then 6 more score-sized maps (mask, supp, ss, the NMS-ed map, the two candidate lists)
+    const size_t sz_map = sp_map_bytes(g);
+    if ((rc = ws_reserve(ctx, sp_enc_bytes(g) + 6 * sz_map))) return rc;
+    SpEncWs w;
+    char* p = sp_enc_carve(ctx->d_ws, g, w);
+    auto take = [&](size_t b) { char* q = p; p += b; return q; };
+    float* mask = (float*)take(sz_map); float* supp = (float*)take(sz_map); float* ss = (float*)take(sz_map);
+    float* own = (float*)take(sz_map);
+    float* nms = d_score_map ? d_score_map : own;
+    int* lidx = (int*)take(sz_map); float* lsc = (float*)take(sz_map);
+    rc = sp_encode(ctx, g, w, d_images, w.score, w.P2, nullptr, s, [&]() {
+        return sp_detect(ctx, d, w.score, mask, supp, ss, nms, lidx, lsc, g.B, g.H, g.W, d_kpts, d_scores, d_count, s);
+    });
+    if (rc) return rc;
+    return sp_sample(ctx, w.P2, d_kpts, d_count, d_desc, g.B, g.Hc, g.Wc, K, s);
+}
+
+// The head of e2emv_superpoint_forward alone (building block for per-kernel parity tests): everything in front of the detector
+// tail and the descriptor sampling, by the same function, with every layer's output on request.
+extern "C" int e2emv_superpoint_encode(e2emv_ctx* ctx, const e2emv_superpoint_desc* d, const float* d_images, float* d_score, float* d_dense,
+                                       float* const* d_taps, void* stream) {
+    if (!ctx) return E2EMV_EINVAL;
+    E2EMV_ENTER(ctx, stream);
+    if (!d || !d_images) return set_err(ctx, E2EMV_EINVAL, "superpoint_encode: NULL argument");
+    if (!ctx->sp_committed) return set_err(ctx, E2EMV_ESTATE, "superpoint_encode: weights not committed (e2emv_superpoint_commit)");
+    SpGeom g;
+    int rc = sp_geometry(ctx, d, "superpoint_encode", g);
+    if (rc) return rc;
+    if ((rc = ws_reserve(ctx, sp_enc_bytes(g)))) return rc;
+    SpEncWs w;
+    sp_enc_carve(ctx->d_ws, g, w);
+    return sp_encode(ctx, g, w, d_images, d_score ? d_score : w.score, d_dense ? d_dense : w.P2, d_taps, (hipStream_t)stream, []() { return (int)E2EMV_OK; });
+}
+
+// The CONV mode of launch_gemm_nt alone (building block for per-kernel parity tests), as e2emv_gemm_nt is its plain mode.
+extern "C" int e2emv_conv3x3_nhwc(e2emv_ctx* ctx, int n_img, int H, int W, int Cin, int Cout, const float* d_in, const float* d_w, const float* d_bias,
+                                  int flags, float* d_out, void* stream) {
+    if (!ctx || !d_in || !d_w || !d_out) return E2EMV_EINVAL;
+    E2EMV_ENTER(ctx, stream);
+    return conv3x3_nhwc(ctx, d_in, d_w, d_bias, d_out, n_img, H, W, Cin, Cout, (flags & 1) != 0, (flags & 2) != 0, (hipStream_t)stream);
 }
 
 // The detector tail alone on a caller-supplied score map (building block for per-kernel parity tests): the same kernels, launch

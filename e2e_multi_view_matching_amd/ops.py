@@ -62,6 +62,26 @@ def gemm_nt(A, W, bias=None, residual=None, A2=None, scale=1.0, relu=False):
     return C if batched else C[0]
 
 
+def conv3x3_nhwc(x_nhwc, w_oihw, bias=None, relu=False, pool=False):
+    """The CONV mode of the fp32 GEMM alone (``e2emv_conv3x3_nhwc``: a building block for per-kernel parity tests): 3x3 / pad 1 /
+    stride 1 convolution of ``x_nhwc`` [n,H,W,Cin] with the upstream-layout weight ``w_oihw`` [Cout,Cin,3,3] (permuted here to the
+    kernel's (O, ky, kx, I)), optional bias and ReLU; ``pool`` fuses the following 2x2 / stride-2 max-pool.  Returns NHWC
+    [n,H,W,Cout], with the pool [n,H/2,W/2,Cout]."""
+    ctx = _ctx(x_nhwc)
+    x = x_nhwc.contiguous().float()
+    n, H, W, Cin = x.shape
+    Cout = int(w_oihw.shape[0])
+    if tuple(w_oihw.shape) != (Cout, Cin, 3, 3):
+        raise AssertionError("weight must be [Cout,{},3,3], got {}".format(Cin, tuple(w_oihw.shape)))
+    w = w_oihw.to(x.device, torch.float32).permute(0, 2, 3, 1).contiguous()
+    b = bias.to(x.device, torch.float32).contiguous() if bias is not None else None
+    out = torch.empty((n, H // 2, W // 2, Cout) if pool else (n, H, W, Cout), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        ctx.call("e2emv_conv3x3_nhwc", n, H, W, Cin, Cout, _lib.ptr(x), _lib.ptr(w), _lib.ptr(b), (1 if relu else 0) | (2 if pool else 0),
+                 _lib.ptr(out), _lib.stream_ptr(x.device))
+    return out
+
+
 def _attention_counts(name, T, n_valid):
     """(entry point, count argument) of an attention building block: an int is the uniform count of `name`, a sequence of
     T ints the per-image counts of `name`_v (host array)."""

@@ -99,6 +99,46 @@ class SuperPoint(nn.Module):
         return out
 
 
+def tap_shapes(B, H, W):
+    """Shapes of the 12 taps of ``encode`` for [B,1,H,W] images (NHWC; tap 9: the 65 detector logits per cell, cells as rows)."""
+    Hp, Wp, Hc, Wc = (H + 7) // 8 * 8, (W + 7) // 8 * 8, H // 8, W // 8
+    return ([(B, Hp, Wp, 64)] + [(B, Hp // 2, Wp // 2, 64)] * 2 + [(B, Hp // 4, Wp // 4, 64), (B, Hp // 4, Wp // 4, 128)] + [(B, Hc, Wc, 128)] * 3 +
+            [(B, Hc, Wc, 256), (B * Hc * Wc, 65), (B, Hc, Wc, 256), (B, Hc, Wc, 256)])
+
+
+def encode(model, images, taps=False):
+    """The head of ``SuperPoint.forward`` alone (``e2emv_superpoint_encode``: a building block for per-kernel parity tests): ``images``
+    [B,1,H,W] on the device, padded and uploaded as ``forward`` does, go through the launches ``forward`` runs in front of its
+    detector tail.  Returns ``(score, dense)`` - ``score`` [B,H//8*8,W//8*8], the map upstream's ``simple_nms`` receives, ``dense``
+    [B,256,H//8,W//8], the UNnormalised output of the descriptor head - and with ``taps`` a third value: the list of the 12 layers'
+    outputs as the next stage reads them (``tap_shapes``: NHWC on the zero-padded grid, masked to the valid size, up to layer 4, on
+    the cell grid from layer 5 on)."""
+    if not images.is_cuda:
+        raise RuntimeError("SuperPoint needs its images on an MI355X (no CPU fallback)")
+    dev = images.device
+    ctx = _lib.context(dev)
+    B, C, H, W = images.shape
+    if C != 1:
+        raise AssertionError("SuperPoint takes one-channel images, got {}".format(tuple(images.shape)))
+    Hv, Wv = H, W
+    if H % 8 or W % 8:
+        Hp, Wp = (H + 7) // 8 * 8, (W + 7) // 8 * 8
+        images = torch.nn.functional.pad(images, (0, Wp - W, 0, Hp - H))
+        H, W = Hp, Wp
+    img = images.to(torch.float32).contiguous()
+    d = _lib.SuperPointDesc(valid_height=Hv, valid_width=Wv, batch=B, height=H, width=W)
+    score = torch.empty((B, Hv // 8 * 8, Wv // 8 * 8), dtype=torch.float32, device=dev)
+    nhwc = torch.empty((B, Hv // 8, Wv // 8, 256), dtype=torch.float32, device=dev)
+    # (filled with NaN: a tap the library did not write in full cannot pass for one)
+    tl = [torch.full(s, float("nan"), dtype=torch.float32, device=dev) for s in tap_shapes(B, Hv, Wv)] if taps else []
+    tp, keep = _lib.ptr_array(tl) if taps else (None, None)
+    with torch.cuda.device(dev), ctx.py_lock:
+        model._upload(ctx)
+        ctx.call("e2emv_superpoint_encode", ctypes.byref(d), _lib.ptr(img), _lib.ptr(score), _lib.ptr(nhwc), tp, _lib.stream_ptr(dev))
+    dense = nhwc.permute(0, 3, 1, 2)
+    return (score, dense, tl) if taps else (score, dense)
+
+
 def detect(score, dense=None, **config):
     """The detector tail alone (``e2emv_superpoint_detect``: a building block for per-kernel parity tests): ``score`` [B,H,W] fp32 on
     the device is the map upstream's ``simple_nms`` receives, ``dense`` (optional) [B,256,H/8,W/8] the UNnormalised output of the

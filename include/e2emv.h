@@ -610,6 +610,28 @@ int e2emv_superpoint_detect(e2emv_ctx* ctx, const e2emv_superpoint_desc* desc,
                             float* d_desc,         /* [B,256,K]; required if and only if d_dense is given               */
                             float* d_nms_map,      /* optional [B,H,W]: the NMS-ed map                                  */
                             void* stream);
+/* The head of e2emv_superpoint_forward alone, image -> score map + dense descriptors: everything in front of the detector tail
+ * and the descriptor sampling, by the same host function (one list of launches).  desc as for forward; its detector fields
+ * (nms_radius, max_keypoints, remove_borders, fill_random, keypoint_threshold, seed) are ignored.  Needs committed weights.
+ * d_taps: optional HOST array of 12 DEVICE pointers (NULL entries are skipped); tap l receives the output of layer l (conv1a ..
+ * convDb in the order of e2emv_superpoint_commit) exactly as the next stage reads it - after the fused 2x2 max-pool, after the
+ * masking to the valid size and, for layer 5, after the crop to the cell grid - by a device-to-device copy on the stream.  With
+ * (Hp, Wp) = (height, width) and (Hc, Wc) = (valid height / 8, valid width / 8) floored, all NHWC fp32:
+ * 0 [B,Hp,Wp,64]; 1, 2 [B,Hp/2,Wp/2,64]; 3 [B,Hp/4,Wp/4,64]; 4 [B,Hp/4,Wp/4,128]; 5, 6, 7 [B,Hc,Wc,128]; 8 [B,Hc,Wc,256];
+ * 9 [B*Hc*Wc,65]; 10, 11 [B,Hc,Wc,256].                                                                                  */
+int e2emv_superpoint_encode(e2emv_ctx* ctx, const e2emv_superpoint_desc* desc,
+                            const float* d_images, /* [B,height,width] fp32, as for forward                                  */
+                            float* d_score,        /* optional [B,H8,W8]: the map simple_nms receives                        */
+                            float* d_dense,        /* optional [B,Hc,Wc,256] NHWC: the UNnormalised descriptor-head output   */
+                            float* const* d_taps, void* stream);
+/* The CONV mode of the fp32 GEMM alone, as e2emv_gemm_nt is its plain mode: a 3x3 / pad 1 / stride 1 convolution as an implicit
+ * GEMM (rows = pixels, K = 9 * Cin, zero padding resolved in the operand fetch).  d_in [n_img,H,W,Cin] NHWC, d_w [Cout][9*Cin]
+ * ordered (ky, kx, cin), d_bias [Cout] or NULL; flags: bit0 relu, bit1 the fused 2x2 / stride-2 max-pool (quad-major rows, maximum
+ * taken in the epilogue); d_out [n_img,H,W,Cout], with the pool [n_img,H/2,W/2,Cout].  Cin % 32 == 0, n_img*H*W < 2^31, sides
+ * <= 32767; the pool needs even sides, Cout % 4 == 0 and 16-byte aligned d_out / d_bias (E2EMV_ESHAPE otherwise); every pointer
+ * 16-byte aligned.                                                                                                       */
+int e2emv_conv3x3_nhwc(e2emv_ctx* ctx, int n_img, int H, int W, int Cin, int Cout, const float* d_in, const float* d_w,
+                       const float* d_bias, int flags, float* d_out, void* stream);
 
 /* ---- arithmetic of the dense GNN contractions -----------------------------------------
  * E2EMV_PRECISION_F32    : v_mfma_f32_32x32x2_f32, exact fp32 products (the audit mode).
