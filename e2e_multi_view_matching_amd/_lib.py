@@ -103,6 +103,8 @@ SIGNATURES = {
                                     ctypes.c_double, c_void_p, c_void_p]),
     "e2emv_ba_2view_backward": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                         c_void_p]),
+    "e2emv_ba_2view_loss_backward": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, ctypes.c_double,
+                                             c_void_p, c_void_p, c_void_p, c_void_p]),
     "e2emv_gt_matches": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                  c_int, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p]),
     "e2emv_match_loss": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -21,6 +21,10 @@
 // bookkeeping compares is sum rho(s0) + sum rho(s1); the linearisation is Ceres' corrector for rho'' <= 0, applied once per block
 // in point_terms: r0, Jp0 times sqrt(rho'(s0)) and r1, Jp1, Jc times sqrt(rho'(s1)), so that the three passes, the positivity
 // check and the preconditioner's floor all see the system that is solved.  rho and sqrt(rho') are mv_loss of mvba.h.
+//
+// Backward pass (e2emv_ba_2view_backward, e2emv_ba_2view_loss_backward; second half of this file): the exact reverse of the loop, to
+// the confidences and the start pose, for the squared loss and for both robust losses - through the corrector and through the pair's
+// scale a_b = loss_scale / cden_b.
 #include "common.h"
 #include "mvba.h"
 #include "small_linalg.h"
@@ -517,9 +521,10 @@ extern "C" int e2emv_ba_2view_loss(e2emv_ctx* ctx, int B, int N, const float* d_
                        d_summary, stream);
 }
 
-// ---- backward pass of ba2view_kernel<kLossNone>: dLoss/dconf and dLoss/dT_init from dLoss/dT_out (e2emv_ba_2view_backward) ----
+// ---- backward pass of ba2view_kernel<LOSS>: dLoss/dconf and dLoss/dT_init from dLoss/dT_out (e2emv_ba_2view_backward for the squared
+// loss, e2emv_ba_2view_loss_backward for all three) ----
 //
-// Phase 1 replays the forward loop from the inputs - ba2view_lm<kLossNone, true>, the very function the forward kernel runs, so that
+// Phase 1 replays the forward loop from the inputs - ba2view_lm<LOSS, true>, the very function the forward kernel runs, so that
 // every accept / reject decision is the forward's - and keeps a tape in the workspace: X_k of every evaluation, and per evaluation a
 // record (Rt_k, lambda_k, precond, skipped, dc_k).  k* = the evaluation whose pose became the result.  Phase 2 walks k = k*-1 .. 0 with the
 // adjoint state (Rt_bar in LDS, X_bar in the workspace).  One LM step solves M d = b, M = A + lambda D, A = J^T J, b = -J^T r, D =
@@ -531,6 +536,16 @@ extern "C" int e2emv_ba_2view_loss(e2emv_ctx* ctx, int B, int N, const float* d_
 // then 1 / (X3 + 1e-8)) and the normalisation of the weights.  lambda, the comparisons and k* are piecewise constant.
 // Phase 2 forms the point blocks with the loop's helpers (point_hpp, point_damp, point_hcp, point_w_row, point_solve) and solves its
 // 6x6 system with the loop's schur6_solve.
+//
+// With a loss the system that is solved is the CORRECTED one, r~ = sq r and J~ = sq J per observation block (block 0: r0, Jp0; block
+// 1: r1, Jp1, Jc), sq = sqrt(rho'(s)), s = |r|^2 of the uncorrected weighted residual, at the pair's scale a = loss_scale / cden.  The
+// formulas above then give the adjoint of (r~, J~), and one more step takes it to the uncorrected terms and to a, per block:
+//     sq_bar = <r~_bar, r> + <J~_bar, J>,   r_bar = sq r~_bar + 2 (dsq/ds) sq_bar r,   J_bar = sq J~_bar,   a_bar += (dsq/da) sq_bar
+//     cauchy: dsq/ds = -sq^3 / (2 a^2), dsq/da = sq^3 s / a^3;   huber: s <= a^2: both 0, else dsq/ds = -sq / (4 s), dsq/da = sq / (2 a)
+// with (r, J) from point_terms<kLossNone> and sq from mv_loss on top of it, in the order point_terms<LOSS> uses; point_terms_reverse
+// runs unchanged on (r_bar, J_bar).  a_bar is summed over matches and steps per thread and across the workgroup once, at the end:
+// a = loss_scale / cden with cden = sum conf gives every positive-confidence row -a_bar a / cden (nothing where cden is the clamp).
+// rho itself - the costs that are compared - carries nothing.  All of it is compiled for LOSS != kLossNone only.
 namespace e2emv {
 
 struct BaBwdParams {
@@ -542,6 +557,29 @@ struct BaBwdParams {
     size_t stride;  // doubles per pair
     float lm_inc, lm_dec;
 };
+// ... and with a loss (the squared-loss kernel keeps the arguments it has)
+struct BaBwdLossParams : BaBwdParams {
+    double loss_scale;  // relative, as in BaParams
+};
+template <int LOSS>
+struct BaBwdArgs { using type = BaBwdLossParams; };
+template <>
+struct BaBwdArgs<kLossNone> { using type = BaBwdParams; };
+
+// d sqrt(rho'(s)) / ds and / da of mv_loss<LOSS> (sq = its sqrt(rho'(s))); Huber's kink at s = a2 takes the first branch, like mv_loss
+template <int LOSS>
+__device__ __forceinline__ void mv_loss_sq_reverse(double s, double sq, double a, double a2, double* dsq_ds, double* dsq_da) {
+    if (LOSS == kLossHuber) {
+        if (s <= a2) {
+            *dsq_ds = 0.0; *dsq_da = 0.0;
+        } else {
+            *dsq_ds = -sq / (4.0 * s); *dsq_da = sq / (2.0 * a);
+        }
+    } else {
+        const double sq3 = sq * sq * sq;
+        *dsq_ds = -sq3 / (2.0 * a2); *dsq_da = sq3 * s / (a2 * a);
+    }
+}
 
 // adjoint of se3_exp_left: nb = adjoint of the new pose -> dcb [6], and tb [12] = the part of the old pose's adjoint that comes
 // through the product.  In the clamped branch f1, f2, f3 are constants: the derivative flows through hat(w) only.
@@ -705,7 +743,8 @@ __device__ __forceinline__ void triangulate_reverse(double x1, double y1, double
     }
 }
 
-__global__ __launch_bounds__(256) void ba2view_backward_kernel(BaBwdParams p) {
+template <int LOSS>
+__global__ __launch_bounds__(256) void ba2view_backward_kernel(typename BaBwdArgs<LOSS>::type p) {
     __shared__ BaLmShared<true> sh;
     __shared__ double sRtBar[12], sDcBar[6];
     double* const red = sh.red;
@@ -724,8 +763,13 @@ __global__ __launch_bounds__(256) void ba2view_backward_kernel(BaBwdParams p) {
 
     // ---- phase 1: the forward loop again, with the tape
     double csum, cden, la;
-    const bool valid = ba2view_lm<kLossNone, true>(sh, N, p.n_it, k0, k1, cf, Ti, tape, xs, recs, p.lm_inc, p.lm_dec, 0.0, csum, cden, la);
+    double loss_scale = 0.0;
+    if constexpr (LOSS != kLossNone) loss_scale = p.loss_scale;
+    const bool valid = ba2view_lm<LOSS, true>(sh, N, p.n_it, k0, k1, cf, Ti, tape, xs, recs, p.lm_inc, p.lm_dec, loss_scale, csum, cden, la);
     const int kstar = valid ? sh.kept.kstar : 0;
+    double la2 = 0.0;
+    [[maybe_unused]] double abar = 0.0;  // adjoint of the pair's scale: this thread's matches, all steps
+    if constexpr (LOSS != kLossNone) la2 = la * la;
 
     // ---- phase 2: the steps k* - 1 .. 0 in reverse
     if (tid < 12) {
@@ -766,7 +810,7 @@ __global__ __launch_bounds__(256) void ba2view_backward_kernel(BaBwdParams p) {
         for (int i = tid; i < N; i += 256) {
             if (!(cf[i] > 0.f)) continue;
             PointTerms q;
-            point_terms<kLossNone>(Rt, X + 3 * i, k0[2 * i], k0[2 * i + 1], k1[2 * i], k1[2 * i + 1], (double)cf[i] / cden, 0.0, 0.0, q);
+            point_terms<LOSS>(Rt, X + 3 * i, k0[2 * i], k0[2 * i + 1], k1[2 * i], k1[2 * i + 1], (double)cf[i] / cden, la, la2, q);
             int idx = 0;
 #pragma unroll
             for (int u = 0; u < 6; ++u)
@@ -812,7 +856,7 @@ __global__ __launch_bounds__(256) void ba2view_backward_kernel(BaBwdParams p) {
             if (!(cf[i] > 0.f)) continue;
             const double c = (double)cf[i] / cden;
             PointTerms q;
-            point_terms<kLossNone>(Rt, X + 3 * i, k0[2 * i], k0[2 * i + 1], k1[2 * i], k1[2 * i + 1], c, 0.0, 0.0, q);
+            point_terms<LOSS>(Rt, X + 3 * i, k0[2 * i], k0[2 * i + 1], k1[2 * i], k1[2 * i + 1], c, la, la2, q);
             double Hpp[6], Hcp[6][3], inv[6], gd[3], gw[3], dp[3], wp[3], wdp[3];
             const double xb[3] = {Xbar[3 * i], Xbar[3 * i + 1], Xbar[3 * i + 2]};
             point_hpp(q, Hpp);
@@ -865,6 +909,40 @@ __global__ __launch_bounds__(256) void ba2view_backward_kernel(BaBwdParams p) {
 #pragma unroll
                 for (int u = 0; u < 6; ++u) qb.Jc[r][u] = -jw1 * dc[u] - e1 * wc[u] - q.Jc[r][u] * wdc[u];
             }
+            if constexpr (LOSS != kLossNone) {  // qb is the adjoint of the corrected blocks: back through the corrector, per block
+                PointTerms qr;
+                point_terms<kLossNone>(Rt, X + 3 * i, k0[2 * i], k0[2 * i + 1], k1[2 * i], k1[2 * i + 1], c, 0.0, 0.0, qr);
+                const double s0 = qr.r0[0] * qr.r0[0] + qr.r0[1] * qr.r0[1], s1 = qr.r1[0] * qr.r1[0] + qr.r1[1] * qr.r1[1];
+                double rho0, sq0, rho1, sq1, ds0, da0, ds1, da1;
+                mv_loss<LOSS>(s0, la, la2, &rho0, &sq0);
+                mv_loss<LOSS>(s1, la, la2, &rho1, &sq1);
+                mv_loss_sq_reverse<LOSS>(s0, sq0, la, la2, &ds0, &da0);
+                mv_loss_sq_reverse<LOSS>(s1, sq1, la, la2, &ds1, &da1);
+                double sb0 = 0.0, sb1 = 0.0;  // sq_bar of the two blocks
+#pragma unroll
+                for (int r = 0; r < 2; ++r) {
+                    sb0 += qb.r0[r] * qr.r0[r];
+                    sb1 += qb.r1[r] * qr.r1[r];
+#pragma unroll
+                    for (int u = 0; u < 3; ++u) {
+                        sb0 += qb.Jp0[r][u] * qr.Jp0[r][u];
+                        sb1 += qb.Jp1[r][u] * qr.Jp1[r][u];
+                    }
+#pragma unroll
+                    for (int u = 0; u < 6; ++u) sb1 += qb.Jc[r][u] * qr.Jc[r][u];
+                }
+                abar += da0 * sb0 + da1 * sb1;
+                const double t0 = 2.0 * ds0 * sb0, t1 = 2.0 * ds1 * sb1;
+#pragma unroll
+                for (int r = 0; r < 2; ++r) {
+                    qb.r0[r] = sq0 * qb.r0[r] + t0 * qr.r0[r];
+                    qb.r1[r] = sq1 * qb.r1[r] + t1 * qr.r1[r];
+#pragma unroll
+                    for (int u = 0; u < 3; ++u) { qb.Jp0[r][u] *= sq0; qb.Jp1[r][u] *= sq1; }
+#pragma unroll
+                    for (int u = 0; u < 6; ++u) qb.Jc[r][u] *= sq1;
+                }
+            }
             double Xb[3];
             cbar[i] += point_terms_reverse(Rt, X + 3 * i, k0[2 * i], k0[2 * i + 1], k1[2 * i], k1[2 * i + 1], c, qb, Xb, g);
             Xbar[3 * i] = xb[0] + Xb[0];
@@ -881,6 +959,7 @@ __global__ __launch_bounds__(256) void ba2view_backward_kernel(BaBwdParams p) {
         double Rt[12], g[12];
 #pragma unroll
         for (int i = 0; i < 12; ++i) { Rt[i] = recs[i]; g[i] = 0.0; }
+        if constexpr (LOSS != kLossNone) t2[1] = abar;
         for (int i = tid; i < N; i += 256) {
             if (!(cf[i] > 0.f)) continue;
             triangulate_reverse(k0[2 * i], k0[2 * i + 1], k1[2 * i], k1[2 * i + 1], Rt, Xbar + 3 * i, g);
@@ -893,7 +972,10 @@ __global__ __launch_bounds__(256) void ba2view_backward_kernel(BaBwdParams p) {
     __syncthreads();
     if (p.gconf) {
         // weights c_i = conf_i / cden, cden = sum conf while 2 sum conf >= 1e-6 (a constant below that)
-        const double shift = 2.0 * csum >= 1e-6 ? t2[0] / cden : 0.0;
+        double shift = 2.0 * csum >= 1e-6 ? t2[0] / cden : 0.0;
+        if constexpr (LOSS != kLossNone) {  // the scale a = loss_scale / cden moves with the same denominator
+            if (2.0 * csum >= 1e-6) shift += t2[1] * la / cden;
+        }
         for (int i = tid; i < N; i += 256)
             p.gconf[(int64_t)b * N + i] = (kstar > 0 && cf[i] > 0.f) ? (float)(cbar[i] / cden - shift) : 0.f;
     }
@@ -905,32 +987,52 @@ __global__ __launch_bounds__(256) void ba2view_backward_kernel(BaBwdParams p) {
 
 }  // namespace e2emv
 
-extern "C" int e2emv_ba_2view_backward(e2emv_ctx* ctx, int B, int N, const float* d_kpts0n, const float* d_kpts1n, const float* d_conf,
-                                       const float* d_T_init, int n_iterations, const float* d_gT, float* d_gconf, float* d_gTinit,
-                                       void* stream) {
+// both entry points of the reverse pass; `who` names the caller in error texts
+static int ba2view_backward_run(e2emv_ctx* ctx, const char* who, int B, int N, const float* d_kpts0n, const float* d_kpts1n,
+                                const float* d_conf, const float* d_T_init, int n_iterations, int loss, double loss_scale, const float* d_gT,
+                                float* d_gconf, float* d_gTinit, void* stream) {
     if (!ctx || !d_kpts0n || !d_kpts1n || !d_conf || !d_T_init || !d_gT) return E2EMV_EINVAL;
     E2EMV_ENTER(ctx, stream);
-    if (B <= 0 || N <= 0 || n_iterations < 0) return set_err(ctx, E2EMV_ESHAPE, "ba_2view_backward: B=%d N=%d iterations=%d", B, N, n_iterations);
+    int rc = mv_check_loss(ctx, who, loss, &loss_scale);
+    if (rc) return rc;
+    if (B <= 0 || N <= 0 || n_iterations < 0) return set_err(ctx, E2EMV_ESHAPE, "%s: B=%d N=%d iterations=%d", who, B, N, n_iterations);
     if (!d_gconf && !d_gTinit) return E2EMV_OK;
     // doubles per pair: X tape (n + 1) N 3, X_bar N 3, c_bar N, records (n + 1) kBaRec - in size_t, and an overflow is an error
     const size_t evals = (size_t)n_iterations + 1, cap = ~(size_t)0 / sizeof(double);
     const size_t per_eval = (size_t)N * 3 + kBaRec;
     if (evals > (cap - (size_t)N * 4) / per_eval)
-        return set_err(ctx, E2EMV_ENOMEM, "ba_2view_backward: the tape of N=%d, %d iterations does not fit a size_t", N, n_iterations);
+        return set_err(ctx, E2EMV_ENOMEM, "%s: the tape of N=%d, %d iterations does not fit a size_t", who, N, n_iterations);
     const size_t stride = evals * per_eval + (size_t)N * 4;
     if ((size_t)B > (cap - 32) / stride)
-        return set_err(ctx, E2EMV_ENOMEM, "ba_2view_backward: the tape of B=%d N=%d, %d iterations does not fit a size_t", B, N, n_iterations);
-    int rc = ws_reserve(ctx, (size_t)B * stride * sizeof(double) + 256);
+        return set_err(ctx, E2EMV_ENOMEM, "%s: the tape of B=%d N=%d, %d iterations does not fit a size_t", who, B, N, n_iterations);
+    rc = ws_reserve(ctx, (size_t)B * stride * sizeof(double) + 256);
     if (rc) return rc;
-    BaBwdParams p{};
+    BaBwdLossParams p{};
     p.B = B; p.N = N; p.n_it = n_iterations;
     p.k0 = d_kpts0n; p.k1 = d_kpts1n; p.conf = d_conf; p.Tin = d_T_init; p.gT = d_gT; p.gconf = d_gconf; p.gTin = d_gTinit;
     p.ws = (double*)ctx->d_ws; p.stride = stride;
     p.lm_inc = 1.5f; p.lm_dec = 3.5f;
+    p.loss_scale = loss_scale;
     hipStream_t s = (hipStream_t)stream;
     prof_begin(ctx, PS_W8PT, s);
-    hipLaunchKernelGGL(ba2view_backward_kernel, dim3(B), dim3(256), 0, s, p);
+    if (loss == kLossHuber) hipLaunchKernelGGL(ba2view_backward_kernel<kLossHuber>, dim3(B), dim3(256), 0, s, p);
+    else if (loss == kLossCauchy) hipLaunchKernelGGL(ba2view_backward_kernel<kLossCauchy>, dim3(B), dim3(256), 0, s, p);
+    else hipLaunchKernelGGL(ba2view_backward_kernel<kLossNone>, dim3(B), dim3(256), 0, s, (const BaBwdParams&)p);
     prof_end(ctx, s);
     E2EMV_CHECK_LAUNCH(ctx, "ba2view_backward_kernel");
     return E2EMV_OK;
+}
+
+extern "C" int e2emv_ba_2view_backward(e2emv_ctx* ctx, int B, int N, const float* d_kpts0n, const float* d_kpts1n, const float* d_conf,
+                                       const float* d_T_init, int n_iterations, const float* d_gT, float* d_gconf, float* d_gTinit,
+                                       void* stream) {
+    return ba2view_backward_run(ctx, "ba_2view_backward", B, N, d_kpts0n, d_kpts1n, d_conf, d_T_init, n_iterations, E2EMV_LOSS_NONE, 0.0, d_gT,
+                                d_gconf, d_gTinit, stream);
+}
+
+extern "C" int e2emv_ba_2view_loss_backward(e2emv_ctx* ctx, int B, int N, const float* d_kpts0n, const float* d_kpts1n, const float* d_conf,
+                                            const float* d_T_init, int n_iterations, int loss, double loss_scale, const float* d_gT,
+                                            float* d_gconf, float* d_gTinit, void* stream) {
+    return ba2view_backward_run(ctx, "ba_2view_loss_backward", B, N, d_kpts0n, d_kpts1n, d_conf, d_T_init, n_iterations, loss, loss_scale, d_gT,
+                                d_gconf, d_gTinit, stream);
 }

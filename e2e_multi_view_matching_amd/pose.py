@@ -445,12 +445,14 @@ def _check_loss(loss, loss_scale):
 
 
 def run_bundle_adjust_2_view(kpts0_norm, kpts1_norm, confidence, init_T021, n_iterations, check_lu_info_strict=False,
-                             check_precond_strict=False, loss=None, loss_scale=None, return_summary=False):
+                             check_precond_strict=False, loss=None, loss_scale=None, return_summary=False, loss_backward=False):
     """``run_bundle_adjust_2_view`` (estimate_relative_pose.py:138-144): returns ``(refined T_021 of the valid samples
     [n_valid,4,4], valid_batch [B] bool)`` so that ``pred_T021[valid] = refined`` works as at ``eval_pairs.py:252-255``.
     Differentiable with respect to ``confidence`` and ``init_T021`` (``_Ba2ViewPose`` / ``e2emv_ba_2view_backward``: the exact reverse of
-    the LM loop; keypoints, lambda and the accept / reject decisions carry no gradient) - with ``loss=None`` only: a robust loss with a
-    graph requested raises ``NotImplementedError`` before any device call.
+    the LM loop; keypoints, lambda and the accept / reject decisions carry no gradient).  A robust loss with a graph requested raises
+    ``NotImplementedError`` before any device call unless ``loss_backward=True``: then ``T`` carries the graph of the robust loop
+    (``e2emv_ba_2view_loss`` / ``e2emv_ba_2view_loss_backward``: through the corrector and through the pair's scale, which moves with
+    the confidences).  ``loss_backward=True`` without a loss, or a value that is not a bool, is a ``ValueError``.
     The two ``*_strict`` flags only matter for singular systems, which the fp64 Schur solve reports the same way.
     ``loss``: ``None`` (default: the reference's squared loss, ``e2emv_ba_2view`` as always), "huber" or "cauchy"
     (``e2emv_ba_2view_loss``): a residual block is one observation - a match has one in each image -, the LM loop compares
@@ -463,10 +465,15 @@ def run_bundle_adjust_2_view(kpts0_norm, kpts1_norm, confidence, init_T021, n_it
     the start, best cost, number of evaluations that improved, the absolute scale used (0 without a loss); zero for an invalid
     sample."""
     code = _check_loss(loss, loss_scale)
+    if not isinstance(loss_backward, bool):
+        raise ValueError("loss_backward must be True or False, not {!r}".format(loss_backward))
+    if loss_backward and not code:
+        raise ValueError("loss_backward=True needs a loss: the squared loss (loss=None) has its backward pass without it")
     graph = torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in (confidence, init_T021))
-    if graph and code:
-        raise NotImplementedError("run_bundle_adjust_2_view: no backward pass through loss={!r}; the gradient exists for the squared "
-                                  "loss only (loss=None) - detach confidence and init_T021 to refine without a graph".format(loss))
+    if graph and code and not loss_backward:
+        raise NotImplementedError("run_bundle_adjust_2_view: loss={!r} with a graph: by default the gradient is that of the squared loss "
+                                  "only (loss=None) - pass loss_backward=True for the backward pass through the robust loss, or detach "
+                                  "confidence and init_T021 to refine without a graph".format(loss))
     dev = _dev_of(kpts0_norm, kpts1_norm, init_T021)
     ctx = _lib.context(dev)
     B, N = kpts0_norm.shape[:2]
@@ -474,7 +481,8 @@ def run_bundle_adjust_2_view(kpts0_norm, kpts1_norm, confidence, init_T021, n_it
     if graph:
         holder = []
         conf_in, T_in = confidence.reshape(B, -1), init_T021
-        To = _Ba2ViewPose.apply(conf_in, T_in, ctx, dev, k0, k1, int(n_iterations), bool(return_summary), holder)
+        To = _Ba2ViewPose.apply(conf_in, T_in, ctx, dev, k0, k1, int(n_iterations), bool(return_summary), holder, code,
+                                float(loss_scale) if code else 0.0)
         vb, summary = holder
         return (To[vb], vb, summary) if return_summary else (To[vb], vb)
     cf = _prep(confidence.reshape(B, -1), dev)
@@ -495,10 +503,11 @@ def run_bundle_adjust_2_view(kpts0_norm, kpts1_norm, confidence, init_T021, n_it
 class _Ba2ViewPose(torch.autograd.Function):
     """T [B,4,4] = two-view BA of every sample (an invalid one keeps its start): ``e2emv_ba_2view`` forward, ``e2emv_ba_2view_backward`` for
     dLoss/dconfidence and dLoss/dinit_T021.  ``holder`` receives ``valid_batch`` and the summary (or ``None``); the selection of the valid
-    samples stays a torch op on top."""
+    samples stays a torch op on top.  ``code``, ``loss_scale``: a robust loss (``LOSSES``) - then ``e2emv_ba_2view_loss`` forward and
+    ``e2emv_ba_2view_loss_backward`` backward; code 0 makes the calls above."""
 
     @staticmethod
-    def forward(fctx, conf, T_init, ctx, dev, k0, k1, n_iterations, want_summary, holder):
+    def forward(fctx, conf, T_init, ctx, dev, k0, k1, n_iterations, want_summary, holder, code=0, loss_scale=0.0):
         B, N = k0.shape[:2]
         cf, Ti = _prep(conf, dev), _prep(T_init, dev)
         To = torch.empty((B, 4, 4), dtype=torch.float32, device=dev)
@@ -506,31 +515,34 @@ class _Ba2ViewPose(torch.autograd.Function):
         summary = torch.empty((B, 4), dtype=torch.float64, device=dev) if want_summary else None
         head = (B, N, _lib.ptr(k0), _lib.ptr(k1), _lib.ptr(cf), _lib.ptr(Ti), n_iterations, _lib.ptr(To), _lib.ptr(valid))
         with torch.cuda.device(dev):
-            if want_summary:
-                ctx.call("e2emv_ba_2view_loss", *head, 0, 0.0, _lib.ptr(summary), _lib.stream_ptr(dev))
+            if code or want_summary:
+                ctx.call("e2emv_ba_2view_loss", *head, code, loss_scale if code else 0.0, _lib.ptr(summary), _lib.stream_ptr(dev))
             else:
                 ctx.call("e2emv_ba_2view", *head, _lib.stream_ptr(dev))
         holder.extend([valid.bool(), summary])
-        fctx.misc = (ctx, dev, n_iterations, conf.shape, conf.dtype, conf.device, T_init.dtype, T_init.device)
+        fctx.misc = (ctx, dev, n_iterations, conf.shape, conf.dtype, conf.device, T_init.dtype, T_init.device, code, loss_scale)
         fctx.save_for_backward(k0, k1, cf, Ti)
         return To
 
     @staticmethod
     def backward(fctx, gT):
         k0, k1, cf, Ti = fctx.saved_tensors
-        ctx, dev, n_iterations, cshape, cdtype, cdev, tdtype, tdev = fctx.misc
+        ctx, dev, n_iterations, cshape, cdtype, cdev, tdtype, tdev, code, loss_scale = fctx.misc
         B, N = k0.shape[:2]
         g = _prep(gT, dev)
         gconf = torch.empty((B, N), dtype=torch.float32, device=dev) if fctx.needs_input_grad[0] else None
         gTi = torch.empty((B, 4, 4), dtype=torch.float32, device=dev) if fctx.needs_input_grad[1] else None
+        head = (B, N, _lib.ptr(k0), _lib.ptr(k1), _lib.ptr(cf), _lib.ptr(Ti), n_iterations)
         with torch.cuda.device(dev):
-            ctx.call("e2emv_ba_2view_backward", B, N, _lib.ptr(k0), _lib.ptr(k1), _lib.ptr(cf), _lib.ptr(Ti), n_iterations, _lib.ptr(g),
-                     _lib.ptr(gconf), _lib.ptr(gTi), _lib.stream_ptr(dev))
+            if code:
+                ctx.call("e2emv_ba_2view_loss_backward", *head, code, loss_scale, _lib.ptr(g), _lib.ptr(gconf), _lib.ptr(gTi), _lib.stream_ptr(dev))
+            else:
+                ctx.call("e2emv_ba_2view_backward", *head, _lib.ptr(g), _lib.ptr(gconf), _lib.ptr(gTi), _lib.stream_ptr(dev))
         if gconf is not None:
             gconf = gconf.reshape(cshape).to(cdev, cdtype)
         if gTi is not None:
             gTi = gTi.to(tdev, tdtype)
-        return gconf, gTi, None, None, None, None, None, None, None
+        return gconf, gTi, None, None, None, None, None, None, None, None, None
 
 
 class _PoseLossTuple(torch.autograd.Function):
@@ -568,18 +580,22 @@ def _pose_loss_tuple_call(ctx, dev, P, B, T, Tgt):
     return l2
 
 
-def pose_loss_tuple(data, result, ba_iterations=0):
+def pose_loss_tuple(data, result, ba_iterations=0, ba_loss=None, ba_loss_scale=None):
     """The pose term of ``helpers.run_matcher`` (helpers.py:243-260) for ALL pairs of the tuple at once: per pair the target
     ``inv(pose_j) @ pose_i``, ``run_weighted_8_point(..., choose_closest=True)``, rotation plus translation-angle error, summed over the
     pairs.  Returns ``{"rot_loss", "transl_loss", "poses": {(i, j): T_021 [B,4,4]}}``; the two losses are 0-dim device tensors that
     carry the graph back to every ``conf_scores_{i}_{j}`` that requires grad.  A fixed number of device calls whatever the batch size,
     and no host synchronisation: P ``e2emv_relative_pose`` into one target buffer, ``e2emv_w8pt_tuple``, ``e2emv_pose_loss_tuple``
     forward; ``e2emv_pose_loss_tuple_backward`` and ``e2emv_w8pt_tuple_backward`` backward.  ``ba_iterations > 0``: the loss is taken
-    on the pose refined by the two-view bundle adjustment (squared loss) of all P*B samples in one call - the gathered confidences
+    on the pose refined by the two-view bundle adjustment of all P*B samples in one call - the gathered confidences
     (P ``e2emv_gather_matched``), ``mask_confidence`` with the positive-depth mask, ``e2emv_ba_2view`` / ``e2emv_ba_2view_backward``; a
-    sample with fewer than 7 usable matches keeps its w8pt pose and passes its gradient through.  ``ValueError`` before any device
-    call: fewer than 8 keypoints, images with different keypoint counts, a missing ``pose{t}``, a missing pair in ``result``, a
-    negative ``ba_iterations``."""
+    sample with fewer than 7 usable matches keeps its w8pt pose and passes its gradient through.  ``ba_loss``, ``ba_loss_scale``: the
+    loss of that refinement, with the meaning and the rules of ``run_bundle_adjust_2_view``'s ``loss`` and ``loss_scale`` (``None``, the
+    default: the squared loss, the calls above; "huber" or "cauchy": ``e2emv_ba_2view_loss`` / ``e2emv_ba_2view_loss_backward`` in their
+    place, the same number of calls) - wrong matches, which a matcher in training produces, pull the squared-loss refinement away
+    and with it the pose the term is taken on.  ``ValueError`` before any device call: fewer than 8 keypoints, images with different
+    keypoint counts, a missing ``pose{t}``, a missing pair in ``result``, a negative ``ba_iterations``, a bad ``ba_loss`` /
+    ``ba_loss_scale`` pair, a ``ba_loss`` with ``ba_iterations == 0``."""
     T = 0
     while "keypoints" + str(T) in data:
         T += 1
@@ -588,6 +604,9 @@ def pose_loss_tuple(data, result, ba_iterations=0):
     if isinstance(ba_iterations, bool) or int(ba_iterations) != ba_iterations or ba_iterations < 0:
         raise ValueError("ba_iterations must be a non-negative integer, not {!r}".format(ba_iterations))
     ba_iterations = int(ba_iterations)
+    ba_code = _check_loss(ba_loss, ba_loss_scale)
+    if ba_code and ba_iterations == 0:
+        raise ValueError("ba_loss={!r} needs ba_iterations > 0: without a refinement there is nothing it acts on".format(ba_loss))
     shapes = {tuple(data["keypoints" + str(t)].shape) for t in range(T)}
     if len(shapes) != 1:
         raise ValueError("pose_loss_tuple needs the same number of keypoints in every image, got {}".format(sorted(shapes)))
@@ -618,7 +637,7 @@ def pose_loss_tuple(data, result, ba_iterations=0):
             Tw, cf = solved
             cm = mask_confidence(cf, o["pos"].reshape(P * B, -1))
             Tp = _Ba2ViewPose.apply(cm, Tw.reshape(P * B, 4, 4), ctx, dev, o["k0n"].reshape(P * B, -1, 2), o["k1n"].reshape(P * B, -1, 2),
-                                    ba_iterations, False, [])
+                                    ba_iterations, False, [], ba_code, float(ba_loss_scale) if ba_code else 0.0)
         else:
             Tp = solved.reshape(P * B, 4, 4)
         l2 = _PoseLossTuple.apply(Tp, Tgt, ctx, dev, P, B) if graph else _pose_loss_tuple_call(ctx, dev, P, B, Tp, Tgt)

@@ -466,6 +466,17 @@ int e2emv_ba_2view_loss(e2emv_ctx* ctx, int B, int N, const float* d_kpts0n, con
 int e2emv_ba_2view_backward(e2emv_ctx* ctx, int B, int N, const float* d_kpts0n, const float* d_kpts1n, const float* d_conf,
                             const float* d_T_init, int n_iterations, const float* d_gT, float* d_gconf, float* d_gTinit,
                             void* stream);
+/* The reverse pass of e2emv_ba_2view_loss: e2emv_ba_2view_backward for a loop that ran with a robust loss.  loss and loss_scale are
+ * those of the forward call (checked the same way, same errors); the loop is replayed with them, so the accept / reject / skip
+ * decisions and k* are the forward's.  The step that is reversed solves the CORRECTED system, and the adjoint goes on through
+ * the corrector - sqrt(rho'(s)) of each observation block depends on the block's residual and on the pair's scale - and through
+ * the scale itself: a_b = loss_scale / cden_b moves with the confidences, and every row with d_conf > 0 receives that term
+ * (nothing where cden_b is the 1e-6 clamp).  rho, the costs that are compared, carries no gradient; Huber's kink s = a^2 takes the
+ * quadratic branch.  Same workspace, outputs (either may be NULL), shape, NULL and tape-overflow rules as e2emv_ba_2view_backward;
+ * E2EMV_LOSS_NONE is e2emv_ba_2view_backward, launch for launch and bit for bit.                                               */
+int e2emv_ba_2view_loss_backward(e2emv_ctx* ctx, int B, int N, const float* d_kpts0n, const float* d_kpts1n, const float* d_conf,
+                                 const float* d_T_init, int n_iterations, int loss, double loss_scale, const float* d_gT,
+                                 float* d_gconf, float* d_gTinit, void* stream);
 
 /* The global initialisation on the DEVICE (csrc/mvinit_device.hip): the solver of e2emv_mv_init with the same options,
  * fp64, one wave per problem, the problem and its working set in LDS; a problem's result depends on neither its

@@ -1,11 +1,12 @@
-"""Timing of the two-view bundle adjustment and of its backward pass (``e2emv_ba_2view`` / ``e2emv_ba_2view_backward``) on synthetic pairs:
+"""Timing of the two-view bundle adjustment and of its backward pass (``e2emv_ba_2view`` / ``e2emv_ba_2view_backward``; with ``--loss huber``
+or ``cauchy``: ``e2emv_ba_2view_loss`` / ``e2emv_ba_2view_loss_backward`` at the relative scale ``--loss-scale``) on synthetic pairs:
 points at depth 3..8 in front of both cameras, a pose perturbed by 0.06 rad / 0.1 as the start, 0.5 pixel (f = 600) of keypoint noise,
 confidences in (0.1, 1] with every seventh at 0.  Default shapes: 32 pairs x 1024 matches and 80 pairs x 2048 matches, 10 iterations.  Per
 shape one warm-up call of each entry (the workspace grows there), then --reps timed calls of each, alternating, each between two events
 on the stream.  Prints one JSON line: median / min / max in milliseconds per shape and entry, and the fraction of pairs whose result
 moved (a pair that stayed at its start has k* = 0 and no step to reverse).
 
-    python tools/bench_ba2view_backward.py [--shapes 32x1024,80x2048] [--iterations 10] [--reps 9]
+    python tools/bench_ba2view_backward.py [--shapes 32x1024,80x2048] [--iterations 10] [--reps 9] [--loss none|huber|cauchy] [--loss-scale 0.0016667]
 """
 import argparse
 import json
@@ -52,10 +53,13 @@ def main():
     ap.add_argument("--shapes", default="32x1024,80x2048")
     ap.add_argument("--iterations", type=int, default=10)
     ap.add_argument("--reps", type=int, default=9)
+    ap.add_argument("--loss", choices=["none", "huber", "cauchy"], default="none")
+    ap.add_argument("--loss-scale", type=float, default=1.0 / 600.0, help="relative scale of the loss: one pixel at f = 600")
     args = ap.parse_args()
+    code = {"none": 0, "huber": 1, "cauchy": 2}[args.loss]
     dev = torch.device("cuda", 0)
     ctx = _lib.context(dev)
-    out = {"iterations": args.iterations, "reps": args.reps, "shapes": {}}
+    out = {"iterations": args.iterations, "reps": args.reps, "loss": args.loss, "loss_scale": args.loss_scale if code else None, "shapes": {}}
     for shape in args.shapes.split(","):
         B, N = (int(x) for x in shape.split("x"))
         k0, k1, conf, Ti = (t.to(dev) for t in make_pairs(B, N, seed=B * 10007 + N))
@@ -67,12 +71,18 @@ def main():
         stream = _lib.stream_ptr(dev)
 
         def forward():
-            ctx.call("e2emv_ba_2view", B, N, _lib.ptr(k0), _lib.ptr(k1), _lib.ptr(conf), _lib.ptr(Ti), args.iterations, _lib.ptr(To),
-                     _lib.ptr(valid), stream)
+            head = (B, N, _lib.ptr(k0), _lib.ptr(k1), _lib.ptr(conf), _lib.ptr(Ti), args.iterations, _lib.ptr(To), _lib.ptr(valid))
+            if code:
+                ctx.call("e2emv_ba_2view_loss", *head, code, args.loss_scale, None, stream)
+            else:
+                ctx.call("e2emv_ba_2view", *head, stream)
 
         def backward():
-            ctx.call("e2emv_ba_2view_backward", B, N, _lib.ptr(k0), _lib.ptr(k1), _lib.ptr(conf), _lib.ptr(Ti), args.iterations, _lib.ptr(gT),
-                     _lib.ptr(gconf), _lib.ptr(gTi), stream)
+            head = (B, N, _lib.ptr(k0), _lib.ptr(k1), _lib.ptr(conf), _lib.ptr(Ti), args.iterations)
+            if code:
+                ctx.call("e2emv_ba_2view_loss_backward", *head, code, args.loss_scale, _lib.ptr(gT), _lib.ptr(gconf), _lib.ptr(gTi), stream)
+            else:
+                ctx.call("e2emv_ba_2view_backward", *head, _lib.ptr(gT), _lib.ptr(gconf), _lib.ptr(gTi), stream)
 
         times = {"forward": [], "backward": []}
         with torch.cuda.device(dev):
