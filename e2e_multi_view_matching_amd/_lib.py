@@ -192,6 +192,11 @@ SIGNATURES = {
     "e2emv_get_grad": (c_int, [c_void_p, c_char_p, c_void_p, c_int64, c_void_p]),
     "e2emv_train_set_batchnorm": (c_int, [c_void_p, c_int, ctypes.c_float]),
     "e2emv_train_running_update": (c_int, [c_void_p, c_int, ctypes.POINTER(ctypes.c_char_p), _PP, _PP, c_void_p]),
+    "e2emv_train_linear_backward": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
+                                            c_void_p, c_void_p, c_int, c_void_p]),
+    "e2emv_train_sinkhorn": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int64, c_float, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_void_p, c_void_p]),
+    "e2emv_train_attention_backward": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "e2emv_w8pt_backward": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "e2emv_pose_errors_backward": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "e2emv_w8pt_tuple_backward": (c_int, [c_void_p, c_int, c_int, c_int, _PP, _PP, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, _PP, c_void_p]),

@@ -173,6 +173,62 @@ static int bn_backward(e2emv_ctx* ctx, const BnCall& a, int calls, hipStream_t s
     return E2EMV_OK;
 }
 
+// ---- the unrolled Sinkhorn of one pair (M = N): B problems, S / alpha in `sk`; uv [b][t][{u, v}][N + 1], t = 0 .. iters ----
+// columns per workgroup of the column kernels: col_width 32 / 64 forces the instance, 0 = by the size of the grid
+static bool sk_col32(const e2emv_ctx* ctx, int B, int N, int col_width) {
+    if (col_width) return col_width == 32;
+    return (int64_t)B * ((N + 1 + 63) / 64) < ctx->num_cus;  // (64-column workgroups would not fill the chip)
+}
+// forward with a tape: u_t, v_t of every iteration into uv (uv[b][0] = zeros on entry), the log assignment into logZ [B][N+1][N+1]
+static int sinkhorn_tape_forward(e2emv_ctx* ctx, const SkT& sk, int B, int iters, float* uv, float* logZ, int col_width, hipStream_t s) {
+    const int N = sk.N;
+    const int64_t uvs = (int64_t)(iters + 1) * 2 * (N + 1);  // per problem
+    const bool col32 = sk_col32(ctx, B, N, col_width);
+    for (int it = 1; it <= iters; ++it) {
+        float* u_t = uv + (int64_t)it * 2 * (N + 1);
+        float* v_t = u_t + (N + 1);
+        const float* v_p = uv + (int64_t)(it - 1) * 2 * (N + 1) + (N + 1);
+        hipLaunchKernelGGL(skt_row_kernel, dim3((N + 1 + 3) / 4, B), dim3(256), 0, s, sk, v_p, u_t, uvs, uvs);
+        if (col32) hipLaunchKernelGGL((skt_col_kernel<32>), dim3((N + 1 + 31) / 32, B), dim3(1024), 0, s, sk, (const float*)u_t, v_t, uvs, uvs);
+        else hipLaunchKernelGGL((skt_col_kernel<64>), dim3((N + 1 + 63) / 64, B), dim3(1024), 0, s, sk, (const float*)u_t, v_t, uvs, uvs);
+    }
+    const float* u_T = uv + (int64_t)iters * 2 * (N + 1);
+    hipLaunchKernelGGL(skt_out_kernel, dim3(ew_grid((int64_t)(N + 1) * (N + 1)), B), dim3(256), 0, s, sk, u_T, u_T + (N + 1), uvs, uvs, logZ);
+    E2EMV_CHECK_LAUNCH(ctx, "sinkhorn training kernels");
+    return E2EMV_OK;
+}
+// reverse sweep over the tape: G = dLoss / dlogZ [B][N+1][N+1] -> dC [B][N+1][N+1] (written), *dalpha += its dustbin row and
+// column; du, dv, dv2: scratch [B][N + 1] each (du is left zeroed when iters > 0)
+static int sinkhorn_tape_backward(e2emv_ctx* ctx, const SkT& sk, int B, int iters, const float* uv, const float* G, float* dC, float* du, float* dv,
+                                  float* dv2, float* dalpha, int col_width, hipStream_t s) {
+    const int N = sk.N;
+    const int64_t uvs = (int64_t)(iters + 1) * 2 * (N + 1);
+    E2EMV_HIP(ctx, hipMemsetAsync(dv, 0, (size_t)B * (N + 1) * sizeof(float), s));
+    hipLaunchKernelGGL(skb_init_kernel, dim3((N + 1 + 3) / 4, B), dim3(256), 0, s, N, N, G, dC, du, dv, (int64_t)(N + 1), (int64_t)(N + 1));
+    float* dv_cur = dv;
+    float* dv_nxt = dv2;
+    const bool col32 = sk_col32(ctx, B, N, col_width);
+    for (int it = iters; it >= 1; --it) {
+        const float* u_t = uv + (int64_t)it * 2 * (N + 1);
+        const float* v_t = u_t + (N + 1);
+        const float* v_p = uv + (int64_t)(it - 1) * 2 * (N + 1) + (N + 1);
+        hipLaunchKernelGGL(skb_vhalf_kernel, dim3((N + 1 + 3) / 4, B), dim3(256), 0, s, sk, u_t, v_t, (const float*)dv_cur, du, dC, uvs, uvs, (int64_t)(N + 1));
+        if (col32) hipLaunchKernelGGL((skb_uhalf_kernel<32>), dim3((N + 1 + 31) / 32, B), dim3(1024), 0, s, sk, u_t, v_p, (const float*)du, dv_nxt, dC, uvs, uvs, (int64_t)(N + 1));
+        else hipLaunchKernelGGL((skb_uhalf_kernel<64>), dim3((N + 1 + 63) / 64, B), dim3(1024), 0, s, sk, u_t, v_p, (const float*)du, dv_nxt, dC, uvs, uvs, (int64_t)(N + 1));
+        E2EMV_HIP(ctx, hipMemsetAsync(du, 0, (size_t)B * (N + 1) * sizeof(float), s));
+        std::swap(dv_cur, dv_nxt);
+    }
+    E2EMV_CHECK_LAUNCH(ctx, "sinkhorn backward kernels");
+    hipLaunchKernelGGL(skb_alpha_kernel, dim3(B), dim3(256), 0, s, N, N, (const float*)dC, dalpha);
+    return E2EMV_OK;
+}
+static SkT sk_problem(const float* S, int64_t ldS, int N, float alpha) {
+    SkT sk{};
+    sk.S = S; sk.ldS = ldS; sk.M = N; sk.N = N; sk.alpha = alpha;
+    sk.norm = -logf((float)(2 * N)); sk.logM = logf((float)N); sk.logN = logf((float)N);
+    return sk;
+}
+
 }  // namespace e2emv
 
 using namespace e2emv;
@@ -574,8 +630,7 @@ extern "C" int e2emv_matcher_forward_train(e2emv_ctx* ctx, const e2emv_forward_d
     }
     // ---- scores, Sinkhorn (log domain, u_t / v_t of every iteration kept), log assignment ----
     const int64_t tuple_stride = (int64_t)T * n_rows * D;
-    SkT sk{};
-    sk.ldS = ldS; sk.M = N; sk.N = N; sk.alpha = t->bin_score; sk.norm = -logf((float)(2 * N)); sk.logM = logf((float)N); sk.logN = logf((float)N);
+    SkT sk = sk_problem(nullptr, ldS, N, t->bin_score);
     const int64_t uvs = (int64_t)(iters + 1) * 2 * (N + 1);  // per problem
     int pidx = 0;
     for (int j = 0; j < T; ++j)
@@ -590,19 +645,8 @@ extern "C" int e2emv_matcher_forward_train(e2emv_ctx* ctx, const e2emv_forward_d
             if ((rc = launch_gemm_nt(ctx, g, s))) return rc;
             sk.S = S;
             float* uv = t->t_uv + (int64_t)pidx * B * uvs;  // [b][t][{u, v}][N + 1]
-            const bool col32 = (int64_t)B * ((N + 1 + 63) / 64) < ctx->num_cus;  // (64-column workgroups would not fill the chip)
-            for (int it = 1; it <= iters; ++it) {
-                float* u_t = uv + (int64_t)it * 2 * (N + 1);
-                float* v_t = u_t + (N + 1);
-                const float* v_p = uv + (int64_t)(it - 1) * 2 * (N + 1) + (N + 1);
-                hipLaunchKernelGGL(skt_row_kernel, dim3((N + 1 + 3) / 4, B), dim3(256), 0, s, sk, v_p, u_t, uvs, uvs);
-                if (col32) hipLaunchKernelGGL((skt_col_kernel<32>), dim3((N + 1 + 31) / 32, B), dim3(1024), 0, s, sk, (const float*)u_t, v_t, uvs, uvs);
-                else hipLaunchKernelGGL((skt_col_kernel<64>), dim3((N + 1 + 63) / 64, B), dim3(1024), 0, s, sk, (const float*)u_t, v_t, uvs, uvs);
-            }
             if (!d_logZ[pidx]) return set_err(ctx, E2EMV_EINVAL, "matcher_forward_train: null logZ for pair %d", pidx);
-            const float* u_T = uv + (int64_t)iters * 2 * (N + 1);
-            hipLaunchKernelGGL(skt_out_kernel, dim3(ew_grid((int64_t)(N + 1) * (N + 1)), B), dim3(256), 0, s, sk, u_T, u_T + (N + 1), uvs, uvs, d_logZ[pidx]);
-            E2EMV_CHECK_LAUNCH(ctx, "sinkhorn training kernels");
+            if ((rc = sinkhorn_tape_forward(ctx, sk, B, iters, uv, d_logZ[pidx], 0, s))) return rc;
         }
     t->have_tape = true;
     return E2EMV_OK;
@@ -644,15 +688,14 @@ extern "C" int e2emv_conf_forward_train(e2emv_ctx* ctx, int pair, const int64_t*
     return E2EMV_OK;
 }
 
-// attention backward of one layer: d att [Mtot][D] -> dqkv [Mtot][3D] (zeroed here); P / dP: scratch [B*H][N][ldP] each
-static int attention_backward(e2emv_ctx* ctx, TrainState* t, int l, const float* datt, float* dqkv, float* Pb, float* dPb, hipStream_t s) {
-    const int B = t->B, T = t->T, N = t->N, n_rows = t->n_rows, D = t->model.desc_dim, H = t->model.num_heads;
-    const bool cross = t->layers[l].type != 0;
-    const float* qkv = t->t_qkv[l];
+// attention backward of one layer (head dim 64): qkv [B*T][n_rows][3D] (N valid rows per image), d att [B*T][n_rows][D] ->
+// dqkv [B*T][n_rows][3D] (zeroed here); P / dP: scratch [B*H][N][ldP] each, ldP = N keys per source image
+static int attention_backward(e2emv_ctx* ctx, int B, int T, int N, int n_rows, int D, int H, bool cross, const float* qkv, const float* datt, float* dqkv,
+                              float* Pb, float* dPb, hipStream_t s) {
     const int n_src = cross ? T - 1 : 1;
     const int64_t ldP = (int64_t)n_src * N;
     const int64_t img3 = (int64_t)n_rows * 3 * D, img1 = (int64_t)n_rows * D;
-    E2EMV_HIP(ctx, hipMemsetAsync(dqkv, 0, (size_t)t->Mtot * 3 * D * sizeof(float), s));
+    E2EMV_HIP(ctx, hipMemsetAsync(dqkv, 0, (size_t)B * T * n_rows * 3 * D * sizeof(float), s));
     int rc;
     for (int tq = 0; tq < T; ++tq) {
         auto src_of = [&](int si) { return !cross ? tq : (si < tq ? si : si + 1); };
@@ -738,8 +781,7 @@ extern "C" int e2emv_matcher_backward(e2emv_ctx* ctx, const float* const* d_dlog
     E2EMV_HIP(ctx, hipMemsetAsync(dmd, 0, (size_t)Mtot * D * sizeof(float), s));
     // ---- Sinkhorn reverse sweep and the score matrix, per pair ----
     const int64_t tuple_stride = (int64_t)T * n_rows * D;
-    SkT sk{};
-    sk.ldS = ldS; sk.M = N; sk.N = N; sk.alpha = t->bin_score; sk.norm = -logf((float)(2 * N)); sk.logM = logf((float)N); sk.logN = logf((float)N);
+    SkT sk = sk_problem(nullptr, ldS, N, t->bin_score);
     const int64_t uvs = (int64_t)(iters + 1) * 2 * (N + 1);
     const int64_t per = (int64_t)(N + 1) * (N + 1);
     int pidx = 0;
@@ -748,23 +790,7 @@ extern "C" int e2emv_matcher_backward(e2emv_ctx* ctx, const float* const* d_dlog
             if (!d_dlogZ[pidx]) continue;  // no gradient reaches this pair's scores
             sk.S = t->t_S + (int64_t)pidx * B * N * ldS;
             const float* uv = t->t_uv + (int64_t)pidx * B * uvs;
-            E2EMV_HIP(ctx, hipMemsetAsync(dv, 0, (size_t)B * (N + 1) * sizeof(float), s));
-            hipLaunchKernelGGL(skb_init_kernel, dim3((N + 1 + 3) / 4, B), dim3(256), 0, s, N, N, d_dlogZ[pidx], dC, du, dv, (int64_t)(N + 1), (int64_t)(N + 1));
-            float* dv_cur = dv;
-            float* dv_nxt = dv2;
-            const bool col32 = (int64_t)B * ((N + 1 + 63) / 64) < ctx->num_cus;
-            for (int it = iters; it >= 1; --it) {
-                const float* u_t = uv + (int64_t)it * 2 * (N + 1);
-                const float* v_t = u_t + (N + 1);
-                const float* v_p = uv + (int64_t)(it - 1) * 2 * (N + 1) + (N + 1);
-                hipLaunchKernelGGL(skb_vhalf_kernel, dim3((N + 1 + 3) / 4, B), dim3(256), 0, s, sk, u_t, v_t, (const float*)dv_cur, du, dC, uvs, uvs, (int64_t)(N + 1));
-                if (col32) hipLaunchKernelGGL((skb_uhalf_kernel<32>), dim3((N + 1 + 31) / 32, B), dim3(1024), 0, s, sk, u_t, v_p, (const float*)du, dv_nxt, dC, uvs, uvs, (int64_t)(N + 1));
-                else hipLaunchKernelGGL((skb_uhalf_kernel<64>), dim3((N + 1 + 63) / 64, B), dim3(1024), 0, s, sk, u_t, v_p, (const float*)du, dv_nxt, dC, uvs, uvs, (int64_t)(N + 1));
-                E2EMV_HIP(ctx, hipMemsetAsync(du, 0, (size_t)B * (N + 1) * sizeof(float), s));
-                std::swap(dv_cur, dv_nxt);
-            }
-            E2EMV_CHECK_LAUNCH(ctx, "sinkhorn backward kernels");
-            hipLaunchKernelGGL(skb_alpha_kernel, dim3(B), dim3(256), 0, s, N, N, (const float*)dC, gw + t->alpha);
+            if ((rc = sinkhorn_tape_backward(ctx, sk, B, iters, uv, d_dlogZ[pidx], dC, du, dv, dv2, gw + t->alpha, 0, s))) return rc;
             // scores = md_i md_j^T / sqrt(D):  d md_i += dS md_j / sqrt(D),  d md_j += dS^T md_i / sqrt(D)
             const float sc = 1.0f / sqrtf((float)D);
             GG g;
@@ -844,7 +870,7 @@ extern "C" int e2emv_matcher_backward(e2emv_ctx* ctx, const float* const* d_dlog
         if ((rc = wgrad(ctx, dcat + D, 2 * D, D, t->t_att[l], D, D, Mtot, gw + Lw.wm, D, s))) return rc;
         if ((rc = colsum(ctx, dcat + D, Mtot, D, 2 * D, gw + Lw.bm, s))) return rc;
         // att = attention(q|k|v)
-        if ((rc = attention_backward(ctx, t, l, datt, dqkv, Pb, dPb, s))) return rc;
+        if ((rc = attention_backward(ctx, B, T, N, n_rows, D, H, Lw.type != 0, t->t_qkv[l], datt, dqkv, Pb, dPb, s))) return rc;
         // q|k|v = Wqkv x_l + b
         if ((rc = dgrad(ctx, dqkv, 3 * D, 3 * D, W + Lw.wqkv, D, D, Mtot, dx, D, true, s))) return rc;
         if ((rc = wgrad(ctx, dqkv, 3 * D, 3 * D, t->t_x[l], D, D, Mtot, gw + Lw.wqkv, D, s))) return rc;
@@ -984,4 +1010,73 @@ extern "C" int e2emv_train_running_update(e2emv_ctx* ctx, int n, const char* con
     }
     E2EMV_CHECK_LAUNCH(ctx, "bn_running_kernel");
     return E2EMV_OK;
+}
+
+// ---- building blocks of the training path: one stage each, through the functions the forward / backward above call ----------
+// They need no committed model and no tape; their scratch is the context's workspace, a tape in the context is left alone.
+
+// y = x W^T + b over `rows` rows: wgrad, colsum and dgrad as e2emv_matcher_backward calls them for a dense layer
+extern "C" int e2emv_train_linear_backward(e2emv_ctx* ctx, int64_t rows, int n_out, int n_in, const float* d_dY, int64_t ldy, const float* d_X, int64_t ldx,
+                                           const float* d_W, int64_t ldw, float* d_dW, float* d_db, float* d_dX, int accumulate, void* stream) {
+    if (!ctx || !d_dY || !d_X || !d_W || !d_dW || !d_db) return E2EMV_EINVAL;
+    E2EMV_ENTER(ctx, stream);
+    if (rows < 1 || rows > (int64_t)64 * 65535 || n_out < 1 || n_in < 1 || n_out > 65535 * 64 || n_in > 65535 * 64)
+        return set_err(ctx, E2EMV_ESHAPE, "train_linear_backward: rows=%lld n_out=%d n_in=%d", (long long)rows, n_out, n_in);
+    if (ldy < n_out || ldx < n_in || ldw < n_in)
+        return set_err(ctx, E2EMV_ESHAPE, "train_linear_backward: a row stride is shorter than its row (ldy=%lld ldx=%lld ldw=%lld)", (long long)ldy,
+                       (long long)ldx, (long long)ldw);
+    (void)hipSetDevice(ctx->device);
+    hipStream_t s = (hipStream_t)stream;
+    int rc;
+    if ((rc = wgrad(ctx, d_dY, ldy, n_out, d_X, ldx, n_in, rows, d_dW, ldw, s))) return rc;
+    if ((rc = colsum(ctx, d_dY, rows, n_out, ldy, d_db, s))) return rc;
+    if (d_dX && (rc = dgrad(ctx, d_dY, ldy, n_out, d_W, ldw, n_in, rows, d_dX, ldx, accumulate != 0, s))) return rc;
+    return E2EMV_OK;
+}
+
+// the unrolled Sinkhorn of B problems of N x N scores with its tape, and (d_G given) the reverse sweep over that tape
+extern "C" int e2emv_train_sinkhorn(e2emv_ctx* ctx, int B, int N, const float* d_S, int64_t ldS, float alpha, int iters, int col_width, const float* d_G,
+                                    float* d_logZ, float* d_uv, float* d_dC, float* d_dalpha, void* stream) {
+    if (!ctx || !d_S || !d_logZ || (d_G && (!d_dC || !d_dalpha))) return E2EMV_EINVAL;
+    E2EMV_ENTER(ctx, stream);
+    if (B < 1 || B > 65535 || N < 1 || N > 2048 || ldS < N) return set_err(ctx, E2EMV_ESHAPE, "train_sinkhorn: B=%d N=%d ldS=%lld", B, N, (long long)ldS);
+    if (iters < 0) return set_err(ctx, E2EMV_EINVAL, "negative sinkhorn_iters");
+    if (col_width != 0 && col_width != 32 && col_width != 64) return set_err(ctx, E2EMV_EINVAL, "train_sinkhorn: col_width %d (0, 32 or 64)", col_width);
+    (void)hipSetDevice(ctx->device);
+    hipStream_t s = (hipStream_t)stream;
+    const size_t sz_uv = al256((size_t)B * (iters + 1) * 2 * (N + 1) * 4), sz_v = al256((size_t)B * (N + 1) * 4);
+    int rc = ws_reserve(ctx, sz_uv + 3 * sz_v);
+    if (rc) return rc;
+    char* w = ctx->d_ws;
+    auto take = [&](size_t bytes) { float* p = (float*)w; w += bytes; return p; };
+    float* uv = take(sz_uv);
+    float* du = take(sz_v);
+    float* dv = take(sz_v);
+    float* dv2 = take(sz_v);
+    E2EMV_HIP(ctx, hipMemsetAsync(uv, 0, sz_uv, s));  // (u_0 = v_0 = 0, as on the zeroed tape)
+    const SkT sk = sk_problem(d_S, ldS, N, alpha);
+    if ((rc = sinkhorn_tape_forward(ctx, sk, B, iters, uv, d_logZ, col_width, s))) return rc;
+    if (d_uv) E2EMV_HIP(ctx, hipMemcpyAsync(d_uv, uv, (size_t)B * (iters + 1) * 2 * (N + 1) * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (!d_G) return E2EMV_OK;
+    E2EMV_HIP(ctx, hipMemsetAsync(d_dalpha, 0, sizeof(float), s));
+    return sinkhorn_tape_backward(ctx, sk, B, iters, uv, d_G, d_dC, du, dv, dv2, d_dalpha, col_width, s);
+}
+
+// attention backward of one layer on q|k|v and d att of the tape's layout (n_rows = N rounded up to 128 rows per image)
+extern "C" int e2emv_train_attention_backward(e2emv_ctx* ctx, int B, int T, int N, int D, int H, int cross, const float* d_qkv, const float* d_datt,
+                                              float* d_dqkv, void* stream) {
+    if (!ctx || !d_qkv || !d_datt || !d_dqkv) return E2EMV_EINVAL;
+    E2EMV_ENTER(ctx, stream);
+    if (D <= 0 || H <= 0 || D != H * 64) return set_err(ctx, E2EMV_ESHAPE, "train_attention_backward: head dim must be 64 (D=%d H=%d)", D, H);
+    if (B < 1 || (int64_t)B * H > 65535 || T < 2 || T > E2EMV_MAX_TUPLE || N < 1 || N > 2048)
+        return set_err(ctx, E2EMV_ESHAPE, "train_attention_backward: batch=%d tuple_size=%d n_kpts=%d", B, T, N);
+    (void)hipSetDevice(ctx->device);
+    hipStream_t s = (hipStream_t)stream;
+    const int n_rows = (N + 127) / 128 * 128, n_src = cross ? T - 1 : 1;
+    const size_t sz_P = al256((size_t)B * H * N * n_src * N * 4);
+    int rc = ws_reserve(ctx, 2 * sz_P);
+    if (rc) return rc;
+    float* Pb = (float*)ctx->d_ws;
+    float* dPb = (float*)(ctx->d_ws + sz_P);
+    return attention_backward(ctx, B, T, N, n_rows, D, H, cross != 0, d_qkv, d_datt, d_dqkv, Pb, dPb, s);
 }

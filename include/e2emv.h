@@ -609,6 +609,30 @@ int e2emv_attention(e2emv_ctx* ctx, int B, int T, int n_rows, int n_valid, int D
 int e2emv_attention_v(e2emv_ctx* ctx, int B, int T, int n_rows, const int* n_valid_per_image, int D, int H,
                       const float* d_qkv, int cross, float* d_out, void* stream);
 
+/* Three stages of the training path (e2emv_matcher_forward_train / e2emv_matcher_backward, below) alone, each through the
+ * host function the product calls.  All fp32 device buffers.  None needs e2emv_train_commit; scratch is the context's
+ * workspace; a tape held by the context is left as it is.  Arguments the product cannot produce are E2EMV_ESHAPE /
+ * E2EMV_EINVAL before any launch.
+ *
+ * Backward of a dense layer y = x W^T + b over `rows` rows: d_dY [rows][ldy] (n_out columns used), d_X [rows][ldx] (n_in
+ * used), d_W [n_out][ldw].  d_dW [n_out][ldw] += dY^T X and d_db [n_out] += column sums of dY (the caller zeroes both, as the
+ * backward zeroes its gradient arena); d_dX (optional) [rows][ldx] = dY W, added to when accumulate != 0. */
+int e2emv_train_linear_backward(e2emv_ctx* ctx, int64_t rows, int n_out, int n_in, const float* d_dY, int64_t ldy,
+                                const float* d_X, int64_t ldx, const float* d_W, int64_t ldw, float* d_dW, float* d_db,
+                                float* d_dX, int accumulate, void* stream);
+/* The unrolled log-domain Sinkhorn with its tape, B problems of N x N scores d_S [B][N][ldS] (N 1..2048, ldS >= N), dustbin
+ * score alpha: d_logZ [B][N+1][N+1]; d_uv (optional) [B][iters+1][2][N+1] = u_t, v_t of every iteration (t = 0: zeros).
+ * With d_G = dLoss / dlogZ [B][N+1][N+1] also the reverse sweep: d_dC [B][N+1][N+1] = dLoss / d couplings (its dustbin row
+ * and column included) and d_dalpha [1] = their sum over all problems.  col_width: columns per workgroup of the two column
+ * kernels, 32 or 64; 0 = the product's rule (64 once B * ceil((N+1)/64) workgroups fill the chip). */
+int e2emv_train_sinkhorn(e2emv_ctx* ctx, int B, int N, const float* d_S, int64_t ldS, float alpha, int iters, int col_width,
+                         const float* d_G, float* d_logZ, float* d_uv, float* d_dC, float* d_dalpha, void* stream);
+/* Backward of e2emv_attention (head dim 64: D = 64 H): d_qkv [B*T][n_rows][3D] and d_datt = dLoss / d out [B*T][n_rows][D]
+ * with n_rows = N rounded up to a multiple of 128, N (1..2048) valid rows per image, T in 2..E2EMV_MAX_TUPLE ->
+ * d_dqkv [B*T][n_rows][3D]; rows N..n_rows of an image are not read and come back as zeros. */
+int e2emv_train_attention_backward(e2emv_ctx* ctx, int B, int T, int N, int D, int H, int cross, const float* d_qkv,
+                                   const float* d_datt, float* d_dqkv, void* stream);
+
 /* The SuperPoint detector tail alone, on a score map the caller supplies: simple_nms -> threshold -> border removal -> top-k,
  * and (if d_dense is given) the descriptor sampling - the kernels, launch geometry and order e2emv_superpoint_forward runs
  * behind its detector and descriptor heads.  desc as for forward (height, width = size of the score map: multiples of 8, at

@@ -325,13 +325,11 @@ def test_pose_error_gradients(gpu):
         assert float((a.grad.cpu().double() - a_ref.grad).abs().max()) < 1e-5 * float(a_ref.grad.abs().max())
 
 
-def test_pose_loss_gradients_end_to_end(gpu):
-    """Stage-2 training step (helpers.run_matcher with opt.pose_loss, helpers.py:243-260): match loss on the scores + a pose loss
-    on run_weighted_8_point's pose, whose confidences come from conf_mlp on the matched descriptors.  Gradients of EVERY
-    parameter (conf_mlp included) against autograd through the oracle (matcher in fp32, weighted 8-point in fp64).
-    Weights: identity-like (real matches, a well-posed 8-point problem) plus a perturbation so that no gradient vanishes."""
+def _pose_loss_reference(B, N, data_seed=9, dtype=torch.float32):
+    """The CPU half of the stage-2 step below (no GPU needed): model, inputs and the oracle's loss and gradients, the matcher in
+    `dtype` (fp32: the reference the device is held to; fp64: what that reference is itself measured against), the weighted
+    8-point solve in fp64."""
     from e2e_multi_view_matching_amd import MultiViewMatcher
-    import e2e_multi_view_matching_amd as E
     from e2e_multi_view_matching_amd.synthetic import identity_like_state, make_tuples
     from oracle.matcher import matcher_forward
     from oracle import w8pt as OW
@@ -344,8 +342,7 @@ def test_pose_loss_gradients_end_to_end(gpu):
         g = torch.Generator().manual_seed(22)
         for _, prm in model.named_parameters():
             prm.add_(torch.randn(prm.shape, generator=g) * (0.01 if prm.dim() > 1 else 0.005))
-    B, N = 2, 256
-    data = make_tuples(batch=B, tuple_size=2, n_kpts=N, seed=9)
+    data = make_tuples(batch=B, tuple_size=2, n_kpts=N, seed=data_seed)
     idx, w = _targets(B, N, 900)
     Wr = torch.randn(B, 3, 4, generator=torch.Generator().manual_seed(23))
     # the 8-point solve sees camera coordinates made ONCE in fp32 (identical numbers on both sides) and identity intrinsics
@@ -361,20 +358,34 @@ def test_pose_loss_gradients_end_to_end(gpu):
         W = Wr.to(T.device).double()
         return (T[:, :3, :] * W).sum() + ((T[:, :3, :] - 0.3) ** 2 * W.flip(1)).sum()
 
-    # ---- oracle ----
-    sd = {k: v.clone() for k, v in model.state_dict().items()}
+    cast = lambda v: v.to(dtype) if torch.is_tensor(v) and v.is_floating_point() else v
+    sd = {k: cast(v.clone()) for k, v in model.state_dict().items()}
     leaves = {k: sd[k].requires_grad_(True) for k, _ in model.named_parameters()}
     ocfg = dict(model.config)
     ocfg.update(full_output=True, grad=True)
     for k in ("mfma_precision", "autograd", "check_finite"):
         ocfg.pop(k, None)
-    ref = matcher_forward(data, sd, ocfg)
+    ref = matcher_forward({k: cast(v) for k, v in data.items()}, sd, ocfg)
     res64 = {"matches0_0_1": ref["matches0_0_1"], "conf_scores_0_1": ref["conf_scores_0_1"].double()}
     T_ref, _ = OW.run_weighted_8_point({k: (v.double() if torch.is_tensor(v) else v) for k, v in pose_in.items()}, res64, 0, 1,
                                        choose_closest=True, target_T_021=Tgt.double())
     loss_ref = _match_loss(ref["scores_0_1"], idx, w).double() + 5.0 * pose_term(T_ref)
     loss_ref.backward()
-    # ---- product ----
+    return dict(model=model, data=data, idx=idx, w=w, pose_in=pose_in, Tgt=Tgt, pose_term=pose_term, leaves=leaves, ref=ref, T_ref=T_ref,
+                loss_ref=loss_ref)
+
+
+def _pose_loss_end_to_end(gpu, B, N, data_seed=9):
+    """Stage-2 training step (helpers.run_matcher with opt.pose_loss, helpers.py:243-260): match loss on the scores + a pose loss
+    on run_weighted_8_point's pose, whose confidences come from conf_mlp on the matched descriptors.  Gradients of EVERY
+    parameter (conf_mlp included) against autograd through the oracle (matcher in fp32, weighted 8-point in fp64).
+    Weights: identity-like (real matches, a well-posed 8-point problem) plus a perturbation so that no gradient vanishes.
+    B tuples of N keypoints per image from make_tuples(seed=data_seed) (tests/test_gpu_train_blocks.py runs it at a keypoint count
+    that is no multiple of 128)."""
+    import e2e_multi_view_matching_amd as E
+    r = _pose_loss_reference(B, N, data_seed)
+    model, data, idx, w, pose_in, Tgt, pose_term = (r[k] for k in ("model", "data", "idx", "w", "pose_in", "Tgt", "pose_term"))
+    leaves, ref, T_ref, loss_ref = (r[k] for k in ("leaves", "ref", "T_ref", "loss_ref"))
     model = model.to(gpu).train()
     out = model({k: (v.to(gpu) if torch.is_tensor(v) else v) for k, v in data.items()})
     assert torch.equal(out["matches0_0_1"].cpu(), ref["matches0_0_1"]) and int((ref["matches0_0_1"] >= 0).sum()) > 0.3 * B * N
@@ -389,6 +400,12 @@ def test_pose_loss_gradients_end_to_end(gpu):
     assert any(k.startswith("conf_mlp.") for k in worst)
     # the pose term reached the network: without it the conf head gets exactly zero
     assert all(float(p.grad.abs().max()) > 0 for k, p in model.named_parameters() if k.startswith("conf_mlp."))
+    return out, ref
+
+
+def test_pose_loss_gradients_end_to_end(gpu):
+    """The stage-2 step at two pairs of 256 keypoints."""
+    _pose_loss_end_to_end(gpu, B=2, N=256)
 
 
 def test_stage2_step_the_way_run_matcher_drives_it(gpu):
