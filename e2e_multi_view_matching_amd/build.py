@@ -11,7 +11,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libe2emv.so")
-SOURCES = ["ctx.hip", "weights.hip", "gemm.hip", "attention.hip", "gemm3.hip", "gemm_x3.hip", "gemm_h2.hip", "gemm_p2.hip", "gemm_p2c.hip", "attention_p2.hip", "attention_p2w.hip", "p2_tools.hip", "kenc_fused.hip", "attention3.hip", "split3_api.hip", "sinkhorn.hip", "sinkhorn_stream.hip", "sinkhorn_resident.hip", "sinkhorn_regs.hip", "sinkhorn_regs2.hip", "pose.hip", "ba2view.hip", "gtmatch.hip",
+SOURCES = ["ctx.hip", "weights.hip", "gemm.hip", "attention.hip", "gemm_x3.hip", "gemm_h2.hip", "gemm_p2.hip", "gemm_p2c.hip", "attention_p2.hip", "attention_p2w.hip", "p2_tools.hip", "kenc_fused.hip", "attention_x3.hip", "attention_h2.hip", "split3_api.hip", "sinkhorn.hip", "sinkhorn_stream.hip", "sinkhorn_resident.hip", "sinkhorn_regs.hip", "sinkhorn_regs2.hip", "pose.hip", "ba2view.hip", "gtmatch.hip",
            "mvinit.hip", "mvinit_device.hip", "mvba.hip", "mvba_backward.hip", "mvtracks.hip", "mvransac.hip", "ransac.hip", "superpoint.hip", "forward.hip", "train.hip", "optim.hip", "image_front.hip", "image_front_pairs.hip", "comm.hip"]
 # (one build: every kernel in these files is part of the product library; measurements and probes live in standalone files under tools/)
 # The kernels of this file keep most of their data in registers they address by number, outside the window their amdgpu_num_vgpr

@@ -21,6 +21,7 @@
 #include <algorithm>
 #include <cstdlib>
 
+#include "attention_walk.h"
 #include "common.h"
 
 namespace e2emv {
@@ -33,12 +34,9 @@ constexpr int ATT_KV = 64;   // keys per LDS tile
 constexpr int HD = 64;       // head dim
 constexpr int KLD = 68;      // padded K row (floats)
 
-struct AttnParams {
+struct AttnParams : AttnShape {
     const float* qkv;
     float* out;
-    int B, T, n_rows, D, H, cross;
-    int nv[E2EMV_MAX_TUPLE];  // valid keypoints (queries and keys) of image t of a tuple
-    int nq, groups, gper;
     // key-split mode (small problems): split sp of ksplit handles a slice of the key tiles and writes UNNORMALISED partial
     // outputs + (running max, sum) per query; attention_merge_kernel folds them
     int ksplit;
@@ -51,17 +49,12 @@ __global__ __launch_bounds__(256, 3) void attention_kernel(AttnParams p) {
     __shared__ __attribute__((aligned(16))) float Ks[ATT_KV * KLD];
     __shared__ __attribute__((aligned(16))) float Vs[ATT_KV * HD];
 
-    // XCD-aware mapping: all query tiles of one (image, head) share an XCD (K/V stay in its L2)
+    // key split: the ksplit parts of an item are neighbours on its XCD
     const int lin = blockIdx.x;
-    const int xcd = lin & 7;
     const int sp = SPLIT ? (lin >> 3) % p.ksplit : 0;
-    const int idx = SPLIT ? (lin >> 3) / p.ksplit : lin >> 3;
-    const int g = xcd * p.gper + idx / p.nq;
-    if (g >= p.groups) return;
-    const int qt = idx % p.nq;
-    const int img = g / p.H, head = g % p.H;
-    const int b = img / p.T, t = img % p.T;
-    if (qt * ATT_Q >= p.nv[t]) return;  // shorter image of a ragged tuple: no queries in this tile
+    const AttnItem it = attn_item(p, SPLIT ? ((lin >> 3) / p.ksplit) << 3 | (lin & 7) : lin, ATT_Q);
+    if (!it.live) return;
+    const int qt = it.qt, img = it.img, head = it.head, b = it.b, t = it.t;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l31 = lane & 31, lh = lane >> 5;
@@ -86,29 +79,16 @@ __global__ __launch_bounds__(256, 3) void attention_kernel(AttnParams p) {
     for (int r = 0; r < 16; ++r) { O0[r] = 0.f; O1[r] = 0.f; }
     float m_run = -1e30f, l_run = 0.f;
 
-    const int n_src = p.cross ? p.T - 1 : 1;
-    auto src_t = [&](int si) { return !p.cross ? t : (si < t ? si : si + 1); };
-    int n_tiles = 0;
-    for (int si = 0; si < n_src; ++si) n_tiles += (p.nv[src_t(si)] + ATT_KV - 1) / ATT_KV;
-    // linear key-tile index -> (source image of the tuple, tile inside it); sources may differ in length
-    auto locate = [&](int tile, int& tt, int& kt) {
-        int si = 0;
-        for (;; ++si) {
-            const int n = (p.nv[src_t(si)] + ATT_KV - 1) / ATT_KV;
-            if (tile < n || si + 1 == n_src) break;
-            tile -= n;
-        }
-        tt = src_t(si);
-        kt = tile;
-    };
+    using Walk = AttnKeyWalk<ATT_KV>;
+    const Walk walk(p, t);
+    const int n_tiles = walk.n_tiles;
 
     // staging map: 4 float4 of K and of V per thread
     const int st_row = tid >> 4;         // 0..15 (+16*i)
     const int st_c4 = (tid & 15) * 4;
     f32x4 rk[4], rv[4];
-    auto gload = [&](int tile) {
-        int tt, kt;
-        locate(tile, tt, kt);
+    auto gload = [&](const Walk::Pos& tp) {
+        const int tt = walk.src(tp.si), kt = tp.kt;
         const float* base = p.qkv + (b * p.T + tt) * img_stride + (int64_t)(kt * ATT_KV) * row_stride + head * HD + st_c4;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -120,7 +100,8 @@ __global__ __launch_bounds__(256, 3) void attention_kernel(AttnParams p) {
 
     const int tile_lo = SPLIT ? (int)((int64_t)n_tiles * sp / p.ksplit) : 0;
     const int tile_hi = SPLIT ? (int)((int64_t)n_tiles * (sp + 1) / p.ksplit) : n_tiles;
-    if (tile_lo < tile_hi) gload(tile_lo);
+    Walk::Pos cur{0, 0}, nxt = SPLIT ? walk.at(tile_lo) : Walk::Pos{0, 0};
+    if (tile_lo < tile_hi) gload(nxt);
     for (int tile = tile_lo; tile < tile_hi; ++tile) {
         __syncthreads();  // everyone is done reading the previous tile
 #pragma unroll
@@ -129,11 +110,12 @@ __global__ __launch_bounds__(256, 3) void attention_kernel(AttnParams p) {
             *reinterpret_cast<f32x4*>(&Vs[(st_row + 16 * i) * HD + st_c4]) = rv[i];
         }
         __syncthreads();
-        if (tile + 1 < tile_hi) gload(tile + 1);
-
-        int tt_cur, kt;
-        locate(tile, tt_cur, kt);
-        const int valid_in_tile = p.nv[tt_cur] - kt * ATT_KV;  // >= 1
+        cur = nxt;
+        if (tile + 1 < tile_hi) {
+            walk.advance(nxt);
+            gload(nxt);
+        }
+        const int valid_in_tile = walk.valid(cur);  // >= 1
 #pragma unroll
         for (int sub = 0; sub < 2; ++sub) {
             if (sub * 32 >= valid_in_tile) break;  // wave-uniform
@@ -234,36 +216,50 @@ __global__ __launch_bounds__(256) void attention_merge_kernel(AttnParams p) {
     *reinterpret_cast<f32x4*>(p.out + ((int64_t)img * p.n_rows + q) * p.D + head * HD + 4 * c4) = acc * (1.f / L);
 }
 
+int attn_shape(e2emv_ctx* ctx, const char* who, int B, int T, int n_rows, const int* nv, int D, int H, int cross, int q_tile,
+               AttnShape* out, int* n_valid) {
+    if (T < 1 || T > E2EMV_MAX_TUPLE) return set_err(ctx, E2EMV_EINVAL, "%s: T=%d images per tuple", who, T);
+    int nmax = 0;
+    for (int t = 0; t < T; ++t) {
+        if (nv[t] <= 0 || nv[t] > n_rows) return set_err(ctx, E2EMV_ESHAPE, "%s: image %d has %d keypoints (n_rows %d)", who, t, nv[t], n_rows);
+        nmax = std::max(nmax, nv[t]);
+    }
+    if (D != H * HD) return set_err(ctx, E2EMV_ESHAPE, "%s: head dim must be 64 (D=%d H=%d)", who, D, H);
+    if (n_rows % q_tile || nmax <= 0 || nmax > n_rows)
+        return set_err(ctx, E2EMV_ESHAPE, "%s: n_rows=%d must be a multiple of %d and >= n_valid=%d", who, n_rows, q_tile, nmax);
+    if (cross && T < 2) return set_err(ctx, E2EMV_ESHAPE, "%s: cross layer needs T >= 2", who);
+    out->B = B; out->T = T; out->n_rows = n_rows; out->D = D; out->H = H; out->cross = cross;
+    for (int t = 0; t < E2EMV_MAX_TUPLE; ++t) out->nv[t] = t < T ? nv[t] : 0;
+    out->nq = (nmax + q_tile - 1) / q_tile;
+    out->groups = B * T * H;
+    out->gper = (out->groups + 7) / 8;
+    *n_valid = nmax;
+    return E2EMV_OK;
+}
+
+int attn_min_tiles(const AttnShape& s, int KV) {
+    int min_tiles = 1 << 30;
+    for (int t = 0; t < s.T; ++t) {
+        int n = 0;
+        for (int u = 0; u < s.T; ++u)
+            if (s.cross ? u != t : u == t) n += (s.nv[u] + KV - 1) / KV;
+        min_tiles = std::min(min_tiles, n);
+    }
+    return min_tiles;
+}
+
 int launch_attention(e2emv_ctx* ctx, int B, int T, int n_rows, const int* nv, int D, int H, const float* qkv,
                      int cross, float* out, hipStream_t s) {
-    int n_valid = 0;
-    for (int t = 0; t < T; ++t) {
-        if (nv[t] <= 0 || nv[t] > n_rows) return set_err(ctx, E2EMV_ESHAPE, "attention: image %d has %d keypoints (n_rows %d)", t, nv[t], n_rows);
-        n_valid = std::max(n_valid, nv[t]);
-    }
-    if (D != H * HD) return set_err(ctx, E2EMV_ESHAPE, "attention: head dim must be 64 (D=%d H=%d)", D, H);
-    if (n_rows % ATT_Q || n_valid <= 0 || n_valid > n_rows)
-        return set_err(ctx, E2EMV_ESHAPE, "attention: n_rows=%d must be a multiple of %d and >= n_valid=%d", n_rows, ATT_Q, n_valid);
-    if (cross && T < 2) return set_err(ctx, E2EMV_ESHAPE, "attention: cross layer needs T >= 2");
     AttnParams p;
-    p.qkv = qkv; p.out = out; p.B = B; p.T = T; p.n_rows = n_rows; p.D = D; p.H = H;
-    for (int t = 0; t < E2EMV_MAX_TUPLE; ++t) p.nv[t] = t < T ? nv[t] : 0;
-    p.cross = cross;
-    p.nq = (n_valid + ATT_Q - 1) / ATT_Q;
-    p.groups = B * T * H;
-    p.gper = (p.groups + 7) / 8;
+    int n_valid;
+    if (int rc = attn_shape(ctx, "attention", B, T, n_rows, nv, D, H, cross, ATT_Q, &p, &n_valid)) return rc;
+    p.qkv = qkv; p.out = out;
     dim3 grid(8 * p.gper * p.nq);
     // Small problems (batch 1-2 of the reference's eval loop): one workgroup per (image, head, 128 queries) leaves most CUs
     // idle while each workgroup walks all key tiles serially.  Split the key tiles over up to 8 workgroups + a merge pass.
     p.ksplit = 1; p.part_o = nullptr; p.part_ml = nullptr;
     {
-        int min_tiles = 1 << 30;  // key tiles a query walks (smallest over the images)
-        for (int t = 0; t < T; ++t) {
-            int n = 0;
-            for (int u = 0; u < T; ++u)
-                if (cross ? u != t : u == t) n += (nv[u] + ATT_KV - 1) / ATT_KV;
-            min_tiles = std::min(min_tiles, n);
-        }
+        const int min_tiles = attn_min_tiles(p, ATT_KV);
         const int blocks = p.groups * p.nq;
         int ks = blocks * 2 <= ctx->num_cus ? ctx->num_cus / blocks : 1;
         ks = std::max(1, std::min(std::min(ks, 8), min_tiles));

@@ -1,6 +1,6 @@
 // Multi-head attention of the f16x2 arithmetic mode on PLANE operands (p2.h):  out = softmax(q k^T / sqrt(64)) v
 //
-// The arithmetic and the transposed flash structure are those of attention_h2f_kernel (attention3.hip: S^T = mfma(K, Q),
+// The arithmetic and the transposed flash structure are those of attention_h2f_kernel (attention_h2.hip: S^T = mfma(K, Q),
 // O^T += mfma(V^T, P^T), three fp16 products per block, lazy running maximum).  What changed is where the operands come
 // from: the q|k|v projection (gemm_p2.hip, P2_OUT_QKV) already wrote
 //   q | k   as plain planes [row][2D] (q pre-scaled by 2^6 log2(e)/8), one 256-byte piece per (row, head), and
@@ -31,14 +31,9 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attention_p2_kernel(
     constexpr int QT = 32 * NW;
     constexpr int LPW = 16 / NW;  // LDS-direct loads per wave, tile and operand
 
-    const int lin = blockIdx.x;
-    const int xcd = lin & 7, idx = lin >> 3;
-    const int g = xcd * p.gper + idx / p.nq;
-    if (g >= p.groups) return;
-    const int qt = idx % p.nq;
-    const int img = g / p.H, head = g % p.H;
-    const int b = img / p.T, t = img % p.T;
-    if (qt * QT >= p.nv[t]) return;  // shorter image of a ragged tuple: no queries in this tile
+    const AttnItem it = attn_item(p, blockIdx.x, QT);
+    if (!it.live) return;
+    const int qt = it.qt, img = it.img, head = it.head, b = it.b, t = it.t;
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -69,14 +64,9 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attention_p2_kernel(
     int e_o = 0;
     bool o_started = false;
 
-    const int n_src = p.cross ? p.T - 1 : 1;
-    auto src_t = [&](int si) { return !p.cross ? t : (si < t ? si : si + 1); };
-    int n_tiles = 0;
-    for (int si = 0; si < n_src; ++si) n_tiles += (p.nv[src_t(si)] + AP_KV - 1) / AP_KV;
-    struct TilePos { int si, kt; };
-    auto advance_pos = [&](TilePos& tp) {
-        if (++tp.kt * AP_KV >= p.nv[src_t(tp.si)] && tp.si + 1 < n_src) { ++tp.si; tp.kt = 0; }
-    };
+    using Walk = AttnKeyWalk<AP_KV>;
+    const Walk walk(p, t);
+    const int n_tiles = walk.n_tiles;
 
     // ---- loader: one load = 4 rows x 256 B; lane -> (row lane >> 4, LDS position lane & 15), source chunk = position ^ (row & 15)
     const __amdgpu_buffer_rsrc_t rsK = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(p.qk), 0, (int)p.qk_bytes, 0x00020000);
@@ -90,7 +80,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attention_p2_kernel(
         v_vo[i] = (unsigned)row * (unsigned)p.n_rows * 4u + c * 16u;
     }
     auto issue = [&](int buf, int tp_si, int tp_kt) {
-        const int tt = src_t(tp_si);
+        const int tt = walk.src(tp_si);
         const unsigned k_so = (unsigned)((b * p.T + tt) * p.n_rows + tp_kt * AP_KV) * row_b;
         const unsigned v_so = (unsigned)(((b * p.T + tt) * p.H + head) * AP_HD) * (unsigned)p.n_rows * 4u + (unsigned)tp_kt * 256u;
         char* dst = smem_ap + buf * AP_BUFB + wave * LPW * 1024;
@@ -111,12 +101,12 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attention_p2_kernel(
     auto fetch_e = [&](int si, int kt, int& ek, int& evv) {
         ek = 0; evv = 0;
         if (p.EQK && lane == 0) {
-            const int blk = ((b * p.T + src_t(si)) * p.n_rows + kt * AP_KV) >> 6;
+            const int blk = ((b * p.T + walk.src(si)) * p.n_rows + kt * AP_KV) >> 6;
             ek = p.EQK[blk * 8 + 4 + head];
             evv = p.EVt ? p.EVt[blk * 4 + head] : 0;
         }
     };
-    TilePos cur{0, 0}, nxt{0, 0};
+    Walk::Pos cur{0, 0}, nxt{0, 0};
     issue(0, nxt.si, nxt.kt);
     int ek_n = 0, ev_n = 0;
     fetch_e(nxt.si, nxt.kt, ek_n, ev_n);
@@ -127,13 +117,13 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attention_p2_kernel(
         cur = nxt;
         const int e_k = __builtin_amdgcn_readfirstlane(ek_n), e_v = __builtin_amdgcn_readfirstlane(ev_n);
         if (tile + 1 < n_tiles) {
-            advance_pos(nxt);
+            walk.advance(nxt);
             issue(buf ^ 1, nxt.si, nxt.kt);
             fetch_e(nxt.si, nxt.kt, ek_n, ev_n);
         }
         const char* Kt = smem_ap + buf * AP_BUFB;
         const char* Vt = Kt + AP_TILEB;
-        const int valid_in_tile = p.nv[src_t(cur.si)] - cur.kt * AP_KV;
+        const int valid_in_tile = walk.valid(cur);
         const float sinv = AP_SINV * p2_exp2i(e_q + e_k);
         if (p.EVt) {
             if (o_started && e_v != e_o) {
@@ -293,26 +283,16 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attention_p2_kernel(
 
 int launch_attention_p2(e2emv_ctx* ctx, int B, int T, int n_rows, const int* nv, int D, int H, const uint16_t* qk,
                         const uint16_t* vt, int cross, uint16_t* outp, hipStream_t s, const int* EQK, const int* EVt, int* EO) {
-    int n_valid = 0;
-    for (int t = 0; t < T; ++t) {
-        if (nv[t] <= 0 || nv[t] > n_rows) return set_err(ctx, E2EMV_ESHAPE, "attention_p2: image %d has %d keypoints (n_rows %d)", t, nv[t], n_rows);
-        n_valid = std::max(n_valid, nv[t]);
-    }
-    if (D != H * AP_HD || D != 256) return set_err(ctx, E2EMV_ESHAPE, "attention_p2: needs 4 heads of 64 (D=%d H=%d)", D, H);
-    if (n_rows % 128 || n_valid <= 0) return set_err(ctx, E2EMV_ESHAPE, "attention_p2: n_rows=%d must be a multiple of 128", n_rows);
-    if (cross && T < 2) return set_err(ctx, E2EMV_ESHAPE, "attention_p2: cross layer needs T >= 2");
+    AttnP2Params p{};
+    int n_valid;
+    if (int rc = attn_shape(ctx, "attention_p2", B, T, n_rows, nv, D, H, cross, 128, &p, &n_valid)) return rc;
+    if (D != 256) return set_err(ctx, E2EMV_ESHAPE, "attention_p2: needs 4 heads of 64 (D=%d H=%d)", D, H);
     if (!qk || !vt || !outp || (uintptr_t)qk % 16 || (uintptr_t)vt % 16 || (uintptr_t)outp % 16) return set_err(ctx, E2EMV_EINVAL, "attention_p2: null / unaligned buffer");
     const int64_t rows = (int64_t)B * T * n_rows;
     if (rows * 8 * D >= ((int64_t)1 << 31)) return set_err(ctx, E2EMV_ESHAPE, "attention_p2: q|k planes larger than 2 GB (32-bit byte offsets)");
-    AttnP2Params p{};
     p.qk = qk; p.vt = vt; p.out = outp;
     p.EQK = EQK; p.EVt = EVt; p.EO = EO;
     p.qk_bytes = (unsigned)(rows * 8 * D); p.vt_bytes = (unsigned)(rows * 4 * D);
-    p.B = B; p.T = T; p.n_rows = n_rows; p.D = D; p.H = H;
-    for (int t = 0; t < E2EMV_MAX_TUPLE; ++t) p.nv[t] = t < T ? nv[t] : 0;
-    p.cross = cross;
-    p.groups = B * T * H;
-    p.gper = (p.groups + 7) / 8;
     // above 256 keys: one wave per SIMD with the overlap of matrix and vector work written into the wave's instruction
     // stream (attention_p2w.hip, attn_p2_nw == 1 forces it); below, and for A/B runs (4 / 8), the two-waves-per-SIMD kernel here
     if (ctx->attn_p2_nw == 1 || (ctx->attn_p2_nw == 0 && n_valid > 256)) return launch_attention_p2w(ctx, p, n_valid, s);

@@ -779,13 +779,7 @@ int launch_attention_p2w(e2emv_ctx* ctx, AttnP2Params& p, int n_valid, hipStream
     // (R = 0: a pair or two per call) split the same way.
     const int n_items = 8 * p.gper * p.nq, cus = std::max(8, ctx->num_cus / 8 * 8);
     const int r = n_items % cus;
-    int min_tiles = 1 << 30;
-    for (int t = 0; t < p.T; ++t) {  // key tiles of the item with the fewest: a part must own at least one
-        int nt = 0;
-        for (int si = 0; si < p.T; ++si)
-            if (p.cross ? si != t : si == t) nt += (p.nv[si] + 63) / 64;
-        min_tiles = std::min(min_tiles, nt);
-    }
+    const int min_tiles = attn_min_tiles(p, 64);  // key tiles of the item with the fewest: a part must own at least one
     p.n_full = n_items;
     p.n_split = 1;
     p.part = nullptr;

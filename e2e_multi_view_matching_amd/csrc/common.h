@@ -219,17 +219,19 @@ int launch_gemm_nt(e2emv_ctx* ctx, const GemmArgs& a, hipStream_t s);
 int launch_attention(e2emv_ctx* ctx, int B, int T, int n_rows, const int* n_valid_img, int D, int H, const float* qkv,
                      int cross, float* out, hipStream_t s);
 
-// ---- bf16x3 split-operand path (gemm3.hip / gemm_x3.hip / attention3.hip): fp32-class accuracy on the bf16 pipe ----
-// "S3" = matrix stored as three bf16 planes per row: row r = [plane0 | plane1 | plane2], each ld wide.
-// gemm_x3.hip: fp32 activations (a.A / a.A2, a.bias, a.R, a.C, a.relu as for launch_gemm_nt) x pre-split weights W3 (S3 [N][3][ldw3])
-// h2_out_scale != 0 selects the fp16 x 2 form (gemm_h2.hip): W3 = fp16 planes [N][{hi, lo}][ldw3] of 2^s W, h2_out_scale = 2^-s
+// ---- split-operand paths on fp32 activations: fp32-class accuracy on the 16-bit matrix pipes ----
+// bf16x3 (split3.h; gemm_x3.hip / attention_x3.hip).  "S3" = matrix stored as three bf16 planes per row: row r = [plane0 |
+// plane1 | plane2], each ld wide.  gemm_x3.hip: fp32 activations (a.A / a.A2, a.bias, a.R, a.C, a.relu as for launch_gemm_nt)
+// x pre-split weights W3 (S3 [N][3][ldw3]).
+int launch_gemm_x3(e2emv_ctx* ctx, const GemmArgs& a, const uint16_t* W3, int64_t ldw3, hipStream_t s);
+// f16x2, the fp16 x 2 form (gemm_h2.hip / attention_h2.hip): WH = fp16 planes [N][{hi, lo}][ldw] of 2^s W, out_scale = 2^-s
 int launch_gemm_h2(e2emv_ctx* ctx, const GemmArgs& a, const uint16_t* WH, int64_t ldw, float out_scale, hipStream_t s);
-int launch_gemm_x3(e2emv_ctx* ctx, const GemmArgs& a, const uint16_t* W3, int64_t ldw3, hipStream_t s, float h2_out_scale = 0.f);
-int launch_split3(e2emv_ctx* ctx, const float* src, int64_t rows, int C, int64_t ld_src, uint16_t* dst, int64_t ld,
-                  hipStream_t s);
-// the same attention fed with the fp32 q|k|v matrix (planes produced inside the kernel)
+// launch_attention's contract in the two arithmetics: fp32 q|k|v in, the planes made inside the kernel
 int launch_attention3f(e2emv_ctx* ctx, int B, int T, int n_rows, const int* n_valid_img, int D, int H, const float* qkv,
-                       int cross, float* out32, hipStream_t s, bool h2 = false);
+                       int cross, float* out32, hipStream_t s);
+int launch_attention_h2f(e2emv_ctx* ctx, int B, int T, int n_rows, const int* n_valid_img, int D, int H, const float* qkv,
+                         int cross, float* out32, hipStream_t s);
+// the first-generation bf16x3 attention on pre-split planes (attention_x3.hip): a tested building block
 int launch_attention3(e2emv_ctx* ctx, int B, int T, int n_rows, const int* n_valid_img, int D, int H, const uint16_t* qk,
                       const uint16_t* vt, int cross, uint16_t* out3, float* out32, hipStream_t s);
 

@@ -134,7 +134,7 @@ static int round_up(int x, int m) { return (x + m - 1) / m * m; }
 // arithmetic of the GNN's dense contractions in one forward call
 enum class FwdMode {
     F32,           // fp32-MFMA kernels
-    BF16X3,        // fp32 activations, split into three bf16 planes in the consumer (gemm_x3.hip, attention3.hip)
+    BF16X3,        // fp32 activations, split into three bf16 planes in the consumer (gemm_x3.hip, attention_x3.hip)
     F16X2,         // fp32 activations, split into two fp16 planes in the consumer (gemm_h2.hip, attention_h2f)
     F16X2_PLANES,  // activations stored as two fp16 planes (p2.h; gemm_p2.hip, gemm_p2c.hip, attention_p2.hip)
 };
@@ -254,7 +254,7 @@ static GemmP2Args dense_gemm_p2(const DenseWeights& w, int M) {
 static int gemm_fp32_act(e2emv_ctx* ctx, const FwdPlan& p, const GemmArgs& g, const DenseWeights& w, hipStream_t s) {
     prof_begin(ctx, PS_GEMM, s);
     int rc;
-    if (p.f16x2() && w.wh) rc = launch_gemm_x3(ctx, g, w.wh, g.K, s, w.hs);
+    if (p.f16x2() && w.wh) rc = launch_gemm_h2(ctx, g, w.wh, g.K, w.hs, s);
     else if (p.mode == FwdMode::BF16X3 && w.w3) rc = launch_gemm_x3(ctx, g, w.w3, g.K, s);
     else rc = launch_gemm_nt(ctx, g, s);
     prof_end(ctx, s);
@@ -319,7 +319,8 @@ static int gnn_fp32_activations(e2emv_ctx* ctx, const FwdPlan& p, hipStream_t s)
         if ((rc = gemm_fp32_act(ctx, p, g, L.qkv, s))) return rc;
         prof_begin(ctx, PS_ATTN, s);
         if (p.mode == FwdMode::F32) rc = launch_attention(ctx, p.B, p.T, p.n_rows, p.Nt, D, p.H, p.qkv, L.type, p.att, s);
-        else rc = launch_attention3f(ctx, p.B, p.T, p.n_rows, p.Nt, D, p.H, p.qkv, L.type, p.att, s, p.mode == FwdMode::F16X2);
+        else if (p.mode == FwdMode::F16X2) rc = launch_attention_h2f(ctx, p.B, p.T, p.n_rows, p.Nt, D, p.H, p.qkv, L.type, p.att, s);
+        else rc = launch_attention3f(ctx, p.B, p.T, p.n_rows, p.Nt, D, p.H, p.qkv, L.type, p.att, s);
         prof_end(ctx, s);
         if (rc) return rc;
         // hidden = relu(BN(W0 [x | message] + b0))   (concat never materialised: two K segments; the second is the attention
@@ -503,7 +504,7 @@ static int conf_heads(e2emv_ctx* ctx, const FwdPlan& p, const SinkhornOut& so, f
                 prof_end(ctx, s);
                 GemmArgs c = dense_gemm(c0, B * n_rows);
                 c.A = gathered; c.lda = 2 * D; c.relu = true; c.C = chid; c.ldc = D;
-                prof_begin(ctx, PS_GEMM, s); rc = launch_gemm_x3(ctx, c, c0.wh, 2 * D, s, c0.hs); prof_end(ctx, s);
+                prof_begin(ctx, PS_GEMM, s); rc = launch_gemm_h2(ctx, c, c0.wh, 2 * D, c0.hs, s); prof_end(ctx, s);
                 if (rc) return rc;
             } else if (use_mlp) {
                 prof_begin(ctx, PS_CONF, s);

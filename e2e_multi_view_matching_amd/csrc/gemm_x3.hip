@@ -205,8 +205,7 @@ __global__ __launch_bounds__(256, 2) void gemm_x3_kernel(GemmX3Params p) {
     }
 }
 
-int launch_gemm_x3(e2emv_ctx* ctx, const GemmArgs& a, const uint16_t* W3, int64_t ldw3, hipStream_t s, float h2_out_scale) {
-    if (h2_out_scale != 0.f) return launch_gemm_h2(ctx, a, W3, ldw3, h2_out_scale, s);  // f16x2 planes: gemm_h2.hip
+int launch_gemm_x3(e2emv_ctx* ctx, const GemmArgs& a, const uint16_t* W3, int64_t ldw3, hipStream_t s) {
     if (a.M <= 0 || a.N <= 0 || a.K <= 0 || a.batch != 1) return set_err(ctx, E2EMV_ESHAPE, "gemm_x3: empty problem or batch != 1");
     const int K1 = a.A2 ? a.K1 : a.K;
     if (a.K % 32 || K1 % 32 || K1 > a.K || (K1 < a.K && !a.A2)) return set_err(ctx, E2EMV_ESHAPE, "gemm_x3: K=%d K1=%d must be multiples of 32", a.K, K1);

@@ -2,6 +2,7 @@
 // entry points that let tests and micro-benchmarks drive gemm_p2.hip / attention_p2.hip on plain fp32 buffers.
 #include <algorithm>
 
+#include "attention_walk.h"
 #include "p2.h"
 
 namespace e2emv {
@@ -362,8 +363,9 @@ static int attention_p2_entry(e2emv_ctx* ctx, int B, int T, int n_rows, const in
     E2EMV_ENTER(ctx, stream);
     if (B <= 0 || T <= 0 || T > E2EMV_MAX_TUPLE || n_rows <= 0 || n_rows % 128 || D != 256 || H != 4)
         return set_err(ctx, E2EMV_ESHAPE, "attention_p2: n_rows %% 128 == 0, D = 256, H = 4");
-    for (int t = 0; t < T; ++t)  // (the launcher checks this too: here before the helper kernels run)
-        if (nv[t] <= 0 || nv[t] > n_rows) return set_err(ctx, E2EMV_ESHAPE, "attention_p2: image %d has %d keypoints (n_rows %d)", t, nv[t], n_rows);
+    AttnShape shape;
+    int n_valid;  // (the launcher checks the shape too: here before the helper kernels run)
+    if (int rc = attn_shape(ctx, "attention_p2", B, T, n_rows, nv, D, H, flags & 1, 128, &shape, &n_valid)) return rc;
     hipStream_t s = (hipStream_t)stream;
     const int64_t M = (int64_t)B * T * n_rows;
     const size_t szQK = al256((size_t)M * 2 * D * 4), szV = al256((size_t)M * D * 4), szO = al256((size_t)M * D * 4);

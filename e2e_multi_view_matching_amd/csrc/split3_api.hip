@@ -1,16 +1,21 @@
-// Test/bench entry points of the bf16x3 building blocks on plain fp32 buffers: the split into S3 planes,
-// the V transpose and the merge back to fp32 are done here by small helper kernels so that the kernels of
-// gemm_x3.hip / attention3.hip can be checked in isolation against an fp64 reference.
+// Test/bench entry points of the bf16x3 / f16x2 building blocks on plain fp32 buffers, so that the kernels of gemm_x3.hip,
+// gemm_h2.hip, attention_x3.hip and attention_h2.hip can be checked in isolation against an fp64 reference.  The bf16x3 GEMM takes
+// its weights as S3 planes: the row splitter that makes them is here, next to the q|k|v splitter of the first-generation attention.
+#include "attention_walk.h"
 #include "common.h"
+#include "split3.h"
 
 namespace e2emv {
 
-__device__ __forceinline__ void split3h(float v, __bf16& a, __bf16& b, __bf16& c) {
-    a = (__bf16)v;
-    const float r1 = v - (float)a;
-    b = (__bf16)r1;
-    const float r2 = r1 - (float)b;
-    c = (__bf16)r2;
+// fp32 [rows][C] -> S3 [rows][3][ld]
+__global__ void split3_rows_kernel(const float* src, int64_t rows, int C, int64_t lds_, uint16_t* dst, int64_t ld) {
+    const int64_t r = blockIdx.x;
+    for (int c = threadIdx.x; c < C; c += blockDim.x) {
+        __bf16 a, b, d;
+        split3(src[r * lds_ + c], a, b, d);
+        __bf16* o = reinterpret_cast<__bf16*>(dst + r * 3 * ld);
+        o[c] = a; o[ld + c] = b; o[2 * ld + c] = d;
+    }
 }
 
 // qkv fp32 [rows][3D] -> qk S3 [rows][3][2D] (q scaled) + V^T [img][3][D][n_rows]
@@ -24,7 +29,7 @@ __global__ void split_qkv_kernel(const float* qkv, int n_rows, int D, float q_sc
         float v = src[c];
         if (c < D) v *= q_scale;
         __bf16 a, b, d;
-        split3h(v, a, b, d);
+        split3(v, a, b, d);
         if (c < 2 * D) {
             qo[c] = a; qo[2 * D + c] = b; qo[4 * D + c] = d;
         } else {
@@ -36,10 +41,12 @@ __global__ void split_qkv_kernel(const float* qkv, int n_rows, int D, float q_sc
     }
 }
 
-__global__ void merge3_kernel(const uint16_t* src, int64_t rows, int C, float* dst) {
-    const int64_t r = blockIdx.x;
-    const __bf16* s = reinterpret_cast<const __bf16*>(src + r * 3 * C);
-    for (int c = threadIdx.x; c < C; c += blockDim.x) dst[r * C + c] = ((float)s[2 * C + c] + (float)s[C + c]) + (float)s[c];
+static int launch_split3(e2emv_ctx* ctx, const float* src, int64_t rows, int C, int64_t ld_src, uint16_t* dst, int64_t ld,
+                         hipStream_t s) {
+    if (rows <= 0 || C <= 0) return E2EMV_OK;
+    hipLaunchKernelGGL(split3_rows_kernel, dim3((unsigned)rows), dim3(256), 0, s, src, rows, C, ld_src, dst, ld);
+    E2EMV_CHECK_LAUNCH(ctx, "split3_rows_kernel");
+    return E2EMV_OK;
 }
 
 }  // namespace e2emv
@@ -62,7 +69,7 @@ extern "C" int e2emv_gemm_bf16x3(e2emv_ctx* ctx, int M, int Nout, int K, const f
         GemmArgs g;
         g.M = M; g.N = Nout; g.K = K; g.K1 = K; g.A = d_A; g.lda = K; g.bias = d_bias; g.C = d_C; g.ldc = Nout; g.relu = (flags & 1) != 0;
         prof_begin(ctx, PS_GEMM, s);
-        rc = launch_gemm_x3(ctx, g, dw.wh, K, s, dw.hs);
+        rc = launch_gemm_h2(ctx, g, dw.wh, K, dw.hs, s);
         prof_end(ctx, s);
         return rc;
     }
@@ -84,29 +91,26 @@ static int attention_bf16x3_entry(e2emv_ctx* ctx, int B, int T, int n_rows, cons
     if (B <= 0 || T <= 0 || n_rows <= 0) return set_err(ctx, E2EMV_ESHAPE, "attention_bf16x3: empty problem");
     hipStream_t s = (hipStream_t)stream;
     const int64_t rows = (int64_t)B * T * n_rows;
-    if (T < 1 || T > E2EMV_MAX_TUPLE) return E2EMV_EINVAL;
-    for (int t = 0; t < T; ++t)  // (the launchers check this too: here before the helper kernels run)
-        if (nv[t] <= 0 || nv[t] > n_rows) return set_err(ctx, E2EMV_ESHAPE, "attention_bf16x3: image %d has %d keypoints (n_rows %d)", t, nv[t], n_rows);
-    int rc;
-    if (cross & 6) {  // the kernels of the forward pass: fp32 q|k|v in, planes made in the kernel (bit2: fp16 x 2 form)
-        E2EMV_HIP(ctx, hipMemsetAsync(d_out, 0, (size_t)rows * D * sizeof(float), s));
-        prof_begin(ctx, PS_ATTN, s);
-        rc = launch_attention3f(ctx, B, T, n_rows, nv, D, H, d_qkv, cross & 1, d_out, s, (cross & 4) != 0);
-        prof_end(ctx, s);
-        return rc;
+    AttnShape shape;
+    int n_valid;  // (the launchers check the shape too: here before the memset runs)
+    if (int rc = attn_shape(ctx, "attention_bf16x3", B, T, n_rows, nv, D, H, cross & 1, 128, &shape, &n_valid)) return rc;
+    uint16_t *qk = nullptr, *vt = nullptr;
+    if (!(cross & 6)) {  // the first-generation kernel: pre-split planes made here by a helper kernel
+        auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
+        const size_t sz_qk = al((size_t)rows * 3 * 2 * D * 2), sz_v = al((size_t)rows * 3 * D * 2);
+        if (int rc = ws_reserve(ctx, sz_qk + sz_v)) return rc;
+        qk = (uint16_t*)ctx->d_ws;
+        vt = (uint16_t*)(ctx->d_ws + sz_qk);
+        hipLaunchKernelGGL(split_qkv_kernel, dim3((unsigned)rows), dim3(256), 0, s, d_qkv, n_rows, D, 0.125f * 1.4426950408889634f, qk, vt);
+        E2EMV_CHECK_LAUNCH(ctx, "split_qkv_kernel");
     }
-    auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
-    const size_t sz_qk = al((size_t)rows * 3 * 2 * D * 2), sz_v = al((size_t)rows * 3 * D * 2);
-    rc = ws_reserve(ctx, sz_qk + sz_v);
-    if (rc) return rc;
-    uint16_t* qk = (uint16_t*)ctx->d_ws;
-    uint16_t* vt = (uint16_t*)(ctx->d_ws + sz_qk);
-    hipLaunchKernelGGL(split_qkv_kernel, dim3((unsigned)rows), dim3(256), 0, s, d_qkv, n_rows, D, 0.125f * 1.4426950408889634f, qk, vt);
     E2EMV_HIP(ctx, hipMemsetAsync(d_out, 0, (size_t)rows * D * sizeof(float), s));
     prof_begin(ctx, PS_ATTN, s);
-    rc = launch_attention3(ctx, B, T, n_rows, nv, D, H, qk, vt, cross & 1, nullptr, d_out, s);
+    int rc;  // bit2: the fp16 x 2 form, bit1: the forward pass's bf16x3 kernel (planes made in the kernel)
+    if (cross & 4) rc = launch_attention_h2f(ctx, B, T, n_rows, nv, D, H, d_qkv, cross & 1, d_out, s);
+    else if (cross & 2) rc = launch_attention3f(ctx, B, T, n_rows, nv, D, H, d_qkv, cross & 1, d_out, s);
+    else rc = launch_attention3(ctx, B, T, n_rows, nv, D, H, qk, vt, cross & 1, nullptr, d_out, s);
     prof_end(ctx, s);
-    E2EMV_CHECK_LAUNCH(ctx, "bf16x3 helper kernels");
     return rc;
 }
 

@@ -44,7 +44,7 @@ def _n_rows(nv):
 
 @functools.lru_cache(maxsize=2)
 def _case(B, nv, cross):
-    """(qkv, fp64 reference) of a case: made once, shared by the nine selections (which pytest runs back to back), never modified."""
+    """(qkv, fp64 reference) of a case: made once, shared by the selections (which pytest runs back to back), never modified."""
     T = len(nv)
     g = torch.Generator().manual_seed(1000 * T + sum(nv) + cross)
     qkv = torch.randn(B * T, _n_rows(nv), 3 * D, generator=g) * 1.5
@@ -152,6 +152,36 @@ def test_ragged_tuples_through_the_key_split_parts(gpu, nv, cross):
     d = ar.valid_error(split, whole, len(nv), nv)
     print(f"attention-edges key-split nv={nv} cross={cross}: {parts} parts, split - whole {d:.3e}")
     assert d < SPLIT_BAR, (nv, d)
+
+
+# ---------------------------------------------------------------------------------------------- 3b. the fp32 kernel's key split
+def _attention_parts(cus, B, nv, cross):
+    """(ks, [per image t: the (first, last + 1) key tile of each part]) of launch_attention (attention.hip), restated: workgroups of
+    128 queries per (image, head); fewer than half the CUs busy -> min(CUs / workgroups, 8, fewest key tiles of an image) parts,
+    part sp of an image with n tiles walks [n sp / ks, n (sp + 1) / ks)."""
+    T = len(nv)
+    tiles = [sum((nv[s] + 63) // 64 for s in range(T) if (s != t if cross else s == t)) for t in range(T)]
+    blocks = B * T * H * ((max(nv) + 127) // 128)
+    ks = max(1, min(cus // blocks if blocks * 2 <= cus else 1, 8, min(tiles)))
+    return ks, [[(n * sp // ks, n * (sp + 1) // ks) for sp in range(ks)] for n in tiles]
+
+
+# (nv, image t, tile a part must begin on, (source image, tile inside it) of that tile)
+ATTENTION_KEY_SPLIT = [((128, 64, 192), 0, 1, (2, 0)),   # t = 0: sources of 1 + 3 tiles; a part begins on the first tile of the second
+                       ((64, 320, 64), 0, 3, (1, 3))]    # t = 0: sources of 5 + 1 tiles; a part begins in the middle of the first
+
+
+@pytest.mark.parametrize("nv,t,tile,where", ATTENTION_KEY_SPLIT)
+def test_fp32_key_split_parts_begin_inside_the_walk(gpu, nv, t, tile, where):
+    """attention_kernel<SPLIT> finds the first tile of a part by a search over the sources and walks on from there with the
+    cursor the other kernels use: a part that begins exactly where a source begins, and one that begins inside a source."""
+    ks, parts = _attention_parts(torch.cuda.get_device_properties(gpu).multi_processor_count, 1, nv, 1)
+    print(f"attention-edges fp32 key split nv={nv}: {ks} parts, image {t}: {parts[t]}")
+    # precondition: on this device a part of image t begins on the tile the case is about (not on tile 0)
+    assert ks >= 2 and tile > 0 and tile in [lo for lo, _ in parts[t]], (nv, ks, parts[t])
+    sources = [(s, k) for s in range(len(nv)) if s != t for k in range((nv[s] + 63) // 64)]
+    assert sources[tile] == where, (nv, sources)
+    _check_accuracy(gpu, "attention", 1, nv, 1, tag="fp32-key-split")
 
 
 # ---------------------------------------------------------------------------------------------- 4. padding rows cannot leak
