@@ -239,6 +239,16 @@ int launch_attention3(e2emv_ctx* ctx, int B, int T, int n_rows, const int* n_val
 // element bb belongs to output group bb / group_batch (= the image pair of a tuple): each group
 // has its own dense logZ [group_batch][M+1][N+1] (optional) and match outputs.
 constexpr int kMaxGroups = E2EMV_MAX_TUPLE * (E2EMV_MAX_TUPLE - 1) / 2;
+// Pair q of a tuple, images i < j, in the order of every per-pair output: (0,1), (0,2), (1,2), (0,3), ... - j ascending, under
+// it i ascending; a T-tuple has T (T - 1) / 2 of them.  (Host side; the kernels have their own mv_pair_index / mr_pair.)
+struct TuplePair {
+    int i, j;
+};
+inline TuplePair tuple_pair(int q) {
+    int j = 1;
+    for (; q >= j; ++j) q -= j;
+    return {q, j};
+}
 struct SinkhornOut {
     int n_groups = 1;
     int group_batch = 0;  // 0: = B (single group)

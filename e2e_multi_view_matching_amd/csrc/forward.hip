@@ -429,37 +429,36 @@ static int match_pairs(e2emv_ctx* ctx, const FwdPlan& p, const e2emv_forward_des
     so.n_groups = p.P;
     so.group_batch = B;
     int rc;
-    int pidx = 0;
-    for (int j = 0; j < p.T; ++j)
-        for (int i = 0; i < j; ++i, ++pidx) {
-            const int Ni = p.Nt[i], Nj = p.Nt[j], ldj = round_up(Nj, 4);
-            GemmArgs g;
-            g.batch = B; g.M = Ni; g.N = Nj; g.K = D; g.K1 = D;
-            g.A = p.att + (int64_t)i * n_rows * D; g.lda = D; g.sA = tuple_stride;
-            g.W = p.att + (int64_t)j * n_rows * D; g.ldw = D; g.sW = tuple_stride;
-            g.C = p.S + pidx * pair_stride; g.ldc = ldj; g.sC = (int64_t)Ni * ldj;
-            g.scale = 1.0f / sqrtf((float)D);
-            prof_begin(ctx, PS_SCORE, s); rc = launch_gemm_nt(ctx, g, s); prof_end(ctx, s);
-            if (rc) return rc;
-            const bool want_conf = p.full && d_conf && d_conf[pidx];
-            SinkhornOut one;  // outputs of this pair: one group of B problems
-            one.logZ[0] = d_logZ ? d_logZ[pidx] : nullptr;
-            if (p.full) {
-                one.m0[0] = (d_m0 && d_m0[pidx]) ? d_m0[pidx] : (want_conf ? p.tmp_m0[pidx] : nullptr);
-                one.m1[0] = d_m1 ? d_m1[pidx] : nullptr;
-                one.ms0[0] = (d_ms0 && d_ms0[pidx]) ? d_ms0[pidx] : (want_conf ? p.tmp_ms0[pidx] : nullptr);
-                one.ms1[0] = d_ms1 ? d_ms1[pidx] : nullptr;
-            }
-            so.logZ[pidx] = one.logZ[0]; so.m0[pidx] = one.m0[0]; so.m1[pidx] = one.m1[0];
-            so.ms0[pidx] = one.ms0[0]; so.ms1[pidx] = one.ms1[0];
-            if (!p.uniform) {
-                prof_begin(ctx, PS_SINKHORN, s);
-                rc = launch_sinkhorn(ctx, B, Ni, Nj, p.S + pidx * pair_stride, ldj, ctx->bin_score, fd->sinkhorn_iters,
-                                     fd->match_threshold, one, p.skws, s);
-                prof_end(ctx, s);
-                if (rc) return rc;
-            }
+    for (int pidx = 0; pidx < p.P; ++pidx) {
+        const int i = tuple_pair(pidx).i, j = tuple_pair(pidx).j;
+        const int Ni = p.Nt[i], Nj = p.Nt[j], ldj = round_up(Nj, 4);
+        GemmArgs g;
+        g.batch = B; g.M = Ni; g.N = Nj; g.K = D; g.K1 = D;
+        g.A = p.att + (int64_t)i * n_rows * D; g.lda = D; g.sA = tuple_stride;
+        g.W = p.att + (int64_t)j * n_rows * D; g.ldw = D; g.sW = tuple_stride;
+        g.C = p.S + pidx * pair_stride; g.ldc = ldj; g.sC = (int64_t)Ni * ldj;
+        g.scale = 1.0f / sqrtf((float)D);
+        prof_begin(ctx, PS_SCORE, s); rc = launch_gemm_nt(ctx, g, s); prof_end(ctx, s);
+        if (rc) return rc;
+        const bool want_conf = p.full && d_conf && d_conf[pidx];
+        SinkhornOut one;  // outputs of this pair: one group of B problems
+        one.logZ[0] = d_logZ ? d_logZ[pidx] : nullptr;
+        if (p.full) {
+            one.m0[0] = (d_m0 && d_m0[pidx]) ? d_m0[pidx] : (want_conf ? p.tmp_m0[pidx] : nullptr);
+            one.m1[0] = d_m1 ? d_m1[pidx] : nullptr;
+            one.ms0[0] = (d_ms0 && d_ms0[pidx]) ? d_ms0[pidx] : (want_conf ? p.tmp_ms0[pidx] : nullptr);
+            one.ms1[0] = d_ms1 ? d_ms1[pidx] : nullptr;
         }
+        so.logZ[pidx] = one.logZ[0]; so.m0[pidx] = one.m0[0]; so.m1[pidx] = one.m1[0];
+        so.ms0[pidx] = one.ms0[0]; so.ms1[pidx] = one.ms1[0];
+        if (!p.uniform) {
+            prof_begin(ctx, PS_SINKHORN, s);
+            rc = launch_sinkhorn(ctx, B, Ni, Nj, p.S + pidx * pair_stride, ldj, ctx->bin_score, fd->sinkhorn_iters,
+                                 fd->match_threshold, one, p.skws, s);
+            prof_end(ctx, s);
+            if (rc) return rc;
+        }
+    }
     if (p.uniform) {
         prof_begin(ctx, PS_SINKHORN, s);
         rc = launch_sinkhorn(ctx, p.P * B, p.N, p.N, p.S, p.ldS, ctx->bin_score, fd->sinkhorn_iters, fd->match_threshold, so, p.skws, s);
@@ -478,53 +477,52 @@ static int conf_heads(e2emv_ctx* ctx, const FwdPlan& p, const SinkhornOut& so, f
     float* gathered = p.msg;  // [B][n_rows][D] ([B][n_rows][2D] in the f16x2 modes)
     float* chid = p.hid;      // [B][n_rows][D]
     int rc;
-    int pidx = 0;
-    for (int j = 0; j < p.T; ++j)
-        for (int i = 0; i < j; ++i, ++pidx) {
-            if (!p.full || !d_conf || !d_conf[pidx]) continue;
-            const int Ni = p.Nt[i];
-            const float* mdesc_i = p.att + (int64_t)i * n_rows * D;
-            const float* mdesc_j = p.att + (int64_t)j * n_rows * D;
-            if (use_mlp && p.mode == FwdMode::F16X2_PLANES && c0.wp) {
-                // plane kernels: [mdesc_i | mdesc_j(match)] -> planes with tile exponents -> conf_mlp.0 (+ BN, ReLU) on gemm_p2
-                // (one pass: the gather is resolved in the source address of the plane conversion - p2_tools.hip)
-                uint16_t* feat = (uint16_t*)p.qkv;  // [B * n_rows][2D]
-                prof_begin(ctx, PS_CONF, s);
-                rc = launch_conf_gather_planes(ctx, mdesc_i, mdesc_j, tuple_stride, so.m0[pidx], Ni, n_rows, B, D, feat, p.e_hid, s);
-                prof_end(ctx, s);
-                if (rc) return rc;
-                GemmP2Args q = dense_gemm_p2(c0, B * n_rows);
-                q.A = feat; q.lda = 2 * D; q.relu = true; q.out = P2_OUT_F32; q.C32 = chid; q.ldc = D; q.EA = p.e_hid;
-                prof_begin(ctx, PS_GEMM, s); rc = launch_gemm_p2(ctx, q, s); prof_end(ctx, s);
-                if (rc) return rc;
-            } else if (use_mlp && p.f16x2() && c0.wh) {
-                prof_begin(ctx, PS_CONF, s);
-                hipLaunchKernelGGL(conf_gather2_kernel, dim3((n_rows + 3) / 4, B), dim3(256), 0, s, Ni, n_rows, D, mdesc_i, mdesc_j,
-                                   tuple_stride, so.m0[pidx], gathered);
-                prof_end(ctx, s);
-                GemmArgs c = dense_gemm(c0, B * n_rows);
-                c.A = gathered; c.lda = 2 * D; c.relu = true; c.C = chid; c.ldc = D;
-                prof_begin(ctx, PS_GEMM, s); rc = launch_gemm_h2(ctx, c, c0.wh, 2 * D, c0.hs, s); prof_end(ctx, s);
-                if (rc) return rc;
-            } else if (use_mlp) {
-                prof_begin(ctx, PS_CONF, s);
-                hipLaunchKernelGGL(conf_gather_kernel, dim3((n_rows + 3) / 4, B), dim3(256), 0, s, Ni, n_rows, D, mdesc_j, tuple_stride,
-                                   so.m0[pidx], gathered);
-                prof_end(ctx, s);
-                GemmArgs c = dense_gemm(c0, n_rows);
-                c.batch = B; c.K1 = D;
-                c.A = mdesc_i; c.lda = D; c.sA = tuple_stride;
-                c.A2 = gathered; c.lda2 = D; c.sA2 = (int64_t)n_rows * D;
-                c.relu = true; c.C = chid; c.ldc = D; c.sC = (int64_t)n_rows * D;
-                prof_begin(ctx, PS_GEMM, s); rc = launch_gemm_nt(ctx, c, s); prof_end(ctx, s);
-                if (rc) return rc;
-            }
+    for (int pidx = 0; pidx < p.P; ++pidx) {
+        const int i = tuple_pair(pidx).i, j = tuple_pair(pidx).j;
+        if (!p.full || !d_conf || !d_conf[pidx]) continue;
+        const int Ni = p.Nt[i];
+        const float* mdesc_i = p.att + (int64_t)i * n_rows * D;
+        const float* mdesc_j = p.att + (int64_t)j * n_rows * D;
+        if (use_mlp && p.mode == FwdMode::F16X2_PLANES && c0.wp) {
+            // plane kernels: [mdesc_i | mdesc_j(match)] -> planes with tile exponents -> conf_mlp.0 (+ BN, ReLU) on gemm_p2
+            // (one pass: the gather is resolved in the source address of the plane conversion - p2_tools.hip)
+            uint16_t* feat = (uint16_t*)p.qkv;  // [B * n_rows][2D]
             prof_begin(ctx, PS_CONF, s);
-            hipLaunchKernelGGL(conf_final_kernel, dim3((Ni + 3) / 4, B), dim3(256), 0, s, Ni, n_rows, D, chid, ctx->w_conf1,
-                               ctx->b_conf1, so.m0[pidx], so.ms0[pidx], use_mlp ? 1 : 0, d_conf[pidx]);
+            rc = launch_conf_gather_planes(ctx, mdesc_i, mdesc_j, tuple_stride, so.m0[pidx], Ni, n_rows, B, D, feat, p.e_hid, s);
             prof_end(ctx, s);
-            E2EMV_CHECK_LAUNCH(ctx, "conf kernels");
+            if (rc) return rc;
+            GemmP2Args q = dense_gemm_p2(c0, B * n_rows);
+            q.A = feat; q.lda = 2 * D; q.relu = true; q.out = P2_OUT_F32; q.C32 = chid; q.ldc = D; q.EA = p.e_hid;
+            prof_begin(ctx, PS_GEMM, s); rc = launch_gemm_p2(ctx, q, s); prof_end(ctx, s);
+            if (rc) return rc;
+        } else if (use_mlp && p.f16x2() && c0.wh) {
+            prof_begin(ctx, PS_CONF, s);
+            hipLaunchKernelGGL(conf_gather2_kernel, dim3((n_rows + 3) / 4, B), dim3(256), 0, s, Ni, n_rows, D, mdesc_i, mdesc_j,
+                               tuple_stride, so.m0[pidx], gathered);
+            prof_end(ctx, s);
+            GemmArgs c = dense_gemm(c0, B * n_rows);
+            c.A = gathered; c.lda = 2 * D; c.relu = true; c.C = chid; c.ldc = D;
+            prof_begin(ctx, PS_GEMM, s); rc = launch_gemm_h2(ctx, c, c0.wh, 2 * D, c0.hs, s); prof_end(ctx, s);
+            if (rc) return rc;
+        } else if (use_mlp) {
+            prof_begin(ctx, PS_CONF, s);
+            hipLaunchKernelGGL(conf_gather_kernel, dim3((n_rows + 3) / 4, B), dim3(256), 0, s, Ni, n_rows, D, mdesc_j, tuple_stride,
+                               so.m0[pidx], gathered);
+            prof_end(ctx, s);
+            GemmArgs c = dense_gemm(c0, n_rows);
+            c.batch = B; c.K1 = D;
+            c.A = mdesc_i; c.lda = D; c.sA = tuple_stride;
+            c.A2 = gathered; c.lda2 = D; c.sA2 = (int64_t)n_rows * D;
+            c.relu = true; c.C = chid; c.ldc = D; c.sC = (int64_t)n_rows * D;
+            prof_begin(ctx, PS_GEMM, s); rc = launch_gemm_nt(ctx, c, s); prof_end(ctx, s);
+            if (rc) return rc;
         }
+        prof_begin(ctx, PS_CONF, s);
+        hipLaunchKernelGGL(conf_final_kernel, dim3((Ni + 3) / 4, B), dim3(256), 0, s, Ni, n_rows, D, chid, ctx->w_conf1,
+                           ctx->b_conf1, so.m0[pidx], so.ms0[pidx], use_mlp ? 1 : 0, d_conf[pidx]);
+        prof_end(ctx, s);
+        E2EMV_CHECK_LAUNCH(ctx, "conf kernels");
+    }
     return E2EMV_OK;
 }
 
@@ -577,27 +575,26 @@ extern "C" int e2emv_matcher_forward(e2emv_ctx* ctx, const e2emv_forward_desc* f
     if (T == 2 || (fd->flags & E2EMV_FLAG_MULTI_FRAME))
         return forward_joint(ctx, fd, d_kpts, d_kscores, d_desc, d_logZ, d_matches0, d_matches1, d_mscores0, d_mscores1, d_conf, s);
     // pairwise mode on a tuple: every pair goes through the 2-view network on its own
-    int pidx = 0;
-    for (int j = 0; j < T; ++j)
-        for (int i = 0; i < j; ++i, ++pidx) {
-            e2emv_forward_desc f2 = *fd;
-            f2.tuple_size = 2;
-            f2.img_w[0] = fd->img_w[i]; f2.img_h[0] = fd->img_h[i];
-            f2.img_w[1] = fd->img_w[j]; f2.img_h[1] = fd->img_h[j];
-            f2.n_kpts_img[0] = fd->n_kpts_img[i]; f2.n_kpts_img[1] = fd->n_kpts_img[j];
-            for (int t = 2; t < E2EMV_MAX_TUPLE; ++t) f2.n_kpts_img[t] = 0;
-            const float* kp[2] = {d_kpts[i], d_kpts[j]};
-            const float* ks[2] = {d_kscores[i], d_kscores[j]};
-            const void* de[2] = {d_desc[i], d_desc[j]};
-            float* lz[1] = {d_logZ ? d_logZ[pidx] : nullptr};
-            int64_t* m0[1] = {d_matches0 ? d_matches0[pidx] : nullptr};
-            int64_t* m1[1] = {d_matches1 ? d_matches1[pidx] : nullptr};
-            float* s0[1] = {d_mscores0 ? d_mscores0[pidx] : nullptr};
-            float* s1[1] = {d_mscores1 ? d_mscores1[pidx] : nullptr};
-            float* cf[1] = {d_conf ? d_conf[pidx] : nullptr};
-            int rc = forward_joint(ctx, &f2, kp, ks, de, lz, m0, m1, s0, s1, cf, s);
-            if (rc) return rc;
-        }
+    for (int pidx = 0; pidx < T * (T - 1) / 2; ++pidx) {
+        const int i = tuple_pair(pidx).i, j = tuple_pair(pidx).j;
+        e2emv_forward_desc f2 = *fd;
+        f2.tuple_size = 2;
+        f2.img_w[0] = fd->img_w[i]; f2.img_h[0] = fd->img_h[i];
+        f2.img_w[1] = fd->img_w[j]; f2.img_h[1] = fd->img_h[j];
+        f2.n_kpts_img[0] = fd->n_kpts_img[i]; f2.n_kpts_img[1] = fd->n_kpts_img[j];
+        for (int t = 2; t < E2EMV_MAX_TUPLE; ++t) f2.n_kpts_img[t] = 0;
+        const float* kp[2] = {d_kpts[i], d_kpts[j]};
+        const float* ks[2] = {d_kscores[i], d_kscores[j]};
+        const void* de[2] = {d_desc[i], d_desc[j]};
+        float* lz[1] = {d_logZ ? d_logZ[pidx] : nullptr};
+        int64_t* m0[1] = {d_matches0 ? d_matches0[pidx] : nullptr};
+        int64_t* m1[1] = {d_matches1 ? d_matches1[pidx] : nullptr};
+        float* s0[1] = {d_mscores0 ? d_mscores0[pidx] : nullptr};
+        float* s1[1] = {d_mscores1 ? d_mscores1[pidx] : nullptr};
+        float* cf[1] = {d_conf ? d_conf[pidx] : nullptr};
+        int rc = forward_joint(ctx, &f2, kp, ks, de, lz, m0, m1, s0, s1, cf, s);
+        if (rc) return rc;
+    }
     return E2EMV_OK;
 }
 

@@ -27,14 +27,16 @@
 
 namespace e2emv {
 
+// A dense layer of the folded arena: weight [out][in] and bias [out] at these offsets (floats) of d_w, their gradients at the
+// same offsets of d_gw
+struct TrainDense { size_t w, b; int out, in; };
+
 struct TrainLayer {
-    size_t wqkv, bqkv, wm, bm, w0, b0, w1, b1;  // offsets (floats) into the folded arena: q|k|v [3D][D] head-major rows,
-    int type;                                    // merge [D][D] head-major columns, MLP0 [2D][2D] BN folded, MLP1 [D][2D]
+    TrainDense qkv, merge, mlp0, mlp1;  // q|k|v [3D][D] head-major rows, merge [D][D] head-major columns, MLP0 [2D][2D] BN folded,
+    int type;                           // MLP1 [D][2D]
 };
 
-struct RawRef {
-    size_t off, numel;
-};
+struct RawRef { size_t off, numel; };
 
 struct TrainState {
     e2emv_model_desc model{};
@@ -42,11 +44,12 @@ struct TrainState {
     float* d_w = nullptr;
     float* d_gw = nullptr;
     size_t w_floats = 0;
-    std::vector<size_t> kw, kb;  // keypoint encoder layers 0..n (BN folded)
-    std::vector<int> kdims;      // [3, c0, ..., D]
+    std::vector<TrainDense> kenc;  // keypoint encoder layers 0..n (BN folded)
+    std::vector<int> kdims;        // [3, c0, ..., D]
     std::vector<TrainLayer> layers;
-    size_t wf = 0, bf = 0, alpha = 0;
-    size_t wc0 = 0, bc0 = 0, wc1 = 0, bc1 = 0;  // conf_mlp.0 (+ BN conf_mlp.1) [D][2D], conf_mlp.3 [1][D]
+    TrainDense final_proj{};
+    TrainDense conf0{}, conf1{};  // conf_mlp.0 (+ BN conf_mlp.1) [D][2D], conf_mlp.3 [1][D]
+    size_t alpha = 0;
     bool conf_mlp = false;
     float bin_score = 1.f;
     // upstream parameters (for the unfolding) and their gradients (same offsets)
@@ -136,6 +139,31 @@ static int colsum(e2emv_ctx* ctx, const float* X, int64_t rows, int N, int64_t l
 }
 static unsigned ew_grid(int64_t n) { return (unsigned)std::min<int64_t>((n + 255) / 256, 4096); }
 
+// The weight side of a forward GEMM over `rows` rows with the dense layer d, one K segment
+static GemmArgs dense_gemm(const TrainState* t, const TrainDense& d, int64_t rows) {
+    GemmArgs g;
+    g.M = (int)rows; g.N = d.out; g.K = d.in; g.K1 = d.in; g.W = t->d_w + d.w; g.ldw = d.in; g.bias = t->d_w + d.b;
+    return g;
+}
+// Backward of y = x W^T + b over `rows` rows, W [n_out][n_in] (row stride ldw): dW += dY^T X, db += the column sums of dY and, with
+// a dX, dX (+)= dY W - three launches, none reads what another writes.  X2: the input is [X | X2] in two buffers of n_in / 2 columns
+// each (MLP0's [x | msg]); the weight gradient is then two wgrad calls, the second at column n_in / 2 of dW.
+static int linear_backward(e2emv_ctx* ctx, const float* W, float* dW, int64_t ldw, float* db, int n_out, int n_in, int64_t rows, const float* dY, int64_t ldy,
+                           const float* X, int64_t ldx, const float* X2, int64_t ldx2, float* dX, int64_t ldx_out, bool accumulate, hipStream_t s) {
+    const int k1 = X2 ? n_in / 2 : n_in;
+    int rc;
+    if ((rc = wgrad(ctx, dY, ldy, n_out, X, ldx, k1, rows, dW, ldw, s))) return rc;
+    if (X2 && (rc = wgrad(ctx, dY, ldy, n_out, X2, ldx2, n_in - k1, rows, dW + k1, ldw, s))) return rc;
+    if ((rc = colsum(ctx, dY, rows, n_out, ldy, db, s))) return rc;
+    if (dX && (rc = dgrad(ctx, dY, ldy, n_out, W, ldw, n_in, rows, dX, ldx_out, accumulate, s))) return rc;
+    return E2EMV_OK;
+}
+// ... of the dense layer d of the folded arena, its gradients into d_gw
+static int dense_backward(e2emv_ctx* ctx, const TrainState* t, const TrainDense& d, int64_t rows, const float* dY, int64_t ldy, const float* X, int64_t ldx,
+                          float* dX, int64_t ldx_out, bool accumulate, hipStream_t s, const float* X2 = nullptr, int64_t ldx2 = 0) {
+    return linear_backward(ctx, t->d_w + d.w, t->d_gw + d.w, d.in, t->d_gw + d.b, d.out, d.in, rows, dY, ldy, X, ldx, X2, ldx2, dX, ldx_out, accumulate, s);
+}
+
 // ---- batch-statistics BatchNorm launches (train_kernels.h, BnCall) ----
 constexpr int BN_MAX_CHUNKS = 64;  // (64 rows per chunk: 16 per thread, 4 steps of 4 loads in flight)
 static int bn_chunks(int64_t rows) { return (int)std::max<int64_t>(1, std::min<int64_t>(BN_MAX_CHUNKS, (rows + 63) / 64)); }
@@ -170,6 +198,18 @@ static int bn_backward(e2emv_ctx* ctx, const BnCall& a, int calls, hipStream_t s
     hipLaunchKernelGGL(bn_bwd_stats_kernel, grid, dim3(256), 0, s, a);
     hipLaunchKernelGGL(bn_bwd_apply_kernel, grid, dim3(256), 0, s, a);
     E2EMV_CHECK_LAUNCH(ctx, "batchnorm backward kernels");
+    return E2EMV_OK;
+}
+// Backward of the activation behind a layer of C channels over the T images, g [Mtot][C]: d h on entry, d y on exit.  Batch
+// statistics: h = relu(BN_j(y)) with the tape's y and statistics (dgamma / dbeta of BN j written); frozen: h = relu(y), the
+// BatchNorm is folded into the layer
+static int activation_backward(e2emv_ctx* ctx, const TrainState* t, int j, int C, float* y, float* stats, const float* h, float* g, double* bpart, hipStream_t s) {
+    if (t->bn_mode == E2EMV_BN_BATCH) {
+        BnCall a = bn_images(t, j, y, g, stats, bpart);
+        a.h = h;
+        return bn_backward(ctx, a, t->T, s);
+    }
+    hipLaunchKernelGGL(relu_bwd_kernel, dim3(ew_grid(t->Mtot * C)), dim3(256), 0, s, g, h, t->Mtot * C);
     return E2EMV_OK;
 }
 
@@ -299,8 +339,7 @@ static int train_build(e2emv_ctx* ctx, const e2emv_model_desc* m, TrainState* t,
     for (int i = 0; i < nk; ++i) {
         const std::string pfx = "kenc.encoder." + std::to_string(3 * i);
         if ((rc = conv_bn(ctx, t, raw, pfx, i < nk - 1 ? "kenc.encoder." + std::to_string(3 * i + 1) : std::string(), t->kdims[i + 1], t->kdims[i], w, b))) return rc;
-        t->kw.push_back(pk.add(w));
-        t->kb.push_back(pk.add(b));
+        t->kenc.push_back({pk.add(w), pk.add(b), t->kdims[i + 1], t->kdims[i]});
     }
     t->layers.resize(m->n_layers);
     for (int l = 0; l < m->n_layers; ++l) {
@@ -317,33 +356,26 @@ static int train_build(e2emv_ctx* ctx, const e2emv_model_desc* m, TrainState* t,
                     bqkv[dst] = b[src];
                 }
         }
-        L.wqkv = pk.add(wqkv);
-        L.bqkv = pk.add(bqkv);
+        L.qkv = {pk.add(wqkv), pk.add(bqkv), 3 * D, D};
         if ((rc = conv_bn(ctx, t, raw, base + ".attn.merge", "", D, D, w, b))) return rc;
         std::vector<float> wm((size_t)D * D);
         for (int o = 0; o < D; ++o)
             for (int h = 0; h < H; ++h)
                 for (int dd = 0; dd < d; ++dd) wm[(size_t)o * D + h * d + dd] = w[(size_t)o * D + dd * H + h];
-        L.wm = pk.add(wm);
-        L.bm = pk.add(b);
+        L.merge = {pk.add(wm), pk.add(b), D, D};
         if ((rc = conv_bn(ctx, t, raw, base + ".mlp.0", base + ".mlp.1", 2 * D, 2 * D, w, b))) return rc;
-        L.w0 = pk.add(w);
-        L.b0 = pk.add(b);
+        L.mlp0 = {pk.add(w), pk.add(b), 2 * D, 2 * D};
         if ((rc = conv_bn(ctx, t, raw, base + ".mlp.3", "", D, 2 * D, w, b))) return rc;
-        L.w1 = pk.add(w);
-        L.b1 = pk.add(b);
+        L.mlp1 = {pk.add(w), pk.add(b), D, 2 * D};
     }
     if ((rc = conv_bn(ctx, t, raw, "final_proj", "", D, D, w, b))) return rc;
-    t->wf = pk.add(w);
-    t->bf = pk.add(b);
+    t->final_proj = {pk.add(w), pk.add(b), D, D};
     t->conf_mlp = m->conf_mlp != 0;
     if (t->conf_mlp) {
         if ((rc = conv_bn(ctx, t, raw, "conf_mlp.0", "conf_mlp.1", D, 2 * D, w, b))) return rc;
-        t->wc0 = pk.add(w);
-        t->bc0 = pk.add(b);
+        t->conf0 = {pk.add(w), pk.add(b), D, 2 * D};
         if ((rc = conv_bn(ctx, t, raw, "conf_mlp.3", "", 1, D, w, b))) return rc;
-        t->wc1 = pk.add(w);
-        t->bc1 = pk.add(b);
+        t->conf1 = {pk.add(w), pk.add(b), 1, D};
     }
     const HostTensor* bs = find(ctx, "bin_score");
     if (!bs || bs->data.size() != 1) return set_err(ctx, E2EMV_ESTATE, "train_commit: missing scalar 'bin_score'");
@@ -413,6 +445,29 @@ extern "C" int e2emv_train_commit(e2emv_ctx* ctx, const e2emv_model_desc* m) {
 
 static size_t al256(size_t b) { return (b + 255) & ~size_t(255); }
 
+// Every upstream convolution of the model, in the order the fold (e2emv_train_update) and the un-fold (unfold_grads) launch them:
+// fn(conv, bn, d, rows, rbase, rmap, cmap) - the convolution, the BatchNorm behind it ("" = none), the dense layer of the folded
+// arena that holds its `rows` output channels from row rbase on, the head-order maps of its rows / columns (null = upstream order)
+template <class F>
+static void for_each_folded(const TrainState* t, F&& fn) {
+    const int nk = (int)t->kenc.size(), D = t->model.desc_dim;
+    for (int i = 0; i < nk; ++i)
+        fn("kenc.encoder." + std::to_string(3 * i), i < nk - 1 ? "kenc.encoder." + std::to_string(3 * i + 1) : std::string(), t->kenc[i], t->kenc[i].out, 0, nullptr, nullptr);
+    for (size_t l = 0; l < t->layers.size(); ++l) {
+        const TrainLayer& Lw = t->layers[l];
+        const std::string base = "gnn.layers." + std::to_string(l);
+        for (int p = 0; p < 3; ++p) fn(base + ".attn.proj." + std::to_string(p), "", Lw.qkv, D, p * D, t->d_maps, nullptr);
+        fn(base + ".attn.merge", "", Lw.merge, D, 0, nullptr, t->d_maps);
+        fn(base + ".mlp.0", base + ".mlp.1", Lw.mlp0, 2 * D, 0, nullptr, nullptr);
+        fn(base + ".mlp.3", "", Lw.mlp1, D, 0, nullptr, nullptr);
+    }
+    fn("final_proj", "", t->final_proj, D, 0, nullptr, nullptr);
+    if (t->conf_mlp) {
+        fn("conf_mlp.0", "conf_mlp.1", t->conf0, D, 0, nullptr, nullptr);
+        fn("conf_mlp.3", "", t->conf1, 1, 0, nullptr, nullptr);
+    }
+}
+
 // After an optimiser step: the new parameter values straight from the caller's DEVICE tensors into the training arena of a
 // context that already trains this model - D2D copies into the raw arena, the folds (BatchNorm, head order) as kernels, all
 // in stream order: no host copy of the weights, no synchronisation, the tape and the arenas stay.
@@ -448,38 +503,168 @@ extern "C" int e2emv_train_update(e2emv_ctx* ctx, const e2emv_model_desc* m, int
     t->have_tape = false;
     for (const auto& c : copies)
         E2EMV_HIP(ctx, hipMemcpyAsync(t->d_raw + c.first, d_params[c.second], numels[c.second] * sizeof(float), hipMemcpyDeviceToDevice, s));
-    const int D = m->desc_dim;
     float* W = t->d_w;
     auto ref = [&](const std::string& k) -> const float* { auto it = t->raw.find(k); return it == t->raw.end() ? nullptr : t->d_raw + it->second.off; };
-    auto fold = [&](const std::string& conv, const std::string& bn, float* Wf, float* bf, int64_t ldwf, int rows, int cols, const int* rmap, int rbase, const int* cmap) {
+    for_each_folded(t, [&](const std::string& conv, const std::string& bn, const TrainDense& d, int rows, int rbase, const int* rmap, const int* cmap) {
         FoldArgs a{};
         a.W = ref(conv + ".weight"); a.b = ref(conv + ".bias");
         if (!bn.empty() && ref(bn + ".running_mean") && t->bn_mode == E2EMV_BN_FROZEN) { a.gamma = ref(bn + ".weight"); a.beta = ref(bn + ".bias"); a.mean = ref(bn + ".running_mean"); a.var = ref(bn + ".running_var"); }
-        a.Wf = Wf + (int64_t)rbase * ldwf; a.bf = bf + rbase; a.ldwf = ldwf; a.col0 = 0; a.rows = rows; a.cols = cols; a.rmap = rmap; a.cmap = cmap;
+        a.Wf = W + d.w + (int64_t)rbase * d.in; a.bf = W + d.b + rbase; a.ldwf = d.in; a.col0 = 0; a.rows = rows; a.cols = d.in; a.rmap = rmap; a.cmap = cmap;
         hipLaunchKernelGGL(fold_kernel, dim3(rows), dim3(256), 0, s, a);
-    };
-    const int nk = (int)t->kdims.size() - 1;
-    for (int i = 0; i < nk; ++i)
-        fold("kenc.encoder." + std::to_string(3 * i), i < nk - 1 ? "kenc.encoder." + std::to_string(3 * i + 1) : std::string(), W + t->kw[i], W + t->kb[i], t->kdims[i],
-             t->kdims[i + 1], t->kdims[i], nullptr, 0, nullptr);
-    for (int l = 0; l < (int)t->layers.size(); ++l) {
-        const TrainLayer& Lw = t->layers[l];
-        const std::string base = "gnn.layers." + std::to_string(l);
-        for (int p = 0; p < 3; ++p) fold(base + ".attn.proj." + std::to_string(p), "", W + Lw.wqkv, W + Lw.bqkv, D, D, D, t->d_maps, p * D, nullptr);
-        fold(base + ".attn.merge", "", W + Lw.wm, W + Lw.bm, D, D, D, nullptr, 0, t->d_maps);
-        fold(base + ".mlp.0", base + ".mlp.1", W + Lw.w0, W + Lw.b0, 2 * D, 2 * D, 2 * D, nullptr, 0, nullptr);
-        fold(base + ".mlp.3", "", W + Lw.w1, W + Lw.b1, 2 * D, D, 2 * D, nullptr, 0, nullptr);
-    }
-    fold("final_proj", "", W + t->wf, W + t->bf, D, D, D, nullptr, 0, nullptr);
-    if (t->conf_mlp) {
-        fold("conf_mlp.0", "conf_mlp.1", W + t->wc0, W + t->bc0, 2 * D, D, 2 * D, nullptr, 0, nullptr);
-        fold("conf_mlp.3", "", W + t->wc1, W + t->bc1, D, 1, D, nullptr, 0, nullptr);
-    }
+    });
     E2EMV_CHECK_LAUNCH(ctx, "fold kernels");
     E2EMV_HIP(ctx, hipMemcpyAsync(W + t->alpha, ref("bin_score"), sizeof(float), hipMemcpyDeviceToDevice, s));
     t->bin_score = bin_score;
     E2EMV_HIP(ctx, hipMemsetAsync(t->d_graw, 0, t->raw_floats * sizeof(float), s));
     t->have_tape = false;
+    return E2EMV_OK;
+}
+
+// ---- the forward with a tape, in stages --------------------------------------------------------------------------------------
+// what e2emv_matcher_forward_train refuses before it touches the tape
+static int check_train_inputs(e2emv_ctx* ctx, const TrainState* t, const e2emv_forward_desc* fd) {
+    const int B = fd->batch, T = fd->tuple_size, N = fd->n_kpts;
+    if (B <= 0 || T < 2 || T > E2EMV_MAX_TUPLE || N <= 0 || N > 2048) return set_err(ctx, E2EMV_ESHAPE, "matcher_forward_train: batch=%d tuple_size=%d n_kpts=%d", B, T, N);
+    if (T > 2 && !(fd->flags & E2EMV_FLAG_MULTI_FRAME)) return set_err(ctx, E2EMV_ESHAPE, "matcher_forward_train: tuples of more than 2 images need multi_frame_matching");
+    for (int i = 0; i < T; ++i)
+        if (fd->n_kpts_img[i] > 0 && fd->n_kpts_img[i] != N) return set_err(ctx, E2EMV_ESHAPE, "matcher_forward_train: all images of a call carry the same number of keypoints");
+    if (fd->sinkhorn_iters < 0) return set_err(ctx, E2EMV_EINVAL, "negative sinkhorn_iters");
+    if (t->bn_mode != ctx->train_bn_mode)
+        return set_err(ctx, E2EMV_ESTATE, "matcher_forward_train: the BatchNorm mode changed since e2emv_train_commit (commit again)");
+    if (t->bn_mode == E2EMV_BN_BATCH && (int64_t)B * N < 2) return set_err(ctx, E2EMV_ESHAPE, "matcher_forward_train: batch statistics need more than one value per channel");
+    return E2EMV_OK;
+}
+
+// The tape of a forward of B tuples of T images, N keypoints each, `iters` Sinkhorn iterations: its regions in order, each on a
+// 256-byte boundary.  Returns the byte count.  base == nullptr: the count only, *t is left as it is; with a base the shape and
+// every t_* pointer of *t are set (t_cmatch: reset - no conf head has run on this tape).
+static size_t carve_tape(TrainState* t, char* base, int B, int T, int N, int iters) {
+    TrainState sizes_only;
+    TrainState* o = base ? t : &sizes_only;
+    const int D = t->model.desc_dim, L = (int)t->layers.size(), nk = (int)t->kenc.size();
+    const int n_rows = (N + 127) / 128 * 128, P = T * (T - 1) / 2, ldS = (N + 3) / 4 * 4;
+    const size_t Mtot = (size_t)B * T * n_rows, BN = (size_t)B * N;
+    const bool bnb = t->bn_mode == E2EMV_BN_BATCH;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { float* p = base ? (float*)(base + off) : nullptr; off += al256(bytes); return p; };
+    for (auto* v : {&o->t_kh, &o->t_ky, &o->t_kst}) v->assign(nk, nullptr);  // (a slot without a region stays null)
+    for (auto* v : {&o->t_qkv, &o->t_att, &o->t_msg, &o->t_h, &o->t_hy, &o->t_hst}) v->assign(L, nullptr);
+    for (auto* v : {&o->t_cfeat, &o->t_chid, &o->t_cy}) v->assign(P, nullptr);
+    o->t_x.assign(L + 1, nullptr); o->t_cmatch.assign(P, nullptr); o->t_cst = nullptr; o->t_part = nullptr;
+    o->t_inp = take(Mtot * 4 * 4);
+    for (int i = 1; i < nk; ++i) o->t_kh[i] = take(Mtot * t->kdims[i] * 4);  // t_kh[i]: output of encoder layer i - 1 (width kdims[i])
+    for (int l = 0; l <= L; ++l) o->t_x[l] = take(Mtot * D * 4);
+    for (int l = 0; l < L; ++l) { o->t_qkv[l] = take(Mtot * 3 * D * 4); o->t_att[l] = take(Mtot * D * 4); o->t_msg[l] = take(Mtot * D * 4); o->t_h[l] = take(Mtot * 2 * D * 4); }
+    o->t_mdesc = take(Mtot * D * 4);
+    o->t_S = take((size_t)P * BN * ldS * 4);
+    o->t_uv = take((size_t)P * B * (iters + 1) * 2 * (N + 1) * 4);
+    if (t->conf_mlp)
+        for (int q = 0; q < P; ++q) { o->t_cfeat[q] = take(BN * 2 * D * 4); o->t_chid[q] = take(BN * D * 4); }
+    if (bnb) {  // y and the statistics of every BatchNorm, the partial sums
+        for (int j = 1; j < nk; ++j) { o->t_ky[j] = take(Mtot * t->kdims[j] * 4); o->t_kst[j] = take((size_t)T * 3 * t->kdims[j] * 4); }
+        for (int l = 0; l < L; ++l) { o->t_hy[l] = take(Mtot * 2 * D * 4); o->t_hst[l] = take((size_t)T * 3 * 2 * D * 4); }
+        if (t->conf_mlp) {
+            for (int q = 0; q < P; ++q) o->t_cy[q] = take(BN * D * 4);
+            o->t_cst = take((size_t)P * 3 * D * 4);
+        }
+        o->t_part = (double*)take((size_t)T * BN_MAX_CHUNKS * 2 * 2 * D * 8);
+    }
+    o->B = B; o->T = T; o->N = N; o->n_rows = n_rows; o->iters = iters; o->P = P; o->ldS = ldS; o->Mtot = (int64_t)Mtot;
+    return off;
+}
+
+// ingest (descriptors -> the desc part of x_0, keypoints -> encoder layer 0) and the keypoint encoder: x_0 = desc + kenc
+static int encode_train(e2emv_ctx* ctx, TrainState* t, const e2emv_forward_desc* fd, const float* const* d_kpts, const float* const* d_kscores,
+                        const void* const* d_desc, hipStream_t s) {
+    const int B = t->B, T = t->T, N = t->N, n_rows = t->n_rows, D = t->model.desc_dim, nk = (int)t->kenc.size();
+    const int64_t Mtot = t->Mtot;
+    const bool bnb = t->bn_mode == E2EMV_BN_BATCH;
+    const float *w0 = t->d_w + t->kenc[0].w, *b0 = t->d_w + t->kenc[0].b;  // layer 0 (3 -> c0) runs inside the ingest
+    const int c0 = t->kenc[0].out;
+    IngestParams ip{};
+    for (int i = 0; i < T; ++i) {
+        if (!d_kpts[i] || !d_kscores[i] || !d_desc[i]) return set_err(ctx, E2EMV_EINVAL, "matcher_forward_train: null input for image %d", i);
+        ip.kpts[i] = d_kpts[i]; ip.ksc[i] = d_kscores[i]; ip.desc[i] = d_desc[i];
+        ip.img_w[i] = fd->img_w[i]; ip.img_h[i] = fd->img_h[i]; ip.Nimg[i] = N;
+    }
+    ip.B = B; ip.T = T; ip.n_rows = n_rows; ip.D = D; ip.c0 = c0; ip.f16 = fd->desc_dtype == E2EMV_DESC_F16;
+    ip.w0 = w0; ip.b0 = b0; ip.x0 = t->t_x[0]; ip.h0 = t->t_kh[1]; ip.inp = t->t_inp;
+    hipLaunchKernelGGL(ingest_transpose, dim3(n_rows / 64, D / 64, B * T), dim3(256), 0, s, ip);
+    hipLaunchKernelGGL(ingest_kenc0, dim3((n_rows + 255) / 256, B * T), dim3(256), 0, s, ip);
+    E2EMV_CHECK_LAUNCH(ctx, "ingest kernels");
+    int rc;
+    if (bnb) {  // layer 0 again, without the BatchNorm ingest_kenc0 fuses: y, then the batch-statistics BN + ReLU over t_kh[1]
+        hipLaunchKernelGGL(kenc0_conv_kernel, dim3(ew_grid(Mtot * c0)), dim3(256), 0, s, (const float*)t->t_inp, w0, b0, c0, Mtot, t->t_ky[1]);
+        E2EMV_CHECK_LAUNCH(ctx, "kenc0_conv_kernel");
+        if ((rc = bn_forward(ctx, bn_images(t, 0, t->t_ky[1], t->t_kh[1], t->t_kst[1], t->t_part), T, s))) return rc;
+    }
+    // encoder layers 1 .. nk-1; the last adds the descriptors (x_0 = desc + kenc)
+    for (int i = 1; i < nk; ++i) {
+        const TrainDense& d = t->kenc[i];
+        const bool last = i == nk - 1;
+        GemmArgs g = dense_gemm(t, d, Mtot);
+        g.A = t->t_kh[i]; g.lda = d.in; g.relu = !last && !bnb;
+        if (last) { g.R = t->t_x[0]; g.ldr = D; g.C = t->t_x[0]; g.ldc = D; }
+        else { g.C = bnb ? t->t_ky[i + 1] : t->t_kh[i + 1]; g.ldc = d.out; }
+        if ((rc = launch_gemm_nt(ctx, g, s))) return rc;
+        if (bnb && !last && (rc = bn_forward(ctx, bn_images(t, i, t->t_ky[i + 1], t->t_kh[i + 1], t->t_kst[i + 1], t->t_part), T, s))) return rc;
+    }
+    return E2EMV_OK;
+}
+
+// attentional GNN: x_l -> x_{l+1}, every intermediate on the tape (merge NOT folded: its parameters get their own gradients)
+static int gnn_train(e2emv_ctx* ctx, TrainState* t, hipStream_t s) {
+    const int D = t->model.desc_dim, L = (int)t->layers.size(), nk = (int)t->kenc.size();
+    const int64_t Mtot = t->Mtot;
+    const bool bnb = t->bn_mode == E2EMV_BN_BATCH;
+    int Nt[E2EMV_MAX_TUPLE] = {0};
+    for (int i = 0; i < t->T; ++i) Nt[i] = t->N;
+    int rc;
+    for (int l = 0; l < L; ++l) {
+        const TrainLayer& Lw = t->layers[l];
+        GemmArgs g = dense_gemm(t, Lw.qkv, Mtot);
+        g.A = t->t_x[l]; g.lda = D; g.C = t->t_qkv[l]; g.ldc = 3 * D;
+        if ((rc = launch_gemm_nt(ctx, g, s))) return rc;
+        if ((rc = launch_attention(ctx, t->B, t->T, t->n_rows, Nt, D, t->model.num_heads, t->t_qkv[l], Lw.type, t->t_att[l], s))) return rc;
+        g = dense_gemm(t, Lw.merge, Mtot);
+        g.A = t->t_att[l]; g.lda = D; g.C = t->t_msg[l]; g.ldc = D;
+        if ((rc = launch_gemm_nt(ctx, g, s))) return rc;
+        g = dense_gemm(t, Lw.mlp0, Mtot);  // two K segments: [x_l | msg]
+        g.K1 = D; g.A = t->t_x[l]; g.lda = D; g.A2 = t->t_msg[l]; g.lda2 = D;
+        g.relu = !bnb; g.C = bnb ? t->t_hy[l] : t->t_h[l]; g.ldc = 2 * D;
+        if ((rc = launch_gemm_nt(ctx, g, s))) return rc;
+        if (bnb && (rc = bn_forward(ctx, bn_images(t, nk - 1 + l, t->t_hy[l], t->t_h[l], t->t_hst[l], t->t_part), t->T, s))) return rc;
+        g = dense_gemm(t, Lw.mlp1, Mtot);
+        g.A = t->t_h[l]; g.lda = 2 * D; g.R = t->t_x[l]; g.ldr = D; g.C = t->t_x[l + 1]; g.ldc = D;
+        if ((rc = launch_gemm_nt(ctx, g, s))) return rc;
+    }
+    return E2EMV_OK;
+}
+
+// final_proj, then per pair: scores, Sinkhorn (log domain, u_t / v_t of every iteration kept), log assignment into d_logZ
+static int scores_train(e2emv_ctx* ctx, TrainState* t, float* const* d_logZ, hipStream_t s) {
+    const int B = t->B, N = t->N, n_rows = t->n_rows, ldS = t->ldS, D = t->model.desc_dim;
+    int rc;
+    GemmArgs f = dense_gemm(t, t->final_proj, t->Mtot);
+    f.A = t->t_x.back(); f.lda = D; f.C = t->t_mdesc; f.ldc = D;
+    if ((rc = launch_gemm_nt(ctx, f, s))) return rc;
+    const int64_t tuple_stride = (int64_t)t->T * n_rows * D;
+    SkT sk = sk_problem(nullptr, ldS, N, t->bin_score);
+    const int64_t uvs = (int64_t)(t->iters + 1) * 2 * (N + 1);  // per problem
+    for (int q = 0; q < t->P; ++q) {
+        const TuplePair pr = tuple_pair(q);
+        float* S = t->t_S + (int64_t)q * B * N * ldS;
+        GemmArgs g;
+        g.batch = B; g.M = N; g.N = N; g.K = D; g.K1 = D;
+        g.A = t->t_mdesc + (int64_t)pr.i * n_rows * D; g.lda = D; g.sA = tuple_stride;
+        g.W = t->t_mdesc + (int64_t)pr.j * n_rows * D; g.ldw = D; g.sW = tuple_stride;
+        g.C = S; g.ldc = ldS; g.sC = (int64_t)N * ldS; g.scale = 1.0f / sqrtf((float)D);
+        if ((rc = launch_gemm_nt(ctx, g, s))) return rc;
+        sk.S = S;
+        float* uv = t->t_uv + (int64_t)q * B * uvs;  // [b][t][{u, v}][N + 1]
+        if (!d_logZ[q]) return set_err(ctx, E2EMV_EINVAL, "matcher_forward_train: null logZ for pair %d", q);
+        if ((rc = sinkhorn_tape_forward(ctx, sk, B, t->iters, uv, d_logZ[q], 0, s))) return rc;
+    }
     return E2EMV_OK;
 }
 
@@ -489,39 +674,14 @@ extern "C" int e2emv_matcher_forward_train(e2emv_ctx* ctx, const e2emv_forward_d
     E2EMV_ENTER(ctx, stream);
     TrainState* t = ts_of(ctx);
     if (!t) return set_err(ctx, E2EMV_ESTATE, "matcher_forward_train: e2emv_train_commit first");
-    const int B = fd->batch, T = fd->tuple_size, N = fd->n_kpts;
-    const int D = t->model.desc_dim, H = t->model.num_heads, L = (int)t->layers.size();
-    if (B <= 0 || T < 2 || T > E2EMV_MAX_TUPLE || N <= 0 || N > 2048) return set_err(ctx, E2EMV_ESHAPE, "matcher_forward_train: batch=%d tuple_size=%d n_kpts=%d", B, T, N);
-    if (T > 2 && !(fd->flags & E2EMV_FLAG_MULTI_FRAME)) return set_err(ctx, E2EMV_ESHAPE, "matcher_forward_train: tuples of more than 2 images need multi_frame_matching");
-    for (int i = 0; i < T; ++i)
-        if (fd->n_kpts_img[i] > 0 && fd->n_kpts_img[i] != N) return set_err(ctx, E2EMV_ESHAPE, "matcher_forward_train: all images of a call carry the same number of keypoints");
-    if (fd->sinkhorn_iters < 0) return set_err(ctx, E2EMV_EINVAL, "negative sinkhorn_iters");
-    if (t->bn_mode != ctx->train_bn_mode)
-        return set_err(ctx, E2EMV_ESTATE, "matcher_forward_train: the BatchNorm mode changed since e2emv_train_commit (commit again)");
-    const bool bnb = t->bn_mode == E2EMV_BN_BATCH;
-    if (bnb && (int64_t)B * N < 2) return set_err(ctx, E2EMV_ESHAPE, "matcher_forward_train: batch statistics need more than one value per channel");
+    if (int rc = check_train_inputs(ctx, t, fd)) return rc;
     (void)hipSetDevice(ctx->device);
     hipStream_t s = (hipStream_t)stream;
-    const int n_rows = (N + 127) / 128 * 128, n_img = B * T, P = T * (T - 1) / 2, iters = fd->sinkhorn_iters, ldS = (N + 3) / 4 * 4;
-    const int64_t Mtot = (int64_t)n_img * n_rows;
-    const int nk = (int)t->kdims.size() - 1;
-    // ---- tape ----
-    size_t need = al256((size_t)Mtot * 4 * 4);
-    for (int i = 1; i < nk; ++i) need += al256((size_t)Mtot * t->kdims[i] * 4);
-    need += (size_t)(L + 1) * al256((size_t)Mtot * D * 4) + (size_t)L * (al256((size_t)Mtot * 3 * D * 4) + 2 * al256((size_t)Mtot * D * 4) + al256((size_t)Mtot * 2 * D * 4));
-    need += al256((size_t)Mtot * D * 4) + al256((size_t)P * B * N * ldS * 4) + al256((size_t)P * B * (iters + 1) * 2 * (N + 1) * 4);
-    if (t->conf_mlp) need += (size_t)P * (al256((size_t)B * N * 2 * D * 4) + al256((size_t)B * N * D * 4));
-    if (bnb) {  // y and the statistics of every BatchNorm, the partial sums
-        for (int j = 1; j < nk; ++j) need += al256((size_t)Mtot * t->kdims[j] * 4) + al256((size_t)T * 3 * t->kdims[j] * 4);
-        need += (size_t)L * (al256((size_t)Mtot * 2 * D * 4) + al256((size_t)T * 3 * 2 * D * 4));
-        if (t->conf_mlp) need += (size_t)P * al256((size_t)B * N * D * 4) + al256((size_t)P * 3 * D * 4);
-        need += al256((size_t)T * BN_MAX_CHUNKS * 2 * 2 * D * 8);
-    }
+    const size_t need = carve_tape(t, nullptr, fd->batch, fd->tuple_size, fd->n_kpts, fd->sinkhorn_iters);
     if (need > t->tape_bytes) {
         E2EMV_HIP(ctx, hipDeviceSynchronize());
         if (t->d_tape) E2EMV_HIP(ctx, hipFree(t->d_tape));
-        t->d_tape = nullptr;
-        t->tape_bytes = 0;
+        t->d_tape = nullptr; t->tape_bytes = 0;
         if (hipMalloc((void**)&t->d_tape, need) != hipSuccess) {
             (void)hipGetLastError();
             return set_err(ctx, E2EMV_ENOMEM, "matcher_forward_train: tape of %zu bytes", need);
@@ -529,125 +689,11 @@ extern "C" int e2emv_matcher_forward_train(e2emv_ctx* ctx, const e2emv_forward_d
         t->tape_bytes = need;
     }
     E2EMV_HIP(ctx, hipMemsetAsync(t->d_tape, 0, need, s));  // padded rows must be finite zeros wherever a GEMM does not write them
-    char* w = t->d_tape;
-    auto take = [&](size_t bytes) { float* p = (float*)w; w += al256(bytes); return p; };
-    t->t_inp = take((size_t)Mtot * 4 * 4);
-    t->t_kh.assign(nk, nullptr);
-    for (int i = 1; i < nk; ++i) t->t_kh[i] = take((size_t)Mtot * t->kdims[i] * 4);  // t_kh[i]: output of encoder layer i - 1 (width kdims[i])
-    t->t_x.assign(L + 1, nullptr);
-    for (int l = 0; l <= L; ++l) t->t_x[l] = take((size_t)Mtot * D * 4);
-    t->t_qkv.assign(L, nullptr); t->t_att.assign(L, nullptr); t->t_msg.assign(L, nullptr); t->t_h.assign(L, nullptr);
-    for (int l = 0; l < L; ++l) {
-        t->t_qkv[l] = take((size_t)Mtot * 3 * D * 4);
-        t->t_att[l] = take((size_t)Mtot * D * 4);
-        t->t_msg[l] = take((size_t)Mtot * D * 4);
-        t->t_h[l] = take((size_t)Mtot * 2 * D * 4);
-    }
-    t->t_mdesc = take((size_t)Mtot * D * 4);
-    t->t_S = take((size_t)P * B * N * ldS * 4);
-    t->t_uv = take((size_t)P * B * (iters + 1) * 2 * (N + 1) * 4);
-    t->t_cfeat.assign(P, nullptr); t->t_chid.assign(P, nullptr); t->t_cmatch.assign(P, nullptr);
-    if (t->conf_mlp)
-        for (int q = 0; q < P; ++q) {
-            t->t_cfeat[q] = take((size_t)B * N * 2 * D * 4);
-            t->t_chid[q] = take((size_t)B * N * D * 4);
-        }
-    t->t_ky.assign(nk, nullptr); t->t_kst.assign(nk, nullptr); t->t_hy.assign(L, nullptr); t->t_hst.assign(L, nullptr); t->t_cy.assign(P, nullptr);
-    t->t_cst = nullptr; t->t_part = nullptr;
-    if (bnb) {
-        for (int j = 1; j < nk; ++j) { t->t_ky[j] = take((size_t)Mtot * t->kdims[j] * 4); t->t_kst[j] = take((size_t)T * 3 * t->kdims[j] * 4); }
-        for (int l = 0; l < L; ++l) { t->t_hy[l] = take((size_t)Mtot * 2 * D * 4); t->t_hst[l] = take((size_t)T * 3 * 2 * D * 4); }
-        if (t->conf_mlp) {
-            for (int q = 0; q < P; ++q) t->t_cy[q] = take((size_t)B * N * D * 4);
-            t->t_cst = take((size_t)P * 3 * D * 4);
-        }
-        t->t_part = (double*)take((size_t)T * BN_MAX_CHUNKS * 2 * 2 * D * 8);
-    }
-    t->B = B; t->T = T; t->N = N; t->n_rows = n_rows; t->iters = iters; t->P = P; t->ldS = ldS; t->Mtot = Mtot;
+    carve_tape(t, t->d_tape, fd->batch, fd->tuple_size, fd->n_kpts, fd->sinkhorn_iters);
     t->have_tape = false;
-
-    // ---- ingest: descriptors -> x_0 (desc part), keypoints -> encoder layer 0 ----
-    int Nt[E2EMV_MAX_TUPLE] = {0};
-    IngestParams ip{};
-    for (int i = 0; i < T; ++i) {
-        if (!d_kpts[i] || !d_kscores[i] || !d_desc[i]) return set_err(ctx, E2EMV_EINVAL, "matcher_forward_train: null input for image %d", i);
-        ip.kpts[i] = d_kpts[i]; ip.ksc[i] = d_kscores[i]; ip.desc[i] = d_desc[i];
-        ip.img_w[i] = fd->img_w[i]; ip.img_h[i] = fd->img_h[i];
-        ip.Nimg[i] = N; Nt[i] = N;
-    }
-    ip.B = B; ip.T = T; ip.n_rows = n_rows; ip.D = D; ip.c0 = t->kdims[1]; ip.f16 = fd->desc_dtype == E2EMV_DESC_F16;
-    ip.w0 = t->d_w + t->kw[0]; ip.b0 = t->d_w + t->kb[0]; ip.x0 = t->t_x[0]; ip.h0 = t->t_kh[1]; ip.inp = t->t_inp;
-    hipLaunchKernelGGL(ingest_transpose, dim3(n_rows / 64, D / 64, n_img), dim3(256), 0, s, ip);
-    hipLaunchKernelGGL(ingest_kenc0, dim3((n_rows + 255) / 256, n_img), dim3(256), 0, s, ip);
-    E2EMV_CHECK_LAUNCH(ctx, "ingest kernels");
-    int rc;
-    if (bnb) {  // layer 0 again, without the BatchNorm ingest_kenc0 fuses: y, then the batch-statistics BN + ReLU over t_kh[1]
-        const int c0 = t->kdims[1];
-        hipLaunchKernelGGL(kenc0_conv_kernel, dim3(ew_grid(Mtot * c0)), dim3(256), 0, s, (const float*)t->t_inp, (const float*)t->d_w + t->kw[0],
-                           (const float*)t->d_w + t->kb[0], c0, Mtot, t->t_ky[1]);
-        E2EMV_CHECK_LAUNCH(ctx, "kenc0_conv_kernel");
-        if ((rc = bn_forward(ctx, bn_images(t, 0, t->t_ky[1], t->t_kh[1], t->t_kst[1], t->t_part), T, s))) return rc;
-    }
-    // encoder layers 1 .. nk-1; the last adds the descriptors (x_0 = desc + kenc)
-    for (int i = 1; i < nk; ++i) {
-        const int cin = t->kdims[i], cout = t->kdims[i + 1];
-        const bool last = i == nk - 1;
-        GemmArgs g;
-        g.M = (int)Mtot; g.N = cout; g.K = cin; g.K1 = cin; g.A = t->t_kh[i]; g.lda = cin;
-        g.W = t->d_w + t->kw[i]; g.ldw = cin; g.bias = t->d_w + t->kb[i]; g.relu = !last && !bnb;
-        if (last) { g.R = t->t_x[0]; g.ldr = D; g.C = t->t_x[0]; g.ldc = D; }
-        else { g.C = bnb ? t->t_ky[i + 1] : t->t_kh[i + 1]; g.ldc = cout; }
-        if ((rc = launch_gemm_nt(ctx, g, s))) return rc;
-        if (bnb && !last && (rc = bn_forward(ctx, bn_images(t, i, t->t_ky[i + 1], t->t_kh[i + 1], t->t_kst[i + 1], t->t_part), T, s))) return rc;
-    }
-    // ---- attentional GNN (merge NOT folded: its parameters get their own gradients) ----
-    for (int l = 0; l < L; ++l) {
-        const TrainLayer& Lw = t->layers[l];
-        GemmArgs g;
-        g.M = (int)Mtot; g.N = 3 * D; g.K = D; g.K1 = D; g.A = t->t_x[l]; g.lda = D; g.W = t->d_w + Lw.wqkv; g.ldw = D; g.bias = t->d_w + Lw.bqkv;
-        g.C = t->t_qkv[l]; g.ldc = 3 * D;
-        if ((rc = launch_gemm_nt(ctx, g, s))) return rc;
-        if ((rc = launch_attention(ctx, B, T, n_rows, Nt, D, H, t->t_qkv[l], Lw.type, t->t_att[l], s))) return rc;
-        g = GemmArgs();
-        g.M = (int)Mtot; g.N = D; g.K = D; g.K1 = D; g.A = t->t_att[l]; g.lda = D; g.W = t->d_w + Lw.wm; g.ldw = D; g.bias = t->d_w + Lw.bm;
-        g.C = t->t_msg[l]; g.ldc = D;
-        if ((rc = launch_gemm_nt(ctx, g, s))) return rc;
-        g = GemmArgs();
-        g.M = (int)Mtot; g.N = 2 * D; g.K = 2 * D; g.K1 = D; g.A = t->t_x[l]; g.lda = D; g.A2 = t->t_msg[l]; g.lda2 = D;
-        g.W = t->d_w + Lw.w0; g.ldw = 2 * D; g.bias = t->d_w + Lw.b0; g.relu = !bnb; g.C = bnb ? t->t_hy[l] : t->t_h[l]; g.ldc = 2 * D;
-        if ((rc = launch_gemm_nt(ctx, g, s))) return rc;
-        if (bnb && (rc = bn_forward(ctx, bn_images(t, nk - 1 + l, t->t_hy[l], t->t_h[l], t->t_hst[l], t->t_part), T, s))) return rc;
-        g = GemmArgs();
-        g.M = (int)Mtot; g.N = D; g.K = 2 * D; g.K1 = 2 * D; g.A = t->t_h[l]; g.lda = 2 * D; g.W = t->d_w + Lw.w1; g.ldw = 2 * D; g.bias = t->d_w + Lw.b1;
-        g.R = t->t_x[l]; g.ldr = D; g.C = t->t_x[l + 1]; g.ldc = D;
-        if ((rc = launch_gemm_nt(ctx, g, s))) return rc;
-    }
-    {
-        GemmArgs g;
-        g.M = (int)Mtot; g.N = D; g.K = D; g.K1 = D; g.A = t->t_x[L]; g.lda = D; g.W = t->d_w + t->wf; g.ldw = D; g.bias = t->d_w + t->bf;
-        g.C = t->t_mdesc; g.ldc = D;
-        if ((rc = launch_gemm_nt(ctx, g, s))) return rc;
-    }
-    // ---- scores, Sinkhorn (log domain, u_t / v_t of every iteration kept), log assignment ----
-    const int64_t tuple_stride = (int64_t)T * n_rows * D;
-    SkT sk = sk_problem(nullptr, ldS, N, t->bin_score);
-    const int64_t uvs = (int64_t)(iters + 1) * 2 * (N + 1);  // per problem
-    int pidx = 0;
-    for (int j = 0; j < T; ++j)
-        for (int i = 0; i < j; ++i, ++pidx) {
-            float* S = t->t_S + (int64_t)pidx * B * N * ldS;
-            GemmArgs g;
-            g.batch = B; g.M = N; g.N = N; g.K = D; g.K1 = D;
-            g.A = t->t_mdesc + (int64_t)i * n_rows * D; g.lda = D; g.sA = tuple_stride;
-            g.W = t->t_mdesc + (int64_t)j * n_rows * D; g.ldw = D; g.sW = tuple_stride;
-            g.C = S; g.ldc = ldS; g.sC = (int64_t)N * ldS;
-            g.scale = 1.0f / sqrtf((float)D);
-            if ((rc = launch_gemm_nt(ctx, g, s))) return rc;
-            sk.S = S;
-            float* uv = t->t_uv + (int64_t)pidx * B * uvs;  // [b][t][{u, v}][N + 1]
-            if (!d_logZ[pidx]) return set_err(ctx, E2EMV_EINVAL, "matcher_forward_train: null logZ for pair %d", pidx);
-            if ((rc = sinkhorn_tape_forward(ctx, sk, B, iters, uv, d_logZ[pidx], 0, s))) return rc;
-        }
+    if (int rc = encode_train(ctx, t, fd, d_kpts, d_kscores, d_desc, s)) return rc;
+    if (int rc = gnn_train(ctx, t, s)) return rc;
+    if (int rc = scores_train(ctx, t, d_logZ, s)) return rc;
     t->have_tape = true;
     return E2EMV_OK;
 }
@@ -664,25 +710,22 @@ extern "C" int e2emv_conf_forward_train(e2emv_ctx* ctx, int pair, const int64_t*
     (void)hipSetDevice(ctx->device);
     hipStream_t s = (hipStream_t)stream;
     const int B = t->B, T = t->T, N = t->N, n_rows = t->n_rows, D = t->model.desc_dim;
-    int pi = 0, pj = 1, q = 0;
-    for (int j = 0; j < T; ++j)
-        for (int i = 0; i < j; ++i, ++q)
-            if (q == pair) { pi = i; pj = j; }
+    const int pi = tuple_pair(pair).i, pj = tuple_pair(pair).j;
     const int64_t tuple_stride = (int64_t)T * n_rows * D;
     float* feat = t->t_cfeat[pair];
     float* hid = t->t_chid[pair];
     hipLaunchKernelGGL(conf_feat_kernel, dim3((N + 3) / 4, B), dim3(256), 0, s, N, D, (const float*)t->t_mdesc + (int64_t)pi * n_rows * D,
                        (const float*)t->t_mdesc + (int64_t)pj * n_rows * D, tuple_stride, d_matches0, feat);
     E2EMV_CHECK_LAUNCH(ctx, "conf_feat_kernel");
-    GemmArgs g;
-    g.M = B * N; g.N = D; g.K = 2 * D; g.K1 = 2 * D; g.A = feat; g.lda = 2 * D; g.W = t->d_w + t->wc0; g.ldw = 2 * D; g.bias = t->d_w + t->bc0;
+    GemmArgs g = dense_gemm(t, t->conf0, (int64_t)B * N);
+    g.A = feat; g.lda = 2 * D;
     const bool bnb = t->bn_mode == E2EMV_BN_BATCH;
     g.relu = !bnb; g.C = bnb ? t->t_cy[pair] : hid; g.ldc = D;
     if (int rc = launch_gemm_nt(ctx, g, s)) return rc;
     if (bnb)
         if (int rc = bn_forward(ctx, bn_conf(t, t->t_cy[pair], hid, t->t_cst + (int64_t)pair * 3 * D, t->t_part), 1, s)) return rc;
     hipLaunchKernelGGL(conf_fwd_kernel, dim3((unsigned)(((int64_t)B * N + 3) / 4)), dim3(256), 0, s, (int64_t)B * N, D, (const float*)hid,
-                       (const float*)t->d_w + t->wc1, (const float*)t->d_w + t->bc1, d_matches0, d_conf);
+                       (const float*)t->d_w + t->conf1.w, (const float*)t->d_w + t->conf1.b, d_matches0, d_conf);
     E2EMV_CHECK_LAUNCH(ctx, "conf_fwd_kernel");
     t->t_cmatch[pair] = d_matches0;
     return E2EMV_OK;
@@ -739,6 +782,153 @@ static int attention_backward(e2emv_ctx* ctx, int B, int T, int N, int n_rows, i
     return E2EMV_OK;
 }
 
+// ---- the backward over the tape, in stages -----------------------------------------------------------------------------------
+// Scratch of e2emv_matcher_backward in the context's workspace.  Gradients of activations: dx, datt, dmd [Mtot][D], dh, dcat
+// [Mtot][2D], dqkv [Mtot][3D]; Sinkhorn: dC [B][N+1][N+1], du, dv, dv2 [B][N+1]; attention: Pb, dPb [B*H][N][n_src N]; bpart: the
+// partial sums of the BatchNorm backward (batch statistics only)
+struct BackwardWs { float *dx, *datt, *dmd, *dh, *dcat, *dqkv, *dC, *du, *dv, *dv2, *Pb, *dPb; double* bpart; size_t bytes; };
+// base == nullptr: the byte count only
+static BackwardWs carve_backward_ws(const TrainState* t, char* base) {
+    const size_t Mtot = (size_t)t->Mtot, D = t->model.desc_dim, B = t->B, N = t->N, H = t->model.num_heads;
+    const size_t n_src_max = t->T > 2 ? t->T - 1 : 1;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { float* p = base ? (float*)(base + off) : nullptr; off += al256(bytes); return p; };
+    BackwardWs w;
+    w.dx = take(Mtot * D * 4); w.datt = take(Mtot * D * 4); w.dmd = take(Mtot * D * 4);
+    w.dh = take(Mtot * 2 * D * 4); w.dcat = take(Mtot * 2 * D * 4);
+    w.dqkv = take(Mtot * 3 * D * 4); w.dC = take(B * (N + 1) * (N + 1) * 4);
+    w.du = take(B * (N + 1) * 4); w.dv = take(B * (N + 1) * 4); w.dv2 = take(B * (N + 1) * 4);
+    w.Pb = take(B * H * N * n_src_max * N * 4); w.dPb = take(B * H * N * n_src_max * N * 4);
+    w.bpart = t->bn_mode == E2EMV_BN_BATCH ? (double*)take((size_t)t->T * BN_MAX_CHUNKS * 2 * 2 * D * 8) : nullptr;
+    w.bytes = off + 4096;
+    return w;
+}
+
+// Sinkhorn reverse sweep and the score matrix, per pair with a d logZ: -> d alpha, d mdesc (added to w.dmd)
+static int scores_backward(e2emv_ctx* ctx, const TrainState* t, const BackwardWs& w, const float* const* d_dlogZ, hipStream_t s) {
+    const int B = t->B, N = t->N, n_rows = t->n_rows, D = t->model.desc_dim;
+    const int64_t tuple_stride = (int64_t)t->T * n_rows * D;
+    SkT sk = sk_problem(nullptr, t->ldS, N, t->bin_score);
+    const int64_t uvs = (int64_t)(t->iters + 1) * 2 * (N + 1), per = (int64_t)(N + 1) * (N + 1);
+    int rc;
+    for (int q = 0; q < t->P; ++q) {
+        if (!d_dlogZ[q]) continue;  // no gradient reaches this pair's scores
+        const TuplePair pr = tuple_pair(q);
+        sk.S = t->t_S + (int64_t)q * B * N * t->ldS;
+        const float* uv = t->t_uv + (int64_t)q * B * uvs;
+        if ((rc = sinkhorn_tape_backward(ctx, sk, B, t->iters, uv, d_dlogZ[q], w.dC, w.du, w.dv, w.dv2, t->d_gw + t->alpha, 0, s))) return rc;
+        // scores = md_i md_j^T / sqrt(D):  d md_i += dS md_j / sqrt(D),  d md_j += dS^T md_i / sqrt(D)
+        for (int side = 0; side < 2; ++side) {  // (side 1: dS read transposed)
+            const int to = side ? pr.j : pr.i, from = side ? pr.i : pr.j;
+            GG g;
+            g.batch = B; g.M = N; g.N = D; g.K = N;
+            g.A = w.dC; g.am = side ? 1 : N + 1; g.ak = side ? N + 1 : 1; g.az0 = per;
+            g.B = t->t_mdesc + (int64_t)from * n_rows * D; g.bk = D; g.bn = 1; g.bz0 = tuple_stride;
+            g.C = w.dmd + (int64_t)to * n_rows * D; g.ldc = D; g.cz0 = tuple_stride; g.alpha = 1.0f / sqrtf((float)D); g.mode = 1;
+            if ((rc = launch_gg(ctx, g, s))) return rc;
+        }
+    }
+    return E2EMV_OK;
+}
+
+// confidence heads (pose loss): d conf of every pair that has one -> conf_mlp gradients and two more contributions to d mdesc
+static int conf_heads_backward(e2emv_ctx* ctx, const TrainState* t, const BackwardWs& w, const float* const* d_dconf, hipStream_t s) {
+    const int B = t->B, N = t->N, n_rows = t->n_rows, D = t->model.desc_dim;
+    const int64_t tuple_stride = (int64_t)t->T * n_rows * D, rows = (int64_t)B * N;
+    const bool bnb = t->bn_mode == E2EMV_BN_BATCH;
+    int rc;
+    if (bnb && t->conf_mlp) {  // conf_mlp.1's dgamma / dbeta are summed over the pairs below (zero when no pair has a d conf)
+        E2EMV_HIP(ctx, hipMemsetAsync(t->d_graw + t->bns.back().gamma, 0, (size_t)D * sizeof(float), s));
+        E2EMV_HIP(ctx, hipMemsetAsync(t->d_graw + t->bns.back().beta, 0, (size_t)D * sizeof(float), s));
+    }
+    if (!d_dconf || !t->conf_mlp) return E2EMV_OK;
+    float* dz = w.du;       // [B*N]      (B (N + 1) floats available)
+    float* dhc = w.dcat;    // [B*N][D]
+    float* dfeat = w.dh;    // [B*N][2D]
+    for (int q = 0; q < t->P; ++q) {
+        if (!d_dconf[q]) continue;
+        if (!t->t_cmatch[q]) return set_err(ctx, E2EMV_ESTATE, "matcher_backward: d conf for pair %d without e2emv_conf_forward_train", q);
+        const TuplePair pr = tuple_pair(q);
+        hipLaunchKernelGGL(conf_bwd_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, rows, D, (const float*)t->t_chid[q],
+                           (const float*)t->d_w + t->conf1.w, (const float*)t->d_w + t->conf1.b, t->t_cmatch[q], d_dconf[q], dz, dhc);
+        E2EMV_CHECK_LAUNCH(ctx, "conf_bwd_kernel");
+        if ((rc = dense_backward(ctx, t, t->conf1, rows, dz, 1, t->t_chid[q], D, nullptr, 0, false, s))) return rc;  // (d hidden: conf_bwd_kernel's dhc)
+        if (bnb) {  // dhc: d hidden (ReLU mask applied) -> d y of conf_mlp.0; frozen: it is d y already
+            BnCall a = bn_conf(t, t->t_cy[q], dhc, t->t_cst + (int64_t)q * 3 * D, w.bpart);
+            a.h = t->t_chid[q]; a.accumulate = 1;
+            if ((rc = bn_backward(ctx, a, 1, s))) return rc;
+        }
+        if ((rc = dense_backward(ctx, t, t->conf0, rows, dhc, D, t->t_cfeat[q], 2 * D, dfeat, 2 * D, false, s))) return rc;
+        hipLaunchKernelGGL(conf_scatter_kernel, dim3((N + 3) / 4, B), dim3(256), 0, s, N, D, (const float*)dfeat, t->t_cmatch[q],
+                           w.dmd + (int64_t)pr.i * n_rows * D, w.dmd + (int64_t)pr.j * n_rows * D, tuple_stride, bnb ? 1 : 0);
+        E2EMV_CHECK_LAUNCH(ctx, "conf_scatter_kernel");
+    }
+    E2EMV_HIP(ctx, hipMemsetAsync(w.du, 0, (size_t)B * (N + 1) * sizeof(float), s));
+    return E2EMV_OK;
+}
+
+// GNN layer l: w.dx = d x_{l+1} on entry, d x_l on exit
+static int gnn_layer_backward(e2emv_ctx* ctx, const TrainState* t, const BackwardWs& w, int l, hipStream_t s) {
+    const int D = t->model.desc_dim, nk = (int)t->kenc.size();
+    const int64_t Mtot = t->Mtot;
+    const TrainLayer& Lw = t->layers[l];
+    int rc;
+    // x_{l+1} = x_l + W1 h + b1
+    if ((rc = dense_backward(ctx, t, Lw.mlp1, Mtot, w.dx, D, t->t_h[l], 2 * D, w.dh, 2 * D, false, s))) return rc;
+    // h = relu(W0 [x_l | msg] + b0), batch statistics: relu(BN(W0 [x_l | msg] + b0))
+    if ((rc = activation_backward(ctx, t, nk - 1 + l, 2 * D, t->t_hy[l], t->t_hst[l], t->t_h[l], w.dh, w.bpart, s))) return rc;
+    if ((rc = dense_backward(ctx, t, Lw.mlp0, Mtot, w.dh, 2 * D, t->t_x[l], D, w.dcat, 2 * D, false, s, t->t_msg[l], D))) return rc;
+    hipLaunchKernelGGL(add2d_kernel, dim3(ew_grid(Mtot * D)), dim3(256), 0, s, w.dx, (int64_t)D, (const float*)w.dcat, (int64_t)2 * D, Mtot, D);
+    // msg = Wm att + bm   (d msg = dcat[:, D:])
+    if ((rc = dense_backward(ctx, t, Lw.merge, Mtot, w.dcat + D, 2 * D, t->t_att[l], D, w.datt, D, false, s))) return rc;
+    // att = attention(q|k|v)
+    if ((rc = attention_backward(ctx, t->B, t->T, t->N, t->n_rows, D, t->model.num_heads, Lw.type != 0, t->t_qkv[l], w.datt, w.dqkv, w.Pb, w.dPb, s))) return rc;
+    // q|k|v = Wqkv x_l + b
+    if ((rc = dense_backward(ctx, t, Lw.qkv, Mtot, w.dqkv, 3 * D, t->t_x[l], D, w.dx, D, true, s))) return rc;
+    E2EMV_CHECK_LAUNCH(ctx, "layer backward kernels");
+    return E2EMV_OK;
+}
+
+// keypoint encoder, last layer to first: x_0 = desc + kenc(keypoints), w.dx = d kenc output.  Layer 0's input is the [Mtot][4]
+// keypoint record of the tape (3 columns used); no gradient w.r.t. it is needed
+static int encoder_backward(e2emv_ctx* ctx, const TrainState* t, const BackwardWs& w, hipStream_t s) {
+    const int nk = (int)t->kenc.size();
+    float* cur = w.dx;  // gradient w.r.t. the output of encoder layer i (width kdims[i + 1])
+    float* bufs[2] = {w.dh, w.dcat};
+    int rc;
+    for (int i = nk - 1; i >= 0; --i) {
+        const TrainDense& d = t->kenc[i];
+        if (i < nk - 1 && (rc = activation_backward(ctx, t, i, d.out, t->t_ky[i + 1], t->t_kst[i + 1], t->t_kh[i + 1], cur, w.bpart, s))) return rc;
+        float* dX = i ? bufs[(nk - 1 - i) & 1] : nullptr;
+        if ((rc = dense_backward(ctx, t, d, t->Mtot, cur, d.out, i ? t->t_kh[i] : t->t_inp, i ? d.in : 4, dX, d.in, false, s))) return rc;
+        cur = dX;
+    }
+    E2EMV_CHECK_LAUNCH(ctx, "encoder backward kernels");
+    return E2EMV_OK;
+}
+
+// folded gradients (d_gw) -> gradients of the upstream parameters (d_graw)
+static int unfold_grads(e2emv_ctx* ctx, const TrainState* t, hipStream_t s) {
+    const float* gw = t->d_gw;
+    auto ref = [&](const std::string& k) -> float* { auto it = t->raw.find(k); return it == t->raw.end() ? nullptr : t->d_raw + it->second.off; };
+    auto gref = [&](const std::string& k) -> float* { auto it = t->raw.find(k); return it == t->raw.end() ? nullptr : t->d_graw + it->second.off; };
+    for_each_folded(t, [&](const std::string& conv, const std::string& bn, const TrainDense& d, int rows, int rbase, const int* rmap, const int* cmap) {
+        UnfoldArgs a{};
+        a.dWf = gw + d.w + (int64_t)rbase * d.in; a.dbf = gw + d.b + rbase; a.ldwf = d.in; a.col0 = 0;
+        a.W = ref(conv + ".weight"); a.b = ref(conv + ".bias");
+        if (!bn.empty() && ref(bn + ".running_mean") && t->bn_mode == E2EMV_BN_FROZEN) {  // (batch statistics: dgamma / dbeta come from bn_backward)
+            a.gamma = ref(bn + ".weight"); a.beta = ref(bn + ".bias"); a.mean = ref(bn + ".running_mean"); a.var = ref(bn + ".running_var");
+            a.dgamma = gref(bn + ".weight"); a.dbeta = gref(bn + ".bias");
+        }
+        a.rmap = rmap; a.cmap = cmap; a.rows = rows; a.cols = d.in;
+        a.dW = gref(conv + ".weight"); a.db = gref(conv + ".bias");
+        hipLaunchKernelGGL(unfold_kernel, dim3(rows), dim3(256), 0, s, a);
+    });
+    E2EMV_HIP(ctx, hipMemcpyAsync(gref("bin_score"), gw + t->alpha, sizeof(float), hipMemcpyDeviceToDevice, s));
+    E2EMV_CHECK_LAUNCH(ctx, "unfold kernels");
+    return E2EMV_OK;
+}
+
 extern "C" int e2emv_matcher_backward(e2emv_ctx* ctx, const float* const* d_dlogZ, const float* const* d_dconf, void* stream) {
     if (!ctx || !d_dlogZ) return E2EMV_EINVAL;
     E2EMV_ENTER(ctx, stream);
@@ -746,205 +936,20 @@ extern "C" int e2emv_matcher_backward(e2emv_ctx* ctx, const float* const* d_dlog
     if (!t || !t->have_tape) return set_err(ctx, E2EMV_ESTATE, "matcher_backward: no tape - e2emv_matcher_forward_train first");
     (void)hipSetDevice(ctx->device);
     hipStream_t s = (hipStream_t)stream;
-    const int B = t->B, T = t->T, N = t->N, n_rows = t->n_rows, iters = t->iters, P = t->P, ldS = t->ldS;
-    const int D = t->model.desc_dim, H = t->model.num_heads, L = (int)t->layers.size();
-    const int64_t Mtot = t->Mtot;
-    const int nk = (int)t->kdims.size() - 1;
-    const int n_src_max = T > 2 ? T - 1 : 1;
-    // ---- workspace ----
-    const size_t sz_x = al256((size_t)Mtot * D * 4), sz_2 = al256((size_t)Mtot * 2 * D * 4), sz_3 = al256((size_t)Mtot * 3 * D * 4);
-    const size_t sz_C = al256((size_t)B * (N + 1) * (N + 1) * 4), sz_v = al256((size_t)B * (N + 1) * 4);
-    const size_t sz_P = al256((size_t)B * H * N * n_src_max * N * 4);
-    const bool bnb = t->bn_mode == E2EMV_BN_BATCH;
-    const size_t sz_bn = bnb ? al256((size_t)T * BN_MAX_CHUNKS * 2 * 2 * D * 8) : 0;
-    const size_t need = 3 * sz_x + 2 * sz_2 + sz_3 + sz_C + 3 * sz_v + 2 * sz_P + sz_bn + 4096;
-    int rc = ws_reserve(ctx, need);
+    int rc = ws_reserve(ctx, carve_backward_ws(t, nullptr).bytes);
     if (rc) return rc;
-    char* w = ctx->d_ws;
-    auto take = [&](size_t bytes) { float* p = (float*)w; w += bytes; return p; };
-    float* dx = take(sz_x);
-    float* datt = take(sz_x);
-    float* dmd = take(sz_x);
-    float* dh = take(sz_2);
-    float* dcat = take(sz_2);
-    float* dqkv = take(sz_3);
-    float* dC = take(sz_C);
-    float* du = take(sz_v);
-    float* dv = take(sz_v);
-    float* dv2 = take(sz_v);
-    float* Pb = take(sz_P);
-    float* dPb = take(sz_P);
-    double* bpart = bnb ? (double*)take(sz_bn) : nullptr;
-    float* gw = t->d_gw;
-    const float* W = t->d_w;
-    E2EMV_HIP(ctx, hipMemsetAsync(gw, 0, t->w_floats * sizeof(float), s));
-    E2EMV_HIP(ctx, hipMemsetAsync(dmd, 0, (size_t)Mtot * D * sizeof(float), s));
-    // ---- Sinkhorn reverse sweep and the score matrix, per pair ----
-    const int64_t tuple_stride = (int64_t)T * n_rows * D;
-    SkT sk = sk_problem(nullptr, ldS, N, t->bin_score);
-    const int64_t uvs = (int64_t)(iters + 1) * 2 * (N + 1);
-    const int64_t per = (int64_t)(N + 1) * (N + 1);
-    int pidx = 0;
-    for (int j = 0; j < T; ++j)
-        for (int i = 0; i < j; ++i, ++pidx) {
-            if (!d_dlogZ[pidx]) continue;  // no gradient reaches this pair's scores
-            sk.S = t->t_S + (int64_t)pidx * B * N * ldS;
-            const float* uv = t->t_uv + (int64_t)pidx * B * uvs;
-            if ((rc = sinkhorn_tape_backward(ctx, sk, B, iters, uv, d_dlogZ[pidx], dC, du, dv, dv2, gw + t->alpha, 0, s))) return rc;
-            // scores = md_i md_j^T / sqrt(D):  d md_i += dS md_j / sqrt(D),  d md_j += dS^T md_i / sqrt(D)
-            const float sc = 1.0f / sqrtf((float)D);
-            GG g;
-            g.batch = B; g.M = N; g.N = D; g.K = N;
-            g.A = dC; g.am = N + 1; g.ak = 1; g.az0 = per;
-            g.B = t->t_mdesc + (int64_t)j * n_rows * D; g.bk = D; g.bn = 1; g.bz0 = tuple_stride;
-            g.C = dmd + (int64_t)i * n_rows * D; g.ldc = D; g.cz0 = tuple_stride; g.alpha = sc; g.mode = 1;
-            if ((rc = launch_gg(ctx, g, s))) return rc;
-            g = GG();
-            g.batch = B; g.M = N; g.N = D; g.K = N;
-            g.A = dC; g.am = 1; g.ak = N + 1; g.az0 = per;
-            g.B = t->t_mdesc + (int64_t)i * n_rows * D; g.bk = D; g.bn = 1; g.bz0 = tuple_stride;
-            g.C = dmd + (int64_t)j * n_rows * D; g.ldc = D; g.cz0 = tuple_stride; g.alpha = sc; g.mode = 1;
-            if ((rc = launch_gg(ctx, g, s))) return rc;
-        }
-    // ---- confidence heads (pose loss): d conf -> conf_mlp gradients and two more contributions to d mdesc ----
-    if (bnb && t->conf_mlp) {  // conf_mlp.1's dgamma / dbeta are summed over the pairs below (zero when no pair has a d conf)
-        E2EMV_HIP(ctx, hipMemsetAsync(t->d_graw + t->bns.back().gamma, 0, (size_t)D * sizeof(float), s));
-        E2EMV_HIP(ctx, hipMemsetAsync(t->d_graw + t->bns.back().beta, 0, (size_t)D * sizeof(float), s));
-    }
-    if (d_dconf && t->conf_mlp) {
-        int q = 0;
-        for (int j = 0; j < T; ++j)
-            for (int i = 0; i < j; ++i, ++q) {
-                if (!d_dconf[q]) continue;
-                if (!t->t_cmatch[q]) return set_err(ctx, E2EMV_ESTATE, "matcher_backward: d conf for pair %d without e2emv_conf_forward_train", q);
-                const int64_t rows = (int64_t)B * N;
-                float* dz = du;       // [B*N]      (B (N + 1) floats available)
-                float* dhc = dcat;    // [B*N][D]
-                float* dfeat = dh;    // [B*N][2D]
-                hipLaunchKernelGGL(conf_bwd_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, rows, D, (const float*)t->t_chid[q],
-                                   W + t->wc1, W + t->bc1, t->t_cmatch[q], d_dconf[q], dz, dhc);
-                E2EMV_CHECK_LAUNCH(ctx, "conf_bwd_kernel");
-                if ((rc = wgrad(ctx, dz, 1, 1, t->t_chid[q], D, D, rows, gw + t->wc1, D, s))) return rc;
-                if ((rc = colsum(ctx, dz, rows, 1, 1, gw + t->bc1, s))) return rc;
-                if (bnb) {  // dhc: d hidden (ReLU mask applied) -> d y of conf_mlp.0
-                    BnCall a = bn_conf(t, t->t_cy[q], dhc, t->t_cst + (int64_t)q * 3 * D, bpart);
-                    a.h = t->t_chid[q];
-                    a.accumulate = 1;
-                    if ((rc = bn_backward(ctx, a, 1, s))) return rc;
-                }
-                if ((rc = wgrad(ctx, dhc, D, D, t->t_cfeat[q], 2 * D, 2 * D, rows, gw + t->wc0, 2 * D, s))) return rc;
-                if ((rc = colsum(ctx, dhc, rows, D, D, gw + t->bc0, s))) return rc;
-                if ((rc = dgrad(ctx, dhc, D, D, W + t->wc0, 2 * D, 2 * D, rows, dfeat, 2 * D, false, s))) return rc;
-                hipLaunchKernelGGL(conf_scatter_kernel, dim3((N + 3) / 4, B), dim3(256), 0, s, N, D, (const float*)dfeat, t->t_cmatch[q],
-                                   dmd + (int64_t)i * n_rows * D, dmd + (int64_t)j * n_rows * D, tuple_stride, bnb ? 1 : 0);
-                E2EMV_CHECK_LAUNCH(ctx, "conf_scatter_kernel");
-            }
-        E2EMV_HIP(ctx, hipMemsetAsync(du, 0, (size_t)B * (N + 1) * sizeof(float), s));
-    }
-    // ---- final_proj ----
-    if ((rc = wgrad(ctx, dmd, D, D, t->t_x[L], D, D, Mtot, gw + t->wf, D, s))) return rc;
-    if ((rc = colsum(ctx, dmd, Mtot, D, D, gw + t->bf, s))) return rc;
-    if ((rc = dgrad(ctx, dmd, D, D, W + t->wf, D, D, Mtot, dx, D, false, s))) return rc;
-    // ---- GNN layers, last to first; dx = d x_{l+1} on entry, d x_l on exit ----
-    for (int l = L - 1; l >= 0; --l) {
-        const TrainLayer& Lw = t->layers[l];
-        // x_{l+1} = x_l + W1 h + b1
-        if ((rc = dgrad(ctx, dx, D, D, W + Lw.w1, 2 * D, 2 * D, Mtot, dh, 2 * D, false, s))) return rc;
-        if ((rc = wgrad(ctx, dx, D, D, t->t_h[l], 2 * D, 2 * D, Mtot, gw + Lw.w1, 2 * D, s))) return rc;
-        if ((rc = colsum(ctx, dx, Mtot, D, D, gw + Lw.b1, s))) return rc;
-        // h = relu(W0 [x_l | msg] + b0)
-        if (bnb) {  // h = relu(BN(y)), y = W0 [x_l | msg] + b0 (batch statistics): dh -> dy
-            BnCall a = bn_images(t, nk - 1 + l, t->t_hy[l], dh, t->t_hst[l], bpart);
-            a.h = t->t_h[l];
-            if ((rc = bn_backward(ctx, a, T, s))) return rc;
-        } else {
-            hipLaunchKernelGGL(relu_bwd_kernel, dim3(ew_grid(Mtot * 2 * D)), dim3(256), 0, s, dh, (const float*)t->t_h[l], Mtot * 2 * D);
-        }
-        if ((rc = dgrad(ctx, dh, 2 * D, 2 * D, W + Lw.w0, 2 * D, 2 * D, Mtot, dcat, 2 * D, false, s))) return rc;
-        if ((rc = wgrad(ctx, dh, 2 * D, 2 * D, t->t_x[l], D, D, Mtot, gw + Lw.w0, 2 * D, s))) return rc;
-        if ((rc = wgrad(ctx, dh, 2 * D, 2 * D, t->t_msg[l], D, D, Mtot, gw + Lw.w0 + D, 2 * D, s))) return rc;
-        if ((rc = colsum(ctx, dh, Mtot, 2 * D, 2 * D, gw + Lw.b0, s))) return rc;
-        hipLaunchKernelGGL(add2d_kernel, dim3(ew_grid(Mtot * D)), dim3(256), 0, s, dx, (int64_t)D, (const float*)dcat, (int64_t)2 * D, Mtot, D);
-        // msg = Wm att + bm   (d msg = dcat[:, D:])
-        if ((rc = dgrad(ctx, dcat + D, 2 * D, D, W + Lw.wm, D, D, Mtot, datt, D, false, s))) return rc;
-        if ((rc = wgrad(ctx, dcat + D, 2 * D, D, t->t_att[l], D, D, Mtot, gw + Lw.wm, D, s))) return rc;
-        if ((rc = colsum(ctx, dcat + D, Mtot, D, 2 * D, gw + Lw.bm, s))) return rc;
-        // att = attention(q|k|v)
-        if ((rc = attention_backward(ctx, B, T, N, n_rows, D, H, Lw.type != 0, t->t_qkv[l], datt, dqkv, Pb, dPb, s))) return rc;
-        // q|k|v = Wqkv x_l + b
-        if ((rc = dgrad(ctx, dqkv, 3 * D, 3 * D, W + Lw.wqkv, D, D, Mtot, dx, D, true, s))) return rc;
-        if ((rc = wgrad(ctx, dqkv, 3 * D, 3 * D, t->t_x[l], D, D, Mtot, gw + Lw.wqkv, D, s))) return rc;
-        if ((rc = colsum(ctx, dqkv, Mtot, 3 * D, 3 * D, gw + Lw.bqkv, s))) return rc;
-        E2EMV_CHECK_LAUNCH(ctx, "layer backward kernels");
-    }
-    // ---- keypoint encoder: x_0 = desc + kenc(keypoints); dx = d kenc output ----
-    {
-        float* cur = dx;  // gradient w.r.t. the output of encoder layer i (width kdims[i + 1])
-        float* bufs[2] = {dh, dcat};
-        int bi = 0;
-        for (int i = nk - 1; i >= 1; --i) {
-            const int cin = t->kdims[i], cout = t->kdims[i + 1];
-            if (i < nk - 1 && bnb) {
-                BnCall a = bn_images(t, i, t->t_ky[i + 1], cur, t->t_kst[i + 1], bpart);
-                a.h = t->t_kh[i + 1];
-                if ((rc = bn_backward(ctx, a, T, s))) return rc;
-            } else if (i < nk - 1) {
-                hipLaunchKernelGGL(relu_bwd_kernel, dim3(ew_grid(Mtot * cout)), dim3(256), 0, s, cur, (const float*)t->t_kh[i + 1], Mtot * cout);
-            }
-            if ((rc = wgrad(ctx, cur, cout, cout, t->t_kh[i], cin, cin, Mtot, gw + t->kw[i], cin, s))) return rc;
-            if ((rc = colsum(ctx, cur, Mtot, cout, cout, gw + t->kb[i], s))) return rc;
-            if ((rc = dgrad(ctx, cur, cout, cout, W + t->kw[i], cin, cin, Mtot, bufs[bi], cin, false, s))) return rc;
-            cur = bufs[bi];
-            bi ^= 1;
-        }
-        // layer 0: 3 -> c0 (+ BN folded, ReLU); its input is re-derived from the keypoints: not kept, the gradient w.r.t. it is not needed
-        const int c0 = t->kdims[1];
-        if (bnb) {
-            BnCall a = bn_images(t, 0, t->t_ky[1], cur, t->t_kst[1], bpart);
-            a.h = t->t_kh[1];
-            if ((rc = bn_backward(ctx, a, T, s))) return rc;
-        } else {
-            hipLaunchKernelGGL(relu_bwd_kernel, dim3(ew_grid(Mtot * c0)), dim3(256), 0, s, cur, (const float*)t->t_kh[1], Mtot * c0);
-        }
-        if ((rc = wgrad(ctx, cur, c0, c0, t->t_inp, 4, 3, Mtot, gw + t->kw[0], 3, s))) return rc;
-        if ((rc = colsum(ctx, cur, Mtot, c0, c0, gw + t->kb[0], s))) return rc;
-        E2EMV_CHECK_LAUNCH(ctx, "encoder backward kernels");
-    }
-    // ---- folded gradients -> gradients of the upstream parameters ----
-    auto ref = [&](const std::string& k) -> float* { auto it = t->raw.find(k); return it == t->raw.end() ? nullptr : t->d_raw + it->second.off; };
-    auto gref = [&](const std::string& k) -> float* { auto it = t->raw.find(k); return it == t->raw.end() ? nullptr : t->d_graw + it->second.off; };
-    auto unfold = [&](const std::string& conv, const std::string& bn, const float* dWf, const float* dbf, int64_t ldwf, int col0, int rows, int cols, const int* rmap,
-                      int rbase, const int* cmap) {
-        UnfoldArgs a{};
-        a.dWf = dWf + (int64_t)rbase * ldwf; a.dbf = dbf + rbase; a.ldwf = ldwf; a.col0 = col0;
-        a.W = ref(conv + ".weight"); a.b = ref(conv + ".bias");
-        if (!bn.empty() && ref(bn + ".running_mean") && t->bn_mode == E2EMV_BN_FROZEN) {  // (batch statistics: dgamma / dbeta come from bn_backward)
-            a.gamma = ref(bn + ".weight"); a.beta = ref(bn + ".bias"); a.mean = ref(bn + ".running_mean"); a.var = ref(bn + ".running_var");
-            a.dgamma = gref(bn + ".weight"); a.dbeta = gref(bn + ".bias");
-        }
-        a.rmap = rmap; a.cmap = cmap; a.rows = rows; a.cols = cols;
-        a.dW = gref(conv + ".weight"); a.db = gref(conv + ".bias");
-        hipLaunchKernelGGL(unfold_kernel, dim3(rows), dim3(256), 0, s, a);
-    };
-    for (int i = 0; i < nk; ++i)
-        unfold("kenc.encoder." + std::to_string(3 * i), i < nk - 1 ? "kenc.encoder." + std::to_string(3 * i + 1) : std::string(), gw + t->kw[i], gw + t->kb[i], t->kdims[i],
-               0, t->kdims[i + 1], t->kdims[i], nullptr, 0, nullptr);
-    for (int l = 0; l < L; ++l) {
-        const TrainLayer& Lw = t->layers[l];
-        const std::string base = "gnn.layers." + std::to_string(l);
-        for (int p = 0; p < 3; ++p) unfold(base + ".attn.proj." + std::to_string(p), "", gw + Lw.wqkv, gw + Lw.bqkv, D, 0, D, D, t->d_maps, p * D, nullptr);
-        unfold(base + ".attn.merge", "", gw + Lw.wm, gw + Lw.bm, D, 0, D, D, nullptr, 0, t->d_maps);
-        unfold(base + ".mlp.0", base + ".mlp.1", gw + Lw.w0, gw + Lw.b0, 2 * D, 0, 2 * D, 2 * D, nullptr, 0, nullptr);
-        unfold(base + ".mlp.3", "", gw + Lw.w1, gw + Lw.b1, 2 * D, 0, D, 2 * D, nullptr, 0, nullptr);
-    }
-    unfold("final_proj", "", gw + t->wf, gw + t->bf, D, 0, D, D, nullptr, 0, nullptr);
-    if (t->conf_mlp) {
-        unfold("conf_mlp.0", "conf_mlp.1", gw + t->wc0, gw + t->bc0, 2 * D, 0, D, 2 * D, nullptr, 0, nullptr);
-        unfold("conf_mlp.3", "", gw + t->wc1, gw + t->bc1, D, 0, 1, D, nullptr, 0, nullptr);
-    }
-    E2EMV_HIP(ctx, hipMemcpyAsync(gref("bin_score"), gw + t->alpha, sizeof(float), hipMemcpyDeviceToDevice, s));
-    E2EMV_CHECK_LAUNCH(ctx, "unfold kernels");
-    return E2EMV_OK;
+    const BackwardWs w = carve_backward_ws(t, ctx->d_ws);
+    const int D = t->model.desc_dim, L = (int)t->layers.size();
+    E2EMV_HIP(ctx, hipMemsetAsync(t->d_gw, 0, t->w_floats * sizeof(float), s));
+    E2EMV_HIP(ctx, hipMemsetAsync(w.dmd, 0, (size_t)t->Mtot * D * sizeof(float), s));
+    if ((rc = scores_backward(ctx, t, w, d_dlogZ, s))) return rc;
+    if ((rc = conf_heads_backward(ctx, t, w, d_dconf, s))) return rc;
+    // final_proj: w.dx = d x_L
+    if ((rc = dense_backward(ctx, t, t->final_proj, t->Mtot, w.dmd, D, t->t_x[L], D, w.dx, D, false, s))) return rc;
+    for (int l = L - 1; l >= 0; --l)
+        if ((rc = gnn_layer_backward(ctx, t, w, l, s))) return rc;
+    if ((rc = encoder_backward(ctx, t, w, s))) return rc;
+    return unfold_grads(ctx, t, s);
 }
 
 extern "C" int e2emv_get_grad(e2emv_ctx* ctx, const char* key, float* d_dst, int64_t numel, void* stream) {
@@ -1015,7 +1020,7 @@ extern "C" int e2emv_train_running_update(e2emv_ctx* ctx, int n, const char* con
 // ---- building blocks of the training path: one stage each, through the functions the forward / backward above call ----------
 // They need no committed model and no tape; their scratch is the context's workspace, a tape in the context is left alone.
 
-// y = x W^T + b over `rows` rows: wgrad, colsum and dgrad as e2emv_matcher_backward calls them for a dense layer
+// y = x W^T + b over `rows` rows: linear_backward, the function dense_backward runs for every dense layer of the backward
 extern "C" int e2emv_train_linear_backward(e2emv_ctx* ctx, int64_t rows, int n_out, int n_in, const float* d_dY, int64_t ldy, const float* d_X, int64_t ldx,
                                            const float* d_W, int64_t ldw, float* d_dW, float* d_db, float* d_dX, int accumulate, void* stream) {
     if (!ctx || !d_dY || !d_X || !d_W || !d_dW || !d_db) return E2EMV_EINVAL;
@@ -1026,12 +1031,7 @@ extern "C" int e2emv_train_linear_backward(e2emv_ctx* ctx, int64_t rows, int n_o
         return set_err(ctx, E2EMV_ESHAPE, "train_linear_backward: a row stride is shorter than its row (ldy=%lld ldx=%lld ldw=%lld)", (long long)ldy,
                        (long long)ldx, (long long)ldw);
     (void)hipSetDevice(ctx->device);
-    hipStream_t s = (hipStream_t)stream;
-    int rc;
-    if ((rc = wgrad(ctx, d_dY, ldy, n_out, d_X, ldx, n_in, rows, d_dW, ldw, s))) return rc;
-    if ((rc = colsum(ctx, d_dY, rows, n_out, ldy, d_db, s))) return rc;
-    if (d_dX && (rc = dgrad(ctx, d_dY, ldy, n_out, d_W, ldw, n_in, rows, d_dX, ldx, accumulate != 0, s))) return rc;
-    return E2EMV_OK;
+    return linear_backward(ctx, d_W, d_dW, ldw, d_db, n_out, n_in, rows, d_dY, ldy, d_X, ldx, nullptr, 0, d_dX, ldx, accumulate != 0, (hipStream_t)stream);
 }
 
 // the unrolled Sinkhorn of B problems of N x N scores with its tape, and (d_G given) the reverse sweep over that tape

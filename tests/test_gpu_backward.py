@@ -88,7 +88,7 @@ def _grads(cfg, data_kw, gpu, seed):
     return model, leaves, out, ref, pairs
 
 
-def _check(model, leaves, conf_too=False):
+def _check(model, leaves, conf_too=False, free=()):
     assert _has_finite_gradients(model)
     worst = {}
     for k, p in model.named_parameters():
@@ -97,8 +97,9 @@ def _check(model, leaves, conf_too=False):
         assert p.grad is not None, k
         g, gr = p.grad.cpu().double(), leaves[k].grad.double()
         assert g.shape == gr.shape, k
-        if k.endswith("attn.proj.1.bias"):
-            # a bias on the keys shifts every logit of a query alike: the softmax, hence the loss, does not depend on it.
+        if k.endswith("attn.proj.1.bias") or k in free:
+            # a bias on the keys shifts every logit of a query alike: the softmax, hence the loss, does not depend on it (`free`: nor
+            # on these biases, which a batch-statistics BatchNorm subtracts again - test_gpu_batchnorm_train._loss_free_biases).
             # Both gradients are rounding noise around zero - compare them with the scale of the weight's gradient instead.
             scale = float(leaves[k.replace(".bias", ".weight")].grad.double().norm())
             assert float(g.norm()) < REL * scale and float(gr.norm()) < REL * scale, k
@@ -450,3 +451,76 @@ def test_stage2_step_the_way_run_matcher_drives_it(gpu):
         assert all(p.grad is not None and float(p.grad.abs().max()) > 0 for p in conf_params)
         opt.step()
     assert all(not torch.equal(a, p.detach()) for a, p in zip(before, conf_params))
+
+
+# ------------------------------------------------------------------------------------------ every region of the tape at once
+# A triplet (three score matrices, three conf heads), conf_mlp, batch-statistics BatchNorm, two layers (self, cross), B = 2 and
+# N = 129: n_rows = 256 != N, the score stride 132 != N, the tape holds every region it can hold and no two of a kind with
+# another kind's size - a region carved too short, or over its neighbour, is a wrong gradient.  The data seed is chosen on the CPU,
+# from the oracle alone (tests/test_train_blocks.py::test_reference_of_the_all_regions_case_is_well_conditioned).
+TAPE_CASE = dict(B=2, N=129, T=3, iters=3, data_seed=1)
+
+
+def _all_regions_reference(data_seed, dtype=torch.float64):
+    """The CPU half (no GPU needed): model, inputs and the oracle's loss and gradients, the oracle in `dtype` with torch's
+    training-mode batch_norm (fp64: what the device is held to; fp32: how well the problem is conditioned in the device's own
+    precision).  Loss: the match loss of the three score matrices + a fixed random linear functional of the three conf_scores."""
+    import oracle.matcher as OM
+    import test_gpu_batchnorm_train as BT
+    from e2e_multi_view_matching_amd import MultiViewMatcher
+    from e2e_multi_view_matching_amd.synthetic import identity_like_state, make_tuples
+    B, N, T = TAPE_CASE["B"], TAPE_CASE["N"], TAPE_CASE["T"]
+    torch.manual_seed(31)
+    cfg = {"GNN_layers": ["self", "cross"], "sinkhorn_iterations": TAPE_CASE["iters"], "conf_mlp": True, "match_threshold": 0.2,
+           "full_output": True, "multi_frame_matching": True, "tuple_size": T, "frozen_batchnorm": False}
+    model = MultiViewMatcher(cfg)
+    _randomize_bn(model, 31)
+    identity_like_state(model)
+    with torch.no_grad():  # (as test_gpu_batchnorm_train's stage-2 case: the descriptors, not the perturbation, decide the matches)
+        g = torch.Generator().manual_seed(32)
+        for k, prm in model.named_parameters():
+            res = k.endswith("mlp.3.weight") or k == "kenc.encoder.12.weight"
+            prm.add_(torch.randn(prm.shape, generator=g) * (0.001 if res else 0.01 if prm.dim() > 1 else 0.005))
+    data = make_tuples(batch=B, tuple_size=T, n_kpts=N, seed=data_seed)
+    pairs = [(i, j) for j in range(T) for i in range(j)]
+    targets = {p: _targets(B, N, 3100 + n) for n, p in enumerate(pairs)}
+    Wc = {p: torch.randn(B, N, 1, generator=torch.Generator().manual_seed(3200 + n)) for n, p in enumerate(pairs)}
+
+    def loss_of(out):
+        dev = out["scores_0_1"].device
+        match = sum(_match_loss(out[f"scores_{i}_{j}"], targets[(i, j)][0].to(dev), targets[(i, j)][1].to(dev)) for i, j in pairs)
+        return match.double() + 5.0 * sum((out[f"conf_scores_{i}_{j}"].double() * Wc[(i, j)].to(dev).double()).sum() for i, j in pairs)
+
+    cast = lambda v: v.detach().to(dtype) if torch.is_tensor(v) and v.is_floating_point() else v
+    sd = {k: cast(v.clone()) for k, v in model.state_dict().items()}
+    leaves = {k: sd[k].requires_grad_(True) for k, _ in model.named_parameters()}
+    ocfg = dict(model.config)
+    ocfg.update(full_output=True, grad=True)
+    for k in ("mfma_precision", "autograd", "check_finite", "frozen_batchnorm"):
+        ocfg.pop(k, None)
+    eval_bn, OM.batchnorm_eval = OM.batchnorm_eval, BT.BatchStatBN(sd)
+    try:
+        ref = OM.matcher_forward({k: cast(v) for k, v in data.items()}, sd, ocfg)
+    finally:
+        OM.batchnorm_eval = eval_bn
+    loss_ref = loss_of(ref)
+    loss_ref.backward()
+    return dict(model=model, data=data, pairs=pairs, loss_of=loss_of, leaves=leaves, ref=ref, loss_ref=loss_ref, free=BT._loss_free_biases(model))
+
+
+def test_every_tape_region_at_once(gpu):
+    r = _all_regions_reference(TAPE_CASE["data_seed"])
+    pairs, ref = r["pairs"], r["ref"]
+    model = r["model"].to(gpu).train()
+    out = model({k: (v.to(gpu) if torch.is_tensor(v) else v) for k, v in r["data"].items()})
+    for i, j in pairs:
+        assert torch.equal(out[f"matches{i}_{i}_{j}"].cpu(), ref[f"matches{i}_{i}_{j}"]), (i, j)
+        assert float((out[f"scores_{i}_{j}"].detach().cpu() - ref[f"scores_{i}_{j}"].detach()).abs().max()) < 1e-4, (i, j)
+        assert out[f"conf_scores_{i}_{j}"].requires_grad
+        assert float((out[f"conf_scores_{i}_{j}"].detach().cpu() - ref[f"conf_scores_{i}_{j}"].detach()).abs().max()) < 1e-5, (i, j)
+    loss = r["loss_of"](out)
+    loss.backward()
+    assert abs(loss.item() - r["loss_ref"].item()) < 1e-3 * abs(r["loss_ref"].item()), (loss.item(), r["loss_ref"].item())
+    worst = _check(model, r["leaves"], conf_too=True, free=r["free"])
+    print("worst relative gradient error per parameter:", {k: f"{v:.1e}" for k, v in worst.items() if v > 1e-5})
+    assert len(worst) == sum(1 for _ in model.parameters())
