@@ -32,7 +32,9 @@
 // LDS: three regions of 32 KB, region j % 3 = [ V(j) | K(j+1) ], filled by LDS-direct loads TWO tiles ahead (issued in
 // segment X(j-2), awaited with a counted vmcnt at the one barrier of a tile, slot 36 of segment Y(j-1): the workgroups of
 // an (image, head) walk its keys in lock step, so every tile is an L2 miss for all of them - one tile of lead did not cover
-// it); fragment reads run two groups of 6 MFMAs ahead of their first use, across the tile boundary.
+// it); fragment reads run two groups of 6 MFMAs ahead of their first use, across the tile boundary.  Behind the regions: the tile
+// exponents (2 KB) and the Q images of waves 1 .. 3 (16 KB each; wave 0's is the V half of region 2, which nobody writes before
+// segment X(0)) - a wave's 64 query rows, staged in whole cache lines and read from there into the accumulator file once.
 #include <algorithm>
 #include <type_traits>
 
@@ -45,6 +47,9 @@ typedef __attribute__((ext_vector_type(16))) float aw_f32x16;
 constexpr int AW_QT = 256;              // queries per workgroup
 constexpr int AW_TILEB = 64 * 256;      // one operand tile: 64 rows x 256 B
 constexpr int AW_REGB = 2 * AW_TILEB;   // region: V(j) | K(j+1)
+constexpr int AW_ELS = 3 * AW_REGB;      // the tile exponents (2 KB) behind the three regions
+constexpr int AW_QIMG = AW_ELS + 2048;  // the Q images (64 rows x 256 B each) of waves 1 .. 3; wave 0's: the V half of region 2
+constexpr int AW_LDS = AW_QIMG + 3 * AW_TILEB;
 constexpr int AW_PART_F = 68;           // floats of a key-split part's record per query: O[64], m, l (+ 2: 16-byte rows)
 // Softmax numerators carry the factor 2^AW_PLOG against the stream's running maximum.  7 (attention_p2: 10) leaves the fast
 // path 8.9 bits of growth of a row's maximum before its sum check sends the tile through the slow path - measured with 10:
@@ -53,8 +58,10 @@ constexpr int AW_PART_F = 68;           // floats of a key-split part's record p
 // low plane (fp16 subnormals) - 2^-21 of the row sum at worst.
 constexpr float AW_SINV = 1.f / P2_QS, AW_PLOG = 7.f, AW_LIMIT = 60000.f;
 
-__device__ __forceinline__ void aw_wait_q(p2_f16x8 (&q)[2][2][4]) {
-    asm volatile("s_waitcnt vmcnt(16)"
+// the wave's 16 asm reads of its Q image have landed in the accumulator file (lgkmcnt), its own pieces of K(0) - the youngest
+// loads so far - in LDS (vmcnt), and then everybody's (the barrier)
+__device__ __forceinline__ void aw_wait_q_k0(p2_f16x8 (&q)[2][2][4]) {
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier"
                  : "+a"(q[0][0][0]), "+a"(q[0][0][1]), "+a"(q[0][0][2]), "+a"(q[0][0][3]), "+a"(q[0][1][0]), "+a"(q[0][1][1]), "+a"(q[0][1][2]), "+a"(q[0][1][3]),
                    "+a"(q[1][0][0]), "+a"(q[1][0][1]), "+a"(q[1][0][2]), "+a"(q[1][0][3]), "+a"(q[1][1][0]), "+a"(q[1][1][1]), "+a"(q[1][1][2]), "+a"(q[1][1][3])
                  :: "memory");
@@ -132,7 +139,7 @@ __device__ __forceinline__ void aw_mfma_oa(aw_f32x16& c, p2_f16x8 a, p2_u32x4 b)
     asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+a"(c) : "a"(a), "v"(b));
 }
 // One fragment (16 bytes per lane) from LDS into its home.  IMM = (V | K) x AW_TILEB + row block x 8192 is the instruction's
-// immediate offset.  Like aw_load_q an asm load is not counted by hipcc: aw_wait_frag is the wait.
+// immediate offset.  An asm load is not counted by hipcc: aw_wait_frag is the wait.
 template <int IMM>
 __device__ __forceinline__ void aw_read_frag(p2_f16x8& d, unsigned addr) {
     static_assert(IMM >= 0 && IMM < 65536, "ds_read offset: 16 bits");
@@ -148,23 +155,6 @@ template <int N>
 __device__ __forceinline__ void aw_wait_frag(p2_f16x8 (&f)[4]) {
     asm volatile("s_waitcnt lgkmcnt(%4)" : "+a"(f[0]), "+a"(f[1]), "+a"(f[2]), "+a"(f[3]) : "n"(N));
 }
-// the 8 fragments of a query row (2 planes x 4 steps of 16 dims), loaded from global memory straight INTO the accumulator
-// file, where they stay.  An asm load is not counted by hipcc: aw_wait_q, which names every destination, is the wait (it
-// sits behind the first tiles' LDS-direct loads: one latency for all of the prologue's loads)
-__device__ __forceinline__ void aw_load_q(const char* qp, p2_f16x8 (&q)[2][4]) {
-    asm volatile(
-        "global_load_dwordx4 %0, %8, off\n\t"
-        "global_load_dwordx4 %1, %8, off offset:32\n\t"
-        "global_load_dwordx4 %2, %8, off offset:128\n\t"
-        "global_load_dwordx4 %3, %8, off offset:160\n\t"
-        "global_load_dwordx4 %4, %8, off offset:64\n\t"
-        "global_load_dwordx4 %5, %8, off offset:96\n\t"
-        "global_load_dwordx4 %6, %8, off offset:192\n\t"
-        "global_load_dwordx4 %7, %8, off offset:224"
-        : "=&a"(q[0][0]), "=&a"(q[0][1]), "=&a"(q[0][2]), "=&a"(q[0][3]), "=&a"(q[1][0]), "=&a"(q[1][1]), "=&a"(q[1][2]), "=&a"(q[1][3])
-        : "v"(qp) : "memory");
-}
-
 // MULTI: more than one source image per query image (cross layers of tuples with T > 2); without it the tile walk is a counter
 // PART: the instantiation that walks the key-split PARTS of a launch's leftover items (its own launch behind the whole items': the
 // whole-item kernel stays the code it was - carrying the part logic as run-time flags cost it 6 % at configs[1])
@@ -204,11 +194,30 @@ __global__ __launch_bounds__(256, 1) void attention_p2w_kernel(AttnP2Params p) {
     for (int a = 0; a < 2; ++a) {
         q_row[a] = qt * AW_QT + wave * 64 + a * 32 + l31;
         q_ok[a] = q_row[a] < p.n_rows;
-        const char* qp = reinterpret_cast<const char*>(p.qk) + ((int64_t)img * p.n_rows + (q_ok[a] ? q_row[a] : p.n_rows - 1)) * row_b + head * 256;
-        aw_load_q(qp + lh * 16, Qf[a]);  // chunk ((s >> 1) * 8 + pl * 4 + 2 * (s & 1) + lh) of the row's 16
     }
     const int q_blk = __builtin_amdgcn_readfirstlane(((int64_t)img * p.n_rows + min(qt * AW_QT + wave * 64, p.n_rows - 1)) >> 6);
-    const int e_q = HAS_E ? p.EQK[q_blk * 8 + head] : 0;
+    // (q's exponent is a vector load: issued in front of the Q pieces, used behind them - a use in front would drain them)
+    const int e_q_v = HAS_E ? p.EQK[q_blk * 8 + head] : 0;
+    // The wave's 64 query rows x 256 B (this head's q slice of the q | k rows) go through an LDS image of its own: 16 LDS-direct
+    // pieces of 4 rows x 256 B, lanes and swizzle as the K pieces' (below) - whole cache lines, where fragment-shaped loads into
+    // the accumulator file touched 32 lines per instruction for a quarter of each.  Rows at and beyond n_rows: the last row, per
+    // lane.  They go out HERE, in front of the walk's set-up, which needs none of them: the first loads of an item are what
+    // the item waits for longest.
+    const unsigned q_img = wave == 0 ? 2u * AW_REGB : (unsigned)(AW_QIMG + (wave - 1) * AW_TILEB);
+    {
+        const __amdgpu_buffer_rsrc_t rsQ = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(p.qk), 0, (int)p.qk_bytes, 0x00020000);
+        const unsigned so = (unsigned)(img * p.n_rows) * row_b;
+        asm volatile("" ::: "memory");
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const int rl = 4 * i + (lane >> 4);
+            const int row = min(qt * AW_QT + wave * 64 + rl, p.n_rows - 1);
+            const unsigned c = (unsigned)((lane & 15) ^ (rl & 15));
+            p2_glds16(rsQ, smem_aw + q_img + i * 1024, (unsigned)row * row_b + (unsigned)head * 256u + c * 16u, so);
+        }
+        asm volatile("" ::: "memory");
+    }
+    const int e_q = __builtin_amdgcn_readfirstlane(e_q_v);
 
     // ---- the tiles of this image's sources, in order.  A cursor = (source, tile in it, that source's keypoint count); the
     // count is re-read from the kernel arguments only when a cursor moves to the next source
@@ -265,8 +274,8 @@ __global__ __launch_bounds__(256, 1) void attention_p2w_kernel(AttnP2Params p) {
     // Tile exponents (k's and v's of every 64-key tile this workgroup walks): copied into LDS once, in the prologue, and read
     // from there as {e_k, e_v} pairs a segment ahead of their use.  (Fetched from global memory inside the loop they sat on the
     // same in-order counter as the tiles' pieces, and every use - or copy - of one drained the loads behind it.)
-    // (loaded first of all - the oldest operations of the prologue's one queue - and written to LDS behind the tiles' pieces)
-    int* const els = reinterpret_cast<int*>(smem_aw + 3 * AW_REGB);
+    // (loaded behind the Q pieces, in front of K(0)'s, and written to LDS behind K(0)'s: the wait of that use leaves K(0) in flight)
+    int* const els = reinterpret_cast<int*>(smem_aw + AW_ELS);
     int ek_mine = 0, ev_mine = 0;
     if (HAS_E && tid < n_tiles) {  // (n_tiles <= 7 sources x 32 tiles)
         int si = 0, kt = PART ? tid + t0 : tid;
@@ -282,7 +291,7 @@ __global__ __launch_bounds__(256, 1) void attention_p2w_kernel(AttnP2Params p) {
         if (p.EVt) ev_mine = p.EVt[blk * 4 + head];
     }
     typedef __attribute__((address_space(3))) const p2_u32x2* lds_pair_t;
-    const unsigned els0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem_aw + 3u * AW_REGB;
+    const unsigned els0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem_aw + (unsigned)AW_ELS;
     auto read_e = [&](int tl) __attribute__((always_inline)) {  // {e_k, e_v} of tile tl (every lane the same address)
         return *reinterpret_cast<lds_pair_t>((uintptr_t)(els0 + 8u * (unsigned)min(tl, n_tiles - 1)));
     };
@@ -364,6 +373,11 @@ __global__ __launch_bounds__(256, 1) void attention_p2w_kernel(AttnP2Params p) {
     // ---- prologue: K(0) into the K half of region 2 (the place of "tile -1"), V(0) | K(1) into region 0, V(1) | K(2) into
     // region 1.  Past the last tile a cursor stays where it is: the tile is loaded once more, into a place nobody reads (no
     // branches around the pieces, and the counted wait of the loop always sees the same number of operations).
+    // One queue, in issue order: q's exponent, the 16 Q pieces (above), the tile exponents, K(0) - and, behind the barrier that
+    // the first scores need, V(0) | K(1), V(1) | K(2), one piece every third MFMA of the first scores.  Every workgroup of the
+    // chip starts at the same time and the memory system takes the prologue's burst (37 MB) no faster than the waves can
+    // issue it: with those 16 pieces in front of the first scores, their issue alone held the scores back by about the time
+    // the scores take (measured: profiles/attention_full_lines.log).
     Cur cK = cur_init(), cV = cur_init(), cS = cur_init();
     int nK = 0, nV = 0;  // tiles issued so far
     auto adv_k = [&]() __attribute__((always_inline)) { if (++nK < n_tiles) cur_next(cK); };
@@ -374,47 +388,69 @@ __global__ __launch_bounds__(256, 1) void attention_p2w_kernel(AttnP2Params p) {
         for (int i = 0; i < 4; ++i) k_piece(2, i, so);
         adv_k();
     }
+    unsigned so_v01[2], so_k12[2];  // V(0), V(1) / K(1), K(2): where their pieces will read
 #pragma unroll
     for (int r = 0; r < 2; ++r) {
-        const unsigned sov = v_so(cV), sok = k_so(cK);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) v_piece(r, i, sov);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) k_piece(r, i, sok);
+        so_v01[r] = v_so(cV);
+        so_k12[r] = k_so(cK);
         adv_v();
         adv_k();
     }
     if (HAS_E && tid < n_tiles) { els[2 * tid] = ek_mine; els[2 * tid + 1] = ev_mine; }
-    // one queue, in issue order: exponents, Q fragments, K(0) | V(0), K(1) | V(1), K(2).  The first scores need the first three:
-    // the 16 youngest pieces stay in flight (every workgroup of the chip starts at the same time: the prologue's loads are a
-    // 37 MB burst, its tail lands under the first scores and the first softmax)
-    aw_wait_q(Qf);
-    __syncthreads();
+    // The Q image is the wave's own: its 16 pieces have landed when at most the 4 of K(0) behind them are in flight, no barrier
+    // (the tile exponents' loads are younger too: the wait then asks for more than it needs).  The fragments Qf[a][pl][s] =
+    // row block a of the image at R[s][pl], as K's; asm reads, waited for by aw_wait_q_k0.
+#pragma unroll
+    for (int s = 0; s < 4; ++s)
+#pragma unroll
+        for (int pl = 0; pl < 2; ++pl) R[s][pl] += q_img;
+    asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+    aw_for<0, 16>([&](auto II) __attribute__((always_inline)) {
+        constexpr int a = decltype(II)::value >> 3, pl = (decltype(II)::value >> 2) & 1, s = decltype(II)::value & 3;
+        aw_read_frag<a * 8192>(Qf[a][pl][s], R[s][pl]);
+    });
+    aw_wait_q_k0(Qf);
     p2_u32x2 e_pair = {0u, 0u};  // {e_k, e_v} of the tile whose exponents are needed next (all lanes equal)
     if constexpr (HAS_E) e_pair = read_e(0);
 #pragma unroll
     for (int s = 0; s < 4; ++s)
 #pragma unroll
-        for (int pl = 0; pl < 2; ++pl) R[s][pl] += 2 * AW_REGB;  // region 2
+        for (int pl = 0; pl < 2; ++pl) R[s][pl] += 2 * AW_REGB - q_img;  // region 2
     {
         const float sinv = AW_SINV * p2_exp2i(e_q + __builtin_amdgcn_readfirstlane((int)e_pair[0]));
+        // 16-dim step outside, stream inside: the four K(0) fragments of a step are read once for both streams, a step ahead
+        // (every S element still accumulates s ascending, then product q ascending)
+        p2_f16x8 kf[2][2][2];  // [step parity][key block][plane]
 #pragma unroll
-        for (int a = 0; a < 2; ++a)
+        for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                p2_f16x8 kf[2][2];
+            for (int pl = 0; pl < 2; ++pl) kf[0][kb][pl] = frag(0, pl, AW_TILEB + kb * 8192);
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            if (s < 3) {
 #pragma unroll
                 for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
-                    for (int pl = 0; pl < 2; ++pl) kf[kb][pl] = frag(s, pl, AW_TILEB + kb * 8192);
+                    for (int pl = 0; pl < 2; ++pl) kf[(s + 1) & 1][kb][pl] = frag(s + 1, pl, AW_TILEB + kb * 8192);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int a = 0; a < 2; ++a)
 #pragma unroll
                 for (int q = 0; q < 3; ++q)
 #pragma unroll
                     for (int kb = 0; kb < 2; ++kb) {
-                        if (s == 0 && q == 0) aw_mfma_s0(S[a][kb], kf[kb][PA[q]], Qf[a][PB[q]][s]);
-                        else aw_mfma_s(S[a][kb], kf[kb][PA[q]], Qf[a][PB[q]][s]);
+                        if (s == 0 && q == 0) aw_mfma_s0(S[a][kb], kf[s & 1][kb][PA[q]], Qf[a][PB[q]][s]);
+                        else aw_mfma_s(S[a][kb], kf[s & 1][kb][PA[q]], Qf[a][PB[q]][s]);
+                        const int slot = s * 12 + a * 6 + q * 2 + kb;
+                        if (slot % 3 == 1) {
+                            const int n = slot / 3, r = n >> 3, i = n & 3;  // piece n of 16: V(0) K(1) V(1) K(2), four each
+                            if ((n & 4) == 0) v_piece(r, i, so_v01[r]);
+                            else k_piece(r, i, so_k12[r]);
+                        }
+                        __builtin_amdgcn_sched_barrier(0);
                     }
-            }
+        }
         // K(0) sits where X(0) puts K(3): everybody is through with it before anybody's pieces go out; and
         // V(0) | K(1) have landed, everybody's (8 pieces - V(1) | K(2) - may still be in flight: the barrier of tile 0 waits for them)
         asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)\n\ts_barrier" ::: "memory");
@@ -767,7 +803,7 @@ int launch_attention_p2w(e2emv_ctx* ctx, AttnP2Params& p, int n_valid, hipStream
     p.nq = (n_valid + AW_QT - 1) / AW_QT;
     if (int rc = ensure_flags(ctx)) return rc;
     p.stats = ctx->d_flags + 5;
-    const size_t lds = 3 * AW_REGB + 2048;  // + the tile exponents (<= 7 sources x 32 tiles x 8 bytes)
+    const size_t lds = AW_LDS;  // three regions, the tile exponents (<= 7 sources x 32 tiles x 8 bytes), the Q images of waves 1 .. 3
     const bool multi = p.cross && p.T > 2;
     const void* fn = p.EQK ? (multi ? reinterpret_cast<const void*>(attention_p2w_kernel<true, true>) : reinterpret_cast<const void*>(attention_p2w_kernel<true, false>))
                            : (multi ? reinterpret_cast<const void*>(attention_p2w_kernel<false, true>) : reinterpret_cast<const void*>(attention_p2w_kernel<false, false>));
