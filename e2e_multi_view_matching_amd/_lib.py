@@ -170,6 +170,8 @@ SIGNATURES = {
     "e2emv_get_precision": (c_int, [c_void_p, ctypes.POINTER(c_int)]),
     "e2emv_set_split_min_rows": (c_int, [c_void_p, c_int64]),
     "e2emv_gemm_bf16x3": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "e2emv_gemm_bf16x3_ex": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                     c_void_p]),
     "e2emv_attention_bf16x3": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p,
                                        c_void_p]),
     "e2emv_attention_bf16x3_v": (c_int, [c_void_p, c_int, c_int, c_int, ctypes.POINTER(c_int), c_int, c_int, c_void_p, c_int, c_void_p,

@@ -53,21 +53,25 @@ static int launch_split3(e2emv_ctx* ctx, const float* src, int64_t rows, int C, 
 
 using namespace e2emv;
 
-extern "C" int e2emv_gemm_bf16x3(e2emv_ctx* ctx, int M, int Nout, int K, const float* d_A, const float* d_W,
-                                 const float* d_bias, float* d_C, int flags, void* stream) {
+extern "C" int e2emv_gemm_bf16x3_ex(e2emv_ctx* ctx, int M, int Nout, int K, int K1, const float* d_A, const float* d_A2, const float* d_W,
+                                    const float* d_bias, const float* d_R, float* d_C, int flags, void* stream) {
     if (!ctx || !d_A || !d_W || !d_C) return E2EMV_EINVAL;
     E2EMV_ENTER(ctx, stream);
-    if (M <= 0 || Nout <= 0 || K <= 0 || K % 32 || Nout % 4) return set_err(ctx, E2EMV_ESHAPE, "gemm_bf16x3: M=%d N=%d K=%d", M, Nout, K);
+    if (M <= 0 || Nout <= 0 || K <= 0 || K % 32 || K1 % 32 || K1 <= 0 || K1 > K || (K1 < K && !d_A2) || Nout % 4)
+        return set_err(ctx, E2EMV_ESHAPE, "gemm_bf16x3: M=%d N=%d K=%d K1=%d", M, Nout, K, K1);
     hipStream_t s = (hipStream_t)stream;
     auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
     int rc = ws_reserve(ctx, al((size_t)Nout * 3 * K * 2));
     if (rc) return rc;
     uint16_t* W3 = (uint16_t*)ctx->d_ws;
+    // activations stay fp32, split on the way into LDS (gemm_x3.hip, gemm_h2.hip); [A | A2] are the two K segments, R the residual
+    GemmArgs g;
+    g.M = M; g.N = Nout; g.K = K; g.K1 = K1; g.A = d_A; g.lda = K1; g.bias = d_bias; g.C = d_C; g.ldc = Nout; g.relu = (flags & 1) != 0;
+    if (K1 < K) { g.A2 = d_A2; g.lda2 = K - K1; }
+    if (d_R) { g.R = d_R; g.ldr = Nout; }
     if (flags & 4) {  // f16x2 GEMM (gemm_h2.hip); the weight planes are made on the host as e2emv_commit_weights makes them
         DenseWeights dw;
         if ((rc = dense_from_device(ctx, d_W, d_bias, Nout, K, WF_H2, W3, dw, s))) return rc;
-        GemmArgs g;
-        g.M = M; g.N = Nout; g.K = K; g.K1 = K; g.A = d_A; g.lda = K; g.bias = d_bias; g.C = d_C; g.ldc = Nout; g.relu = (flags & 1) != 0;
         prof_begin(ctx, PS_GEMM, s);
         rc = launch_gemm_h2(ctx, g, dw.wh, K, dw.hs, s);
         prof_end(ctx, s);
@@ -75,13 +79,15 @@ extern "C" int e2emv_gemm_bf16x3(e2emv_ctx* ctx, int M, int Nout, int K, const f
     }
     if (flags & 2) return set_err(ctx, E2EMV_EINVAL, "gemm_bf16x3: flags bit1 (the all-planes first-generation kernel) is retired");
     if ((rc = launch_split3(ctx, d_W, Nout, K, K, W3, K, s))) return rc;
-    // activations stay fp32, split on the way into LDS (gemm_x3.hip)
-    GemmArgs g;
-    g.M = M; g.N = Nout; g.K = K; g.K1 = K; g.A = d_A; g.lda = K; g.bias = d_bias; g.C = d_C; g.ldc = Nout; g.relu = (flags & 1) != 0;
     prof_begin(ctx, PS_GEMM, s);
     rc = launch_gemm_x3(ctx, g, W3, K, s);
     prof_end(ctx, s);
     return rc;
+}
+
+extern "C" int e2emv_gemm_bf16x3(e2emv_ctx* ctx, int M, int Nout, int K, const float* d_A, const float* d_W,
+                                 const float* d_bias, float* d_C, int flags, void* stream) {
+    return e2emv_gemm_bf16x3_ex(ctx, M, Nout, K, K, d_A, nullptr, d_W, d_bias, nullptr, d_C, flags, stream);
 }
 
 // body of e2emv_attention_bf16x3 / e2emv_attention_bf16x3_v: nv = valid keypoints of image t of a tuple, T entries

@@ -109,18 +109,25 @@ def attention(qkv, B, T, n_valid, H, cross):
     return out
 
 
-def gemm_bf16x3(A, W, bias=None, relu=False, f16x2=False):
-    """bf16x3 split-operand GEMM building block on fp32 tensors: act(A W^T + bias).  Default: gemm_x3.hip (activations
-    split on the way into LDS); ``f16x2=True``: the fp16 x 2 form of gemm_x3.hip (two activation planes, three products)."""
+def gemm_bf16x3(A, W, bias=None, relu=False, f16x2=False, A2=None, residual=None):
+    """bf16x3 split-operand GEMM building block on fp32 tensors: act([A | A2] W^T + bias) (+ residual).  Default: gemm_x3.hip
+    (activations split on the way into LDS); ``f16x2=True``: the fp16 x 2 form of gemm_x3.hip (two activation planes, three
+    products)."""
     ctx = _ctx(A)
     A_, W_ = A.contiguous().float(), W.contiguous().float()
-    M, K = A_.shape
-    N = W_.shape[0]
+    A2_ = A2.contiguous().float() if A2 is not None else None
+    M, K1 = A_.shape
+    N, K = W_.shape
     C = torch.empty((M, N), dtype=torch.float32, device=A.device)
     b = bias.contiguous().float() if bias is not None else None
+    R = residual.contiguous().float() if residual is not None else None
+    if R is not None and tuple(R.shape) != (M, N):
+        raise ValueError(f"residual must be [{M},{N}], got {tuple(R.shape)}")
+    if A2_ is not None and tuple(A2_.shape) != (M, K - K1):
+        raise ValueError(f"A2 must be [{M},{K - K1}], got {tuple(A2_.shape)}")
     with torch.cuda.device(A.device):
-        ctx.call("e2emv_gemm_bf16x3", M, N, K, _lib.ptr(A_), _lib.ptr(W_), _lib.ptr(b), _lib.ptr(C), (1 if relu else 0) | (4 if f16x2 else 0),
-                 _lib.stream_ptr(A.device))
+        ctx.call("e2emv_gemm_bf16x3_ex", M, N, K, K1, _lib.ptr(A_), _lib.ptr(A2_), _lib.ptr(W_), _lib.ptr(b), _lib.ptr(R), _lib.ptr(C),
+                 (1 if relu else 0) | (4 if f16x2 else 0), _lib.stream_ptr(A.device))
     return C
 
 

@@ -697,6 +697,11 @@ int e2emv_set_split_min_rows(e2emv_ctx* ctx, int64_t min_rows);
  * first-generation kernel on pre-split activation planes) returns E2EMV_EINVAL. */
 int e2emv_gemm_bf16x3(e2emv_ctx* ctx, int M, int Nout, int K, const float* d_A, const float* d_W, const float* d_bias,
                       float* d_C, int flags, void* stream);
+/* ... as the forward pass runs these kernels, with the argument list of e2emv_gemm_p2: C = act([A | A2] W^T + bias) (+ R);
+ * A [M,K1], A2 [M,K-K1] or NULL (then K1 = K), W [N,K], R [M,N] or NULL; same flags.  e2emv_gemm_bf16x3 is this call with
+ * K1 = K and no A2, no R. */
+int e2emv_gemm_bf16x3_ex(e2emv_ctx* ctx, int M, int Nout, int K, int K1, const float* d_A, const float* d_A2, const float* d_W,
+                         const float* d_bias, const float* d_R, float* d_C, int flags, void* stream);
 /* same contract as e2emv_attention; cross: bit0 = cross layer, bit1 = the forward pass's kernel (fp32 q|k|v in, the
  * planes made inside the kernel) instead of the pre-split building block, bit2 = its f16x2 form. */
 int e2emv_attention_bf16x3(e2emv_ctx* ctx, int B, int T, int n_rows, int n_valid, int D, int H, const float* d_qkv,
