@@ -10,7 +10,8 @@
 //     resolve  one wave per problem: the sequential rule "a model replaces the best only with strictly more inliers than
 //              max(best, 4); each new best shrinks niters" over the round's (iteration, model) order.  A wave prefix-max
 //              over 64 entries at a time finds the few entries that set a new running maximum; only those are walked in
-//              order (an entry of an iteration at or past niters ends the problem's loop)
+//              order (an entry of an iteration at or past niters ends the problem's loop; all models of a running
+//              iteration compete, also where the iteration straddles two 64-entry chunks)
 //   finalize  one workgroup per problem: the inlier mask of the best E, then recoverPose of every candidate
 //              (SVD, four (R, t), DLT triangulation + depth tests) and the candidate with the most points in front
 #include "common.h"
@@ -158,7 +159,11 @@ __global__ void __launch_bounds__(64) ransac_resolve_kernel(RansacParams p, int 
     int best = st[ST_BEST], last_it = st[ST_LAST_IT], run = best, best_k = -1;
     const int* counts = p.counts + (size_t)q * RANSAC_ROUND * 10;
     for (int c = 0; c < RANSAC_ROUND * 10 / 64; ++c) {
-        if (r0 + (c * 64) / 10 >= niters) break;  // (the whole chunk lies past the loop's end)
+        // the whole chunk lies past the loop's end - unless it opens with the rest of the iteration that set the last best:
+        // ten entries per iteration and 64 per chunk leave iterations 6, 12, 19, 25 (mod 32) in two chunks, and a record of
+        // the models before the seam may have shrunk niters to that very iteration, whose other models still compete
+        const int it0 = r0 + (c * 64) / 10;
+        if (it0 >= niters && it0 != last_it) break;
         const int k = c * 64 + lane;
         const int cnt = counts[k];
         int v = cnt;  // inclusive prefix maximum over the wave
