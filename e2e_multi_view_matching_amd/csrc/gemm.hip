@@ -26,10 +26,10 @@
 //    tile) - removes the lockstep load/store bursts of one-tile-per-workgroup launches.
 //  * XCD-aware tile ranges: the tiles in flight on one XCD are neighbours (shared A panels
 //    stay in that XCD's L2).
-#include <algorithm>
 #include <cstdlib>
 
 #include "common.h"
+#include "gemm_walk.h"
 
 namespace e2emv {
 
@@ -60,9 +60,7 @@ struct GemmParams {
     int conv_pool;
 };
 
-// Persistent kernel: gridDim.x = 8 * slots workgroups (2 per CU); workgroup (xcd = id & 7,
-// slot = id >> 3) walks tiles xcd*per_xcd + slot, + slots, ... of its XCD's contiguous tile range,
-// so the tiles in flight on one XCD are neighbours (shared A panels stay in that L2).  The K
+// Persistent kernel: the workgroup walks the tiles of a GemmWalk (gemm_walk.h).  The K
 // tiles of consecutive output tiles form ONE software-pipelined stream: the first K tile of
 // the next output tile is prefetched under the last MFMAs of the current one and the
 // epilogue's stores drain under the next tile's MFMAs - no lockstep load/store bursts.
@@ -84,13 +82,10 @@ __global__ __launch_bounds__(256, TN == 1 ? 2 : 3) void gemm_nt_kernel(GemmParam
     float* As = smem;                       // [BM][BK + 4]  activations
     float* Bs = smem + BM * (BK + 4);       // [BN][BK + 4]  weights
 
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, slots = gridDim.x >> 3;
-    const int per_xcd = (p.total + 7) / 8;
-    const int t_begin = xcd * per_xcd;
-    const int t_end = min(t_begin + per_xcd, p.total);
-    int tile = t_begin + slot;
-    if (tile >= t_end) return;
-    const int tiles_mn = p.tiles_m * p.tiles_n;
+    const GemmWalk walk(p.total, blockIdx.x, gridDim.x);
+    if (walk.empty()) return;
+    int tile = walk.tile;
+    const int t_end = walk.t_end, slots = walk.slots;
 
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = tid >> 6;
@@ -106,8 +101,7 @@ __global__ __launch_bounds__(256, TN == 1 ? 2 : 3) void gemm_nt_kernel(GemmParam
     const float* w_ptr[NCHB];
     int cyx[CONV ? NCH : 1];  // CONV: pixel coordinates (y << 16 | x) of this thread's A rows
     auto setup = [&](int t) {
-        const int z = t / tiles_mn, r = t - z * tiles_mn;
-        const int tm = r / p.tiles_n, tn = r - tm * p.tiles_n;
+        const auto [z, tm, tn] = gemm_tile(t, p.tiles_m, p.tiles_n);
         const float* A = p.A + z * p.sA;
         const float* A2 = p.A2 ? p.A2 + z * p.sA2 : nullptr;
         const float* W = p.W + z * p.sW;
@@ -203,8 +197,7 @@ __global__ __launch_bounds__(256, TN == 1 ? 2 : 3) void gemm_nt_kernel(GemmParam
         }
     };
     auto epilogue = [&](int t) {
-        const int z = t / tiles_mn, r = t - z * tiles_mn;
-        const int tm = r / p.tiles_n, tn = r - tm * p.tiles_n;
+        const auto [z, tm, tn] = gemm_tile(t, p.tiles_m, p.tiles_n);
         float* C = p.C ? p.C + z * p.sC : nullptr;
         const float* R = p.R ? p.R + z * p.sR : nullptr;
 #pragma unroll
@@ -289,11 +282,23 @@ __global__ __launch_bounds__(256, TN == 1 ? 2 : 3) void gemm_nt_kernel(GemmParam
     }
 }
 
+// ---- the operand checks the launchers of the GEMM family share (gemm_walk.h) ----
+int gemm_k_segments(e2emv_ctx* ctx, const char* who, int K, int K1, bool has_A2, int* K1_out) {
+    *K1_out = K1 = has_A2 ? K1 : K;
+    if (K % 32 || K1 % 32 || K1 > K) return set_err(ctx, E2EMV_ESHAPE, "%s: K=%d K1=%d must be multiples of 32", who, K, K1);
+    return E2EMV_OK;
+}
+int gemm_rows16(e2emv_ctx* ctx, const char* who, const GemmArgs& a, const void* W, int64_t ldw, const char* ldw_name) {
+    if (!W || !a.C || a.N % 4 || a.ldc % 4 || (uintptr_t)a.C % 16 || (a.bias && (uintptr_t)a.bias % 16) ||
+        (a.R && (a.ldr % 4 || (uintptr_t)a.R % 16)) || a.lda % 4 || (a.A2 && a.lda2 % 4) || ldw % 8 || a.scale != 1.f)
+        return set_err(ctx, E2EMV_ESHAPE, "%s: needs 16-byte aligned rows (N %% 4, ld %% 4, %s %% 8) and scale 1", who, ldw_name);
+    return E2EMV_OK;
+}
+
 int launch_gemm_nt(e2emv_ctx* ctx, const GemmArgs& a, hipStream_t s) {
     if (a.M <= 0 || a.N <= 0 || a.K <= 0 || a.batch <= 0) return set_err(ctx, E2EMV_ESHAPE, "gemm: empty problem");
-    const int K1 = a.A2 ? a.K1 : a.K;
-    if (a.K % 32 || K1 % 32 || K1 > a.K || (K1 < a.K && !a.A2))
-        return set_err(ctx, E2EMV_ESHAPE, "gemm: K=%d K1=%d must be multiples of 32", a.K, K1);
+    int K1;
+    if (int rc = gemm_k_segments(ctx, "gemm", a.K, a.K1, a.A2 != nullptr, &K1)) return rc;
     GemmParams p;
     p.A = a.A; p.A2 = a.A2; p.W = a.W; p.bias = a.bias; p.R = a.R; p.C = a.C;
     if (!a.C) return set_err(ctx, E2EMV_EINVAL, "gemm: no output");
@@ -325,12 +330,10 @@ int launch_gemm_nt(e2emv_ctx* ctx, const GemmArgs& a, hipStream_t s) {
     // the pool lives in the 16-byte epilogue only: the scalar epilogue would write all M unpooled rows into an M/4-row output
     if (a.conv_pool && !p.vec_store)
         return set_err(ctx, E2EMV_ESHAPE, "gemm: fused 2x2 max-pool needs 16-byte aligned output and bias and ldc %% 4 == 0");
-    const int per_xcd = (p.total + 7) / 8;
-    // K tile: 32.  A 64-deep tile (half the barrier / staging episodes per MFMA, 2 workgroups per CU) was measured
+    // K tile: 32. A 64-deep tile (half the barrier / staging episodes per MFMA, 2 workgroups per CU) was measured
     // 1-5 % SLOWER at every shape; so were 1 or 2 workgroups per CU and s_setprio around the MFMA block: the main
     // loop sits at ~125 TFLOP/s (MFMA pipe ~82 % busy at ~2.3 GHz) whatever the schedule.
-    const int per_cu = narrow ? 2 : 3;
-    const int sl = std::min(per_xcd, std::max(1, ctx->num_cus * per_cu / 8));
+    const int sl = gemm_slots(p.total, ctx->num_cus, narrow ? 2 : 3);
     const size_t lds = sizeof(float) * (bm + bn) * (BK + 4);
     if (small) {
         hipLaunchKernelGGL((gemm_nt_kernel<false, 0>), dim3(8 * sl), dim3(256), lds, s, p);

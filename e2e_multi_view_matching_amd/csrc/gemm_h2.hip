@@ -22,11 +22,11 @@
 //     stored while the MFMAs of step k run; global prefetch distance of two K tiles in registers;
 //   * one workgroup per CU (2 waves per SIMD), persistent over an XCD-contiguous range of tiles ordered N-fastest, so
 //     the column tiles that share an A row block run back to back on one XCD's L2.
-#include <algorithm>
 #include <cstdlib>
 #include <type_traits>
 
 #include "common.h"
+#include "gemm_walk.h"
 
 namespace e2emv {
 
@@ -63,12 +63,10 @@ __global__ __launch_bounds__(512, 1) void gemm_h2_kernel(GemmH2Params p) {
     constexpr bool DB = NJ == 2;   // LDS double-buffered
     constexpr int WR = H2_BN / 128;  // weight rows per thread and plane
 
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, slots = gridDim.x >> 3;
-    const int per_xcd = (p.total + 7) / 8;
-    const int t_begin = xcd * per_xcd;
-    const int t_end = min(t_begin + per_xcd, p.total);
-    int tile = t_begin + slot;
-    if (tile >= t_end) return;
+    const GemmWalk walk(p.total, blockIdx.x, gridDim.x);
+    if (walk.empty()) return;
+    int tile = walk.tile;
+    const int t_end = walk.t_end, slots = walk.slots;
 
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = tid >> 6;
@@ -85,7 +83,7 @@ __global__ __launch_bounds__(512, 1) void gemm_h2_kernel(GemmH2Params p) {
     // which runs two K steps ahead of the compute position across tiles
     unsigned a_off[4], a2_off[4], w_off[WR];
     auto setup = [&](int t) {
-        const int tm = t / p.tiles_n, tn = t - tm * p.tiles_n;
+        const auto [tm, tn] = gemm_tile(t, p.tiles_n);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const unsigned ra = (unsigned)min(tm * H2_BM + a_row + 64 * i, p.M - 1);
@@ -216,7 +214,7 @@ __global__ __launch_bounds__(512, 1) void gemm_h2_kernel(GemmH2Params p) {
     constexpr int RPI = 64 / LPR;                  // rows per store instruction
     auto epilogue = [&](int t, int free_buf) {
         float* slab = reinterpret_cast<float*>(smem_h2 + (DB ? free_buf * H2_BUF : H2_BUF)) + wave * 32 * SLD;
-        const int tm = t / p.tiles_n, tn = t - tm * p.tiles_n;
+        const auto [tm, tn] = gemm_tile(t, p.tiles_n);
         const int o_row = lane / LPR, o_col = (lane % LPR) * 4;
 #pragma unroll
         for (int i = 0; i < 2; ++i)
@@ -299,11 +297,9 @@ __global__ __launch_bounds__(512, 1) void gemm_h2_kernel(GemmH2Params p) {
 
 int launch_gemm_h2(e2emv_ctx* ctx, const GemmArgs& a, const uint16_t* WH, int64_t ldw, float out_scale, hipStream_t s) {
     if (a.M <= 0 || a.N <= 0 || a.K <= 0 || a.batch != 1) return set_err(ctx, E2EMV_ESHAPE, "gemm_h2: empty problem or batch != 1");
-    const int K1 = a.A2 ? a.K1 : a.K;
-    if (a.K % 32 || K1 % 32 || K1 > a.K || (K1 < a.K && !a.A2)) return set_err(ctx, E2EMV_ESHAPE, "gemm_h2: K=%d K1=%d must be multiples of 32", a.K, K1);
-    if (!WH || !a.C || a.N % 4 || a.ldc % 4 || (uintptr_t)a.C % 16 || (a.bias && (uintptr_t)a.bias % 16) ||
-        (a.R && (a.ldr % 4 || (uintptr_t)a.R % 16)) || a.lda % 4 || (a.A2 && a.lda2 % 4) || ldw % 8 || a.scale != 1.f)
-        return set_err(ctx, E2EMV_ESHAPE, "gemm_h2: needs 16-byte aligned rows (N %% 4, ld %% 4, ldw %% 8) and scale 1");
+    int K1;
+    if (int rc = gemm_k_segments(ctx, "gemm_h2", a.K, a.K1, a.A2 != nullptr, &K1)) return rc;
+    if (int rc = gemm_rows16(ctx, "gemm_h2", a, WH, ldw, "ldw")) return rc;
     if ((int64_t)a.M * a.lda >= (int64_t)1 << 30 || (a.A2 && (int64_t)a.M * a.lda2 >= (int64_t)1 << 30) || (int64_t)a.N * 2 * ldw >= (int64_t)1 << 31)
         return set_err(ctx, E2EMV_ESHAPE, "gemm_h2: operand larger than 4 GB (M=%d lda=%lld): 32-bit byte offsets", a.M, (long long)a.lda);
     GemmH2Params p;
@@ -318,8 +314,7 @@ int launch_gemm_h2(e2emv_ctx* ctx, const GemmArgs& a, const uint16_t* WH, int64_
     p.total = tiles_m * p.tiles_n;
     p.relu = a.relu ? 1 : 0;
     p.out_scale = out_scale;
-    const int per_xcd = (p.total + 7) / 8;
-    const int sl = std::min(per_xcd, std::max(1, ctx->num_cus / 8));
+    const int sl = gemm_slots(p.total, ctx->num_cus, 1);
     // NJ = 2: two tile buffers (the idle one carries the epilogue slabs); NJ = 4: one tile buffer + 8 slabs of 32 x 68 floats
     const size_t lds = nj == 2 ? sizeof(uint16_t) * 2 * (2 * H2_APLANE + 2 * bn * H2_LD)
                                : sizeof(uint16_t) * (2 * H2_APLANE + 2 * bn * H2_LD) + sizeof(float) * 8 * 32 * 68;

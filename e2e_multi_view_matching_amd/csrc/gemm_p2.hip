@@ -13,11 +13,11 @@
 // back from its planes (22 bits) in the same layout.  Output kinds: fp32, scaled planes (the next GEMM's operand), or
 // the attention operands q | k (plain planes, q pre-scaled) + V^T (transposed plain planes, keys in the order of the
 // transposed-score registers) - attention_p2.hip then never touches an fp32 q|k|v matrix.
-#include <algorithm>
 #include <cstdlib>
 #include <type_traits>
 
 #include "gemm_p2_core.h"
+#include "gemm_walk.h"
 
 namespace e2emv {
 
@@ -25,12 +25,10 @@ template <int OUT, bool HAS_R = false>
 __global__ __launch_bounds__(512, 1) void gemm_p2_kernel(GemmP2Params p) {
     extern __shared__ __attribute__((aligned(16))) char smem_p2[];
 
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, slots = gridDim.x >> 3;
-    const int per_xcd = (p.total + 7) / 8;
-    const int t_begin = xcd * per_xcd;
-    const int t_end = min(t_begin + per_xcd, p.total);
-    int tile = t_begin + slot;
-    if (tile >= t_end) return;
+    const GemmWalk walk(p.total, blockIdx.x, gridDim.x);
+    if (walk.empty()) return;
+    int tile = walk.tile;
+    const int t_end = walk.t_end, slots = walk.slots;
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -46,7 +44,7 @@ __global__ __launch_bounds__(512, 1) void gemm_p2_kernel(GemmP2Params p) {
     const int ld_r = lane >> 3, ld_p = lane & 7;
     unsigned a_vo[4], a2_vo[4], w_vo[4];
     auto setup = [&](int t) {
-        const int tm = t / p.tiles_n, tn = t - tm * p.tiles_n;
+        const auto [tm, tn] = gemm_tile(t, p.tiles_n);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int row = 32 * wave + 8 * i + ld_r;
@@ -122,7 +120,7 @@ __global__ __launch_bounds__(512, 1) void gemm_p2_kernel(GemmP2Params p) {
     auto fetch_e = [&](int t) {
         int v = 0;
         if (has_e) {
-            const int tm_ = t / p.tiles_n, tn_ = t - tm_ * p.tiles_n;
+            const auto [tm_, tn_] = gemm_tile(t, p.tiles_n);
             const int erow = tm_ * 4 + wr;
             const int nb1 = nk1 >> 1, nb = (nk + 1) >> 1;
             if (erow * 64 < p.M) {
@@ -199,6 +197,7 @@ __global__ __launch_bounds__(512, 1) void gemm_p2_kernel(GemmP2Params p) {
         cur_kt = 0;
         if (has_e && nk < 4 && tile + slots < t_end) ev_next = fetch_e(tile + slots);
         gp_acc_fence(acc);
+        // (gemm_tile's decode, written out: through the header every instance of this kernel got another instruction stream)
         gp_epilogue<OUT, HAS_R>(p, smem_p2, acc, wave, tile / p.tiles_n, tile % p.tiles_n, e_run, ev);
         ev = ev_next;
         since = overlap ? 0 : 8;
@@ -210,9 +209,9 @@ __global__ __launch_bounds__(512, 1) void gemm_p2_kernel(GemmP2Params p) {
 // validates one GEMM and fills its kernel parameter block (shared with the chained launch, gemm_p2c.hip)
 int fill_gemm_p2_params(e2emv_ctx* ctx, const GemmP2Args& a, GemmP2Params& p) {
     if (a.M <= 0 || a.N <= 0 || a.K <= 0) return set_err(ctx, E2EMV_ESHAPE, "gemm_p2: empty problem");
-    const int K1 = a.A2 ? a.K1 : a.K;
-    if (a.K % 32 || K1 % 32 || K1 <= 0 || K1 > a.K || (K1 < a.K && !a.A2))
-        return set_err(ctx, E2EMV_ESHAPE, "gemm_p2: K=%d K1=%d must be multiples of 32", a.K, K1);
+    int K1;
+    if (int rc = gemm_k_segments(ctx, "gemm_p2", a.K, a.K1, a.A2 != nullptr, &K1)) return rc;
+    if (K1 <= 0) return set_err(ctx, E2EMV_ESHAPE, "gemm_p2: K=%d K1=%d must be multiples of 32", a.K, K1);  // the planes' first segment is never empty
     if (!a.A || !a.W || a.lda % 32 || a.lda < K1 || (a.A2 && (a.lda2 % 32 || a.lda2 < a.K - K1)))
         return set_err(ctx, E2EMV_ESHAPE, "gemm_p2: operand planes need whole 32-column blocks (lda=%lld lda2=%lld)", (long long)a.lda, (long long)a.lda2);
     if ((uintptr_t)a.A % 16 || (a.A2 && (uintptr_t)a.A2 % 16) || (uintptr_t)a.W % 16 || (a.bias && (uintptr_t)a.bias % 16) || (a.Rp && (uintptr_t)a.Rp % 16))
@@ -275,8 +274,7 @@ int launch_gemm_p2(e2emv_ctx* ctx, const GemmP2Args& a, hipStream_t s) {
         case P2_OUT_PLANES: fn = a.Rp ? reinterpret_cast<const void*>(gemm_p2_kernel<P2_OUT_PLANES, true>) : reinterpret_cast<const void*>(gemm_p2_kernel<P2_OUT_PLANES, false>); break;
         default: fn = reinterpret_cast<const void*>(gemm_p2_kernel<P2_OUT_QKV, false>); break;
     }
-    const int per_xcd = (p.total + 7) / 8;
-    const int sl = std::min(per_xcd, std::max(1, ctx->num_cus / 8));
+    const int sl = gemm_slots(p.total, ctx->num_cus, 1);
     const size_t lds = P2_LDSB;
     if (int rc = ensure_dynamic_lds(ctx, fn, lds)) return rc;
     void* args[] = {&p};

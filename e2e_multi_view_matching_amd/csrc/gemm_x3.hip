@@ -13,10 +13,10 @@
 //  * a product is the 6 largest of the 9 plane products (dropped terms <= 2^-25 |ab|), each exact in fp32, accumulated
 //    in fp32 by v_mfma_f32_32x32x16_bf16: 48 MFMAs x 32 cycles per wave and K tile against 64 x 64 cycles for fp32.
 // LDS rows are 40 bf16 (80 B): 16 rows x 16 B of a ds_read_b128 fall in 16 distinct 16-byte bank groups.
-#include <algorithm>
 #include <cstdlib>
 
 #include "common.h"
+#include "gemm_walk.h"
 
 namespace e2emv {
 
@@ -47,12 +47,10 @@ __global__ __launch_bounds__(256, 2) void gemm_x3_kernel(GemmX3Params p) {
     uint16_t* As = smem3;                 // [3][128][40] activations (planes)
     uint16_t* Bs = smem3 + 3 * X3_PLANE;  // [3][128][40] weights
 
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, slots = gridDim.x >> 3;
-    const int per_xcd = (p.total + 7) / 8;
-    const int t_begin = xcd * per_xcd;
-    const int t_end = min(t_begin + per_xcd, p.total);
-    int tile = t_begin + slot;
-    if (tile >= t_end) return;
+    const GemmWalk walk(p.total, blockIdx.x, gridDim.x);
+    if (walk.empty()) return;
+    int tile = walk.tile;
+    const int t_end = walk.t_end, slots = walk.slots;
 
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = tid >> 6;
@@ -68,7 +66,7 @@ __global__ __launch_bounds__(256, 2) void gemm_x3_kernel(GemmX3Params p) {
     const float* a2_ptr[4];
     const uint16_t* w_ptr[6];
     auto setup = [&](int t) {
-        const int tm = t / p.tiles_n, tn = t - tm * p.tiles_n;
+        const auto [tm, tn] = gemm_tile(t, p.tiles_n);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int ra = min(tm * X3_BM + a_row + 32 * i, p.M - 1);
@@ -152,7 +150,7 @@ __global__ __launch_bounds__(256, 2) void gemm_x3_kernel(GemmX3Params p) {
         }
     };
     auto epilogue = [&](int t) {
-        const int tm = t / p.tiles_n, tn = t - tm * p.tiles_n;
+        const auto [tm, tn] = gemm_tile(t, p.tiles_n);
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             const int m = tm * X3_BM + wr * 64 + i * 32 + l31;
@@ -207,11 +205,9 @@ __global__ __launch_bounds__(256, 2) void gemm_x3_kernel(GemmX3Params p) {
 
 int launch_gemm_x3(e2emv_ctx* ctx, const GemmArgs& a, const uint16_t* W3, int64_t ldw3, hipStream_t s) {
     if (a.M <= 0 || a.N <= 0 || a.K <= 0 || a.batch != 1) return set_err(ctx, E2EMV_ESHAPE, "gemm_x3: empty problem or batch != 1");
-    const int K1 = a.A2 ? a.K1 : a.K;
-    if (a.K % 32 || K1 % 32 || K1 > a.K || (K1 < a.K && !a.A2)) return set_err(ctx, E2EMV_ESHAPE, "gemm_x3: K=%d K1=%d must be multiples of 32", a.K, K1);
-    if (!W3 || !a.C || a.N % 4 || a.ldc % 4 || (uintptr_t)a.C % 16 || (a.bias && (uintptr_t)a.bias % 16) ||
-        (a.R && (a.ldr % 4 || (uintptr_t)a.R % 16)) || a.lda % 4 || (a.A2 && a.lda2 % 4) || ldw3 % 8 || a.scale != 1.f)
-        return set_err(ctx, E2EMV_ESHAPE, "gemm_x3: needs 16-byte aligned rows (N %% 4, ld %% 4, ldw3 %% 8) and scale 1");
+    int K1;
+    if (int rc = gemm_k_segments(ctx, "gemm_x3", a.K, a.K1, a.A2 != nullptr, &K1)) return rc;
+    if (int rc = gemm_rows16(ctx, "gemm_x3", a, W3, ldw3, "ldw3")) return rc;
     GemmX3Params p;
     p.A = a.A; p.A2 = a.A2; p.W3 = W3; p.bias = a.bias; p.R = a.R; p.C = a.C;
     p.lda = a.lda; p.lda2 = a.lda2; p.ldw3 = ldw3; p.ldr = a.ldr; p.ldc = a.ldc;
@@ -220,8 +216,7 @@ int launch_gemm_x3(e2emv_ctx* ctx, const GemmArgs& a, const uint16_t* W3, int64_
     p.tiles_n = (a.N + X3_BN - 1) / X3_BN;
     p.total = p.tiles_m * p.tiles_n;
     p.relu = a.relu ? 1 : 0;
-    const int per_xcd = (p.total + 7) / 8;
-    const int sl = std::min(per_xcd, std::max(1, ctx->num_cus * 2 / 8));
+    const int sl = gemm_slots(p.total, ctx->num_cus, 2);
     const size_t lds = sizeof(uint16_t) * 6 * X3_PLANE;
     hipLaunchKernelGGL(gemm_x3_kernel, dim3(8 * sl), dim3(256), lds, s, p);
     E2EMV_CHECK_LAUNCH(ctx, "gemm_x3_kernel");

@@ -1,5 +1,6 @@
-"""The persistent tile walk of the layer GEMMs restated in plain Python (helper of tests/test_gemm_walk_plan.py and
-tests/test_gpu_gemm_walk.py; no test lives here).
+"""The persistent tile walk of the layer GEMMs restated in plain Python (helper of tests/test_gemm_walk_plan.py, tests/test_gemm_walk.py
+and tests/test_gpu_gemm_walk.py; no test lives here).  The library states the rule once, in csrc/gemm_walk.h (GemmWalk, gemm_slots,
+gemm_tile); this file stays independent of it, and tests/test_gemm_walk.py holds the header to it on the host.
 
 Every dense GEMM kernel (gemm_nt_kernel, gemm_x3_kernel, gemm_h2_kernel<2|4>, gemm_p2_kernel<...>) is launched by the same rule,
     per_xcd = ceil(total / 8),   slots = min(per_xcd, max(1, num_cus * wg_per_cu / 8)),   grid = 8 * slots workgroups,
